@@ -9,14 +9,17 @@ blackbox_ode RK4" per GPU; N GPUs run N such shards (config[3]: 8 x 1024 = 8192)
 the strong-scaling figure (the same global batch on one GPU / the data-parallel step) and the collective's own time.
 Inputs are generated on the host from a seed and are resident in HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (a fresh
 `python -m torch.distributed.run` child, before this process touches a GPU) and exits with the child's status; launched under
 torch.distributed.run it is one rank per GPU over RCCL.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then the K-step block (barrier + synchronize on both sides, MAX over ranks) is repeated R >= 25 times and
-`ms_per_step` is the MEDIAN block / K (K = 20 steps is 1.3 ms: one sample of that says little).  `roofline` is for the dominant
+Timing: a pre-warm, W warm-up steps, then exactly K timed steps in one block (barrier + synchronize on both sides, MAX over ranks);
+`ms_per_step` is that block / K.  The timed steps start from the initial parameters and optimiser state, so what they compute
+depends on the arguments alone: --dump-outputs DIR writes what the last timed step handed its caller (rank 0) as DIR/loss.npy (-ELBO
+summed over the global batch), DIR/grads.npy (the flat gradient) and DIR/params.npy (the flat parameters after Adam), float32, 1.2 MB
+in all.  The side legs below time blocks of a fixed size, independent of K.  `roofline` is for the dominant
 kernel of the step on ONE clock: the dispatch's own begin -> end device timestamps (hipExtLaunchKernelGGL start / stop events
 through slode_profile_enable), the quantity rocprofv3 --kernel-trace reports (profiles/).  `other_configs` runs the remaining
 BASELINE configs the same way; `run_batch` is the reference's whole minibatch (main + auxiliary SVI step, two Adam passes,
@@ -39,14 +42,15 @@ sys.path.insert(0, ROOT)
 B_PER_GPU, T, Z_SPLIT = 1024, 200, (3, 3, 2)
 PEAK_FP32 = 157.3                               # TFLOP/s, fp32 vector == fp32 MFMA peak (MI355X_MICROARCH.md)
 PEAK_HBM = 8000.0                               # GB/s
+SIDE_K = 50                                     # steps per timed block of every side leg: their cost does not grow with --steps
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the metric step; ms_per_step is their time / K")
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=25, help="timed K-step blocks; ms_per_step is their median / K")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write loss / grads / params of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-run-batch", action="store_true", help="skip the run_batch (main + auxiliary step) block: profiling runs of the metric step alone")
@@ -54,6 +58,8 @@ def parse_args():
     ap.add_argument("--grad-mode", choices=["exact", "reference_adjoint"], default="exact",
                     help="exact: gradient of the discrete scheme (adjoint_solver=False); reference_adjoint: torchdiffeq.odeint_adjoint's")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.ab:
         a.no_cpu_baseline = a.no_other_configs = a.no_run_batch = True
     return a
@@ -201,9 +207,8 @@ def other_config_line(name, fam, gauss, B, T_, kw, shape, dev, grad_mode_ra=True
     step = lambda: svi.step_async(obs_d, eps=eps_d, u=u_d)
     sync = lambda: torch.cuda.synchronize(dev)
     prewarm(step, sync, blocks=12, n=30)
-    K = 50
-    blocks = timed_blocks(step, sync, K, 9, 1, dev)
-    ms = 1e3 * statistics.median(blocks) / K
+    blocks = timed_blocks(step, sync, SIDE_K, 9, 1, dev)
+    ms = 1e3 * statistics.median(blocks) / SIDE_K
     kern = kernel_clocks(b.engine, [step], n=20)
     dom, fl, ach = roofline_of(kern, shape, B)
     step_fl = 3 * sum(flops_fwd(shape).values()) * B
@@ -262,12 +267,20 @@ def main():
         torch.cuda.synchronize(dev)
 
     step = lambda: svi.step_async(obs_d, eps=eps_d, u=u_d)
+    # the pre-warm runs until the step time settles, a varying number of Adam steps: the timed steps start from the state before it
+    state0, t0_adam = [t.clone() for t in (flat, opt.exp_avg, opt.exp_avg_sq)], opt.t
     prewarm(step, sync)
     for _ in range(args.warmup):
         step()
-    R = max(1, args.repeats)
-    blocks = timed_blocks(step, sync, args.steps, R, world, dev)
-    dt = statistics.median(blocks)
+    for t, t0 in zip((flat, opt.exp_avg, opt.exp_avg_sq), state0):
+        t.copy_(t0)
+    opt.t = t0_adam
+    dt = timed_blocks(step, sync, args.steps, 1, world, dev)[0]
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("loss", svi.loss), ("grads", svi.grads), ("params", flat)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
     final_loss = float(svi.loss.item())
     ms_per_step = 1e3 * dt / args.steps
     value = world * B_PER_GPU * args.steps / dt
@@ -340,9 +353,7 @@ def main():
         "n_gpus": world, "nranks": world,
         "backend": ("gloo (rehearsal)" if rehearse else "nccl (RCCL over xGMI)") if world > 1 else "none (single process)",
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "timing": {"repeats": R, "statistic": "median of R blocks of K steps, each block barrier+synchronize bracketed, max over ranks",
-                   "ms_per_step_min": 1e3 * min(blocks) / args.steps, "ms_per_step_max": 1e3 * max(blocks) / args.steps,
-                   "ms_per_step_first_block": 1e3 * blocks[0] / args.steps},
+        "timing": {"statistic": "one block of K steps, barrier+synchronize bracketed, max over ranks"},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         **({"rehearsal": "all ranks on cuda:0 over gloo: NOT a measurement"} if rehearse else {}),
         "config": {"workload": "BASELINE config[1]: synthetic CVS, B=1024/GPU, T=200, C=3, latent_dim=8 (3,3,2), S=5, "
@@ -390,7 +401,7 @@ def main():
         svi2 = ELBOStep(b2.engine, b2.flat, FlatAdam(b2.engine, b2.flat, lr=cfg2.learning_rate))
         step2 = lambda: svi2.step_async(obs2, eps=eps2, u=u2)
         prewarm(step2, sync, blocks=12, n=50)
-        ms2 = 1e3 * statistics.median(timed_blocks(step2, sync, args.steps, 9, 1, dev)) / args.steps
+        ms2 = 1e3 * statistics.median(timed_blocks(step2, sync, SIDE_K, 9, 1, dev)) / SIDE_K
         out["value_" + other_mode] = B_PER_GPU / (ms2 * 1e-3)
         out["ms_per_step_" + other_mode] = ms2
         out["value_" + args.grad_mode] = value
@@ -401,7 +412,7 @@ def main():
         aux_step = lambda: aux.step_async(obs_d, eps=eps_d, **labels_d)
         both = lambda: (step(), aux_step())
         prewarm(aux_step, sync, blocks=12, n=30)
-        K = max(args.steps, 50)
+        K = SIDE_K
         t_main = 1e3 * statistics.median(timed_blocks(step, sync, K, 9, 1, dev)) / K
         t_aux = 1e3 * statistics.median(timed_blocks(aux_step, sync, K, 9, 1, dev)) / K
         t_both = 1e3 * statistics.median(timed_blocks(both, sync, K, 9, 1, dev)) / K
@@ -482,7 +493,7 @@ def main():
             step1 = lambda: one.step_async(obs1, eps=eps1, u=u1)
             lsync = lambda: torch.cuda.synchronize(dev)
             prewarm(step1, lsync, blocks=12, n=30)
-            K1 = max(20, min(args.steps, 200))
+            K1 = SIDE_K
             ms_one = 1e3 * statistics.median(timed_blocks(step1, lsync, K1, 9, 1, dev)) / K1
             out["strong_scaling"] = {"global_batch": world * B_PER_GPU, "one_gpu_ms_per_step": ms_one, "n_gpu_ms_per_step": ms_per_step,
                                      "strong_speedup": ms_one / ms_per_step,

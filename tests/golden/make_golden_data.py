@@ -10,9 +10,22 @@ data.challenge.challenge_data.build_datasets -- with two accommodations recorded
   * the .pkl files are numpy pickles (opcodes inspected, numpy reconstruct only); torch >= 2.6 refuses them under its
     default weights_only=True, so torch.load is called with weights_only=False for these three files.
 The .npz holds DATA only: split ids, sizes, scales, time grids, the first samples of every split and float64 checksums.
+
+Two further fixtures let the data tests run without the reference tree:
+  * g6_data_files.npz: the shipped data files the readers open, for tests/test_data_cpu.py to lay out in a temporary directory.
+    Every file but cvs/processed_data.pkl is stored byte for byte (one xz stream of the files end to end: "files.xz", with
+    "files.names" and "files.sizes").  Of the CVS observations (1000 series, 3 MB of float64) only the rows the tests read are
+    stored -- the first three and the last series of the train, val and test splits -- with their row numbers and the arrays'
+    shapes; the test writes processed_data.pkl back with NaN in every other row;
+  * g7_import_lines.json: per reference entry point, the sha256 of its first-party import lines joined by newlines
+    (tests/test_import_dropin_cpu.py); a digest, so no line of the reference is stored.
 Usage: python tests/golden/make_golden_data.py
 """
+import ast
 import functools
+import hashlib
+import json
+import lzma
 import os
 import sys
 import types
@@ -22,7 +35,49 @@ import numpy as np
 import torch
 
 REF = "/root/reference"
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "g5_data.npz")
+HERE = os.path.dirname(os.path.abspath(__file__))
+OUT = os.path.join(HERE, "g5_data.npz")
+DATA_FILES = ["cvs/data_norm_params.pkl", "cvs/processed_data.pkl", "cvs/train_params_data.pkl", "cvs/test_params_data.pkl",
+              "challenge/data.pkl"] + ["proc/" + f for f in ("proc140916.csv", "proc140930.csv", "proc141006.csv", "proc141021.csv",
+                                                             "proc141023.csv", "proc141028.csv")]
+ENTRY_POINTS = ["training_challenge.py", "training_cvs.py", "training_proc.py"]
+
+
+def write_data_files():
+    names = [f for f in DATA_FILES if f != "cvs/processed_data.pkl"]
+    blobs = []
+    for f in names:
+        with open(os.path.join(REF, "data", f), "rb") as fh:
+            blobs.append(fh.read())
+    out = {"files.xz": np.frombuffer(lzma.compress(b"".join(blobs), preset=9 | lzma.PRESET_EXTREME), dtype=np.uint8),
+           "files.names": np.array(names), "files.sizes": np.array([len(b) for b in blobs], dtype=np.int64)}
+    obs = torch.load(os.path.join(REF, "data", "cvs", "processed_data.pkl"), weights_only=False)
+    buffer = int(round(obs["train"].shape[0] * 0.9))                 # train | val boundary of the CVS reader (first 90 % / rest)
+    ends = {"train": [(0, buffer), (buffer, obs["train"].shape[0])], "test": [(0, obs["test"].shape[0])]}
+    for split, spans in ends.items():
+        rows = sorted({r for a, b in spans for r in (a, a + 1, a + 2, b - 1)})
+        out["cvs.%s.shape" % split] = np.array(obs[split].shape)
+        out["cvs.%s.rows" % split] = np.array(rows)
+        out["cvs.%s.obs" % split] = obs[split][rows]
+    path = os.path.join(HERE, "g6_data_files.npz")
+    np.savez(path, **out)
+    print("wrote", path, "%d bytes" % os.path.getsize(path))
+
+
+def write_import_lines():
+    digests = {}
+    for script in ENTRY_POINTS:
+        lines = []
+        with open(os.path.join(REF, script)) as fh:
+            for node in ast.parse(fh.read()).body:
+                if isinstance(node, ast.ImportFrom) and node.module.split(".")[0] in ("models", "utils", "data"):
+                    lines.append("from %s import %s" % (node.module, ", ".join(a.name for a in node.names)))
+        digests[script] = hashlib.sha256("\n".join(lines).encode()).hexdigest()
+    path = os.path.join(HERE, "g7_import_lines.json")
+    with open(path, "w") as fh:
+        json.dump(digests, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote", path)
 
 
 class NS(types.SimpleNamespace):
@@ -122,3 +177,5 @@ def main():
 
 if __name__ == "__main__":
     main()
+    write_data_files()
+    write_import_lines()

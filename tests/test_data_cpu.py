@@ -1,6 +1,7 @@
 """Real-data front end: readers, transforms, splits and the pinned-buffer feeder, on files written by the test in the
-reference's on-disk formats; when the reference tree is present (this container, not the GPU box) the readers are also run on its
-shipped data files (shapes and label conventions only -- nothing from those files is copied)."""
+reference's on-disk formats, and on the reference's shipped data files themselves (tests/golden/g6_data_files.npz; the `ref` fixture
+lays them out in their directory layout)."""
+import lzma
 import os
 import pickle
 
@@ -10,7 +11,29 @@ import torch
 
 from structured_latent_odes_amd import data as D
 
-REF = "/root/reference/data"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    """Directory holding the reference's shipped data files (cvs/, challenge/, proc/) as written by tests/golden/make_golden_data.py:
+    every file byte for byte but cvs/processed_data.pkl, which holds the stored CVS series in their rows and NaN in every row no test
+    reads (only those rows are kept in the fixture)."""
+    root = tmp_path_factory.mktemp("ref_data")
+    with np.load(os.path.join(GOLDEN, "g6_data_files.npz")) as z:
+        blob, off = lzma.decompress(z["files.xz"].tobytes()), 0
+        for name, size in zip(z["files.names"], z["files.sizes"]):
+            path = root / str(name)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            path.write_bytes(blob[off:off + int(size)])
+            off += int(size)
+        assert off == len(blob)
+        obs = {}
+        for split in ("train", "test"):
+            obs[split] = np.full(tuple(z["cvs.%s.shape" % split]), np.nan)
+            obs[split][z["cvs.%s.rows" % split]] = z["cvs.%s.obs" % split]
+    torch.save(obs, str(root / "cvs" / "processed_data.pkl"))
+    return str(root)
 
 
 def _write_cvs(tmp, n_train=40, n_test=7, T=30, C=3, seed=0):
@@ -129,37 +152,33 @@ def test_proc_csv_reader(tmp_path):
     assert len(va_h) == 1 and float(va_h[0]["aR"][0]) == 1.0 and len(tr_h) == 3
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference data tree not present (GPU box)")
-def test_readers_on_the_shipped_reference_files():
-    tr = D.CVSDataset(REF + "/cvs/", "train", 86, False, D.create_transforms("zero_to_one", D._torch_load(REF + "/cvs/data_norm_params.pkl")))
+def test_readers_on_the_shipped_reference_files(ref):
+    tr = D.CVSDataset(ref + "/cvs/", "train", 86, False, D.create_transforms("zero_to_one", D._torch_load(ref + "/cvs/data_norm_params.pkl")))
     assert len(tr) == 810 and tr[0]["observations"].shape == (86, 3) and set(float(tr[i]["iext"]) for i in range(50)) <= {0.0, 1.0}
-    assert len(D.CVSDataset(REF + "/cvs/", "val", 86, False)) == 90 and len(D.CVSDataset(REF + "/cvs/", "test", 86, False)) == 100
-    pair = D.build_challenge_datasets(REF + "/challenge/data.pkl", seed=12, folds=5, split=5)
+    assert len(D.CVSDataset(ref + "/cvs/", "val", 86, False)) == 90 and len(D.CVSDataset(ref + "/cvs/", "test", 86, False)) == 100
+    pair = D.build_challenge_datasets(ref + "/challenge/data.pkl", seed=12, folds=5, split=5)
     assert (pair.n_train, pair.n_test, pair.max_time) == (28, 7, 142) and pair.train["observations"].shape == (28, 142, 4)
     devices = ["Pcat_Y81C76", "RS100S32_Y81C76", "RS100S34_Y81C76", "R33S32_Y81C76", "R33S34_Y81C76", "R33S175_Y81C76"]
     dmap = {d: float(i) for i, d in enumerate(devices)}
-    parsed = D.load_proc_csv(REF + "/proc/proc140916.csv", devices, dmap, ["C6", "C12"], ["OD", "mRFP1", "EYFP", "ECFP"])
+    parsed = D.load_proc_csv(ref + "/proc/proc140916.csv", devices, dmap, ["C6", "C12"], ["OD", "mRFP1", "EYFP", "ECFP"])
     assert parsed is not None and parsed[3].shape[1:] == (4, 100) and parsed[1].shape[1] == 2 and len(parsed[2]) == 100
-    tr, va, times = D.build_proc_datasets(REF + "/proc", seed=12, folds=4, split=1)
+    tr, va, times = D.build_proc_datasets(ref + "/proc", seed=12, folds=4, split=1)
     assert len(tr) == 234 and len(va) == 78 and times.shape == (100,) and tr[0]["observations"].shape == (4, 100)
     assert 0.0 <= float(tr.ds.observations.min()) and float(tr.ds.observations.max()) <= 1.0
 
 
 # ---- pinned against the reference's own loaders (tests/golden/g5_data.npz, written by tests/golden/make_golden_data.py) ----------
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g5_data.npz")
-needs_ref_data = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "proc", "proc140916.csv")),
-                                    reason="the reference's shipped data files are only present in the build container")
+GOLD = os.path.join(GOLDEN, "g5_data.npz")
 
 
-@needs_ref_data
-def test_cvs_reader_equals_reference_loader():
+def test_cvs_reader_equals_reference_loader(ref):
     g = np.load(GOLD)
     import torch as _t
-    params = _t.load(os.path.join(REF, "cvs", "data_norm_params.pkl"), weights_only=False)
+    params = _t.load(os.path.join(ref, "cvs", "data_norm_params.pkl"), weights_only=False)
     tf = D.create_transforms("zero_to_one", params)
     assert np.allclose(np.asarray(tf["normalize"].min_val, dtype=np.float64), g["cvs.norm.min"], rtol=1e-6)
     for split in ("train", "val", "test"):
-        ds = D.CVSDataset(os.path.join(REF, "cvs") + "/", split, 86, False, tf)
+        ds = D.CVSDataset(os.path.join(ref, "cvs") + "/", split, 86, False, tf)
         assert len(ds) == int(g["cvs.%s.len" % split])
         first = [ds[i] for i in range(3)] + [ds[len(ds) - 1]]
         assert np.array_equal(np.stack([s["observations"].numpy() for s in first]), g["cvs.%s.obs" % split])     # bit-exact
@@ -169,10 +188,9 @@ def test_cvs_reader_equals_reference_loader():
         assert sums == list(g["cvs.%s.label_sums" % split])
 
 
-@needs_ref_data
-def test_challenge_split_and_norm_equal_reference_loader():
+def test_challenge_split_and_norm_equal_reference_loader(ref):
     g = np.load(GOLD)
-    pair = D.build_challenge_datasets(os.path.join(REF, "challenge", "data.pkl"), seed=12, folds=5, split=5)
+    pair = D.build_challenge_datasets(os.path.join(ref, "challenge", "data.pkl"), seed=12, folds=5, split=5)
     assert (pair.n_train, pair.n_test, pair.max_time) == (int(g["challenge.n_train"]), int(g["challenge.n_test"]), int(g["challenge.max_time"]))
     for k in ("mean", "std", "max", "min"):
         assert np.array_equal(np.asarray(pair.data_norm_params[k], dtype=np.float64), g["challenge.norm.%s" % k]), k
@@ -188,13 +206,12 @@ def test_challenge_split_and_norm_equal_reference_loader():
         assert np.allclose(got[k], g["norm_params.synthetic.%s" % k], rtol=1e-12, atol=0)
 
 
-@needs_ref_data
-def test_proc_front_end_equals_reference_loader():
+def test_proc_front_end_equals_reference_loader(ref):
     g = np.load(GOLD)
     dmap = {d: float(i) for i, d in enumerate(D.PROC_DEVICES)}
     parsed = []
     for f in D.PROC_FILES:
-        dev, treat, times, obs = D.load_proc_csv(os.path.join(REF, "proc", f), D.PROC_DEVICES, dmap, D.PROC_CONDITIONS, D.PROC_SIGNALS)
+        dev, treat, times, obs = D.load_proc_csv(os.path.join(ref, "proc", f), D.PROC_DEVICES, dmap, D.PROC_CONDITIONS, D.PROC_SIGNALS)
         assert np.array_equal(dev, g["proc.file.%s.devices" % f])
         assert np.array_equal(treat, g["proc.file.%s.treatments" % f])
         assert np.array_equal(times, g["proc.file.%s.times" % f])
@@ -218,7 +235,7 @@ def test_proc_front_end_equals_reference_loader():
     tr, va = D.holdout_ids(ds.devices, int(dmap["R33S34_Y81C76"]))
     assert np.array_equal(tr, g["proc.heldout.train_ids"]) and np.array_equal(va, g["proc.heldout.val_ids"])
     # the training view and builder used by training_proc.py
-    tv, vv, times = D.build_proc_datasets(os.path.join(REF, "proc"), seed=12, folds=4, split=1)
+    tv, vv, times = D.build_proc_datasets(os.path.join(ref, "proc"), seed=12, folds=4, split=1)
     assert len(tv) == len(g["proc.fold1.train_ids"]) and len(vv) == len(g["proc.fold1.val_ids"])
     assert np.array_equal(times.numpy(), g["proc.times"].astype(np.float32))
 

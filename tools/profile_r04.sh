@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $ROOT
 M="--steps 100 --warmup 20 --ab"
-S="--steps 20 --warmup 5 --repeats 5 --ab"
+S="--steps 100 --warmup 5 --ab"
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_main -- python3 bench.py $M > $OUT/bench_main.json 2> $OUT/bench_main.err || echo "stats main failed"
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_full -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline > $OUT/bench_full.json 2> $OUT/bench_full.err || echo "stats full failed"
 for c in "config[0]" "rk4 (fixed" "dopri5" "config[4]"; do
