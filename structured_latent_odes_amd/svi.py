@@ -57,21 +57,31 @@ class _StepBase:
         # gradient buffer with the loss scalar appended => a single collective per step
         self.gbuf = torch.zeros(n_grad + 1, dtype=torch.float32, device=params.device)
         self.grads, self.loss = self.gbuf[:n_grad], self.gbuf[n_grad:]
-        self._rng_sharded = False
         self.dp_payload = "G"      # "G": reduce [G | head products | ODE-half row] and chain-rule after; "grad": reduce [flat gradient | loss]
         self._payload = None
         self.unfused = False       # True: take the data-parallel code path at world size 1 too (tests: RCCL at world size 1)
 
     def _batch(self, observations, eps, labels, u):
         eng = self.engine
-        if self.world > 1 and not self._rng_sharded and eps is None:
-            # in-kernel noise is keyed by the GLOBAL trajectory index: this rank's shard starts at rank * B (contiguous batch split)
-            seed, b0, n = eng.rng_state()
-            if b0 == 0 and self.rank > 0:
-                eng.rng_seed(seed, self.rank * observations.shape[0])
-                eng.rng_set_counter(n)
-            self._rng_sharded = True
+        if self.world > 1 and eps is None:
+            # in-kernel noise is keyed by the GLOBAL trajectory index: this rank's shard starts after the shards of the lower ranks
+            # (contiguous batch split).  Shard sizes can differ between ranks and change between steps (the last, partial batch of an
+            # epoch), and only the rank whose size changed would know: one all_gather of each rank's size, on every such step
+            b0 = self._shard_offset(observations.shape[0])
+            seed, cur, n = eng.rng_state()
+            if cur != b0:
+                eng.rng_seed(seed, b0)
+                eng.rng_set_counter(n)          # (rng_seed resets the call counter: keep it)
         return eng.make_batch(observations, _label_list(labels, u), eps)
+
+    def _shard_offset(self, B: int) -> int:
+        """Global index of this rank's first trajectory: the sum of the shard sizes of the lower ranks."""
+        nccl = "nccl" in str(torch.distributed.get_backend(self.pg))
+        dev = self.params.device if nccl else torch.device("cpu")
+        mine = torch.full((1,), B, dtype=torch.int64, device=dev)
+        sizes = [torch.zeros_like(mine) for _ in range(self.world)]
+        torch.distributed.all_gather(sizes, mine, group=self.pg)
+        return int(sum(torch.cat(sizes).tolist()[:self.rank]))
 
     def _named(self, labels, named):
         """Label tensors given by name (``iext=..., rtpr=...``, as the reference's batches carry them): the owner model's order."""

@@ -123,3 +123,74 @@ def test_two_rank_data_parallel_equals_single_process():
         assert abs(a - b) / abs(b) < 1e-5                         # summed over shards == whole batch (fp32 reduction order differs)
     assert abs(e0 - want_ev) / abs(want_ev) < 1e-5
     assert ((f0 - flat).norm() / flat.norm()).item() < 1e-4
+
+
+class KeyRecordingEngine:
+    """Engine test double for the in-kernel noise bookkeeping: records every rng_seed(seed, first_trajectory) call and the generator
+    key (first trajectory, call number) each step draws its noise with; the step itself returns zeros."""
+
+    def __init__(self):
+        self.n_params = 4
+        self.device = torch.device("cpu")
+        self.seed, self.b0, self.n = 2026, 0, 0
+        self.seeds, self.keys = [], []
+
+    def rng_seed(self, seed, first_trajectory=0):
+        self.seeds.append((seed, first_trajectory))
+        self.seed, self.b0, self.n = seed, first_trajectory, 0
+
+    def rng_state(self):
+        return self.seed, self.b0, self.n
+
+    def rng_set_counter(self, n):
+        self.n = n
+
+    def make_batch(self, obs, labels, eps=None):
+        return obs, eps
+
+    def svi_step(self, kind, params, batch, B, loss_out, grads=None, adam=None):
+        if batch[1] is None:                                        # noise drawn "in the kernels": one drawing call
+            self.keys.append((self.b0, self.n))
+            self.n += 1
+        loss_out.zero_()
+        if grads is not None:
+            grads.zero_()
+        return loss_out
+
+    def adam_step(self, params, grads, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8):
+        pass
+
+
+def _run_ragged(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    torch.distributed.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from structured_latent_odes_amd.svi import ELBOStep, FlatAdam
+        eng = KeyRecordingEngine()
+        flat = torch.zeros(eng.n_params)
+        svi = ELBOStep(eng, flat, FlatAdam(eng, flat, lr=1e-3))
+        for sizes in ([3, 5], [4, 1]):                              # global batches of 8 and 5, split unevenly
+            svi.step(torch.zeros(sizes[rank], 3, 10))
+        q.put((rank, eng.seeds, eng.keys))
+    finally:
+        torch.distributed.destroy_process_group()
+
+
+def test_ragged_shards_key_the_noise_by_the_global_trajectory_index():
+    """Shard sizes [3, 5] and then [4, 1]: rank 1's first trajectory is global trajectory 3 in the first step and 4 in the second, and
+    the call counter moves on as in a single process (one drawing call per step)."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_run_ragged, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = dict((r, (seeds, keys)) for r, seeds, keys in [q.get(timeout=240) for _ in procs])
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    assert res[0][1] == [(0, 0), (0, 1)], res[0]
+    assert res[1][1] == [(3, 0), (4, 1)], res[1]
+    assert res[1][0] == [(2026, 3), (2026, 4)], res[1]

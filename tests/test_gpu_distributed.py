@@ -25,7 +25,7 @@ def _free_port():
     return str(p)
 
 
-def _launch(world, steps, backend, payload, draw=False, timeout=280):
+def _launch(world, steps, backend, payload, draw=False, timeout=280, shards=None):
     """`world` fresh child processes on cuda:0 (tests/dp_worker.py); returns rank 0's result dict."""
     port = _free_port()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -36,7 +36,8 @@ def _launch(world, steps, backend, payload, draw=False, timeout=280):
         log_paths = [os.path.join(tmp, "rank%d.log" % r) for r in range(world)]
         handles = [open(lp, "wb") for lp in log_paths]
         procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dp_worker.py"), str(r), str(world), port, str(steps), out,
-                                   backend, payload] + (["draw"] if draw else []),
+                                   backend, payload] + (["draw" if draw else "explicit"] if draw or shards else [])
+                                  + ([shards] if shards else []),
                                   env=env, stdout=handles[r], stderr=subprocess.STDOUT) for r in range(world)]
         try:
             for p in procs:
@@ -53,10 +54,10 @@ def _launch(world, steps, backend, payload, draw=False, timeout=280):
         return torch.load(out)
 
 
-def _single(steps, draw=False):
+def _single(steps, draw=False, shards=None):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import dp_worker
-    return dp_worker.run(0, 1, steps, draw=draw)            # whole batch, one process: the fused one-call step
+    return dp_worker.run(0, 1, steps, draw=draw, shards=shards)   # whole batch, one process: the fused one-call step
 
 
 def _same(dp, single):
@@ -85,6 +86,14 @@ def test_two_ranks_drawing_their_own_noise_match_single_process():
     the sharded job and the single-process job integrate the same latent samples."""
     steps = 3
     _same(_launch(2, steps, "gloo", "G", draw=True), _single(steps, draw=True))
+
+
+def test_ragged_shards_drawing_their_own_noise_match_single_process():
+    """A global batch of 64 split 32 / 32, then one of 40 split 24 / 16 (the last, partial batch of an epoch; unequal shards): every step
+    keys rank 1's noise at the global index of its first trajectory -- 32, then 24 -- so the sharded job still integrates the latent
+    samples of the single-process job over the same two global batches."""
+    dp = _launch(2, 2, "gloo", "G", draw=True, shards="32,32:24,16")
+    _same(dp, _single(2, draw=True, shards=[[64], [40]]))
 
 
 @pytest.mark.parametrize("payload", ["G", "grad"])
