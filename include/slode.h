@@ -332,7 +332,10 @@ int slode_adam_step(slode_handle h, int64_t n, float* params, const float* grads
 int slode_adam_region(slode_handle h, int64_t lo, int64_t hi, int64_t step_delta);
 
 /* Diagnostic (no reference counterpart; torchdiffeq does not report it): accepted steps per trajectory of the last dopri5 training
- * step run on this workspace -> counts[B] (int32, device).  -1: 20,000 attempted steps exhausted; > capacity: record overflow. */
+ * step run on this workspace -> counts[B] (int32, device).  -1: 20,000 attempted steps exhausted; > capacity: record overflow (the
+ * capacity is slode_dopri5_kmax: 2^26 / (B (S + 2)) steps, within [64, 2048]).  A training step in which any trajectory did either
+ * returns a NaN loss and an all-NaN gradient (with Adam inside: NaN parameters), never a finite gradient that lacks that trajectory's
+ * solver share; the trajectories and the forward-only loss of an overflowed step are those of the solve, which is complete. */
 int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_layout* lay, const void* workspace,
                              size_t workspace_bytes, int* counts, void* stream);
 

@@ -857,6 +857,7 @@ struct DpBK {
   const float *w1, *b1, *w2, *b2, *wh, *bh, *wg, *bg, *wd, *bd;
   float *g_loc, *g_scale, *slabs;   // the latent gradient through the solver is ADDED to the scorer's dLoss/dloc, dLoss/dscale [B][L]
   const float* eps;                 // (z = loc + scale eps);  slabs: one row per workgroup, slot 0 = loss (0 / NaN on a failed solve), then the ode segment
+                                    // (all NaN on a failed solve, as is the latent gradient of the trajectory that failed)
   const float* tabs;           // the forward kernel's tables of this workgroup's trajectories (dump_tables) or nullptr: rebuilt here
   float* snap;                 // [B][2][H][4S] running sums parked when the sweep passes a switching time, by lane group and RANK (see grp::sweep_sample)
   int slab_stride, nseg, stage_gx;
@@ -1186,7 +1187,7 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
   }
 #undef SLODE_LDREC
   const bool any_bad = __syncthreads_or(live && bad) != 0;   // (also: every wave is done with the staged dL/dx rows)
-  if (tid == 0) row[0] = any_bad ? __builtin_nanf("") : 0.f;
+  if (tid == 0) row[0] = any_bad ? __builtin_nanf("") : 0.f;   // (the ode segment of the row follows it: see the end of the init-net section)
   // ---- the units' partial sums: every trajectory's terms go through one LDS tile [unit][term][trajectory] and are summed over the
   //      workgroup's trajectories in a fixed order --------------------------------------------------------------------------------
   {
@@ -1330,7 +1331,9 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
         if (l < L) {
           float o_loc = 0.f, o_ls = 0.f;
           if (live) {
-            const float gl = a1[q] + (k.drop_z ? 0.f : a2[q]);
+            // a trajectory without records (overflow, failed solve) has no solver share: its latent gradient is NaN, not the scorer's
+            // share alone, so that every encoder gradient element (a sum over the batch) is NaN too
+            const float gl = bad ? __builtin_nanf("") : a1[q] + (k.drop_z ? 0.f : a2[q]);
             const long long i = bb * L + l;
             o_loc = gl_[q] + gl;
             const float o_sc = fmaf(gl, ep_[q], gs_[q]);
@@ -1370,6 +1373,11 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
         for (int r = 0; r < BTP; ++r) acc += s_go[r * 8 + s];
         prm[k.o_b2 + s] = acc;
       }
+    }
+    if (any_bad) {   // (uniform) and the whole ode segment of the row: the sum over the slab rows is NaN for every element, not a
+                     // finite gradient without this workgroup's solver share (SVI.step applies Adam in the same launch)
+      __syncthreads();   // every store of the row above is done
+      for (int i = 1 + tid; i <= k.nseg; i += BNT) row[i] = __builtin_nanf("");
     }
   }
   {
