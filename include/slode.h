@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 110 /* 0.1.1: slode_svi_step, slode_rng_*, slode_grad_* */
+#define SLODE_VERSION 120 /* 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN (0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -44,7 +44,10 @@ typedef enum slode_status {
 } slode_status;
 
 /* torchdiffeq method strings accepted by OdeModel.init_with_params(solver=...), models/blackbox_ode.py:7-17,41-45 */
-typedef enum slode_method { SLODE_EULER = 0, SLODE_MIDPOINT = 1, SLODE_RK4 = 2, SLODE_DOPRI5 = 3 } slode_method;
+typedef enum slode_method {
+  SLODE_EULER = 0, SLODE_MIDPOINT = 1, SLODE_RK4 = 2,   /* fixed grid */
+  SLODE_DOPRI5 = 3, SLODE_BOSH3 = 4, SLODE_FEHLBERG2 = 5, SLODE_ADAPTIVE_HEUN = 6   /* adaptive (see slode_elbo_step) */
+} slode_method;
 
 /* Decoder (models/decoders.py:8-54, asymmetric-Laplace, 3 heads q50/q75/q25) or GaussianDecoder (:57-91, 1 head) */
 typedef enum slode_likelihood { SLODE_ALD = 0, SLODE_GAUSS = 1 } slode_likelihood;
@@ -91,7 +94,7 @@ typedef struct slode_shape {
   int32_t method;     /* slode_method                                                  */
   int32_t likelihood; /* slode_likelihood                                              */
   float quantile_diff; /* config.quantile_diff (ALD only), data/cvs/config_cvs.py:48    */
-  float rtol, atol;    /* dopri5 only (torchdiffeq defaults 1e-7 / 1e-9)                */
+  float rtol, atol;    /* adaptive methods (torchdiffeq defaults 1e-7 / 1e-9)           */
   int32_t n_aux;       /* label heads (auxiliary loss; also the main loss iff aux_in_main)  */
   int32_t U;           /* config.u_hidden_dim (<= 32)                                      */
   float aux_mult;      /* config.aux_loss_multiplier                                       */
@@ -213,7 +216,17 @@ int slode_decode_heads_bwd(slode_handle h, const slode_shape* s, const slode_lay
  * trajectories per call; a trajectory whose accepted steps exceed the record capacity (256 MB / (B*(S+2)) floats, clamped to
  * [64, 2048] steps) or that exhausts 20,000 attempted steps turns the loss into NaN.  slode_workspace_bytes accounts for the records, for
  * the running sums the reverse sweep parks at the hidden units' switching times ([B][2][H][4S]: one set per lane group of a trajectory) and
- * for the forward kernel's set-up tables of every sixteen trajectories, which the reverse sweep reads back instead of rebuilding them. */
+ * for the forward kernel's set-up tables of every sixteen trajectories, which the reverse sweep reads back instead of rebuilding them.
+ * method == SLODE_BOSH3 / SLODE_FEHLBERG2 / SLODE_ADAPTIVE_HEUN (torchdiffeq's other RKAdaptiveStepsizeODESolver methods: Bogacki-Shampine
+ * 3(2), Fehlberg 2(1), Heun-Euler 2(1)): the same contract as dopri5 -- one controller per trajectory, rtol / atol of the shape, a step
+ * at the fp32 time floor accepted, 20,000 attempts, the same record of accepted steps with the same capacity, the same overflow and
+ * failed-solve results, the reverse mode of the method's own stages and dense output -- with the method's tableau and its order p in
+ * the controller (factor 0.9 ratio^(-1/p)) and in the Hairer initial step ((0.01 / max(d1, d2))^(1/p)).  The low orders take many more
+ * steps at the same tolerance (measured at cvs B = 1024 T = 200 and config[2] B = 4096 T = 100): bosh3 and fehlberg2 train at
+ * both shapes at the defaults (bosh3 141-428 accepted steps, fehlberg2 225-751); adaptive_heun trains down to rtol 1e-5 / atol 1e-7
+ * (356-1206 steps) and at the defaults (3516-11906 steps) overflows the record, and the step returns NaN by contract.
+ * Forward-only solves (slode_ode_solve_fwd) take every adaptive method.  SLODE_DP5_LPT=32 / 64 (a test hook) is dopri5-only: with
+ * another adaptive method the step returns SLODE_EINVAL. */
 int slode_elbo_step(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params,
                     const float* times, const float* stage_t, const float* obs, const int64_t obs_strides[3],
                     const float* u, const float* eps, float* loss_out, float* grads, float* x_out, float* z_out,
@@ -331,8 +344,8 @@ int slode_adam_step(slode_handle h, int64_t n, float* params, const float* grads
  * slode_elbo_adam_step, slode_aux_step).  Default: empty region. */
 int slode_adam_region(slode_handle h, int64_t lo, int64_t hi, int64_t step_delta);
 
-/* Diagnostic (no reference counterpart; torchdiffeq does not report it): accepted steps per trajectory of the last dopri5 training
- * step run on this workspace -> counts[B] (int32, device).  -1: 20,000 attempted steps exhausted; > capacity: record overflow (the
+/* Diagnostic (no reference counterpart; torchdiffeq does not report it): accepted steps per trajectory of the last adaptive (dopri5,
+ * bosh3, fehlberg2, adaptive_heun) training step run on this workspace -> counts[B] (int32, device).  -1: 20,000 attempted steps exhausted; > capacity: record overflow (the
  * capacity is slode_dopri5_kmax: 2^26 / (B (S + 2)) steps, within [64, 2048]).  A training step in which any trajectory did either
  * returns a NaN loss and an all-NaN gradient (with Adam inside: NaN parameters), never a finite gradient that lacks that trajectory's
  * solver share; the trajectories and the forward-only loss of an overflowed step are those of the solve, which is complete. */

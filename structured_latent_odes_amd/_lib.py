@@ -8,9 +8,11 @@ LIB_PATH = os.environ.get("SLODE_LIB_PATH") or os.path.join(_HERE, "libslode.so"
 
 MAX_GROUPS, MAX_HEADS, MAX_AUX, MAX_LABELS = 4, 3, 4, 4
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
-EULER, MIDPOINT, RK4, DOPRI5 = 0, 1, 2, 3
+EULER, MIDPOINT, RK4, DOPRI5, BOSH3, FEHLBERG2, ADAPTIVE_HEUN = 0, 1, 2, 3, 4, 5, 6
 ALD, GAUSS = 0, 1
-METHODS = {"euler": EULER, "midpoint": MIDPOINT, "rk4": RK4, "dopri5": DOPRI5}
+METHODS = {"euler": EULER, "midpoint": MIDPOINT, "rk4": RK4, "dopri5": DOPRI5,
+           "bosh3": BOSH3, "fehlberg2": FEHLBERG2, "adaptive_heun": ADAPTIVE_HEUN}
+ADAPTIVE = ("dopri5", "bosh3", "fehlberg2", "adaptive_heun")   # torchdiffeq's RKAdaptiveStepsizeODESolver methods (slode_elbo_step)
 GRAD_MODES = {"exact": 0, "reference_adjoint": 1}   # slode_grad_mode
 
 

@@ -15,6 +15,11 @@
 // 2 fmas and one sigmoid pair -- branch-free, the evaluations of a step independent of each other; all the Runge-Kutta arithmetic is
 // scalar per lane.
 //
+// The same kernels run torchdiffeq's other adaptive Runge-Kutta pairs -- bosh3, fehlberg2, adaptive_heun -- which share the solver class
+// and everything above but the tableau and the order: the kernels are templates on a constexpr tableau type (Dopri5 / SmallRk<...>
+// below).  A step costs what its DISTINCT new stage times cost (one table look-up and sigmoid pair each); stages at the same time share
+// one evaluation.
+//
 // Training with dopri5 (BASELINE config[2]): the forward kernel also records every accepted step (t, dt, y) and
 // `dopri5_bwd_kernel` walks a trajectory's record backwards -- the exact reverse mode of the accepted Dormand-Prince steps and of
 // the dense-output polynomial, step sizes held fixed (the controller is not differentiated) -- in the same 8-lane mapping.  The
@@ -207,6 +212,112 @@ __device__ __forceinline__ float init_state(const InitRegs<S, H>& r, const float
   const float v = group_scatter8(o, g);
   return own ? sigmoidf_fast(v + r.b2) : 0.f;
 }
+
+// ---- tableaus ----------------------------------------------------------------------------------------------------------------------
+// A tableau type gives: NT distinct new stage times t + dt C[i] per attempted step (the first stage is the FSAL value at t), RP = 1 / order
+// (the controller's exponent and the Hairer initial step's), and step() / ymid(): the stages from the coefficients (a, d) at those times,
+// the solution y1, the embedded error estimate and the dense output's midpoint.  K carries the stage values from step() to ymid().
+//
+// Dormand-Prince 5(4), torchdiffeq/_impl/dopri5.py: written out by hand (the seven stages are the hot path of BASELINE config[2]).
+struct Dopri5 {
+  static constexpr int method = SLODE_DOPRI5, NT = 5;
+  static constexpr float RP = 0.2f;
+  static constexpr float C[NT] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f};   // stages 6 and 7 share t + dt
+  struct K { float k1, k3, k4, k5, k6, k7; };
+  __device__ static __forceinline__ void step(float dt, float y, float fcur, const float (&av)[NT], const float (&dv)[NT], K& k, float& y1, float& err) {
+    const float a2 = av[0], d2 = dv[0], a3 = av[1], d3 = dv[1], a4 = av[2], d4 = dv[2], a5 = av[3], d5 = dv[3], a6 = av[4], d6 = dv[4];
+    const float k2 = a2 - d2 * fmaf(dt, (1.f / 5) * fcur, y);
+    const float k3 = a3 - d3 * fmaf(dt, (3.f / 40) * fcur + (9.f / 40) * k2, y);
+    const float k4 = a4 - d4 * fmaf(dt, (44.f / 45) * fcur + (-56.f / 15) * k2 + (32.f / 9) * k3, y);
+    const float k5 = a5 - d5 * fmaf(dt, (19372.f / 6561) * fcur + (-25360.f / 2187) * k2 + (64448.f / 6561) * k3 + (-212.f / 729) * k4, y);
+    const float k6 = a6 - d6 * fmaf(dt, (9017.f / 3168) * fcur + (-355.f / 33) * k2 + (46732.f / 5247) * k3 + (49.f / 176) * k4 + (-5103.f / 18656) * k5, y);
+    y1 = fmaf(dt, (35.f / 384) * fcur + (500.f / 1113) * k3 + (125.f / 192) * k4 + (-2187.f / 6784) * k5 + (11.f / 84) * k6, y);
+    const float k7 = a6 - d6 * y1;
+    err = dt * ((35.f / 384 - 1951.f / 21600) * fcur + (500.f / 1113 - 22642.f / 50085) * k3 + (125.f / 192 - 451.f / 720) * k4 +
+                (-2187.f / 6784 + 12231.f / 42400) * k5 + (11.f / 84 - 649.f / 6300) * k6 + (-1.f / 60) * k7);
+    k.k1 = fcur; k.k3 = k3; k.k4 = k4; k.k5 = k5; k.k6 = k6; k.k7 = k7;
+  }
+  __device__ static __forceinline__ float ymid(float dt, float y, const K& k) {
+    return fmaf(dt, (6025192743.f / 30085553152.f / 2) * k.k1 + (51252292925.f / 65400821598.f / 2) * k.k3 +
+                        (-2691868925.f / 45128329728.f / 2) * k.k4 + (187940372067.f / 1594534317056.f / 2) * k.k5 +
+                        (-1776094331.f / 19743644256.f / 2) * k.k6 + (11237099.f / 235043384.f / 2) * k.k7, y);
+  }
+  __device__ static __forceinline__ float klast(const K& k) { return k.k7; }
+};
+
+// The small pairs, generic over their coefficients.  D gives NS stages (the last is FSAL: k_NS = f(t + dt, y1), its beta row = c_sol), the
+// NT distinct new stage times C (ascending), TI[i] = the time of stage i (-1: t), the beta rows A[i][j], c_sol B, c_error E, c_mid CM and RP.
+template <class D>
+struct SmallRk : D {
+  using D::NS; using D::NT; using D::C; using D::TI; using D::A; using D::B; using D::E; using D::CM;
+  struct K { float k[NS]; };
+  __device__ static __forceinline__ void step(float dt, float y, float fcur, const float (&av)[NT], const float (&dv)[NT], K& k, float& y1, float& err) {
+    k.k[0] = fcur;
+#pragma unroll
+    for (int i = 1; i + 1 < NS; ++i) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < i; ++j)
+        if (A[i][j] != 0.f) s = fmaf(A[i][j], k.k[j], s);
+      k.k[i] = av[TI[i]] - dv[TI[i]] * fmaf(dt, s, y);
+    }
+    float s = 0.f, e = 0.f;
+#pragma unroll
+    for (int j = 0; j + 1 < NS; ++j)
+      if (B[j] != 0.f) s = fmaf(B[j], k.k[j], s);
+    y1 = fmaf(dt, s, y);
+    k.k[NS - 1] = av[TI[NS - 1]] - dv[TI[NS - 1]] * y1;
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+      if (E[j] != 0.f) e = fmaf(E[j], k.k[j], e);
+    err = dt * e;
+  }
+  __device__ static __forceinline__ float ymid(float dt, float y, const K& k) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+      if (CM[j] != 0.f) s = fmaf(CM[j], k.k[j], s);
+    return fmaf(dt, s, y);
+  }
+  __device__ static __forceinline__ float klast(const K& k) { return k.k[NS - 1]; }
+};
+
+// Bogacki-Shampine 3(2), torchdiffeq/_impl/bosh3.py
+struct Bosh3Def {
+  static constexpr int method = SLODE_BOSH3, NS = 4, NT = 3;
+  static constexpr float RP = 1.f / 3;
+  static constexpr float C[NT] = {1.f / 2, 3.f / 4, 1.f};
+  static constexpr int TI[NS] = {-1, 0, 1, 2};
+  static constexpr float A[NS][NS] = {{0.f}, {1.f / 2}, {0.f, 3.f / 4}, {2.f / 9, 1.f / 3, 4.f / 9}};
+  static constexpr float B[NS] = {2.f / 9, 1.f / 3, 4.f / 9, 0.f};
+  static constexpr float E[NS] = {(float)(2.0 / 9 - 7.0 / 24), (float)(1.0 / 3 - 1.0 / 4), (float)(4.0 / 9 - 1.0 / 3), -1.f / 8};
+  static constexpr float CM[NS] = {0.f, 0.5f, 0.f, 0.f};
+};
+// Runge-Kutta-Fehlberg 2(1), torchdiffeq/_impl/fehlberg2.py (stages 3 and 4 share t + dt)
+struct Fehlberg2Def {
+  static constexpr int method = SLODE_FEHLBERG2, NS = 4, NT = 2;
+  static constexpr float RP = 1.f / 2;
+  static constexpr float C[NT] = {1.f / 2, 1.f};
+  static constexpr int TI[NS] = {-1, 0, 1, 1};
+  static constexpr float A[NS][NS] = {{0.f}, {1.f / 2}, {1.f / 256, 255.f / 256}, {1.f / 512, 255.f / 256, 1.f / 512}};
+  static constexpr float B[NS] = {1.f / 512, 255.f / 256, 1.f / 512, 0.f};
+  static constexpr float E[NS] = {-1.f / 512, 0.f, 1.f / 512, 0.f};
+  static constexpr float CM[NS] = {0.f, 0.5f, 0.f, 0.f};
+};
+// Heun-Euler 2(1), torchdiffeq/_impl/adaptive_heun.py (stages 2 and 3 share t + dt)
+struct AdaptiveHeunDef {
+  static constexpr int method = SLODE_ADAPTIVE_HEUN, NS = 3, NT = 1;
+  static constexpr float RP = 1.f / 2;
+  static constexpr float C[NT] = {1.f};
+  static constexpr int TI[NS] = {-1, 0, 0};
+  static constexpr float A[NS][NS] = {{0.f}, {1.f}, {1.f / 2, 1.f / 2}};
+  static constexpr float B[NS] = {1.f / 2, 1.f / 2, 0.f};
+  static constexpr float E[NS] = {1.f / 2, -1.f / 2, 0.f};
+  static constexpr float CM[NS] = {1.f / 2, 0.f, 0.f};
+};
+using Bosh3 = SmallRk<Bosh3Def>;
+using Fehlberg2 = SmallRk<Fehlberg2Def>;
+using AdaptiveHeun = SmallRk<AdaptiveHeunDef>;
 
 // LDS of one trajectory group: the shared tables (time weights, head weights by unit) and per trajectory the hidden offsets, the
 // switching times, their order, the segment centres and the segment table
@@ -520,7 +631,7 @@ __device__ __forceinline__ void latent_store(const DpK& k, long long bb, bool li
   }
 }
 
-template <int S, int H>
+template <class M, int S, int H>
 __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
   static_assert(S <= G && H <= G * JL && H <= 32, "one state component and JL hidden units per lane; unit bits in one word");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -570,7 +681,7 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
     eval_ad<H>(t + h0, w, g, own, tab, ctr, a, d);
     const float f1 = a - d * y1;
     const float d2 = group_rms<S>((f1 - fcur) / sc, own) / h0;
-    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
+    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), M::RP);
     dt = fminf(100.f * h0, h1);
   }
   float* rrec = k.rec + bb * (S + 2);                      // this trajectory's record of the next accepted step
@@ -583,21 +694,16 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
   while (__any(live && j < T && steps < k.max_steps)) {
     const bool act = live && j < T && steps < k.max_steps;
     ++steps;
-    // the five evaluation times of the step are known up front: five independent table look-ups
-    const float te[5] = {t + dt * (1.f / 5), t + dt * (3.f / 10), t + dt * (4.f / 5), t + dt * (8.f / 9), t + dt};   // stages 6 and 7 share t + dt
-    float av[5], dv[5];
-    int rv[5];
-    eval_ad_batch<H, 5>(te, w, g, own, tab, ctr, av, dv, rv);
-    const float a2 = av[0], d2 = dv[0], a3 = av[1], d3 = dv[1], a4 = av[2], d4 = dv[2], a5 = av[3], d5 = dv[3], a6 = av[4], d6 = dv[4];
-    const float k2 = a2 - d2 * fmaf(dt, (1.f / 5) * fcur, y);
-    const float k3 = a3 - d3 * fmaf(dt, (3.f / 40) * fcur + (9.f / 40) * k2, y);
-    const float k4 = a4 - d4 * fmaf(dt, (44.f / 45) * fcur + (-56.f / 15) * k2 + (32.f / 9) * k3, y);
-    const float k5 = a5 - d5 * fmaf(dt, (19372.f / 6561) * fcur + (-25360.f / 2187) * k2 + (64448.f / 6561) * k3 + (-212.f / 729) * k4, y);
-    const float k6 = a6 - d6 * fmaf(dt, (9017.f / 3168) * fcur + (-355.f / 33) * k2 + (46732.f / 5247) * k3 + (49.f / 176) * k4 + (-5103.f / 18656) * k5, y);
-    const float y1 = fmaf(dt, (35.f / 384) * fcur + (500.f / 1113) * k3 + (125.f / 192) * k4 + (-2187.f / 6784) * k5 + (11.f / 84) * k6, y);
-    const float k7 = a6 - d6 * y1;
-    const float e = dt * ((35.f / 384 - 1951.f / 21600) * fcur + (500.f / 1113 - 22642.f / 50085) * k3 + (125.f / 192 - 451.f / 720) * k4 +
-                          (-2187.f / 6784 + 12231.f / 42400) * k5 + (11.f / 84 - 649.f / 6300) * k6 + (-1.f / 60) * k7);
+    // the NT evaluation times of the step are known up front: NT independent table look-ups
+    float te[M::NT];
+#pragma unroll
+    for (int i = 0; i < M::NT; ++i) te[i] = t + dt * M::C[i];
+    float av[M::NT], dv[M::NT];
+    int rv[M::NT];
+    eval_ad_batch<H, M::NT>(te, w, g, own, tab, ctr, av, dv, rv);
+    typename M::K kk;
+    float y1, e;
+    M::step(dt, y, fcur, av, dv, kk, y1, e);
     const float ratio = group_rms_fast<S>(e * DP5_RCP(atol + rtol * fmaxf(fabsf(y), fabsf(y1))), own);
     // a step at the resolution floor of fp32 time is accepted regardless (torchdiffeq would raise 'underflow in dt')
     const bool accept = act && (ratio <= 1.f || dt <= 16.f * 1.1920929e-7f * fmaxf(fabsf(t), 1.f));
@@ -609,10 +715,9 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
       }
       rrec += rstride;   // (the record of step nacc sits at rec + (nacc B + b)(S + 2): advanced, not multiplied out, per accepted step)
       ++nacc;
+      const float k7 = M::klast(kk);   // f(t + dt, y1): the next step's first stage
       if (j < T && tj <= t1) {
-        const float ymid = fmaf(dt, (6025192743.f / 30085553152.f / 2) * fcur + (51252292925.f / 65400821598.f / 2) * k3 +
-                                        (-2691868925.f / 45128329728.f / 2) * k4 + (187940372067.f / 1594534317056.f / 2) * k5 +
-                                        (-1776094331.f / 19743644256.f / 2) * k6 + (11237099.f / 235043384.f / 2) * k7, y);
+        const float ymid = M::ymid(dt, y, kk);
         const float ca = 2.f * dt * (k7 - fcur) - 8.f * (y1 + y) + 16.f * ymid;
         const float cb = dt * (5.f * fcur - 3.f * k7) + 18.f * y + 14.f * y1 - 32.f * ymid;
         const float cc = dt * (k7 - 4.f * fcur) - 11.f * y - 5.f * y1 + 16.f * ymid;
@@ -639,9 +744,9 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
       if (ratio == 0.f) factor = 10.f;
       else {
 #ifdef SLODE_DP5_PRECISE
-        const float safe = 0.9f * powf(ratio, -0.2f);
+        const float safe = 0.9f * powf(ratio, -M::RP);
 #else
-        const float safe = 0.9f * __builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/5) (v_log_f32 is log2)
+        const float safe = 0.9f * __builtin_amdgcn_exp2f(-M::RP * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/p) (v_log_f32 is log2)
 #endif
         factor = fminf(10.f, fmaxf(safe, ratio < 1.f ? 1.f : 0.2f));
       }
@@ -668,11 +773,11 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
 // about the three widths is in DESIGN 3.3 (LPT = 64 turns the latency problem into an equally large throughput problem: every lane group
 // repeats the combination, and the scalar bookkeeping of 16 waves per CU saturates the issue slots).
 constexpr int WNTH = 256;         // threads per workgroup: WNTH / LPT trajectories
-template <int S, int H, int LPT>
+template <class M, int S, int H, int LPT>
 __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
   static_assert(S <= G && H <= G * JL && H <= 32, "one state component and JL hidden units per lane; unit bits in one word");
   static_assert(LPT == 16 || LPT == 32 || LPT == 64, "lane groups of eight inside a wave");
-  constexpr int NG = LPT / G, NR = (5 + NG - 1) / NG, WTP = WNTH / LPT;   // lane groups, evaluation rounds, trajectories per workgroup
+  constexpr int NT = M::NT, NG = LPT / G, NR = (NT + NG - 1) / NG, WTP = WNTH / LPT;   // lane groups, evaluation rounds, trajectories per workgroup
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, g = lane & (G - 1), e = (lane & (LPT - 1)) >> 3, slot = tid / LPT, b = blockIdx.x * WTP + slot;
   const int L = k.L, T = k.T;
@@ -718,7 +823,7 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
     eval_ad<H>(t + h0, w, g, own, tab, ctr, a, d);
     const float f1 = a - d * y1;
     const float d2 = group_rms<S>((f1 - fcur) / sc, own) / h0;
-    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
+    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), M::RP);
     dt = fminf(100.f * h0, h1);
   }
   float* rrec = k.rec + bb * (S + 2);                      // this trajectory's record of the next accepted step
@@ -727,53 +832,48 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
   int steps = bad_grid ? k.max_steps : 0, nacc = 0;
   float tj = s_times[j < T ? j : T - 1];   // the next output time, read ahead of its use
   float tj1 = s_times[min(j + 1, T - 1)];  // (sixteen lanes per trajectory: and the one after)
-  // stage i (t + dt {1/5, 3/10, 4/5, 8/9, 1}; stages 6 and 7 share the last) is evaluated by lane group i % NG in round i / NG
+  // new stage time i (dopri5: t + dt {1/5, 3/10, 4/5, 8/9, 1}; stages 6 and 7 share the last) is evaluated by lane group i % NG in round i / NG
   const int base = ((lane & ~(LPT - 1)) + g) << 2;   // ds_bpermute byte index of lane (this trajectory, group 0, component g)
   // every lane leaves the loop: either all outputs written or max_steps reached (the missing outputs are then NaN).  The butterflies inside
   // eval_ad / group_rms and the gathers sit at the top level of the loop body: all 64 lanes execute them.
   while (__any(live && j < T && steps < k.max_steps)) {
     const bool act = live && j < T && steps < k.max_steps;
     ++steps;
-    const float te5[5] = {t + dt * (1.f / 5), t + dt * (3.f / 10), t + dt * (4.f / 5), t + dt * (8.f / 9), t + dt};
+    float te5[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) te5[i] = t + dt * M::C[i];
     float ar[NR], dr[NR], ter[NR];
     int rr[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-      float te = te5[4];
+      float te = te5[NT - 1];
 #pragma unroll
-      for (int i = 0; i < 5; ++i)
+      for (int i = 0; i < NT; ++i)
         if (i / NG == r) te = (e == i % NG) ? te5[i] : te;   // (groups without a stage in this round repeat the last one)
       ter[r] = te;
     }
     eval_ad_batch<H, NR>(ter, w, g, own, tab, ctr, ar, dr, rr);   // the rounds' table reads in one batch (one LDS round trip per attempt)
-    float av[5], dv[5];
+    float av[NT], dv[NT];
     if (LPT == 16) {
       // two lane groups = the two halves of a DPP row: the other group's value is one row rotation by eight lanes away (no LDS round trip)
 #pragma unroll
-      for (int r = 0; r < 2; ++r) {
+      for (int r = 0; r < NT / 2; ++r) {
         const float oa = __uint_as_float(dpp_u<0x128>(__float_as_uint(ar[r]))), od = __uint_as_float(dpp_u<0x128>(__float_as_uint(dr[r])));   // row_ror:8
         av[2 * r] = e == 0 ? ar[r] : oa; dv[2 * r] = e == 0 ? dr[r] : od;
         av[2 * r + 1] = e == 0 ? oa : ar[r]; dv[2 * r + 1] = e == 0 ? od : dr[r];
       }
-      av[4] = ar[2]; dv[4] = dr[2];   // (both groups evaluated t + dt in the last round)
+      if (NT % 2) { av[NT - 1] = ar[NR - 1]; dv[NT - 1] = dr[NR - 1]; }   // (both groups evaluated the last time in the last round)
     } else {
 #pragma unroll
-      for (int i = 0; i < 5; ++i) {
+      for (int i = 0; i < NT; ++i) {
         const int srcl = base + ((i % NG) << 5);
         av[i] = __uint_as_float((unsigned)__builtin_amdgcn_ds_bpermute(srcl, (int)__float_as_uint(ar[i / NG])));
         dv[i] = __uint_as_float((unsigned)__builtin_amdgcn_ds_bpermute(srcl, (int)__float_as_uint(dr[i / NG])));
       }
     }
-    const float a2 = av[0], d2 = dv[0], a3 = av[1], d3 = dv[1], a4 = av[2], d4 = dv[2], a5 = av[3], d5 = dv[3], a6 = av[4], d6 = dv[4];
-    const float k2 = a2 - d2 * fmaf(dt, (1.f / 5) * fcur, y);
-    const float k3 = a3 - d3 * fmaf(dt, (3.f / 40) * fcur + (9.f / 40) * k2, y);
-    const float k4 = a4 - d4 * fmaf(dt, (44.f / 45) * fcur + (-56.f / 15) * k2 + (32.f / 9) * k3, y);
-    const float k5 = a5 - d5 * fmaf(dt, (19372.f / 6561) * fcur + (-25360.f / 2187) * k2 + (64448.f / 6561) * k3 + (-212.f / 729) * k4, y);
-    const float k6 = a6 - d6 * fmaf(dt, (9017.f / 3168) * fcur + (-355.f / 33) * k2 + (46732.f / 5247) * k3 + (49.f / 176) * k4 + (-5103.f / 18656) * k5, y);
-    const float y1 = fmaf(dt, (35.f / 384) * fcur + (500.f / 1113) * k3 + (125.f / 192) * k4 + (-2187.f / 6784) * k5 + (11.f / 84) * k6, y);
-    const float k7 = a6 - d6 * y1;
-    const float er = dt * ((35.f / 384 - 1951.f / 21600) * fcur + (500.f / 1113 - 22642.f / 50085) * k3 + (125.f / 192 - 451.f / 720) * k4 +
-                           (-2187.f / 6784 + 12231.f / 42400) * k5 + (11.f / 84 - 649.f / 6300) * k6 + (-1.f / 60) * k7);
+    typename M::K kk;
+    float y1, er;
+    M::step(dt, y, fcur, av, dv, kk, y1, er);
     const float ratio = group_rms_fast<S>(er * DP5_RCP(atol + rtol * fmaxf(fabsf(y), fabsf(y1))), own);
     // a step at the resolution floor of fp32 time is accepted regardless (torchdiffeq would raise 'underflow in dt')
     const bool accept = act && (ratio <= 1.f || dt <= 16.f * 1.1920929e-7f * fmaxf(fabsf(t), 1.f));
@@ -785,10 +885,9 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
       }
       rrec += rstride;
       ++nacc;
+      const float k7 = M::klast(kk);   // f(t + dt, y1): the next step's first stage
       if (j < T && tj <= t1) {
-        const float ymid = fmaf(dt, (6025192743.f / 30085553152.f / 2) * fcur + (51252292925.f / 65400821598.f / 2) * k3 +
-                                        (-2691868925.f / 45128329728.f / 2) * k4 + (187940372067.f / 1594534317056.f / 2) * k5 +
-                                        (-1776094331.f / 19743644256.f / 2) * k6 + (11237099.f / 235043384.f / 2) * k7, y);
+        const float ymid = M::ymid(dt, y, kk);
         const float ca = 2.f * dt * (k7 - fcur) - 8.f * (y1 + y) + 16.f * ymid;
         const float cb = dt * (5.f * fcur - 3.f * k7) + 18.f * y + 14.f * y1 - 32.f * ymid;
         const float cc = dt * (k7 - 4.f * fcur) - 11.f * y - 5.f * y1 + 16.f * ymid;
@@ -833,9 +932,9 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
       if (ratio == 0.f) factor = 10.f;
       else {
 #ifdef SLODE_DP5_PRECISE
-        const float safe = 0.9f * powf(ratio, -0.2f);
+        const float safe = 0.9f * powf(ratio, -M::RP);
 #else
-        const float safe = 0.9f * __builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/5) (v_log_f32 is log2)
+        const float safe = 0.9f * __builtin_amdgcn_exp2f(-M::RP * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/p) (v_log_f32 is log2)
 #endif
         factor = fminf(10.f, fmaxf(safe, ratio < 1.f ? 1.f : 0.2f));
       }
@@ -914,7 +1013,7 @@ __device__ __forceinline__ void sweep_sample(float t, int now, float ga, float g
   RTa = fmaf(a, t, RTa); RTd = fmaf(d, t, RTd);
 }
 
-template <int S, int H>
+template <class M, int S, int H>
 __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) dopri5_bwd_kernel(const DpBK k) {   // (register budget of two waves per SIMD: left alone, the scheduler parks values in AGPRs)
   static_assert(S <= G && H <= G * JL && H <= 32, "one state component and JL hidden units per lane; unit bits in one word");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1058,7 +1157,21 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
   // `request`: the read-ahead of the step record after next.  It goes out BEHIND the loop over the step's output samples: that loop may read
   // dL/dx from global memory (rows that do not fit in LDS), so it waits with s_waitcnt vmcnt(0) -- which, counting in order, also waits for
   // whatever was requested before it; requested at the top of the step the records were a memory round trip per step on the critical path
+  auto outputs = [&](const float t, const float dt, const bool act, float& Ga, float& Gb, float& Gc, float& Gd, float& gy) __attribute__((always_inline)) {
+    const float rdt = __builtin_amdgcn_rcpf(dt);   // (1 ulp: q only places the sample on the step's polynomial)
+    while (act && j >= 1 && tj > t) {
+      const float q = (tj - t) * rdt, q2 = q * q, q3 = q2 * q, q4 = q2 * q2;
+      const float gq = gj;
+      --j;
+      tj = s_times[j];                                  // read ahead of their use (j >= 0)
+      gj = k.stage_gx ? gxs[j * S] : gxb[j * S];
+      gj = own ? gj : 0.f;
+      gy += gq;
+      Gd = fmaf(q, gq, Gd); Gc = fmaf(q2, gq, Gc); Gb = fmaf(q3, gq, Gb); Ga = fmaf(q4, gq, Ga);
+    }
+  };
   auto step = [&](const float t, const float dt, const float y, const bool act, auto&& request) __attribute__((always_inline)) {
+   if constexpr (M::method == SLODE_DOPRI5) {
     const float te0 = t, te1 = t + dt * (1.f / 5), te2 = t + dt * (3.f / 10), te3 = t + dt * (4.f / 5), te4 = t + dt * (8.f / 9), te5 = t + dt;
     // ---- forward recomputation of the stages from the recorded (t, dt, y) ------------------------------------------------------
     // this lane group's three stage times: three independent table look-ups, their LDS reads in one batch; the other group's
@@ -1177,6 +1290,104 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
     // stage 1
     gy = fmaf(-d0, g1, gy);
     lam = act ? gy : lam;
+   } else {
+    // The small pairs.  NT + 1 distinct times per step (t itself: the first stage), in decreasing order u = NT, NT - 1, ..., 0 (u = 0: t,
+    // u = i + 1: t + dt C[i]); round r gives time NT - 2r to lane group 1 and NT - 2r - 1 to group 0, so each group's own samples still
+    // fall along the sweep.  A group left without a time in the last round repeats t with a zero sample.
+    constexpr int NS = M::NS, NT = M::NT, NRB = (NT + 2) / 2;
+    float tu[NT + 1];
+    tu[0] = t;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) tu[i + 1] = t + dt * M::C[i];
+    float mt[NRB], ma[NRB], md[NRB];
+    int mr[NRB];
+#pragma unroll
+    for (int r = 0; r < NRB; ++r) mt[r] = e ? tu[NT - 2 * r] : tu[NT - 2 * r - 1 >= 0 ? NT - 2 * r - 1 : 0];
+    eval_ad_batch<H, NRB>(mt, w, g, own, tab, ctr, ma, md, mr);
+    float au[NT + 1], du[NT + 1], apu[NT + 1], dpu[NT + 1];   // coefficients at time u and their sigmoid'
+#pragma unroll
+    for (int r = 0; r < NRB; ++r) {
+      const float oa = __uint_as_float(dpp_u<0x128>(__float_as_uint(ma[r])));   // row_ror:8: the other group's evaluation
+      const float od = __uint_as_float(dpp_u<0x128>(__float_as_uint(md[r])));
+      const int u1 = NT - 2 * r, u0 = NT - 2 * r - 1;
+      au[u1] = e ? ma[r] : oa; du[u1] = e ? md[r] : od;
+      if (u0 >= 0) { au[u0] = e ? oa : ma[r]; du[u0] = e ? od : md[r]; }
+    }
+#pragma unroll
+    for (int u = 0; u <= NT; ++u) { apu[u] = au[u] * (1.f - au[u]); dpu[u] = du[u] * (1.f - du[u]); }
+    // ---- forward recomputation of the stages from the recorded (t, dt, y) ------------------------------------------------------------
+    float kk[NS], ys[NS];
+    ys[0] = y;
+    kk[0] = au[0] - du[0] * y;
+#pragma unroll
+    for (int i = 1; i + 1 < NS; ++i) {
+      float sacc = 0.f;
+#pragma unroll
+      for (int jj = 0; jj < i; ++jj)
+        if (M::A[i][jj] != 0.f) sacc = fmaf(M::A[i][jj], kk[jj], sacc);
+      ys[i] = fmaf(dt, sacc, y);
+      kk[i] = au[M::TI[i] + 1] - du[M::TI[i] + 1] * ys[i];
+    }
+    {
+      float sacc = 0.f;
+#pragma unroll
+      for (int jj = 0; jj + 1 < NS; ++jj)
+        if (M::B[jj] != 0.f) sacc = fmaf(M::B[jj], kk[jj], sacc);
+      ys[NS - 1] = fmaf(dt, sacc, y);   // y1
+    }
+    // ---- dense outputs inside (t, t + dt] ---------------------------------------------------------------------------------------------
+    float Ga = 0.f, Gb = 0.f, Gc = 0.f, Gd = 0.f, gy = 0.f;
+    outputs(t, dt, act, Ga, Gb, Gc, Gd, gy);
+    request();
+    // ---- reverse mode of the step: dL/dk_i into gk[i], through the dense output (f0 = k_1, f1 = k_NS, y_mid = y + dt sum c_mid k) --------
+    const float gm = 16.f * Ga - 32.f * Gb + 16.f * Gc;          // dL/dy_mid
+    gy += -8.f * Ga + 18.f * Gb - 11.f * Gc + gm;
+    float gy1 = lam - 8.f * Ga + 14.f * Gb - 5.f * Gc;
+    const float dgm = dt * gm;
+    float gk[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) gk[i] = M::CM[i] != 0.f ? dgm * M::CM[i] : 0.f;
+    gk[0] += dt * (-2.f * Ga + 5.f * Gb - 4.f * Gc + Gd);
+    gk[NS - 1] += dt * (2.f * Ga - 3.f * Gb + Gc);
+    // last stage: k_NS = a - d y1
+    gy1 = fmaf(-du[M::TI[NS - 1] + 1], gk[NS - 1], gy1);
+    // y1 = y + dt sum c_sol k
+    gy += gy1;
+    {
+      const float dg = dt * gy1;
+#pragma unroll
+      for (int jj = 0; jj + 1 < NS; ++jj)
+        if (M::B[jj] != 0.f) gk[jj] = fmaf(dg, M::B[jj], gk[jj]);
+    }
+#pragma unroll
+    for (int i = NS - 2; i >= 1; --i) {   // k_i = a - d ys_i, ys_i = y + dt sum_j beta_ij k_j
+      const float ee = -du[M::TI[i] + 1] * gk[i];
+      gy += ee;
+      const float de = dt * ee;
+#pragma unroll
+      for (int jj = 0; jj < i; ++jj)
+        if (M::A[i][jj] != 0.f) gk[jj] = fmaf(de, M::A[i][jj], gk[jj]);
+    }
+    gy = fmaf(-du[0], gk[0], gy);   // stage 1
+    // ---- samples: the head gradients at each distinct time, summed over the stages at that time ------------------------------------
+    float xu[NT + 1], xv[NT + 1];
+#pragma unroll
+    for (int u = 0; u <= NT; ++u) { xu[u] = 0.f; xv[u] = 0.f; }
+    xu[0] = gk[0] * apu[0]; xv[0] = -gk[0] * y * dpu[0];
+#pragma unroll
+    for (int i = 1; i < NS; ++i) {
+      const int u = M::TI[i] + 1;
+      xu[u] = fmaf(gk[i], apu[u], xu[u]);
+      xv[u] = fmaf(-gk[i] * ys[i], dpu[u], xv[u]);
+    }
+#pragma unroll
+    for (int r = 0; r < NRB; ++r) {
+      const int u1 = NT - 2 * r, u0 = NT - 2 * r - 1;
+      const float xa = e ? xu[u1] : (u0 >= 0 ? xu[u0] : 0.f), xd = e ? xv[u1] : (u0 >= 0 ? xv[u0] : 0.f);
+      sweep_sample<S>(mt[r], mr[r], xa, xd, RSa, RSd, RTa, RTd, cnt_prev, cnt_first, act, own, gs, snap);
+    }
+    lam = act ? gy : lam;
+   }
   };
   for (int it = 0; __any(it < K); it += 3) {
     step(ta, dta, ya, it < K, [&]() __attribute__((always_inline)) { SLODE_LDREC(it + 2, tc, dtc, yc) });
@@ -1442,6 +1653,37 @@ int slode_dopri5_kmax(const slode_shape& s) {
   return (int)(kmax < 64 ? 64 : (kmax > 2048 ? 2048 : kmax));
 }
 
+// (S, H) in {(5, 25), (8, 25)}.  dopri5: 8, 16, 32 or 64 lanes per trajectory; the small pairs: 8 or 16 (hipErrorNotSupported otherwise --
+// slode_dp5_lanes_ok refuses the rest before anything is launched)
+template <class M>
+static hipError_t launch_fwd(const slode_shape& s, const DpK& k, int lpt, hipStream_t stream) {
+  if (lpt == 16 || lpt == 32 || lpt == 64) {
+    const int wtp = WNTH / lpt, grid = (s.B + wtp - 1) / wtp;
+    const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(wtp) + (size_t)wtp * ((s.L + 3) & ~3) + (size_t)s.T);
+#define SLODE_DP5_LPT(SS, LL) SLODE_LAUNCH("dopri5_fwd", (dopri5_lpt_kernel<M, SS, 25, LL>), dim3(grid), dim3(WNTH), lds, stream, k)
+    if constexpr (M::method == SLODE_DOPRI5) {
+      if (s.S == 5) { if (lpt == 16) SLODE_DP5_LPT(5, 16); else if (lpt == 32) SLODE_DP5_LPT(5, 32); else SLODE_DP5_LPT(5, 64); }
+      else { if (lpt == 16) SLODE_DP5_LPT(8, 16); else if (lpt == 32) SLODE_DP5_LPT(8, 32); else SLODE_DP5_LPT(8, 64); }
+    } else {
+      if (lpt != 16) return hipErrorNotSupported;
+      if (s.S == 5) SLODE_DP5_LPT(5, 16); else SLODE_DP5_LPT(8, 16);
+    }
+#undef SLODE_DP5_LPT
+    return hipGetLastError();
+  }
+  if (lpt != 8) return hipErrorNotSupported;
+  const int grid = (s.B + TPB - 1) / TPB;
+  const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(TPB) + (size_t)TPB * ((s.L + 3) & ~3) + (size_t)s.T);
+  if (s.S == 5) SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<M, 5, 25>), dim3(grid), dim3(DNT), lds, stream, k);
+  else SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<M, 8, 25>), dim3(grid), dim3(DNT), lds, stream, k);
+  return hipGetLastError();
+}
+
+int slode_dp5_lanes_ok(int method, int lpt) {
+  if (lpt == 8 || lpt == 16) return 1;
+  return method == SLODE_DOPRI5 && (lpt == 32 || lpt == 64);
+}
+
 hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, const float* p, const float* times, const float* z,
                                float* x, hipStream_t stream, const DopriRec* rec) {
   DpK k;
@@ -1456,21 +1698,26 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
   k.atol = s.atol > 0.f ? s.atol : 1e-9f;
   k.max_steps = 20000;
   const int lpt = rec ? rec->w64 : 8;    // lanes per trajectory of the forward solve: 8 (the round-2 kernel), 16, 32 or 64 -- all the same bits
-  if (lpt == 16 || lpt == 32 || lpt == 64) {
-    const int wtp = WNTH / lpt, grid = (s.B + wtp - 1) / wtp;
-    const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(wtp) + (size_t)wtp * ((s.L + 3) & ~3) + (size_t)s.T);
-#define SLODE_DP5_LPT(SS, LL) SLODE_LAUNCH("dopri5_fwd", (dopri5_lpt_kernel<SS, 25, LL>), dim3(grid), dim3(WNTH), lds, stream, k)
-    if (s.H != 25 || (s.S != 5 && s.S != 8)) return hipErrorInvalidValue;
-    if (s.S == 5) { if (lpt == 16) SLODE_DP5_LPT(5, 16); else if (lpt == 32) SLODE_DP5_LPT(5, 32); else SLODE_DP5_LPT(5, 64); }
-    else { if (lpt == 16) SLODE_DP5_LPT(8, 16); else if (lpt == 32) SLODE_DP5_LPT(8, 32); else SLODE_DP5_LPT(8, 64); }
-#undef SLODE_DP5_LPT
-    return hipGetLastError();
+  if (s.H != 25 || (s.S != 5 && s.S != 8)) return hipErrorInvalidValue;
+  switch (s.method) {
+    case SLODE_DOPRI5: return launch_fwd<Dopri5>(s, k, lpt, stream);
+    case SLODE_BOSH3: return launch_fwd<Bosh3>(s, k, lpt, stream);
+    case SLODE_FEHLBERG2: return launch_fwd<Fehlberg2>(s, k, lpt, stream);
+    case SLODE_ADAPTIVE_HEUN: return launch_fwd<AdaptiveHeun>(s, k, lpt, stream);
+    default: return hipErrorInvalidValue;
   }
-  const int grid = (s.B + TPB - 1) / TPB;
-  const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(TPB) + (size_t)TPB * ((s.L + 3) & ~3) + (size_t)s.T);
-  if (s.H == 25 && s.S == 5) SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<5, 25>), dim3(grid), dim3(DNT), lds, stream, k);
-  else if (s.H == 25 && s.S == 8) SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<8, 25>), dim3(grid), dim3(DNT), lds, stream, k);
-  else return hipErrorInvalidValue;
+}
+
+template <class M>
+static hipError_t launch_bwd(const slode_shape& s, const DpBK& k, int grid, size_t lds, hipStream_t stream) {
+  using grp::BNT;
+  if (s.S == 5) {
+    (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<M, 5, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<M, 5, 25>), dim3(grid), dim3(BNT), lds, stream, k);
+  } else {
+    (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<M, 8, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<M, 8, 25>), dim3(grid), dim3(BNT), lds, stream, k);
+  }
   return hipGetLastError();
 }
 
@@ -1506,13 +1753,13 @@ hipError_t slode_launch_dopri5_bwd(const slode_shape& s, const slode_layout& lay
     k.zw_off = (int)big;
     const size_t lds = sizeof(float) * (fixed + big + zwf);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (s.H == 25 && s.S == 5) {
-      (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<5, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<5, 25>), dim3(grid), dim3(BNT), lds, stream, k);
-    } else if (s.H == 25 && s.S == 8) {
-      (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<8, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<8, 25>), dim3(grid), dim3(BNT), lds, stream, k);
-    } else return hipErrorInvalidValue;
+    if (s.H != 25 || (s.S != 5 && s.S != 8)) return hipErrorInvalidValue;
+    switch (s.method) {
+      case SLODE_DOPRI5: return launch_bwd<Dopri5>(s, k, grid, lds, stream);
+      case SLODE_BOSH3: return launch_bwd<Bosh3>(s, k, grid, lds, stream);
+      case SLODE_FEHLBERG2: return launch_bwd<Fehlberg2>(s, k, grid, lds, stream);
+      case SLODE_ADAPTIVE_HEUN: return launch_bwd<AdaptiveHeun>(s, k, grid, lds, stream);
+      default: return hipErrorInvalidValue;
+    }
   }
-  return hipGetLastError();
 }

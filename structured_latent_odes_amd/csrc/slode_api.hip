@@ -41,6 +41,13 @@ static int dp5_lanes(const slode_ctx* h, int B) {
   return (B + 3) / 4 <= 4 * h->num_cu ? 16 : 8;
 }
 
+static const char* method_name(int method) {
+  static const char* const names[] = {"euler", "midpoint", "rk4", "dopri5", "bosh3", "fehlberg2", "adaptive_heun"};
+  return method >= SLODE_EULER && method <= SLODE_ADAPTIVE_HEUN ? names[method] : "?";
+}
+// the adaptive methods: dopri5 and torchdiffeq's other RKAdaptiveStepsizeODESolver pairs (dopri5_kernel.hip)
+static bool is_adaptive(int method) { return slode_is_adaptive(method); }
+
 static int stages_per_step(int method) { return method == SLODE_EULER ? 1 : (method == SLODE_MIDPOINT ? 2 : 3); }
 
 static const char* check_shape(const slode_shape* s) {
@@ -67,7 +74,7 @@ static const char* check_shape(const slode_shape* s) {
       if (gr.z_off < o.z_off + o.z_dim && o.z_off < gr.z_off + gr.z_dim) return "prior groups overlap";
     }
   }
-  if (s->method < SLODE_EULER || s->method > SLODE_DOPRI5) return "unknown method";
+  if (s->method < SLODE_EULER || s->method > SLODE_ADAPTIVE_HEUN) return "unknown method (slode_method: 0 .. 6)";
   if (s->likelihood != SLODE_ALD && s->likelihood != SLODE_GAUSS) return "likelihood must be ALD or GAUSS";
   if (s->n_aux < 0 || s->n_aux > SLODE_MAX_AUX) return "n_aux out of range [0, 4]";
   if (s->n_aux > 0 && (s->U < 1 || s->U > 32)) return "U (u_hidden_dim) out of range [1, 32]";
@@ -191,7 +198,7 @@ int slode_layout_init(const slode_shape* s, slode_layout* lay) {
 
 int slode_num_stage_times(const slode_shape* s) {
   if (!s || s->T < 2) return SLODE_EINVAL;
-  if (s->method == SLODE_DOPRI5) return 1;  // adaptive: no table (a 1-element dummy keeps callers uniform)
+  if (is_adaptive(s->method)) return 1;  // adaptive: no table (a 1-element dummy keeps callers uniform)
   return stages_per_step(s->method) * (s->T - 1) + 1;
 }
 
@@ -245,14 +252,14 @@ static size_t align_up(size_t v) { return (v + 63) & ~(size_t)63; }  // in float
 // placeholder solver: nothing flows through it) -- the shape that kernel, the grid and the workspace are sized for
 static slode_shape scorer_shape(const slode_shape& s) {
   slode_shape e = s;
-  if (s.method == SLODE_DOPRI5) { e.method = SLODE_EULER; e.grad_mode = SLODE_GRAD_EXACT; }
+  if (is_adaptive(s.method)) { e.method = SLODE_EULER; e.grad_mode = SLODE_GRAD_EXACT; }
   return e;
 }
 
 static Workspace carve(slode_handle h, const slode_shape& s_in, const slode_layout& lay, void* base) {
   Workspace w{};
   const slode_shape s = scorer_shape(s_in);
-  const bool dp5 = s_in.method == SLODE_DOPRI5;
+  const bool dp5 = is_adaptive(s_in.method);
   w.dp_rows = dp5 ? slode_dopri5_rows(s) : 0;
   const int n_conv = s.T - s.K + 1, FQ = s.F * (n_conv - s.P + 1);
   w.ode_grid = ode_grid_for(h, s);
@@ -398,11 +405,13 @@ int slode_ode_solve_fwd(slode_handle h, const slode_shape* s, const slode_layout
   const char* why = check_common(h, s, lay, params);
   if (why) return fail(h, SLODE_EINVAL, "%s", why);
   if (!times || !z || !x) return fail(h, SLODE_EINVAL, "times / z / x is NULL");
-  if (s->method == SLODE_DOPRI5) {  // adaptive solve: per-trajectory controller, no stage-time table
+  if (is_adaptive(s->method)) {  // adaptive solve: per-trajectory controller, no stage-time table
     DopriRec plain{};   // (no guide sample, no records: a bare solve) -- carries the handle's choice of forward kernel
     plain.w64 = dp5_lanes(h, s->B);
+    if (!slode_dp5_lanes_ok(s->method, plain.w64))
+      return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", method_name(s->method), plain.w64);
     hipError_t e5 = slode_launch_dopri5(*s, *lay, params, times, z, x, (hipStream_t)stream, &plain);
-    if (e5 == hipErrorInvalidValue) return fail(h, SLODE_EINVAL, "dopri5 kernel is instantiated for (S,H) in {(5,25),(8,25)}");
+    if (e5 == hipErrorInvalidValue) return fail(h, SLODE_EINVAL, "%s kernel is instantiated for (S,H) in {(5,25),(8,25)}", method_name(s->method));
     HIP_TRY(h, e5);
     return SLODE_OK;
   }
@@ -424,7 +433,8 @@ int slode_ode_solve_bwd(slode_handle h, const slode_shape* s, const slode_layout
   const char* why = check_common(h, s, lay, params);
   if (why) return fail(h, SLODE_EINVAL, "%s", why);
   if (!times || !stage_t || !z || !g_x || !g_z || !grads || !workspace) return fail(h, SLODE_EINVAL, "a required pointer is NULL");
-  if (s->method == SLODE_DOPRI5) return fail(h, SLODE_EINVAL, "dopri5 is forward-only (slode_ode_solve_fwd); gradients need a fixed-grid method");
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "%s is forward-only (slode_ode_solve_fwd); gradients need a fixed-grid method", method_name(s->method));
   Workspace w = carve(h, *s, *lay, workspace);
   if (workspace_bytes < w.bytes) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, w.bytes);
   OdeLaunch a{};
@@ -492,11 +502,14 @@ static int elbo_step_impl(slode_handle h, const slode_shape* s, const slode_layo
       }
   }
   if (s->n_groups > 0 && !u && phase != 2) return fail(h, SLODE_EINVAL, "u is NULL but the shape has conditional prior groups");
-  const bool dp5 = !aux_mode && s->method == SLODE_DOPRI5;
+  const bool dp5 = !aux_mode && is_adaptive(s->method);
   if (dp5 && !(s->H == 25 && (s->S == 5 || s->S == 8)))
-    return fail(h, SLODE_EINVAL, "dopri5 kernels are instantiated for (S,H) in {(5,25),(8,25)}");
+    return fail(h, SLODE_EINVAL, "%s kernels are instantiated for (S,H) in {(5,25),(8,25)}", method_name(s->method));
   if (dp5 && (s->B > 65536 || h->ode_loop))
-    return fail(h, SLODE_EINVAL, "the dopri5 ELBO step takes at most 65,536 trajectories per call");
+    return fail(h, SLODE_EINVAL, "the %s ELBO step takes at most 65,536 trajectories per call", method_name(s->method));
+  if (dp5 && !slode_dp5_lanes_ok(s->method, dp5_lanes(h, s->B)))
+    return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", method_name(s->method),
+                dp5_lanes(h, s->B));
   Workspace w = carve(h, *s, *lay, workspace);
   if (workspace_bytes < w.bytes) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, w.bytes);
   hipStream_t st = (hipStream_t)stream;
@@ -898,7 +911,8 @@ int slode_label_heads(slode_handle h, const slode_shape* s, const slode_layout* 
 int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_layout* lay, const void* workspace, size_t workspace_bytes,
                              int* counts, void* stream) {
   if (!h) return SLODE_EINVAL;
-  if (!s || !lay || !workspace || !counts || s->method != SLODE_DOPRI5) return fail(h, SLODE_EINVAL, "slode_dopri5_step_counts: dopri5 shape, workspace and output required");
+  if (!s || !lay || !workspace || !counts || !is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "slode_dopri5_step_counts: adaptive-method shape, workspace and output required");
   if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_EINVAL, "slode_dopri5_step_counts: workspace too small");
   const Workspace w = carve(h, *s, *lay, const_cast<void*>(workspace));
   HIP_TRY(h, hipMemcpyAsync(counts, w.dp_nrec, sizeof(int) * (size_t)s->B, hipMemcpyDeviceToDevice, (hipStream_t)stream));

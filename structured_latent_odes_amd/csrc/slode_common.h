@@ -554,6 +554,10 @@ struct DopriRec { const float *loc, *scale, *eps; float* z_out; float* rec; int*
 size_t slode_dopri5_tab_floats(const slode_shape& s);
 int slode_dopri5_kmax(const slode_shape& s);
 int slode_dopri5_rows(const slode_shape& s);
+int slode_dp5_lanes_ok(int method, int lpt);   // 1: the forward kernels of `method` are instantiated for lpt lanes per trajectory
+__host__ __device__ static inline bool slode_is_adaptive(int method) {
+  return method == SLODE_DOPRI5 || method == SLODE_BOSH3 || method == SLODE_FEHLBERG2 || method == SLODE_ADAPTIVE_HEUN;
+}
 hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const float* z,
                                float* x, hipStream_t stream, const DopriRec* rec = nullptr);
 hipError_t slode_launch_dopri5_bwd(const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const DopriRec& rec,

@@ -51,13 +51,13 @@ class ModelSpec:
     filter_size: int = 10
     pool_size: int = 5
     cnn_hidden_dim: int = 50
-    solver: str = "midpoint"
+    solver: str = "midpoint"   # _lib.METHODS: euler / midpoint / rk4 (fixed grid), dopri5 / bosh3 / fehlberg2 / adaptive_heun (adaptive)
     quantile_diff: float = 0.475
     aux_heads: List[AuxHead] = field(default_factory=list)
     labels_in_main: bool = False   # proc: the main model also scores the label heads (mechanistic_proc.py:145-146)
     u_hidden_dim: int = 25
     aux_mult: float = 46.0
-    rtol: float = 1e-7      # dopri5 only (torchdiffeq defaults)
+    rtol: float = 1e-7      # adaptive methods only (torchdiffeq defaults)
     atol: float = 1e-9
     # "exact": gradient of the discrete scheme (== adjoint_solver=False); "reference_adjoint": torchdiffeq.odeint_adjoint's backward,
     # the reference default (config.adjoint_solver = True; models/blackbox_ode.py:40-42) -- no gradient to z through the dynamics
@@ -223,10 +223,10 @@ class Engine:
         d = times[1:] - times[:-1]
         if not (bool((d > 0).all()) or bool((d < 0).all())):    # torchdiffeq odeint's own precondition (misc._check_timelike)
             raise ValueError("t must be strictly increasing or decreasing")
-        if self.spec.solver == "dopri5" and not bool((d > 0).all()):
+        if self.spec.solver in L.ADAPTIVE and not bool((d > 0).all()):
             # torchdiffeq integrates a decreasing grid in s = -t; the adaptive kernels here only walk forward in time
             # (dopri5_kernel.hip: dt > 0, outputs emitted while tj <= t1) and answer such a grid with NaN trajectories
-            raise ValueError("solver='dopri5' needs a strictly increasing time grid (decreasing grids: fixed-grid solvers only)")
+            raise ValueError("solver=%r needs a strictly increasing time grid (decreasing grids: fixed-grid solvers only)" % self.spec.solver)
         n = int(self.lib.slode_num_stage_times(C.byref(self.shape(1))))
         st = torch.empty(n, dtype=torch.float32, device=self.device)
         _check(self.lib, self.handle, self.lib.slode_stage_times(self.handle, C.byref(self.shape(1)), self._p(times), self._p(st), self._stream()))
@@ -314,7 +314,8 @@ class Engine:
         return out
 
     def dopri5_step_counts(self, B: int) -> torch.Tensor:
-        """Accepted steps per trajectory of the last dopri5 training step at batch size B (diagnostic; int32 [B])."""
+        """Accepted steps per trajectory of the last adaptive-method (dopri5, bosh3, fehlberg2, adaptive_heun) training step at batch
+        size B (diagnostic; int32 [B]; -1: 20,000 attempts exhausted, > slode_dopri5_kmax: record overflow)."""
         out = torch.empty(B, dtype=torch.int32, device=self.device)
         w = self.workspace(B)
         _check(self.lib, self.handle, self.lib.slode_dopri5_step_counts(

@@ -9,6 +9,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .. import _lib as L
 from ..engine import ModelSpec
 
 _O = "decoder.ode_model."
@@ -105,7 +106,7 @@ class OdeModel(nn.Module):
             T = int(self.times.numel())
             spec = ModelSpec("ode_only", True, 3, self.latent_dim, self.latent_dim, 0, [], ode_state_dim=self.ode_state_dim,
                              ode_hidden_dim=self.ode_hidden_dim, solver=self.solver,
-                             grad_mode="reference_adjoint" if (self.adjoint_solver and self.solver != "dopri5") else "exact")
+                             grad_mode="reference_adjoint" if (self.adjoint_solver and self.solver not in L.ADAPTIVE) else "exact")
             if T < 14:
                 spec.filter_size, spec.pool_size = 1, 1   # the (unused) encoder segment must still be a valid shape
             named = self._named_for_binding()
