@@ -291,11 +291,9 @@ hipError_t slode_launch_reduce(const ReduceLaunch& a_in, hipStream_t stream) {
   k.lin_w_off = a.folded ? a.lay.conv_w : a.lay.lin_w;
   k.grads = a.grads; k.loss_out = a.loss_out; k.n_params = a.lay.n_params; k.zero_rest = a.zero_rest;
   int n = a.grads ? a.lay.n_params : 1;
-  if (a.adam_p && a.grads) {
-    AdamHost ah{a.adam_p, a.adam_m, a.adam_v, a.adam_lr, a.adam_b1, a.adam_b2, a.adam_eps, a.adam_step, a.adam_n};
-    ah.lo2 = a.adam_lo2; ah.hi2 = a.adam_hi2; ah.delta2 = a.adam_delta2;
-    k.ad = make_adamk(&ah);
-    k.n_total = a.adam_n > a.lay.n_params ? (int)a.adam_n : a.lay.n_params;
+  if (a.adam.p && a.grads) {
+    k.ad = make_adamk(&a.adam);
+    k.n_total = a.adam.n > a.lay.n_params ? (int)a.adam.n : a.lay.n_params;
     n = k.n_total;
   }
   SLODE_LAUNCH("reduce", reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, k);

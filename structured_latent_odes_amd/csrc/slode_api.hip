@@ -118,8 +118,8 @@ int slode_create(slode_handle* out, int device_id) {
   // (profiles/r04_c_ab*_fold_next_*.log)
   c->fold_on = getenv("SLODE_FOLD_NEXT") ? atoi(getenv("SLODE_FOLD_NEXT")) : 0;
   c->fold_valid = 0; c->fold_tmajor = 0; c->fold_ws = nullptr; c->fold_params = nullptr; c->fold_gen = 0;
-  // (measured arms: 16 / 32 / 64 lanes per trajectory give the same bits and the same time, profiles/r04_f_ab11_*: the shipped form stays 8)
-  c->dp5_w64 = getenv("SLODE_DP5_LPT") ? atoi(getenv("SLODE_DP5_LPT")) : 0;   // 0: chosen per batch (dp5_lanes)
+  // (measured arms: 16 / 32 / 64 lanes per trajectory give the same bits and the same time, profiles/r04_f_ab11_*)
+  c->dp5_w64 = getenv("SLODE_DP5_LPT") ? atoi(getenv("SLODE_DP5_LPT")) : 0;   // 0: by batch size (dp5_lanes: 16 while B / 4 <= 4 x CUs, else 8)
   c->chain_resident = 0; memset(c->chain_resident_sig, 0, sizeof(c->chain_resident_sig));
   // diagnostics and test hooks: the environment is read here, once per handle, never at launch time
   c->no_fold = getenv("SLODE_NO_FOLD") != nullptr;   // force the layer-by-layer encoder kernels
@@ -395,7 +395,9 @@ int slode_encoder_conv_bwd(slode_handle h, const slode_shape* s, const slode_lay
   hipError_t e = slode_launch_enc_bwd(a, (hipStream_t)stream);
   if (e == hipErrorInvalidValue) return fail(h, SLODE_EINVAL, "unsupported encoder shape C=%d K=%d T=%d", s->C, s->K, s->T);
   HIP_TRY(h, e);
-  ReduceLaunch r{*s, *lay, nullptr, 0, 0, w.small_slabs, w.small_stride, w.small_grid, w.lin_slabs, w.lin_splitk, grads, nullptr, 0, nullptr, w.small_part, 0};
+  ReduceLaunch r{};
+  r.s = *s; r.lay = *lay; r.small_slabs = w.small_slabs; r.small_stride = w.small_stride; r.small_n = w.small_grid; r.small_part = w.small_part;
+  r.lin_slabs = w.lin_slabs; r.lin_n = w.lin_splitk; r.grads = grads;
   HIP_TRY(h, slode_launch_reduce(r, (hipStream_t)stream));
   return SLODE_OK;
 }
@@ -444,7 +446,8 @@ int slode_ode_solve_bwd(slode_handle h, const slode_shape* s, const slode_layout
   hipError_t e = slode_launch_ode(a, (hipStream_t)stream, h->err, sizeof(h->err));
   if (e == hipErrorInvalidValue) return SLODE_EINVAL;
   HIP_TRY(h, e);
-  ReduceLaunch r{*s, *lay, w.ode_slabs, w.ode_stride, w.ode_grid, nullptr, 0, 0, nullptr, 0, grads, nullptr, 0, w.ode_part, nullptr, 0};
+  ReduceLaunch r{};
+  r.s = *s; r.lay = *lay; r.ode_slabs = w.ode_slabs; r.ode_stride = w.ode_stride; r.ode_n = w.ode_grid; r.ode_part = w.ode_part; r.grads = grads;
   HIP_TRY(h, slode_launch_reduce(r, (hipStream_t)stream));
   return SLODE_OK;
 }
@@ -467,332 +470,335 @@ int slode_decode_heads_bwd(slode_handle h, const slode_shape* s, const slode_lay
   return SLODE_OK;
 }
 
-struct AdamArgs { float *p, *m, *v; float lr, b1, b2, eps; int64_t step, n; };
+}  // extern "C"
 
-static int elbo_step_impl(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
-                          const float* stage_t, const float* obs, const int64_t obs_strides[3], const float* u, const float* eps,
-                          float* loss_out, float* grads, float* x_out, float* z_out, void* workspace, size_t workspace_bytes,
-                          void* stream, const AdamArgs* adam, int aux_mode = 0, const LabelSrc* labels = nullptr, int phase = 0,
-                          float* payload = nullptr) {
-  // phase 0: the whole step.  Data parallel with the small payload (slode_grad_partial / slode_grad_apply): phase 1 = everything up to the
-  // split-K products, then the partials packed into `payload` = [G | G_loc | G_ls | loss | ODE-half row]; phase 2 = chain rule + tail
-  // (+ Adam) from the (all-reduced) payload.
-  const char* why = check_common(h, s, lay, params);
-  if (why) return fail(h, SLODE_EINVAL, "%s", why);
-  if (phase == 2) {
-    if (!obs_strides || !payload || !grads || !workspace) return fail(h, SLODE_EINVAL, "a required pointer is NULL");
-  } else if ((!aux_mode && (!times || !stage_t)) || !obs || !obs_strides || (!loss_out && phase == 0) || !workspace || (phase == 1 && !payload))
-    return fail(h, SLODE_EINVAL, "a required pointer is NULL");
-  // eps == NULL: this call draws the guide's noise inside its kernels -- call number rng_counter of the handle's Philox stream
-  RngK rng{};
-  if (!eps && phase != 2) rng = rng_of(h, h->rng_counter++);
-  LabelSrc lab{};
-  if (labels) lab = *labels;
-  if (lab.n > 0) u = u ? u : lab.p[0];   // (non-null = "labels present"; the kernels read through the accessor)
-  if (aux_mode && (s->n_aux < 1 || (!u && phase != 2))) return fail(h, SLODE_EINVAL, "the auxiliary loss needs label heads (n_aux >= 1) and labels u");
-  if (aux_mode) {
-    // aux_kernel only: every head owns the latent-gradient slots of the dims it reads (one writer per slot).  The reference's heads read
-    // disjoint groups (z_iext / z_rtpr, z_aR / z_aS / z_C12 / z_C6, ...); the main step, the solves and the eval-side entry points
-    // have no such limit and are not affected.  Heads wider than 16 dims take the kernel's wide instantiation.
-    for (int a = 0; a < s->n_aux; ++a)
-      for (int a2 = 0; a2 < a; ++a2) {
-        const slode_aux &x = s->aux[a], &o = s->aux[a2];
-        if (x.z_off < o.z_off + o.z_dim && o.z_off < x.z_off + x.z_dim)
-          return fail(h, SLODE_EINVAL, "slode_aux_step: label heads %d and %d read overlapping latent ranges", a2, a);
-      }
-  }
-  if (s->n_groups > 0 && !u && phase != 2) return fail(h, SLODE_EINVAL, "u is NULL but the shape has conditional prior groups");
-  const bool dp5 = !aux_mode && is_adaptive(s->method);
-  if (dp5 && !(s->H == 25 && (s->S == 5 || s->S == 8)))
-    return fail(h, SLODE_EINVAL, "%s kernels are instantiated for (S,H) in {(5,25),(8,25)}", method_name(s->method));
-  if (dp5 && (s->B > 65536 || h->ode_loop))
-    return fail(h, SLODE_EINVAL, "the %s ELBO step takes at most 65,536 trajectories per call", method_name(s->method));
-  if (dp5 && !slode_dp5_lanes_ok(s->method, dp5_lanes(h, s->B)))
-    return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", method_name(s->method),
-                dp5_lanes(h, s->B));
-  Workspace w = carve(h, *s, *lay, workspace);
-  if (workspace_bytes < w.bytes) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, w.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  const bool bwd = grads != nullptr || phase == 1;
-  ClockScope clock_scope(h, true);
+// ---- the ELBO step: one call description, four stages.  Data parallel (slode_grad_partial / slode_grad_apply): STEP_PARTIAL = up to the
+// split-K products, packed into `payload` = [G | G_loc | G_ls | loss | ODE-half row]; STEP_APPLY = chain rule + tail (+ Adam) from it.
+enum StepPhase { STEP_WHOLE = 0, STEP_PARTIAL = 1, STEP_APPLY = 2 };
+struct StepCall {
+  int kind = SLODE_SVI_MAIN, phase = STEP_WHOLE;   // kind SLODE_SVI_MAIN: the ELBO; SLODE_SVI_AUX: the auxiliary label-head loss
+  const float *params = nullptr, *times = nullptr, *stage_t = nullptr, *obs = nullptr, *u = nullptr, *eps = nullptr;
+  const int64_t* obs_strides = nullptr; void* workspace = nullptr; size_t workspace_bytes = 0; hipStream_t stream = nullptr;
+  float *loss_out = nullptr, *grads = nullptr, *x_out = nullptr, *z_out = nullptr, *payload = nullptr;
+  AdamHost adam{}; LabelSrc lab{};   // fused Adam (adam_args; adam.p == nullptr: none); label tensors one by one (batch_labels; n == 0: u)
+};
+struct Step {   // what the stages share, worked out once by step_setup
+  slode_handle h; const slode_shape& s; const slode_layout& lay; const StepCall& c;
+  bool aux = false, dp5 = false, bwd = false, folded = false, t_major = false;
+  RngK rng{}; const float* u = nullptr; Workspace w{};
+};
+// the slab rows the tail reduces: n rows of [loss | flat elements [part_lo, part_hi)]; rows [0, zr_rows) carry nothing in slab columns
+// [zr_lo, zr_hi) (the dopri5 scorer's rows: Stage1::zr_*)
+struct SlabRows { int n, part_lo, part_hi, zr_rows = 0, zr_lo = 0, zr_hi = 0; };
 
-  // Folded encoder (encoder_fused.hip) when every trajectory's C*T observations are one dense block; else layer by layer.
-  const long long CT = (long long)s->C * s->T;
-  const bool t_major = obs_strides[1] == 1 && obs_strides[2] == s->C;          // [B,T,C] contiguous (cvs / challenge batches)
-  const bool c_major = obs_strides[2] == 1 && obs_strides[1] == s->T;          // [B,C,T] contiguous (proc batches)
-  const bool folded = !h->no_fold && obs_strides[0] == CT && (t_major || c_major) && (s->C == 3 || s->C == 4);
-  FoldLaunch fl{};
-  hipError_t e;
-  bool enc_fused = false;
-  if (phase != 0 && !folded)
-    return fail(h, SLODE_EINVAL, "slode_grad_partial / slode_grad_apply need the folded encoder path (dense [B,T,C] or [B,C,T] observations, C in {3,4})");
-  if (phase == 2) {   // no forward work: the fold launch of phase 1 left w' / rowsum / the zeroed arrival counters in this workspace
-    fl.s = *s; fl.lay = *lay; fl.params = params; fl.x = obs; fl.t_major = t_major ? 1 : 0;
-    fl.weff = w.weff; fl.rowsum = w.rowsum; fl.wprime = w.wprime; fl.beff = w.beff; fl.loc = w.loc; fl.scale = w.scale; fl.hid = w.hid;
-    fl.g_loc = w.g_loc; fl.g_scale = w.g_scale; fl.g_pre = w.g_pre; fl.small_slabs = w.small_slabs; fl.small_stride = w.small_stride;
-    fl.g_lin_w = grads + lay->lin_w; fl.conv_slabs = w.conv_slabs; fl.counter = w.counter;
-  } else if (folded) {
-    fl.s = *s; fl.lay = *lay; fl.params = params; fl.x = obs; fl.t_major = t_major ? 1 : 0;
-    fl.weff = w.weff; fl.rowsum = w.rowsum; fl.wprime = w.wprime; fl.beff = w.beff; fl.loc = w.loc; fl.scale = w.scale; fl.hid = w.hid;
-    fl.g_loc = w.g_loc; fl.g_scale = w.g_scale; fl.g_pre = w.g_pre; fl.small_slabs = w.small_slabs; fl.small_stride = w.small_stride;
-    fl.gslabs = w.gslabs; fl.n_gslabs = w.gsplit; fl.g_lin_w = grads ? grads + lay->lin_w : nullptr; fl.conv_slabs = w.conv_slabs;
-    fl.counter = w.counter;
-    fl.sigtab = w.sigtab;   // (the auxiliary step does not read it, but the fold it leaves in the workspace serves the next main step too)
-    // the loop-free ODE kernel of the metric shape runs the encoder forward of its own trajectories (ode_kernel.hip, ENCF): fold only
-    enc_fused = !aux_mode && !dp5 && bwd && h->enc_fuse && !h->ode_loop && !h->ode_generic && h->ode_alg == 0 && (h->ode_pack == 0 || h->ode_pack >= 10) && !x_out &&
-                slode_ode_can_fuse_encoder(*s, bwd, w.ode_grid);
-    fl.skip_enc = enc_fused ? 1 : 0;
-    // The previous weight-updating step on this (workspace, params) left W_eff / b_eff / rowsum / w' / the likelihood-scale table of the
-    // CURRENT weights behind (enc_chain_kernel, FOLD-NEXT): no fold launch then.  Anything else -- first step, another workspace, weights
-    // changed outside this handle (slode_fold_invalidate) -- folds here, which also zeroes the arrival counters.
-    const bool have_fold = h->fold_on && h->fold_valid && h->fold_ws == workspace && h->fold_params == (const void*)params &&
-                           h->fold_tmajor == (t_major ? 1 : 0);
-    if (have_fold && enc_fused) {
-      // (nothing to launch)
-    } else if (have_fold) {
-      fl.fold_skip = 1;                  // the encoder forward launch alone
-      e = slode_launch_fold_fwd(fl, st);
-      HIP_TRY(h, e);
-    } else {
-      e = slode_launch_fold_fwd(fl, st);
-      HIP_TRY(h, e);
-      h->fold_gen = 0;                   // (the fold launch zeroed the in-launch fold's arrival counter)
-      h->fold_valid = 1; h->fold_ws = workspace; h->fold_params = params; h->fold_tmajor = t_major ? 1 : 0;
-    }
-  } else {
-    EncLaunch ef{*s, *lay, params, obs, obs_strides[0], obs_strides[1], obs_strides[2], w.loc, w.scale, w.pooled, w.hid};
-    e = slode_launch_enc_fwd(ef, st);
-    if (e == hipErrorInvalidValue) return fail(h, SLODE_EINVAL, "unsupported encoder shape C=%d K=%d T=%d", s->C, s->K, s->T);
-    HIP_TRY(h, e);
-  }
-
-  int n_slabs = w.ode_grid;
-  int part_lo = lay->ode_begin, part_hi = lay->n_params;   // flat range the slab rows carry (after the loss slot)
-  int zr_rows = 0, zr_lo = 0, zr_hi = 0;                   // rows [0, zr_rows) carry nothing in slab columns [zr_lo, zr_hi) (dopri5 scorer)
-  if (phase == 2) {
-    if (aux_mode) { part_lo = lay->aux_w1[0]; part_hi = lay->cstd; }
-  } else if (aux_mode) {
-    // one workgroup per trajectory up to 2,048 of them, then a loop; on the folded path the kernel also runs the encoder-head backward and
-    // its slab rows carry only the label-head range (the fused tail below reduces exactly that)
-    AuxLaunch al{*s, *lay, params, w.loc, w.scale, eps, u, w.g_loc, w.g_scale, w.ode_slabs, w.ode_stride,
-                 w.ode_grid < 2048 ? w.ode_grid : 2048, bwd ? 1 : 0};
-    al.rng = rng; al.lab = lab;
-    // compact rows carry the flat range [aux_w1[0], cstd): every label-head tensor must lie inside it (a caller-made layout may not)
-    bool aux_contig = lay->aux_w1[0] <= lay->cstd;
-    for (int a = 0; a < s->n_aux; ++a) {
-      const int hi = s->aux[a].kind == SLODE_AUX_EXPEXP ? lay->aux_c[a] + 1 : lay->aux_b2[a] + s->aux[a].u_dim;
-      aux_contig = aux_contig && lay->aux_w1[a] >= lay->aux_w1[0] && hi <= lay->cstd;
-    }
-    if (bwd && folded && !aux_contig) return fail(h, SLODE_EINVAL, "slode_aux_step: the label heads must lie in [aux_w1[0], cstd) of the layout (slode_layout_init's order)");
-    if (bwd && folded) {
-      al.compact = 1; al.enc_hid = w.hid; al.g_pre = w.g_pre; al.glat = w.glat; al.g_loc = nullptr; al.g_scale = nullptr;
-      part_lo = lay->aux_w1[0]; part_hi = lay->cstd;
-    }
-    n_slabs = al.grid;
-    HIP_TRY(h, slode_launch_aux(al, st));
-  } else {
-    OdeLaunch a{};
-    a.s = scorer_shape(*s); a.lay = *lay; a.params = params; a.times = times; a.stage_t = dp5 ? times : stage_t;
-    a.obs = obs; a.sb = obs_strides[0]; a.sc = obs_strides[1]; a.st = obs_strides[2];
-    a.u = u; a.eps = eps; a.loc = w.loc; a.scale = w.scale; a.x_out = x_out; a.z_out = z_out;
-    a.g_loc = w.g_loc; a.g_scale = w.g_scale; a.slabs = w.ode_slabs; a.slab_stride = w.ode_stride; a.grid = w.ode_grid;
-    a.backward = bwd ? 1 : 0; a.with_ll = 1;
-    a.rng = rng; a.lab = lab;
-    a.sigtab = folded ? w.sigtab : nullptr;   // written by the fold launch above
-    a.force_loop = h->ode_loop; a.force_generic = h->ode_generic; a.alg = h->ode_alg; a.pack = h->ode_pack;
-    if (bwd && folded) { a.enc_hid = w.hid; a.g_pre = w.g_pre; a.glat = w.glat; a.g_loc = nullptr; a.g_scale = nullptr; }
-    if (enc_fused) { a.enc_fuse = 1; a.enc_weff = w.weff; a.enc_beff = w.beff; a.enc_hid_out = w.hid; }
-    // ext_skip assumes slode_layout_init's order: the ten solver-side tensors tile [init_w1, dyn_bd + S) exactly and nothing else (prior
-    // nets, decoder heads, label heads, constant_std) lies inside; a caller-made layout that does not keeps the zeros written and read
-    bool solver_contig = lay->init_b1 == lay->init_w1 + s->H * s->L && lay->init_w2 == lay->init_b1 + s->H && lay->init_b2 == lay->init_w2 + s->S * s->H &&
-                         lay->dyn_wh == lay->init_b2 + s->S && lay->dyn_bh == lay->dyn_wh + s->H * (1 + s->L) && lay->dyn_wg == lay->dyn_bh + s->H &&
-                         lay->dyn_bg == lay->dyn_wg + s->S * s->H && lay->dyn_wd == lay->dyn_bg + s->S && lay->dyn_bd == lay->dyn_wd + s->S * s->H;
-    {
-      const int lo = lay->init_w1, hi = lay->dyn_bd + s->S;
-      auto inside = [&](int off) { return off >= lo && off < hi; };
-      for (int g = 0; g < s->n_groups; ++g)
-        solver_contig = solver_contig && !inside(lay->ploc_w[g]) && !inside(lay->ploc_b[g]) && !inside(lay->pls_w[g]) && !inside(lay->pls_b[g]);
-      for (int q = 0; q < (s->likelihood == SLODE_GAUSS ? 1 : 3); ++q) solver_contig = solver_contig && !inside(lay->head_w[q]);
-      for (int a2 = 0; a2 < s->n_aux; ++a2)
-        solver_contig = solver_contig && !inside(lay->aux_w1[a2]) && !inside(lay->aux_b1[a2]) && !inside(lay->aux_w2[a2]) && !inside(lay->aux_b2[a2]) &&
-                        (s->aux[a2].kind != SLODE_AUX_EXPEXP || (!inside(lay->aux_w3[a2]) && !inside(lay->aux_b3[a2]) && !inside(lay->aux_c[a2])));
-      solver_contig = solver_contig && !inside(lay->cstd);
-    }
-    if (dp5 && bwd && folded && solver_contig && w.ode_grid + w.dp_rows > 2 * SLODE_REDUCE_GROUPS) {
-      // the scorer's rows carry nothing in the solver-side range [init net | dynamics] (the reverse sweep's rows do): the scorer does not
-      // write those zeros and stage 1 of the fused tail (the only reader of the rows) does not read them
-      a.ext_skip = 1;
-      zr_rows = w.ode_grid; zr_lo = 1 + (lay->init_w1 - lay->ode_begin); zr_hi = 1 + (lay->dyn_bd + s->S - lay->ode_begin);
-    }
-    if (dp5) {
-      // adaptive solve (per-trajectory controller, accepted steps recorded) -> ONE scorer pass (loss terms, dLoss/dx, every gradient
-      // that does not flow through the solver, its own share of the latent gradient into g_loc / g_scale) -> reverse mode over the
-      // records: solver-side gradients as extra slab rows, the latent gradient through the solver added to g_loc / g_scale -> the
-      // unfused encoder tail below
-      DopriRec rc{w.loc, w.scale, eps, w.dp_z, bwd ? w.dp_rec : nullptr, w.dp_nrec, w.dp_kmax};
-      rc.w64 = dp5_lanes(h, s->B);
-      const bool hand_over = bwd && (rc.w64 == 8 || rc.w64 == 16);   // forward workgroups of sixteen trajectories, as the reverse sweep's
-      rc.tabs = hand_over ? w.dp_tabs : nullptr;
-      if (rng.on) {   // the forward kernel draws the noise once and materialises it: the scorer and the reverse sweep read the same values
-        rc.rng = rng; rc.eps_out = w.dp_eps;
-        a.rng = RngK{}; a.eps = w.dp_eps; eps = w.dp_eps;
-      }
-      HIP_TRY(h, slode_launch_dopri5(*s, *lay, params, times, nullptr, w.dp_x, st, &rc));
-      a.x_ext = w.dp_x;
-      if (bwd) {
-        a.gx_out = w.dp_gx;
-        a.enc_hid = nullptr; a.g_pre = nullptr; a.glat = nullptr; a.g_loc = w.g_loc; a.g_scale = w.g_scale;
-        n_slabs = w.ode_grid + w.dp_rows;
-      }
-    }
-    e = slode_launch_ode(a, st, h->err, sizeof(h->err));
-    if (e == hipErrorInvalidValue) return SLODE_EINVAL;
-    HIP_TRY(h, e);
-    if (dp5 && bwd) {
-      DopriRec rc{w.loc, w.scale, eps, w.dp_z, w.dp_rec, w.dp_nrec, w.dp_kmax};
-      { const int l5 = dp5_lanes(h, s->B); rc.tabs = (l5 == 8 || l5 == 16) ? w.dp_tabs : nullptr; }
-      HIP_TRY(h, slode_launch_dopri5_bwd(*s, *lay, params, times, rc, w.dp_gx, w.g_loc, w.g_scale, w.ode_slabs + (size_t)w.ode_grid * w.ode_stride,
-                                         w.ode_stride, s->grad_mode == SLODE_GRAD_REFERENCE_ADJOINT ? 1 : 0, w.dp_snap, st,
-                                         folded ? w.hid : nullptr, folded ? w.g_pre : nullptr, folded ? w.glat : nullptr));
-    }
-  }
-
-  if (phase != 0 && !(bwd && folded)) return fail(h, SLODE_EINVAL, "the payload split needs a backward step on the folded encoder path");
-  if (bwd && folded) {
-    // Fused tail.  The ODE kernel (auxiliary step: the aux kernel; dopri5: its reverse sweep) has already run the encoder heads + tanh
-    // backward (g_pre, glat): two launches remain --
-    // split-K MFMA GEMMs (+ rider blocks: stage 1 of the ODE-slab reduction), chain rule, one final reduction (+ Adam).
-    AdamHost ah{};
-    if (adam) {
-      ah = AdamHost{adam->p, adam->m, adam->v, adam->lr, adam->b1, adam->b2, adam->eps, adam->step, adam->n};
-      ah.lo2 = h->adam_lo2; ah.hi2 = h->adam_hi2; ah.delta2 = h->adam_delta2;
-    }
-    const float* ode_part = nullptr;
-    int ode_pn = 0;
-    const PayloadMap pm = payload_map(*s, part_hi - part_lo);
-    if (phase != 2)
-      HIP_TRY(h, slode_launch_gemm_tail(w.g_pre, obs, w.gslabs, s->Hc, (int)CT, w.glat, w.hid, w.gslabs2, w.gslabs3, s->L, s->B, w.gsplit,
-                                        w.ode_slabs, w.ode_stride, n_slabs, (part_hi - part_lo) + 1, w.ode_part, &ode_part, &ode_pn, st,
-                                        zr_rows, zr_lo, zr_hi));
-    if (phase == 1) {   // split-K partials and partial slab rows, summed in fixed order, into the contiguous payload
-      HIP_TRY(h, slode_launch_pack_payload(w.gslabs, w.gslabs2, w.gslabs3, w.gsplit, s->Hc, (int)CT, s->L, ode_part, w.ode_stride, ode_pn,
-                                           (part_hi - part_lo) + 1, payload, pm.g_loc, pm.g_ls, pm.ode, pm.total, st));
-      return SLODE_OK;
-    }
-    TailK tl{};
-    tl.gslabs = w.gslabs; tl.gslabs_loc = w.gslabs2; tl.gslabs_ls = w.gslabs3; tl.conv_slabs = w.conv_slabs;
-    tl.ode_part = ode_part; tl.ode_stride = w.ode_stride; tl.ode_n = ode_pn; tl.loss_out = loss_out;
-    int gsplit_eff = w.gsplit;
-    if (phase == 2) {   // the (reduced) payload stands for ONE split / ONE partial row
-      fl.gslabs = payload; fl.n_gslabs = 1; gsplit_eff = 1;
-      tl.gslabs = payload; tl.gslabs_loc = payload + pm.g_loc; tl.gslabs_ls = payload + pm.g_ls;
-      tl.ode_part = payload + pm.ode; tl.ode_stride = 0; tl.ode_n = 1;
-    }
-    tl.part_lo = part_lo; tl.part_hi = part_hi;
-    tl.gsplit = gsplit_eff; tl.Hc = s->Hc; tl.L = s->L; tl.CT = (int)CT; tl.n_cv = s->F * s->C * s->K + s->F;
-    tl.conv_w = lay->conv_w; tl.lin_w = lay->lin_w; tl.lin_b = lay->lin_b; tl.zloc_w = lay->zloc_w; tl.zloc_b = lay->zloc_b;
-    tl.zls_w = lay->zls_w; tl.zls_b = lay->zls_b; tl.ode_begin = lay->ode_begin; tl.n_params = lay->n_params;
-    tl.n_total = (adam && adam->n > lay->n_params) ? (int)adam->n : lay->n_params;
-    tl.grads = grads; tl.ad = make_adamk(adam ? &ah : nullptr); tl.counter = w.counter;
-    // FOLD-NEXT: this launch updates the weights (Adam inside) => it also folds them for the next step, provided every block of the launch
-    // is resident at once (the blocks wait for each other) and the handle's W_eff bookkeeping covers this workspace
-    int n_chain = 0;
-    int nblk = slode_chain_blocks(*s, tl.n_total, lay->lin_b, &n_chain);
-    int resident = 0;
-    if (h->fold_on && adam) {   // (the occupancy query is asked once per shape and handle)
-      const int sig[8] = {s->T, s->C, s->F, s->K, s->P, s->Hc, s->L, lay->n_params};
-      if (memcmp(sig, h->chain_resident_sig, sizeof(sig)) != 0) {
-        h->chain_resident = slode_chain_resident_blocks(*s, h->num_cu);
-        memcpy(h->chain_resident_sig, sig, sizeof(sig));
-      }
-      resident = h->chain_resident;
-    }
-    tl.n_riders = 0;
-    if (nblk > resident && resident > n_chain && nblk - n_chain <= 4 * (resident - n_chain)) {   // fewer, looping riders: the grid fits
-      tl.n_riders = resident - n_chain;
-      nblk = resident;
-    }
-    const bool fold_next = h->fold_on && adam && adam->p == params && nblk <= resident && h->fold_valid && h->fold_ws == workspace &&
-                           h->fold_params == (const void*)params;
-    tl.fold_next = fold_next ? 1 : 0;
-    if (!fold_next) tl.n_riders = 0;
-    tl.done = w.counter; tl.done_target = 0; tl.cstd_off = lay->cstd; tl.gauss = s->likelihood == SLODE_GAUSS ? 1 : 0;
-    tl.sigtab = w.sigtab;
-    if (fold_next) {
-      ++h->fold_gen;
-      tl.done_target = h->fold_gen;   // (the generation: every counter's target is gen x its number of arrivals per launch)
-      if (tl.n_riders == 0) tl.n_riders = nblk - n_chain;
-    }
-    fl.tail = &tl;
-    if (adam) h->fold_valid = fold_next ? 1 : 0;   // the weights change now: what the workspace holds is current only if this launch re-folds
-    HIP_TRY(h, slode_launch_fold_chain(fl, st));   // + rider blocks and the last-block conv reduction: the flat gradient is complete
-  } else if (bwd) {
-    if (adam) h->fold_valid = 0;
-    EncBwdLaunch eb{*s, *lay, params, obs, obs_strides[0], obs_strides[1], obs_strides[2], w.scale, w.pooled, w.hid,
-                    w.g_loc, w.g_scale, w.g_pre, w.small_slabs, w.small_stride, w.small_grid, w.lin_slabs, w.lin_splitk};
-    HIP_TRY(h, slode_launch_enc_bwd(eb, st));
-    ReduceLaunch r{*s, *lay, w.ode_slabs, w.ode_stride, n_slabs, w.small_slabs, w.small_stride, w.small_grid,
-                   w.lin_slabs, w.lin_splitk, grads, loss_out, 1, w.ode_part, w.small_part, 0};
-    if (adam) { r.adam_p = adam->p; r.adam_m = adam->m; r.adam_v = adam->v; r.adam_lr = adam->lr; r.adam_b1 = adam->b1;
-                r.adam_b2 = adam->b2; r.adam_eps = adam->eps; r.adam_step = adam->step; r.adam_n = adam->n;
-                r.adam_lo2 = h->adam_lo2; r.adam_hi2 = h->adam_hi2; r.adam_delta2 = h->adam_delta2; }
-    HIP_TRY(h, slode_launch_reduce(r, st));
-  } else {
-    ReduceLaunch r{*s, *lay, w.ode_slabs, w.ode_stride, n_slabs, nullptr, 0, 0, nullptr, 0, nullptr, loss_out, 0, w.ode_part, nullptr, 0};
-    HIP_TRY(h, slode_launch_reduce(r, st));
-  }
+// The optional Adam arguments of a step entry point: checked (the message names `who`) and converted once, with the handle's Adam region.
+static int adam_args(slode_handle h, const char* who, const char* moments, const slode_layout* lay, float* params, const slode_adam* a, StepCall* c) {
+  if (!a) return SLODE_OK;
+  if (!c->grads || !a->exp_avg || !a->exp_avg_sq || a->step < 1 || !lay || a->n_total < lay->n_params)
+    return fail(h, SLODE_EINVAL, "%s needs grads, %s moments, step >= 1 and n_total >= layout n_params", who, moments);
+  c->adam = AdamHost{params, a->exp_avg, a->exp_avg_sq, a->lr, a->beta1, a->beta2, a->eps, a->step, a->n_total};
+  if (h) { c->adam.lo2 = h->adam_lo2; c->adam.hi2 = h->adam_hi2; c->adam.delta2 = h->adam_delta2; }   // (no handle: the step refuses the call)
   return SLODE_OK;
 }
+
+// handle, kind and batch of slode_svi_step / slode_grad_partial checked; the batch (observations, label tensors, noise) into the call
+static int batch_call(slode_handle h, const slode_shape* s, int kind, const slode_batch* batch, StepCall* c) {
+  if (!h) return fail(nullptr, SLODE_EINVAL, "handle is NULL");
+  if (!s || !batch) return fail(h, SLODE_EINVAL, "shape / batch is NULL");
+  if (kind != SLODE_SVI_MAIN && kind != SLODE_SVI_AUX) return fail(h, SLODE_EINVAL, "kind must be SLODE_SVI_MAIN or SLODE_SVI_AUX");
+  c->kind = kind; c->obs = batch->obs; c->obs_strides = batch->obs_strides; c->eps = batch->eps;
+  return batch_labels(h, s, batch, &c->lab);
+}
+
+// ext_skip assumes slode_layout_init's order: the ten solver-side tensors tile [init_w1, dyn_bd + S) exactly and nothing else (prior
+// nets, decoder heads, label heads, constant_std) lies inside; a caller-made layout that does not keeps the zeros written and read
+static bool solver_contig(const slode_shape& s, const slode_layout& lay) {
+  bool ok = lay.init_b1 == lay.init_w1 + s.H * s.L && lay.init_w2 == lay.init_b1 + s.H && lay.init_b2 == lay.init_w2 + s.S * s.H &&
+            lay.dyn_wh == lay.init_b2 + s.S && lay.dyn_bh == lay.dyn_wh + s.H * (1 + s.L) && lay.dyn_wg == lay.dyn_bh + s.H &&
+            lay.dyn_bg == lay.dyn_wg + s.S * s.H && lay.dyn_wd == lay.dyn_bg + s.S && lay.dyn_bd == lay.dyn_wd + s.S * s.H;
+  const int lo = lay.init_w1, hi = lay.dyn_bd + s.S;
+  auto inside = [&](int off) { return off >= lo && off < hi; };
+  for (int g = 0; g < s.n_groups; ++g)
+    ok = ok && !inside(lay.ploc_w[g]) && !inside(lay.ploc_b[g]) && !inside(lay.pls_w[g]) && !inside(lay.pls_b[g]);
+  for (int q = 0; q < (s.likelihood == SLODE_GAUSS ? 1 : 3); ++q) ok = ok && !inside(lay.head_w[q]);
+  for (int a = 0; a < s.n_aux; ++a)
+    ok = ok && !inside(lay.aux_w1[a]) && !inside(lay.aux_b1[a]) && !inside(lay.aux_w2[a]) && !inside(lay.aux_b2[a]) &&
+         (s.aux[a].kind != SLODE_AUX_EXPEXP || (!inside(lay.aux_w3[a]) && !inside(lay.aux_b3[a]) && !inside(lay.aux_c[a])));
+  return ok && !inside(lay.cstd);
+}
+
+// ---- in-launch fold (SLODE_FOLD_NEXT, a measured arm, off by default: DESIGN 5) ----------------------------------------------------
+// The fold launch.  The previous weight-updating step on this (workspace, params) left W_eff / b_eff / rowsum / w' / the likelihood-scale
+// table of the CURRENT weights behind (enc_chain_kernel, FOLD-NEXT): then the encoder forward alone, or nothing when the ODE kernel runs it.
+// Anything else -- first step, another workspace, weights changed outside this handle (slode_fold_invalidate) -- folds here, which also
+// zeroes the in-launch fold's arrival counter.
+static int fold_fwd(slode_handle h, const StepCall& c, FoldLaunch& fl, bool enc_fused) {
+  const bool have_fold = h->fold_on && h->fold_valid && h->fold_ws == c.workspace && h->fold_params == (const void*)c.params && h->fold_tmajor == fl.t_major;
+  if (have_fold && enc_fused) return SLODE_OK;
+  fl.fold_skip = have_fold ? 1 : 0;
+  HIP_TRY(h, slode_launch_fold_fwd(fl, c.stream));
+  if (!have_fold) { h->fold_gen = 0; h->fold_valid = 1; h->fold_ws = c.workspace; h->fold_params = c.params; h->fold_tmajor = fl.t_major; }
+  return SLODE_OK;
+}
+// The chain launch updates the weights (Adam inside) => it also folds them for the next step, provided every block of the launch is resident
+// at once (the blocks wait for each other) and the handle's W_eff bookkeeping covers this workspace: tl.fold_next / n_riders / done_target.
+static void fold_next_plan(slode_ctx* h, const slode_shape& s, const slode_layout& lay, const StepCall& c, TailK& tl) {
+  int n_chain = 0, resident = 0, nblk = slode_chain_blocks(s, tl.n_total, lay.lin_b, &n_chain);
+  if (h->fold_on && c.adam.p) {   // (the occupancy query is asked once per shape and handle)
+    const int sig[8] = {s.T, s.C, s.F, s.K, s.P, s.Hc, s.L, lay.n_params};
+    if (memcmp(sig, h->chain_resident_sig, sizeof(sig)) != 0) {
+      h->chain_resident = slode_chain_resident_blocks(s, h->num_cu);
+      memcpy(h->chain_resident_sig, sig, sizeof(sig));
+    }
+    resident = h->chain_resident;
+  }
+  if (nblk > resident && resident > n_chain && nblk - n_chain <= 4 * (resident - n_chain)) nblk = resident;   // fewer, looping riders: the grid fits
+  const bool fold_next = h->fold_on && c.adam.p && c.adam.p == c.params && nblk <= resident && h->fold_valid && h->fold_ws == c.workspace &&
+                         h->fold_params == (const void*)c.params;
+  tl.fold_next = fold_next ? 1 : 0;
+  tl.n_riders = fold_next ? nblk - n_chain : 0;
+  tl.done_target = fold_next ? ++h->fold_gen : 0;   // (the generation: every counter's target is gen x its number of arrivals per launch)
+  if (c.adam.p) h->fold_valid = fold_next ? 1 : 0;
+}
+
+// ---- stage 0: the checks, the call's noise draw, the workspace.  rng_counter is consumed between the pointer checks and the rest: a call
+// that a later check refuses still uses up its draw.
+static int step_setup(Step& p) {
+  slode_handle h = p.h; const slode_shape& s = p.s; const StepCall& c = p.c;
+  p.aux = c.kind == SLODE_SVI_AUX;
+  const bool missing = c.phase == STEP_APPLY ? !c.payload || !c.grads
+                                             : (!p.aux && (!c.times || !c.stage_t)) || !c.obs || (c.phase == STEP_WHOLE ? !c.loss_out : !c.payload);
+  if (missing || !c.obs_strides || !c.workspace) return fail(h, SLODE_EINVAL, "a required pointer is NULL");
+  // eps == NULL: this call draws the guide's noise inside its kernels -- call number rng_counter of the handle's Philox stream
+  if (!c.eps && c.phase != STEP_APPLY) p.rng = rng_of(h, h->rng_counter++);
+  p.u = c.lab.n > 0 && !c.u ? c.lab.p[0] : c.u;   // (non-null = "labels present"; the kernels read through the accessor)
+  if (p.aux && (s.n_aux < 1 || (!p.u && c.phase != STEP_APPLY)))
+    return fail(h, SLODE_EINVAL, "the auxiliary loss needs label heads (n_aux >= 1) and labels u");
+  // aux_kernel only: every head owns the latent-gradient slots of the dims it reads (one writer per slot).  The reference's heads read disjoint
+  // groups (z_iext / z_rtpr, z_aR / z_aS / z_C12 / z_C6, ...).  Heads wider than 16 dims take the kernel's wide instantiation.
+  for (int a = 0; p.aux && a < s.n_aux; ++a)
+    for (int a2 = 0; a2 < a; ++a2)
+      if (s.aux[a].z_off < s.aux[a2].z_off + s.aux[a2].z_dim && s.aux[a2].z_off < s.aux[a].z_off + s.aux[a].z_dim)
+        return fail(h, SLODE_EINVAL, "slode_aux_step: label heads %d and %d read overlapping latent ranges", a2, a);
+  if (s.n_groups > 0 && !p.u && c.phase != STEP_APPLY) return fail(h, SLODE_EINVAL, "u is NULL but the shape has conditional prior groups");
+  p.dp5 = !p.aux && is_adaptive(s.method);
+  const char* m = method_name(s.method);
+  if (p.dp5 && !(s.H == 25 && (s.S == 5 || s.S == 8))) return fail(h, SLODE_EINVAL, "%s kernels are instantiated for (S,H) in {(5,25),(8,25)}", m);
+  if (p.dp5 && (s.B > 65536 || h->ode_loop)) return fail(h, SLODE_EINVAL, "the %s ELBO step takes at most 65,536 trajectories per call", m);
+  if (p.dp5 && !slode_dp5_lanes_ok(s.method, dp5_lanes(h, s.B)))
+    return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", m, dp5_lanes(h, s.B));
+  p.w = carve(h, s, p.lay, c.workspace);
+  if (c.workspace_bytes < p.w.bytes) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", c.workspace_bytes, p.w.bytes);
+  p.bwd = c.grads != nullptr || c.phase == STEP_PARTIAL;
+  // Folded encoder (encoder_fused.hip) when every trajectory's C*T observations are one dense block; else layer by layer.
+  const int64_t* os = c.obs_strides;
+  p.t_major = os[1] == 1 && os[2] == s.C;            // [B,T,C] contiguous (cvs / challenge batches)
+  const bool c_major = os[2] == 1 && os[1] == s.T;   // [B,C,T] contiguous (proc batches)
+  p.folded = !h->no_fold && os[0] == (long long)s.C * s.T && (p.t_major || c_major) && (s.C == 3 || s.C == 4);
+  return SLODE_OK;
+}
+
+// ---- stage 1: the encoder forward -- the fold launch (or its encoder half, when the workspace holds a current fold; or nothing, when the ODE
+// kernel runs the encoder forward itself: *enc_fused), layer by layer, or nothing at all (STEP_APPLY).  Fills the fused tail's FoldLaunch.
+static int step_encode(Step& p, FoldLaunch& fl, bool* enc_fused) {
+  slode_handle h = p.h; const slode_shape& s = p.s; const slode_layout& lay = p.lay; const StepCall& c = p.c; const Workspace& w = p.w;
+  if (c.phase != STEP_WHOLE && !p.folded)
+    return fail(h, SLODE_EINVAL, "slode_grad_partial / slode_grad_apply need the folded encoder path (dense [B,T,C] or [B,C,T] observations, C in {3,4})");
+  if (!p.folded) {
+    EncLaunch ef{s, lay, c.params, c.obs, c.obs_strides[0], c.obs_strides[1], c.obs_strides[2], w.loc, w.scale, w.pooled, w.hid};
+    hipError_t e = slode_launch_enc_fwd(ef, c.stream);
+    if (e == hipErrorInvalidValue) return fail(h, SLODE_EINVAL, "unsupported encoder shape C=%d K=%d T=%d", s.C, s.K, s.T);
+    HIP_TRY(h, e);
+    return SLODE_OK;
+  }
+  fl.s = s; fl.lay = lay; fl.params = c.params; fl.x = c.obs; fl.t_major = p.t_major ? 1 : 0;
+  fl.weff = w.weff; fl.rowsum = w.rowsum; fl.wprime = w.wprime; fl.beff = w.beff; fl.loc = w.loc; fl.scale = w.scale; fl.hid = w.hid;
+  fl.g_loc = w.g_loc; fl.g_scale = w.g_scale; fl.g_pre = w.g_pre; fl.small_slabs = w.small_slabs; fl.small_stride = w.small_stride;
+  fl.g_lin_w = c.grads ? c.grads + lay.lin_w : nullptr; fl.conv_slabs = w.conv_slabs; fl.counter = w.counter;
+  // STEP_APPLY: no forward work (STEP_PARTIAL's fold launch left w' / rowsum / the zeroed arrival counters); the payload is ONE split
+  if (c.phase == STEP_APPLY) { fl.gslabs = c.payload; fl.n_gslabs = 1; return SLODE_OK; }
+  fl.gslabs = w.gslabs; fl.n_gslabs = w.gsplit; fl.sigtab = w.sigtab;   // (the aux step does not read the table; the next main step may)
+  // the loop-free ODE kernel of the metric shape runs the encoder forward of its own trajectories (ode_kernel.hip, ENCF): fold only
+  *enc_fused = !p.aux && !p.dp5 && p.bwd && h->enc_fuse && !h->ode_loop && !h->ode_generic && h->ode_alg == 0 &&
+               (h->ode_pack == 0 || h->ode_pack >= 10) && !c.x_out && slode_ode_can_fuse_encoder(s, p.bwd, w.ode_grid);
+  fl.skip_enc = *enc_fused ? 1 : 0;
+  return fold_fwd(h, c, fl, *enc_fused);
+}
+
+// ---- stage 2: the loss terms into the slab rows.  Aux: one workgroup per trajectory up to 2,048 of them, then a loop; on the folded path
+// the kernel also runs the encoder-head backward and its slab rows carry only the label-head range (the fused tail reduces exactly that).
+static int score_aux(Step& p, SlabRows* rows) {
+  slode_handle h = p.h; const slode_shape& s = p.s; const slode_layout& lay = p.lay; const Workspace& w = p.w;
+  AuxLaunch al{s, lay, p.c.params, w.loc, w.scale, p.c.eps, p.u, w.g_loc, w.g_scale, w.ode_slabs, w.ode_stride,
+               w.ode_grid < 2048 ? w.ode_grid : 2048, p.bwd ? 1 : 0};
+  al.rng = p.rng; al.lab = p.c.lab;
+  // compact rows carry the flat range [aux_w1[0], cstd): every label-head tensor must lie inside it (a caller-made layout may not)
+  bool aux_contig = lay.aux_w1[0] <= lay.cstd;
+  for (int a = 0; a < s.n_aux; ++a) {
+    const int hi = s.aux[a].kind == SLODE_AUX_EXPEXP ? lay.aux_c[a] + 1 : lay.aux_b2[a] + s.aux[a].u_dim;
+    aux_contig = aux_contig && lay.aux_w1[a] >= lay.aux_w1[0] && hi <= lay.cstd;
+  }
+  if (p.bwd && p.folded && !aux_contig) return fail(h, SLODE_EINVAL, "slode_aux_step: the label heads must lie in [aux_w1[0], cstd) of the layout (slode_layout_init's order)");
+  if (p.bwd && p.folded) { al.compact = 1; al.enc_hid = w.hid; al.g_pre = w.g_pre; al.glat = w.glat; al.g_loc = nullptr; al.g_scale = nullptr; }
+  rows->n = al.grid;
+  HIP_TRY(h, slode_launch_aux(al, p.c.stream));
+  return SLODE_OK;
+}
+
+static int score_ode(Step& p, bool enc_fused, SlabRows* rows) {
+  slode_handle h = p.h; const slode_shape& s = p.s; const slode_layout& lay = p.lay; const StepCall& c = p.c; const Workspace& w = p.w;
+  OdeLaunch a{};
+  a.s = scorer_shape(s); a.lay = lay; a.params = c.params; a.times = c.times; a.stage_t = p.dp5 ? c.times : c.stage_t;
+  a.obs = c.obs; a.sb = c.obs_strides[0]; a.sc = c.obs_strides[1]; a.st = c.obs_strides[2];
+  a.u = p.u; a.eps = c.eps; a.loc = w.loc; a.scale = w.scale; a.x_out = c.x_out; a.z_out = c.z_out;
+  a.g_loc = w.g_loc; a.g_scale = w.g_scale; a.slabs = w.ode_slabs; a.slab_stride = w.ode_stride; a.grid = w.ode_grid;
+  a.backward = p.bwd ? 1 : 0; a.with_ll = 1; a.rng = p.rng; a.lab = c.lab;
+  a.sigtab = p.folded ? w.sigtab : nullptr;   // written by the fold launch
+  a.force_loop = h->ode_loop; a.force_generic = h->ode_generic; a.alg = h->ode_alg; a.pack = h->ode_pack;
+  if (p.bwd && p.folded && !p.dp5) { a.enc_hid = w.hid; a.g_pre = w.g_pre; a.glat = w.glat; a.g_loc = nullptr; a.g_scale = nullptr; }
+  if (enc_fused) { a.enc_fuse = 1; a.enc_weff = w.weff; a.enc_beff = w.beff; a.enc_hid_out = w.hid; }
+  if (p.dp5 && p.bwd && p.folded && solver_contig(s, lay) && w.ode_grid + w.dp_rows > 2 * SLODE_REDUCE_GROUPS) {
+    // the scorer's rows carry nothing in the solver-side range [init net | dynamics] (the reverse sweep's rows do): the scorer does not
+    // write those zeros and stage 1 of the fused tail (the only reader of the rows) does not read them
+    a.ext_skip = 1;
+    rows->zr_rows = w.ode_grid; rows->zr_lo = 1 + (lay.init_w1 - lay.ode_begin); rows->zr_hi = 1 + (lay.dyn_bd + s.S - lay.ode_begin);
+  }
+  // adaptive solve (accepted steps recorded) -> ONE scorer pass (loss terms, dLoss/dx, the gradients that do not flow through the solver)
+  // -> reverse sweep over the records (solver-side gradients as extra slab rows, the latent gradient through the solver added to g_loc /
+  // g_scale, the encoder-head backward).  Forward workgroups of 16 trajectories (8 or 16 lanes), as the sweep's, hand it their tables.
+  DopriRec rc{w.loc, w.scale, c.eps, w.dp_z, p.bwd ? w.dp_rec : nullptr, w.dp_nrec, w.dp_kmax};
+  if (p.dp5) {
+    rc.w64 = dp5_lanes(h, s.B);
+    rc.tabs = p.bwd && (rc.w64 == 8 || rc.w64 == 16) ? w.dp_tabs : nullptr;
+    // in-kernel noise: the forward kernel draws it once and materialises it, the scorer and the reverse sweep read the same values
+    if (p.rng.on) { rc.rng = p.rng; rc.eps_out = w.dp_eps; a.rng = RngK{}; a.eps = w.dp_eps; }
+    HIP_TRY(h, slode_launch_dopri5(s, lay, c.params, c.times, nullptr, w.dp_x, c.stream, &rc));
+    a.x_ext = w.dp_x;
+    if (p.bwd) { a.gx_out = w.dp_gx; rows->n = w.ode_grid + w.dp_rows; }
+  }
+  hipError_t e = slode_launch_ode(a, c.stream, h->err, sizeof(h->err));
+  if (e == hipErrorInvalidValue) return SLODE_EINVAL;
+  HIP_TRY(h, e);
+  rc.eps = a.eps;   // (the noise the forward kernel drew, when it drew it)
+  if (p.dp5 && p.bwd)
+    HIP_TRY(h, slode_launch_dopri5_bwd(s, lay, c.params, c.times, rc, w.dp_gx, w.g_loc, w.g_scale, w.ode_slabs + (size_t)w.ode_grid * w.ode_stride,
+                                       w.ode_stride, s.grad_mode == SLODE_GRAD_REFERENCE_ADJOINT ? 1 : 0, w.dp_snap, c.stream,
+                                       p.folded ? w.hid : nullptr, p.folded ? w.g_pre : nullptr, p.folded ? w.glat : nullptr));
+  return SLODE_OK;
+}
+
+// ---- stage 3, folded backward: the fused tail.  Stage 2 ran the encoder heads + tanh backward (g_pre, glat): two launches remain -- split-K
+// MFMA GEMMs (+ rider blocks: stage 1 of the ODE-slab reduction), chain rule + final reduction (+ Adam).  STEP_PARTIAL: the payload instead.
+static int tail_fused(Step& p, FoldLaunch& fl, const SlabRows& rows) {
+  slode_handle h = p.h; const slode_shape& s = p.s; const slode_layout& lay = p.lay; const StepCall& c = p.c; const Workspace& w = p.w;
+  const int CT = s.C * s.T, count = (rows.part_hi - rows.part_lo) + 1;
+  const PayloadMap pm = payload_map(s, rows.part_hi - rows.part_lo);
+  const float* ode_part = nullptr; int ode_pn = 0;
+  if (c.phase != STEP_APPLY)
+    HIP_TRY(h, slode_launch_gemm_tail(w.g_pre, c.obs, w.gslabs, s.Hc, CT, w.glat, w.hid, w.gslabs2, w.gslabs3, s.L, s.B, w.gsplit,
+                                      w.ode_slabs, w.ode_stride, rows.n, count, w.ode_part, &ode_part, &ode_pn, c.stream,
+                                      rows.zr_rows, rows.zr_lo, rows.zr_hi));
+  if (c.phase == STEP_PARTIAL) {   // split-K partials and partial slab rows, summed in fixed order, into the contiguous payload
+    HIP_TRY(h, slode_launch_pack_payload(w.gslabs, w.gslabs2, w.gslabs3, w.gsplit, s.Hc, CT, s.L, ode_part, w.ode_stride, ode_pn,
+                                         count, c.payload, pm.g_loc, pm.g_ls, pm.ode, pm.total, c.stream));
+    return SLODE_OK;
+  }
+  TailK tl{};
+  if (c.phase == STEP_APPLY) {   // the (reduced) payload stands for ONE split / ONE partial row
+    tl.gslabs = c.payload; tl.gslabs_loc = c.payload + pm.g_loc; tl.gslabs_ls = c.payload + pm.g_ls;
+    tl.ode_part = c.payload + pm.ode; tl.ode_stride = 0; tl.ode_n = 1; tl.gsplit = 1;
+  } else {
+    tl.gslabs = w.gslabs; tl.gslabs_loc = w.gslabs2; tl.gslabs_ls = w.gslabs3;
+    tl.ode_part = ode_part; tl.ode_stride = w.ode_stride; tl.ode_n = ode_pn; tl.gsplit = w.gsplit;
+  }
+  tl.conv_slabs = w.conv_slabs; tl.loss_out = c.loss_out; tl.part_lo = rows.part_lo; tl.part_hi = rows.part_hi; tl.grads = c.grads;
+  tl.Hc = s.Hc; tl.L = s.L; tl.CT = CT; tl.n_cv = s.F * s.C * s.K + s.F; tl.ode_begin = lay.ode_begin; tl.n_params = lay.n_params;
+  tl.conv_w = lay.conv_w; tl.lin_w = lay.lin_w; tl.lin_b = lay.lin_b; tl.zloc_w = lay.zloc_w; tl.zloc_b = lay.zloc_b; tl.zls_w = lay.zls_w;
+  tl.zls_b = lay.zls_b; tl.n_total = (c.adam.p && c.adam.n > lay.n_params) ? (int)c.adam.n : lay.n_params; tl.ad = make_adamk(&c.adam);
+  tl.counter = tl.done = w.counter; tl.cstd_off = lay.cstd; tl.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; tl.sigtab = w.sigtab;
+  fold_next_plan(h, s, lay, c, tl);
+  fl.tail = &tl;
+  HIP_TRY(h, slode_launch_fold_chain(fl, c.stream));   // + rider blocks and the last-block conv reduction: the flat gradient is complete
+  return SLODE_OK;
+}
+
+// ---- stage 3, otherwise: the layer-by-layer encoder backward + the slab reduction (+ Adam), or the forward-only loss reduction
+static int tail_reduce(Step& p, const SlabRows& rows) {
+  slode_handle h = p.h; const StepCall& c = p.c; const Workspace& w = p.w;
+  ReduceLaunch r{};
+  r.s = p.s; r.lay = p.lay; r.ode_slabs = w.ode_slabs; r.ode_stride = w.ode_stride; r.ode_n = rows.n; r.ode_part = w.ode_part; r.loss_out = c.loss_out;
+  if (p.bwd) {
+    if (c.adam.p) h->fold_valid = 0;
+    EncBwdLaunch eb{p.s, p.lay, c.params, c.obs, c.obs_strides[0], c.obs_strides[1], c.obs_strides[2], w.scale, w.pooled, w.hid,
+                    w.g_loc, w.g_scale, w.g_pre, w.small_slabs, w.small_stride, w.small_grid, w.lin_slabs, w.lin_splitk};
+    HIP_TRY(h, slode_launch_enc_bwd(eb, c.stream));
+    r.small_slabs = w.small_slabs; r.small_stride = w.small_stride; r.small_n = w.small_grid; r.small_part = w.small_part;
+    r.lin_slabs = w.lin_slabs; r.lin_n = w.lin_splitk; r.grads = c.grads; r.zero_rest = 1; r.adam = c.adam;
+  }
+  HIP_TRY(h, slode_launch_reduce(r, c.stream));
+  return SLODE_OK;
+}
+
+static int elbo_step_impl(slode_handle h, const slode_shape* s, const slode_layout* lay, const StepCall& call) {
+  const char* why = check_common(h, s, lay, call.params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  Step p{h, *s, *lay, call};
+  int rc = step_setup(p);
+  if (rc != SLODE_OK) return rc;
+  ClockScope clock_scope(h, true);
+  FoldLaunch fl{}; bool enc_fused = false;
+  SlabRows rows{p.w.ode_grid, lay->ode_begin, lay->n_params};
+  if (p.aux && p.bwd && p.folded) { rows.part_lo = lay->aux_w1[0]; rows.part_hi = lay->cstd; }   // compact aux rows
+  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  if (call.phase != STEP_APPLY && (rc = p.aux ? score_aux(p, &rows) : score_ode(p, enc_fused, &rows)) != SLODE_OK) return rc;
+  return p.bwd && p.folded ? tail_fused(p, fl, rows) : tail_reduce(p, rows);
+}
+
+extern "C" {
 
 int slode_elbo_step(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                     const float* stage_t, const float* obs, const int64_t obs_strides[3], const float* u, const float* eps,
                     float* loss_out, float* grads, float* x_out, float* z_out, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  return elbo_step_impl(h, s, lay, params, times, stage_t, obs, obs_strides, u, eps, loss_out, grads, x_out, z_out, workspace,
-                        workspace_bytes, stream, nullptr);
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.obs = obs; c.obs_strides = obs_strides; c.u = u; c.eps = eps; c.loss_out = loss_out;
+  c.grads = grads; c.x_out = x_out; c.z_out = z_out; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  return elbo_step_impl(h, s, lay, c);
 }
 
 int slode_elbo_adam_step(slode_handle h, const slode_shape* s, const slode_layout* lay, float* params, const float* times,
                          const float* stage_t, const float* obs, const int64_t obs_strides[3], const float* u, const float* eps,
                          float* loss_out, float* grads, void* workspace, size_t workspace_bytes, int64_t n_total, float* exp_avg,
                          float* exp_avg_sq, float lr, float beta1, float beta2, float adam_eps, int64_t step, void* stream) {
-  if (!grads || !exp_avg || !exp_avg_sq || step < 1 || !lay || n_total < lay->n_params)
-    return fail(h, SLODE_EINVAL, "slode_elbo_adam_step needs grads, Adam moments, step >= 1 and n_total >= layout n_params");
-  const AdamArgs ad{params, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, step, n_total};
-  return elbo_step_impl(h, s, lay, params, times, stage_t, obs, obs_strides, u, eps, loss_out, grads, nullptr, nullptr, workspace,
-                        workspace_bytes, stream, &ad);
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.obs = obs; c.obs_strides = obs_strides; c.u = u; c.eps = eps; c.loss_out = loss_out;
+  c.grads = grads; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  const slode_adam a{n_total, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, step};
+  const int rc = adam_args(h, "slode_elbo_adam_step", "Adam", lay, params, &a, &c);
+  return rc != SLODE_OK ? rc : elbo_step_impl(h, s, lay, c);
 }
 
 int slode_aux_step(slode_handle h, const slode_shape* s, const slode_layout* lay, float* params, const float* obs,
                    const int64_t obs_strides[3], const float* u, const float* eps, float* loss_out, float* grads, void* workspace,
                    size_t workspace_bytes, int64_t n_total, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
                    float adam_eps, int64_t step, void* stream) {
-  const bool with_adam = exp_avg != nullptr;
-  if (with_adam && (!grads || !exp_avg_sq || step < 1 || !lay || n_total < lay->n_params))
-    return fail(h, SLODE_EINVAL, "slode_aux_step with Adam needs grads, both moments, step >= 1 and n_total >= layout n_params");
-  const AdamArgs ad{params, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, step, n_total};
-  return elbo_step_impl(h, s, lay, params, nullptr, nullptr, obs, obs_strides, u, eps, loss_out, grads, nullptr, nullptr, workspace,
-                        workspace_bytes, stream, with_adam ? &ad : nullptr, 1);
+  StepCall c;
+  c.kind = SLODE_SVI_AUX; c.params = params; c.obs = obs; c.obs_strides = obs_strides; c.u = u; c.eps = eps; c.loss_out = loss_out;
+  c.grads = grads; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  const slode_adam a{n_total, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, step};
+  const int rc = adam_args(h, "slode_aux_step with Adam", "both", lay, params, exp_avg ? &a : nullptr, &c);
+  return rc != SLODE_OK ? rc : elbo_step_impl(h, s, lay, c);
 }
 
 int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay, int kind, float* params, const float* times,
                    const float* stage_t, const slode_batch* batch, float* loss_out, float* grads, void* workspace, size_t workspace_bytes,
                    const slode_adam* adam, void* stream) {
-  if (!h) return fail(nullptr, SLODE_EINVAL, "handle is NULL");
-  if (!s || !batch) return fail(h, SLODE_EINVAL, "shape / batch is NULL");
-  if (kind != SLODE_SVI_MAIN && kind != SLODE_SVI_AUX) return fail(h, SLODE_EINVAL, "kind must be SLODE_SVI_MAIN or SLODE_SVI_AUX");
-  LabelSrc lab{};
-  const int rc_lab = batch_labels(h, s, batch, &lab);
-  if (rc_lab != SLODE_OK) return rc_lab;
-  AdamArgs ad{};
-  if (adam) {
-    if (!grads || !adam->exp_avg || !adam->exp_avg_sq || adam->step < 1 || !lay || adam->n_total < lay->n_params)
-      return fail(h, SLODE_EINVAL, "slode_svi_step with Adam needs grads, both moments, step >= 1 and n_total >= layout n_params");
-    ad = AdamArgs{params, adam->exp_avg, adam->exp_avg_sq, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->n_total};
-  }
-  return elbo_step_impl(h, s, lay, params, kind == SLODE_SVI_AUX ? nullptr : times, kind == SLODE_SVI_AUX ? nullptr : stage_t, batch->obs,
-                        batch->obs_strides, nullptr, batch->eps, loss_out, grads, nullptr, nullptr, workspace, workspace_bytes, stream,
-                        adam ? &ad : nullptr, kind == SLODE_SVI_AUX ? 1 : 0, batch->n_labels > 0 ? &lab : nullptr);
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.loss_out = loss_out; c.grads = grads;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  int rc = batch_call(h, s, kind, batch, &c);
+  if (rc != SLODE_OK || (rc = adam_args(h, "slode_svi_step with Adam", "both", lay, params, adam, &c)) != SLODE_OK) return rc;
+  return elbo_step_impl(h, s, lay, c);
 }
 
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {
@@ -803,16 +809,11 @@ size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, 
 
 int slode_grad_partial(slode_handle h, const slode_shape* s, const slode_layout* lay, int kind, const float* params, const float* times,
                        const float* stage_t, const slode_batch* batch, float* payload, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return fail(nullptr, SLODE_EINVAL, "handle is NULL");
-  if (!s || !batch) return fail(h, SLODE_EINVAL, "shape / batch is NULL");
-  if (kind != SLODE_SVI_MAIN && kind != SLODE_SVI_AUX) return fail(h, SLODE_EINVAL, "kind must be SLODE_SVI_MAIN or SLODE_SVI_AUX");
-  LabelSrc lab{};
-  const int rc = batch_labels(h, s, batch, &lab);
-  if (rc != SLODE_OK) return rc;
-  const bool aux = kind == SLODE_SVI_AUX;
-  return elbo_step_impl(h, s, lay, params, aux ? nullptr : times, aux ? nullptr : stage_t, batch->obs, batch->obs_strides, nullptr, batch->eps,
-                        nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, aux ? 1 : 0,
-                        batch->n_labels > 0 ? &lab : nullptr, 1, payload);
+  StepCall c;
+  c.phase = STEP_PARTIAL; c.params = params; c.times = times; c.stage_t = stage_t; c.payload = payload;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  const int rc = batch_call(h, s, kind, batch, &c);
+  return rc != SLODE_OK ? rc : elbo_step_impl(h, s, lay, c);
 }
 
 int slode_grad_apply(slode_handle h, const slode_shape* s, const slode_layout* lay, int kind, float* params, const int64_t obs_strides[3],
@@ -820,14 +821,11 @@ int slode_grad_apply(slode_handle h, const slode_shape* s, const slode_layout* l
                      void* stream) {
   if (!h) return fail(nullptr, SLODE_EINVAL, "handle is NULL");
   if (kind != SLODE_SVI_MAIN && kind != SLODE_SVI_AUX) return fail(h, SLODE_EINVAL, "kind must be SLODE_SVI_MAIN or SLODE_SVI_AUX");
-  AdamArgs ad{};
-  if (adam) {
-    if (!grads || !adam->exp_avg || !adam->exp_avg_sq || adam->step < 1 || !lay || adam->n_total < lay->n_params)
-      return fail(h, SLODE_EINVAL, "slode_grad_apply with Adam needs grads, both moments, step >= 1 and n_total >= layout n_params");
-    ad = AdamArgs{params, adam->exp_avg, adam->exp_avg_sq, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->n_total};
-  }
-  return elbo_step_impl(h, s, lay, params, nullptr, nullptr, nullptr, obs_strides, nullptr, nullptr, loss_out, grads, nullptr, nullptr, workspace,
-                        workspace_bytes, stream, adam ? &ad : nullptr, kind == SLODE_SVI_AUX ? 1 : 0, nullptr, 2, const_cast<float*>(payload));
+  StepCall c;
+  c.kind = kind; c.phase = STEP_APPLY; c.params = params; c.obs_strides = obs_strides; c.payload = const_cast<float*>(payload);
+  c.loss_out = loss_out; c.grads = grads; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  const int rc = adam_args(h, "slode_grad_apply with Adam", "both", lay, params, adam, &c);
+  return rc != SLODE_OK ? rc : elbo_step_impl(h, s, lay, c);
 }
 
 int slode_fold_invalidate(slode_handle h) {

@@ -55,8 +55,9 @@ struct slode_ctx {
   int ode_grid_cap;       // SLODE_ODE_GRID = n: at most n workgroups in the persistent-loop grid (tests: several trajectories per workgroup at small B)
   // slode_rng_seed: the Philox stream of the calls that draw their own noise (eps == NULL); rng_counter = drawing calls made so far
   uint64_t rng_seed, rng_counter; int64_t rng_b0;
-  // in-launch fold (SLODE_FOLD_NEXT, default on): the chain launch of a step that updates the weights leaves W_eff & co. of the NEW weights
-  // in the workspace; the next step on the same (workspace, params) skips its fold launch.  fold_gen: launches that counted on `done`.
+  // in-launch fold (SLODE_FOLD_NEXT, a measured arm, default off: DESIGN 5): the chain launch of a step that updates the weights leaves
+  // W_eff & co. of the NEW weights in the workspace; the next step on the same (workspace, params) skips its fold launch.  fold_gen:
+  // launches that counted on `done`.
   int fold_on, fold_valid, fold_tmajor;
   const void* fold_ws; const void* fold_params;
   unsigned int fold_gen;
@@ -514,22 +515,19 @@ struct AuxLaunch {
 hipError_t slode_launch_aux(const AuxLaunch& a, hipStream_t stream);
 
 #define SLODE_REDUCE_GROUPS 16
-struct ReduceLaunch {
+struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;
   slode_layout lay;
-  const float* ode_slabs; int ode_stride; int ode_n;       // may be null
-  const float* small_slabs; int small_stride; int small_n; // may be null
-  const float* lin_slabs; int lin_n;                       // may be null
-  float* grads;       // flat gradient (may be null when only the loss is wanted)
-  float* loss_out;    // may be null
-  int zero_rest;      // also zero grads outside the written segments [0, n_params)
-  float* ode_part;    // [SLODE_REDUCE_GROUPS][ode_stride] scratch for the two-stage reduction (may be null)
-  float* small_part;  // [SLODE_REDUCE_GROUPS][small_stride] likewise
-  int folded;         // 1: folded-encoder families (small = [lin_b..zls_b]; `lin` family = per-m conv slabs at flat offset conv_w)
-  float *adam_p = nullptr, *adam_m = nullptr, *adam_v = nullptr;  // optional fused Adam (after the positional members)
-  float adam_lr = 0.f, adam_b1 = 0.f, adam_b2 = 0.f, adam_eps = 0.f;
-  int64_t adam_step = 0, adam_n = 0;
-  int adam_lo2 = 0, adam_hi2 = 0; int64_t adam_delta2 = 0;
+  const float* ode_slabs = nullptr; int ode_stride = 0, ode_n = 0;       // may be null
+  const float* small_slabs = nullptr; int small_stride = 0, small_n = 0; // may be null
+  const float* lin_slabs = nullptr; int lin_n = 0;                       // may be null
+  float* grads = nullptr;       // flat gradient (may be null when only the loss is wanted)
+  float* loss_out = nullptr;    // may be null
+  int zero_rest = 0;            // also zero grads outside the written segments [0, n_params)
+  float* ode_part = nullptr;    // [SLODE_REDUCE_GROUPS][ode_stride] scratch for the two-stage reduction (may be null)
+  float* small_part = nullptr;  // [SLODE_REDUCE_GROUPS][small_stride] likewise
+  int folded = 0;               // 1: folded-encoder families (small = [lin_b..zls_b]; `lin` family = per-m conv slabs at flat offset conv_w)
+  AdamHost adam{};              // optional fused Adam (adam.p == nullptr: none)
 };
 hipError_t slode_launch_reduce(const ReduceLaunch& a, hipStream_t stream);
 

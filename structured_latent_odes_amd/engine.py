@@ -402,7 +402,9 @@ class Engine:
     # ---- SVI.step(**batch) as one call: labels as the loader yields them, noise drawn in the kernels -----------------------------
     def make_batch(self, obs, labels, eps=None) -> L.Batch:
         """slode_batch for `obs` [B, C, T] (any strides) and the label tensors in the model's concatenation order (each [B, width] or [B],
-        float32, contiguous, on the device).  eps [B, L] or None (None: drawn in-kernel from the handle's Philox stream, rng_seed)."""
+        float32, contiguous, on the device).  eps [B, L] or None (None: drawn in-kernel from the handle's Philox stream, rng_seed).
+        The batch carries raw device pointers; it also holds the tensors they point at (``tensors``), so a label tensor converted just
+        for this batch lives until the batch does -- until the step that reads it is enqueued."""
         B = obs.shape[0]
         self._f32(obs, "observations", contiguous=False)
         bt = L.Batch()
@@ -428,6 +430,7 @@ class Engine:
             if tuple(eps.shape) != (B, self.spec.latent_dim):
                 raise ValueError("eps must be [%d, %d], got %s" % (B, self.spec.latent_dim, tuple(eps.shape)))
             bt.eps = eps.data_ptr()
+        bt.tensors = (obs, *labels, eps)
         return bt
 
     def svi_step(self, kind: int, params, batch: L.Batch, B: int, loss_out, grads=None, adam=None):

@@ -95,8 +95,12 @@ class _StepBase:
     def step_async(self, observations, eps=None, u=None, labels=None, **named):
         """Enqueue one optimisation step on the current stream; returns the device tensor holding -ELBO (global sum)."""
         B = observations.shape[0]
-        bt = self._batch(observations, eps, self._named(labels, named), u)
         opt = self.optimizer
+        small_payload = (self.dp_payload == "G" and (self.world > 1 or self.unfused) and self._payload is not False and
+                         hasattr(self.engine, "grad_partial"))
+        if small_payload and self._payload is None:   # (allocated before the batch is built: nothing new is allocated while it is in use)
+            self._payload = torch.zeros(self.engine.payload_floats(self.KIND), dtype=torch.float32, device=self.params.device)
+        bt = self._batch(observations, eps, self._named(labels, named), u)
         # parameters appended after engine.n_params get no main-loss gradient: that region of gbuf is zero-initialised and never
         # written by the main step, so it needs no per-step fill
         if self.world == 1 and opt is not None and not self.unfused:
@@ -104,13 +108,11 @@ class _StepBase:
             self.engine.svi_step(self.KIND, self.params, bt, B, self.loss, self.grads,
                                  adam=(opt.exp_avg, opt.exp_avg_sq, opt.lr, opt.t, opt.betas, opt.eps))
             return self.loss
-        if self.dp_payload == "G" and (self.world > 1 or self.unfused) and self._payload is not False and hasattr(self.engine, "grad_partial"):
+        if small_payload:
             # data parallel, small payload: every rank contributes G = g_pre^T [X | 1], its head-layer products and its ODE-half row with
             # the loss scalar (137 KB instead of the 386 KB flat gradient at the metric shape); the chain rule -- linear in G -- runs once,
             # on the reduced payload, with Adam applied by the same launch (include/slode.h: slode_grad_partial / slode_grad_apply)
             try:
-                if self._payload is None:
-                    self._payload = torch.zeros(self.engine.payload_floats(self.KIND), dtype=torch.float32, device=self.params.device)
                 self.engine.grad_partial(self.KIND, self.params, bt, B, self._payload)
             except L.SlodeError:
                 self._payload = False          # (observations the folded encoder path does not take: reduce the flat gradient instead)

@@ -89,7 +89,9 @@ def _run(rank, world, port, q):
         svi = ELBOStep(eng, flat, FlatAdam(eng, flat, lr=1e-2))
         losses = [svi.step(obs[sl], eps=eps[sl], u=u[sl]) for _ in range(3)]
         ev = svi.evaluate_loss(obs[sl], eps=eps[sl], u=u[sl])
-        q.put((rank, losses, ev, flat.clone()))
+        # the weights go by value: a queued tensor would be handed over as a file descriptor that this process serves until it exits,
+        # and it may exit before the parent has fetched it
+        q.put((rank, losses, ev, flat.numpy().copy()))
     finally:
         torch.distributed.destroy_process_group()
 
@@ -116,7 +118,7 @@ def test_two_rank_data_parallel_equals_single_process():
     svi = ELBOStep(eng, flat, FlatAdam(eng, flat, lr=1e-2))
     want = [svi.step(obs, eps=eps, u=u) for _ in range(3)]
     want_ev = svi.evaluate_loss(obs, eps=eps, u=u)
-    (r0, l0, e0, f0), (r1, l1, e1, f1) = res
+    (r0, l0, e0, f0), (r1, l1, e1, f1) = [(r, l, e, torch.from_numpy(f)) for r, l, e, f in res]
     assert l0 == l1 and torch.equal(f0, f1)                       # every rank holds the same loss and the same weights
     assert e0 == e1
     for a, b in zip(l0, want):

@@ -181,3 +181,30 @@ def test_chain_hand_off_is_write_through_in_the_isa():
     loads = [l for l in body.splitlines() if "global_load_dword" in l and " sc1" in l]
     atomics = [l for l in body.splitlines() if "global_atomic_add" in l]
     assert len(stores) >= 2 and len(loads) >= 16 and len(atomics) >= 1, (len(stores), len(loads), len(atomics))
+
+
+def test_batch_keeps_its_converted_label_tensors_alive(monkeypatch):
+    """slode_batch carries raw pointers.  A label tensor converted for the step (float64 -> float32, strided -> contiguous) exists only
+    for that batch: the batch must hold it as long as it lives, or the caching allocator can hand its memory to the next allocation
+    before the step reads it."""
+    import gc
+    import weakref
+    from structured_latent_odes_amd import engine as E
+    from structured_latent_odes_amd import svi as S
+    B, T = 4, 20
+    eng = E.Engine.__new__(E.Engine)   # (no device here; make_batch only reads shapes, strides and pointers)
+    eng.device, eng.spec, eng.T = torch.device("cpu"), E.cvs_spec(3, 3, 2), T
+    step = S.ELBOStep.__new__(S.ELBOStep)
+    step.engine, step.world = eng, 1
+    made = []
+    label_list = S._label_list
+    monkeypatch.setattr(S, "_label_list", lambda labels, u: [made.append(weakref.ref(t)) or t for t in label_list(labels, u)])
+    labels = [torch.rand(B, 1, dtype=torch.float64), torch.rand(B, 2)[:, :1]]
+    bt = step._batch(torch.rand(B, T, 3).permute(0, 2, 1), None, labels, None)
+    gc.collect()
+    assert all(r() is not None for r in made) and len(made) == 2
+    assert [bt.labels[i] for i in range(2)] == [r().data_ptr() for r in made]
+    assert all(r() is not t for r, t in zip(made, labels))   # (both were converted)
+    del bt
+    gc.collect()
+    assert [r() for r in made] == [None, None]
