@@ -29,12 +29,13 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 120 /* 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN (0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 130 /* 0.1.3: slode_shape::particles (0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
 #define SLODE_MAX_AUX 4
 #define SLODE_MAX_LABELS 4 /* label tensors of one minibatch (proc: aR, aS, C12, C6) */
+#define SLODE_MAX_PARTICLES 1024
 
 typedef enum slode_status {
   SLODE_OK = 0,
@@ -101,6 +102,21 @@ typedef struct slode_shape {
   slode_aux aux[SLODE_MAX_AUX];
   int32_t aux_in_main; /* 1: the main model scores the label heads too (proc family)       */
   int32_t grad_mode;   /* slode_grad_mode: which gradient the backward pass returns         */
+  /* pyro.infer.Trace_ELBO(num_particles=K) (training_cvs.py:237 `Trace_ELBO(num_particles=config.num_particles)`): the ELBO steps
+   * (slode_elbo_step, slode_elbo_adam_step, slode_aux_step, slode_svi_step, slode_grad_partial / slode_grad_apply; kind MAIN and AUX)
+   * evaluate model and guide K times on the same minibatch and parameters, each with its own reparameterisation noise, and return the
+   * MEAN of the K losses and the MEAN of the K gradients; Adam, where the step applies it, steps ONCE with that mean.  0 and 1 both mean
+   * one particle (a zero-initialised shape behaves as before this field existed); at most SLODE_MAX_PARTICLES.  The encoder runs once
+   * (its output does not depend on the particle); the solver / scorer kernels run over K * B virtual trajectories, particle-major:
+   * virtual row k * B + b is particle k of data row b.
+   *   Noise: eps == NULL draws particle k from drawing call n + k of the handle's generator (n = the counter at the call; trajectory
+   *   index unchanged, so sharding stays a matter of first_trajectory alone) and leaves the counter at n + K:
+   *   slode_rng_normal(h, n + k, B, L, ...) reads particle k's noise back.  eps != NULL is one dense [K, B, L] tensor ([B, L] for K = 1).
+   *   Limits are the per-call ones applied to B * K: the adaptive methods' 65,536 trajectories (SLODE_EINVAL beyond), their step-record
+   *   capacity 2^26 / (B K (S + 2)) clamped to [64, 2048]; slode_dopri5_step_counts returns K * B counts (virtual-row order).
+   *   x_out / z_out with K > 1: SLODE_EINVAL.  A handle created with SLODE_FOLD_NEXT, SLODE_ODE_PACK or SLODE_ODE_ALG set refuses K > 1
+   *   (SLODE_EINVAL): the measured arms take one particle.  slode_workspace_bytes accounts for K.  The other entry points ignore it. */
+  int32_t particles;
 } slode_shape;
 
 /* Offsets (in floats) of each parameter tensor inside the flat parameter / gradient vector.
@@ -266,7 +282,7 @@ typedef struct slode_batch {
   int32_t n_labels;            /* 0: no labels (shapes without conditional priors / label heads) */
   int32_t label_width[SLODE_MAX_LABELS];
   const float* labels[SLODE_MAX_LABELS];
-  const float* eps;            /* [B, L] or NULL */
+  const float* eps;            /* [B, L] ([K, B, L] with the shape's particles = K > 1) or NULL */
 } slode_batch;
 /* Adam hyper-parameters and state for the update applied by the step's last kernel (NULL: gradient only) */
 typedef struct slode_adam {
@@ -345,7 +361,7 @@ int slode_adam_step(slode_handle h, int64_t n, float* params, const float* grads
 int slode_adam_region(slode_handle h, int64_t lo, int64_t hi, int64_t step_delta);
 
 /* Diagnostic (no reference counterpart; torchdiffeq does not report it): accepted steps per trajectory of the last adaptive (dopri5,
- * bosh3, fehlberg2, adaptive_heun) training step run on this workspace -> counts[B] (int32, device).  -1: 20,000 attempted steps exhausted; > capacity: record overflow (the
+ * bosh3, fehlberg2, adaptive_heun) training step run on this workspace -> counts[B] (int32, device; [K * B] with K particles).  -1: 20,000 attempted steps exhausted; > capacity: record overflow (the
  * capacity is slode_dopri5_kmax: 2^26 / (B (S + 2)) steps, within [64, 2048]).  A training step in which any trajectory did either
  * returns a NaN loss and an all-NaN gradient (with Adam inside: NaN parameters), never a finite gradient that lacks that trajectory's
  * solver share; the trajectories and the forward-only loss of an overflowed step are those of the solve, which is complete. */

@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SLODE_LIB_PATH") or os.path.join(_HERE, "libslode.so")  # env override: diagnostics only
 
 MAX_GROUPS, MAX_HEADS, MAX_AUX, MAX_LABELS = 4, 3, 4, 4
+MAX_PARTICLES = 1024   # SLODE_MAX_PARTICLES
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
 EULER, MIDPOINT, RK4, DOPRI5, BOSH3, FEHLBERG2, ADAPTIVE_HEUN = 0, 1, 2, 3, 4, 5, 6
 ALD, GAUSS = 0, 1
@@ -28,7 +29,7 @@ class Shape(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "C", "L", "S", "H", "F", "K", "P", "Hc", "n_u", "n_groups")] + [
         ("groups", Group * MAX_GROUPS), ("method", C.c_int32), ("likelihood", C.c_int32),
         ("quantile_diff", C.c_float), ("rtol", C.c_float), ("atol", C.c_float), ("n_aux", C.c_int32), ("U", C.c_int32),
-        ("aux_mult", C.c_float), ("aux", Aux * MAX_AUX), ("aux_in_main", C.c_int32), ("grad_mode", C.c_int32)]
+        ("aux_mult", C.c_float), ("aux", Aux * MAX_AUX), ("aux_in_main", C.c_int32), ("grad_mode", C.c_int32), ("particles", C.c_int32)]
 
 
 class Layout(C.Structure):

@@ -77,13 +77,16 @@ __global__ void __launch_bounds__(128) aux_kernel(const AuxK k) {
   }
   __syncthreads();
 
+  // particles (slode_common.h): grid.y = particle kp; data rows b as with one particle, outputs in virtual row b + pv, slab row blockIdx.x + kp * gridDim.x
+  const int kp = (int)blockIdx.y;
+  const long long pv = (long long)kp * k.B;
   for (int b = blockIdx.x; b < k.B; b += gridDim.x) {
     // ---- the head's latent sample z_g = loc + scale * eps (lane l' < z_dim), -log N(z_g; loc, scale) ----
     float sc = 1.f, e = 0.f;
     if (head_on && j < zd) {
       const long long i = (long long)b * L + ax.z_off + j;
       const float loc = k.loc[i];
-      sc = k.scale[i]; e = slode_eps_at(k.rng, k.eps, b, L, ax.z_off + j);
+      sc = k.scale[i]; e = slode_eps_at(k.rng, k.eps, b, L, ax.z_off + j, kp, k.B);
       const float z = fmaf(sc, e, loc);
       const float zq = (z - loc) / sc;
       loss_acc += logf(sc) + 0.91893853320467274178f + 0.5f * zq * zq;
@@ -168,25 +171,25 @@ __global__ void __launch_bounds__(128) aux_kernel(const AuxK k) {
       if (head_on && j < zd) {
         const int l = ax.z_off + j;
         const float gsc = fmaf(gz, e, 1.0f / sc);               // d(-log N)/dloc = 0 (z moves with loc); + d(log scale)/dscale
-        if (k.g_loc) { k.g_loc[(long long)b * L + l] = gz; k.g_scale[(long long)b * L + l] = gsc; }
+        if (k.g_loc) { k.g_loc[(b + pv) * L + l] = gz; k.g_scale[(b + pv) * L + l] = gsc; }
         s_gl[l] = gz; s_gs[l] = gsc * sc;
       }
       if (k.g_loc && tid < L) {   // dims outside every head
         bool in = false;
         for (int h2 = 0; h2 < k.n_aux; ++h2) in = in || (tid >= k.aux[h2].z_off && tid < k.aux[h2].z_off + k.aux[h2].z_dim);
-        if (!in) { k.g_loc[(long long)b * L + tid] = 0.f; k.g_scale[(long long)b * L + tid] = 0.f; }
+        if (!in) { k.g_loc[(b + pv) * L + tid] = 0.f; k.g_scale[(b + pv) * L + tid] = 0.f; }
       }
       if (k.g_pre) {
         // encoder heads + tanh, backward (models/encoder_conv.py:48-51): thread <-> hidden unit of the encoder
         __syncthreads();
-        if (tid < L) { k.glat[(long long)b * 128 + tid] = s_gl[tid]; k.glat[(long long)b * 128 + 64 + tid] = s_gs[tid]; }
+        if (tid < L) { k.glat[(b + pv) * 128 + tid] = s_gl[tid]; k.glat[(b + pv) * 128 + 64 + tid] = s_gs[tid]; }
         if (zw_regs) {
           if (tid < k.Hc) {
             float g0 = 0.f, g1 = 0.f;
 #pragma unroll
             for (int l = 0; l < ZW; ++l)
               if (l < L) { g0 = fmaf(zw0[l], s_gl[l], g0); g1 = fmaf(zw1[l], s_gs[l], g1); }
-            k.g_pre[(long long)b * 64 + tid] = (g0 + g1) * (1.f - enc_hv * enc_hv);
+            k.g_pre[(b + pv) * 64 + tid] = (g0 + g1) * (1.f - enc_hv * enc_hv);
           }
         } else {
           for (int mm = tid; mm < k.Hc; mm += blockDim.x) {
@@ -197,7 +200,7 @@ __global__ void __launch_bounds__(128) aux_kernel(const AuxK k) {
               g0 = fmaf(k.enc_zloc_w[l * k.Hc + mm], s_gl[l], g0);
               g1 = fmaf(k.enc_zls_w[l * k.Hc + mm], s_gs[l], g1);
             }
-            k.g_pre[(long long)b * 64 + mm] = (g0 + g1) * (1.f - hvv * hvv);
+            k.g_pre[(b + pv) * 64 + mm] = (g0 + g1) * (1.f - hvv * hvv);
           }
         }
         __syncthreads();   // s_gl / s_gs are rewritten by the next trajectory
@@ -208,7 +211,7 @@ __global__ void __launch_bounds__(128) aux_kernel(const AuxK k) {
   const float v = wave_sum(loss_acc);
   if ((tid & 63) == 0) s_red[tid >> 6] = v;
   __syncthreads();
-  float* slab = k.slabs + (long long)blockIdx.x * k.slab_stride;
+  float* slab = k.slabs + ((long long)blockIdx.x + (long long)blockIdx.y * gridDim.x) * k.slab_stride;
   if (tid == 0) {
     float t = 0.f;
     for (int w = 0; w < ((int)blockDim.x >> 6); ++w) t += s_red[w];
@@ -254,7 +257,7 @@ hipError_t slode_launch_aux(const AuxLaunch& a, hipStream_t stream) {
   const int nthreads = s.n_aux <= 2 ? 64 : 128;
   int zmax = 0;
   for (int q = 0; q < s.n_aux; ++q) zmax = s.aux[q].z_dim > zmax ? s.aux[q].z_dim : zmax;
-  if (zmax <= 16) SLODE_LAUNCH("aux", aux_kernel<16>, dim3(a.grid), dim3(nthreads), 0, stream, k);
-  else SLODE_LAUNCH("aux", aux_kernel<SLODE_MAX_L>, dim3(a.grid), dim3(nthreads), 0, stream, k);
+  if (zmax <= 16) SLODE_LAUNCH("aux", aux_kernel<16>, dim3(a.grid, a.particles > 1 ? a.particles : 1), dim3(nthreads), 0, stream, k);
+  else SLODE_LAUNCH("aux", aux_kernel<SLODE_MAX_L>, dim3(a.grid, a.particles > 1 ? a.particles : 1), dim3(nthreads), 0, stream, k);
   return hipGetLastError();
 }

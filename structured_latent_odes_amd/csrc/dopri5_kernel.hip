@@ -40,6 +40,7 @@ constexpr int JL = 4;           // hidden units per lane (H <= 32)
 
 struct DpK {
   int B, T, L;
+  int Bd;   // data rows: B = K * Bd virtual trajectories, particle-major (slode_common.h); loc / scale are [Bd][L], eps / z_out / eps_out [B][L]
   const float *times, *z, *w1, *b1, *w2, *b2, *wh, *bh, *wg, *bg, *wd, *bd;
   const float *loc, *scale, *eps;   // z == nullptr: z = loc + scale * eps (the guide's sample), written to z_out
   float* x;
@@ -606,7 +607,12 @@ __device__ __forceinline__ void latent_request(const DpK& k, long long bb, int l
     const int l = min(lg + LPT * q, L - 1);
     const long long i = bb * L + l;
     if (k.z) { r.lo[q] = k.z[i]; r.sc[q] = 0.f; r.ep[q] = 0.f; }
-    else { r.lo[q] = k.loc[i]; r.sc[q] = k.scale[i]; r.ep[q] = slode_eps_at(k.rng, k.eps, bb, L, l); }
+    else {
+      const int kp = (int)bb / k.Bd;   // particle kp of data row bd: noise of drawing call n + kp at trajectory bd
+      const long long bd = bb - (long long)kp * k.Bd, id = bd * L + l;
+      r.lo[q] = k.loc[id]; r.sc[q] = k.scale[id];
+      r.ep[q] = k.rng.on ? slode_rng_normal(slode_rng_particle(k.rng, kp), bd, l) : k.eps[i];
+    }
   }
 }
 template <int LPT>
@@ -966,6 +972,7 @@ struct DpBK {
   const float *scale, *enc_hid, *enc_zloc_w, *enc_zls_w;
   float *g_pre, *glat;
   int Hc, zw_off;   // zw_off: floats from s_big to the dedicated [2][L][Hc] copy of the encoder head weights
+  int Bd;           // data rows (DpK::Bd): scale and enc_hid are [Bd] rows, everything else [B] = [K * Bd]
 };
 
 namespace grp {
@@ -1514,6 +1521,7 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
     float* const l_glat = *(float* const __attribute__((address_space(4)))*)(ka0 + offsetof(DpBK, glat));
     const float* const l_scale = *(const float* const __attribute__((address_space(4)))*)(ka0 + offsetof(DpBK, scale));
     const bool l_enc = *(float* const __attribute__((address_space(4)))*)(ka0 + offsetof(DpBK, g_pre)) != nullptr;
+    const long long l_bd = (int)bb % *(const int __attribute__((address_space(4)))*)(ka0 + offsetof(DpBK, Bd));   // this trajectory's data row
     float* s_g = s_big + 2 * H * L;   // [BTP][2][L]
     for (int l0 = tid & (LB - 1); l0 < L; l0 += LB * 4) {   // (sixteen lanes per trajectory: four latent dims per lane and pass)
       float gl_[4], gs_[4], ep_[4], sc_[4];
@@ -1521,7 +1529,7 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
       for (int q = 0; q < 4; ++q) {
         const long long i = bb * L + min(l0 + q * LB, L - 1);
         gl_[q] = k.g_loc[i]; gs_[q] = k.g_scale[i]; ep_[q] = k.eps[i];
-        sc_[q] = l_enc ? l_scale[i] : 0.f;
+        sc_[q] = l_enc ? l_scale[l_bd * L + min(l0 + q * LB, L - 1)] : 0.f;
       }
       __builtin_amdgcn_sched_barrier(0);
       float a1[4], a2[4];   // through the init net / through the dynamics' hidden layer: 8 independent chains, unit-major
@@ -1607,7 +1615,7 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
     float* const e_g_pre = DP5_KFIELD(fptr_t, g_pre);
     if (e_g_pre != nullptr) {
       const float* const e_hid = DP5_KFIELD(cfptr_t, enc_hid);
-      const int Hc = DP5_KFIELD(int, Hc), zw_off = DP5_KFIELD(int, zw_off), eB = DP5_KFIELD(int, B);
+      const int Hc = DP5_KFIELD(int, Hc), zw_off = DP5_KFIELD(int, zw_off), eB = DP5_KFIELD(int, B), eBd = DP5_KFIELD(int, Bd);
 #undef DP5_KFIELD
       const float* s_zw = s_big + zw_off;     // [2][L][Hc]  z_loc.weight | z_scale.0.weight (in place since the prologue)
       const float* s_g = s_big + 2 * H * L;   // [BTP][2][L] dLoss/dloc | dLoss/dscale * scale: written by the latent-gradient loop above
@@ -1620,7 +1628,7 @@ __global__ void __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(2))) d
 #pragma unroll
         for (int q = 0; q < RQ; ++q) {
           g0[q] = 0.f;
-          hv[q] = e_hid[min((long long)blockIdx.x * BTP + rq * RQ + q, (long long)eB - 1) * Hc + mm];   // (requested ahead of the sums)
+          hv[q] = e_hid[(long long)(min((int)blockIdx.x * BTP + rq * RQ + q, eB - 1) % eBd) * Hc + mm];   // (requested ahead of the sums)
         }
         for (int l = 0; l < L; ++l) {
           const float w0 = s_zw[l * Hc + mm], w1 = s_zw[(L + l) * Hc + mm];
@@ -1688,6 +1696,7 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
                                float* x, hipStream_t stream, const DopriRec* rec) {
   DpK k;
   k.B = s.B; k.T = s.T; k.L = s.L; k.times = times; k.z = z; k.x = x;
+  k.Bd = rec && rec->data_rows > 0 ? rec->data_rows : s.B;
   k.loc = k.scale = k.eps = nullptr; k.z_out = nullptr; k.rec = nullptr; k.nrec = nullptr; k.kmax = 0;
   k.rng = RngK{}; k.eps_out = nullptr; k.tabs = nullptr;
   if (rec) { k.loc = rec->loc; k.scale = rec->scale; k.eps = rec->eps; k.z_out = rec->z_out; k.rec = rec->rec; k.nrec = rec->nrec; k.kmax = rec->kmax;
@@ -1730,6 +1739,7 @@ hipError_t slode_launch_dopri5_bwd(const slode_shape& s, const slode_layout& lay
   k.tabs = rec.tabs;
   k.snap = snap; k.g_loc = g_loc; k.g_scale = g_scale; k.eps = rec.eps;
   k.B = s.B; k.T = s.T; k.L = s.L; k.kmax = rec.kmax; k.drop_z = drop_z;
+  k.Bd = rec.data_rows > 0 ? rec.data_rows : s.B;
   k.times = times; k.z = rec.z_out; k.gx = gx; k.rec = rec.rec; k.nrec = rec.nrec;
   k.w1 = p + lay.init_w1; k.b1 = p + lay.init_b1; k.w2 = p + lay.init_w2; k.b2 = p + lay.init_b2;
   k.wh = p + lay.dyn_wh; k.bh = p + lay.dyn_bh; k.wg = p + lay.dyn_wg; k.bg = p + lay.dyn_bg; k.wd = p + lay.dyn_wd; k.bd = p + lay.dyn_bd;

@@ -29,6 +29,7 @@ struct ReduceK {
   // optional fused Adam (single-process training): applied to element i right after its gradient is final
   AdamK ad;     // ad.p == nullptr: no fused Adam
   int n_total;  // >= n_params: parameters appended by the caller (zero main-loss gradient) are stepped too
+  float inv_k; int particles;   // the ode slabs hold sums over K particles: loss and ode-segment gradient take the mean (TailK::inv_k)
 };
 
 __global__ void __launch_bounds__(256) slab_stage1_kernel(const Stage1 fam0, const Stage1 fam1) {
@@ -44,7 +45,7 @@ __global__ void reduce_kernel(const ReduceK k) {
   if (i == 0 && k.loss_out && k.ode_slabs) {
     double acc = 0.0;
     for (int w = 0; w < k.ode_n; ++w) acc += (double)k.ode_slabs[(long long)w * k.ode_stride];
-    k.loss_out[0] = (float)acc;
+    k.loss_out[0] = (float)(k.particles > 1 ? acc / (double)k.particles : acc);
   }
   if (k.grads == nullptr) return;
   const int n_all = k.ad.p ? k.n_total : k.n_params;
@@ -59,7 +60,7 @@ __global__ void reduce_kernel(const ReduceK k) {
       else if (i >= k.lin_b_off && i < k.lin_b_off + (k.small_count - k.n_conv_part)) j = k.n_conv_part + (i - k.lin_b_off);
     }
     if (k.ode_slabs && i >= k.ode_begin && i < k.ode_begin + k.nseg) {
-      g = strided_sum(k.ode_slabs + 1 + (i - k.ode_begin), k.ode_stride, k.ode_n);
+      g = strided_sum(k.ode_slabs + 1 + (i - k.ode_begin), k.ode_stride, k.ode_n) * k.inv_k;
       write = true;
     } else if (k.lin_slabs && i >= k.lin_w_off && i < k.lin_w_off + k.lin_count) {
       g = strided_sum(k.lin_slabs + (i - k.lin_w_off), k.lin_count, k.lin_n);
@@ -290,6 +291,7 @@ hipError_t slode_launch_reduce(const ReduceLaunch& a_in, hipStream_t stream) {
   k.lin_count = a.folded ? s.F * s.C * s.K + s.F : s.Hc * FQ;
   k.lin_w_off = a.folded ? a.lay.conv_w : a.lay.lin_w;
   k.grads = a.grads; k.loss_out = a.loss_out; k.n_params = a.lay.n_params; k.zero_rest = a.zero_rest;
+  k.particles = a.particles > 1 ? a.particles : 1; k.inv_k = 1.0f / (float)k.particles;
   int n = a.grads ? a.lay.n_params : 1;
   if (a.adam.p && a.grads) {
     k.ad = make_adamk(&a.adam);
@@ -379,6 +381,39 @@ hipError_t slode_launch_pack_payload(const float* gslabs, const float* gslabs_lo
                                      int total, hipStream_t stream) {
   SLODE_LAUNCH("pack_payload", pack_payload_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, gslabs, gslabs_loc, gslabs_ls, gsplit,
                Hc * (CT + 1), L * (Hc + 1), ode_part, ode_stride, ode_n, ode_count, out, o_loc, o_ls, o_ode, total);
+  return hipGetLastError();
+}
+
+// The particle fold (slode_common.h: slode_launch_particle_fold).  Every thread owns four consecutive floats of a data row (or one, when
+// the array is not a whole number of float4) and reads them from the K particle rows, which lie n floats apart: K independent 16-byte
+// loads, summed in the order k = 0, 1, ..., K - 1 -- the step stays bitwise repeatable -- and written over particle 0's row as the mean.
+// In place is safe: the thread that writes element i of rows [0, B) is the only one that reads it.
+struct PFoldK { float* p; long long n; };
+__global__ void __launch_bounds__(256) particle_fold_kernel(const PFoldK fa, const PFoldK fb, int K, float inv_k) {
+  typedef float f4_t __attribute__((ext_vector_type(4)));
+  const PFoldK f = blockIdx.y == 0 ? fa : fb;
+  if (f.p == nullptr) return;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if ((f.n & 3) == 0) {
+    if (4 * i >= f.n) return;
+    f4_t* p = reinterpret_cast<f4_t*>(f.p) + i;
+    const long long n4 = f.n >> 2;
+    f4_t acc = p[0];
+    for (int k = 1; k < K; ++k) acc += p[(long long)k * n4];
+    p[0] = acc * inv_k;
+  } else {
+    if (i >= f.n) return;
+    float acc = f.p[i];
+    for (int k = 1; k < K; ++k) acc += f.p[(long long)k * f.n + i];
+    f.p[i] = acc * inv_k;
+  }
+}
+hipError_t slode_launch_particle_fold(float* a, long long n_a, float* b, long long n_b, int K, hipStream_t stream) {
+  const long long n_max = n_a > n_b ? n_a : n_b;
+  // (one thread per float4 where an array allows it; an array that does not takes one thread per float: the grid covers both)
+  const long long threads = ((n_a & 3) == 0 && (n_b & 3) == 0) ? (n_max + 3) / 4 : n_max;
+  SLODE_LAUNCH("particle_fold", particle_fold_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, stream, PFoldK{a, n_a}, PFoldK{b, n_b}, K,
+               1.0f / (float)K);
   return hipGetLastError();
 }
 

@@ -96,6 +96,7 @@ struct OdeK {
   long long sb, sc, st;
   float *x_out, *z_out, *g_loc, *g_scale, *slabs;
   int slab_stride, backward, with_ll;
+  int particles;   // grid.y: particles per data row (slode_common.h)
   // fused encoder-head backward (folded encoder path): g_pre[b][m] = (1 - hid^2) * (zloc_w^T g_loc + zls_w^T (g_scale * scale))
   const float *enc_hid, *enc_zloc_w, *enc_zls_w;
   const float *enc_weff, *enc_beff, *enc_zloc_b, *enc_zls_b;   // ENCF: folded encoder weights of this step (fold launch), head biases
@@ -587,6 +588,11 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   const int traj = PK > 1 ? wave_wg / NWT : 0;
   const int tid = PK > 1 ? (((wave_wg % NWT) + NWT - (traj % NWT)) % NWT) * 64 + (int)(threadIdx.x & 63) : (int)threadIdx.x;
   const int vblk = PK > 1 ? (int)blockIdx.x * PK + traj : (int)blockIdx.x, vgrid = (int)gridDim.x * PK;
+  // particles (slode_common.h): grid.y = particle kp; this workgroup's data rows are b = vblk, vblk + vgrid, ... as with one particle, its
+  // virtual rows b + pv and its slab row vblk + kp * vgrid.  One particle: kp = 0, pv = 0.
+  const int kp = PK > 1 ? 0 : (int)blockIdx.y;
+  const long long pv = (long long)kp * k.B, srow = vblk + (long long)kp * vgrid;
+  const RngK rngp = slode_rng_particle(k.rng, kp);
   const int T = T_ ? T_ : k.T, C = C_ ? C_ : k.C, L = L_ ? L_ : k.L, Q = Q_ ? Q_ : k.Q;
   const int method = M_ >= 0 ? M_ : k.method;
   const int R = M_ >= 0 ? (M_ == SLODE_EULER ? 1 : (M_ == SLODE_MIDPOINT ? 2 : 3)) : k.R;
@@ -764,7 +770,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
       if (!ENCF) v_l0 = pl_loc[(long long)b_first * L + lc];     // (pure solve: z_in)
       if (pl_scale != nullptr) {
         if (!ENCF) v_l1 = pl_scale[(long long)b_first * L + lc];
-        v_l2 = k.rng.on ? slode_rng_normal(k.rng, b_first, lc) : pl_eps[(long long)b_first * L + lc];
+        v_l2 = k.rng.on ? slode_rng_normal(rngp, b_first, lc) : pl_eps[(b_first + pv) * L + lc];
       }
       if (pl_u != nullptr) v_u = k.lab.n ? slode_label_at(k.lab, pl_u, k.nu, b_first, min(tid, k.nu - 1)) : pl_u[(long long)b_first * k.nu + min(tid, k.nu - 1)];
     }
@@ -943,7 +949,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   }
   STAMP(13);
   if (BWD) {   // elements no phase owns (e.g. label-head parameters the main loss does not score): zero gradient
-    float* sl = k.slabs + (long long)vblk * k.slab_stride + 1;
+    float* sl = k.slabs + srow * k.slab_stride + 1;
     for (int z = 0; z < k.nz; ++z)
       for (int i = k.zlo[z] + tid; i < k.zhi[z]; i += NT) sl[i] = 0.f;
   }
@@ -985,7 +991,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
     if (!ONE) asm volatile("" : "+v"(tid));
     // Every gradient element of the segment has exactly one owning thread per trajectory and goes straight to this workgroup's
     // slab (no LDS copy): written on the workgroup's first trajectory, added to on later ones (same owner, program order).
-    float* const sl1 = k.slabs + (long long)vblk * k.slab_stride + 1;
+    float* const sl1 = k.slabs + srow * k.slab_stride + 1;
     const bool first_traj = ONE || b == vblk;
     auto accum = [&](int idx, float v) { float* d = sl1 + idx; *d = first_traj ? v : (*d + v); };
     if (COLDB && !ONE && b != vblk) {
@@ -1402,7 +1408,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
       constexpr int CLc = T_ ? ((T_ - 1) + (NTc / 64) * SCAN_NCH - 1) / ((NTc / 64) * SCAN_NCH) : 8;   // steps per lane of the forward scan
       block_affine_scan<S, false, (CLc < 8 ? CLc : 8)>(s_A, s_x, T, tid, NT, s_ct, BAR);   // (the chunk-sum buffer of P6 carries the waves' total maps)
     } else {   // score the adaptive solver's trajectory instead
-      const float* xe = k.x_ext + (long long)b * T * S;
+      const float* xe = k.x_ext + (b + pv) * T * S;
       for (int i = tid; i < T * S; i += NT) s_x[i] = xe[i];
     }
     // what P3 needs of the likelihood scales besides the scale itself comes from the per-step table when there is one: issued ahead of
@@ -1466,7 +1472,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
             }
           }
           if (BWD) {  // constant_std gradient: thread t owns slab entry (c, t); softplus'(x) = 1 - exp(-softplus(x))
-            float* dst = k.slabs + (long long)vblk * k.slab_stride + 1 + k.o_cstd + c * T + t;
+            float* dst = k.slabs + srow * k.slab_stride + 1 + k.o_cstd + c * T + t;
             const float val = gsig * (use_tab ? t_ds[c] : 1.f - expf(-sig));
             *dst = (ONE || b == vblk) ? val : (*dst + val);
           }
@@ -1476,7 +1482,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
           if (ext) {   // dLoss/dx goes to the adaptive solver's backward pass
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-              if (k.gx_out) k.gx_out[((long long)b * T + t) * S + s] = gx[s];
+              if (k.gx_out) k.gx_out[((b + pv) * T + t) * S + s] = gx[s];
             }
           } else {
 #pragma unroll
@@ -1943,17 +1949,17 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
             const float sc = s_gls[L + l];
             const float gsc = fmaf(gz, s_gpl[L + l], -1.0f / sc);
             if (k.g_loc) {
-              k.g_loc[(long long)b * L + l] = gz;
-              k.g_scale[(long long)b * L + l] = gsc;
+              k.g_loc[(b + pv) * L + l] = gz;
+              k.g_scale[(b + pv) * L + l] = gsc;
             }
             if (k.g_pre) {  // hand (g_loc, g_scale * scale) to the head-backward block after the trajectory's last barrier
               s_gzl[l] = gz;
               s_gpl[L + l] = gsc * sc;
-              k.glat[(long long)b * 128 + l] = gz;
-              k.glat[(long long)b * 128 + 64 + l] = gsc * sc;
+              k.glat[(b + pv) * 128 + l] = gz;
+              k.glat[(b + pv) * 128 + 64 + l] = gsc * sc;
             }
           } else {
-            k.g_loc[(long long)b * L + l] = gz;
+            k.g_loc[(b + pv) * L + l] = gz;
           }
         }
         STAMP(19);
@@ -2044,13 +2050,13 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
           g1 = fmaf(k.enc_zls_w[l * Hc + mm], s_gpl[L + l], g1);
         }
       }
-      k.g_pre[(long long)b * 64 + mm] = (g0 + g1) * (1.f - hv * hv);
+      k.g_pre[(b + pv) * 64 + mm] = (g0 + g1) * (1.f - hv * hv);
     }
     if (!ONE && b + vgrid < k.B && tid >= 64 && tid < 128) {   // next trajectory's latent inputs (P0a is long past)
       const int bn = b + vgrid, t1 = tid - 64;
       if (t1 < L) {
         if (k.loc != nullptr) {
-          const float a0 = k.loc[(long long)bn * L + t1], a1 = k.scale[(long long)bn * L + t1], a2 = slode_eps_at(k.rng, k.eps, bn, L, t1);
+          const float a0 = k.loc[(long long)bn * L + t1], a1 = k.scale[(long long)bn * L + t1], a2 = k.rng.on ? slode_rng_normal(rngp, bn, t1) : k.eps[(bn + pv) * L + t1];
           s_pf[t1] = a0; s_pf[pad4(L) + t1] = a1; s_pf[2 * pad4(L) + t1] = a2;
         } else {
           s_pf[t1] = k.z_in[(long long)bn * L + t1];
@@ -2063,7 +2069,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   }  // trajectories
 
   // ---- workgroup epilogue: loss partial, then the LDS gradient segment leaves as one slab ------------------------------
-  float* slab = k.slabs + (long long)vblk * k.slab_stride;
+  float* slab = k.slabs + srow * k.slab_stride;
   if (ts_bad) loss_acc = __builtin_nanf("");
   const float lw = wave_sum(loss_acc);
   if ((tid & 63) == 0) s_red[tid >> 6] = lw;
@@ -2086,7 +2092,8 @@ template <int S, int H, bool BWD, int T_, int C_, int L_, int Q_, int M_, bool R
 hipError_t launch_one(const OdeK& k, int grid, int nthreads, size_t lds, hipStream_t stream) {
   auto fn = ode_elbo_kernel<S, H, BWD, T_, C_, L_, Q_, M_, RA, ONE, ALG, PK, ENCF, SOFTB>;
   (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  SLODE_LAUNCH("ode_elbo", fn, dim3(grid), dim3(nthreads), lds, stream, k.stage_t, k.pseg, k.loc ? k.loc : k.z_in, k.loc ? k.scale : nullptr,
+  if (PK > 1 && k.particles > 1) return hipErrorInvalidValue;   // (refused by the caller: the packed forms take one particle)
+  SLODE_LAUNCH("ode_elbo", fn, dim3(grid, k.particles), dim3(nthreads), lds, stream, k.stage_t, k.pseg, k.loc ? k.loc : k.z_in, k.loc ? k.scale : nullptr,
                k.eps, k.u, k.sigtab ? k.sigtab : k.cstd, k);
   return hipGetLastError();
 }
@@ -2188,6 +2195,7 @@ hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, s
   k.enc_zloc_w = p + lay.zloc_w; k.enc_zls_w = p + lay.zls_w; k.enc_zloc_b = p + lay.zloc_b; k.enc_zls_b = p + lay.zls_b;
   k.enc_weff = a.enc_weff; k.enc_beff = a.enc_beff; k.enc_hid_out = a.enc_hid_out;
   k.rng = a.rng; k.lab = a.lab;
+  k.particles = a.particles > 1 ? a.particles : 1;
   if (k.lab.n > 0 && !k.u) k.u = k.lab.p[0];   // (non-null = "this launch has labels"; the reads go through the accessor)
   if (k.rng.on && !k.eps) k.eps = k.loc;       // (never dereferenced: a valid address for the preloaded argument)
 

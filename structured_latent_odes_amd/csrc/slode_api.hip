@@ -48,6 +48,9 @@ static const char* method_name(int method) {
 // the adaptive methods: dopri5 and torchdiffeq's other RKAdaptiveStepsizeODESolver pairs (dopri5_kernel.hip)
 static bool is_adaptive(int method) { return slode_is_adaptive(method); }
 
+// particles of a step (slode_shape::particles; 0 and 1 both mean one)
+static int particles_of(const slode_shape& s) { return s.particles > 1 ? s.particles : 1; }
+
 static int stages_per_step(int method) { return method == SLODE_EULER ? 1 : (method == SLODE_MIDPOINT ? 2 : 3); }
 
 static const char* check_shape(const slode_shape* s) {
@@ -85,6 +88,8 @@ static const char* check_shape(const slode_shape* s) {
     if (x.u_off < 0 || x.u_dim < 1 || x.u_dim > 8 || x.u_off + x.u_dim > s->n_u) return "aux head label range outside [0, n_u) or wider than 8";
   }
   if (s->grad_mode != SLODE_GRAD_EXACT && s->grad_mode != SLODE_GRAD_REFERENCE_ADJOINT) return "grad_mode must be SLODE_GRAD_EXACT or SLODE_GRAD_REFERENCE_ADJOINT";
+  if (s->particles < 0 || s->particles > SLODE_MAX_PARTICLES) return "particles out of range [0, 1024] (0 and 1: one particle)";
+  if ((long long)s->B * (s->particles > 1 ? s->particles : 1) > 0x3fffffff) return "B x particles exceeds 2^30 - 1 trajectories";
   return nullptr;
 }
 
@@ -231,8 +236,13 @@ static int ode_grid_for(slode_handle h, const slode_shape& s) {
   long long g = (long long)cus * occ;
   // One workgroup per trajectory up to 65,536 trajectories (the hardware queues the workgroups; one slab per trajectory);
   // beyond that (and under the SLODE_ODE_LOOP handle flag, which the persistent-loop tests set) a resident grid loops over them.
-  if (s.B <= 65536 && !(h && h->ode_loop)) g = s.B;
-  else if (h && h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+  // With K particles the grid is (g, K): g workgroups per particle over the B data rows, the same rule applied to the B * K virtual trajectories.
+  const int K = particles_of(s);
+  if ((long long)s.B * K <= 65536 && !(h && h->ode_loop)) g = s.B;
+  else {
+    if (K > 1) g = g / K > 0 ? g / K : 1;
+    if (h && h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+  }
   if (g > s.B) g = s.B;
   return (int)g;
 }
@@ -260,7 +270,13 @@ static Workspace carve(slode_handle h, const slode_shape& s_in, const slode_layo
   Workspace w{};
   const slode_shape s = scorer_shape(s_in);
   const bool dp5 = is_adaptive(s_in.method);
-  w.dp_rows = dp5 ? slode_dopri5_rows(s) : 0;
+  // particles: K * B virtual trajectories (slode_common.h).  Per DATA row: loc, scale, pooled, hid.  Per VIRTUAL row: the latent and
+  // pre-activation gradients (folded over the particles into rows [0, B) before the encoder backward), the slab rows (K grids) and
+  // everything of the adaptive solve (sv: the shape its kernels see, B = K * B).
+  const int K = particles_of(s);
+  const size_t BK = (size_t)s.B * K;
+  slode_shape sv = s; sv.B = (int)BK; sv.particles = 0;
+  w.dp_rows = dp5 ? slode_dopri5_rows(sv) : 0;
   const int n_conv = s.T - s.K + 1, FQ = s.F * (n_conv - s.P + 1);
   w.ode_grid = ode_grid_for(h, s);
   w.ode_stride = (int)align_up((size_t)(lay.ode_end - lay.ode_begin) + 1);
@@ -274,10 +290,10 @@ static Workspace carve(slode_handle h, const slode_shape& s_in, const slode_layo
   w.scale = take((size_t)s.B * s.L);
   w.pooled = take((size_t)s.B * FQ);
   w.hid = take((size_t)s.B * s.Hc);
-  w.g_loc = take((size_t)s.B * s.L);
-  w.g_scale = take((size_t)s.B * s.L);
-  w.g_pre = take((size_t)s.B * 64);
-  w.ode_slabs = take((size_t)(w.ode_grid + w.dp_rows) * w.ode_stride);   // dopri5: its backward kernel's rows follow the scorer's
+  w.g_loc = take(BK * s.L);
+  w.g_scale = take(BK * s.L);
+  w.g_pre = take(BK * 64);
+  w.ode_slabs = take(((size_t)w.ode_grid * K + w.dp_rows) * w.ode_stride);   // dopri5: its backward kernel's rows follow the scorer's
   w.ode_part = take((size_t)SLODE_REDUCE_GROUPS * w.ode_stride);
   w.small_slabs = take((size_t)w.small_grid * w.small_stride);
   w.small_part = take((size_t)SLODE_REDUCE_GROUPS * w.small_stride);
@@ -289,22 +305,22 @@ static Workspace carve(slode_handle h, const slode_shape& s_in, const slode_layo
   w.beff = take(64);
   w.gslabs = take((size_t)w.gsplit * s.Hc * (s.C * s.T + 1));
   w.conv_slabs = take((size_t)s.Hc * (s.F * s.C * s.K + s.F));
-  w.glat = take((size_t)s.B * 128);
+  w.glat = take(BK * 128);
   w.gslabs2 = take((size_t)w.gsplit * s.L * (s.Hc + 1));
   w.gslabs3 = take((size_t)w.gsplit * s.L * (s.Hc + 1));
   w.counter = reinterpret_cast<unsigned int*>(take(32 * (16 + SLODE_MAX_HC)));   // arrival counters 128 B apart: one per conv-filter pair (0..7), the in-launch fold's (8, 9, 16 + m)
   w.sigtab = take(4 * (size_t)s.C * s.T);
   if (dp5) {
-    w.dp_kmax = slode_dopri5_kmax(s);
-    w.dp_x = take((size_t)s.B * s.T * s.S);
-    w.dp_gx = take((size_t)s.B * s.T * s.S);
-    w.dp_gz = take((size_t)s.B * s.L);
-    w.dp_z = take((size_t)s.B * s.L);
-    w.dp_nrec = reinterpret_cast<int*>(take((size_t)s.B));
-    w.dp_rec = take((size_t)w.dp_kmax * s.B * (s.S + 2));
-    w.dp_tabs = take((size_t)slode_dopri5_rows(s) * slode_dopri5_tab_floats(s));   // the forward kernel's set-up tables, handed to the reverse sweep
-    w.dp_snap = take((size_t)s.B * 2 * s.H * 4 * s.S);   // running sums parked at the hidden units' switching times, per lane group (dopri5_kernel.hip)
-    w.dp_eps = take((size_t)s.B * s.L);              // the noise the forward kernel drew (eps == NULL), for the scorer and the reverse sweep
+    w.dp_kmax = slode_dopri5_kmax(sv);
+    w.dp_x = take(BK * s.T * s.S);
+    w.dp_gx = take(BK * s.T * s.S);
+    w.dp_gz = take(BK * s.L);
+    w.dp_z = take(BK * s.L);
+    w.dp_nrec = reinterpret_cast<int*>(take(BK));
+    w.dp_rec = take((size_t)w.dp_kmax * BK * (s.S + 2));
+    w.dp_tabs = take((size_t)slode_dopri5_rows(sv) * slode_dopri5_tab_floats(s));   // the forward kernel's set-up tables, handed to the reverse sweep
+    w.dp_snap = take(BK * 2 * s.H * 4 * s.S);   // running sums parked at the hidden units' switching times, per lane group (dopri5_kernel.hip)
+    w.dp_eps = take(BK * s.L);              // the noise the forward kernel drew (eps == NULL), for the scorer and the reverse sweep
   }
   w.bytes = o * sizeof(float);
   return w;
@@ -485,6 +501,7 @@ struct StepCall {
 struct Step {   // what the stages share, worked out once by step_setup
   slode_handle h; const slode_shape& s; const slode_layout& lay; const StepCall& c;
   bool aux = false, dp5 = false, bwd = false, folded = false, t_major = false;
+  int K = 1;   // particles (slode_shape::particles): K * B virtual trajectories, particle-major (slode_common.h)
   RngK rng{}; const float* u = nullptr; Workspace w{};
 };
 // the slab rows the tail reduces: n rows of [loss | flat elements [part_lo, part_hi)]; rows [0, zr_rows) carry nothing in slab columns
@@ -569,8 +586,15 @@ static int step_setup(Step& p) {
   const bool missing = c.phase == STEP_APPLY ? !c.payload || !c.grads
                                              : (!p.aux && (!c.times || !c.stage_t)) || !c.obs || (c.phase == STEP_WHOLE ? !c.loss_out : !c.payload);
   if (missing || !c.obs_strides || !c.workspace) return fail(h, SLODE_EINVAL, "a required pointer is NULL");
-  // eps == NULL: this call draws the guide's noise inside its kernels -- call number rng_counter of the handle's Philox stream
-  if (!c.eps && c.phase != STEP_APPLY) p.rng = rng_of(h, h->rng_counter++);
+  p.K = particles_of(s);
+  // eps == NULL: this call draws the guide's noise inside its kernels -- call number rng_counter of the handle's Philox stream; K particles
+  // are the K drawing calls rng_counter .. rng_counter + K - 1 (particle k: call rng_counter + k, same trajectory index)
+  if (!c.eps && c.phase != STEP_APPLY) { p.rng = rng_of(h, h->rng_counter); h->rng_counter += (uint64_t)p.K; }
+  if (p.K > 1) {
+    if (c.x_out || c.z_out) return fail(h, SLODE_EINVAL, "x_out / z_out take one particle: the shape has particles = %d", p.K);
+    if (h->fold_on || h->ode_pack || h->ode_alg)
+      return fail(h, SLODE_EINVAL, "particles = %d cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG", p.K);
+  }
   p.u = c.lab.n > 0 && !c.u ? c.lab.p[0] : c.u;   // (non-null = "labels present"; the kernels read through the accessor)
   if (p.aux && (s.n_aux < 1 || (!p.u && c.phase != STEP_APPLY)))
     return fail(h, SLODE_EINVAL, "the auxiliary loss needs label heads (n_aux >= 1) and labels u");
@@ -584,9 +608,10 @@ static int step_setup(Step& p) {
   p.dp5 = !p.aux && is_adaptive(s.method);
   const char* m = method_name(s.method);
   if (p.dp5 && !(s.H == 25 && (s.S == 5 || s.S == 8))) return fail(h, SLODE_EINVAL, "%s kernels are instantiated for (S,H) in {(5,25),(8,25)}", m);
-  if (p.dp5 && (s.B > 65536 || h->ode_loop)) return fail(h, SLODE_EINVAL, "the %s ELBO step takes at most 65,536 trajectories per call", m);
-  if (p.dp5 && !slode_dp5_lanes_ok(s.method, dp5_lanes(h, s.B)))
-    return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", m, dp5_lanes(h, s.B));
+  if (p.dp5 && ((long long)s.B * p.K > 65536 || h->ode_loop))
+    return fail(h, SLODE_EINVAL, "the %s ELBO step takes at most 65,536 trajectories per call (B x particles = %lld)", m, (long long)s.B * p.K);
+  if (p.dp5 && !slode_dp5_lanes_ok(s.method, dp5_lanes(h, s.B * p.K)))
+    return fail(h, SLODE_EINVAL, "%s: SLODE_DP5_LPT=%d is not instantiated (8 or 16; 32 / 64 are dopri5 only)", m, dp5_lanes(h, s.B * p.K));
   p.w = carve(h, s, p.lay, c.workspace);
   if (c.workspace_bytes < p.w.bytes) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", c.workspace_bytes, p.w.bytes);
   p.bwd = c.grads != nullptr || c.phase == STEP_PARTIAL;
@@ -631,7 +656,7 @@ static int score_aux(Step& p, SlabRows* rows) {
   slode_handle h = p.h; const slode_shape& s = p.s; const slode_layout& lay = p.lay; const Workspace& w = p.w;
   AuxLaunch al{s, lay, p.c.params, w.loc, w.scale, p.c.eps, p.u, w.g_loc, w.g_scale, w.ode_slabs, w.ode_stride,
                w.ode_grid < 2048 ? w.ode_grid : 2048, p.bwd ? 1 : 0};
-  al.rng = p.rng; al.lab = p.c.lab;
+  al.rng = p.rng; al.lab = p.c.lab; al.particles = p.K;
   // compact rows carry the flat range [aux_w1[0], cstd): every label-head tensor must lie inside it (a caller-made layout may not)
   bool aux_contig = lay.aux_w1[0] <= lay.cstd;
   for (int a = 0; a < s.n_aux; ++a) {
@@ -640,7 +665,7 @@ static int score_aux(Step& p, SlabRows* rows) {
   }
   if (p.bwd && p.folded && !aux_contig) return fail(h, SLODE_EINVAL, "slode_aux_step: the label heads must lie in [aux_w1[0], cstd) of the layout (slode_layout_init's order)");
   if (p.bwd && p.folded) { al.compact = 1; al.enc_hid = w.hid; al.g_pre = w.g_pre; al.glat = w.glat; al.g_loc = nullptr; al.g_scale = nullptr; }
-  rows->n = al.grid;
+  rows->n = al.grid * p.K;
   HIP_TRY(h, slode_launch_aux(al, p.c.stream));
   return SLODE_OK;
 }
@@ -652,38 +677,53 @@ static int score_ode(Step& p, bool enc_fused, SlabRows* rows) {
   a.obs = c.obs; a.sb = c.obs_strides[0]; a.sc = c.obs_strides[1]; a.st = c.obs_strides[2];
   a.u = p.u; a.eps = c.eps; a.loc = w.loc; a.scale = w.scale; a.x_out = c.x_out; a.z_out = c.z_out;
   a.g_loc = w.g_loc; a.g_scale = w.g_scale; a.slabs = w.ode_slabs; a.slab_stride = w.ode_stride; a.grid = w.ode_grid;
-  a.backward = p.bwd ? 1 : 0; a.with_ll = 1; a.rng = p.rng; a.lab = c.lab;
+  a.backward = p.bwd ? 1 : 0; a.with_ll = 1; a.rng = p.rng; a.lab = c.lab; a.particles = p.K;
   a.sigtab = p.folded ? w.sigtab : nullptr;   // written by the fold launch
   a.force_loop = h->ode_loop; a.force_generic = h->ode_generic; a.alg = h->ode_alg; a.pack = h->ode_pack;
   if (p.bwd && p.folded && !p.dp5) { a.enc_hid = w.hid; a.g_pre = w.g_pre; a.glat = w.glat; a.g_loc = nullptr; a.g_scale = nullptr; }
   if (enc_fused) { a.enc_fuse = 1; a.enc_weff = w.weff; a.enc_beff = w.beff; a.enc_hid_out = w.hid; }
-  if (p.dp5 && p.bwd && p.folded && solver_contig(s, lay) && w.ode_grid + w.dp_rows > 2 * SLODE_REDUCE_GROUPS) {
+  const int n_scorer = w.ode_grid * p.K;   // the scorer's slab rows: one grid per particle
+  slode_shape sv = s; sv.B = s.B * p.K; sv.particles = 0;   // what the adaptive solver's kernels see: every virtual trajectory
+  if (p.dp5 && p.bwd && p.folded && solver_contig(s, lay) && n_scorer + w.dp_rows > 2 * SLODE_REDUCE_GROUPS) {
     // the scorer's rows carry nothing in the solver-side range [init net | dynamics] (the reverse sweep's rows do): the scorer does not
     // write those zeros and stage 1 of the fused tail (the only reader of the rows) does not read them
     a.ext_skip = 1;
-    rows->zr_rows = w.ode_grid; rows->zr_lo = 1 + (lay.init_w1 - lay.ode_begin); rows->zr_hi = 1 + (lay.dyn_bd + s.S - lay.ode_begin);
+    rows->zr_rows = n_scorer; rows->zr_lo = 1 + (lay.init_w1 - lay.ode_begin); rows->zr_hi = 1 + (lay.dyn_bd + s.S - lay.ode_begin);
   }
   // adaptive solve (accepted steps recorded) -> ONE scorer pass (loss terms, dLoss/dx, the gradients that do not flow through the solver)
   // -> reverse sweep over the records (solver-side gradients as extra slab rows, the latent gradient through the solver added to g_loc /
   // g_scale, the encoder-head backward).  Forward workgroups of 16 trajectories (8 or 16 lanes), as the sweep's, hand it their tables.
   DopriRec rc{w.loc, w.scale, c.eps, w.dp_z, p.bwd ? w.dp_rec : nullptr, w.dp_nrec, w.dp_kmax};
+  rc.data_rows = s.B;
   if (p.dp5) {
-    rc.w64 = dp5_lanes(h, s.B);
+    rc.w64 = dp5_lanes(h, sv.B);
     rc.tabs = p.bwd && (rc.w64 == 8 || rc.w64 == 16) ? w.dp_tabs : nullptr;
     // in-kernel noise: the forward kernel draws it once and materialises it, the scorer and the reverse sweep read the same values
     if (p.rng.on) { rc.rng = p.rng; rc.eps_out = w.dp_eps; a.rng = RngK{}; a.eps = w.dp_eps; }
-    HIP_TRY(h, slode_launch_dopri5(s, lay, c.params, c.times, nullptr, w.dp_x, c.stream, &rc));
+    HIP_TRY(h, slode_launch_dopri5(sv, lay, c.params, c.times, nullptr, w.dp_x, c.stream, &rc));
     a.x_ext = w.dp_x;
-    if (p.bwd) { a.gx_out = w.dp_gx; rows->n = w.ode_grid + w.dp_rows; }
+    if (p.bwd) { a.gx_out = w.dp_gx; rows->n = n_scorer + w.dp_rows; }
   }
   hipError_t e = slode_launch_ode(a, c.stream, h->err, sizeof(h->err));
   if (e == hipErrorInvalidValue) return SLODE_EINVAL;
   HIP_TRY(h, e);
   rc.eps = a.eps;   // (the noise the forward kernel drew, when it drew it)
   if (p.dp5 && p.bwd)
-    HIP_TRY(h, slode_launch_dopri5_bwd(s, lay, c.params, c.times, rc, w.dp_gx, w.g_loc, w.g_scale, w.ode_slabs + (size_t)w.ode_grid * w.ode_stride,
+    HIP_TRY(h, slode_launch_dopri5_bwd(sv, lay, c.params, c.times, rc, w.dp_gx, w.g_loc, w.g_scale, w.ode_slabs + (size_t)n_scorer * w.ode_stride,
                                        w.ode_stride, s.grad_mode == SLODE_GRAD_REFERENCE_ADJOINT ? 1 : 0, w.dp_snap, c.stream,
                                        p.folded ? w.hid : nullptr, p.folded ? w.g_pre : nullptr, p.folded ? w.glat : nullptr));
+  return SLODE_OK;
+}
+
+// ---- between stages 2 and 3, K > 1 particles only: the particle fold.  The encoder-head backward and the tanh backward are linear in the
+// latent gradient and their coefficients (head weights, scale, hid) do not depend on the particle, so the K rows of a data row are averaged
+// BEFORE the encoder backward: g_pre / glat on the folded path, g_loc / g_scale on the layer-by-layer one.  Stage 3 then runs on B rows,
+// once, whatever K is; only the slab reduction sees K times the rows.  A separate launch behind the scorers: no cross-workgroup wait.
+static int particle_fold(Step& p) {
+  const slode_shape& s = p.s; const Workspace& w = p.w;
+  if (p.K < 2 || !p.bwd || p.c.phase == STEP_APPLY) return SLODE_OK;
+  if (p.folded) HIP_TRY(p.h, slode_launch_particle_fold(w.g_pre, (long long)s.B * 64, w.glat, (long long)s.B * 128, p.K, p.c.stream));
+  else HIP_TRY(p.h, slode_launch_particle_fold(w.g_loc, (long long)s.B * s.L, w.g_scale, (long long)s.B * s.L, p.K, p.c.stream));
   return SLODE_OK;
 }
 
@@ -715,6 +755,7 @@ static int tail_fused(Step& p, FoldLaunch& fl, const SlabRows& rows) {
   tl.Hc = s.Hc; tl.L = s.L; tl.CT = CT; tl.n_cv = s.F * s.C * s.K + s.F; tl.ode_begin = lay.ode_begin; tl.n_params = lay.n_params;
   tl.conv_w = lay.conv_w; tl.lin_w = lay.lin_w; tl.lin_b = lay.lin_b; tl.zloc_w = lay.zloc_w; tl.zloc_b = lay.zloc_b; tl.zls_w = lay.zls_w;
   tl.zls_b = lay.zls_b; tl.n_total = (c.adam.p && c.adam.n > lay.n_params) ? (int)c.adam.n : lay.n_params; tl.ad = make_adamk(&c.adam);
+  tl.particles = p.K; tl.inv_k = 1.0f / (float)p.K;   // the slab rows sum over the particles: mean of the loss and of the ODE-half gradient
   tl.counter = tl.done = w.counter; tl.cstd_off = lay.cstd; tl.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; tl.sigtab = w.sigtab;
   fold_next_plan(h, s, lay, c, tl);
   fl.tail = &tl;
@@ -727,6 +768,7 @@ static int tail_reduce(Step& p, const SlabRows& rows) {
   slode_handle h = p.h; const StepCall& c = p.c; const Workspace& w = p.w;
   ReduceLaunch r{};
   r.s = p.s; r.lay = p.lay; r.ode_slabs = w.ode_slabs; r.ode_stride = w.ode_stride; r.ode_n = rows.n; r.ode_part = w.ode_part; r.loss_out = c.loss_out;
+  r.particles = p.K;
   if (p.bwd) {
     if (c.adam.p) h->fold_valid = 0;
     EncBwdLaunch eb{p.s, p.lay, c.params, c.obs, c.obs_strides[0], c.obs_strides[1], c.obs_strides[2], w.scale, w.pooled, w.hid,
@@ -747,10 +789,11 @@ static int elbo_step_impl(slode_handle h, const slode_shape* s, const slode_layo
   if (rc != SLODE_OK) return rc;
   ClockScope clock_scope(h, true);
   FoldLaunch fl{}; bool enc_fused = false;
-  SlabRows rows{p.w.ode_grid, lay->ode_begin, lay->n_params};
+  SlabRows rows{p.w.ode_grid * p.K, lay->ode_begin, lay->n_params};
   if (p.aux && p.bwd && p.folded) { rows.part_lo = lay->aux_w1[0]; rows.part_hi = lay->cstd; }   // compact aux rows
   if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
   if (call.phase != STEP_APPLY && (rc = p.aux ? score_aux(p, &rows) : score_ode(p, enc_fused, &rows)) != SLODE_OK) return rc;
+  if ((rc = particle_fold(p)) != SLODE_OK) return rc;
   return p.bwd && p.folded ? tail_fused(p, fl, rows) : tail_reduce(p, rows);
 }
 
@@ -911,9 +954,10 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
   if (!h) return SLODE_EINVAL;
   if (!s || !lay || !workspace || !counts || !is_adaptive(s->method))
     return fail(h, SLODE_EINVAL, "slode_dopri5_step_counts: adaptive-method shape, workspace and output required");
+  if (check_shape(s)) return fail(h, SLODE_EINVAL, "%s", check_shape(s));
   if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_EINVAL, "slode_dopri5_step_counts: workspace too small");
   const Workspace w = carve(h, *s, *lay, const_cast<void*>(workspace));
-  HIP_TRY(h, hipMemcpyAsync(counts, w.dp_nrec, sizeof(int) * (size_t)s->B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  HIP_TRY(h, hipMemcpyAsync(counts, w.dp_nrec, sizeof(int) * (size_t)s->B * particles_of(*s), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SLODE_OK;
 }
 

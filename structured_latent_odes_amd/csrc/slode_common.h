@@ -103,6 +103,19 @@ __device__ __forceinline__ float slode_rng_normal(const RngK& r, long long b, in
 __device__ __forceinline__ float slode_eps_at(const RngK& r, const float* eps, long long b, int L, int l) {
   return r.on ? slode_rng_normal(r, b, l) : eps[b * L + l];
 }
+// Particles (slode_shape::particles = K > 1): the step scores K * B virtual trajectories, particle-major -- virtual row kp * B + b is
+// particle kp of data row b.  It reads the observations, labels, loc, scale and the encoder's hidden row of data row b and draws the
+// noise of drawing call n + kp at trajectory index b (explicit noise: row kp * B + b of eps[K, B, L]); its slab row, latent gradient
+// and pre-activation gradient are rows of their own, folded over kp by particle_fold_kernel (misc_kernels.hip).
+__device__ __forceinline__ RngK slode_rng_particle(const RngK& r, int kp) {
+  RngK q = r;
+  q.c2 = r.c2 + (unsigned int)kp;
+  q.c3 = r.c3 + (q.c2 < r.c2 ? 1u : 0u);   // drawing call n + kp, 64 bits
+  return q;
+}
+__device__ __forceinline__ float slode_eps_at(const RngK& r, const float* eps, long long b, int L, int l, int kp, long long B) {
+  return r.on ? slode_rng_normal(slode_rng_particle(r, kp), b, l) : eps[((long long)kp * B + b) * L + l];
+}
 __device__ __forceinline__ float slode_label_at(const LabelSrc& ls, const float* u, int nu, long long b, int col) {
   if (ls.n == 0) return u[b * nu + col];
   int i = 0;
@@ -273,19 +286,23 @@ struct TailK {
   unsigned int done_target;
   int cstd_off, gauss;
   float* sigtab;
+  // particles: the part rows hold the SUM over the K particles -- the loss and the elements of [part_lo, part_hi) take the mean here
+  // (inv_k = 1 / K as a float, particles = K; 1.0f and 1 with one particle: the same bits as without them).  The encoder-side
+  // gradients arrive as means already (particle_fold_kernel).
+  float inv_k; int particles;
 };
 __device__ __forceinline__ void tail_loss(const TailK& k) {
   if (!k.loss_out) return;
   double acc = 0.0;
   for (int w = 0; w < k.ode_n; ++w) acc += (double)k.ode_part[(long long)w * k.ode_stride];   // fixed order
-  k.loss_out[0] = (float)acc;
+  k.loss_out[0] = (float)(k.particles > 1 ? acc / (double)k.particles : acc);
 }
 // element i of [0, lin_w) (conv) or [lin_b, n_total): gradient, write, optional Adam
 template <bool FN = false>   // FN: the in-launch fold form of the chain launch (its riders publish what the fold reads, and write the scale table)
 __device__ __forceinline__ void tail_element(const TailK& k, int i) {
   float g = 0.f;
   if (i >= k.ode_begin && i < k.n_params) {
-    if (i >= k.part_lo && i < k.part_hi) g = strided_sum(k.ode_part + 1 + (i - k.part_lo), k.ode_stride, k.ode_n);
+    if (i >= k.part_lo && i < k.part_hi) g = strided_sum(k.ode_part + 1 + (i - k.part_lo), k.ode_stride, k.ode_n) * k.inv_k;
   } else if (i < k.lin_w) {
     g = strided_sum(k.conv_slabs + (i - k.conv_w), k.n_cv, k.Hc);
   } else if (i < k.n_params) {
@@ -422,6 +439,7 @@ struct OdeLaunch {
   int pack = 0;          // 4: four trajectories per workgroup where the shape has such an instantiation (ode_kernel.hip, PK)
   RngK rng{};            // on: eps is drawn in the kernel (eps may be NULL)
   LabelSrc lab{};        // n > 0: the label columns come from separate tensors (u may be NULL)
+  int particles = 1;     // K: grid.y; s.B stays the number of DATA rows; eps [K, B, L], slabs [K * grid] rows, g_* / glat / g_pre / x_ext / gx_out [K * B] rows
 };
 hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, size_t errlen);
 size_t slode_ode_lds_bytes(const slode_shape& s, int nthreads, bool one = false);
@@ -511,6 +529,7 @@ struct AuxLaunch {
   float *g_pre = nullptr, *glat = nullptr;
   RngK rng{};
   LabelSrc lab{};
+  int particles = 1;                 // K: grid.y (see OdeLaunch::particles)
 };
 hipError_t slode_launch_aux(const AuxLaunch& a, hipStream_t stream);
 
@@ -528,6 +547,7 @@ struct ReduceLaunch {   // (filled by field name: everything not set is null / 0
   float* small_part = nullptr;  // [SLODE_REDUCE_GROUPS][small_stride] likewise
   int folded = 0;               // 1: folded-encoder families (small = [lin_b..zls_b]; `lin` family = per-m conv slabs at flat offset conv_w)
   AdamHost adam{};              // optional fused Adam (adam.p == nullptr: none)
+  int particles = 1;            // K > 1: the ode slabs hold the sum over K particles; the loss and their gradient elements take the mean
 };
 hipError_t slode_launch_reduce(const ReduceLaunch& a, hipStream_t stream);
 
@@ -548,6 +568,8 @@ hipError_t slode_launch_dynamics_eval(const slode_shape& s, const slode_layout& 
 struct DopriRec { const float *loc, *scale, *eps; float* z_out; float* rec; int* nrec; int kmax; RngK rng{}; float* eps_out = nullptr;
                   int w64 = 8;   // lanes per trajectory of the forward solve: 8 (dopri5_kernel), 16 / 32 / 64 (dopri5_lpt_kernel); SLODE_DP5_LPT
                   float* tabs = nullptr;   // [rows][slode_dopri5_tab_floats]: the forward kernel's per-workgroup tables, handed to the reverse sweep
+                  int data_rows = 0;       // particles: the shape's B counts K * data_rows virtual trajectories (0: B data rows, one particle);
+                                           // loc / scale (and the reverse sweep's enc_hid) have data_rows rows, everything else B
 };
 size_t slode_dopri5_tab_floats(const slode_shape& s);
 int slode_dopri5_kmax(const slode_shape& s);
@@ -561,6 +583,9 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
 hipError_t slode_launch_dopri5_bwd(const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const DopriRec& rec,
                                    const float* gx, float* g_loc, float* g_scale, float* slabs, int slab_stride, int drop_z, float* snap, hipStream_t stream,
                                    const float* enc_hid = nullptr, float* g_pre = nullptr, float* glat = nullptr);   // (rec.tabs: tables of the forward kernel)
+// Particles: rows [K * B] -> the mean over the particles in rows [0, B), in place, summed in the fixed order k = 0 .. K - 1 (row k * B + b is
+// particle k of data row b).  Two arrays per launch (g_pre [.][64] and glat [.][128], or g_loc and g_scale [.][L]); n floats per particle.
+hipError_t slode_launch_particle_fold(float* a, long long n_a, float* b, long long n_b, int K, hipStream_t stream);
 hipError_t slode_launch_adam_k(int64_t n, const float* g, const AdamHost& a, hipStream_t stream);
 hipError_t slode_launch_adam(int64_t n, float* p, const float* g, float* m, float* v, float lr, float b1, float b2,
                              float eps, int64_t step, hipStream_t stream);

@@ -88,11 +88,11 @@ class Engine:
         self.spec, self.T = spec, int(n_time)
         self.handle = C.c_void_p()
         _check(self.lib, None, self.lib.slode_create(C.byref(self.handle), self.device.index or 0))
-        self._shapes: Dict[int, L.Shape] = {}
+        self._shapes: Dict[Tuple[int, int], L.Shape] = {}
         self.layout = L.Layout()
         _check(self.lib, None, self.lib.slode_layout_init(C.byref(self.shape(1)), C.byref(self.layout)))
         self.n_params = int(self.layout.n_params)
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
         self._stage_t: Optional[torch.Tensor] = None
         self._times: Optional[torch.Tensor] = None
 
@@ -104,8 +104,12 @@ class Engine:
             pass
 
     # ---- shapes / layout ---------------------------------------------------------------------------------
-    def shape(self, B: int) -> L.Shape:
-        s = self._shapes.get(B)
+    def shape(self, B: int, particles: int = 1) -> L.Shape:
+        """slode_shape for B data rows and `particles` ELBO particles (Trace_ELBO(num_particles=...): include/slode.h)."""
+        particles = int(particles)
+        if particles < 1 or particles > L.MAX_PARTICLES:
+            raise ValueError("particles must be in [1, %d], got %d" % (L.MAX_PARTICLES, particles))
+        s = self._shapes.get((B, particles))
         if s is None:
             sp = self.spec
             if sp.solver not in L.METHODS:
@@ -115,12 +119,12 @@ class Engine:
                         n_groups=len(sp.prior_groups), method=L.METHODS[sp.solver],
                         likelihood=L.GAUSS if sp.gauss else L.ALD, quantile_diff=sp.quantile_diff, rtol=sp.rtol, atol=sp.atol,
                         n_aux=len(sp.aux_heads), U=sp.u_hidden_dim, aux_mult=sp.aux_mult, aux_in_main=int(sp.labels_in_main),
-                        grad_mode=L.GRAD_MODES[sp.grad_mode])
+                        grad_mode=L.GRAD_MODES[sp.grad_mode], particles=particles)
             for i, a in enumerate(sp.aux_heads):
                 s.aux[i] = L.Aux(L.AUX_KINDS[a.kind], a.z_off, a.z_dim, a.u_off, a.u_dim)
             for i, g in enumerate(sp.prior_groups):
                 s.groups[i] = L.Group(g.z_off, g.z_dim, g.u_off, g.u_dim)
-            self._shapes[B] = s
+            self._shapes[(B, particles)] = s
         return s
 
     def param_table(self) -> List[Tuple[str, int, Tuple[int, ...]]]:
@@ -193,7 +197,11 @@ class Engine:
             raise ValueError("%s must be contiguous" % name)
         return t
 
-    def _check_batch(self, obs, u, eps):
+    def _eps_shape(self, B: int, particles: int):
+        """Explicit noise: [B, L] for one particle, one dense particle-major [K, B, L] tensor for K > 1."""
+        return (B, self.spec.latent_dim) if particles == 1 else (particles, B, self.spec.latent_dim)
+
+    def _check_batch(self, obs, u, eps, particles: int = 1):
         """The kernels read raw device pointers: a CPU / float64 / strided label or noise tensor must not get that far."""
         B = obs.shape[0]
         self._f32(obs, "observations", contiguous=False)
@@ -202,17 +210,17 @@ class Engine:
             if tuple(u.shape) != (B, self.spec.n_u):
                 raise ValueError("u must be [%d, %d], got %s" % (B, self.spec.n_u, tuple(u.shape)))
         self._f32(eps, "eps")
-        if tuple(eps.shape) != (B, self.spec.latent_dim):
-            raise ValueError("eps must be [%d, %d], got %s" % (B, self.spec.latent_dim, tuple(eps.shape)))
+        if tuple(eps.shape) != self._eps_shape(B, particles):
+            raise ValueError("eps must be %s, got %s" % (list(self._eps_shape(B, particles)), tuple(eps.shape)))
 
-    def workspace(self, B: int) -> torch.Tensor:
-        w = self._ws.get(B)
+    def workspace(self, B: int, particles: int = 1) -> torch.Tensor:
+        w = self._ws.get((B, particles))
         if w is None:
-            nbytes = int(self.lib.slode_workspace_bytes(self.handle, C.byref(self.shape(B))))
+            nbytes = int(self.lib.slode_workspace_bytes(self.handle, C.byref(self.shape(B, particles))))
             if nbytes == 0:
                 _check(self.lib, None, -1)
             w = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
-            self._ws[B] = w
+            self._ws[(B, particles)] = w
         return w
 
     def set_times(self, times: torch.Tensor) -> torch.Tensor:
@@ -313,13 +321,14 @@ class Engine:
             self.handle, C.byref(self.shape(B)), C.byref(self.layout), self._p(params), self._p(self._f32(z, "z")), self._p(out), self._stream()))
         return out
 
-    def dopri5_step_counts(self, B: int) -> torch.Tensor:
+    def dopri5_step_counts(self, B: int, particles: int = 1) -> torch.Tensor:
         """Accepted steps per trajectory of the last adaptive-method (dopri5, bosh3, fehlberg2, adaptive_heun) training step at batch
-        size B (diagnostic; int32 [B]; -1: 20,000 attempts exhausted, > slode_dopri5_kmax: record overflow)."""
-        out = torch.empty(B, dtype=torch.int32, device=self.device)
-        w = self.workspace(B)
+        size B (diagnostic; int32 [B], [particles * B] particle-major with particles; -1: 20,000 attempts exhausted, > slode_dopri5_kmax:
+        record overflow)."""
+        out = torch.empty(B * particles, dtype=torch.int32, device=self.device)
+        w = self.workspace(B, particles)
         _check(self.lib, self.handle, self.lib.slode_dopri5_step_counts(
-            self.handle, C.byref(self.shape(B)), C.byref(self.layout), self._p(w), w.numel() * 4, self._p(out), self._stream()))
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(w), w.numel() * 4, self._p(out), self._stream()))
         return out
 
     def decode_heads(self, params, x):
@@ -400,9 +409,10 @@ class Engine:
         return loss_out
 
     # ---- SVI.step(**batch) as one call: labels as the loader yields them, noise drawn in the kernels -----------------------------
-    def make_batch(self, obs, labels, eps=None) -> L.Batch:
+    def make_batch(self, obs, labels, eps=None, particles: int = 1) -> L.Batch:
         """slode_batch for `obs` [B, C, T] (any strides) and the label tensors in the model's concatenation order (each [B, width] or [B],
-        float32, contiguous, on the device).  eps [B, L] or None (None: drawn in-kernel from the handle's Philox stream, rng_seed).
+        float32, contiguous, on the device).  eps [B, L] ([particles, B, L] for particles > 1) or None (None: drawn in-kernel from the
+        handle's Philox stream, rng_seed: particle k is drawing call n + k).
         The batch carries raw device pointers; it also holds the tensors they point at (``tensors``), so a label tensor converted just
         for this batch lives until the batch does -- until the step that reads it is enqueued."""
         B = obs.shape[0]
@@ -427,22 +437,23 @@ class Engine:
         bt.n_labels = len(labels)
         if eps is not None:
             self._f32(eps, "eps")
-            if tuple(eps.shape) != (B, self.spec.latent_dim):
-                raise ValueError("eps must be [%d, %d], got %s" % (B, self.spec.latent_dim, tuple(eps.shape)))
+            if tuple(eps.shape) != self._eps_shape(B, int(particles)):
+                raise ValueError("eps must be %s, got %s" % (list(self._eps_shape(B, int(particles))), tuple(eps.shape)))
             bt.eps = eps.data_ptr()
         bt.tensors = (obs, *labels, eps)
         return bt
 
-    def svi_step(self, kind: int, params, batch: L.Batch, B: int, loss_out, grads=None, adam=None):
-        """slode_svi_step: kind L.SVI_MAIN | L.SVI_AUX; adam = (exp_avg, exp_avg_sq, lr, step, betas, eps) or None."""
-        ws = self.workspace(B)
+    def svi_step(self, kind: int, params, batch: L.Batch, B: int, loss_out, grads=None, adam=None, particles: int = 1):
+        """slode_svi_step: kind L.SVI_MAIN | L.SVI_AUX; adam = (exp_avg, exp_avg_sq, lr, step, betas, eps) or None; particles = K: the mean
+        loss and mean gradient of K particles in the same one call (the batch's eps, if given, is [K, B, L])."""
+        ws = self.workspace(B, particles)
         self._guard(params, ws)
         ad = None
         if adam is not None:
             m, v, lr, step, betas, aeps = adam
             ad = L.AdamArgs(params.numel(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(aeps), int(step))
         _check(self.lib, self.handle, self.lib.slode_svi_step(
-            self.handle, C.byref(self.shape(B)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
             C.byref(batch), self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, C.byref(ad) if ad is not None else None, self._stream()))
         return loss_out
 
@@ -450,21 +461,21 @@ class Engine:
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))
 
-    def grad_partial(self, kind: int, params, batch: L.Batch, B: int, payload):
-        ws = self.workspace(B)
+    def grad_partial(self, kind: int, params, batch: L.Batch, B: int, payload, particles: int = 1):
+        ws = self.workspace(B, particles)
         self._guard(params, ws)
         _check(self.lib, self.handle, self.lib.slode_grad_partial(
-            self.handle, C.byref(self.shape(B)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
             C.byref(batch), self._p(self._f32(payload, "payload")), self._p(ws), ws.numel() * 4, self._stream()))
 
-    def grad_apply(self, kind: int, params, batch: L.Batch, B: int, payload, loss_out, grads, adam=None):
-        ws = self.workspace(B)
+    def grad_apply(self, kind: int, params, batch: L.Batch, B: int, payload, loss_out, grads, adam=None, particles: int = 1):
+        ws = self.workspace(B, particles)
         ad = None
         if adam is not None:
             m, v, lr, step, betas, aeps = adam
             ad = L.AdamArgs(params.numel(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(aeps), int(step))
         _check(self.lib, self.handle, self.lib.slode_grad_apply(
-            self.handle, C.byref(self.shape(B)), C.byref(self.layout), int(kind), self._p(params), batch.obs_strides, self._p(payload),
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), batch.obs_strides, self._p(payload),
             self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, C.byref(ad) if ad is not None else None, self._stream()))
         return loss_out
 

@@ -7,6 +7,7 @@ all-reduce of the flat gradient with the loss scalar appended, one `
 no autograd, no torch operator on this path."""
 from __future__ import annotations
 
+import numbers
 from typing import Callable, Dict, Optional
 
 import torch
@@ -48,6 +49,7 @@ class _StepBase:
     ``Engine.rng_seed``; the guide's ``rsample`` sites, mechanistic_cvs.py:225-237).  ``eps=`` / ``u=`` keep the explicit parity path.
     Data parallel (``world > 1``): gradient-only call -> one SUM all-reduce of [gradient | loss] -> ``slode_adam_step``."""
     KIND = L.SVI_MAIN
+    num_particles = 1   # Trace_ELBO(num_particles=K): K particles per step, inside the same one engine call (set by the constructors)
 
     def _setup(self, engine: Engine, params: torch.Tensor, n_grad: int, optimizer, process_group):
         self.engine, self.params, self.optimizer, self.pg = engine, params, optimizer, process_group
@@ -61,8 +63,15 @@ class _StepBase:
         self._payload = None
         self.unfused = False       # True: take the data-parallel code path at world size 1 too (tests: RCCL at world size 1)
 
+    def _pk(self) -> dict:
+        """The engine calls' particle keyword: given only when there is more than one particle."""
+        return {"particles": self.num_particles} if self.num_particles != 1 else {}
+
     def _batch(self, observations, eps, labels, u):
         eng = self.engine
+        K = self.num_particles
+        if K != 1 and eps is not None and (eps.dim() != 3 or eps.shape[0] != K or eps.shape[1] != observations.shape[0]):
+            raise ValueError("eps must be [num_particles = %d, B = %d, L] (particle-major), got %s" % (K, observations.shape[0], tuple(eps.shape)))
         if self.world > 1 and eps is None:
             # in-kernel noise is keyed by the GLOBAL trajectory index: this rank's shard starts after the shards of the lower ranks
             # (contiguous batch split).  Shard sizes can differ between ranks and change between steps (the last, partial batch of an
@@ -72,7 +81,7 @@ class _StepBase:
             if cur != b0:
                 eng.rng_seed(seed, b0)
                 eng.rng_set_counter(n)          # (rng_seed resets the call counter: keep it)
-        return eng.make_batch(observations, _label_list(labels, u), eps)
+        return eng.make_batch(observations, _label_list(labels, u), eps, **self._pk())
 
     def _shard_offset(self, B: int) -> int:
         """Global index of this rank's first trajectory: the sum of the shard sizes of the lower ranks."""
@@ -106,14 +115,14 @@ class _StepBase:
         if self.world == 1 and opt is not None and not self.unfused:
             opt.t += 1   # single process: Adam applied by the final gradient-reduction kernel
             self.engine.svi_step(self.KIND, self.params, bt, B, self.loss, self.grads,
-                                 adam=(opt.exp_avg, opt.exp_avg_sq, opt.lr, opt.t, opt.betas, opt.eps))
+                                 adam=(opt.exp_avg, opt.exp_avg_sq, opt.lr, opt.t, opt.betas, opt.eps), **self._pk())
             return self.loss
         if small_payload:
             # data parallel, small payload: every rank contributes G = g_pre^T [X | 1], its head-layer products and its ODE-half row with
             # the loss scalar (137 KB instead of the 386 KB flat gradient at the metric shape); the chain rule -- linear in G -- runs once,
             # on the reduced payload, with Adam applied by the same launch (include/slode.h: slode_grad_partial / slode_grad_apply)
             try:
-                self.engine.grad_partial(self.KIND, self.params, bt, B, self._payload)
+                self.engine.grad_partial(self.KIND, self.params, bt, B, self._payload, **self._pk())
             except L.SlodeError:
                 self._payload = False          # (observations the folded encoder path does not take: reduce the flat gradient instead)
             if self._payload is not False:
@@ -122,9 +131,10 @@ class _StepBase:
                 if opt is not None:
                     opt.t += 1
                 self.engine.grad_apply(self.KIND, self.params, bt, B, self._payload, self.loss, self.grads,
-                                       adam=(opt.exp_avg, opt.exp_avg_sq, opt.lr, opt.t, opt.betas, opt.eps) if opt is not None else None)
+                                       adam=(opt.exp_avg, opt.exp_avg_sq, opt.lr, opt.t, opt.betas, opt.eps) if opt is not None else None,
+                                       **self._pk())
                 return self.loss
-        self.engine.svi_step(self.KIND, self.params, bt, B, self.loss, self.grads)
+        self.engine.svi_step(self.KIND, self.params, bt, B, self.loss, self.grads, **self._pk())
         if self.world > 1 or (self.unfused and torch.distributed.is_initialized()):
             torch.distributed.all_reduce(self.gbuf, op=torch.distributed.ReduceOp.SUM, group=self.pg)
         if opt is not None:
@@ -141,7 +151,7 @@ class _StepBase:
 
     def evaluate_loss(self, observations, eps=None, u=None, labels=None, **named) -> float:
         B = observations.shape[0]
-        self.engine.svi_step(self.KIND, self.params, self._batch(observations, eps, self._named(labels, named), u), B, self.loss, None)
+        self.engine.svi_step(self.KIND, self.params, self._batch(observations, eps, self._named(labels, named), u), B, self.loss, None, **self._pk())
         if self.world > 1:
             torch.distributed.all_reduce(self.loss, op=torch.distributed.ReduceOp.SUM, group=self.pg)
         return float(self.loss.item())
@@ -151,9 +161,11 @@ class ELBOStep(_StepBase):
     """Main-loss SVI object, SVI(model, guide) (training_cvs.py:236-243)."""
     KIND = L.SVI_MAIN
 
-    def __init__(self, engine: Engine, params: torch.Tensor, optimizer: Optional[FlatAdam] = None, process_group=None, owner=None):
+    def __init__(self, engine: Engine, params: torch.Tensor, optimizer: Optional[FlatAdam] = None, process_group=None, owner=None,
+                 num_particles: int = 1):
         self.owner = owner
         self._setup(engine, params, params.numel(), optimizer, process_group)
+        self.num_particles = _particles(num_particles)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -183,13 +195,22 @@ class Adam:
         return self._flat
 
 
-class Trace_ELBO:
-    """pyro.infer.Trace_ELBO stand-in; only num_particles=1 (the reference's setting, config_cvs.py:44) is supported."""
+def _particles(num_particles) -> int:
+    if isinstance(num_particles, bool) or not isinstance(num_particles, numbers.Integral) or num_particles < 1:
+        raise ValueError("num_particles must be an integer >= 1, got %r" % (num_particles,))
+    return int(num_particles)
 
-    def __init__(self, num_particles=1, **kwargs):
-        if num_particles != 1:
-            raise NotImplementedError("num_particles != 1")
-        self.num_particles = num_particles
+
+class Trace_ELBO:
+    """pyro.infer.Trace_ELBO stand-in.  ``num_particles=K`` (config.num_particles; config_cvs.py:44 sets 1): every SVI step evaluates
+    model and guide K times on the same minibatch, each time with fresh reparameterisation noise, returns the mean of the K losses and
+    applies the mean of the K gradients in ONE optimizer step -- here inside the one engine call of the step (include/slode.h,
+    slode_shape::particles).  Other keywords (``vectorize_particles``, ``max_plate_nesting``, ...) change how Pyro executes the
+    particles, not what they compute: accepted and ignored."""
+
+    def __init__(self, num_particles=1, vectorize_particles=False, **kwargs):
+        self.num_particles = _particles(num_particles)
+        self.vectorize_particles = bool(vectorize_particles)
 
 
 class AuxStep(_StepBase):
@@ -197,10 +218,11 @@ class AuxStep(_StepBase):
     group latents sampled in the model + label heads at aux_loss_multiplier -> encoder backward -> reduction [+ Adam]), all HIP."""
     KIND = L.SVI_AUX
 
-    def __init__(self, owner, optimizer: Optional[FlatAdam], process_group=None):
+    def __init__(self, owner, optimizer: Optional[FlatAdam], process_group=None, num_particles: int = 1):
         self.owner = owner
         b = owner._bind()
         self._setup(b.engine, b.flat, b.n_total, optimizer, process_group)
+        self.num_particles = _particles(num_particles)
 
 
 class SVI:
@@ -215,10 +237,11 @@ class SVI:
         self.owner, self.kind = owner, ("aux" if model.__name__ == "model_meta" else "main")
         binding = owner._bind()
         flat_opt = optim.for_binding(binding) if optim is not None else None
+        K = _particles(getattr(loss, "num_particles", 1)) if loss is not None else 1
         if self.kind == "main":
-            self._impl = ELBOStep(binding.engine, binding.flat, flat_opt, owner=owner)
+            self._impl = ELBOStep(binding.engine, binding.flat, flat_opt, owner=owner, num_particles=K)
         else:
-            self._impl = AuxStep(owner, flat_opt)
+            self._impl = AuxStep(owner, flat_opt, num_particles=K)
 
     def _split(self, batch):
         """observations, optional explicit eps, and the label tensors in the model's order -- as the loader yields them, not concatenated."""
