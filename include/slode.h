@@ -29,13 +29,14 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 130 /* 0.1.3: slode_shape::particles (0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 140 /* 0.1.4: slode_eval_stats (0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
 #define SLODE_MAX_AUX 4
 #define SLODE_MAX_LABELS 4 /* label tensors of one minibatch (proc: aR, aS, C12, C6) */
 #define SLODE_MAX_PARTICLES 1024
+#define SLODE_EVAL_SLOTS 8 /* floats of one slode_eval_stats row */
 
 typedef enum slode_status {
   SLODE_OK = 0,
@@ -299,6 +300,33 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
                    const float* stage_t, const slode_batch* batch, float* loss_out, float* grads, void* workspace, size_t workspace_bytes,
                    const slode_adam* adam, void* stream);
 
+/* ---- one batch of the per-epoch statistics as ONE call (training_cvs.py:43-144 `input_pred_stats`: evaluate_loss of both SVI objects, recon,
+ * classifier / pred_inputs; four such passes per epoch, :270-315) ---------------------------------------------------------------------------
+ * Writes one row of SLODE_EVAL_SLOTS floats to device memory:
+ *   out[0]      -ELBO of the main loss, summed over the batch          (= slode_svi_step, kind MAIN, grads NULL)
+ *   out[1]      auxiliary loss, summed over the batch; 0 with n_aux = 0 (= slode_svi_step, kind AUX, grads NULL)
+ *   out[2]      sum over [B, C, T] of |centre curve - observation|: mu_50 (ALD) or mean (Gauss) of the reconstruction of ONE latent draw --
+ *               is_post != 0: from the posterior N(loc(x), scale(x)); is_post == 0: from the conditional prior p(z | labels), N(0, 1) on the
+ *               dims outside every prior group (= recon(is_post)["l1"] * B * C * T, models/mechanistic_cvs.py:298-323)
+ *   out[3 + a]  a < n_aux: trajectories whose prediction of label head a (the order of slode_shape::aux) is a hit.  Prediction from one
+ *               posterior draw, as classifier / pred_inputs decide it (mechanistic_cvs.py:278-296): SIGMOID: p > 0.5; SOFTMAX: one-hot of
+ *               the arg-max, lowest index on a tie; EXPEXP: the Laplace location, the value slode_label_heads writes.  Hit: every column
+ *               within 0.5 of the label.  Slots of absent heads: 0.
+ *   out[7]      B
+ * Four independent latent draws per trajectory, in the order main, auxiliary, recon, labels: batch->eps == NULL takes drawing calls n, n + 1,
+ * n + 2, n + 3 of the handle's generator and leaves the counter at n + 4 -- what the unfused sequence of calls consumes, so from the same
+ * (seed, first_trajectory, n) the row equals theirs up to fp32 summation order; batch->eps != NULL is a dense [4, B, L] tensor in that order.
+ * Enqueue only (no allocation, no synchronisation, capturable); at most four launches ("weff", "enc_fwd2", "eval_stats", "eval_reduce" in
+ * slode_profile_read): the encoder runs once; one partial row per workgroup, summed in a fixed order: bitwise reproducible.
+ * Takes the fixed-grid methods, one particle, the two dense observation layouts of the folded encoder ([B,T,C] or [B,C,T] contiguous, C in
+ * {3, 4}).  Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: adaptive solver (dopri5, bosh3,
+ * fehlberg2, adaptive_heun); particles > 1; observation strides the folded path does not take (and SLODE_NO_FOLD); the measured arms
+ * SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG set in the environment of slode_create.  The caller then runs the unfused calls.
+ * Workspace: slode_workspace_bytes of the shape (unchanged: the partial rows live in the ELBO step's slab rows). */
+int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                     const float* stage_t, const slode_batch* batch, int is_post, float* out /* [SLODE_EVAL_SLOTS] */, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -373,7 +401,7 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -844,6 +844,60 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
   return elbo_step_impl(h, s, lay, c);
 }
 
+// The statistics row of one batch (include/slode.h): refusals first -- nothing launched, no draw consumed -- then the fold + encoder launches
+// of a forward-only step, the fused kernel and the fixed-order reduction of its partial rows.
+int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                     const float* stage_t, const slode_batch* batch, int is_post, float* out, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  const char* why = check_common(h, s, lay, params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  if (!batch || !out) return fail(h, SLODE_EINVAL, "slode_eval_stats: batch / out is NULL");
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "slode_eval_stats: adaptive solver %s is not taken (fixed-grid methods only); run the unfused calls", method_name(s->method));
+  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_eval_stats: particles = %d is not taken (one particle only); run the unfused calls", s->particles);
+  if (h->fold_on || h->ode_pack || h->ode_alg)
+    return fail(h, SLODE_EINVAL, "slode_eval_stats cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
+    return fail(h, SLODE_EINVAL, "slode_eval_stats: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
+                                 "[B,T,C] or [B,C,T] observations with C in {3, 4}; run the unfused calls",
+                (long long)os[0], (long long)os[1], (long long)os[2]);
+  if (slode_eval_lds_bytes(*s) + 4096 > 160 * 1024)
+    return fail(h, SLODE_EINVAL, "slode_eval_stats: T x S = %d x %d does not fit the step table into the LDS; run the unfused calls", s->T, s->S);
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.loss_out = out;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  int rc = batch_call(h, s, SLODE_SVI_MAIN, batch, &c);
+  if (rc != SLODE_OK) return rc;
+  const uint64_t n0 = h->rng_counter;
+  Step p{h, *s, *lay, c};
+  rc = step_setup(p);
+  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its four once nothing can refuse it any more)
+  if (rc != SLODE_OK) return rc;
+  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_eval_stats: the folded encoder path does not take these observations");
+  EvalLaunch a{};
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.sc = os[1]; a.st = os[2];
+  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.part = p.w.ode_slabs; a.out = out;
+  a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic; a.lab = c.lab;
+  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
+  long long g = s->B;
+  if (s->B > 65536 || h->ode_loop) {
+    g = (long long)h->num_cu * 4;
+    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+    if (g > s->B) g = s->B;
+  }
+  a.grid = (int)g;
+  if ((size_t)a.grid * SLODE_EVAL_SLOTS > (size_t)p.w.ode_grid * p.w.ode_stride)
+    return fail(h, SLODE_ENOSPC, "slode_eval_stats: %d partial rows do not fit the workspace's slab rows", a.grid);
+  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 4; }
+  ClockScope clock_scope(h, true);
+  FoldLaunch fl{}; bool enc_fused = false;
+  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_eval(a, c.stream));
+  return SLODE_OK;
+}
+
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {
   if (check_shape(s) || !lay) return 0;
   const int part = kind == SLODE_SVI_AUX ? lay->cstd - lay->aux_w1[0] : lay->n_params - lay->ode_begin;

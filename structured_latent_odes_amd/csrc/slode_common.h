@@ -533,6 +533,23 @@ struct AuxLaunch {
 };
 hipError_t slode_launch_aux(const AuxLaunch& a, hipStream_t stream);
 
+// Fused statistics pass (eval_kernel.hip; slode_eval_stats): loc / scale from the encoder launch, four noise rows per trajectory (rng.on: drawing
+// calls c2 .. c2 + 3 of the generator; else eps [4, B, L]), one partial row [SLODE_EVAL_SLOTS] per workgroup and the fixed-order reduction
+// of the rows into out, as a second launch
+struct EvalLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *obs;
+  int64_t sb, sc, st;
+  const float *loc, *scale, *eps, *u, *sigtab;
+  float *part, *out;
+  int grid, is_post, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
+size_t slode_eval_lds_bytes(const slode_shape& s);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

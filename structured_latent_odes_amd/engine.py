@@ -457,6 +457,22 @@ class Engine:
             C.byref(batch), self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, C.byref(ad) if ad is not None else None, self._stream()))
         return loss_out
 
+    def eval_stats(self, params, batch: L.Batch, B: int, is_post: bool, out, particles: int = 1):
+        """slode_eval_stats: the statistics row of one batch -- [-ELBO main, auxiliary loss, sum |centre curve - observation|, hits of label
+        head 0..3 (spec.aux_heads order), B] -- into ``out`` (float32 [L.EVAL_SLOTS], device), enqueued on the current stream: no
+        synchronisation, no read-back.  Four latent draws per trajectory (main, auxiliary, recon, labels): the batch's eps is [4, B, L] or
+        None (drawing calls n .. n + 3 of the generator).  Raises SlodeError naming the reason for what the fused kernel does not take
+        (adaptive solver, ``particles`` > 1, strided observations, measured arms): nothing is launched and no draw is consumed then."""
+        if out.numel() != L.EVAL_SLOTS:
+            raise ValueError("out must hold %d floats, got %d" % (L.EVAL_SLOTS, out.numel()))
+        self._f32(out, "out")
+        ws = self.workspace(B, particles)
+        self._guard(params, ws)
+        _check(self.lib, self.handle, self.lib.slode_eval_stats(
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
+            C.byref(batch), 1 if is_post else 0, self._p(out), self._p(ws), ws.numel() * 4, self._stream()))
+        return out
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

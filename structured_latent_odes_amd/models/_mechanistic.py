@@ -227,6 +227,55 @@ class MechanisticBase(nn.Module):
             return {"l1": self.l1_func(mu_50, observations), "solution_xt": solution_xt, "mu_75": mu_75, "mu_50": mu_50,
                     "mu_25": mu_25, "std": std, "z": z}
 
+    # ---- the statistics row of one batch (training.input_pred_stats_fused) -------------------------------------------------
+    def eval_stat_slots(self) -> Dict[str, int]:
+        """{label name: its hit-count slot in the eval_stats row}: 3 + index of the label's head in ``AUX`` (include/slode.h)."""
+        return {label: 3 + a for a, (_, _, label, _) in enumerate(self.AUX)}
+
+    def eval_stats(self, observations, is_post, out=None, eps=None, num_particles: int = 1, **labels):
+        """What one batch of ``input_pred_stats`` (training_cvs.py:43-144) needs, as one device row of ``EVAL_SLOTS`` floats --
+        [-ELBO of the main loss, auxiliary loss, sum over [B, C, T] of |mu_50 or mean - observations| of one reconstruction (posterior if
+        ``is_post`` else prior), hits per label head (``eval_stat_slots``), B] -- from ONE engine call (``slode_eval_stats``): nothing is
+        read back and the stream is not synchronised.  ``out``: a float32 [EVAL_SLOTS] device tensor (a row of the caller's table).
+        ``eps`` [4, B, L] (main, auxiliary, recon, labels) makes it reproducible; None draws four calls of the engine's generator, the
+        ones the unfused sequence evaluate_loss, evaluate_loss, recon, classifier would draw.  Where the engine refuses (adaptive solver,
+        ``num_particles`` > 1, strided observations, measured arms) the row is composed from those unfused calls instead."""
+        from .. import _lib as L
+        b = self._bind()
+        B = observations.shape[0]
+        if out is None:
+            out = torch.empty(L.EVAL_SLOTS, dtype=torch.float32, device=b.flat.device)
+        if int(num_particles) == 1:
+            labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+            bt = b.engine.make_batch(observations, labs, eps, particles=4 if eps is not None else 1)
+            try:
+                return b.engine.eval_stats(b.flat, bt, B, is_post, out)
+            except L.SlodeError:
+                pass
+        if eps is not None:
+            raise ValueError("explicit eps is taken by the fused statistics call only; this configuration runs the unfused calls")
+        return self._eval_stats_composed(observations, is_post, out, int(num_particles), labels)
+
+    def _eval_stats_composed(self, observations, is_post, out, num_particles, labels):
+        """The same row from the existing calls, in their order (each draws its own noise and reads its own result back)."""
+        from ..svi import SVI, Trace_ELBO
+        cache = self.__dict__.setdefault("_stat_svi", {})
+        if num_particles not in cache:
+            elbo = Trace_ELBO(num_particles=num_particles)
+            cache[num_particles] = (SVI(self.model, self.guide, None, loss=elbo), SVI(self.model_meta, self.guide_meta, None, loss=elbo))
+        main, aux = cache[num_particles]
+        row = [0.0] * out.numel()
+        row[0] = main.evaluate_loss(observations=observations, **labels)
+        row[1] = aux.evaluate_loss(observations=observations, **labels) if self.AUX else 0.0
+        row[2] = float(self.recon(observations=observations, is_post=is_post, **labels)["l1"]) * observations.numel()
+        pred = self._predict_labels(observations)
+        for label, slot in self.eval_stat_slots().items():
+            want = labels[label].reshape(observations.shape[0], -1)
+            row[slot] = float((pred[label] - want).abs().lt(0.5).all(dim=1).float().sum())
+        row[-1] = float(observations.shape[0])
+        out.copy_(torch.tensor(row, dtype=torch.float32))
+        return out
+
     def recon_samples(self, observations, is_post, num_samples: int, eps=None, **labels):
         """``multiple_samples`` of the reference (training_proc.py:205-223, training_cvs.py / training_challenge.py alike): it calls
         ``recon`` ``num_samples`` times (config.num_samples = 200) and concatenates the quantile curves along a new last axis.

@@ -61,6 +61,43 @@ def input_pred_stats(batches, model, losses, is_post: bool, device, family: str)
     return out
 
 
+STATS_CHUNK = 64   # rows by which the table of a fused statistics pass grows when the batch source has no len()
+
+
+def _to_host(table: torch.Tensor) -> np.ndarray:
+    """THE device-to-host copy of a fused statistics pass (float64 on the host)."""
+    return table.detach().cpu().double().numpy()
+
+
+def input_pred_stats_fused(batches, model, is_post: bool, device, family: str, num_particles: int = 1):
+    """``input_pred_stats`` with one engine call per batch and ONE read-back per pass: every batch writes its row of sums
+    (``model.eval_stats``: -ELBO main, auxiliary loss, reconstruction L1 sum, hits per label, B) into a device table; the table comes back
+    once, at the end, and the pass is summed on the host in float64.  Same dict, same arithmetic quirks of the reference: ``elbo`` is the sum
+    over batches of loss / B, ``l1`` the sum of the per-batch means over the number of trajectories."""
+    from . import _lib as L
+    n = len(batches) if hasattr(batches, "__len__") else STATS_CHUNK
+    table = torch.empty(max(n, 1), L.EVAL_SLOTS, dtype=torch.float32, device=device)
+    elems, i = [], 0
+    for batch in batches:
+        batch = batch_to_device(batch, device, family)
+        if i == table.shape[0]:
+            grown = torch.empty(i + STATS_CHUNK, L.EVAL_SLOTS, dtype=torch.float32, device=device)
+            grown[:i].copy_(table)
+            table = grown
+        obs = batch["observations"]
+        model.eval_stats(is_post=is_post, out=table[i], num_particles=num_particles, **batch)
+        elems.append(obs.shape[1] * obs.shape[2])
+        i += 1
+    rows = _to_host(table[:i]) if i else np.zeros((0, L.EVAL_SLOTS))
+    B = rows[:, L.EVAL_SLOTS - 1]
+    size = float(B.sum())
+    slots = model.eval_stat_slots()
+    out = {l: (float(rows[:, slots[l]].sum()) if l in slots else 0.0) / max(size, 1) for l in FAMILY_LABELS[family]}
+    l1 = float((rows[:, 2] / (B * np.asarray(elems, dtype=np.float64))).sum()) if i else 0.0
+    out.update(l1=l1 / max(size, 1), elbo=torch.tensor([float((rows[:, 0] / B).sum()), float((rows[:, 1] / B).sum())]))
+    return out
+
+
 def make_batches(config, family: str, n_batches: int, seed: int):
     out = []
     for i in range(n_batches):
@@ -73,7 +110,10 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
-          test_batches: Optional[Sequence[dict]] = None):
+          test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False):
+    """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
+    read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
+    var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -113,10 +153,14 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
         traj_per_s = n_traj / max(time.perf_counter() - t_ep, 1e-9)
         # the reference's four statistics passes per epoch (training_cvs.py:270-315): validation posterior / prior, training
         # posterior / prior -- every one a full pass over its loader: evaluate_loss of both SVI objects, recon, label prediction
-        val = input_pred_stats(val_b, var_model, losses, True, device, family)
-        _ = input_pred_stats(val_b, var_model, losses, False, device, family)
-        trn = input_pred_stats(train_b, var_model, losses, True, device, family)
-        trn_prior = input_pred_stats(train_b, var_model, losses, False, device, family)
+        if fused_stats:
+            def stats(b, post): return input_pred_stats_fused(b, var_model, post, device, family, config.num_particles)
+        else:
+            def stats(b, post): return input_pred_stats(b, var_model, losses, post, device, family)
+        val = stats(val_b, True)
+        _ = stats(val_b, False)
+        trn = stats(train_b, True)
+        trn_prior = stats(train_b, False)
         val_elbo = torch.sum(val["elbo"]) * len(val["elbo"])
         improved = ""
         if best_val_loss >= val_elbo:
@@ -188,12 +232,13 @@ def main(family: str, load_config, model_cls, model_cls_gauss):
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batches-per-epoch", type=int, default=7)
     ap.add_argument("--data-dir", default=None, help="directory with the reference's data files (default: synthetic batches)")
+    ap.add_argument("--fused-stats", action="store_true", help="per-epoch statistics: one engine call per batch, one read-back per pass")
     a = ap.parse_args()
     config = load_config()
     config.num_epochs = a.epochs
     os.makedirs("results_%s" % config.model, exist_ok=True)
     logging.basicConfig(filename="results_%s/model.log" % config.model, filemode="w", level=logging.DEBUG)
-    kw = {}
+    kw = {"fused_stats": a.fused_stats}
     if a.data_dir:
         got = real_batches(config, family, a.data_dir)
         kw["train_batches"], kw["val_batches"], kw["times"] = got[:3]

@@ -1,0 +1,90 @@
+"""Time one statistics pass of the epoch loop, unfused against fused, in ONE process: training.input_pred_stats (evaluate_loss x 2, recon,
+label prediction: five to seven read-backs per batch) against training.input_pred_stats_fused (one slode_eval_stats call per batch, one
+read-back per pass).  Shapes: the metric shape (cvs, B = 1024, T = 200, rk4) and config[4]'s shard (challenge-Gauss, B = 512, T = 300,
+rk4).  A pass = 50 batches already on the device; warmed; device-synchronised at both ends; the two legs ALTERNATE `--rounds` times and each
+leg reports its median and its spread (max - min) in microseconds per batch, posterior and prior.  Also the kernels of one fused call
+from slode_profile_read.  Prints one JSON line; --out writes it to a file.
+
+    python tools/stats_pass_bench.py --out profiles/eval_stats_pass.json
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/stats_pass_bench.py --rounds 1      # the kernel's time on the profiler's clock
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {
+    "metric_cvs_B1024_T200_rk4": ("cvs", "mechanistic_cvs", "MechanisticModel", 1024, 200, dict(z_iext_dim=3, z_rtpr_dim=3, z_epsilon_dim=2)),
+    "config4_challenge_gauss_B512_T300_rk4": ("challenge", "mechanistic_challenge_Gauss", "MechanisticModelGauss", 512, 300, dict()),
+}
+
+
+def _pass_us(fn, n_batches, dev):
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize(dev)
+    return 1e6 * (time.perf_counter() - t0) / n_batches
+
+
+def run_shape(name, n_batches, rounds, dev):
+    from structured_latent_odes_amd import configs as CF
+    from structured_latent_odes_amd import training as TR
+    from structured_latent_odes_amd.svi import SVI
+    from structured_latent_odes_amd.synthetic import synthetic_batch
+    fam, mod, cls, B, T, kw = SHAPES[name]
+    cfg = getattr(CF, "load_config_" + fam)()
+    cfg.update(seq_len=T, solver="rk4", num_particles=1, **kw)
+    torch.manual_seed(3)
+    obs, labels, times = synthetic_batch(fam, B, T, cfg.obs_dim, seed=7)
+    m = getattr(importlib.import_module("structured_latent_odes_amd.models." + mod), cls)(cfg, dev, times.to(dev))
+    one = {"observations": obs.to(dev)}
+    one.update({k: v.to(dev) for k, v in labels.items()})
+    batches = [one] * n_batches                                    # already on the device: batch_to_device is a no-op copy
+    losses = [SVI(m.model, m.guide, None), SVI(m.model_meta, m.guide_meta, None)]
+    legs = {"baseline": lambda post: TR.input_pred_stats(batches, m, losses, post, dev, fam),
+            "fused": lambda post: TR.input_pred_stats_fused(batches, m, post, dev, fam)}
+    res = {"B": B, "T": T, "batches_per_pass": n_batches, "rounds": rounds}
+    for post in (True, False):
+        for leg in legs.values():                                  # warm: workspaces, per-shape set-up
+            leg(post)
+        t = {k: [] for k in legs}
+        for _ in range(rounds):                                    # alternating legs
+            for k, leg in legs.items():
+                t[k].append(_pass_us(lambda: leg(post), n_batches, dev))
+        key = "posterior" if post else "prior"
+        res[key] = {k: {"median_us_per_batch": statistics.median(v), "spread_us_per_batch": max(v) - min(v), "all": v} for k, v in t.items()}
+        res[key]["faster_by_more_than_baseline_spread"] = bool(
+            res[key]["baseline"]["median_us_per_batch"] - res[key]["fused"]["median_us_per_batch"] > res[key]["baseline"]["spread_us_per_batch"])
+    eng = m._bind().engine
+    eng.profile_enable(True)
+    m.eval_stats(is_post=True, **{k: (v.reshape(v.shape[0], -1) if k != "observations" else v) for k, v in one.items()})
+    res["fused_call_kernels_us"] = eng.profile_read()
+    eng.profile_enable(False)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    out = {"tool": "stats_pass_bench", "device": torch.cuda.get_device_name(dev), "shapes": {n: run_shape(n, a.batches, a.rounds, dev) for n in SHAPES}}
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
