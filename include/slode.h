@@ -183,7 +183,9 @@ int slode_ode_solve_fwd(slode_handle h, const slode_shape* s, const slode_layout
                         const float* times, const float* stage_t, const float* z, float* x, void* stream);
 
 /* Exact discrete adjoint of slode_ode_solve_fwd (== autograd through torchdiffeq.odeint, adjoint_solver=False):
- * g_x[B,T,S] -> g_z[B,L] and grads[init_w1 .. dyn_bd] (overwritten). */
+ * g_x[B,T,S] -> g_z[B,L] and grads[init_w1 .. dyn_bd] (overwritten).
+ * Of `params` the call reads the flat range [lay->ode_begin, lay->n_params) only -- nothing of the encoder below it -- so a caller may pass
+ * (copy of that range) - lay->ode_begin as `params`: the weights of an earlier forward, frozen (the Python layer's autograd backward does). */
 int slode_ode_solve_bwd(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params,
                         const float* times, const float* stage_t, const float* z, const float* g_x,
                         float* g_z, float* grads, void* workspace, size_t workspace_bytes, void* stream);
@@ -216,7 +218,9 @@ int slode_decode_heads(slode_handle h, const slode_shape* s, const slode_layout*
 
 /* Backward of slode_decode_heads (autograd through Decoder.forward / GaussianDecoder.forward, models/decoders.py:42-54, 84-91, as the
  * reference's recon-style callers would differentiate it): g_mu[Q][B,C,T] (zeros for heads without a gradient), g_std[C,T] (NULL: none) ->
- * g_x[B,T,S], g_heads[Q][C,S] (the head weights' gradients, in slode_decode_heads' head order), g_cstd[C,T] (NULL to skip). */
+ * g_x[B,T,S], g_heads[Q][C,S] (the head weights' gradients, in slode_decode_heads' head order), g_cstd[C,T] (NULL to skip).
+ * Of `params` the call reads the flat range [lay->head_w[0], lay->n_params) only (the head weights and constant_std), so a caller may pass
+ * (copy of that range) - lay->head_w[0] as `params`. */
 int slode_decode_heads_bwd(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* x,
                            const float* g_mu, const float* g_std, float* g_x, float* g_heads, float* g_cstd, void* stream);
 

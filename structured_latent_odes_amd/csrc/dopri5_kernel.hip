@@ -700,6 +700,11 @@ __global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
   while (__any(live && j < T && steps < k.max_steps)) {
     const bool act = live && j < T && steps < k.max_steps;
     ++steps;
+    // The state must take the step the clock takes: t + dt is rounded to fp32, so the attempt uses that representable increment as its dt.
+    // Otherwise every accepted step advances y by dt and t by fl(t + dt) - t -- half an ulp of t apart, 1e-4 of a small step late in the
+    // grid -- and a low-order method's thousands of steps add that up to a time drift (adaptive_heun, rtol 1e-6: 2e-5 in the solution).
+    // (The expression must be evaluated as written: never build this file with -ffast-math / -fassociative-math, which fold it to dt.)
+    { const float dq = (t + dt) - t; dt = dq > 0.f ? dq : dt; }
     // the NT evaluation times of the step are known up front: NT independent table look-ups
     float te[M::NT];
 #pragma unroll
@@ -845,6 +850,11 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
   while (__any(live && j < T && steps < k.max_steps)) {
     const bool act = live && j < T && steps < k.max_steps;
     ++steps;
+    // The state must take the step the clock takes: t + dt is rounded to fp32, so the attempt uses that representable increment as its dt.
+    // Otherwise every accepted step advances y by dt and t by fl(t + dt) - t -- half an ulp of t apart, 1e-4 of a small step late in the
+    // grid -- and a low-order method's thousands of steps add that up to a time drift (adaptive_heun, rtol 1e-6: 2e-5 in the solution).
+    // (The expression must be evaluated as written: never build this file with -ffast-math / -fassociative-math, which fold it to dt.)
+    { const float dq = (t + dt) - t; dt = dq > 0.f ? dq : dt; }
     float te5[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) te5[i] = t + dt * M::C[i];

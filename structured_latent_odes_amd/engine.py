@@ -278,12 +278,27 @@ class Engine:
             self._p(self._f32(z, "z")), self._p(x), self._stream()))
         return x
 
-    def ode_solve_bwd(self, params, z, g_x, grads):
+    def ode_snapshot(self, params):
+        """Copy of the flat range [layout.ode_begin, n_params) -- everything ode_solve_bwd reads of the parameters -- and its start:
+        the weights of a forward solve, frozen for its backward (the fused Adam kernels update the flat vector in place)."""
+        lo = int(self.layout.ode_begin)
+        return params[lo:self.n_params].clone(), lo
+
+    def ode_solve_bwd(self, params, z, g_x, grads, snapshot=None):
+        """Backward of ode_solve.  `snapshot` = ode_snapshot(...) of the forward: the kernel then differentiates at those weights (it
+        reads no parameter below layout.ode_begin, so the base pointer is the snapshot's, moved back by its start)."""
         B = z.shape[0]
         ws = self.workspace(B)
         g_z = torch.empty_like(z)
+        if snapshot is not None:
+            snap, lo = snapshot
+            if snap.numel() != self.n_params - lo or lo != int(self.layout.ode_begin):
+                raise ValueError("snapshot does not match this engine's layout")
+            p_ptr = C.c_void_p(self._f32(snap, "snapshot").data_ptr() - 4 * lo)
+        else:
+            p_ptr = self._p(params)
         _check(self.lib, self.handle, self.lib.slode_ode_solve_bwd(
-            self.handle, C.byref(self.shape(B)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
+            self.handle, C.byref(self.shape(B)), C.byref(self.layout), p_ptr, self._p(self._times), self._p(self._stage_t),
             self._p(self._f32(z, "z")), self._p(self._f32(g_x, "g_x")), self._p(g_z), self._p(grads), self._p(ws), ws.numel() * 4, self._stream()))
         return g_z
 

@@ -173,10 +173,16 @@ class MechanisticBase(nn.Module):
         return SVI(self.model, self.guide, None).evaluate_loss(observations=observations, **labels)
 
     def guide(self, observations, **labels):
-        """q(z | x): encoder + one reparameterised Normal per latent group (mechanistic_cvs.py:213-238)."""
+        """q(z | x): encoder + one reparameterised Normal per latent group (mechanistic_cvs.py:213-238).  The sites are reparameterised,
+        so z carries the encoder's graph: the noise is one drawing call of the engine's generator (the call ``sample_normal`` would
+        make: same draw, the counter moves by one) and z = loc + scale * eps is formed in torch.  Without gradients the one-kernel
+        ``sample_normal`` is used (the same draw; the multiply-add may be fused, so z can differ in the last bit)."""
         b = self._bind()
         loc, scale = self.encoder.forward(observations)
-        z = b.engine.sample_normal(loc.contiguous(), scale.contiguous())
+        if torch.is_grad_enabled() and (loc.requires_grad or scale.requires_grad):
+            z = loc + scale * b.engine.draw_normal(loc.shape[0])
+        else:
+            z = b.engine.sample_normal(loc.contiguous(), scale.contiguous())
         return tuple(self._z_group(z, g) for g in self.Z_GROUPS)
 
     def model_meta(self, observations, **labels):

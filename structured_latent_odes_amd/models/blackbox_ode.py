@@ -61,15 +61,22 @@ class _SolveFn(torch.autograd.Function):
         z = z.contiguous()
         x = b.engine.ode_solve(b.flat, z)
         ctx.model = model
-        ctx.save_for_backward(z)
+        # The backward differentiates at the weights the FORWARD saw: the nets are views of the flat parameter vector, which the fused
+        # Adam kernels update in place through raw pointers (no autograd version bump) -- so a forward that will be differentiated
+        # keeps its own copy of the segment the backward kernel reads (as _HeadsFn does for the heads).
+        if any(ctx.needs_input_grad):
+            snap, ctx.snap_lo = b.engine.ode_snapshot(b.flat)
+            ctx.save_for_backward(z, snap)
+        else:
+            ctx.save_for_backward(z)
         return x
 
     @staticmethod
     def backward(ctx, g_x):
         b = ctx.model._binding_or_raise()
-        (z,) = ctx.saved_tensors
+        z, snap = ctx.saved_tensors
         grads = torch.zeros(b.engine.n_params, dtype=torch.float32, device=b.engine.device)
-        g_z = b.engine.ode_solve_bwd(b.flat, z, g_x.contiguous(), grads)
+        g_z = b.engine.ode_solve_bwd(b.flat, z, g_x.contiguous(), grads, snapshot=(snap, ctx.snap_lo))
         out = [grads[b.slices[_O + k]].view(p.shape) for k, p in zip(_KEYS, ctx.model._param_list())]
         return (None, g_z, *out)
 
