@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 140 /* 0.1.4: slode_eval_stats (0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 150 /* 0.1.5: slode_recon_moments (0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -331,6 +331,31 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
                      const float* stage_t, const slode_batch* batch, int is_post, float* out /* [SLODE_EVAL_SLOTS] */, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- the Monte-Carlo summary of `multiple_samples` as ONE call (training_proc.py:205-223: num_samples = config.num_samples = 200 calls of recon,
+ * saved as mu_50_post_sample.npy & co.; the evaluation notebook reduces them at once with np.mean(..., 2) / np.std(..., 2)) -----------------------
+ * Per trajectory, the sample moments of every decoder head curve over num_samples latent draws: mean[q][b][c][t] and sd[q][b][c][t] (T contiguous;
+ * sd may be NULL), sd the POPULATION standard deviation (divisor num_samples: np.std's default); num_samples = 1 gives sd = 0 exactly and mean =
+ * that draw's curve.  Nothing sized num_samples x B x C x T is written anywhere: one workgroup walks the draws of its trajectory and keeps the
+ * running moments of its Q x C x T values on chip, shifted by the first draw's value (no sum of squares of the values themselves).
+ *   Head order: Q and the order of q are those of slode_layout::head_w, as in slode_decode_heads -- SLODE_ALD: Q = 3, q = 0: mu_50 (output_q50),
+ *   q = 1: mu_75 (output_q75), q = 2: mu_25 (output_q25); SLODE_GAUSS: Q = 1, q = 0: mean (output_mean).
+ *   is_post != 0: draws from the posterior N(loc(x), scale(x)) -- three launches ("weff", "enc_fwd2", "recon_moments" in slode_profile_read): the
+ *   encoder runs once, as in slode_eval_stats.  is_post == 0: draws from the conditional prior p(z | labels), N(0, 1) on the dims outside every
+ *   prior group -- ONE launch ("recon_moments"): the encoder does not run, batch->obs may be NULL and its strides are not read.
+ *   Noise: batch->eps == NULL uses ONE drawing call n of the handle's generator -- draw k of trajectory b is row k * B + b (plus first_trajectory)
+ *   of that call, i.e. slode_rng_normal(h, n, num_samples * B, L, ...) viewed as [num_samples, B, L] -- and leaves the counter at n + 1;
+ *   batch->eps != NULL is a dense [num_samples, B, L] tensor.  The result is a function of (parameters, inputs, noise) alone: independent of the
+ *   grid, bitwise reproducible from run to run (every value has one owner thread, which takes the draws in the order k = 0 .. num_samples - 1).
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: a NULL handle (before anything else);
+ * num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1;
+ * posterior with observation strides the folded encoder path does not take ([B,T,C] or [B,C,T] contiguous, C in {3, 4}) or under SLODE_NO_FOLD;
+ * the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG set in the environment of slode_create; LDS tables (step table 2 (T - 1) S,
+ * moments 3 Q C T, staged weights) beyond the budget of 160 KiB.  The caller then reduces slode_ode_solve_fwd + slode_decode_heads itself. */
+int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                        const float* stage_t, const slode_batch* batch, int is_post, int num_samples, float* mean /* [Q,B,C,T] */,
+                        float* sd /* [Q,B,C,T] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -401,11 +426,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -496,6 +496,7 @@ struct StepCall {
   const float *params = nullptr, *times = nullptr, *stage_t = nullptr, *obs = nullptr, *u = nullptr, *eps = nullptr;
   const int64_t* obs_strides = nullptr; void* workspace = nullptr; size_t workspace_bytes = 0; hipStream_t stream = nullptr;
   float *loss_out = nullptr, *grads = nullptr, *x_out = nullptr, *z_out = nullptr, *payload = nullptr;
+  int no_loss = 0;   // 1: a forward-only set-up that writes no loss (slode_recon_moments): loss_out may be NULL
   AdamHost adam{}; LabelSrc lab{};   // fused Adam (adam_args; adam.p == nullptr: none); label tensors one by one (batch_labels; n == 0: u)
 };
 struct Step {   // what the stages share, worked out once by step_setup
@@ -584,7 +585,7 @@ static int step_setup(Step& p) {
   slode_handle h = p.h; const slode_shape& s = p.s; const StepCall& c = p.c;
   p.aux = c.kind == SLODE_SVI_AUX;
   const bool missing = c.phase == STEP_APPLY ? !c.payload || !c.grads
-                                             : (!p.aux && (!c.times || !c.stage_t)) || !c.obs || (c.phase == STEP_WHOLE ? !c.loss_out : !c.payload);
+                                             : (!p.aux && (!c.times || !c.stage_t)) || !c.obs || (c.phase == STEP_WHOLE ? (!c.loss_out && !c.no_loss) : !c.payload);
   if (missing || !c.obs_strides || !c.workspace) return fail(h, SLODE_EINVAL, "a required pointer is NULL");
   p.K = particles_of(s);
   // eps == NULL: this call draws the guide's noise inside its kernels -- call number rng_counter of the handle's Philox stream; K particles
@@ -895,6 +896,75 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
   FoldLaunch fl{}; bool enc_fused = false;
   if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_eval(a, c.stream));
+  return SLODE_OK;
+}
+
+// Mean / sd of the decoder head curves over num_samples latent draws (include/slode.h): refusals first -- nothing launched, no draw consumed --
+// then, for the posterior, the fold + encoder launches of a forward-only step; then the one kernel that walks the draws of its trajectories.
+int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                        const float* stage_t, const slode_batch* batch, int is_post, int num_samples, float* mean, float* sd, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  const char* why = check_common(h, s, lay, params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  if (!batch || !mean || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_recon_moments: batch / mean / times / stage_t / workspace is NULL");
+  if (num_samples < 1) return fail(h, SLODE_EINVAL, "slode_recon_moments: num_samples = %d < 1", num_samples);
+  if ((long long)s->B * num_samples > 0x3fffffff)
+    return fail(h, SLODE_EINVAL, "slode_recon_moments: B x num_samples = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_samples);
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "slode_recon_moments: adaptive solver %s is not taken (fixed-grid methods only); reduce recon_samples instead", method_name(s->method));
+  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_recon_moments: particles = %d is not taken (one particle only)", s->particles);
+  if (h->fold_on || h->ode_pack || h->ode_alg)
+    return fail(h, SLODE_EINVAL, "slode_recon_moments cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
+  const int64_t* os = batch->obs_strides;
+  if (is_post) {
+    const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+    if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_recon_moments: the posterior needs observations (batch->obs is NULL)");
+    if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
+      return fail(h, SLODE_EINVAL, "slode_recon_moments: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
+                                   "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD); reduce recon_samples instead",
+                  (long long)os[0], (long long)os[1], (long long)os[2]);
+  }
+  const size_t lds = slode_recon_moments_lds_bytes(*s, h->ode_generic);
+  if (lds > SLODE_RECON_MOMENTS_LDS_MAX)
+    return fail(h, SLODE_EINVAL, "slode_recon_moments: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, moments, staged weights) exceed "
+                                 "the budget of %d B; reduce recon_samples instead", s->T, s->S, s->C, lds, SLODE_RECON_MOMENTS_LDS_MAX);
+  ReconMomentsLaunch a{};
+  int rc = batch_labels(h, s, batch, &a.lab);
+  if (rc != SLODE_OK) return rc;
+  if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_recon_moments: the prior needs the label tensors of the conditional prior groups");
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps; a.mean = mean; a.sd = sd;
+  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
+  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
+  long long g = s->B;
+  if (s->B > 65536 || h->ode_loop) {
+    g = (long long)h->num_cu * 4;
+    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+    if (g > s->B) g = s->B;
+  }
+  a.grid = (int)g;
+  const uint64_t n0 = h->rng_counter;
+  if (!is_post) {
+    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
+    if (!batch->eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
+    ClockScope clock_scope(h, true);
+    HIP_TRY(h, slode_launch_recon_moments(a, (hipStream_t)stream));
+    return SLODE_OK;
+  }
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = a.lab;
+  Step p{h, *s, *lay, c};
+  rc = step_setup(p);
+  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
+  if (rc != SLODE_OK) return rc;
+  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_recon_moments: the folded encoder path does not take these observations");
+  a.loc = p.w.loc; a.scale = p.w.scale;
+  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
+  ClockScope clock_scope(h, true);
+  FoldLaunch fl{}; bool enc_fused = false;
+  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_recon_moments(a, c.stream));
   return SLODE_OK;
 }
 

@@ -550,6 +550,22 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
+// Sample moments of the reconstruction (recon_moments_kernel.hip; slode_recon_moments): mean / sd [Q, B, C, T] over num_samples latent draws per
+// trajectory.  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise:
+// rng.on: row k * B + b of ONE drawing call; else eps [num_samples, B, L].  sd may be NULL.
+struct ReconMomentsLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *loc, *scale, *eps, *u;
+  float *mean, *sd;
+  int num_samples, grid, is_post, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+#define SLODE_RECON_MOMENTS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moments, staged weights) must fit
+hipError_t slode_launch_recon_moments(const ReconMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
+size_t slode_recon_moments_lds_bytes(const slode_shape& s, int force_generic);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

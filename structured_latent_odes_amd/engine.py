@@ -71,7 +71,9 @@ class ModelSpec:
 def _check(lib, handle, rc):
     if rc != 0:
         msg = lib.slode_last_error(handle)
-        raise L.SlodeError("libslode call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+        err = L.SlodeError("libslode call failed (%d): %s" % (rc, msg.decode() if msg else "?"))
+        err.status = int(rc)   # slode_status: -1 = SLODE_EINVAL (a refusal: nothing was launched), -2 = SLODE_EHIP, -3 = SLODE_ENOSPC
+        raise err
 
 
 PROFILE_MAX_KERNELS = 16   # include/slode.h, SLODE_PROFILE_MAX_KERNELS
@@ -487,6 +489,30 @@ class Engine:
             self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
             C.byref(batch), 1 if is_post else 0, self._p(out), self._p(ws), ws.numel() * 4, self._stream()))
         return out
+
+    def recon_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, mean=None, sd=None, particles: int = 1):
+        """slode_recon_moments: per trajectory, the mean and the population sd (np.std) over ``num_samples`` latent draws of every decoder
+        head curve -- ``(mean, sd)``, each float32 [Q, B, C, T] with q in the layout's head order (ALD: mu_50, mu_75, mu_25; Gauss: mean)
+        -- enqueued on the current stream; nothing sized num_samples x B x C x T exists anywhere.  The batch's eps is
+        [num_samples, B, L] or None (ONE drawing call of the generator: row k * B + b is draw k of trajectory b, what
+        ``draw_normal(num_samples * B).view(num_samples, B, L)`` yields).  Raises SlodeError naming the reason for what the kernel does not
+        take (adaptive solver, ``particles`` > 1, strided posterior observations, measured arms, num_samples < 1, LDS budget): nothing is
+        launched and no draw is consumed then."""
+        sp = self.spec
+        shp = (1 if sp.gauss else 3, B, sp.n_channels, self.T)
+        if mean is None:
+            mean = torch.empty(shp, dtype=torch.float32, device=self.device)
+        if sd is None:
+            sd = torch.empty(shp, dtype=torch.float32, device=self.device)
+        for t, name in ((mean, "mean"), (sd, "sd")):
+            if tuple(self._f32(t, name).shape) != shp:
+                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
+        ws = self.workspace(B, particles)
+        self._guard(params, ws)
+        _check(self.lib, self.handle, self.lib.slode_recon_moments(
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
+            C.byref(batch), 1 if is_post else 0, int(num_samples), self._p(mean), self._p(sd), self._p(ws), ws.numel() * 4, self._stream()))
+        return mean, sd
 
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:

@@ -323,3 +323,69 @@ class MechanisticBase(nn.Module):
                 written.append(path)
         return written
 
+
+    # ---- the Monte-Carlo summary of multiple_samples: mean and sd over the draws, nothing per draw kept -------------------------------
+    MOMENT_HEADS = {False: ("mu_50", "mu_75", "mu_25"), True: ("mean",)}   # GAUSS -> curve names in the engine's head order q = 0, 1, 2
+    MOMENTS_CHUNK_ROWS = 65536                                             # composed route: trajectories (num_samples x rows) per chunk
+
+    def recon_moments(self, observations, is_post, num_samples: int, eps=None, **labels):
+        """What the reference's evaluation takes from ``multiple_samples``: per trajectory, the mean and the population standard
+        deviation (``np.mean(..., -1)`` / ``np.std(..., -1)``) over ``num_samples`` latent draws of every decoder head curve, as
+        ``{"mu_50": (mean, sd), "mu_75": ..., "mu_25": ...}`` (``{"mean": (mean, sd)}`` for the Gaussian family), each tensor
+        ``[B, C, T]`` -- from ONE engine call (``slode_recon_moments``) that keeps the running moments on chip: no
+        ``[B, C, T, num_samples]`` tensor exists.  ``eps`` ``[num_samples, B, L]`` makes it reproducible; None draws one call of the
+        engine's generator, the draw ``recon_samples`` makes.  Where the engine refuses (adaptive solver, strided observations,
+        measured arms, LDS budget) the same dict is composed from ``recon_samples`` in chunks over B."""
+        from .. import _lib as L
+        b = self._bind()
+        B, ns = observations.shape[0], int(num_samples)
+        if ns < 1:
+            raise ValueError("num_samples must be >= 1, got %d" % ns)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        try:
+            labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+            e = eps if eps is None or ns > 1 else eps.reshape(B, -1)
+            bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=ns)
+            mean, sd = b.engine.recon_moments(b.flat, bt, B, is_post, ns)
+            return {n: (mean[q], sd[q]) for q, n in enumerate(names)}
+        except L.SlodeError as err:
+            if getattr(err, "status", None) != -1:      # only a refusal (SLODE_EINVAL: nothing launched, nothing drawn) leads to the composition
+                raise
+            return self._recon_moments_composed(observations, is_post, ns, eps, labels)
+
+    def _recon_moments_composed(self, observations, is_post, num_samples, eps, labels):
+        """The same dict from ``recon_samples``, ``MOMENTS_CHUNK_ROWS // num_samples`` rows of the batch at a time, reduced in fp32 with
+        ``mean`` / ``std(unbiased=False)`` over the sample axis.  The noise is drawn once for the whole batch (counter n -> n + 1, row
+        k * B + b = draw k of trajectory b) and sliced per chunk, so the result does not depend on the chunking."""
+        B = observations.shape[0]
+        rows = max(1, self.MOMENTS_CHUNK_ROWS // num_samples)
+        if eps is None:      # ONE drawing call for the whole batch, as recon_samples and the engine call make it; the chunks take their rows
+            eps = self._bind().engine.draw_normal(num_samples * B).view(num_samples, B, -1)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        parts = {n: ([], []) for n in names}
+        for lo in range(0, B, rows):
+            hi = min(B, lo + rows)
+            res = self.recon_samples(observations[lo:hi], is_post, num_samples, eps=None if eps is None else eps[:, lo:hi],
+                                     **{k: v[lo:hi] for k, v in labels.items()})
+            for n in names:
+                v = res[n].to(torch.float32)
+                parts[n][0].append(v.mean(dim=-1))
+                parts[n][1].append(v.std(dim=-1, unbiased=False))
+            del res
+        return {n: (torch.cat(m, 0), torch.cat(s, 0)) for n, (m, s) in parts.items()}
+
+    def save_recon_moments(self, results_dir: str, observations, is_post, num_samples: int, **labels):
+        """Writes ``<curve>_<post|prior>_sample_mean.npy`` and ``..._sample_sd.npy`` (``[B, C, T]`` each) for every head curve: new names
+        beside the reference's ``mu_50_post_sample.npy`` & co., which ``save_recon_samples`` keeps writing."""
+        import os
+        import numpy as np
+        res = self.recon_moments(observations, is_post, num_samples, **labels)
+        os.makedirs(results_dir, exist_ok=True)
+        tag = "post_sample" if is_post else "prior_sample"
+        written = []
+        for name, (mean, sd) in res.items():
+            for kind, val in (("mean", mean), ("sd", sd)):
+                path = os.path.join(results_dir, "%s_%s_%s.npy" % (name, tag, kind))
+                np.save(path, val.cpu().numpy())
+                written.append(path)
+        return written

@@ -110,10 +110,14 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
-          test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False):
+          test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
+          results_dir: Optional[str] = None):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
-    var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form."""
+    var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
+    sample_moments: after the final test passes, the reference's ``multiple_samples`` stage (training_proc.py:205-223) on the first test
+    batch, posterior and prior, config.num_samples draws -- as ``save_recon_moments`` (mean and sd over the draws per curve, written to
+    ``results_dir``, default ``results_<config.model>``); off by default: no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -183,6 +187,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     tail = "ELBO: best_epoch: {} post: {} prior: {}".format(best_epoch, test_post["elbo"], test_prior["elbo"])
     print(tail)
     logging.debug(tail)
+    if sample_moments:
+        d = batch_to_device(next(iter(test_b)), device, family)
+        out_dir = results_dir or "results_%s" % config.model
+        for is_post in (True, False):
+            written = best_model.save_recon_moments(out_dir, is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), **d)
+            logging.debug("multiple_samples moments: %s", written)
     return var_model, best_model, best_epoch
 
 
@@ -226,19 +236,27 @@ def real_batches(config, family: str, data_dir: str):
     return out
 
 
-def main(family: str, load_config, model_cls, model_cls_gauss):
+def build_parser():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batches-per-epoch", type=int, default=7)
     ap.add_argument("--data-dir", default=None, help="directory with the reference's data files (default: synthetic batches)")
     ap.add_argument("--fused-stats", action="store_true", help="per-epoch statistics: one engine call per batch, one read-back per pass")
-    a = ap.parse_args()
+    ap.add_argument("--sample-moments", action="store_true",
+                    help="after training: mean and sd of config.num_samples reconstructions per curve (save_recon_moments), posterior and prior")
+    return ap
+
+
+def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
+    a = build_parser().parse_args(argv)
     config = load_config()
     config.num_epochs = a.epochs
     os.makedirs("results_%s" % config.model, exist_ok=True)
     logging.basicConfig(filename="results_%s/model.log" % config.model, filemode="w", level=logging.DEBUG)
     kw = {"fused_stats": a.fused_stats}
+    if a.sample_moments:
+        kw["sample_moments"] = True
     if a.data_dir:
         got = real_batches(config, family, a.data_dir)
         kw["train_batches"], kw["val_batches"], kw["times"] = got[:3]
