@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 150 /* 0.1.5: slode_recon_moments (0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 160 /* 0.1.6: slode_traj_bounds (0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -37,6 +37,7 @@ extern "C" {
 #define SLODE_MAX_LABELS 4 /* label tensors of one minibatch (proc: aR, aS, C12, C6) */
 #define SLODE_MAX_PARTICLES 1024
 #define SLODE_EVAL_SLOTS 8 /* floats of one slode_eval_stats row */
+#define SLODE_BOUND_SLOTS 4 /* floats of one slode_traj_bounds row */
 
 typedef enum slode_status {
   SLODE_OK = 0,
@@ -356,6 +357,33 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
                         const float* stage_t, const slode_batch* batch, int is_post, int num_samples, float* mean /* [Q,B,C,T] */,
                         float* sd /* [Q,B,C,T] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-trajectory -ELBO and importance-weighted bounds from K latent draws as ONE call (no reference counterpart: the reference's losses are
+ * sums over the batch; what a user asks of a test set -- which subjects the model explains badly, a held-out log-likelihood estimate, an outlier
+ * score -- is per trajectory) -------------------------------------------------------------------------------------------------------------------
+ * For trajectory b and draw k, z = loc(x_b) + scale(x_b) eps[k][b], loss[k][b] is the main loss of that single row:
+ *   -(log-likelihood + log p(z | labels) - log q(z | x)), plus the 46 x label terms where the main model scores the labels (aux_in_main: proc)
+ * -- separable over rows, so sum_b loss[k][b] = slode_svi_step(kind MAIN, grads NULL) on that noise.  Written per trajectory:
+ *   bounds[b][0]  mean over k of loss[k][b]: the trajectory's -ELBO, the summand of Trace_ELBO(num_particles = K).evaluate_loss
+ *   bounds[b][1]  -log(1/K sum_k exp(-loss[k][b])): the importance-weighted bound (IWAE); <= bounds[b][0], equal to it at K = 1
+ *   bounds[b][2]  effective sample size (sum w)^2 / sum w^2 of w_k = exp(-loss[k][b] + min_k loss[k][b]); in [1, K], exactly 1 at K = 1
+ *   bounds[b][3]  mean over k of the negative log-likelihood term alone (bounds[b][0] - bounds[b][3]: the KL-and-label part)
+ * and, when loss_kb != NULL, every loss[k][b] itself ([num_draws, B]).  bounds must be 16-byte aligned (one 16-byte store per row).
+ * Posterior draws only.  Noise: batch->eps == NULL uses drawing calls n .. n + K - 1 of the handle's generator -- draw k of trajectory b is row b
+ * of call n + k, the convention of slode_svi_step with particles = K -- and leaves the counter at n + K; batch->eps != NULL is a dense [K, B, L]
+ * tensor.  One workgroup walks the K draws of its trajectory; the K losses are kept on chip and reduced in fp64 in a fixed order: the result is a
+ * function of (parameters, inputs, noise) alone -- bitwise equal from run to run, for every grid, for in-kernel and explicit noise.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Three launches ("weff", "enc_fwd2", "traj_bounds" in
+ * slode_profile_read): the encoder runs once per trajectory, not once per draw.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: a NULL handle (before anything else);
+ * num_draws < 1 (and B x num_draws beyond 2^30 - 1 noise rows); adaptive solver (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1 in the
+ * shape (the draws are num_draws); observation strides the folded encoder path does not take ([B,T,C] or [B,C,T] contiguous, C in {3, 4}) or
+ * SLODE_NO_FOLD; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG set in the environment of slode_create; LDS tables (step table
+ * 2 (T - 1) S, observations and likelihood scales 3 C T, staged weights, the 2 K per-draw values) beyond the budget of 160 KiB.  There is no
+ * composed fallback: no other call returns a per-trajectory loss. */
+int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                      const float* stage_t, const slode_batch* batch, int num_draws, float* bounds /* [B, SLODE_BOUND_SLOTS] */,
+                      float* loss_kb /* [num_draws, B] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -426,11 +454,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -968,6 +968,68 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
   return SLODE_OK;
 }
 
+// Per-trajectory -ELBO, importance-weighted bound, effective sample size and mean negative log-likelihood from num_draws posterior draws
+// (include/slode.h): refusals first -- nothing launched, no draw consumed -- then the fold + encoder launches of a forward-only step and the
+// one kernel that walks the draws of its trajectories.  No composed fallback: no other call returns a per-trajectory loss.
+int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                      const float* stage_t, const slode_batch* batch, int num_draws, float* bounds, float* loss_kb, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  const char* why = check_common(h, s, lay, params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  if (!batch || !bounds || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_traj_bounds: batch / bounds / times / stage_t / workspace is NULL");
+  if (((uintptr_t)bounds & 15) != 0) return fail(h, SLODE_EINVAL, "slode_traj_bounds: bounds must be 16-byte aligned");
+  if (num_draws < 1) return fail(h, SLODE_EINVAL, "slode_traj_bounds: num_draws = %d < 1", num_draws);
+  if ((long long)s->B * num_draws > 0x3fffffff)
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds: B x num_draws = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_draws);
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds: adaptive solver %s is not taken (fixed-grid methods only)", method_name(s->method));
+  if (particles_of(*s) > 1)
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds: particles = %d is not taken (the shape has one particle; the draws are num_draws)", s->particles);
+  if (h->fold_on || h->ode_pack || h->ode_alg)
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_traj_bounds: batch->obs is NULL");
+  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
+                                 "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD)",
+                (long long)os[0], (long long)os[1], (long long)os[2]);
+  const size_t lds = slode_traj_bounds_lds_bytes(*s, num_draws, h->ode_generic);
+  if (lds > SLODE_TRAJ_BOUNDS_LDS_MAX)
+    return fail(h, SLODE_EINVAL, "slode_traj_bounds: the LDS tables of T = %d, S = %d, C = %d, num_draws = %d (%zu B: step table, observations, staged "
+                                 "weights, the per-draw losses) exceed the budget of %d B; fewer draws per call fit",
+                s->T, s->S, s->C, num_draws, lds, SLODE_TRAJ_BOUNDS_LDS_MAX);
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  int rc = batch_call(h, s, SLODE_SVI_MAIN, batch, &c);
+  if (rc != SLODE_OK) return rc;
+  const uint64_t n0 = h->rng_counter;
+  Step p{h, *s, *lay, c};
+  rc = step_setup(p);
+  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
+  if (rc != SLODE_OK) return rc;
+  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_traj_bounds: the folded encoder path does not take these observations");
+  TrajBoundsLaunch a{};
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.t_major = p.t_major ? 1 : 0;
+  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.bounds = bounds; a.loss_kb = loss_kb;
+  a.num_draws = num_draws; a.force_generic = h->ode_generic; a.lab = c.lab;
+  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
+  long long g = s->B;
+  if (s->B > 65536 || h->ode_loop) {
+    g = (long long)h->num_cu * 4;
+    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+    if (g > s->B) g = s->B;
+  }
+  a.grid = (int)g;
+  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + (uint64_t)num_draws; }
+  ClockScope clock_scope(h, true);
+  FoldLaunch fl{}; bool enc_fused = false;
+  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_traj_bounds(a, c.stream));
+  return SLODE_OK;
+}
+
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {
   if (check_shape(s) || !lay) return 0;
   const int part = kind == SLODE_SVI_AUX ? lay->cstd - lay->aux_w1[0] : lay->n_params - lay->ode_begin;

@@ -566,6 +566,24 @@ struct ReconMomentsLaunch {
 hipError_t slode_launch_recon_moments(const ReconMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_recon_moments_lds_bytes(const slode_shape& s, int force_generic);
 
+// Per-trajectory bounds from K draws (traj_bounds_kernel.hip; slode_traj_bounds): bounds [B, SLODE_BOUND_SLOTS] (16-byte aligned), loss_kb
+// [num_draws, B] or NULL.  loc / scale [B, L] from the encoder launch, sigtab from the fold launch; obs: dense rows of C*T floats (sb apart),
+// t_major: [T][C] inside a row, else [C][T].  Noise: rng.on: row b of drawing calls c2 .. c2 + num_draws - 1; else eps [num_draws, B, L].
+struct TrajBoundsLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *obs;
+  int64_t sb;
+  const float *loc, *scale, *eps, *u, *sigtab;
+  float *bounds, *loss_kb;
+  int num_draws, grid, t_major, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+#define SLODE_TRAJ_BOUNDS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, observations, staged weights, K losses) must fit
+hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
+size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

@@ -514,6 +514,30 @@ class Engine:
             C.byref(batch), 1 if is_post else 0, int(num_samples), self._p(mean), self._p(sd), self._p(ws), ws.numel() * 4, self._stream()))
         return mean, sd
 
+    def traj_bounds(self, params, batch: L.Batch, B: int, num_draws: int, bounds=None, loss_kb=None, particles: int = 1):
+        """slode_traj_bounds: per trajectory, from ``num_draws`` posterior draws, ``bounds`` float32 [B, L.BOUND_SLOTS] = [-ELBO (mean of
+        the per-draw losses), importance-weighted bound -log(1/K sum exp(-loss)), effective sample size of the weights, mean negative
+        log-likelihood] and ``loss_kb`` float32 [num_draws, B], the per-draw losses themselves (the main loss of the single row b on draw
+        k) -- ``(bounds, loss_kb)``, enqueued on the current stream: no synchronisation, no read-back.  The batch's eps is
+        [num_draws, B, L] (``make_batch(..., particles=num_draws)``) or None (drawing calls n .. n + num_draws - 1 of the generator: draw
+        k of trajectory b is row b of call n + k, as ``svi_step(particles=num_draws)`` draws).  Raises SlodeError naming the reason for
+        what the kernel does not take (adaptive solver, ``particles`` > 1 in the shape, strided observations, SLODE_NO_FOLD, measured arms, num_draws < 1, LDS budget):
+        nothing is launched and no draw is consumed then; there is no composed fallback."""
+        K = int(num_draws)
+        if bounds is None:
+            bounds = torch.empty(B, L.BOUND_SLOTS, dtype=torch.float32, device=self.device)
+        if loss_kb is None:
+            loss_kb = torch.empty(max(K, 0), B, dtype=torch.float32, device=self.device)
+        for t, name, shp in ((bounds, "bounds", (B, L.BOUND_SLOTS)), (loss_kb, "loss_kb", (max(K, 0), B))):
+            if tuple(self._f32(t, name).shape) != shp:
+                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
+        ws = self.workspace(B, particles)
+        self._guard(params, ws)
+        _check(self.lib, self.handle, self.lib.slode_traj_bounds(
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
+            C.byref(batch), K, self._p(bounds), self._p(loss_kb), self._p(ws), ws.numel() * 4, self._stream()))
+        return bounds, loss_kb
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

@@ -389,3 +389,45 @@ class MechanisticBase(nn.Module):
                 np.save(path, val.cpu().numpy())
                 written.append(path)
         return written
+
+    # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
+    BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
+
+    def trajectory_bounds(self, observations, num_draws: int, eps=None, return_draws: bool = False, **labels):
+        """Per trajectory, from ``num_draws`` = K posterior draws z_k = loc(x) + scale(x) eps_k: ``{"elbo": [B], "iw_bound": [B], "ess": [B],
+        "nll": [B]}`` -- the -ELBO of the trajectory (mean over k of the main loss of that single row: the summand of
+        ``Trace_ELBO(num_particles=K).evaluate_loss``), the importance-weighted bound -log(1/K sum_k exp(-loss_k)) (<= elbo; a tighter
+        estimate of -log p(x | labels), comparable between the ALD and Gauss variants), the effective sample size of the importance weights
+        (in [1, K]) and the mean negative log-likelihood term -- plus ``"loss": [K, B]``, the per-draw losses, with ``return_draws``.  ONE
+        engine call (``slode_traj_bounds``): the encoder runs once per trajectory, the K solves of a trajectory in one workgroup.  ``eps``
+        ``[K, B, L]`` makes it reproducible; None takes drawing calls n .. n + K - 1 of the engine's generator (draw k of trajectory b: row b
+        of call n + k, as a K-particle ELBO step draws).  What the engine refuses (adaptive solver, strided observations, measured arms,
+        LDS budget) raises its SlodeError: no other call yields a per-trajectory loss to compose from."""
+        b = self._bind()
+        B, K = observations.shape[0], int(num_draws)
+        if K < 1:
+            raise ValueError("num_draws must be >= 1, got %d" % K)
+        labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+        e = eps if eps is None or K > 1 else eps.reshape(B, -1)
+        bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=K)
+        bounds, loss = b.engine.traj_bounds(b.flat, bt, B, K)
+        res = {n: bounds[:, i] for i, n in enumerate(self.BOUND_NAMES)}
+        if return_draws:
+            res["loss"] = loss
+        return res
+
+    def save_trajectory_bounds(self, results_dir: str, batches, num_draws: int):
+        """Runs ``trajectory_bounds`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes the table
+        ``bounds_post.npy``, float32 ``[n, 4]`` with the columns of ``BOUND_NAMES`` and the trajectories in loader order, beside the
+        reference's result files.  One read-back, at the end.  Returns the path."""
+        import os
+        import numpy as np
+        rows = []
+        for d in batches:
+            r = self.trajectory_bounds(num_draws=num_draws, **d)
+            rows.append(torch.stack([r[n] for n in self.BOUND_NAMES], dim=1))
+        table = torch.cat(rows, 0).cpu().numpy().astype(np.float32) if rows else np.zeros((0, len(self.BOUND_NAMES)), np.float32)
+        os.makedirs(results_dir, exist_ok=True)
+        path = os.path.join(results_dir, "bounds_post.npy")
+        np.save(path, table)
+        return path

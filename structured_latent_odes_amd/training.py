@@ -111,13 +111,16 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
-          results_dir: Optional[str] = None):
+          results_dir: Optional[str] = None, test_bounds: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
     sample_moments: after the final test passes, the reference's ``multiple_samples`` stage (training_proc.py:205-223) on the first test
     batch, posterior and prior, config.num_samples draws -- as ``save_recon_moments`` (mean and sd over the draws per curve, written to
-    ``results_dir``, default ``results_<config.model>``); off by default: no such stage runs."""
+    ``results_dir``, default ``results_<config.model>``); off by default: no such stage runs.
+    test_bounds = K > 0: after training, the best model's per-trajectory bounds from K posterior draws (``save_trajectory_bounds``: -ELBO,
+    importance-weighted bound, effective sample size, mean NLL) over the validation loader, written to ``results_dir`` as
+    ``bounds_post.npy`` [n, 4]; 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -193,6 +196,10 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
         for is_post in (True, False):
             written = best_model.save_recon_moments(out_dir, is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), **d)
             logging.debug("multiple_samples moments: %s", written)
+    if test_bounds:
+        path = best_model.save_trajectory_bounds(results_dir or "results_%s" % config.model,
+                                                 (batch_to_device(b, device, family) for b in val_b), int(test_bounds))
+        logging.debug("per-trajectory bounds: %s", path)
     return var_model, best_model, best_epoch
 
 
@@ -245,6 +252,9 @@ def build_parser():
     ap.add_argument("--fused-stats", action="store_true", help="per-epoch statistics: one engine call per batch, one read-back per pass")
     ap.add_argument("--sample-moments", action="store_true",
                     help="after training: mean and sd of config.num_samples reconstructions per curve (save_recon_moments), posterior and prior")
+    ap.add_argument("--test-bounds", type=int, default=0, metavar="K",
+                    help="after training: per-trajectory -ELBO, importance-weighted bound, ESS and NLL of the best model from K posterior draws over "
+                         "the validation loader (save_trajectory_bounds: bounds_post.npy)")
     return ap
 
 
@@ -257,6 +267,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
     kw = {"fused_stats": a.fused_stats}
     if a.sample_moments:
         kw["sample_moments"] = True
+    if a.test_bounds:
+        kw["test_bounds"] = a.test_bounds
     if a.data_dir:
         got = real_batches(config, family, a.data_dir)
         kw["train_batches"], kw["val_batches"], kw["times"] = got[:3]
