@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 160 /* 0.1.6: slode_traj_bounds (0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 170 /* 0.1.7: slode_intervene_moments (0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -384,6 +384,41 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
                       const float* stage_t, const slode_batch* batch, int num_draws, float* bounds /* [B, SLODE_BOUND_SLOTS] */,
                       float* loss_kb /* [num_draws, B] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- counterfactual curves as ONE call (no reference counterpart: the reference's recon takes the whole latent from the posterior or the whole
+ * latent from the conditional prior; the structured latent exists to ask "what would THIS subject's curves have looked like under THAT input?") ----
+ * For trajectory b and draw k, with ONE noise row eps[k][b][0..L) shared by both arms:
+ *   factual         z_f = loc(x_b) + scale(x_b) eps: exactly the posterior draw of slode_recon_moments(is_post = 1)
+ *   counterfactual  z_cf[l] = z_f[l] outside every intervened prior group; inside an intervened group g:
+ *                   z_cf[l] = ploc_g(u'_b) + exp(pls_g(u'_b)) eps[l] -- the group's conditional prior nets on the counterfactual labels u'
+ * Both latents go through the same fixed-grid solve and decoder heads.  Over the num_samples draws, for every head value (q, c, t):
+ *   cf_mean, cf_sd    mean and POPULATION sd (divisor num_samples) of the counterfactual curve v_cf
+ *   eff_mean, eff_sd  mean and POPULATION sd of the PAIRED difference v_cf - v_f (not recoverable from the moments of two separate calls)
+ * each [Q, B, C, T] (T contiguous) in the head order of slode_recon_moments (ALD: mu_50, mu_75, mu_25; Gauss: mean); any of the four may be NULL
+ * (both effect outputs NULL: the factual arm is not run).  num_samples = 1 gives both sds = 0 exactly.  Nothing sized num_samples x B x C x T is
+ * written anywhere: one workgroup walks the draws of its trajectory through both arms and keeps two sets of shifted running moments on chip.
+ *   group_mask: bit g set = prior group g of the shape (slode_shape::groups) is intervened.  group_mask == 0 is accepted: cf = the factual
+ *   moments, the effect exactly 0.
+ *   cf_labels: batch->n_labels device pointers, a second label set in the form of batch->labels (dense [B, batch->label_width[i]] each).  Only
+ *   the columns of intervened groups are read; a tensor none of whose columns an intervened group reads may be NULL, one with such a column
+ *   may not (a group over several labels -- challenge, proc -- reads all of them: pass the unchanged ones as they are in batch->labels).
+ *   Noise: batch->eps == NULL uses ONE drawing call n of the handle's generator -- draw k of trajectory b is row k * B + b (plus
+ *   first_trajectory) of that call -- and leaves the counter at n + 1; batch->eps != NULL is a dense [num_samples, B, L] tensor.  The result is
+ *   a function of (parameters, inputs, labels, noise) alone: independent of the grid, bitwise reproducible from run to run (every value has one
+ *   owner thread, which takes the draws in the order k = 0 .. num_samples - 1; no atomics).
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Three launches ("weff", "enc_fwd2", "intervene_moments" in
+ * slode_profile_read) on one stream.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments(is_post = 1)
+ * -- a NULL handle (before anything else); num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver (dopri5, bosh3,
+ * fehlberg2, adaptive_heun); particles > 1; observation strides the folded encoder path does not take ([B,T,C] or [B,C,T] contiguous, C in
+ * {3, 4}) or SLODE_NO_FOLD; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG set in the environment of slode_create; LDS tables
+ * (step table 2 (T - 1) S, moments 6 Q C T, factual values Q C T, staged weights) beyond the budget of 160 KiB -- and: group_mask bits at or beyond
+ * n_groups; a non-zero group_mask with cf_labels NULL (or with a NULL tensor that an intervened group reads, or with batch->n_labels == 0). */
+int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, const float* const* cf_labels, unsigned int group_mask,
+                            int num_samples, float* cf_mean /* [Q,B,C,T] or NULL */, float* cf_sd /* [Q,B,C,T] or NULL */,
+                            float* eff_mean /* [Q,B,C,T] or NULL */, float* eff_sd /* [Q,B,C,T] or NULL */, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -454,11 +489,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

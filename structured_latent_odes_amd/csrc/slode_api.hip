@@ -1030,6 +1030,82 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
   return SLODE_OK;
 }
 
+// Paired-draw moments of the counterfactual curves and of their difference to the factual ones (include/slode.h): refusals first -- nothing
+// launched, no draw consumed -- then the fold + encoder launches of a forward-only step, then the one kernel that walks the draws of its
+// trajectories through both arms.
+int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, const float* const* cf_labels, unsigned int group_mask, int num_samples,
+                            float* cf_mean, float* cf_sd, float* eff_mean, float* eff_sd, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* why = check_common(h, s, lay, params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  if (!batch || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_intervene_moments: batch / times / stage_t / workspace is NULL");
+  if (num_samples < 1) return fail(h, SLODE_EINVAL, "slode_intervene_moments: num_samples = %d < 1", num_samples);
+  if ((long long)s->B * num_samples > 0x3fffffff)
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments: B x num_samples = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_samples);
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments: adaptive solver %s is not taken (fixed-grid methods only); reduce counterfactual samples instead", method_name(s->method));
+  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_intervene_moments: particles = %d is not taken (one particle only)", s->particles);
+  if (h->fold_on || h->ode_pack || h->ode_alg)
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the posterior needs observations (batch->obs is NULL)");
+  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
+                                 "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD); reduce counterfactual samples instead",
+                (long long)os[0], (long long)os[1], (long long)os[2]);
+  if (s->n_groups < 32 && (group_mask >> s->n_groups) != 0)
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x has bits at or beyond n_groups = %d", group_mask, s->n_groups);
+  if (group_mask != 0 && !cf_labels) return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x needs the counterfactual labels (cf_labels is NULL)", group_mask);
+  const size_t lds = slode_intervene_moments_lds_bytes(*s, h->ode_generic);
+  if (lds > SLODE_INTERVENE_MOMENTS_LDS_MAX)
+    return fail(h, SLODE_EINVAL, "slode_intervene_moments: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, moments, factual values, staged "
+                                 "weights) exceed the budget of %d B; reduce counterfactual samples instead", s->T, s->S, s->C, lds, SLODE_INTERVENE_MOMENTS_LDS_MAX);
+  InterveneMomentsLaunch a{};
+  LabelSrc lab{};
+  int rc = batch_labels(h, s, batch, &lab);
+  if (rc != SLODE_OK) return rc;
+  a.cf = lab;   // widths as the batch's; a counterfactual tensor that no intervened group reads may be NULL (its slot keeps the batch's pointer, unread)
+  if (group_mask != 0) {
+    if (lab.n == 0) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the counterfactual labels take the widths of batch->labels (n_labels is 0)");
+    for (int i = 0; i < lab.n; ++i) {
+      bool read = false;
+      for (int g = 0; g < s->n_groups; ++g)
+        read = read || (((group_mask >> g) & 1) && lab.off[i] < s->groups[g].u_off + s->groups[g].u_dim && lab.off[i + 1] > s->groups[g].u_off);
+      if (cf_labels[i]) a.cf.p[i] = cf_labels[i];
+      else if (read) return fail(h, SLODE_EINVAL, "slode_intervene_moments: counterfactual label tensor %d is NULL but an intervened group reads its columns", i);
+    }
+  }
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
+  a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd;
+  a.group_mask = group_mask; a.num_samples = num_samples; a.force_generic = h->ode_generic;
+  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
+  long long g = s->B;
+  if (s->B > 65536 || h->ode_loop) {
+    g = (long long)h->num_cu * 4;
+    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+    if (g > s->B) g = s->B;
+  }
+  a.grid = (int)g;
+  const uint64_t n0 = h->rng_counter;
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = lab;
+  Step p{h, *s, *lay, c};
+  rc = step_setup(p);
+  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
+  if (rc != SLODE_OK) return rc;
+  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the folded encoder path does not take these observations");
+  a.loc = p.w.loc; a.scale = p.w.scale;
+  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
+  ClockScope clock_scope(h, true);
+  FoldLaunch fl{}; bool enc_fused = false;
+  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_intervene_moments(a, c.stream));
+  return SLODE_OK;
+}
+
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {
   if (check_shape(s) || !lay) return 0;
   const int part = kind == SLODE_SVI_AUX ? lay->cstd - lay->aux_w1[0] : lay->n_params - lay->ode_begin;

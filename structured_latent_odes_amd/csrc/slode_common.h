@@ -584,6 +584,24 @@ struct TrajBoundsLaunch {
 hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
+// Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over num_samples paired posterior draws per trajectory, mean / sd
+// [Q, B, C, T] of the curve under swapped labels and of its difference to the factual curve; each of the four outputs may be NULL.  loc / scale
+// [B, L] from the encoder launch; cf: the counterfactual label tensors (read in the columns of the groups in group_mask alone).  Noise: rng.on:
+// row k * B + b of ONE drawing call; else eps [num_samples, B, L].
+struct InterveneMomentsLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *loc, *scale, *eps;
+  float *cf_mean, *cf_sd, *eff_mean, *eff_sd;
+  unsigned int group_mask;
+  int num_samples, grid, force_generic;
+  RngK rng{};
+  LabelSrc cf{};
+};
+#define SLODE_INTERVENE_MOMENTS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moments, factual values, staged weights) must fit
+hipError_t slode_launch_intervene_moments(const InterveneMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
+size_t slode_intervene_moments_lds_bytes(const slode_shape& s, int force_generic);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

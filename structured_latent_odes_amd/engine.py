@@ -538,6 +538,56 @@ class Engine:
             C.byref(batch), K, self._p(bounds), self._p(loss_kb), self._p(ws), ws.numel() * 4, self._stream()))
         return bounds, loss_kb
 
+    def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
+                          eff_mean=None, eff_sd=None, particles: int = 1):
+        """slode_intervene_moments: counterfactual curves from ``num_samples`` paired posterior draws per trajectory.  Both arms of a draw
+        share one noise row: the factual latent is the posterior draw of ``recon_moments(is_post=True)``; the counterfactual latent replaces
+        the dims of every prior group g with bit g of ``group_mask`` set by that group's conditional prior on ``cf_labels``, driven by the
+        same noise.  Returns ``(cf_mean, cf_sd, eff_mean, eff_sd)``, each float32 [Q, B, C, T] in the head order of ``recon_moments``: mean /
+        population sd of the counterfactual curve and of the paired difference counterfactual - factual (an output passed as False is not computed: None in its place); enqueued on the current
+        stream, nothing sized num_samples x B x C x T exists anywhere.  ``cf_labels``: the label tensors of ``make_batch`` once more, with the
+        counterfactual values (an entry no intervened group reads may be None, one that an intervened group reads raises ValueError; None
+        altogether with ``group_mask`` = 0).  The batch's eps is
+        [num_samples, B, L] or None (ONE drawing call: row k * B + b is draw k of trajectory b).  Raises SlodeError naming the reason for what
+        the kernel does not take (everything ``recon_moments(is_post=True)`` refuses; mask bits beyond the prior groups; a non-zero mask
+        without counterfactual labels): nothing is launched and no draw is consumed then."""
+        sp = self.spec
+        shp = (1 if sp.gauss else 3, B, sp.n_channels, self.T)
+        outs = []
+        for t, name in ((cf_mean, "cf_mean"), (cf_sd, "cf_sd"), (eff_mean, "eff_mean"), (eff_sd, "eff_sd")):
+            if t is False:                      # not wanted: NULL in the C call
+                outs.append(None)
+                continue
+            if t is None:
+                t = torch.empty(shp, dtype=torch.float32, device=self.device)
+            if tuple(self._f32(t, name).shape) != shp:
+                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
+            outs.append(t)
+        ptrs = None
+        if cf_labels is not None:
+            if len(cf_labels) != int(batch.n_labels):
+                raise ValueError("cf_labels has %d entries, the batch %d label tensors" % (len(cf_labels), int(batch.n_labels)))
+            ptrs = (C.c_void_p * L.MAX_LABELS)()
+            groups = [g for i, g in enumerate(sp.prior_groups) if (int(group_mask) >> i) & 1]
+            col = 0
+            for i, t in enumerate(cf_labels):
+                lo, col = col, col + int(batch.label_width[i])
+                if t is None:                   # an argument error of the caller, not a configuration the kernel does not take
+                    reader = [g.prefix for g in groups if lo < g.u_off + g.u_dim and col > g.u_off]
+                    if reader:
+                        raise ValueError("cf label %d is None, but the intervened prior group %s (group_mask = 0x%x) reads its label columns "
+                                         "[%d, %d): pass every label tensor of an intervened group" % (i, reader[0], int(group_mask), lo, col))
+                    continue
+                if self._f32(t, "cf label %d" % i).numel() != B * int(batch.label_width[i]):
+                    raise ValueError("cf label %d must be [%d, %d], got %s" % (i, B, int(batch.label_width[i]), tuple(t.shape)))
+                ptrs[i] = t.data_ptr()
+        ws = self.workspace(B, particles)
+        self._guard(params, ws)
+        _check(self.lib, self.handle, self.lib.slode_intervene_moments(
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
+            C.byref(batch), ptrs, int(group_mask), int(num_samples), *(self._p(t) for t in outs), self._p(ws), ws.numel() * 4, self._stream()))
+        return tuple(outs)
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

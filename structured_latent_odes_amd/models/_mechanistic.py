@@ -390,6 +390,121 @@ class MechanisticBase(nn.Module):
                 written.append(path)
         return written
 
+    # ---- counterfactual curves: the subject's own latent groups kept, the intervened groups redrawn from p(z_g | u'_g) on the same noise ----
+    def _intervened(self, intervene, labels):
+        """(group_mask, labels with the counterfactual tensors swapped in) of ``intervene`` = {label name: tensor [B, u_dim]}: bit g of the
+        mask is set when a label of prior group g (``PRIORS`` order = the engine's) is named.  A name that is no conditional-prior label of the
+        family raises ValueError."""
+        known = [l for _, ls, _ in self.PRIORS for l in ls]
+        mask, swapped = 0, dict(labels)
+        for name, val in intervene.items():
+            if name not in known:
+                raise ValueError("intervene: %r is not a conditional-prior label of the %s family (labels: %s)" % (name, self.FAMILY, ", ".join(known)))
+            if val.numel() != labels[name].numel():
+                raise ValueError("intervene[%r] must hold %d values, got %s" % (name, labels[name].numel(), tuple(val.shape)))
+            swapped[name] = val.reshape(labels[name].shape).to(labels[name].device)
+            mask |= 1 << next(g for g, (_, ls, _) in enumerate(self.PRIORS) if name in ls)
+        return mask, swapped
+
+    def counterfactual_samples(self, observations, num_samples: int, intervene, eps=None, **labels):
+        """The materialising form of ``intervention_moments``: ``{"mu_50": (factual, counterfactual), ...}`` (``{"mean": ...}`` for the Gaussian
+        family), each tensor ``[B, C, T, num_samples]``, plus ``"z"``: the two latents ``[num_samples, B, L]``.  Draw k of trajectory b uses
+        ONE noise row for both arms: z_f = loc(x) + scale(x) eps; z_cf = z_f outside the intervened prior groups and
+        ploc_g(u') + pscale_g(u') eps inside them (``_prior_loc_scale`` on the swapped labels).  Composed from the encoder, the prior nets and
+        ``decoder.forward`` on both latents; ``eps`` ``[num_samples, B, L]`` or None (one drawing call of the engine's generator)."""
+        mask, swapped = self._intervened(intervene, labels)
+        b = self._bind()
+        with torch.no_grad():
+            B, ns = observations.shape[0], int(num_samples)
+            loc, scale = self.encoder.forward(observations)
+            cloc, cscale = loc.clone(), scale.clone()
+            if mask:
+                ploc, pscale = self._prior_loc_scale(swapped)
+                for g, (_, _, zgroups) in enumerate(self.PRIORS):
+                    if (mask >> g) & 1:
+                        lo = self.z_off[zgroups[0]]
+                        hi = lo + sum(self.z_dims[z] for z in zgroups)
+                        cloc[:, lo:hi], cscale[:, lo:hi] = ploc[:, lo:hi], pscale[:, lo:hi]
+            if eps is None:
+                eps = b.engine.draw_normal(ns * B).view(ns, B, loc.shape[1])
+            e = eps.to(loc.device).reshape(ns, B, -1)
+            z_f = loc.unsqueeze(0) + scale.unsqueeze(0) * e
+            z_cf = cloc.unsqueeze(0) + cscale.unsqueeze(0) * e
+            names = ("solution_xt", "mean", "std") if self.GAUSS else ("solution_xt", "mu_75", "mu_50", "mu_25", "std")
+            arms = []
+            for z in (z_f, z_cf):
+                out = self.decoder.forward(z=z.reshape(ns * B, -1).contiguous())
+                arms.append({n: v.reshape(ns, B, v.shape[1], v.shape[2]).permute(1, 2, 3, 0).contiguous()
+                             for n, v in zip(names, out) if n not in ("solution_xt", "std")})
+            res = {n: (arms[0][n], arms[1][n]) for n in self.MOMENT_HEADS[bool(self.GAUSS)]}
+            res["z"] = (z_f, z_cf)
+            return res
+
+    def intervention_moments(self, observations, num_samples: int, intervene, eps=None, **labels):
+        """"What would THIS subject's curves have looked like under THAT input?": per head curve
+        ``{"mu_50": {"cf": (mean, sd), "effect": (mean, sd)}, ...}`` (``{"mean": ...}`` for the Gaussian family), each tensor ``[B, C, T]`` --
+        the mean and the population sd over ``num_samples`` draws of the counterfactual curve, and of the PAIRED difference counterfactual -
+        factual (both arms of a draw share their noise, so ``z_epsilon`` and the groups left alone cancel in the effect).  ``intervene`` maps
+        label names of the family's conditional priors to counterfactual tensors ``[B, u_dim]``; every prior group with a named label is
+        redrawn from p(z_g | u'_g), the other latent dims keep the subject's posterior draw.  ONE engine call (``slode_intervene_moments``):
+        no ``[B, C, T, num_samples]`` tensor exists.  ``eps`` ``[num_samples, B, L]`` makes it reproducible; None draws one call of the
+        engine's generator.  Where the engine refuses (adaptive solver, strided observations, measured arms, LDS budget) the same dict is
+        composed from ``counterfactual_samples`` in chunks over B."""
+        from .. import _lib as L
+        B, ns = observations.shape[0], int(num_samples)
+        if ns < 1:
+            raise ValueError("num_samples must be >= 1, got %d" % ns)
+        mask, swapped = self._intervened(intervene, labels)
+        b = self._bind()
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        # every label tensor goes to the engine, the named ones with their counterfactual values: a prior group over several labels
+        # (challenge, proc) reads all of its columns, whichever of them were named
+        labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+        cf = [swapped[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+        e = eps if eps is None or ns > 1 else eps.reshape(B, -1)
+        try:
+            bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=ns)
+            cm, cs, em, es = b.engine.intervene_moments(b.flat, bt, B, cf if mask else None, mask, ns)
+            return {n: {"cf": (cm[q], cs[q]), "effect": (em[q], es[q])} for q, n in enumerate(names)}
+        except L.SlodeError as err:
+            if getattr(err, "status", None) != -1:      # only a refusal (SLODE_EINVAL: nothing launched, nothing drawn) leads to the composition
+                raise
+        rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
+        if eps is None:      # ONE drawing call for the whole batch, as the engine call makes it; the chunks take their rows
+            eps = b.engine.draw_normal(ns * B).view(ns, B, -1)
+        eps = eps.reshape(ns, B, -1)
+        parts = {n: [[], [], [], []] for n in names}
+        for lo in range(0, B, rows):
+            hi = min(B, lo + rows)
+            res = self.counterfactual_samples(observations[lo:hi], ns, {k: swapped[k][lo:hi] for k in intervene}, eps=eps[:, lo:hi],
+                                              **{k: v[lo:hi] for k, v in labels.items()})
+            for n in names:
+                f, c = (v.to(torch.float32) for v in res[n])
+                d = c - f
+                for i, v in enumerate((c.mean(dim=-1), c.std(dim=-1, unbiased=False), d.mean(dim=-1), d.std(dim=-1, unbiased=False))):
+                    parts[n][i].append(v)
+            del res
+        cat = {n: [torch.cat(p, 0) for p in ps] for n, ps in parts.items()}
+        return {n: {"cf": (v[0], v[1]), "effect": (v[2], v[3])} for n, v in cat.items()}
+
+    def save_intervention_moments(self, results_dir: str, observations, num_samples: int, intervene, **labels):
+        """Writes ``<curve>_cf_<names>_sample_mean.npy`` / ``..._sample_sd.npy`` and ``<curve>_effect_<names>_sample_mean.npy`` /
+        ``..._sample_sd.npy`` (``[B, C, T]`` each) for every head curve, ``<names>`` the intervened label names joined by '+' in the order
+        given."""
+        import os
+        import numpy as np
+        res = self.intervention_moments(observations, num_samples, intervene, **labels)
+        os.makedirs(results_dir, exist_ok=True)
+        tag = "+".join(intervene)
+        written = []
+        for name, arms in res.items():
+            for arm, key in (("cf", "cf"), ("effect", "effect")):
+                for kind, val in zip(("mean", "sd"), arms[key]):
+                    path = os.path.join(results_dir, "%s_%s_%s_sample_%s.npy" % (name, arm, tag, kind))
+                    np.save(path, val.cpu().numpy())
+                    written.append(path)
+        return written
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 
