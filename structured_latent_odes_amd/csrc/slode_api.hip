@@ -845,6 +845,33 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
   return elbo_step_impl(h, s, lay, c);
 }
 
+// ---- what the four eval-side calls (eval_stats, recon_moments, traj_bounds, intervene_moments) share ----
+// one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
+static int eval_grid_for(const slode_ctx* h, int B) {
+  long long g = B;
+  if (B > 65536 || h->ode_loop) {
+    g = (long long)h->num_cu * 4;
+    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
+    if (g > B) g = B;
+  }
+  return (int)g;
+}
+// The forward-only step of a call that counts its own draws: step_setup's checks and workspace without its draw (step_setup counts one
+// draw; the caller counts its own once nothing can refuse it any more), on the folded encoder path alone ...
+static int forward_setup(Step& p, const char* who) {
+  const uint64_t n0 = p.h->rng_counter;
+  const int rc = step_setup(p);
+  p.h->rng_counter = n0;
+  if (rc != SLODE_OK) return rc;
+  if (!p.folded) return fail(p.h, SLODE_EINVAL, "%s: the folded encoder path does not take these observations", who);
+  return SLODE_OK;
+}
+// ... and its fold + encoder launches, which leave loc / scale (and the likelihood scale table) in the workspace
+static int forward_encode(Step& p) {
+  FoldLaunch fl{}; bool enc_fused = false;
+  return step_encode(p, fl, &enc_fused);
+}
+
 // The statistics row of one batch (include/slode.h): refusals first -- nothing launched, no draw consumed -- then the fold + encoder launches
 // of a forward-only step, the fused kernel and the fixed-order reduction of its partial rows.
 int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
@@ -873,28 +900,17 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
   if (rc != SLODE_OK) return rc;
   const uint64_t n0 = h->rng_counter;
   Step p{h, *s, *lay, c};
-  rc = step_setup(p);
-  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its four once nothing can refuse it any more)
-  if (rc != SLODE_OK) return rc;
-  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_eval_stats: the folded encoder path does not take these observations");
+  if ((rc = forward_setup(p, "slode_eval_stats")) != SLODE_OK) return rc;
   EvalLaunch a{};
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.sc = os[1]; a.st = os[2];
   a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.part = p.w.ode_slabs; a.out = out;
   a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic; a.lab = c.lab;
-  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
-  long long g = s->B;
-  if (s->B > 65536 || h->ode_loop) {
-    g = (long long)h->num_cu * 4;
-    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
-    if (g > s->B) g = s->B;
-  }
-  a.grid = (int)g;
+  a.grid = eval_grid_for(h, s->B);
   if ((size_t)a.grid * SLODE_EVAL_SLOTS > (size_t)p.w.ode_grid * p.w.ode_stride)
     return fail(h, SLODE_ENOSPC, "slode_eval_stats: %d partial rows do not fit the workspace's slab rows", a.grid);
   if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 4; }
   ClockScope clock_scope(h, true);
-  FoldLaunch fl{}; bool enc_fused = false;
-  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_eval(a, c.stream));
   return SLODE_OK;
 }
@@ -934,14 +950,7 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
   if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_recon_moments: the prior needs the label tensors of the conditional prior groups");
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps; a.mean = mean; a.sd = sd;
   a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
-  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
-  long long g = s->B;
-  if (s->B > 65536 || h->ode_loop) {
-    g = (long long)h->num_cu * 4;
-    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
-    if (g > s->B) g = s->B;
-  }
-  a.grid = (int)g;
+  a.grid = eval_grid_for(h, s->B);
   const uint64_t n0 = h->rng_counter;
   if (!is_post) {
     if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
@@ -955,15 +964,11 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
   c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
   c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = a.lab;
   Step p{h, *s, *lay, c};
-  rc = step_setup(p);
-  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
-  if (rc != SLODE_OK) return rc;
-  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_recon_moments: the folded encoder path does not take these observations");
+  if ((rc = forward_setup(p, "slode_recon_moments")) != SLODE_OK) return rc;
   a.loc = p.w.loc; a.scale = p.w.scale;
   if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
   ClockScope clock_scope(h, true);
-  FoldLaunch fl{}; bool enc_fused = false;
-  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_recon_moments(a, c.stream));
   return SLODE_OK;
 }
@@ -1006,26 +1011,15 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
   if (rc != SLODE_OK) return rc;
   const uint64_t n0 = h->rng_counter;
   Step p{h, *s, *lay, c};
-  rc = step_setup(p);
-  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
-  if (rc != SLODE_OK) return rc;
-  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_traj_bounds: the folded encoder path does not take these observations");
+  if ((rc = forward_setup(p, "slode_traj_bounds")) != SLODE_OK) return rc;
   TrajBoundsLaunch a{};
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.t_major = p.t_major ? 1 : 0;
   a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.bounds = bounds; a.loss_kb = loss_kb;
   a.num_draws = num_draws; a.force_generic = h->ode_generic; a.lab = c.lab;
-  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
-  long long g = s->B;
-  if (s->B > 65536 || h->ode_loop) {
-    g = (long long)h->num_cu * 4;
-    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
-    if (g > s->B) g = s->B;
-  }
-  a.grid = (int)g;
+  a.grid = eval_grid_for(h, s->B);
   if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + (uint64_t)num_draws; }
   ClockScope clock_scope(h, true);
-  FoldLaunch fl{}; bool enc_fused = false;
-  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_traj_bounds(a, c.stream));
   return SLODE_OK;
 }
@@ -1079,29 +1073,18 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
   a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd;
   a.group_mask = group_mask; a.num_samples = num_samples; a.force_generic = h->ode_generic;
-  // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
-  long long g = s->B;
-  if (s->B > 65536 || h->ode_loop) {
-    g = (long long)h->num_cu * 4;
-    if (h->ode_grid_cap > 0 && g > h->ode_grid_cap) g = h->ode_grid_cap;
-    if (g > s->B) g = s->B;
-  }
-  a.grid = (int)g;
+  a.grid = eval_grid_for(h, s->B);
   const uint64_t n0 = h->rng_counter;
   StepCall c;
   c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
   c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
   c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = lab;
   Step p{h, *s, *lay, c};
-  rc = step_setup(p);
-  h->rng_counter = n0;   // (step_setup counts one draw; this call counts its own once nothing can refuse it any more)
-  if (rc != SLODE_OK) return rc;
-  if (!p.folded) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the folded encoder path does not take these observations");
+  if ((rc = forward_setup(p, "slode_intervene_moments")) != SLODE_OK) return rc;
   a.loc = p.w.loc; a.scale = p.w.scale;
   if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
   ClockScope clock_scope(h, true);
-  FoldLaunch fl{}; bool enc_fused = false;
-  if ((rc = step_encode(p, fl, &enc_fused)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_intervene_moments(a, c.stream));
   return SLODE_OK;
 }

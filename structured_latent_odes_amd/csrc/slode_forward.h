@@ -1,0 +1,318 @@
+// The fixed-grid forward pass the four eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
+// intervene_moments_kernel.hip; no other translation unit includes this header): each phase ONCE --
+//   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads)
+//                      and the host functions that fill them from slode_shape / slode_layout
+//   prior nets         fwd_prior_at: loc / log scale of one latent dim from the staged labels
+//   step coefficients  fwd_step_coeffs: x' = A x + b of one grid step for euler / midpoint / rk4, the a, d evaluator passed in;
+//                      fwd_step_table: thread <-> step, the table of a whole solve
+//   scan               fwd_scan: forward affine scan, one state component per wave pass
+//   label heads        fwd_label_logits: hidden layer and logits of one head on a half-wave
+//   staged weights     (recon, bounds, intervene) FWD_ROW, FwdLds / FwdSm, fwd_stage_weights, fwd_init_state, fwd_ad: the weights every
+//                      draw reuses live in the LDS; the a, d evaluator reads one 16-byte-aligned row per hidden unit
+//   launch             fwd_generic, fwd_dispatch over the compile-time state dim {5, 8, 0}, fwd_launch
+// Every routine keeps the operation order of the kernels it came from: results are bitwise those of the separate copies.
+#pragma once
+#include <type_traits>
+#include "slode_common.h"
+
+namespace {   // (internal linkage: every including translation unit has its own copy, as before)
+
+constexpr int FWD_NT = 256;   // threads of a workgroup: four waves
+constexpr float FWD_HL2PI = 0.91893853320467274178f;
+#define FWD_ROW(SM) ((2 + 2 * (SM) + 3) & ~3)   // floats of one hidden unit's LDS row: w_t | u_j | W_g[0..SM) | W_d[0..SM)
+
+// ---- kernel-argument parts ----------------------------------------------------------------------------------
+struct FwdK {
+  int B, T, C, L, S, H, R, method, Q;
+  int init_w1, init_b1, init_w2, init_b2, dyn_wh, dyn_bh, dyn_wg, dyn_bg, dyn_wd, dyn_bd, head[SLODE_MAX_HEADS];
+  const float *params, *times, *stage_t;
+};
+struct PriorK {
+  int nu, n_groups;
+  slode_group grp[SLODE_MAX_GROUPS];
+  int ploc_w[SLODE_MAX_GROUPS], ploc_b[SLODE_MAX_GROUPS], pls_w[SLODE_MAX_GROUPS], pls_b[SLODE_MAX_GROUPS];
+};
+struct LabelHeadK {
+  int n_aux, U;
+  float aux_mult;
+  slode_aux aux[SLODE_MAX_AUX];
+  int aux_w1[SLODE_MAX_AUX], aux_b1[SLODE_MAX_AUX], aux_w2[SLODE_MAX_AUX], aux_b2[SLODE_MAX_AUX], aux_c[SLODE_MAX_AUX];
+};
+
+inline void fwd_fill(FwdK& k, const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const float* stage_t) {
+  k.B = s.B; k.T = s.T; k.C = s.C; k.L = s.L; k.S = s.S; k.H = s.H;
+  k.method = s.method; k.R = s.method == SLODE_EULER ? 1 : (s.method == SLODE_MIDPOINT ? 2 : 3);
+  k.Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+  k.init_w1 = lay.init_w1; k.init_b1 = lay.init_b1; k.init_w2 = lay.init_w2; k.init_b2 = lay.init_b2;
+  k.dyn_wh = lay.dyn_wh; k.dyn_bh = lay.dyn_bh; k.dyn_wg = lay.dyn_wg; k.dyn_bg = lay.dyn_bg; k.dyn_wd = lay.dyn_wd; k.dyn_bd = lay.dyn_bd;
+  for (int q = 0; q < SLODE_MAX_HEADS; ++q) k.head[q] = lay.head_w[q];
+  k.params = params; k.times = times; k.stage_t = stage_t;
+}
+inline void fwd_fill(PriorK& k, const slode_shape& s, const slode_layout& lay) {
+  k.nu = s.n_u; k.n_groups = s.n_groups;
+  for (int g = 0; g < SLODE_MAX_GROUPS; ++g) {
+    k.grp[g] = s.groups[g]; k.ploc_w[g] = lay.ploc_w[g]; k.ploc_b[g] = lay.ploc_b[g]; k.pls_w[g] = lay.pls_w[g]; k.pls_b[g] = lay.pls_b[g];
+  }
+}
+inline void fwd_fill(LabelHeadK& k, const slode_shape& s, const slode_layout& lay) {
+  k.n_aux = s.n_aux; k.U = s.U; k.aux_mult = s.aux_mult;
+  for (int q = 0; q < SLODE_MAX_AUX; ++q) {
+    k.aux[q] = s.aux[q]; k.aux_w1[q] = lay.aux_w1[q]; k.aux_b1[q] = lay.aux_b1[q]; k.aux_w2[q] = lay.aux_w2[q]; k.aux_b2[q] = lay.aux_b2[q];
+    k.aux_c[q] = lay.aux_c[q];
+  }
+}
+
+// ---- conditional prior nets -----------------------------------------------------------------------------------
+// loc pl and log scale pls of latent dim l under its group's prior nets on the staged labels s_u; false (pl = pls = 0) when l lies in no
+// group whose bit is set in mask (intervene: the intervened groups; everyone else: all)
+__device__ __forceinline__ bool fwd_prior_at(const PriorK& k, const float* __restrict__ par, const float* s_u, int l, float& pl, float& pls,
+                                             int mask = -1) {
+  bool found = false;
+  pl = 0.f; pls = 0.f;
+  for (int g = 0; g < k.n_groups; ++g) {
+    const slode_group gr = k.grp[g];
+    if (((mask >> g) & 1) && l >= gr.z_off && l < gr.z_off + gr.z_dim) {
+      const int ll = l - gr.z_off;
+      pl = par[k.ploc_b[g] + ll]; pls = par[k.pls_b[g] + ll];
+      for (int q = 0; q < gr.u_dim; ++q) {
+        const float uv = s_u[gr.u_off + q];
+        pl = fmaf(par[k.ploc_w[g] + ll * gr.u_dim + q], uv, pl);
+        pls = fmaf(par[k.pls_w[g] + ll * gr.u_dim + q], uv, pls);
+      }
+      found = true;
+    }
+  }
+  return found;
+}
+
+// ---- step coefficients ------------------------------------------------------------------------------------------
+// x' = A x + b of one grid step of size h (f = a(t, z) - d(t, z) x: tests/kernel_math.py step_coeffs); st: the step's stage times;
+// ad(t, a, d): the caller's evaluator of a(t, z), d(t, z) -- eval_stats reads the weights from global memory, the others from the LDS rows
+template <int SM, class AD>
+__device__ __forceinline__ void fwd_step_coeffs(int method, float h, const float* st, const AD& ad, float (&A)[SM], float (&bb)[SM]) {
+  float a[SM], d[SM];
+  ad(st[0], a, d);
+  if (method == SLODE_EULER) {
+#pragma unroll
+    for (int s = 0; s < SM; ++s) { A[s] = 1.f - h * d[s]; bb[s] = h * a[s]; }
+  } else if (method == SLODE_MIDPOINT) {
+    float m[SM], c[SM];
+#pragma unroll
+    for (int s = 0; s < SM; ++s) { m[s] = 1.f - 0.5f * h * d[s]; c[s] = 0.5f * h * a[s]; }
+    ad(st[1], a, d);
+#pragma unroll
+    for (int s = 0; s < SM; ++s) { A[s] = 1.f - h * d[s] * m[s]; bb[s] = h * (a[s] - d[s] * c[s]); }
+  } else {   // torchdiffeq's rk4: the 3/8 rule
+    const float third = 1.0f / 3.0f, h3 = h * third;
+    float p1[SM], q1[SM], p2[SM], q2[SM], c[SM], m[SM];
+#pragma unroll
+    for (int s = 0; s < SM; ++s) { p1[s] = a[s]; q1[s] = -d[s]; c[s] = h3 * p1[s]; m[s] = 1.f + h3 * q1[s]; }
+    ad(st[1], a, d);
+#pragma unroll
+    for (int s = 0; s < SM; ++s) {
+      p2[s] = a[s] - d[s] * c[s]; q2[s] = -d[s] * m[s];
+      c[s] = h * (p2[s] - p1[s] * third); m[s] = 1.f + h * (q2[s] - q1[s] * third);
+    }
+    ad(st[2], a, d);
+#pragma unroll
+    for (int s = 0; s < SM; ++s) {
+      const float p3 = a[s] - d[s] * c[s], q3 = -d[s] * m[s];
+      c[s] = h * (p1[s] - p2[s] + p3); m[s] = 1.f + h * (q1[s] - q2[s] + q3);
+      A[s] = q1[s] + 3.f * (q2[s] + q3); bb[s] = p1[s] + 3.f * (p2[s] + p3);   // (partial sums: q4 / p4 follow)
+    }
+    ad(st[3], a, d);
+    const float G = h * 0.125f;
+#pragma unroll
+    for (int s = 0; s < SM; ++s) {
+      const float p4 = a[s] - d[s] * c[s], q4 = -d[s] * m[s];
+      A[s] = 1.f + G * (A[s] + q4); bb[s] = G * (bb[s] + p4);
+    }
+  }
+}
+
+// the step table of one solve, thread <-> step: steps n_first, n_first + n_stride, ... into pa[n][s] / pb[n][s]
+template <int SM, class AD>
+__device__ __forceinline__ void fwd_step_table(const FwdK& k, int S, int n_first, int n_stride, float* pa, float* pb, const AD& ad) {
+  const int NS = k.T - 1;
+  for (int n = n_first; n < NS; n += n_stride) {
+    float A[SM], bb[SM];
+    fwd_step_coeffs<SM>(k.method, k.times[n + 1] - k.times[n], k.stage_t + n * k.R, ad, A, bb);
+#pragma unroll
+    for (int s = 0; s < SM; ++s)
+      if (s < S) { pa[n * S + s] = A[s]; pb[n * S + s] = bb[s]; }
+  }
+}
+
+// ---- forward affine scan ---------------------------------------------------------------------------------------
+// In place: x[n + 1][s] takes the slot of A[n][s] (pa, pb: [NS][S]; x0: [S]).  One state component per wave pass -- s_first, s_first +
+// s_stride, ... -- a chunk of steps per lane, Kogge-Stone over the lanes' maps.  Call with whole waves.
+__device__ __forceinline__ void fwd_scan(float* pa, const float* pb, const float* x0, int S, int NS, int lane, int s_first, int s_stride) {
+  const int chunk = (NS + 63) / 64, n0 = min(lane * chunk, NS), n1 = min(n0 + chunk, NS);
+  for (int s = s_first; s < S; s += s_stride) {
+    float* a = pa + s;
+    const float* b = pb + s;
+    float Ac = 1.f, bc = 0.f;   // the lane's chunk as one map
+    for (int n = n0; n < n1; ++n) { const float An = a[n * S]; bc = fmaf(An, bc, b[n * S]); Ac *= An; }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {   // inclusive scan of the maps over the lanes (later map o earlier map)
+      const float Ap = __shfl_up(Ac, off, 64), bp = __shfl_up(bc, off, 64);
+      if (lane >= off) { bc = fmaf(Ac, bp, bc); Ac *= Ap; }
+    }
+    float Ae = __shfl_up(Ac, 1, 64), be = __shfl_up(bc, 1, 64);
+    if (lane == 0) { Ae = 1.f; be = 0.f; }
+    float x = fmaf(Ae, x0[s], be);
+    for (int n = n0; n < n1; ++n) { x = fmaf(a[n * S], x, b[n * S]); a[n * S] = x; }
+  }
+}
+
+// ---- label heads ------------------------------------------------------------------------------------------------
+// logits lg[0 .. u_dim) of label head a on the latents zz (the head's own dims), half-wave = head, lane j32 = hidden unit.  Every lane of the
+// wave takes part in every sum (columns beyond u_dim add zeros): call from wave-uniform control flow.
+// (The per-kind log-probability stays with the callers: eval_stats forms its hit test inside the same loops, from the same exponentials.)
+__device__ __forceinline__ void fwd_label_logits(const LabelHeadK& k, const float* __restrict__ par, int a, const float* zz, int j32, float (&lg)[8]) {
+  const int zd = k.aux[a].z_dim, ud = k.aux[a].u_dim, U = k.U;
+  const bool unit_on = j32 < U;
+  const int jj = min(j32, U - 1);
+  float pre = par[k.aux_b1[a] + jj];
+  for (int l = 0; l < zd; ++l) pre = fmaf(par[k.aux_w1[a] + jj * zd + l], zz[l], pre);
+  const float hv = unit_on ? softplusf(pre) : 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const float w = (q < ud) ? par[k.aux_w2[a] + min(q, ud - 1) * U + jj] : 0.f;
+    lg[q] = half_wave_sum(w * hv) + par[k.aux_b2[a] + min(q, ud - 1)];
+  }
+}
+
+// ---- staged weights (recon, bounds, intervene) ----------------------------------------------------------------------
+// offsets (in floats, multiples of 4) of the shared pieces of the dynamic LDS region; each kernel's own pieces follow them
+struct FwdLds { int a, b, row, w1, b1, w2, hw, bgd, z, u, h0, x0; };
+struct LdsCarve {
+  int n = 0;
+  int take(int c) { const int at = n; n += (c + 3) & ~3; return at; }
+};
+// generic: the run-time-S instantiation (rows sized for SLODE_MAX_S)
+inline FwdLds fwd_lds(LdsCarve& cv, const slode_shape& s, bool generic) {
+  const int Q = s.likelihood == SLODE_GAUSS ? 1 : 3, RW = FWD_ROW(generic ? SLODE_MAX_S : s.S);
+  FwdLds o{};
+  o.a = cv.take((s.T - 1) * s.S); o.b = cv.take((s.T - 1) * s.S); o.row = cv.take(s.H * RW);
+  o.w1 = cv.take(s.L * 2 * s.H); o.b1 = cv.take(2 * s.H); o.w2 = cv.take(s.H * s.S + s.S); o.hw = cv.take(Q * s.C * s.S); o.bgd = cv.take(2 * s.S);
+  o.z = cv.take(s.L); o.u = cv.take(s.n_u > 0 ? s.n_u : 1); o.h0 = cv.take(s.H); o.x0 = cv.take(s.S);
+  return o;
+}
+
+struct FwdSm {
+  float* A;     // A[T-1][S], overwritten by x[n+1][.] in the scan
+  float* B;     // b[T-1][S]
+  float* row;   // [H][RW]: w_t | u_j (per solve) | W_g[0..S)[j] | W_d[0..S)[j]
+  float* w1;    // [L][2H]: z-columns of the hidden layer (r < H) and the init net's first layer (r >= H), transposed
+  float* b1;    // [2H]
+  float* w2;    // [H][S] init net's output layer, transposed | [S] its bias
+  float* hw;    // [Q*C][S] head weights
+  float* bgd;   // [2S] growth | degradation bias
+  float *z, *u, *h0, *x0;
+};
+__device__ __forceinline__ FwdSm fwd_sm(float* base, const FwdLds& o) {
+  return FwdSm{base + o.a, base + o.b, base + o.row, base + o.w1, base + o.b1, base + o.w2, base + o.hw, base + o.bgd,
+               base + o.z, base + o.u, base + o.h0, base + o.x0};
+}
+
+// once per workgroup: the weights every solve reuses, into the LDS (a barrier must follow before they are read)
+template <int SM>
+__device__ __forceinline__ void fwd_stage_weights(const FwdK& k, const FwdSm& m, int S, int tid) {
+  constexpr int RW = FWD_ROW(SM);
+  const float* __restrict__ par = k.params;
+  const int L = k.L, H = k.H, C = k.C, QC = k.Q * k.C;
+  for (int i = tid; i < H * RW; i += FWD_NT) {
+    const int j = i / RW, c = i - j * RW;
+    float v = 0.f;
+    if (c == 0) v = par[k.dyn_wh + j * (1 + L)];
+    else if (c >= 2 && c < 2 + S) v = par[k.dyn_wg + (c - 2) * H + j];
+    else if (c >= 2 + SM && c < 2 + SM + S) v = par[k.dyn_wd + (c - 2 - SM) * H + j];
+    m.row[i] = v;
+  }
+  for (int i = tid; i < L * 2 * H; i += FWD_NT) {
+    const int l = i / (2 * H), r = i - l * 2 * H;
+    m.w1[i] = r < H ? par[k.dyn_wh + r * (1 + L) + 1 + l] : par[k.init_w1 + (r - H) * L + l];
+  }
+  for (int i = tid; i < 2 * H; i += FWD_NT) m.b1[i] = i < H ? par[k.dyn_bh + i] : par[k.init_b1 + i - H];
+  for (int i = tid; i < H * S + S; i += FWD_NT) {
+    const int j = i / S, s = i - j * S;
+    m.w2[i] = i < H * S ? par[k.init_w2 + s * H + j] : par[k.init_b2 + i - H * S];
+  }
+  for (int i = tid; i < QC * S; i += FWD_NT) {
+    const int qc = i / S, q = qc / C;
+    m.hw[i] = par[k.head[q] + (qc - q * C) * S + (i - qc * S)];
+  }
+  for (int i = tid; i < 2 * S; i += FWD_NT) m.bgd[i] = i < S ? par[k.dyn_bg + i] : par[k.dyn_bd + i - S];
+}
+
+// per solve, from z in m.z: u = W_z z + b_h into the units' rows and the init net's hidden layer; then x0.  Contains the barrier between
+// the hidden layer and x0: call from workgroup-uniform control flow only.  (x0 and the rows are visible after the caller's next barrier.)
+template <int SM>
+__device__ __forceinline__ void fwd_init_state(const FwdSm& m, int H, int L, int S, int tid) {
+  constexpr int RW = FWD_ROW(SM);
+  if (tid < 2 * H) {
+    float v = m.b1[tid];
+    for (int l = 0; l < L; ++l) v = fmaf(m.w1[l * 2 * H + tid], m.z[l], v);
+    if (tid < H) m.row[tid * RW + 1] = v;
+    else m.h0[tid - H] = fmaxf(v, 0.f);
+  }
+  __syncthreads();
+  if (tid < S) {
+    float o = m.w2[H * S + tid];
+    for (int j = 0; j < H; ++j) o = fmaf(m.w2[j * S + tid], m.h0[j], o);
+    m.x0[tid] = sigmoidf_fast(o);
+  }
+}
+
+// a(t, z), d(t, z) of one stage time from the LDS rows [w_t | u_j | W_g[.][j] | W_d[.][j]] (every lane reads the same address: broadcast)
+// (rows are RW = 2 + 2 SM floats rounded up to a multiple of four, 16-byte aligned: read as 16-byte LDS loads)
+template <int SM>
+__device__ __forceinline__ void fwd_ad(const float* __restrict__ s_row, const float* __restrict__ s_bgd, int H, float t, int S,
+                                       float (&a)[SM], float (&d)[SM]) {
+  typedef float f4_t __attribute__((ext_vector_type(4)));
+  constexpr int RW = FWD_ROW(SM);
+#pragma unroll
+  for (int s = 0; s < SM; ++s) { a[s] = s < S ? s_bgd[s] : 0.f; d[s] = s < S ? s_bgd[S + s] : 0.f; }
+  for (int j = 0; j < H; ++j) {
+    float r[RW];
+#pragma unroll
+    for (int i = 0; i < RW / 4; ++i) {
+      const f4_t v = reinterpret_cast<const f4_t*>(s_row + j * RW)[i];
+      r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+    }
+    const float hj = fmaxf(fmaf(r[0], t, r[1]), 0.f);
+#pragma unroll
+    for (int s = 0; s < SM; ++s)
+      if (s < S) { a[s] = fmaf(r[2 + s], hj, a[s]); d[s] = fmaf(r[2 + SM + s], hj, d[s]); }
+  }
+#pragma unroll
+  for (int s = 0; s < SM; ++s) { a[s] = sigmoidf_fast(a[s]); d[s] = sigmoidf_fast(d[s]); }
+}
+
+// the staged form of the step table and the scan: one solve on all four waves
+template <int SM>
+__device__ __forceinline__ void fwd_step_table_staged(const FwdK& k, const FwdSm& m, int S, int tid) {
+  const float* s_row = m.row; const float* s_bgd = m.bgd;
+  const int H = k.H;
+  fwd_step_table<SM>(k, S, tid, FWD_NT, m.A, m.B, [&](float t, float (&a)[SM], float (&d)[SM]) { fwd_ad<SM>(s_row, s_bgd, H, t, S, a, d); });
+}
+
+// ---- launch ---------------------------------------------------------------------------------------------------------
+// the run-time-S instantiation serves every state dim without a compiled one, and every shape under SLODE_ODE_GENERIC
+inline bool fwd_generic(const slode_shape& s, int force_generic) { return force_generic || !(s.S == 5 || s.S == 8); }
+
+// go(std::integral_constant<int, SC>) with SC the compile-time state dim of the shape: 5 (cvs / challenge), 8 (proc), 0 (run time)
+template <class F>
+inline void fwd_dispatch(const slode_shape& s, int force_generic, F&& go) {
+  if (fwd_generic(s, force_generic)) go(std::integral_constant<int, 0>{});
+  else if (s.S == 5) go(std::integral_constant<int, 5>{});
+  else go(std::integral_constant<int, 8>{});
+}
+template <class K>
+inline void fwd_launch(const char* name, void (*fn)(K), int grid, size_t lds, hipStream_t stream, const K& k) {
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  SLODE_LAUNCH(name, fn, dim3(grid), dim3(FWD_NT), lds, stream, k);
+}
+
+}  // namespace

@@ -208,3 +208,35 @@ def test_batch_keeps_its_converted_label_tensors_alive(monkeypatch):
     del bt
     gc.collect()
     assert [r() for r in made] == [None, None]
+
+
+def test_eval_side_lds_byte_totals_are_pinned():
+    """The dynamic LDS regions of the four eval-side kernels, through the library's own functions (host arithmetic, no device needed),
+    at the shapes DESIGN 3.6-3.9 quote: metric cvs T = 200, challenge-Gauss T = 300, proc T = 100; K = 64 draws for the bounds; the
+    shape-specialised and the forced run-time-S form (proc's S = 8 rows are already SLODE_MAX_S wide).  The kernels share their forward
+    pieces (csrc/slode_forward.h): a change there that moves any of these totals moves occupancy and the refusal thresholds."""
+    from structured_latent_odes_amd import _lib as L, engine as E
+    lib = L.load()
+
+    class _E(E.Engine):
+        def __init__(self, spec, T):
+            self.spec, self.T, self._shapes = spec, T, {}
+
+    def fn(mangled):
+        f = getattr(lib, mangled)
+        f.restype = C.c_size_t
+        return f
+
+    ev = fn("_Z20slode_eval_lds_bytesRK11slode_shape")
+    rm = fn("_Z29slode_recon_moments_lds_bytesRK11slode_shapei")
+    tb = fn("_Z27slode_traj_bounds_lds_bytesRK11slode_shapeii")
+    iv = fn("_Z33slode_intervene_moments_lds_bytesRK11slode_shapei")
+    # shape -> eval, then (recon, bounds at K = 64, intervene) specialised and forced generic
+    want = {"cvs": (15920, (33600, 19792, 62464), (34400, 20592, 63264)),
+            "challenge": (23920, (31792, 32320, 51120), (32592, 33120, 51920)),
+            "proc": (12672, (35040, 25680, 54656), (35040, 25680, 54656))}
+    for name, spec, T in (("cvs", E.cvs_spec(3, 3, 2, solver="rk4"), 200), ("challenge", E.challenge_spec(gauss=True, solver="rk4"), 300),
+                          ("proc", E.proc_spec(z_g=10, z_eps=10, solver="rk4"), 100)):
+        s = _E(spec, T).shape(1024)
+        got = (ev(C.byref(s)),) + tuple((rm(C.byref(s), g), tb(C.byref(s), 64, g), iv(C.byref(s), g)) for g in (0, 1))
+        assert got == want[name], (name, got, want[name])
