@@ -856,8 +856,67 @@ static int eval_grid_for(const slode_ctx* h, int B) {
   }
   return (int)g;
 }
-// The forward-only step of a call that counts its own draws: step_setup's checks and workspace without its draw (step_setup counts one
-// draw; the caller counts its own once nothing can refuse it any more), on the folded encoder path alone ...
+// One of the four calls as data: its name and the per-call pieces of the refusal texts they share.  A nullptr text: the
+// call does not make that check.
+struct EvalCall {
+  const char* name;                      // "slode_traj_bounds"
+  const char* pointers; bool missing;    // the pointers the call cannot do without, as its message lists them; whether one of them is NULL
+  const char* draws_noun; int draws;     // "num_samples" / "num_draws" and its value (nullptr: eval_stats, whose four draws are fixed)
+  const char* adaptive_tail;             // after "... (fixed-grid methods only)" of the adaptive solvers' refusal
+  const char* one_particle;              // after "... particles = %d is not taken "
+  const char* obs_null;                  // the refusal of batch->obs == NULL (nullptr: the prior; eval_stats, where step_setup finds it)
+  const char* strides_tail;              // after "... observations with C in {3, 4}" (nullptr: the prior, which reads no observations)
+  const char* lds_tables = nullptr;      // what the LDS figure counts, and the advice that ends that refusal (eval_lds)
+  const char* lds_advice = nullptr;
+  bool lds_per_draw = false;             // the LDS figure grows with the draw count: the refusal names it
+};
+// The shared refusal ladder, in this order.  First: handle, shape, layout, params; the call's own pointers ...
+static int eval_args(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const EvalCall& d) {
+  const char* why = check_common(h, s, lay, params);
+  if (why) return fail(h, SLODE_EINVAL, "%s", why);
+  if (d.missing) return fail(h, SLODE_EINVAL, "%s: %s is NULL", d.name, d.pointers);
+  return SLODE_OK;
+}
+// ... then the draw count; what the fused kernels do not take (adaptive solvers, particles, the measured arms); the observations
+static int eval_refuse(slode_handle h, const slode_shape* s, const slode_batch* batch, const EvalCall& d) {
+  if (d.draws_noun && d.draws < 1) return fail(h, SLODE_EINVAL, "%s: %s = %d < 1", d.name, d.draws_noun, d.draws);
+  if (d.draws_noun && (long long)s->B * d.draws > 0x3fffffff)
+    return fail(h, SLODE_EINVAL, "%s: B x %s = %lld exceeds 2^30 - 1 noise rows", d.name, d.draws_noun, (long long)s->B * d.draws);
+  if (is_adaptive(s->method))
+    return fail(h, SLODE_EINVAL, "%s: adaptive solver %s is not taken (fixed-grid methods only)%s", d.name, method_name(s->method), d.adaptive_tail);
+  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "%s: particles = %d is not taken %s", d.name, s->particles, d.one_particle);
+  if (h->fold_on || h->ode_pack || h->ode_alg)
+    return fail(h, SLODE_EINVAL, "%s cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG", d.name);
+  if (d.obs_null && !batch->obs) return fail(h, SLODE_EINVAL, "%s: %s", d.name, d.obs_null);
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (d.strides_tail && (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4)))
+    return fail(h, SLODE_EINVAL, "%s: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
+                                 "[B,T,C] or [B,C,T] observations with C in {3, 4}%s",
+                d.name, (long long)os[0], (long long)os[1], (long long)os[2], d.strides_tail);
+  return SLODE_OK;
+}
+// ... then the LDS budget of a kernel that walks the draws of its trajectories (slode_*_lds_bytes against SLODE_*_LDS_MAX); the label
+// tensors (batch_labels) follow it, and step_setup's checks and workspace (forward_setup) come last
+static int eval_lds(slode_handle h, const slode_shape* s, const EvalCall& d, size_t lds, int budget) {
+  if (lds <= (size_t)budget) return SLODE_OK;
+  char per_draw[48] = "";
+  if (d.lds_per_draw) snprintf(per_draw, sizeof(per_draw), ", %s = %d", d.draws_noun, d.draws);
+  return fail(h, SLODE_EINVAL, "%s: the LDS tables of T = %d, S = %d, C = %d%s (%zu B: %s) exceed the budget of %d B; %s", d.name, s->T, s->S,
+              s->C, per_draw, lds, d.lds_tables, budget, d.lds_advice);
+}
+
+// The shared tail.  The forward-only step on the batch (labels: batch_labels; loss_out == NULL: a set-up that writes no loss) ...
+static StepCall forward_call(const float* params, const float* times, const float* stage_t, const slode_batch* batch, const LabelSrc& lab,
+                             float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
+  StepCall c;
+  c.params = params; c.times = times; c.stage_t = stage_t; c.loss_out = loss_out; c.no_loss = loss_out ? 0 : 1;
+  c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = lab;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+  return c;
+}
+// ... step_setup's checks and workspace without its draw (step_setup counts one draw; the call counts its own once nothing can refuse it
+// any more), on the folded encoder path alone ...
 static int forward_setup(Step& p, const char* who) {
   const uint64_t n0 = p.h->rng_counter;
   const int rc = step_setup(p);
@@ -866,8 +925,17 @@ static int forward_setup(Step& p, const char* who) {
   if (!p.folded) return fail(p.h, SLODE_EINVAL, "%s: the folded encoder path does not take these observations", who);
   return SLODE_OK;
 }
-// ... and its fold + encoder launches, which leave loc / scale (and the likelihood scale table) in the workspace
-static int forward_encode(Step& p) {
+// the drawing calls of a call that takes `draws` of them (the batch carries no eps), counted once nothing can refuse the call any more
+static RngK take_draws(slode_handle h, const float* eps, int draws) {
+  if (eps) return RngK{};
+  const RngK r = rng_of(h, h->rng_counter);
+  h->rng_counter += (uint64_t)draws;
+  return r;
+}
+// ... and, inside the caller's ClockScope, the call's draws counted and the fold + encoder launches, which leave loc / scale (and the
+// likelihood scale table) in the workspace for the call's own kernel
+static int forward_encode(Step& p, int draws, RngK* rng) {
+  *rng = take_draws(p.h, p.c.eps, draws);
   FoldLaunch fl{}; bool enc_fused = false;
   return step_encode(p, fl, &enc_fused);
 }
@@ -877,40 +945,26 @@ static int forward_encode(Step& p) {
 int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                      const float* stage_t, const slode_batch* batch, int is_post, float* out, void* workspace, size_t workspace_bytes,
                      void* stream) {
-  const char* why = check_common(h, s, lay, params);
-  if (why) return fail(h, SLODE_EINVAL, "%s", why);
-  if (!batch || !out) return fail(h, SLODE_EINVAL, "slode_eval_stats: batch / out is NULL");
-  if (is_adaptive(s->method))
-    return fail(h, SLODE_EINVAL, "slode_eval_stats: adaptive solver %s is not taken (fixed-grid methods only); run the unfused calls", method_name(s->method));
-  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_eval_stats: particles = %d is not taken (one particle only); run the unfused calls", s->particles);
-  if (h->fold_on || h->ode_pack || h->ode_alg)
-    return fail(h, SLODE_EINVAL, "slode_eval_stats cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
-  const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
-    return fail(h, SLODE_EINVAL, "slode_eval_stats: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
-                                 "[B,T,C] or [B,C,T] observations with C in {3, 4}; run the unfused calls",
-                (long long)os[0], (long long)os[1], (long long)os[2]);
+  const EvalCall d{"slode_eval_stats", "batch / out", !batch || !out, nullptr, 0, "; run the unfused calls",
+                   "(one particle only); run the unfused calls", nullptr, "; run the unfused calls"};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (slode_eval_lds_bytes(*s) + 4096 > 160 * 1024)
     return fail(h, SLODE_EINVAL, "slode_eval_stats: T x S = %d x %d does not fit the step table into the LDS; run the unfused calls", s->T, s->S);
-  StepCall c;
-  c.params = params; c.times = times; c.stage_t = stage_t; c.loss_out = out;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
-  int rc = batch_call(h, s, SLODE_SVI_MAIN, batch, &c);
-  if (rc != SLODE_OK) return rc;
-  const uint64_t n0 = h->rng_counter;
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, "slode_eval_stats")) != SLODE_OK) return rc;
   EvalLaunch a{};
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, out, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  const int64_t* os = batch->obs_strides;
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.sc = os[1]; a.st = os[2];
   a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.part = p.w.ode_slabs; a.out = out;
-  a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic; a.lab = c.lab;
+  a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
   a.grid = eval_grid_for(h, s->B);
   if ((size_t)a.grid * SLODE_EVAL_SLOTS > (size_t)p.w.ode_grid * p.w.ode_stride)
     return fail(h, SLODE_ENOSPC, "slode_eval_stats: %d partial rows do not fit the workspace's slab rows", a.grid);
-  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 4; }
   ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p, 4, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_eval(a, c.stream));
   return SLODE_OK;
 }
@@ -920,55 +974,33 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
 int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                         const float* stage_t, const slode_batch* batch, int is_post, int num_samples, float* mean, float* sd, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  const char* why = check_common(h, s, lay, params);
-  if (why) return fail(h, SLODE_EINVAL, "%s", why);
-  if (!batch || !mean || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_recon_moments: batch / mean / times / stage_t / workspace is NULL");
-  if (num_samples < 1) return fail(h, SLODE_EINVAL, "slode_recon_moments: num_samples = %d < 1", num_samples);
-  if ((long long)s->B * num_samples > 0x3fffffff)
-    return fail(h, SLODE_EINVAL, "slode_recon_moments: B x num_samples = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_samples);
-  if (is_adaptive(s->method))
-    return fail(h, SLODE_EINVAL, "slode_recon_moments: adaptive solver %s is not taken (fixed-grid methods only); reduce recon_samples instead", method_name(s->method));
-  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_recon_moments: particles = %d is not taken (one particle only)", s->particles);
-  if (h->fold_on || h->ode_pack || h->ode_alg)
-    return fail(h, SLODE_EINVAL, "slode_recon_moments cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
-  const int64_t* os = batch->obs_strides;
-  if (is_post) {
-    const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-    if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_recon_moments: the posterior needs observations (batch->obs is NULL)");
-    if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
-      return fail(h, SLODE_EINVAL, "slode_recon_moments: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
-                                   "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD); reduce recon_samples instead",
-                  (long long)os[0], (long long)os[1], (long long)os[2]);
-  }
-  const size_t lds = slode_recon_moments_lds_bytes(*s, h->ode_generic);
-  if (lds > SLODE_RECON_MOMENTS_LDS_MAX)
-    return fail(h, SLODE_EINVAL, "slode_recon_moments: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, moments, staged weights) exceed "
-                                 "the budget of %d B; reduce recon_samples instead", s->T, s->S, s->C, lds, SLODE_RECON_MOMENTS_LDS_MAX);
+  const EvalCall d{"slode_recon_moments", "batch / mean / times / stage_t / workspace", !batch || !mean || !times || !stage_t || !workspace,
+                   "num_samples", num_samples, "; reduce recon_samples instead", "(one particle only)",
+                   is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr,
+                   is_post ? " (and no SLODE_NO_FOLD); reduce recon_samples instead" : nullptr,
+                   "step table, moments, staged weights", "reduce recon_samples instead"};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if ((rc = eval_lds(h, s, d, slode_recon_moments_lds_bytes(*s, h->ode_generic), SLODE_RECON_MOMENTS_LDS_MAX)) != SLODE_OK) return rc;
   ReconMomentsLaunch a{};
-  int rc = batch_labels(h, s, batch, &a.lab);
-  if (rc != SLODE_OK) return rc;
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
   if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_recon_moments: the prior needs the label tensors of the conditional prior groups");
   a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps; a.mean = mean; a.sd = sd;
   a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
   a.grid = eval_grid_for(h, s->B);
-  const uint64_t n0 = h->rng_counter;
-  if (!is_post) {
+  if (!is_post) {   // the prior: no observations, no encoder launches, nothing of the workspace but its size
     if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
-    if (!batch->eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
+    a.rng = take_draws(h, batch->eps, 1);
     ClockScope clock_scope(h, true);
     HIP_TRY(h, slode_launch_recon_moments(a, (hipStream_t)stream));
     return SLODE_OK;
   }
-  StepCall c;
-  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
-  c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = a.lab;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
   Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, "slode_recon_moments")) != SLODE_OK) return rc;
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
   a.loc = p.w.loc; a.scale = p.w.scale;
-  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
   ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_recon_moments(a, c.stream));
   return SLODE_OK;
 }
@@ -979,47 +1011,25 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
 int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                       const float* stage_t, const slode_batch* batch, int num_draws, float* bounds, float* loss_kb, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  const char* why = check_common(h, s, lay, params);
-  if (why) return fail(h, SLODE_EINVAL, "%s", why);
-  if (!batch || !bounds || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_traj_bounds: batch / bounds / times / stage_t / workspace is NULL");
-  if (((uintptr_t)bounds & 15) != 0) return fail(h, SLODE_EINVAL, "slode_traj_bounds: bounds must be 16-byte aligned");
-  if (num_draws < 1) return fail(h, SLODE_EINVAL, "slode_traj_bounds: num_draws = %d < 1", num_draws);
-  if ((long long)s->B * num_draws > 0x3fffffff)
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds: B x num_draws = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_draws);
-  if (is_adaptive(s->method))
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds: adaptive solver %s is not taken (fixed-grid methods only)", method_name(s->method));
-  if (particles_of(*s) > 1)
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds: particles = %d is not taken (the shape has one particle; the draws are num_draws)", s->particles);
-  if (h->fold_on || h->ode_pack || h->ode_alg)
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
-  const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_traj_bounds: batch->obs is NULL");
-  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
-                                 "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD)",
-                (long long)os[0], (long long)os[1], (long long)os[2]);
-  const size_t lds = slode_traj_bounds_lds_bytes(*s, num_draws, h->ode_generic);
-  if (lds > SLODE_TRAJ_BOUNDS_LDS_MAX)
-    return fail(h, SLODE_EINVAL, "slode_traj_bounds: the LDS tables of T = %d, S = %d, C = %d, num_draws = %d (%zu B: step table, observations, staged "
-                                 "weights, the per-draw losses) exceed the budget of %d B; fewer draws per call fit",
-                s->T, s->S, s->C, num_draws, lds, SLODE_TRAJ_BOUNDS_LDS_MAX);
-  StepCall c;
-  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
-  int rc = batch_call(h, s, SLODE_SVI_MAIN, batch, &c);
+  const EvalCall d{"slode_traj_bounds", "batch / bounds / times / stage_t / workspace", !batch || !bounds || !times || !stage_t || !workspace,
+                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
+                   " (and no SLODE_NO_FOLD)", "step table, observations, staged weights, the per-draw losses", "fewer draws per call fit", true};
+  int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK) return rc;
-  const uint64_t n0 = h->rng_counter;
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, "slode_traj_bounds")) != SLODE_OK) return rc;
+  if (((uintptr_t)bounds & 15) != 0) return fail(h, SLODE_EINVAL, "slode_traj_bounds: bounds must be 16-byte aligned");
+  if ((rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if ((rc = eval_lds(h, s, d, slode_traj_bounds_lds_bytes(*s, num_draws, h->ode_generic), SLODE_TRAJ_BOUNDS_LDS_MAX)) != SLODE_OK) return rc;
   TrajBoundsLaunch a{};
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = os[0]; a.t_major = p.t_major ? 1 : 0;
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = batch->obs_strides[0]; a.t_major = p.t_major ? 1 : 0;
   a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.bounds = bounds; a.loss_kb = loss_kb;
-  a.num_draws = num_draws; a.force_generic = h->ode_generic; a.lab = c.lab;
+  a.num_draws = num_draws; a.force_generic = h->ode_generic;
   a.grid = eval_grid_for(h, s->B);
-  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + (uint64_t)num_draws; }
   ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_traj_bounds(a, c.stream));
   return SLODE_OK;
 }
@@ -1030,35 +1040,19 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
 int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                             const float* stage_t, const slode_batch* batch, const float* const* cf_labels, unsigned int group_mask, int num_samples,
                             float* cf_mean, float* cf_sd, float* eff_mean, float* eff_sd, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* why = check_common(h, s, lay, params);
-  if (why) return fail(h, SLODE_EINVAL, "%s", why);
-  if (!batch || !times || !stage_t || !workspace) return fail(h, SLODE_EINVAL, "slode_intervene_moments: batch / times / stage_t / workspace is NULL");
-  if (num_samples < 1) return fail(h, SLODE_EINVAL, "slode_intervene_moments: num_samples = %d < 1", num_samples);
-  if ((long long)s->B * num_samples > 0x3fffffff)
-    return fail(h, SLODE_EINVAL, "slode_intervene_moments: B x num_samples = %lld exceeds 2^30 - 1 noise rows", (long long)s->B * num_samples);
-  if (is_adaptive(s->method))
-    return fail(h, SLODE_EINVAL, "slode_intervene_moments: adaptive solver %s is not taken (fixed-grid methods only); reduce counterfactual samples instead", method_name(s->method));
-  if (particles_of(*s) > 1) return fail(h, SLODE_EINVAL, "slode_intervene_moments: particles = %d is not taken (one particle only)", s->particles);
-  if (h->fold_on || h->ode_pack || h->ode_alg)
-    return fail(h, SLODE_EINVAL, "slode_intervene_moments cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG");
-  const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (!batch->obs) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the posterior needs observations (batch->obs is NULL)");
-  if (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4))
-    return fail(h, SLODE_EINVAL, "slode_intervene_moments: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
-                                 "[B,T,C] or [B,C,T] observations with C in {3, 4} (and no SLODE_NO_FOLD); reduce counterfactual samples instead",
-                (long long)os[0], (long long)os[1], (long long)os[2]);
+  const EvalCall d{"slode_intervene_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
+                   "num_samples", num_samples, "; reduce counterfactual samples instead", "(one particle only)",
+                   "the posterior needs observations (batch->obs is NULL)", " (and no SLODE_NO_FOLD); reduce counterfactual samples instead",
+                   "step table, moments, factual values, staged weights", "reduce counterfactual samples instead"};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (s->n_groups < 32 && (group_mask >> s->n_groups) != 0)
     return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x has bits at or beyond n_groups = %d", group_mask, s->n_groups);
   if (group_mask != 0 && !cf_labels) return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x needs the counterfactual labels (cf_labels is NULL)", group_mask);
-  const size_t lds = slode_intervene_moments_lds_bytes(*s, h->ode_generic);
-  if (lds > SLODE_INTERVENE_MOMENTS_LDS_MAX)
-    return fail(h, SLODE_EINVAL, "slode_intervene_moments: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, moments, factual values, staged "
-                                 "weights) exceed the budget of %d B; reduce counterfactual samples instead", s->T, s->S, s->C, lds, SLODE_INTERVENE_MOMENTS_LDS_MAX);
+  if ((rc = eval_lds(h, s, d, slode_intervene_moments_lds_bytes(*s, h->ode_generic), SLODE_INTERVENE_MOMENTS_LDS_MAX)) != SLODE_OK) return rc;
   InterveneMomentsLaunch a{};
   LabelSrc lab{};
-  int rc = batch_labels(h, s, batch, &lab);
-  if (rc != SLODE_OK) return rc;
+  if ((rc = batch_labels(h, s, batch, &lab)) != SLODE_OK) return rc;
   a.cf = lab;   // widths as the batch's; a counterfactual tensor that no intervened group reads may be NULL (its slot keeps the batch's pointer, unread)
   if (group_mask != 0) {
     if (lab.n == 0) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the counterfactual labels take the widths of batch->labels (n_labels is 0)");
@@ -1074,17 +1068,12 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
   a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd;
   a.group_mask = group_mask; a.num_samples = num_samples; a.force_generic = h->ode_generic;
   a.grid = eval_grid_for(h, s->B);
-  const uint64_t n0 = h->rng_counter;
-  StepCall c;
-  c.params = params; c.times = times; c.stage_t = stage_t; c.no_loss = 1;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
-  c.obs = batch->obs; c.obs_strides = batch->obs_strides; c.eps = batch->eps; c.lab = lab;
+  const StepCall c = forward_call(params, times, stage_t, batch, lab, nullptr, workspace, workspace_bytes, stream);
   Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, "slode_intervene_moments")) != SLODE_OK) return rc;
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
   a.loc = p.w.loc; a.scale = p.w.scale;
-  if (!c.eps) { a.rng = rng_of(h, n0); h->rng_counter = n0 + 1; }
   ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_intervene_moments(a, c.stream));
   return SLODE_OK;
 }

@@ -460,18 +460,35 @@ class Engine:
         bt.tensors = (obs, *labels, eps)
         return bt
 
+    def _batch_call(self, fn, params, batch: L.Batch, B: int, particles: int, *args, kind=None, last=()):
+        """The call every entry point that takes a slode_batch makes: the workspace of (B, particles), the fold guard, then
+        ``fn(handle, shape, layout, [kind,] params, times, stage_t, batch, *args, workspace, bytes, *last, stream)``, checked."""
+        ws = self.workspace(B, particles)
+        self._guard(params, ws)
+        _check(self.lib, self.handle, fn(
+            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), *(() if kind is None else (int(kind),)), self._p(params),
+            self._p(self._times), self._p(self._stage_t), C.byref(batch), *args, self._p(ws), ws.numel() * 4, *last, self._stream()))
+
+    def _out(self, t, name: str, shp):
+        """The output tensor ``t`` of an eval-side call: a float32 device tensor of shape ``shp``, allocated when None."""
+        if t is None:
+            return torch.empty(shp, dtype=torch.float32, device=self.device)
+        if tuple(self._f32(t, name).shape) != tuple(shp):
+            raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
+        return t
+
+    def _adam_args(self, params, adam):
+        """slode_adam of ``adam`` = (exp_avg, exp_avg_sq, lr, step, betas, eps), by reference; None: no fused update."""
+        if adam is None:
+            return None
+        m, v, lr, step, betas, aeps = adam
+        return C.byref(L.AdamArgs(params.numel(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(aeps), int(step)))
+
     def svi_step(self, kind: int, params, batch: L.Batch, B: int, loss_out, grads=None, adam=None, particles: int = 1):
         """slode_svi_step: kind L.SVI_MAIN | L.SVI_AUX; adam = (exp_avg, exp_avg_sq, lr, step, betas, eps) or None; particles = K: the mean
         loss and mean gradient of K particles in the same one call (the batch's eps, if given, is [K, B, L])."""
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        ad = None
-        if adam is not None:
-            m, v, lr, step, betas, aeps = adam
-            ad = L.AdamArgs(params.numel(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(aeps), int(step))
-        _check(self.lib, self.handle, self.lib.slode_svi_step(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, C.byref(ad) if ad is not None else None, self._stream()))
+        self._batch_call(self.lib.slode_svi_step, params, batch, B, particles, self._p(loss_out), self._p(grads), kind=kind,
+                         last=(self._adam_args(params, adam),))
         return loss_out
 
     def eval_stats(self, params, batch: L.Batch, B: int, is_post: bool, out, particles: int = 1):
@@ -482,12 +499,7 @@ class Engine:
         (adaptive solver, ``particles`` > 1, strided observations, measured arms): nothing is launched and no draw is consumed then."""
         if out.numel() != L.EVAL_SLOTS:
             raise ValueError("out must hold %d floats, got %d" % (L.EVAL_SLOTS, out.numel()))
-        self._f32(out, "out")
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        _check(self.lib, self.handle, self.lib.slode_eval_stats(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), 1 if is_post else 0, self._p(out), self._p(ws), ws.numel() * 4, self._stream()))
+        self._batch_call(self.lib.slode_eval_stats, params, batch, B, particles, 1 if is_post else 0, self._p(self._f32(out, "out")))
         return out
 
     def recon_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, mean=None, sd=None, particles: int = 1):
@@ -498,20 +510,9 @@ class Engine:
         ``draw_normal(num_samples * B).view(num_samples, B, L)`` yields).  Raises SlodeError naming the reason for what the kernel does not
         take (adaptive solver, ``particles`` > 1, strided posterior observations, measured arms, num_samples < 1, LDS budget): nothing is
         launched and no draw is consumed then."""
-        sp = self.spec
-        shp = (1 if sp.gauss else 3, B, sp.n_channels, self.T)
-        if mean is None:
-            mean = torch.empty(shp, dtype=torch.float32, device=self.device)
-        if sd is None:
-            sd = torch.empty(shp, dtype=torch.float32, device=self.device)
-        for t, name in ((mean, "mean"), (sd, "sd")):
-            if tuple(self._f32(t, name).shape) != shp:
-                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        _check(self.lib, self.handle, self.lib.slode_recon_moments(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), 1 if is_post else 0, int(num_samples), self._p(mean), self._p(sd), self._p(ws), ws.numel() * 4, self._stream()))
+        shp = (1 if self.spec.gauss else 3, B, self.spec.n_channels, self.T)
+        mean, sd = self._out(mean, "mean", shp), self._out(sd, "sd", shp)
+        self._batch_call(self.lib.slode_recon_moments, params, batch, B, particles, 1 if is_post else 0, int(num_samples), self._p(mean), self._p(sd))
         return mean, sd
 
     def traj_bounds(self, params, batch: L.Batch, B: int, num_draws: int, bounds=None, loss_kb=None, particles: int = 1):
@@ -524,18 +525,9 @@ class Engine:
         what the kernel does not take (adaptive solver, ``particles`` > 1 in the shape, strided observations, SLODE_NO_FOLD, measured arms, num_draws < 1, LDS budget):
         nothing is launched and no draw is consumed then; there is no composed fallback."""
         K = int(num_draws)
-        if bounds is None:
-            bounds = torch.empty(B, L.BOUND_SLOTS, dtype=torch.float32, device=self.device)
-        if loss_kb is None:
-            loss_kb = torch.empty(max(K, 0), B, dtype=torch.float32, device=self.device)
-        for t, name, shp in ((bounds, "bounds", (B, L.BOUND_SLOTS)), (loss_kb, "loss_kb", (max(K, 0), B))):
-            if tuple(self._f32(t, name).shape) != shp:
-                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        _check(self.lib, self.handle, self.lib.slode_traj_bounds(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), K, self._p(bounds), self._p(loss_kb), self._p(ws), ws.numel() * 4, self._stream()))
+        bounds = self._out(bounds, "bounds", (B, L.BOUND_SLOTS))
+        loss_kb = self._out(loss_kb, "loss_kb", (max(K, 0), B))
+        self._batch_call(self.lib.slode_traj_bounds, params, batch, B, particles, K, self._p(bounds), self._p(loss_kb))
         return bounds, loss_kb
 
     def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
@@ -553,16 +545,9 @@ class Engine:
         without counterfactual labels): nothing is launched and no draw is consumed then."""
         sp = self.spec
         shp = (1 if sp.gauss else 3, B, sp.n_channels, self.T)
-        outs = []
-        for t, name in ((cf_mean, "cf_mean"), (cf_sd, "cf_sd"), (eff_mean, "eff_mean"), (eff_sd, "eff_sd")):
-            if t is False:                      # not wanted: NULL in the C call
-                outs.append(None)
-                continue
-            if t is None:
-                t = torch.empty(shp, dtype=torch.float32, device=self.device)
-            if tuple(self._f32(t, name).shape) != shp:
-                raise ValueError("%s must be %s, got %s" % (name, list(shp), tuple(t.shape)))
-            outs.append(t)
+        # (an output passed as False is not wanted: NULL in the C call, None in the result)
+        outs = [None if t is False else self._out(t, name, shp)
+                for t, name in ((cf_mean, "cf_mean"), (cf_sd, "cf_sd"), (eff_mean, "eff_mean"), (eff_sd, "eff_sd"))]
         ptrs = None
         if cf_labels is not None:
             if len(cf_labels) != int(batch.n_labels):
@@ -581,11 +566,8 @@ class Engine:
                 if self._f32(t, "cf label %d" % i).numel() != B * int(batch.label_width[i]):
                     raise ValueError("cf label %d must be [%d, %d], got %s" % (i, B, int(batch.label_width[i]), tuple(t.shape)))
                 ptrs[i] = t.data_ptr()
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        _check(self.lib, self.handle, self.lib.slode_intervene_moments(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), ptrs, int(group_mask), int(num_samples), *(self._p(t) for t in outs), self._p(ws), ws.numel() * 4, self._stream()))
+        self._batch_call(self.lib.slode_intervene_moments, params, batch, B, particles, ptrs, int(group_mask), int(num_samples),
+                         *(self._p(t) for t in outs))
         return tuple(outs)
 
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
@@ -593,21 +575,13 @@ class Engine:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))
 
     def grad_partial(self, kind: int, params, batch: L.Batch, B: int, payload, particles: int = 1):
-        ws = self.workspace(B, particles)
-        self._guard(params, ws)
-        _check(self.lib, self.handle, self.lib.slode_grad_partial(
-            self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), self._p(self._times), self._p(self._stage_t),
-            C.byref(batch), self._p(self._f32(payload, "payload")), self._p(ws), ws.numel() * 4, self._stream()))
+        self._batch_call(self.lib.slode_grad_partial, params, batch, B, particles, self._p(self._f32(payload, "payload")), kind=kind)
 
     def grad_apply(self, kind: int, params, batch: L.Batch, B: int, payload, loss_out, grads, adam=None, particles: int = 1):
         ws = self.workspace(B, particles)
-        ad = None
-        if adam is not None:
-            m, v, lr, step, betas, aeps = adam
-            ad = L.AdamArgs(params.numel(), m.data_ptr(), v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(aeps), int(step))
         _check(self.lib, self.handle, self.lib.slode_grad_apply(
             self.handle, C.byref(self.shape(B, particles)), C.byref(self.layout), int(kind), self._p(params), batch.obs_strides, self._p(payload),
-            self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, C.byref(ad) if ad is not None else None, self._stream()))
+            self._p(loss_out), self._p(grads), self._p(ws), ws.numel() * 4, self._adam_args(params, adam), self._stream()))
         return loss_out
 
     def fold_invalidate(self):

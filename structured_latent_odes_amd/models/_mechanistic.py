@@ -233,6 +233,57 @@ class MechanisticBase(nn.Module):
             return {"l1": self.l1_func(mu_50, observations), "solution_xt": solution_xt, "mu_75": mu_75, "mu_50": mu_50,
                     "mu_25": mu_25, "std": std, "z": z}
 
+    # ---- what the fused eval-side calls below share ----------------------------------------------------------------------------
+    def _label_tensors(self, labels, B):
+        """The label tensors in ``LABELS`` order as ``make_batch`` takes them: ``[B, width]``, float32, contiguous."""
+        return [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
+
+    def _draws_batch(self, observations, labels, eps, draws):
+        """The engine batch of a call with ``draws`` draws per trajectory: ``eps`` ``[draws, B, L]`` (``[B, L]`` for one draw) or None."""
+        B = observations.shape[0]
+        e = eps if eps is None or draws > 1 else eps.reshape(B, -1)
+        return self._bind().engine.make_batch(observations, self._label_tensors(labels, B),
+                                              None if e is None else e.to(torch.float32).contiguous(), particles=draws)
+
+    @staticmethod
+    def _raise_unless_refused(err):
+        """Only a refusal (SLODE_EINVAL, status -1: nothing launched, nothing drawn) leads to a composed fallback: anything else is raised."""
+        if getattr(err, "status", None) != -1:
+            raise err
+
+    def _composed_moments(self, B, num_samples, eps, materialise, reduce):
+        """The chunk loop of a composed fallback: ``MOMENTS_CHUNK_ROWS // num_samples`` rows of the batch at a time,
+        ``materialise(lo, hi, eps[:, lo:hi])`` yields the per-draw curves of rows [lo, hi) (``{curve: ...}``) and ``reduce`` turns one
+        curve's into a tuple of ``[rows, C, T]`` tensors; returns ``{curve: tuple of [B, C, T]}``.  The noise is drawn once for the whole
+        batch (ONE drawing call, counter n -> n + 1, row k * B + b = draw k of trajectory b, as the engine call makes it) and sliced per
+        chunk, so the result does not depend on the chunking."""
+        rows = max(1, self.MOMENTS_CHUNK_ROWS // num_samples)
+        if eps is None:
+            eps = self._bind().engine.draw_normal(num_samples * B).view(num_samples, B, -1)
+        eps = eps.reshape(num_samples, B, -1)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        parts = {n: [] for n in names}
+        for lo in range(0, B, rows):
+            hi = min(B, lo + rows)
+            res = materialise(lo, hi, eps[:, lo:hi])
+            for n in names:
+                parts[n].append(reduce(res[n]))
+            del res
+        return {n: tuple(torch.cat(col, 0) for col in zip(*chunks)) for n, chunks in parts.items()}
+
+    @staticmethod
+    def _save_arrays(results_dir, named):
+        """``np.save`` of every ``(file name, tensor)`` of ``named`` under ``results_dir`` (created if missing): the paths written, in order."""
+        import os
+        import numpy as np
+        os.makedirs(results_dir, exist_ok=True)
+        written = []
+        for fname, val in named:
+            path = os.path.join(results_dir, fname)
+            np.save(path, val.cpu().numpy())
+            written.append(path)
+        return written
+
     # ---- the statistics row of one batch (training.input_pred_stats_fused) -------------------------------------------------
     def eval_stat_slots(self) -> Dict[str, int]:
         """{label name: its hit-count slot in the eval_stats row}: 3 + index of the label's head in ``AUX`` (include/slode.h)."""
@@ -252,12 +303,11 @@ class MechanisticBase(nn.Module):
         if out is None:
             out = torch.empty(L.EVAL_SLOTS, dtype=torch.float32, device=b.flat.device)
         if int(num_particles) == 1:
-            labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
-            bt = b.engine.make_batch(observations, labs, eps, particles=4 if eps is not None else 1)
+            bt = b.engine.make_batch(observations, self._label_tensors(labels, B), eps, particles=4 if eps is not None else 1)
             try:
                 return b.engine.eval_stats(b.flat, bt, B, is_post, out)
-            except L.SlodeError:
-                pass
+            except L.SlodeError:      # ANY engine error leads to the unfused calls here, not a refusal (_raise_unless_refused) alone:
+                pass                  # they name the same fault themselves, and the row is wanted wherever they can make it
         if eps is not None:
             raise ValueError("explicit eps is taken by the fused statistics call only; this configuration runs the unfused calls")
         return self._eval_stats_composed(observations, is_post, out, int(num_particles), labels)
@@ -310,19 +360,9 @@ class MechanisticBase(nn.Module):
 
     def save_recon_samples(self, results_dir: str, observations, is_post, num_samples: int, **labels):
         """Writes the arrays ``multiple_samples`` saves, under the reference's file names (``mu_50_post_sample.npy`` ...)."""
-        import os
-        import numpy as np
         res = self.recon_samples(observations, is_post, num_samples, **labels)
-        os.makedirs(results_dir, exist_ok=True)
         tag = "post_sample" if is_post else "prior_sample"
-        written = []
-        for name in ("mu_50", "mu_75", "mu_25", "mean"):
-            if name in res:
-                path = os.path.join(results_dir, "%s_%s.npy" % (name, tag))
-                np.save(path, res[name].cpu().numpy())
-                written.append(path)
-        return written
-
+        return self._save_arrays(results_dir, (("%s_%s.npy" % (name, tag), res[name]) for name in ("mu_50", "mu_75", "mu_25", "mean") if name in res))
 
     # ---- the Monte-Carlo summary of multiple_samples: mean and sd over the draws, nothing per draw kept -------------------------------
     MOMENT_HEADS = {False: ("mu_50", "mu_75", "mu_25"), True: ("mean",)}   # GAUSS -> curve names in the engine's head order q = 0, 1, 2
@@ -343,52 +383,22 @@ class MechanisticBase(nn.Module):
             raise ValueError("num_samples must be >= 1, got %d" % ns)
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
         try:
-            labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
-            e = eps if eps is None or ns > 1 else eps.reshape(B, -1)
-            bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=ns)
-            mean, sd = b.engine.recon_moments(b.flat, bt, B, is_post, ns)
+            mean, sd = b.engine.recon_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns)
             return {n: (mean[q], sd[q]) for q, n in enumerate(names)}
         except L.SlodeError as err:
-            if getattr(err, "status", None) != -1:      # only a refusal (SLODE_EINVAL: nothing launched, nothing drawn) leads to the composition
-                raise
-            return self._recon_moments_composed(observations, is_post, ns, eps, labels)
-
-    def _recon_moments_composed(self, observations, is_post, num_samples, eps, labels):
-        """The same dict from ``recon_samples``, ``MOMENTS_CHUNK_ROWS // num_samples`` rows of the batch at a time, reduced in fp32 with
-        ``mean`` / ``std(unbiased=False)`` over the sample axis.  The noise is drawn once for the whole batch (counter n -> n + 1, row
-        k * B + b = draw k of trajectory b) and sliced per chunk, so the result does not depend on the chunking."""
-        B = observations.shape[0]
-        rows = max(1, self.MOMENTS_CHUNK_ROWS // num_samples)
-        if eps is None:      # ONE drawing call for the whole batch, as recon_samples and the engine call make it; the chunks take their rows
-            eps = self._bind().engine.draw_normal(num_samples * B).view(num_samples, B, -1)
-        names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        parts = {n: ([], []) for n in names}
-        for lo in range(0, B, rows):
-            hi = min(B, lo + rows)
-            res = self.recon_samples(observations[lo:hi], is_post, num_samples, eps=None if eps is None else eps[:, lo:hi],
-                                     **{k: v[lo:hi] for k, v in labels.items()})
-            for n in names:
-                v = res[n].to(torch.float32)
-                parts[n][0].append(v.mean(dim=-1))
-                parts[n][1].append(v.std(dim=-1, unbiased=False))
-            del res
-        return {n: (torch.cat(m, 0), torch.cat(s, 0)) for n, (m, s) in parts.items()}
+            self._raise_unless_refused(err)
+        # composed from ``recon_samples``, reduced in fp32 with ``mean`` / ``std(unbiased=False)`` over the sample axis
+        return self._composed_moments(
+            B, ns, eps, lambda lo, hi, e: self.recon_samples(observations[lo:hi], is_post, ns, eps=e, **{k: v[lo:hi] for k, v in labels.items()}),
+            lambda v: (v.to(torch.float32).mean(dim=-1), v.to(torch.float32).std(dim=-1, unbiased=False)))
 
     def save_recon_moments(self, results_dir: str, observations, is_post, num_samples: int, **labels):
         """Writes ``<curve>_<post|prior>_sample_mean.npy`` and ``..._sample_sd.npy`` (``[B, C, T]`` each) for every head curve: new names
         beside the reference's ``mu_50_post_sample.npy`` & co., which ``save_recon_samples`` keeps writing."""
-        import os
-        import numpy as np
         res = self.recon_moments(observations, is_post, num_samples, **labels)
-        os.makedirs(results_dir, exist_ok=True)
         tag = "post_sample" if is_post else "prior_sample"
-        written = []
-        for name, (mean, sd) in res.items():
-            for kind, val in (("mean", mean), ("sd", sd)):
-                path = os.path.join(results_dir, "%s_%s_%s.npy" % (name, tag, kind))
-                np.save(path, val.cpu().numpy())
-                written.append(path)
-        return written
+        return self._save_arrays(results_dir, (("%s_%s_%s.npy" % (name, tag, kind), val)
+                                               for name, moments in res.items() for kind, val in zip(("mean", "sd"), moments)))
 
     # ---- counterfactual curves: the subject's own latent groups kept, the intervened groups redrawn from p(z_g | u'_g) on the same noise ----
     def _intervened(self, intervene, labels):
@@ -459,51 +469,30 @@ class MechanisticBase(nn.Module):
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
         # every label tensor goes to the engine, the named ones with their counterfactual values: a prior group over several labels
         # (challenge, proc) reads all of its columns, whichever of them were named
-        labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
-        cf = [swapped[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
-        e = eps if eps is None or ns > 1 else eps.reshape(B, -1)
+        cf = self._label_tensors(swapped, B)
         try:
-            bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=ns)
-            cm, cs, em, es = b.engine.intervene_moments(b.flat, bt, B, cf if mask else None, mask, ns)
+            cm, cs, em, es = b.engine.intervene_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, cf if mask else None, mask, ns)
             return {n: {"cf": (cm[q], cs[q]), "effect": (em[q], es[q])} for q, n in enumerate(names)}
         except L.SlodeError as err:
-            if getattr(err, "status", None) != -1:      # only a refusal (SLODE_EINVAL: nothing launched, nothing drawn) leads to the composition
-                raise
-        rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
-        if eps is None:      # ONE drawing call for the whole batch, as the engine call makes it; the chunks take their rows
-            eps = b.engine.draw_normal(ns * B).view(ns, B, -1)
-        eps = eps.reshape(ns, B, -1)
-        parts = {n: [[], [], [], []] for n in names}
-        for lo in range(0, B, rows):
-            hi = min(B, lo + rows)
-            res = self.counterfactual_samples(observations[lo:hi], ns, {k: swapped[k][lo:hi] for k in intervene}, eps=eps[:, lo:hi],
-                                              **{k: v[lo:hi] for k, v in labels.items()})
-            for n in names:
-                f, c = (v.to(torch.float32) for v in res[n])
-                d = c - f
-                for i, v in enumerate((c.mean(dim=-1), c.std(dim=-1, unbiased=False), d.mean(dim=-1), d.std(dim=-1, unbiased=False))):
-                    parts[n][i].append(v)
-            del res
-        cat = {n: [torch.cat(p, 0) for p in ps] for n, ps in parts.items()}
-        return {n: {"cf": (v[0], v[1]), "effect": (v[2], v[3])} for n, v in cat.items()}
+            self._raise_unless_refused(err)
+
+        def paired(arms):      # (factual, counterfactual) [rows, C, T, ns] -> moments of the counterfactual and of the paired difference
+            f, c = (v.to(torch.float32) for v in arms)
+            d = c - f
+            return c.mean(dim=-1), c.std(dim=-1, unbiased=False), d.mean(dim=-1), d.std(dim=-1, unbiased=False)
+        res = self._composed_moments(
+            B, ns, eps, lambda lo, hi, e: self.counterfactual_samples(observations[lo:hi], ns, {k: swapped[k][lo:hi] for k in intervene}, eps=e,
+                                                                       **{k: v[lo:hi] for k, v in labels.items()}), paired)
+        return {n: {"cf": (v[0], v[1]), "effect": (v[2], v[3])} for n, v in res.items()}
 
     def save_intervention_moments(self, results_dir: str, observations, num_samples: int, intervene, **labels):
         """Writes ``<curve>_cf_<names>_sample_mean.npy`` / ``..._sample_sd.npy`` and ``<curve>_effect_<names>_sample_mean.npy`` /
         ``..._sample_sd.npy`` (``[B, C, T]`` each) for every head curve, ``<names>`` the intervened label names joined by '+' in the order
         given."""
-        import os
-        import numpy as np
         res = self.intervention_moments(observations, num_samples, intervene, **labels)
-        os.makedirs(results_dir, exist_ok=True)
         tag = "+".join(intervene)
-        written = []
-        for name, arms in res.items():
-            for arm, key in (("cf", "cf"), ("effect", "effect")):
-                for kind, val in zip(("mean", "sd"), arms[key]):
-                    path = os.path.join(results_dir, "%s_%s_%s_sample_%s.npy" % (name, arm, tag, kind))
-                    np.save(path, val.cpu().numpy())
-                    written.append(path)
-        return written
+        return self._save_arrays(results_dir, (("%s_%s_%s_sample_%s.npy" % (name, arm, tag, kind), val) for name, arms in res.items()
+                                               for arm in ("cf", "effect") for kind, val in zip(("mean", "sd"), arms[arm])))
 
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
@@ -522,10 +511,7 @@ class MechanisticBase(nn.Module):
         B, K = observations.shape[0], int(num_draws)
         if K < 1:
             raise ValueError("num_draws must be >= 1, got %d" % K)
-        labs = [labels[l].reshape(B, -1).to(torch.float32).contiguous() for l in self.LABELS]
-        e = eps if eps is None or K > 1 else eps.reshape(B, -1)
-        bt = b.engine.make_batch(observations, labs, None if e is None else e.to(torch.float32).contiguous(), particles=K)
-        bounds, loss = b.engine.traj_bounds(b.flat, bt, B, K)
+        bounds, loss = b.engine.traj_bounds(b.flat, self._draws_batch(observations, labels, eps, K), B, K)
         res = {n: bounds[:, i] for i, n in enumerate(self.BOUND_NAMES)}
         if return_draws:
             res["loss"] = loss

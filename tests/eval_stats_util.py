@@ -21,10 +21,12 @@ MARGIN = 1e-4        # no decision of the hit test may be closer than this to it
 _OSPEC = {"cvs": O.cvs_spec, "challenge": O.challenge_spec, "proc": O.proc_spec}
 
 
-def build(case, solver="rk4"):
-    """Parameters (reference initialisers, every tensor moved by 0.05 randn, the label heads by another 0.3 randn: at their N(0, 1e-3)
-    initialisation every sigmoid sits within 1e-3 of 0.5), one synthetic batch (seed 7) and the four noise rows -- CPU generators only."""
-    fam, kw, B, T = CASES[case]
+def build_case(case, noise, solver="rk4", B=None, jitter_heads=True):
+    """One seeded case at any B (None: the case's own): parameters (reference initialisers, every tensor moved by 0.05 randn and, with
+    ``jitter_heads``, the label heads by another 0.3 randn: at their N(0, 1e-3) initialisation every sigmoid sits within 1e-3 of 0.5),
+    one synthetic batch (seed 7) and the noise ``noise`` = (key, rows, seed): [rows, B, L] under ``key`` -- CPU generators only."""
+    fam, kw, B0, T = CASES[case]
+    B = B or B0
     ospec = _OSPEC[fam](solver=solver, **kw)
     S = 8 if fam == "proc" else 5
     p = O.init_params(ospec, T=T, S=S)
@@ -32,11 +34,18 @@ def build(case, solver="rk4"):
     p = {k: v + 0.05 * torch.randn(v.shape, generator=g) for k, v in p.items()}
     g3 = torch.Generator().manual_seed(3)
     for k in sorted(p):
-        if k.startswith("q_"):
+        if jitter_heads and k.startswith("q_"):
             p[k] = p[k] + 0.3 * torch.randn(p[k].shape, generator=g3)
     obs, u, _, times = O.synthetic_batch(ospec, B, T, seed=7)
-    eps4 = torch.randn(4, B, ospec.latent_dim, generator=torch.Generator().manual_seed(NOISE_SEED))
-    return dict(fam=fam, kw=dict(kw, solver=solver), ospec=ospec, p=p, obs=obs, u=u, eps4=eps4, times=times, B=B, T=T, S=S)
+    key, rows, seed = noise
+    c = dict(fam=fam, kw=dict(kw, solver=solver), ospec=ospec, p=p, obs=obs, u=u, times=times, B=B, T=T, S=S)
+    c[key] = torch.randn(rows, B, ospec.latent_dim, generator=torch.Generator().manual_seed(seed))
+    return c
+
+
+def build(case, solver="rk4"):
+    """The case of the statistics row: the four noise rows [4, B, L] (main, auxiliary, recon, labels) under ``eps4``."""
+    return build_case(case, ("eps4", 4, NOISE_SEED), solver)
 
 
 def f64(p):

@@ -69,17 +69,8 @@ def accumulation_bars(mean64, sd64, ns):
 
 # ---- seeded cases and the fp64 oracle ------------------------------------------------------------------------------------------------
 def build(case, solver="rk4", B=None, ns=7):
-    """EU.build's parameters (reference initialisers moved by 0.05 randn) and synthetic batch at any B, and [ns, B, L] noise."""
-    fam, kw, B0, T = EU.CASES[case]
-    B = B or B0
-    ospec = EU._OSPEC[fam](solver=solver, **kw)
-    S = 8 if fam == "proc" else 5
-    p = O.init_params(ospec, T=T, S=S)
-    g = torch.Generator().manual_seed(11)
-    p = {k: v + 0.05 * torch.randn(v.shape, generator=g) for k, v in p.items()}
-    obs, u, _, times = O.synthetic_batch(ospec, B, T, seed=7)
-    eps = torch.randn(ns, B, ospec.latent_dim, generator=torch.Generator().manual_seed(NOISE_SEED + ns))
-    return dict(fam=fam, kw=dict(kw, solver=solver), ospec=ospec, p=p, obs=obs, u=u, eps=eps, times=times, B=B, T=T, S=S, ns=ns)
+    """EU.build_case's parameters (the label heads not moved: no curve reads them) and synthetic batch at any B, and [ns, B, L] noise."""
+    return dict(EU.build_case(case, ("eps", ns, NOISE_SEED + ns), solver, B, jitter_heads=False), ns=ns)
 
 
 def oracle_curves(p64, ospec, z, times, solver):

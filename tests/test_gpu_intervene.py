@@ -11,7 +11,8 @@ import torch
 from tests import eval_stats_util as EU
 from tests import intervene_util as IU
 from tests import recon_moments_util as RU
-from tests.test_gpu_recon_moments import ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _device_batch, _engine, _eps_dev, _model
+from tests.eval_gpu_util import ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _device_batch, _engine, _eps_dev
+from tests.test_gpu_recon_moments import SIZES, _model
 from tests.test_gpu_recon_moments import _moments as _recon_moments
 
 pytestmark = pytest.mark.gpu

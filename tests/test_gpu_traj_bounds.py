@@ -10,7 +10,8 @@ import torch
 
 from tests import eval_stats_util as EU
 from tests import traj_bounds_util as TU
-from tests.test_gpu_recon_moments import ADAPTIVE, _device_batch, _engine, _model
+from tests.eval_gpu_util import ADAPTIVE, _device_batch, _engine
+from tests.test_gpu_recon_moments import _model
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")

@@ -21,22 +21,8 @@ REL = 1e-5
 
 
 def build(case, solver="rk4", B=None, K=4):
-    """EU.build's parameters (reference initialisers moved by 0.05 randn, the label heads by another 0.3 randn) and synthetic batch
-    (seed 7) at any B, and the [K, B, L] noise of seed 33 -- CPU generators only."""
-    fam, kw, B0, T = EU.CASES[case]
-    B = B or B0
-    ospec = EU._OSPEC[fam](solver=solver, **kw)
-    S = 8 if fam == "proc" else 5
-    p = O.init_params(ospec, T=T, S=S)
-    g = torch.Generator().manual_seed(11)
-    p = {k: v + 0.05 * torch.randn(v.shape, generator=g) for k, v in p.items()}
-    g3 = torch.Generator().manual_seed(3)
-    for k in sorted(p):
-        if k.startswith("q_"):
-            p[k] = p[k] + 0.3 * torch.randn(p[k].shape, generator=g3)
-    obs, u, _, times = O.synthetic_batch(ospec, B, T, seed=7)
-    eps = torch.randn(K, B, ospec.latent_dim, generator=torch.Generator().manual_seed(NOISE_SEED))
-    return dict(fam=fam, kw=dict(kw, solver=solver), ospec=ospec, p=p, obs=obs, u=u, eps=eps, times=times, B=B, T=T, S=S, K=K)
+    """EU.build_case's parameters (label heads moved) and synthetic batch (seed 7) at any B, and the [K, B, L] noise of seed 33."""
+    return dict(EU.build_case(case, ("eps", K, NOISE_SEED), solver, B), K=K)
 
 
 def oracle_rows(c, eps=None, rows=None, dtype=torch.float64):
