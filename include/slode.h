@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 180 /* 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n (0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 190 /* 0.1.9: slode_cohort_moments, slode_cohort_plan (0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -38,6 +38,8 @@ extern "C" {
 #define SLODE_MAX_PARTICLES 1024
 #define SLODE_EVAL_SLOTS 8 /* floats of one slode_eval_stats row */
 #define SLODE_BOUND_SLOTS 4 /* floats of one slode_traj_bounds row */
+#define SLODE_COHORT_MAX_G 1024 /* most cohorts of one slode_cohort_moments call */
+#define SLODE_COHORT_MAX_CHUNK 64 /* most members one workgroup folds into one partial */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -474,6 +476,49 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
                            float* sd /* [Q,B,C,T_out] or NULL */, float* x_mean /* [B,S,T_out] or NULL */, float* x_sd /* [B,S,T_out] or NULL */,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- cohort curves: per-condition moments and the evaluation notebooks' L1 as ONE call (cvs_eval_final, sbio_eval_*, challenge_eval_*: the
+ * subjects of one condition selected, every head curve averaged over them (and over the sample axis), np.std over the subjects for the band,
+ * the observations averaged the same way, l1_error = sum_t |mean_y - mean_mu_50|) ------------------------------------------------------------
+ * A cohort is a set of trajectories of the batch.  For cohort g with members b_1 .. b_n and K = num_samples draws per member, every head
+ * value (q, c, t) takes v[b][k], the head curve of draw k of trajectory b: EXACTLY the draws of slode_recon_moments for the same is_post
+ * (row k * B + b of one drawing call, b the trajectory's index in the batch).  With clip_min > -INFINITY, v is replaced by clip_min where
+ * v < clip_min (a comparison: NaN stays NaN; the sbio notebooks' mu_50[mu_50 < 0] = 0 on the samples).
+ *   mean[q][g][c][t]         mean over the n K values
+ *   sd[q][g][c][t]           population sd over the n K values (divisor n K)
+ *   sd_subjects[q][g][c][t]  population sd over the members of the per-member draw mean (divisor n); at K = 1 the notebooks' np.std(data[loc], 0)
+ *   obs_mean[g][c][t]        mean over the members of the observation
+ *   l1[g][c]                 sum_t |obs_mean[g][c][t] - mean[0][g][c][t]| (head 0 = mu_50 / the Gauss mean), in fp64 from the fp32 outputs
+ * An empty cohort gives NaN in every output.  A trajectory may belong to no cohort; it must not belong to two (precondition, not checked).
+ *
+ * slode_cohort_plan: pure host arithmetic -- no handle, no HIP call.  chunk = R is the number of consecutive members of one cohort that one
+ * workgroup folds on chip before it writes a partial: chunk in [1, SLODE_COHORT_MAX_CHUNK] is used as given; chunk == 0 lets the library
+ * choose, as a function of M alone: the smallest power of two <= 64 with ceil(M / R) <= 1024.  *n_partials = ceil(M / R) + G is the bound the
+ * scratch is sized by; *lds_bytes the dynamic LDS of the main kernel (budget 160 KiB: SLODE_EINVAL naming T beyond it); *scratch_bytes what
+ * slode_cohort_moments needs at `scratch`.  num_samples does not enter any figure; it is checked (>= 1) only. */
+int slode_cohort_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                      size_t* scratch_bytes);
+
+/* members [M] (device): the member trajectories sorted by cohort; offsets [G + 1] (device): offsets[g] .. offsets[g + 1] is cohort g's slice of
+ * members, offsets[0] = 0, offsets[G] = M; 0 <= M <= B, 1 <= G <= SLODE_COHORT_MAX_G.  The host cannot check their contents; the kernels read
+ * nothing out of bounds whatever they hold: offsets are clamped to [0, M] (a decreasing pair is an empty cohort), member positions to [0, M),
+ * and a member index outside [0, B) is never used as an address -- it turns every output of its cohort into NaN.
+ * Launches (slode_profile_read): posterior "weff", "enc_fwd2", then "cohort_plan", "cohort_moments", "cohort_merge"; the prior the last three.
+ * The result is a function of (parameters, inputs, noise, members, offsets, chunk) alone: bitwise equal across runs, launch grids and in-kernel
+ * vs explicit noise; two chunk sizes agree to rounding.  Noise: as slode_recon_moments (batch->eps == NULL: ONE drawing call, counter n -> n + 1;
+ * else a dense [num_samples, B, L] tensor, counter unchanged).  Enqueue only, capturable, a linear graph.  scratch: 16-byte aligned device
+ * memory of the plan's scratch_bytes; its contents after the call are the partials (unspecified layout).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_recon_moments refuses
+ * for the same is_post (its LDS rung replaced by this call's own); then members / offsets NULL with M > 0; M outside [0, B]; G outside
+ * [1, SLODE_COHORT_MAX_G]; chunk outside [0, SLODE_COHORT_MAX_CHUNK]; mean NULL; obs_mean or l1 given with batch->obs NULL; observation
+ * strides other than dense [B,T,C] / [B,C,T] whenever observations are read (the prior included); scratch NULL or misaligned; the LDS tables
+ * beyond 160 KiB; and with SLODE_ENOSPC scratch_bytes below the plan's figure. */
+int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                         const float* stage_t, const slode_batch* batch, int is_post, int num_samples,
+                         const int32_t* members /* device [M] */, const int32_t* offsets /* device [G + 1] */, int M, int G, int chunk,
+                         float clip_min /* -INFINITY: off */, float* mean /* [Q,G,C,T] */, float* sd /* [Q,G,C,T] or NULL */,
+                         float* sd_subjects /* [Q,G,C,T] or NULL */, float* obs_mean /* [G,C,T] or NULL */, float* l1 /* [G,C] or NULL */,
+                         void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -544,11 +589,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments / slode_forecast_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", "forecast_moments", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -1,0 +1,309 @@
+// Cohort moments (slode_cohort_moments): per COHORT -- a set of trajectories of the batch, e.g. the subjects of one condition -- the mean, the
+// population sd over members x draws, the population sd over the members of the per-member draw mean, the mean observation and the
+// reference notebooks' L1 error of every decoder head curve, without writing anything per trajectory.  The draws are those of
+// slode_recon_moments (row k * B + b of one drawing call, b the member's index in the batch).  Three launches:
+//   cohort_plan     one workgroup: offsets[G + 1] -> the chunk table {cohort, first position, length} and the per-cohort partial ranges
+//                   [cs[g], cs[g + 1]) by a block scan over ceil(n_g / R); offsets are clamped to [0, M], a decreasing pair is an empty cohort
+//   cohort_moments  one workgroup of four waves folds one chunk -- R consecutive members of ONE cohort -- at a time (persistent loop over
+//                   the chunk ids) and writes one partial:
+//     M0  once per workgroup: the staged weights of slode_forward.h
+//     per member: M1 loc / scale of the posterior or of the prior nets on the member's labels; its observations added into [C][T]
+//     per draw:   M2-M5 the shared phases, as recon_moments_kernel runs them
+//     M6' thread <-> time point: per (q, c) the value v (clipped) updates six floats in the LDS, shifted by v00, the chunk's first
+//         member's first draw: t1 += dv, t2 += dv^2 (all values), m1 += dv (this member); after the member's last draw mb = m1 / K,
+//         b1 += mb, b2 += mb^2, m1 = 0 -- never a sum of v^2
+//     the partial: v00, t1, t2, b1, b2 per value and the observation sum, plain per-lane stores, t contiguous, by the values' owner threads
+//   cohort_merge    one workgroup per (cohort, channel), thread <-> time point: walks the cohort's partials in slot order, each as (count,
+//                   mean, M2) of the values and of the member means in fp64, merged by Chan's pairwise update; the L1 sum over t in fp64 by
+//                   a fixed-shape tree
+// Every value has ONE owner thread which sees members and draws in list order; no atomics: the result is a function of (parameters,
+// inputs, noise, members, offsets, chunk) alone, independent of the launch grid.  A member index outside [0, B) is never used as an
+// address: it flags its chunk, and the merge turns every output of that cohort into NaN; positions are clamped to [0, M).
+#include "slode_forward.h"
+
+namespace {
+
+constexpr int CM_NT = FWD_NT;
+
+// offsets (in floats, multiples of 4) of the pieces of the dynamic LDS region: the shared ones, then the six-float table [Q*C][6][T], the
+// observation sum [C][T] and loc / scale
+struct CmLds { FwdLds f; int acc, obs, loc, sc, total; };
+
+struct CmK {
+  FwdK f;
+  PriorK pr;
+  int is_post, ns, M, G, t_major;
+  long long sb, PS;   // floats between observation rows; floats of one partial
+  float clip;
+  const float *loc, *scale, *eps, *u, *obs;
+  const int *members, *cs;
+  const int4* tab;
+  int* flags;
+  float* part;
+  CmLds o;
+  RngK rng;
+  LabelSrc lab;
+};
+
+// ---- cohort_plan ----------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CM_NT) cohort_plan_kernel(const int* __restrict__ offsets, int M, int G, int R, int NP, int* __restrict__ cs,
+                                                           int4* __restrict__ tab) {
+  __shared__ int s_o[SLODE_COHORT_MAX_G + 1];
+  __shared__ int s_cs[SLODE_COHORT_MAX_G + 1];
+  __shared__ long long s_sum[CM_NT];
+  const int tid = threadIdx.x;
+  for (int g = tid; g <= G; g += CM_NT) s_o[g] = M > 0 ? min(max(offsets[g], 0), M) : 0;
+  __syncthreads();
+  constexpr int PER = SLODE_COHORT_MAX_G / CM_NT;   // consecutive cohorts per thread
+  long long own = 0;
+  for (int j = 0; j < PER; ++j) {
+    const int g = tid * PER + j;
+    if (g < G) own += (max(s_o[g + 1] - s_o[g], 0) + R - 1) / R;
+  }
+  s_sum[tid] = own;
+  __syncthreads();
+  for (int off = 1; off < CM_NT; off <<= 1) {   // inclusive scan of the threads' sums
+    const long long add = tid >= off ? s_sum[tid - off] : 0;
+    __syncthreads();
+    s_sum[tid] += add;
+    __syncthreads();
+  }
+  long long run = s_sum[tid] - own;
+  for (int j = 0; j < PER; ++j) {
+    const int g = tid * PER + j;
+    if (g <= G) s_cs[g] = (int)(run < NP ? run : NP);   // (never beyond the scratch, whatever offsets hold)
+    if (g < G) run += (max(s_o[g + 1] - s_o[g], 0) + R - 1) / R;
+  }
+  if (tid == CM_NT - 1 && G == SLODE_COHORT_MAX_G) s_cs[G] = (int)(run < NP ? run : NP);
+  __syncthreads();
+  for (int g = tid; g <= G; g += CM_NT) cs[g] = s_cs[g];
+  const int NCH = s_cs[G];
+  for (int i = tid; i < NCH; i += CM_NT) {
+    int lo = 0, hi = G - 1;   // the cohort whose range holds i: the largest g with cs[g] <= i
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (s_cs[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    const int j = i - s_cs[lo], n = max(s_o[lo + 1] - s_o[lo], 0);
+    tab[i] = make_int4(lo, s_o[lo] + j * R, min(R, n - j * R), 0);
+  }
+}
+
+// ---- cohort_moments -------------------------------------------------------------------------------------------------
+// SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
+template <int SC>
+__global__ void __launch_bounds__(CM_NT) cohort_moments_kernel(const CmK k) {
+  constexpr int SM = SC ? SC : SLODE_MAX_S;
+  extern __shared__ __attribute__((aligned(16))) float s_cm[];
+  const FwdK& f = k.f;
+  const float* __restrict__ par = f.params;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = f.T, L = f.L, S = SC ? SC : f.S, H = f.H, C = f.C, NS = T - 1, QC = f.Q * C, ns = k.ns, CT = C * T;
+  const int NCH = k.cs[k.G];
+  if ((int)blockIdx.x >= NCH) return;   // (the grid is sized by the bound ceil(M / R) + G)
+  const FwdSm sm = fwd_sm(s_cm, k.o.f);
+  float* s_acc = s_cm + k.o.acc;   // [Q*C][6: v00, t1, t2, m1, b1, b2][T]
+  float* s_obs = s_cm + k.o.obs;   // [C][T]
+  float* s_loc = s_cm + k.o.loc;
+  float* s_sc = s_cm + k.o.sc;
+
+  // ---- M0: the weights every draw reuses ----
+  fwd_stage_weights<SM>(f, sm, S, tid);
+
+  for (int i = blockIdx.x; i < NCH; i += gridDim.x) {
+    const int4 ch = k.tab[i];   // cohort, first position, length
+    float* part = k.part + (long long)i * k.PS;
+    int bad = 0;
+    bool first = true;
+    // the observation sum: memory index e of a row <-> slot c * T + t, one owner thread per slot from here to the partial's store
+    if (k.obs)
+      for (int e = tid; e < CT; e += CM_NT) s_obs[k.t_major ? (e % C) * T + e / C : e] = 0.f;
+    for (int j = 0; j < ch.z; ++j) {
+      const int pos = min(max(ch.y + j, 0), k.M - 1);
+      const int b = k.members[pos];
+      if (b < 0 || b >= f.B) { bad = 1; continue; }   // (workgroup-uniform: never an address)
+      // ---- M1 ----
+      __syncthreads();   // (M0's writes; the previous member's readers of s_u / s_loc / s_sc)
+      if (!k.is_post && k.pr.n_groups > 0 && tid < k.pr.nu) sm.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
+      __syncthreads();
+      if (tid < L) {
+        const int l = tid;
+        float loc, sc;
+        if (k.is_post) {
+          loc = k.loc[(long long)b * L + l]; sc = k.scale[(long long)b * L + l];
+        } else {
+          float pl, pls;
+          fwd_prior_at(k.pr, par, sm.u, l, pl, pls);
+          loc = pl; sc = expf(pls);
+        }
+        s_loc[l] = loc; s_sc[l] = sc;
+      }
+      if (k.obs) {
+        const float* __restrict__ y = k.obs + (long long)b * k.sb;   // (dense row: consecutive lanes, consecutive addresses)
+        for (int e = tid; e < CT; e += CM_NT) s_obs[k.t_major ? (e % C) * T + e / C : e] += y[e];
+      }
+      for (int kk = 0; kk < ns; ++kk) {
+        // ---- M2: draw kk = row kk * B + b of the call's noise ----
+        if (tid < L) sm.z[tid] = fmaf(s_sc[tid], slode_eps_at(k.rng, k.eps, (long long)kk * f.B + b, L, tid), s_loc[tid]);
+        __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] are done)
+        // ---- M3 - M5 ----
+        fwd_init_state<SM>(sm, H, L, S, tid);
+        fwd_step_table_staged<SM>(f, sm, S, tid);
+        __syncthreads();
+        fwd_scan(sm.A, sm.B, sm.x0, S, NS, lane, wave, CM_NT / 64);
+        __syncthreads();
+        // ---- M6': head values of the thread's time points into the six-float table ----
+        const bool init = first && kk == 0, last = kk == ns - 1;
+        for (int t = tid; t < T; t += CM_NT) {
+          float x[SM];
+#pragma unroll
+          for (int s = 0; s < SM; ++s) x[s] = s < S ? (t == 0 ? sm.x0[s] : sm.A[(t - 1) * S + s]) : 0.f;
+          for (int qc = 0; qc < QC; ++qc) {
+            float v = 0.f;
+#pragma unroll
+            for (int s = 0; s < SM; ++s) if (s < S) v = fmaf(sm.hw[qc * S + s], x[s], v);
+            if (v < k.clip) v = k.clip;   // (a comparison: NaN stays NaN)
+            float* m = s_acc + (qc * 6) * T + t;
+            float m1;
+            if (init) { m[0] = v; m[T] = 0.f; m[2 * T] = 0.f; m[4 * T] = 0.f; m[5 * T] = 0.f; m1 = 0.f; }
+            else {
+              const float dv = v - m[0];
+              m[T] += dv; m[2 * T] = fmaf(dv, dv, m[2 * T]); m1 = m[3 * T] + dv;
+            }
+            if (last) {
+              const float mb = m1 / (float)ns;
+              m[4 * T] += mb; m[5 * T] = fmaf(mb, mb, m[5 * T]); m1 = 0.f;
+            }
+            m[3 * T] = m1;
+          }
+        }
+      }
+      first = false;
+    }
+    // ---- the partial: the thread's own values, lanes <-> consecutive t ----
+    for (int t = tid; t < T; t += CM_NT)
+      for (int qc = 0; qc < QC; ++qc) {
+        const float* m = s_acc + (qc * 6) * T + t;
+        float* p = part + (long long)(qc * 5) * T + t;
+        p[0] = m[0]; p[T] = m[T]; p[2 * T] = m[2 * T]; p[3 * T] = m[4 * T]; p[4 * T] = m[5 * T];
+      }
+    if (k.obs)
+      for (int e = tid; e < CT; e += CM_NT) {
+        const int slot = k.t_major ? (e % C) * T + e / C : e;
+        part[(long long)5 * QC * T + slot] = s_obs[slot];
+      }
+    if (tid == 0) k.flags[i] = bad;
+  }
+}
+
+// ---- cohort_merge ---------------------------------------------------------------------------------------------------
+struct CgK {
+  int G, C, T, Q, K, has_obs;
+  long long PS;
+  const int* cs;
+  const int4* tab;
+  const int* flags;
+  const float* part;
+  float *mean, *sd, *sdb, *obs_mean, *l1;
+};
+
+__global__ void __launch_bounds__(CM_NT) cohort_merge_kernel(const CgK k) {
+  __shared__ double s_w[CM_NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x / k.C, c = blockIdx.x - g * k.C, T = k.T, C = k.C, QC = k.Q * k.C;
+  const int p0 = k.cs[g], p1 = k.cs[g + 1];
+  long long N = 0;
+  int bad = 0;
+  for (int p = p0; p < p1; ++p) { N += k.tab[p].z; bad |= k.flags[p]; }
+  const bool none = N == 0 || bad;
+  const float fnan = __builtin_nanf("");
+  double l1 = 0.0;
+  for (int t = tid; t < T; t += CM_NT) {
+    float om = fnan;
+    if (k.has_obs) {
+      double so = 0.0;
+      for (int p = p0; p < p1; ++p) so += (double)k.part[(long long)p * k.PS + (long long)5 * QC * T + c * T + t];
+      if (!none) om = (float)(so / (double)N);
+      if (k.obs_mean) k.obs_mean[((long long)g * C + c) * T + t] = om;
+    }
+    float m0 = fnan;
+    for (int q = 0; q < k.Q; ++q) {
+      const int qc = q * C + c;
+      double nA = 0.0, meanA = 0.0, M2A = 0.0, mA = 0.0, meanbA = 0.0, M2bA = 0.0;   // values: (count, mean, M2); member means: the same
+      for (int p = p0; p < p1; ++p) {
+        const float* v = k.part + (long long)p * k.PS + (long long)(qc * 5) * T + t;
+        const double n = (double)k.tab[p].z, nk = n * (double)k.K;
+        const double v00 = v[0], t1 = v[T], t2 = v[2 * T], b1 = v[3 * T], b2 = v[4 * T];
+        const double meanB = v00 + t1 / nk, M2B = nk > 1.0 ? fmax(t2 - t1 * t1 / nk, 0.0) : 0.0;
+        const double meanbB = v00 + b1 / n, M2bB = n > 1.0 ? fmax(b2 - b1 * b1 / n, 0.0) : 0.0;
+        {
+          const double nn = nA + nk, d = meanB - meanA;
+          meanA += d * (nk / nn); M2A += M2B + d * d * (nA * nk / nn); nA = nn;
+        }
+        {
+          const double nn = mA + n, d = meanbB - meanbA;
+          meanbA += d * (n / nn); M2bA += M2bB + d * d * (mA * n / nn); mA = nn;
+        }
+      }
+      const long long o = (((long long)q * k.G + g) * C + c) * T + t;
+      const float mean = none ? fnan : (float)meanA;
+      k.mean[o] = mean;
+      if (k.sd) k.sd[o] = none ? fnan : (float)sqrt(M2A / nA);
+      if (k.sdb) k.sdb[o] = none ? fnan : (float)sqrt(M2bA / mA);
+      if (q == 0) m0 = mean;
+    }
+    l1 += fabs((double)om - (double)m0);
+  }
+  if (k.l1) {   // (workgroup-uniform) the sum over t: per thread t = tid, tid + 256, ..; then a fixed tree over lanes and waves
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) l1 += __shfl_down(l1, off, 64);
+    if (lane == 0) s_w[wave] = l1;
+    __syncthreads();
+    if (tid == 0) k.l1[g * C + c] = none ? fnan : (float)(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+  }
+}
+
+CmLds cm_lds(const slode_shape& s, bool generic) {
+  const int Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+  LdsCarve cv;
+  CmLds o{};
+  o.f = fwd_lds(cv, s, generic);
+  o.acc = cv.take(Q * s.C * 6 * s.T); o.obs = cv.take(s.C * s.T); o.loc = cv.take(s.L); o.sc = cv.take(s.L);
+  o.total = cv.n;
+  return o;
+}
+
+}  // namespace
+
+size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic) {
+  return (size_t)cm_lds(s, fwd_generic(s, force_generic)).total * sizeof(float);
+}
+
+hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream) {
+  const slode_shape& s = a.s;
+  const slode_layout& lay = a.lay;
+  const CohortScratch sc = slode_cohort_scratch(s, a.M, a.G, a.chunk);
+  const size_t lds = slode_cohort_lds_bytes(s, a.force_generic);
+  if (lds > SLODE_COHORT_LDS_MAX || a.num_samples < 1 || a.grid < 1 || a.chunk < 1 || a.chunk > SLODE_COHORT_MAX_CHUNK || a.G < 1 ||
+      a.G > SLODE_COHORT_MAX_G || a.M < 0 || a.M > s.B || !a.mean || !a.scratch || (a.M > 0 && (!a.members || !a.offsets)))
+    return hipErrorInvalidValue;
+  char* base = (char*)a.scratch;
+  int* cs = (int*)(base + sc.cs);
+  int4* tab = (int4*)(base + sc.tab);
+  int* flags = (int*)(base + sc.flags);
+  float* part = (float*)(base + sc.part);
+  SLODE_LAUNCH("cohort_plan", cohort_plan_kernel, dim3(1), dim3(CM_NT), 0, stream, a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab);
+  CmK k{};
+  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay);
+  k.is_post = a.is_post; k.ns = a.num_samples; k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.sb = a.sb; k.PS = sc.partial_floats;
+  k.clip = a.clip_min;
+  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.obs = a.obs; k.members = a.members; k.cs = cs; k.tab = tab; k.flags = flags;
+  k.part = part; k.rng = a.rng; k.lab = a.lab; k.o = cm_lds(s, fwd_generic(s, a.force_generic));
+  fwd_dispatch(s, a.force_generic, [&](auto scv) { fwd_launch("cohort_moments", cohort_moments_kernel<decltype(scv)::value>, a.grid, lds, stream, k); });
+  CgK m{};
+  m.G = a.G; m.C = s.C; m.T = s.T; m.Q = k.f.Q; m.K = a.num_samples; m.has_obs = a.obs ? 1 : 0; m.PS = sc.partial_floats;
+  m.cs = cs; m.tab = tab; m.flags = flags; m.part = part;
+  m.mean = a.mean; m.sd = a.sd; m.sdb = a.sd_subjects; m.obs_mean = a.obs_mean; m.l1 = a.l1;
+  SLODE_LAUNCH("cohort_merge", cohort_merge_kernel, dim3(a.G * s.C), dim3(CM_NT), 0, stream, m);
+  return hipGetLastError();
+}

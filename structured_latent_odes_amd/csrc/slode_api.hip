@@ -845,7 +845,7 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
   return elbo_step_impl(h, s, lay, c);
 }
 
-// ---- what the eval-side calls (eval_stats, recon_moments, traj_bounds, intervene_moments, forecast_moments) share ----
+// ---- what the eval-side calls (eval_stats, recon_moments, traj_bounds, intervene_moments, forecast_moments, cohort_moments) share ----
 // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
 static int eval_grid_for(const slode_ctx* h, int B) {
   long long g = B;
@@ -1191,6 +1191,89 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
   ClockScope clock_scope(h, true);
   if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_forecast_moments(a, c.stream));
+  return SLODE_OK;
+}
+
+// ---- cohort curves: the draws of slode_recon_moments reduced by cohort (include/slode.h) ----
+// the call's own argument rungs, shared by the plan and the call (who: the speaker)
+static const char* cohort_sizes(const slode_shape* s, int M, int G, int chunk, char* why, size_t why_n) {
+  if (M < 0 || M > s->B) { snprintf(why, why_n, "M = %d out of range [0, B = %d]", M, s->B); return why; }
+  if (G < 1 || G > SLODE_COHORT_MAX_G) { snprintf(why, why_n, "G = %d out of range [1, %d]", G, SLODE_COHORT_MAX_G); return why; }
+  if (chunk < 0 || chunk > SLODE_COHORT_MAX_CHUNK) { snprintf(why, why_n, "chunk = %d out of range [0, %d]", chunk, SLODE_COHORT_MAX_CHUNK); return why; }
+  return nullptr;
+}
+
+int slode_cohort_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                      size_t* scratch_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: %s", bad);
+  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
+    return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL");
+  if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: num_samples = %d < 1", num_samples);
+  char why[128];
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: %s", why);
+  const size_t lds = slode_cohort_lds_bytes(*s, 0);
+  if (lds > SLODE_COHORT_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, six-float table, observation "
+                                       "sum, staged weights) exceed the budget of %d B", s->T, s->S, s->C, lds, SLODE_COHORT_LDS_MAX);
+  const int R = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CohortScratch sc = slode_cohort_scratch(*s, M, G, R);
+  *chunk_out = R; *n_partials = sc.n_partials; *lds_bytes = lds; *scratch_bytes = sc.bytes;
+  return SLODE_OK;
+}
+
+// Refusals first -- slode_recon_moments' for the same is_post, then the call's own; nothing launched, no draw consumed -- then, for the
+// posterior, the fold + encoder launches of a forward-only step; then cohort_plan, cohort_moments, cohort_merge.
+int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                         const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const int32_t* members,
+                         const int32_t* offsets, int M, int G, int chunk, float clip_min, float* mean, float* sd, float* sd_subjects,
+                         float* obs_mean, float* l1, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+  const EvalCall d{"slode_cohort_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
+                   "num_samples", num_samples, "; reduce recon_samples instead", "(one particle only)",
+                   is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr,
+                   is_post ? " (and no SLODE_NO_FOLD); reduce recon_samples instead" : nullptr,
+                   "step table, six-float table, observation sum, staged weights", "reduce recon_samples instead"};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "slode_cohort_moments: members / offsets is NULL with M = %d", M);
+  char why[128];
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(h, SLODE_EINVAL, "slode_cohort_moments: %s", why);
+  if (!mean) return fail(h, SLODE_EINVAL, "slode_cohort_moments: mean is NULL");
+  const bool want_obs = obs_mean || l1;
+  if (want_obs && !batch->obs) return fail(h, SLODE_EINVAL, "slode_cohort_moments: obs_mean / l1 need observations (batch->obs is NULL)");
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (want_obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))
+    return fail(h, SLODE_EINVAL, "slode_cohort_moments: observation strides (%lld, %lld, %lld) are not taken: obs_mean / l1 need dense [B,T,C] or "
+                                 "[B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
+  if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "slode_cohort_moments: scratch is NULL or not 16-byte aligned");
+  if ((rc = eval_lds(h, s, d, slode_cohort_lds_bytes(*s, h->ode_generic), SLODE_COHORT_LDS_MAX)) != SLODE_OK) return rc;
+  CohortMomentsLaunch a{};
+  a.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CohortScratch sc = slode_cohort_scratch(*s, M, G, a.chunk);
+  if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "slode_cohort_moments: scratch_bytes %zu B < required %zu B (slode_cohort_plan)", scratch_bytes, sc.bytes);
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_cohort_moments: the prior needs the label tensors of the conditional prior groups");
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
+  a.obs = want_obs ? batch->obs : nullptr; a.sb = os[0]; a.t_major = t_major && !c_major ? 1 : 0;
+  a.members = members; a.offsets = offsets; a.M = M; a.G = G; a.clip_min = clip_min;
+  a.mean = mean; a.sd = sd; a.sd_subjects = sd_subjects; a.obs_mean = obs_mean; a.l1 = l1; a.scratch = scratch;
+  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, sc.n_partials);
+  if (!is_post) {   // the prior: no encoder launches, nothing of the workspace but its size
+    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
+    a.rng = take_draws(h, batch->eps, 1);
+    ClockScope clock_scope(h, true);
+    HIP_TRY(h, slode_launch_cohort_moments(a, (hipStream_t)stream));
+    return SLODE_OK;
+  }
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.loc = p.w.loc; a.scale = p.w.scale;
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_cohort_moments(a, c.stream));
   return SLODE_OK;
 }
 

@@ -618,6 +618,47 @@ struct ForecastMomentsLaunch {
 hipError_t slode_launch_forecast_moments(const ForecastMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the window's tables do not fit the LDS
 size_t slode_forecast_lds_bytes(const slode_shape& s, int num_samples, int want_states, int window, int force_generic);
 
+// Cohort moments (cohort_moments_kernel.hip; slode_cohort_moments): the draws of ReconMomentsLaunch folded by cohort.  members [M] / offsets
+// [G + 1] on the device; chunk = R in [1, SLODE_COHORT_MAX_CHUNK] (from the plan); obs: dense rows of C*T floats (sb apart), t_major: [T][C]
+// inside a row, else [C][T], NULL: no observation sum; mean / sd / sd_subjects [Q, G, C, T], obs_mean [G, C, T], l1 [G, C] (all but mean
+// may be NULL).  scratch: slode_cohort_scratch(..).bytes, 16-byte aligned.  Launches cohort_plan, cohort_moments, cohort_merge.
+struct CohortMomentsLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *loc, *scale, *eps, *u, *obs;
+  int64_t sb;
+  const int32_t *members, *offsets;
+  float *mean, *sd, *sd_subjects, *obs_mean, *l1;
+  void* scratch;
+  float clip_min;
+  int M, G, chunk, t_major, num_samples, grid, is_post, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+// The scratch of one call (byte offsets, multiples of 16): the partial ranges cs [G + 1], the chunk table [n_partials] of 4 ints, the
+// chunks' bad-member flags [n_partials], then n_partials partials of partial_floats floats: [Q*C][5: v00, t1, t2, b1, b2][T] | obs sum [C][T].
+// n_partials = ceil(M / R) + G bounds the chunk count sum_g ceil(n_g / R) of any disjoint cohorts of M members.
+struct CohortScratch { int n_partials; long long partial_floats; size_t cs, tab, flags, part, bytes; };
+inline CohortScratch slode_cohort_scratch(const slode_shape& s, int M, int G, int R) {
+  const long long Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+  CohortScratch o{};
+  o.n_partials = (M + R - 1) / R + G;
+  o.partial_floats = ((5 * Q * s.C + s.C) * (long long)s.T + 3) & ~3LL;
+  auto pad = [](size_t ints) { return ((ints + 3) & ~(size_t)3) * sizeof(int); };
+  o.cs = 0; o.tab = o.cs + pad((size_t)G + 1); o.flags = o.tab + (size_t)o.n_partials * 16; o.part = o.flags + pad((size_t)o.n_partials);
+  o.bytes = o.part + (size_t)o.n_partials * (size_t)o.partial_floats * sizeof(float);
+  return o;
+}
+// the default chunk: a pure function of M -- the smallest power of two <= 64 with ceil(M / R) <= 1024
+inline int slode_cohort_default_chunk(int M) {
+  int R = 1;
+  while (R < SLODE_COHORT_MAX_CHUNK && (M + R - 1) / R > 1024) R <<= 1;
+  return R;
+}
+#define SLODE_COHORT_LDS_MAX (160 * 1024)   // the LDS of one CU: staged weights, step table, the six-float table and the observation sum must fit
+hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

@@ -1,5 +1,5 @@
 // The fixed-grid forward pass the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
-// intervene_moments_kernel.hip, forecast_moments_kernel.hip; no other translation unit includes this header): each phase ONCE --
+// intervene_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip; no other translation unit includes this header): each phase ONCE --
 //   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads)
 //                      and the host functions that fill them from slode_shape / slode_layout
 //   prior nets         fwd_prior_at: loc / log scale of one latent dim from the staged labels

@@ -581,6 +581,52 @@ class Engine:
                          T_out, int(window), self._p(mean), self._p(sd), self._p(x_mean), self._p(x_sd))
         return mean, sd, x_mean, x_sd
 
+    # ---- cohort curves: the draws of recon_moments reduced by cohort -------------------------------------------------------------
+    COHORT_OUTPUTS = ("sd", "sd_subjects", "obs_mean", "l1")
+
+    def cohort_plan(self, B: int, M: int, G: int, num_samples: int, chunk: int = 0):
+        """``slode_cohort_plan``: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes) of ``cohort_moments`` for
+        these sizes; host arithmetic only."""
+        r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_cohort_plan(C.byref(self.shape(B)), int(M), int(G), int(num_samples), int(chunk), C.byref(r),
+                                                          C.byref(n), C.byref(lds), C.byref(scr)))
+        return int(r.value), int(n.value), int(lds.value), int(scr.value)
+
+    def cohort_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, members, offsets, G: int, chunk: int = 0,
+                       clip_min=None, mean=None, sd=None, sd_subjects=None, obs_mean=None, l1=None, outputs=COHORT_OUTPUTS, scratch=None):
+        """slode_cohort_moments: the draws of ``recon_moments`` reduced by cohort -- ``(mean, sd, sd_subjects, obs_mean, l1)``: mean,
+        population sd over members x draws and population sd over the members' draw means of every head curve, float32 [Q, G, C, T]; the
+        members' mean observation [G, C, T]; sum_t |obs_mean - mean[0]|, [G, C].  ``members`` int32 [M] on the device: the member
+        trajectories sorted by cohort; ``offsets`` int32 [G + 1]: cohort g is members[offsets[g]:offsets[g + 1]].  ``outputs`` names the
+        optional outputs to produce (the others come back None, unless a tensor is given); ``chunk``: members folded per partial, 0 = the
+        library's choice (``cohort_plan``); ``clip_min``: values below it are replaced by it (None: off).  ``scratch``: a float32 device
+        tensor of at least the plan's scratch bytes (allocated when None).  Enqueued on the current stream.  Raises SlodeError naming the
+        reason for what the kernel does not take (everything ``recon_moments`` refuses; sizes out of range; obs_mean / l1 without dense
+        observations; LDS budget): nothing is launched and no draw is consumed then."""
+        for name, t in (("members", members), ("offsets", offsets)):
+            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("%s must be a contiguous 1-d int32 tensor on %s" % (name, self.device))
+        M, G = members.numel(), int(G)
+        if offsets.numel() != G + 1:
+            raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
+        Q, Cn = 1 if self.spec.gauss else 3, self.spec.n_channels
+        shp = (Q, G, Cn, self.T)
+        mean = self._out(mean, "mean", shp)
+        if sd is not None or "sd" in outputs:
+            sd = self._out(sd, "sd", shp)
+        if sd_subjects is not None or "sd_subjects" in outputs:
+            sd_subjects = self._out(sd_subjects, "sd_subjects", shp)
+        if obs_mean is not None or "obs_mean" in outputs:
+            obs_mean = self._out(obs_mean, "obs_mean", (G, Cn, self.T))
+        if l1 is not None or "l1" in outputs:
+            l1 = self._out(l1, "l1", (G, Cn))
+        if scratch is None:    # (sized by the library's own arithmetic; a refusal there is raised as the call's would be)
+            scratch = torch.empty((self.cohort_plan(B, M, G, max(int(num_samples), 1), chunk)[3] + 3) // 4, dtype=torch.float32, device=self.device)
+        self._batch_call(self.lib.slode_cohort_moments, params, batch, B, 1, 1 if is_post else 0, int(num_samples), self._p(members),
+                         self._p(offsets), M, G, int(chunk), float("-inf") if clip_min is None else float(clip_min), self._p(mean), self._p(sd),
+                         self._p(sd_subjects), self._p(obs_mean), self._p(l1), self._p(self._f32(scratch, "scratch")), scratch.numel() * 4)
+        return mean, sd, sd_subjects, obs_mean, l1
+
     def traj_bounds(self, params, batch: L.Batch, B: int, num_draws: int, bounds=None, loss_kb=None, particles: int = 1):
         """slode_traj_bounds: per trajectory, from ``num_draws`` posterior draws, ``bounds`` float32 [B, L.BOUND_SLOTS] = [-ELBO (mean of
         the per-draw losses), importance-weighted bound -log(1/K sum exp(-loss)), effective sample size of the weights, mean negative

@@ -400,6 +400,130 @@ class MechanisticBase(nn.Module):
         return self._save_arrays(results_dir, (("%s_%s_%s.npy" % (name, tag, kind), val)
                                                for name, moments in res.items() for kind, val in zip(("mean", "sd"), moments)))
 
+    # ---- cohort curves: the draws of recon_moments reduced by condition, as the reference's evaluation notebooks report them ----------
+    def cohort_index(self, by=None, **labels):
+        """``(ids [B] int64, keys [G, width])``: the cohort of every trajectory under the label columns named in ``by`` (default: all of
+        the family's labels, ``LABELS`` order) -- ``torch.unique(dim=0, return_inverse=True)`` over the concatenated columns, so cohort g
+        is the set of trajectories whose labels equal ``keys[g]``, keys in sorted order.  This step synchronises with the device (the
+        number of distinct rows decides a shape)."""
+        names = tuple(by) if by else tuple(self.LABELS)
+        missing = [n for n in names if n not in labels]
+        if missing or not names:
+            raise ValueError("cohort_index needs the label tensors %s (missing: %s)" % (list(names), missing))
+        B = labels[names[0]].shape[0]
+        cols = torch.cat([labels[n].reshape(B, -1).to(torch.float32) for n in names], dim=1)
+        keys, ids = torch.unique(cols, dim=0, return_inverse=True)
+        return ids.reshape(B).to(torch.int64), keys
+
+    def _cohort_lists(self, observations, cohorts, num_cohorts, labels):
+        """``(ids, keys, G, members int32 [M], offsets int32 [G + 1], count int64 [G])`` of ``cohorts``: a ``[B]`` integer tensor (negative: no
+        cohort) or a tuple of label names for ``cohort_index``; members sorted by cohort with a stable sort (batch order inside a cohort)."""
+        B, dev = observations.shape[0], observations.device
+        if torch.is_tensor(cohorts):
+            ids = cohorts.reshape(-1).to(dev, torch.int64)
+            if ids.numel() != B:
+                raise ValueError("cohorts must have B = %d entries, got %d" % (B, ids.numel()))
+            G = int(num_cohorts) if num_cohorts is not None else (int(ids.max()) + 1 if B else 0)
+            if G < 1:
+                raise ValueError("no cohort: every id is negative (pass num_cohorts to keep empty cohorts)")
+            if B and int(ids.max()) >= G:
+                raise ValueError("cohort id %d beyond num_cohorts = %d" % (int(ids.max()), G))
+            keys = torch.arange(G, device=dev).reshape(G, 1)
+        else:
+            ids, keys = self.cohort_index(by=cohorts, **labels)
+            G = keys.shape[0]
+        key = torch.where(ids < 0, torch.full_like(ids, G), ids)
+        order = torch.sort(key, stable=True).indices
+        count = torch.bincount(key, minlength=G + 1)[:G]
+        offsets = torch.cat([count.new_zeros(1), count.cumsum(0)]).to(torch.int32)
+        members = order[:int(count.sum())].to(torch.int32).contiguous()
+        return ids, keys, G, members, offsets, count
+
+    def cohort_moments(self, observations, is_post, num_samples: int, cohorts, eps=None, chunk: int = 0, clip_min=None, num_cohorts=None,
+                       **labels):
+        """Per-condition curves, as the reference's evaluation notebooks report them: for every cohort g (a set of trajectories of this
+        batch) and head curve, ``(mean, sd, sd_subjects)``, ``[G, C, T]`` each -- the mean over members x draws, the population sd over
+        members x draws, and the population sd over the members of their draw means (at ``num_samples`` = 1 the notebooks'
+        ``np.std(data[loc], 0)``) -- with ``"observations"`` ``[G, C, T]`` (the members' mean observation), ``"l1"`` ``[G, C]`` (``sum_t
+        |mean observation - mean mu_50|``, the notebooks' ``l1_error`` summand), ``"count"`` ``[G]`` and ``"keys"``.  ``cohorts``: a
+        ``[B]`` integer tensor, negative = no cohort (``num_cohorts`` keeps trailing empty cohorts), or a tuple of label names for
+        ``cohort_index`` (which synchronises).  An empty cohort is NaN throughout.  The draws are those of ``recon_moments`` (``eps``
+        ``[num_samples, B, L]`` or one drawing call); ``clip_min`` replaces head values below it (the sbio notebooks' ``mu_50[mu_50 < 0] =
+        0``).  ONE engine call (``slode_cohort_moments``); ``chunk``: members folded per partial, 0 = the library's choice.  Where the engine
+        refuses (adaptive solver, strided observations, measured arms, LDS budget, more than 1024 cohorts) the same dict is reduced from
+        ``recon_samples`` in chunks of rows in fp64."""
+        from .. import _lib as L
+        b = self._bind()
+        B, ns = observations.shape[0], int(num_samples)
+        if ns < 1:
+            raise ValueError("num_samples must be >= 1, got %d" % ns)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        ids, keys, G, members, offsets, count = self._cohort_lists(observations, cohorts, num_cohorts, labels)
+        res = {"count": count, "keys": keys}
+        try:
+            mean, sd, sdb, om, l1 = b.engine.cohort_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, members,
+                                                            offsets, G, chunk=chunk, clip_min=clip_min)
+            res.update({n: (mean[q], sd[q], sdb[q]) for q, n in enumerate(names)})
+            res.update(observations=om, l1=l1)
+            return res
+        except L.SlodeError as err:
+            self._raise_unless_refused(err)
+        res.update(self._cohort_composed(observations, is_post, ns, ids, G, count, eps, clip_min, labels))
+        return res
+
+    def _cohort_composed(self, observations, is_post, ns, ids, G, count, eps, clip_min, labels):
+        """The composed route: ``recon_samples`` of ``MOMENTS_CHUNK_ROWS // ns`` rows at a time (ONE drawing call for the whole batch, sliced
+        per chunk), every row's draw mean and sum of squares added to its cohort's fp64 sums."""
+        B, dev = observations.shape[0], observations.device
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        if eps is None:
+            eps = self._bind().engine.draw_normal(ns * B).view(ns, B, -1)
+        eps = eps.reshape(ns, B, -1)
+        Cn, T = observations.shape[1], observations.shape[2]
+        slot = torch.where(ids < 0, torch.full_like(ids, G), ids)           # (bucket G: the trajectories of no cohort)
+        s1 = {n: torch.zeros(G + 1, Cn, T, dtype=torch.float64, device=dev) for n in names}
+        sb2 = {n: torch.zeros_like(s1[n]) for n in names}
+        sv2 = {n: torch.zeros_like(s1[n]) for n in names}
+        so = torch.zeros(G + 1, Cn, T, dtype=torch.float64, device=dev).index_add_(0, slot, observations.to(torch.float64))
+        rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
+        for lo in range(0, B, rows):
+            hi = min(B, lo + rows)
+            got = self.recon_samples(observations[lo:hi], is_post, ns, eps=eps[:, lo:hi], **{k: v[lo:hi] for k, v in labels.items()})
+            for n in names:
+                v = got[n].to(torch.float64)                                # [rows, C, T, ns]
+                if clip_min is not None:
+                    v = torch.where(v < clip_min, torch.full_like(v, float(clip_min)), v)
+                mb = v.mean(dim=-1)
+                s1[n].index_add_(0, slot[lo:hi], mb)
+                sb2[n].index_add_(0, slot[lo:hi], mb * mb)
+                sv2[n].index_add_(0, slot[lo:hi], (v * v).sum(dim=-1))
+            del got
+        cnt = count.to(torch.float64).reshape(G, 1, 1)
+        nan = torch.full((G, Cn, T), float("nan"), dtype=torch.float64, device=dev)
+        live = (cnt > 0).expand(G, Cn, T)
+        res = {}
+        for n in names:
+            mean = s1[n][:G] / cnt
+            sd = (sv2[n][:G] / (cnt * ns) - mean * mean).clamp_min(0).sqrt()
+            sdb = (sb2[n][:G] / cnt - mean * mean).clamp_min(0).sqrt()
+            res[n] = tuple(torch.where(live, x, nan).to(torch.float32) for x in (mean, sd, sdb))
+        res["observations"] = torch.where(live, so[:G] / cnt, nan).to(torch.float32)
+        res["l1"] = (res["observations"].to(torch.float64) - res[names[0]][0].to(torch.float64)).abs().sum(dim=-1).to(torch.float32)
+        return res
+
+    def save_cohort_moments(self, results_dir: str, observations, is_post, num_samples: int, cohorts, **labels):
+        """Writes ``<curve>_<post|prior>_cohort_{mean,sd,sd_subjects}.npy`` (``[G, C, T]`` each) for every head curve,
+        ``observations_cohort_mean.npy``, ``cohort_keys.npy``, ``cohort_count.npy`` and ``l1_<post|prior>_cohort.npy``; returns the paths."""
+        return self._save_arrays(results_dir, self._cohort_named(self.cohort_moments(observations, is_post, num_samples, cohorts, **labels), is_post))
+
+    def _cohort_named(self, res, is_post):
+        """``(file name, tensor)`` of every array of a ``cohort_moments`` result, under ``save_cohort_moments``' names."""
+        tag = "post" if is_post else "prior"
+        named = [("%s_%s_cohort_%s.npy" % (name, tag, kind), val) for name in self.MOMENT_HEADS[bool(self.GAUSS)]
+                 for kind, val in zip(("mean", "sd", "sd_subjects"), res[name])]
+        return named + [("observations_cohort_mean.npy", res["observations"]), ("cohort_keys.npy", res["keys"]),
+                        ("cohort_count.npy", res["count"]), ("l1_%s_cohort.npy" % tag, res["l1"])]
+
     # ---- forecast: the same draws, solved on an output grid of the caller's -- past the observed window, or finer than the training grid ----
     def horizon_times(self, extra_steps: int, refine: int = 1) -> torch.Tensor:
         """The training grid with each interval split in ``refine`` equal parts, followed by ``extra_steps`` steps of the (refined) last

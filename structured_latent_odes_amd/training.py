@@ -111,7 +111,7 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
-          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0):
+          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -123,7 +123,10 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     ``bounds_post.npy`` [n, 4]; 0 (the default): no such stage runs.
     forecast_steps = N > 0: after training, the best model's posterior forecast over the validation loader on ``horizon_times(N)`` -- the
     training grid and N more steps of its last spacing -- mean and sd over config.num_samples draws per curve, the trajectories in loader
-    order, written to ``results_dir`` under ``save_forecast_moments``' file names; 0 (the default): no such stage runs."""
+    order, written to ``results_dir`` under ``save_forecast_moments``' file names; 0 (the default): no such stage runs.
+    cohort_curves: after training, the per-condition curves of the reference's evaluation notebooks on the first test batch -- cohorts
+    from all of the family's labels, posterior and prior, config.num_samples draws (``save_cohort_moments``) -- and the notebooks' number,
+    printed as ``l1_error_post`` / ``l1_error_prior``: the mean of ``l1`` over non-empty cohorts and channels; off by default."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -199,6 +202,15 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
         for is_post in (True, False):
             written = best_model.save_recon_moments(out_dir, is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), **d)
             logging.debug("multiple_samples moments: %s", written)
+    if cohort_curves:
+        d = batch_to_device(next(iter(test_b)), device, family)
+        out_dir = results_dir or "results_%s" % config.model
+        for is_post in (True, False):
+            res = best_model.cohort_moments(is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), cohorts=tuple(best_model.LABELS), **d)
+            written = best_model._save_arrays(out_dir, best_model._cohort_named(res, is_post))
+            line = "l1_error_%s: %s" % ("post" if is_post else "prior", float(res["l1"][res["count"] > 0].mean()))
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if test_bounds:
         path = best_model.save_trajectory_bounds(results_dir or "results_%s" % config.model,
                                                  (batch_to_device(b, device, family) for b in val_b), int(test_bounds))
@@ -272,6 +284,9 @@ def build_parser():
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
+    ap.add_argument("--cohort-curves", action="store_true",
+                    help="after training: per-condition mean / sd curves, mean observations and the evaluation notebooks' l1_error on the first "
+                         "test batch, posterior and prior (save_cohort_moments)")
     return ap
 
 
@@ -288,6 +303,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["test_bounds"] = a.test_bounds
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
+    if a.cohort_curves:
+        kw["cohort_curves"] = True
     if a.data_dir:
         got = real_batches(config, family, a.data_dir)
         kw["train_batches"], kw["val_batches"], kw["times"] = got[:3]

@@ -1,0 +1,129 @@
+// Every refusing configuration of slode_cohort_moments, on a hand-filled handle: no slode_create, no HIP call, no device.  One line per case:
+//   <case> | <status> | <rng_counter afterwards> | <slode_last_error>
+// tests/test_cohort_cpu.py holds the expected status and the words each message must carry.  No refusal touches HIP and a refused call
+// launches nothing, so this program makes NO call that would be taken: a taken call would launch.
+// Build (host pass only): hipcc -x hip --cuda-host-only -std=c++17 cohort_refusals.cpp -x none <package dir>/libslode.so
+#include "../../structured_latent_odes_amd/csrc/slode_common.h"
+
+#include <functional>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+alignas(64) static float g_mem[64];   // stands for every device buffer: non-NULL, never read or written
+static float* const DEV = g_mem;
+static const size_t BIG = (size_t)1 << 40;   // workspace and scratch are "large enough" unless a case says otherwise
+
+struct Cfg {
+  slode_ctx ctx;
+  slode_shape s;
+  slode_batch b;
+  bool no_handle = false, no_shape = false, no_layout = false, no_params = false, no_batch = false;
+  const float *times = DEV, *stage_t = DEV;
+  const int32_t *members = (const int32_t*)DEV, *offsets = (const int32_t*)DEV;
+  float *mean = DEV, *sd = DEV, *sdb = DEV, *obs_mean = DEV, *l1 = DEV;
+  void *ws = DEV, *scratch = DEV;
+  size_t ws_bytes = BIG, scratch_bytes = BIG;
+  int draws = 2, is_post = 1, M = 3, G = 2, chunk = 0;
+};
+
+// B = 4, T = 86, C = 3 with the cvs prior groups (tests/eval_refusals/eval_refusals.cpp), dense [B,T,C] observations, two label tensors
+static Cfg base() {
+  Cfg c;
+  memset(&c.ctx, 0, sizeof(c.ctx));
+  c.ctx.num_cu = 256; c.ctx.enc_fuse = 1; c.ctx.rng_seed = 3;
+  memset(&c.s, 0, sizeof(c.s));
+  c.s.B = 4; c.s.T = 86; c.s.C = 3; c.s.L = 8; c.s.S = 5; c.s.H = 25; c.s.F = 10; c.s.K = 10; c.s.P = 5; c.s.Hc = 50;
+  c.s.n_u = 2; c.s.n_groups = 2; c.s.groups[0] = slode_group{0, 3, 0, 1}; c.s.groups[1] = slode_group{3, 3, 1, 1};
+  c.s.method = SLODE_RK4; c.s.likelihood = SLODE_ALD; c.s.quantile_diff = 0.475f; c.s.rtol = 1e-7f; c.s.atol = 1e-9f;
+  memset(&c.b, 0, sizeof(c.b));
+  c.b.obs = DEV; c.b.obs_strides[0] = (int64_t)c.s.C * c.s.T; c.b.obs_strides[1] = 1; c.b.obs_strides[2] = c.s.C;
+  c.b.n_labels = 2; c.b.label_width[0] = c.b.label_width[1] = 1; c.b.labels[0] = c.b.labels[1] = DEV;
+  return c;
+}
+
+static void run(const char* name, Cfg c) {
+  slode_layout lay;
+  slode_shape plain = base().s;   // (the layout of the unmodified shape where the case's own shape is not a valid one)
+  if (slode_layout_init(&c.s, &lay) != SLODE_OK) slode_layout_init(&plain, &lay);
+  c.ctx.rng_counter = 7;
+  slode_handle h = c.no_handle ? nullptr : &c.ctx;
+  const int rc = slode_cohort_moments(h, c.no_shape ? nullptr : &c.s, c.no_layout ? nullptr : &lay, c.no_params ? nullptr : DEV, c.times,
+                                      c.stage_t, c.no_batch ? nullptr : &c.b, c.is_post, c.draws, c.members, c.offsets, c.M, c.G, c.chunk,
+                                      -INFINITY, c.mean, c.sd, c.sdb, c.obs_mean, c.l1, c.scratch, c.scratch_bytes, c.ws, c.ws_bytes, nullptr);
+  printf("%s | %d | %llu | %s\n", name, rc, (unsigned long long)c.ctx.rng_counter, slode_last_error(h));
+}
+
+typedef std::function<void(Cfg&)> Edit;
+static void one(const char* name, const Edit& edit) { Cfg c = base(); edit(c); run(name, c); }
+// posterior and prior
+static void both(const char* name, const Edit& edit) {
+  char n[128];
+  for (int post : {1, 0}) {
+    snprintf(n, sizeof(n), "%s: %s", post ? "post" : "prior", name);
+    Cfg c = base(); c.is_post = post; edit(c); run(n, c);
+  }
+}
+
+int main() {
+  // ---- what slode_recon_moments refuses for the same is_post, in its order
+  both("handle NULL", [](Cfg& c) { c.no_handle = true; });
+  both("shape NULL", [](Cfg& c) { c.no_shape = true; });
+  both("layout NULL", [](Cfg& c) { c.no_layout = true; });
+  both("params NULL", [](Cfg& c) { c.no_params = true; });
+  both("batch NULL", [](Cfg& c) { c.no_batch = true; });
+  both("times NULL", [](Cfg& c) { c.times = nullptr; });
+  both("stage_t NULL", [](Cfg& c) { c.stage_t = nullptr; });
+  both("workspace NULL", [](Cfg& c) { c.ws = nullptr; });
+  both("bad shape", [](Cfg& c) { c.s.T = 1; });
+  both("draws 0", [](Cfg& c) { c.draws = 0; });
+  both("draws 2^30", [](Cfg& c) { c.draws = 1 << 30; });
+  for (int m : {SLODE_DOPRI5, SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN}) {
+    char name[64];
+    snprintf(name, sizeof(name), "adaptive method %d", m);
+    both(name, [m](Cfg& c) { c.s.method = m; });
+  }
+  both("particles 2", [](Cfg& c) { c.s.particles = 2; });
+  both("fold_on", [](Cfg& c) { c.ctx.fold_on = 1; });
+  both("ode_pack", [](Cfg& c) { c.ctx.ode_pack = 4; });
+  both("ode_alg", [](Cfg& c) { c.ctx.ode_alg = 1; });
+  one("post: obs NULL", [](Cfg& c) { c.b.obs = nullptr; });
+  one("post: padded strides", [](Cfg& c) { c.b.obs_strides[0] += 8; });
+  one("post: no_fold", [](Cfg& c) { c.ctx.no_fold = 1; });
+  // ---- the call's own rungs
+  both("members NULL", [](Cfg& c) { c.members = nullptr; });
+  both("offsets NULL", [](Cfg& c) { c.offsets = nullptr; });
+  both("M -1", [](Cfg& c) { c.M = -1; });
+  both("M B + 1", [](Cfg& c) { c.M = 5; });
+  both("G 0", [](Cfg& c) { c.G = 0; });
+  both("G 1025", [](Cfg& c) { c.G = 1025; });
+  both("chunk -1", [](Cfg& c) { c.chunk = -1; });
+  both("chunk 65", [](Cfg& c) { c.chunk = 65; });
+  both("mean NULL", [](Cfg& c) { c.mean = nullptr; });
+  one("prior: obs_mean without observations", [](Cfg& c) { c.is_post = 0; c.b.obs = nullptr; c.l1 = nullptr; });
+  one("prior: l1 without observations", [](Cfg& c) { c.is_post = 0; c.b.obs = nullptr; c.obs_mean = nullptr; });
+  one("prior: obs_mean with padded strides", [](Cfg& c) { c.is_post = 0; c.b.obs_strides[0] += 8; });
+  one("prior: l1 with strides of another T", [](Cfg& c) { c.is_post = 0; c.obs_mean = nullptr; c.b.obs_strides[1] = c.s.T + 1; c.b.obs_strides[2] = 1; });
+  both("scratch NULL", [](Cfg& c) { c.scratch = nullptr; });
+  both("scratch misaligned", [](Cfg& c) { c.scratch = (char*)DEV + 4; });
+  both("T 1024: the LDS tables", [](Cfg& c) { c.s.T = 1024; c.b.obs_strides[0] = 3 * 1024; c.scratch_bytes = 64; });
+  both("scratch too small", [](Cfg& c) { c.scratch_bytes = 64; });
+  // ---- the label tensors, the workspace
+  both("label columns 3, n_u 2", [](Cfg& c) { c.b.label_width[1] = 2; });
+  one("prior without labels", [](Cfg& c) { c.is_post = 0; c.b.n_labels = 0; });
+  both("workspace too small", [](Cfg& c) { c.ws_bytes = 64; });
+  // ---- two conditions at once: the earlier check of the ladder names the reason; a slode_recon_moments refusal before a cohort-only one
+  both("adaptive + G 0", [](Cfg& c) { c.s.method = SLODE_DOPRI5; c.G = 0; });
+  both("draws 0 + mean NULL", [](Cfg& c) { c.draws = 0; c.mean = nullptr; });
+  both("particles 2 + chunk 65", [](Cfg& c) { c.s.particles = 2; c.chunk = 65; });
+  one("post: padded strides + members NULL", [](Cfg& c) { c.b.obs_strides[0] += 8; c.members = nullptr; });
+  both("members NULL + M -1", [](Cfg& c) { c.members = nullptr; c.M = -1; });
+  both("M 5 + G 0", [](Cfg& c) { c.M = 5; c.G = 0; });
+  both("G 0 + chunk 65", [](Cfg& c) { c.G = 0; c.chunk = 65; });
+  both("chunk 65 + mean NULL", [](Cfg& c) { c.chunk = 65; c.mean = nullptr; });
+  both("scratch too small + workspace too small", [](Cfg& c) { c.scratch_bytes = 64; c.ws_bytes = 64; });
+  // ---- taken by the ladder up to the first launch is not tested here; M = 0 with NULL lists is no refusal of the argument rungs:
+  //      the scratch rung behind them speaks
+  both("M 0 with NULL lists, scratch too small", [](Cfg& c) { c.M = 0; c.members = nullptr; c.offsets = nullptr; c.scratch_bytes = 0; });
+  return 0;
+}
