@@ -6,11 +6,10 @@
 //                   [cs[g], cs[g + 1]) by a block scan over ceil(n_g / R); offsets are clamped to [0, M], a decreasing pair is an empty cohort
 //   cohort_moments  one workgroup of four waves folds one chunk -- R consecutive members of ONE cohort -- at a time (persistent loop over
 //                   the chunk ids) and writes one partial:
-//     M0  once per workgroup: the staged weights of slode_forward.h
-//     per member: M1 loc / scale of the posterior or of the prior nets on the member's labels; its observations added into [C][T]
-//     per draw:   M2-M5 the shared phases, as recon_moments_kernel runs them
+//     M0-M5 are the draw loop of slode_forward.h, a member in the place of recon_moments_kernel's trajectory; per member its
+//     observations are also added into [C][T]
 //     M6' thread <-> time point: per (q, c) the value v (clipped) updates six floats in the LDS, shifted by v00, the chunk's first
-//         member's first draw: t1 += dv, t2 += dv^2 (all values), m1 += dv (this member); after the member's last draw mb = m1 / K,
+//         member's first draw: t1 += dv, t2 += dv^2 (all values: fwd_moment_add), m1 += dv (this member); after the member's last draw mb = m1 / K,
 //         b1 += mb, b2 += mb^2, m1 = 0 -- never a sum of v^2
 //     the partial: v00, t1, t2, b1, b2 per value and the observation sum, plain per-lane stores, t contiguous, by the values' owner threads
 //   cohort_merge    one workgroup per (cohort, channel), thread <-> time point: walks the cohort's partials in slot order, each as (count,
@@ -27,22 +26,19 @@ constexpr int CM_NT = FWD_NT;
 
 // offsets (in floats, multiples of 4) of the pieces of the dynamic LDS region: the shared ones, then the six-float table [Q*C][6][T], the
 // observation sum [C][T] and loc / scale
-struct CmLds { FwdLds f; int acc, obs, loc, sc, total; };
+struct CmLds { FwdLds f; int acc, obs; LocScLds ls; int total; };
 
 struct CmK {
-  FwdK f;
-  PriorK pr;
-  int is_post, ns, M, G, t_major;
+  DrawsK d;
+  int M, G, t_major;
   long long sb, PS;   // floats between observation rows; floats of one partial
   float clip;
-  const float *loc, *scale, *eps, *u, *obs;
+  const float* obs;
   const int *members, *cs;
   const int4* tab;
   int* flags;
   float* part;
   CmLds o;
-  RngK rng;
-  LabelSrc lab;
 };
 
 // ---- cohort_plan ----------------------------------------------------------------------------------------------------
@@ -95,20 +91,18 @@ template <int SC>
 __global__ void __launch_bounds__(CM_NT) cohort_moments_kernel(const CmK k) {
   constexpr int SM = SC ? SC : SLODE_MAX_S;
   extern __shared__ __attribute__((aligned(16))) float s_cm[];
-  const FwdK& f = k.f;
-  const float* __restrict__ par = f.params;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, H = f.H, C = f.C, NS = T - 1, QC = f.Q * C, ns = k.ns, CT = C * T;
+  const FwdK& f = k.d.f;
+  const int tid = threadIdx.x;
+  const int T = f.T, S = SC ? SC : f.S, C = f.C, QC = f.Q * C, ns = k.d.ns, CT = C * T;
   const int NCH = k.cs[k.G];
   if ((int)blockIdx.x >= NCH) return;   // (the grid is sized by the bound ceil(M / R) + G)
   const FwdSm sm = fwd_sm(s_cm, k.o.f);
   float* s_acc = s_cm + k.o.acc;   // [Q*C][6: v00, t1, t2, m1, b1, b2][T]
   float* s_obs = s_cm + k.o.obs;   // [C][T]
-  float* s_loc = s_cm + k.o.loc;
-  float* s_sc = s_cm + k.o.sc;
+  float* s_loc = s_cm + k.o.ls.loc;
+  float* s_sc = s_cm + k.o.ls.sc;
 
-  // ---- M0: the weights every draw reuses ----
-  fwd_stage_weights<SM>(f, sm, S, tid);
+  fwd_stage_weights<SM>(f, sm, S, tid);   // M0
 
   for (int i = blockIdx.x; i < NCH; i += gridDim.x) {
     const int4 ch = k.tab[i];   // cohort, first position, length
@@ -122,54 +116,28 @@ __global__ void __launch_bounds__(CM_NT) cohort_moments_kernel(const CmK k) {
       const int pos = min(max(ch.y + j, 0), k.M - 1);
       const int b = k.members[pos];
       if (b < 0 || b >= f.B) { bad = 1; continue; }   // (workgroup-uniform: never an address)
-      // ---- M1 ----
-      __syncthreads();   // (M0's writes; the previous member's readers of s_u / s_loc / s_sc)
-      if (!k.is_post && k.pr.n_groups > 0 && tid < k.pr.nu) sm.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
-      __syncthreads();
-      if (tid < L) {
-        const int l = tid;
-        float loc, sc;
-        if (k.is_post) {
-          loc = k.loc[(long long)b * L + l]; sc = k.scale[(long long)b * L + l];
-        } else {
-          float pl, pls;
-          fwd_prior_at(k.pr, par, sm.u, l, pl, pls);
-          loc = pl; sc = expf(pls);
-        }
-        s_loc[l] = loc; s_sc[l] = sc;
-      }
+      fwd_draw_source(k.d, sm, s_loc, s_sc, b, tid);   // M1
       if (k.obs) {
         const float* __restrict__ y = k.obs + (long long)b * k.sb;   // (dense row: consecutive lanes, consecutive addresses)
         for (int e = tid; e < CT; e += CM_NT) s_obs[k.t_major ? (e % C) * T + e / C : e] += y[e];
       }
       for (int kk = 0; kk < ns; ++kk) {
-        // ---- M2: draw kk = row kk * B + b of the call's noise ----
-        if (tid < L) sm.z[tid] = fmaf(s_sc[tid], slode_eps_at(k.rng, k.eps, (long long)kk * f.B + b, L, tid), s_loc[tid]);
+        fwd_draw_z(k.d, sm, s_loc, s_sc, kk, b, tid);   // M2
         __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] are done)
-        // ---- M3 - M5 ----
-        fwd_init_state<SM>(sm, H, L, S, tid);
-        fwd_step_table_staged<SM>(f, sm, S, tid);
-        __syncthreads();
-        fwd_scan(sm.A, sm.B, sm.x0, S, NS, lane, wave, CM_NT / 64);
-        __syncthreads();
+        fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // M3 - M5
         // ---- M6': head values of the thread's time points into the six-float table ----
         const bool init = first && kk == 0, last = kk == ns - 1;
         for (int t = tid; t < T; t += CM_NT) {
           float x[SM];
-#pragma unroll
-          for (int s = 0; s < SM; ++s) x[s] = s < S ? (t == 0 ? sm.x0[s] : sm.A[(t - 1) * S + s]) : 0.f;
+          fwd_state_at<SM>(sm, S, t, x);
           for (int qc = 0; qc < QC; ++qc) {
-            float v = 0.f;
-#pragma unroll
-            for (int s = 0; s < SM; ++s) if (s < S) v = fmaf(sm.hw[qc * S + s], x[s], v);
+            float v = fwd_head_value<SM>(sm, S, qc, x);
             if (v < k.clip) v = k.clip;   // (a comparison: NaN stays NaN)
             float* m = s_acc + (qc * 6) * T + t;
-            float m1;
-            if (init) { m[0] = v; m[T] = 0.f; m[2 * T] = 0.f; m[4 * T] = 0.f; m[5 * T] = 0.f; m1 = 0.f; }
-            else {
-              const float dv = v - m[0];
-              m[T] += dv; m[2 * T] = fmaf(dv, dv, m[2 * T]); m1 = m[3 * T] + dv;
-            }
+            const float dv = fwd_moment_add(m, T, init, v);   // slots 0 - 2: v00, t1, t2
+            float m1 = 0.f;
+            if (init) { m[4 * T] = 0.f; m[5 * T] = 0.f; }
+            else m1 = m[3 * T] + dv;
             if (last) {
               const float mb = m1 / (float)ns;
               m[4 * T] += mb; m[5 * T] = fmaf(mb, mb, m[5 * T]); m1 = 0.f;
@@ -268,7 +236,7 @@ CmLds cm_lds(const slode_shape& s, bool generic) {
   LdsCarve cv;
   CmLds o{};
   o.f = fwd_lds(cv, s, generic);
-  o.acc = cv.take(Q * s.C * 6 * s.T); o.obs = cv.take(s.C * s.T); o.loc = cv.take(s.L); o.sc = cv.take(s.L);
+  o.acc = cv.take(Q * s.C * 6 * s.T); o.obs = cv.take(s.C * s.T); o.ls = fwd_lds_loc_sc(cv, s);
   o.total = cv.n;
   return o;
 }
@@ -280,11 +248,10 @@ size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic) {
 }
 
 hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
+  const slode_shape& s = a.d.s;
   const CohortScratch sc = slode_cohort_scratch(s, a.M, a.G, a.chunk);
-  const size_t lds = slode_cohort_lds_bytes(s, a.force_generic);
-  if (lds > SLODE_COHORT_LDS_MAX || a.num_samples < 1 || a.grid < 1 || a.chunk < 1 || a.chunk > SLODE_COHORT_MAX_CHUNK || a.G < 1 ||
+  const size_t lds = slode_cohort_lds_bytes(s, a.d.force_generic);
+  if (lds > SLODE_COHORT_LDS_MAX || a.d.num_samples < 1 || a.d.grid < 1 || a.chunk < 1 || a.chunk > SLODE_COHORT_MAX_CHUNK || a.G < 1 ||
       a.G > SLODE_COHORT_MAX_G || a.M < 0 || a.M > s.B || !a.mean || !a.scratch || (a.M > 0 && (!a.members || !a.offsets)))
     return hipErrorInvalidValue;
   char* base = (char*)a.scratch;
@@ -294,14 +261,13 @@ hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t
   float* part = (float*)(base + sc.part);
   SLODE_LAUNCH("cohort_plan", cohort_plan_kernel, dim3(1), dim3(CM_NT), 0, stream, a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab);
   CmK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay);
-  k.is_post = a.is_post; k.ns = a.num_samples; k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.sb = a.sb; k.PS = sc.partial_floats;
-  k.clip = a.clip_min;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.obs = a.obs; k.members = a.members; k.cs = cs; k.tab = tab; k.flags = flags;
-  k.part = part; k.rng = a.rng; k.lab = a.lab; k.o = cm_lds(s, fwd_generic(s, a.force_generic));
-  fwd_dispatch(s, a.force_generic, [&](auto scv) { fwd_launch("cohort_moments", cohort_moments_kernel<decltype(scv)::value>, a.grid, lds, stream, k); });
+  fwd_fill(k.d, a.d);
+  k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.sb = a.sb; k.PS = sc.partial_floats; k.clip = a.clip_min;
+  k.obs = a.obs; k.members = a.members; k.cs = cs; k.tab = tab; k.flags = flags; k.part = part;
+  k.o = cm_lds(s, fwd_generic(s, a.d.force_generic));
+  fwd_dispatch(s, a.d.force_generic, [&](auto scv) { fwd_launch("cohort_moments", cohort_moments_kernel<decltype(scv)::value>, a.d.grid, lds, stream, k); });
   CgK m{};
-  m.G = a.G; m.C = s.C; m.T = s.T; m.Q = k.f.Q; m.K = a.num_samples; m.has_obs = a.obs ? 1 : 0; m.PS = sc.partial_floats;
+  m.G = a.G; m.C = s.C; m.T = s.T; m.Q = k.d.f.Q; m.K = a.d.num_samples; m.has_obs = a.obs ? 1 : 0; m.PS = sc.partial_floats;
   m.cs = cs; m.tab = tab; m.flags = flags; m.part = part;
   m.mean = a.mean; m.sd = a.sd; m.sdb = a.sd_subjects; m.obs_mean = a.obs_mean; m.l1 = a.l1;
   SLODE_LAUNCH("cohort_merge", cohort_merge_kernel, dim3(a.G * s.C), dim3(CM_NT), 0, stream, m);

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(EV_NT) eval_stats_kernel(const EvalK k) {
     {
       const int q = wave >> 1;
       const float* uh = s_uh + q * SLODE_MAX_H;
-      fwd_step_table<SM>(f, S, tid & 127, 128, s_A + q * NS * S, s_B + q * NS * S,
+      fwd_step_table<SM>(f, S, 0, NS, tid & 127, 128, s_A + q * NS * S, s_B + q * NS * S,
                          [&](float t, float (&a)[SM], float (&d)[SM]) { eval_ad<SM>(f, par, uh, t, S, a, d); });
     }
     __syncthreads();

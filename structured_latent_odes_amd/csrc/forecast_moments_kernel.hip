@@ -15,6 +15,8 @@
 // Every (q, c, t) and (s, t) has ONE owner thread, which sees the draws in the order k = 0 .. ns - 1: no atomics, no merge; the result is a
 // function of (parameters, inputs, noise, output grid, W) alone, bitwise reproducible and independent of the launch grid.  W decides which
 // scan chunk a step falls into, i.e. how the affine maps are associated: two windows agree to fp32 rounding, not bitwise.
+// (This kernel keeps its own text of M1, M2, M6, M7 and of the M3-M5 sequence: written through the draw-loop routines of slode_forward.h it
+// measured 2-3 % slower wherever a t loop takes more than one thread round -- DESIGN 3.13.  The step table is the shared one.)
 #include "slode_forward.h"
 
 namespace {
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(FC_NT) forecast_moments_kernel(const FcK k) {
         // ---- M3: u = W_z z + b_h into the units' rows; the init net's hidden layer; x0 ----
         fwd_init_state<SM>(sm, H, L, S, tid);
         // ---- M4: step coefficients of the window's steps ----
-        fwd_step_table_range_staged<SM>(f, sm, S, n_lo, n_hi, tid);
+        fwd_step_table_staged<SM>(f, sm, S, n_lo, n_hi, tid);
         __syncthreads();
         // ---- M5: forward affine scan of the window, in place: x[n_lo + i + 1][s] takes the slot of A[i][s] ----
         fwd_scan(sm.A, sm.B, n_lo == 0 ? sm.x0 : s_carry + kk * S, S, nw, lane, wave, FC_NT / 64);
@@ -162,19 +164,19 @@ size_t slode_forecast_lds_bytes(const slode_shape& s, int num_samples, int want_
 }
 
 hipError_t slode_launch_forecast_moments(const ForecastMomentsLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
-  if (a.num_samples < 1 || a.grid < 1 || a.T_out < 2 || a.window < 1 || a.window > a.T_out - 1 || !a.mean) return hipErrorInvalidValue;
+  const DrawsLaunch& d = a.d;
+  const slode_shape& s = d.s;
+  if (d.num_samples < 1 || d.grid < 1 || a.T_out < 2 || a.window < 1 || a.window > a.T_out - 1 || !a.mean) return hipErrorInvalidValue;
   const int states = (a.x_mean || a.x_sd) ? 1 : 0;
-  const size_t lds = slode_forecast_lds_bytes(s, a.num_samples, states, a.window, a.force_generic);
+  const size_t lds = slode_forecast_lds_bytes(s, d.num_samples, states, a.window, d.force_generic);
   if (lds > SLODE_FORECAST_LDS_MAX) return hipErrorInvalidValue;
   FcK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times_out, a.stage_t_out); fwd_fill(k.pr, s, lay);
+  fwd_fill(k.f, s, d.lay, d.params, d.times, d.stage_t); fwd_fill(k.pr, s, d.lay);
   k.f.T = a.T_out;
-  k.is_post = a.is_post; k.ns = a.num_samples; k.W = a.window; k.states = states;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u;
-  k.mean = a.mean; k.sd = a.sd; k.x_mean = a.x_mean; k.x_sd = a.x_sd; k.rng = a.rng; k.lab = a.lab;
-  k.o = fc_lds(s, a.num_samples, states, a.window, fwd_generic(s, a.force_generic));
-  fwd_dispatch(s, a.force_generic, [&](auto sc) { fwd_launch("forecast_moments", forecast_moments_kernel<decltype(sc)::value>, a.grid, lds, stream, k); });
+  k.is_post = d.is_post; k.ns = d.num_samples; k.W = a.window; k.states = states;
+  k.loc = d.loc; k.scale = d.scale; k.eps = d.eps; k.u = d.u;
+  k.mean = a.mean; k.sd = a.sd; k.x_mean = a.x_mean; k.x_sd = a.x_sd; k.rng = d.rng; k.lab = d.lab;
+  k.o = fc_lds(s, d.num_samples, states, a.window, fwd_generic(s, d.force_generic));
+  fwd_dispatch(s, d.force_generic, [&](auto sc) { fwd_launch("forecast_moments", forecast_moments_kernel<decltype(sc)::value>, d.grid, lds, stream, k); });
   return hipGetLastError();
 }

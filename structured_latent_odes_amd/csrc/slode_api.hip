@@ -940,6 +940,62 @@ static int forward_encode(Step& p, int draws, RngK* rng) {
   return step_encode(p, fl, &enc_fused);
 }
 
+// ---- the calls that walk num_samples draws per trajectory from one source (recon, forecast, cohort; intervene: the posterior alone) ----
+// Their EvalCall: the refusal texts differ by the call's name, its advice ("reduce recon_samples instead") and what its LDS figure counts
+// (nullptr: the call has an LDS rung of its own); the observation rungs exist for the posterior alone.
+struct DrawsCall : EvalCall {
+  char adaptive[80], strides[112];
+  DrawsCall(const char* name_, const char* pointers_, bool missing_, int num_samples, int is_post, const char* advice, const char* tables) : EvalCall{} {
+    snprintf(adaptive, sizeof(adaptive), "; %s", advice);
+    snprintf(strides, sizeof(strides), " (and no SLODE_NO_FOLD); %s", advice);
+    name = name_; pointers = pointers_; missing = missing_; draws_noun = "num_samples"; draws = num_samples;
+    adaptive_tail = adaptive; one_particle = "(one particle only)";
+    obs_null = is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr;
+    strides_tail = is_post ? strides : nullptr;
+    lds_tables = tables; lds_advice = tables ? advice : nullptr;
+  }
+  DrawsCall(const DrawsCall&) = delete;
+};
+// the label tensors of the batch; the prior reads them through the conditional prior nets
+static int draws_labels(slode_handle h, const slode_shape* s, const slode_batch* batch, const EvalCall& d, int is_post, LabelSrc* lab) {
+  const int rc = batch_labels(h, s, batch, lab);
+  if (rc != SLODE_OK) return rc;
+  if (!is_post && s->n_groups > 0 && lab->n == 0) return fail(h, SLODE_EINVAL, "%s: the prior needs the label tensors of the conditional prior groups", d.name);
+  return SLODE_OK;
+}
+// everything of DrawsLaunch but lab (draws_labels) and loc / scale / rng (draws_run); items: what the persistent grid walks
+static void draws_fill(DrawsLaunch& a, slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                       const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int items) {
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
+  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, items);
+}
+// The tail: launch(stream) runs the call's own kernel(s) on a.  The prior: no observations, no encoder launches, nothing of the workspace but
+// its size.  The posterior: the fold + encoder launches of a forward-only step on the training grid times / stage_t, which leave loc /
+// scale in the workspace.  Either way the one drawing call is counted once nothing can refuse the call any more.
+extern "C++" template <class Launch>
+static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* lay, const EvalCall& d, DrawsLaunch& a, const float* times,
+                     const float* stage_t, const slode_batch* batch, void* workspace, size_t workspace_bytes, void* stream, Launch&& launch) {
+  auto run = [&](hipStream_t st) {
+    const hipError_t e = launch(st);
+    return e == hipSuccess ? SLODE_OK : fail(h, SLODE_EHIP, "%s: launch: %s", d.name, hipGetErrorString(e));
+  };
+  if (!a.is_post) {
+    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
+    a.rng = take_draws(h, batch->eps, 1);
+    ClockScope clock_scope(h, true);
+    return run((hipStream_t)stream);
+  }
+  const StepCall c = forward_call(a.params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  int rc = forward_setup(p, d.name);
+  if (rc != SLODE_OK) return rc;
+  a.loc = p.w.loc; a.scale = p.w.scale;
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
+  return run(c.stream);
+}
+
 // The statistics row of one batch (include/slode.h): refusals first -- nothing launched, no draw consumed -- then the fold + encoder launches
 // of a forward-only step, the fused kernel and the fixed-order reduction of its partial rows.
 int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
@@ -974,35 +1030,17 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
 int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                         const float* stage_t, const slode_batch* batch, int is_post, int num_samples, float* mean, float* sd, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_recon_moments", "batch / mean / times / stage_t / workspace", !batch || !mean || !times || !stage_t || !workspace,
-                   "num_samples", num_samples, "; reduce recon_samples instead", "(one particle only)",
-                   is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr,
-                   is_post ? " (and no SLODE_NO_FOLD); reduce recon_samples instead" : nullptr,
-                   "step table, moments, staged weights", "reduce recon_samples instead"};
+  const DrawsCall d("slode_recon_moments", "batch / mean / times / stage_t / workspace", !batch || !mean || !times || !stage_t || !workspace,
+                    num_samples, is_post, "reduce recon_samples instead", "step table, moments, staged weights");
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if ((rc = eval_lds(h, s, d, slode_recon_moments_lds_bytes(*s, h->ode_generic), SLODE_RECON_MOMENTS_LDS_MAX)) != SLODE_OK) return rc;
   ReconMomentsLaunch a{};
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_recon_moments: the prior needs the label tensors of the conditional prior groups");
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps; a.mean = mean; a.sd = sd;
-  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  if (!is_post) {   // the prior: no observations, no encoder launches, nothing of the workspace but its size
-    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
-    a.rng = take_draws(h, batch->eps, 1);
-    ClockScope clock_scope(h, true);
-    HIP_TRY(h, slode_launch_recon_moments(a, (hipStream_t)stream));
-    return SLODE_OK;
-  }
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.loc = p.w.loc; a.scale = p.w.scale;
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_recon_moments(a, c.stream));
-  return SLODE_OK;
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
+  a.mean = mean; a.sd = sd;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_recon_moments(a, st); });
 }
 
 // Per-trajectory -ELBO, importance-weighted bound, effective sample size and mean negative log-likelihood from num_draws posterior draws
@@ -1040,10 +1078,8 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
 int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                             const float* stage_t, const slode_batch* batch, const float* const* cf_labels, unsigned int group_mask, int num_samples,
                             float* cf_mean, float* cf_sd, float* eff_mean, float* eff_sd, void* workspace, size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_intervene_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
-                   "num_samples", num_samples, "; reduce counterfactual samples instead", "(one particle only)",
-                   "the posterior needs observations (batch->obs is NULL)", " (and no SLODE_NO_FOLD); reduce counterfactual samples instead",
-                   "step table, moments, factual values, staged weights", "reduce counterfactual samples instead"};
+  const DrawsCall d("slode_intervene_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, 1,
+                    "reduce counterfactual samples instead", "step table, moments, factual values, staged weights");
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (s->n_groups < 32 && (group_mask >> s->n_groups) != 0)
@@ -1051,8 +1087,8 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
   if (group_mask != 0 && !cf_labels) return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x needs the counterfactual labels (cf_labels is NULL)", group_mask);
   if ((rc = eval_lds(h, s, d, slode_intervene_moments_lds_bytes(*s, h->ode_generic), SLODE_INTERVENE_MOMENTS_LDS_MAX)) != SLODE_OK) return rc;
   InterveneMomentsLaunch a{};
-  LabelSrc lab{};
-  if ((rc = batch_labels(h, s, batch, &lab)) != SLODE_OK) return rc;
+  const LabelSrc& lab = a.d.lab;
+  if ((rc = batch_labels(h, s, batch, &a.d.lab)) != SLODE_OK) return rc;
   a.cf = lab;   // widths as the batch's; a counterfactual tensor that no intervened group reads may be NULL (its slot keeps the batch's pointer, unread)
   if (group_mask != 0) {
     if (lab.n == 0) return fail(h, SLODE_EINVAL, "slode_intervene_moments: the counterfactual labels take the widths of batch->labels (n_labels is 0)");
@@ -1064,18 +1100,10 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
       else if (read) return fail(h, SLODE_EINVAL, "slode_intervene_moments: counterfactual label tensor %d is NULL but an intervened group reads its columns", i);
     }
   }
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
-  a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd;
-  a.group_mask = group_mask; a.num_samples = num_samples; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  const StepCall c = forward_call(params, times, stage_t, batch, lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.loc = p.w.loc; a.scale = p.w.scale;
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_intervene_moments(a, c.stream));
-  return SLODE_OK;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, 1, num_samples, s->B);
+  a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd; a.group_mask = group_mask;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_intervene_moments(a, st); });
 }
 
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
@@ -1155,10 +1183,8 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
                            const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const float* times_out,
                            const float* stage_t_out, int T_out, int window, float* mean, float* sd, float* x_mean, float* x_sd, void* workspace,
                            size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_forecast_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
-                   "num_samples", num_samples, "; reduce forecast_samples instead", "(one particle only)",
-                   is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr,
-                   is_post ? " (and no SLODE_NO_FOLD); reduce forecast_samples instead" : nullptr};
+  const DrawsCall d("slode_forecast_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+                    "reduce forecast_samples instead", nullptr);
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (!times_out || !stage_t_out) return fail(h, SLODE_EINVAL, "slode_forecast_moments: times_out / stage_t_out is NULL");
@@ -1171,27 +1197,11 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
   char why[384];
   if (forecast_plan(*s, T_out, num_samples, (x_mean || x_sd) ? 1 : 0, window, h->ode_generic, &a.window, &lds, why, sizeof(why)) != SLODE_OK)
     return fail(h, SLODE_EINVAL, "slode_forecast_moments: %s", why);
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_forecast_moments: the prior needs the label tensors of the conditional prior groups");
-  a.s = *s; a.lay = *lay; a.params = params; a.times_out = times_out; a.stage_t_out = stage_t_out; a.T_out = T_out; a.eps = batch->eps;
-  a.mean = mean; a.sd = sd; a.x_mean = x_mean; a.x_sd = x_sd;
-  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  if (!is_post) {   // the prior: no observations, no encoder launches, nothing of the workspace but its size
-    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
-    a.rng = take_draws(h, batch->eps, 1);
-    ClockScope clock_scope(h, true);
-    HIP_TRY(h, slode_launch_forecast_moments(a, (hipStream_t)stream));
-    return SLODE_OK;
-  }
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.loc = p.w.loc; a.scale = p.w.scale;
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_forecast_moments(a, c.stream));
-  return SLODE_OK;
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times_out, stage_t_out, batch, is_post, num_samples, s->B);   // (the kernel solves on the output grid)
+  a.T_out = T_out; a.mean = mean; a.sd = sd; a.x_mean = x_mean; a.x_sd = x_sd;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_forecast_moments(a, st); });
 }
 
 // ---- cohort curves: the draws of slode_recon_moments reduced by cohort (include/slode.h) ----
@@ -1228,11 +1238,8 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
                          const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const int32_t* members,
                          const int32_t* offsets, int M, int G, int chunk, float clip_min, float* mean, float* sd, float* sd_subjects,
                          float* obs_mean, float* l1, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_cohort_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
-                   "num_samples", num_samples, "; reduce recon_samples instead", "(one particle only)",
-                   is_post ? "the posterior needs observations (batch->obs is NULL)" : nullptr,
-                   is_post ? " (and no SLODE_NO_FOLD); reduce recon_samples instead" : nullptr,
-                   "step table, six-float table, observation sum, staged weights", "reduce recon_samples instead"};
+  const DrawsCall d("slode_cohort_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+                    "reduce recon_samples instead", "step table, six-float table, observation sum, staged weights");
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "slode_cohort_moments: members / offsets is NULL with M = %d", M);
@@ -1252,29 +1259,13 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
   a.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
   const CohortScratch sc = slode_cohort_scratch(*s, M, G, a.chunk);
   if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "slode_cohort_moments: scratch_bytes %zu B < required %zu B (slode_cohort_plan)", scratch_bytes, sc.bytes);
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  if (!is_post && s->n_groups > 0 && a.lab.n == 0) return fail(h, SLODE_EINVAL, "slode_cohort_moments: the prior needs the label tensors of the conditional prior groups");
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.eps = batch->eps;
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, sc.n_partials);
   a.obs = want_obs ? batch->obs : nullptr; a.sb = os[0]; a.t_major = t_major && !c_major ? 1 : 0;
   a.members = members; a.offsets = offsets; a.M = M; a.G = G; a.clip_min = clip_min;
   a.mean = mean; a.sd = sd; a.sd_subjects = sd_subjects; a.obs_mean = obs_mean; a.l1 = l1; a.scratch = scratch;
-  a.num_samples = num_samples; a.is_post = is_post ? 1 : 0; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, sc.n_partials);
-  if (!is_post) {   // the prior: no encoder launches, nothing of the workspace but its size
-    if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
-    a.rng = take_draws(h, batch->eps, 1);
-    ClockScope clock_scope(h, true);
-    HIP_TRY(h, slode_launch_cohort_moments(a, (hipStream_t)stream));
-    return SLODE_OK;
-  }
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.loc = p.w.loc; a.scale = p.w.scale;
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_cohort_moments(a, c.stream));
-  return SLODE_OK;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_cohort_moments(a, st); });
 }
 
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {

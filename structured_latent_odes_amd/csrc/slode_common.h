@@ -550,17 +550,23 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// Sample moments of the reconstruction (recon_moments_kernel.hip; slode_recon_moments): mean / sd [Q, B, C, T] over num_samples latent draws per
-// trajectory.  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise:
-// rng.on: row k * B + b of ONE drawing call; else eps [num_samples, B, L].  sd may be NULL.
-struct ReconMomentsLaunch {
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort; intervene: the posterior
+// alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
+// row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
+struct DrawsLaunch {
   slode_shape s;
   slode_layout lay;
   const float *params, *times, *stage_t, *loc, *scale, *eps, *u;
-  float *mean, *sd;
   int num_samples, grid, is_post, force_generic;
   RngK rng{};
   LabelSrc lab{};
+};
+
+// Sample moments of the reconstruction (recon_moments_kernel.hip; slode_recon_moments): mean / sd [Q, B, C, T] over the draws of d per
+// trajectory.  sd may be NULL.
+struct ReconMomentsLaunch {
+  DrawsLaunch d;
+  float *mean, *sd;
 };
 #define SLODE_RECON_MOMENTS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moments, staged weights) must fit
 hipError_t slode_launch_recon_moments(const ReconMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
@@ -584,56 +590,45 @@ struct TrajBoundsLaunch {
 hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
-// Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over num_samples paired posterior draws per trajectory, mean / sd
-// [Q, B, C, T] of the curve under swapped labels and of its difference to the factual curve; each of the four outputs may be NULL.  loc / scale
-// [B, L] from the encoder launch; cf: the counterfactual label tensors (read in the columns of the groups in group_mask alone).  Noise: rng.on:
-// row k * B + b of ONE drawing call; else eps [num_samples, B, L].
+// Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over the paired posterior draws of d (is_post = 1; u unread, lab:
+// the batch's own labels, which the encoder launch takes) per trajectory, mean / sd [Q, B, C, T] of the curve under swapped labels and of its
+// difference to the factual curve; each of the four outputs may be NULL.  cf: the counterfactual label tensors (read in the columns of the
+// groups in group_mask alone).
 struct InterveneMomentsLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times, *stage_t, *loc, *scale, *eps;
+  DrawsLaunch d;
   float *cf_mean, *cf_sd, *eff_mean, *eff_sd;
   unsigned int group_mask;
-  int num_samples, grid, force_generic;
-  RngK rng{};
   LabelSrc cf{};
 };
 #define SLODE_INTERVENE_MOMENTS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moments, factual values, staged weights) must fit
 hipError_t slode_launch_intervene_moments(const InterveneMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_intervene_moments_lds_bytes(const slode_shape& s, int force_generic);
 
-// Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of ReconMomentsLaunch, solved on the output grid times_out
-// [T_out] (stage_t_out from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]
+// Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
+// from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]
 // and the moments of the ODE state x_mean / x_sd [B, S, T_out]; sd, x_mean, x_sd may be NULL (both state outputs NULL: no state tables).
 struct ForecastMomentsLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times_out, *stage_t_out, *loc, *scale, *eps, *u;
+  DrawsLaunch d;
   float *mean, *sd, *x_mean, *x_sd;
-  int T_out, window, num_samples, grid, is_post, force_generic;
-  RngK rng{};
-  LabelSrc lab{};
+  int T_out, window;
 };
 #define SLODE_FORECAST_LDS_MAX (160 * 1024)   // the LDS of one CU: staged weights, loc | scale, the carry table and one window's tables must fit
 hipError_t slode_launch_forecast_moments(const ForecastMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the window's tables do not fit the LDS
 size_t slode_forecast_lds_bytes(const slode_shape& s, int num_samples, int want_states, int window, int force_generic);
 
-// Cohort moments (cohort_moments_kernel.hip; slode_cohort_moments): the draws of ReconMomentsLaunch folded by cohort.  members [M] / offsets
+// Cohort moments (cohort_moments_kernel.hip; slode_cohort_moments): the draws of d folded by cohort.  members [M] / offsets
 // [G + 1] on the device; chunk = R in [1, SLODE_COHORT_MAX_CHUNK] (from the plan); obs: dense rows of C*T floats (sb apart), t_major: [T][C]
 // inside a row, else [C][T], NULL: no observation sum; mean / sd / sd_subjects [Q, G, C, T], obs_mean [G, C, T], l1 [G, C] (all but mean
 // may be NULL).  scratch: slode_cohort_scratch(..).bytes, 16-byte aligned.  Launches cohort_plan, cohort_moments, cohort_merge.
 struct CohortMomentsLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times, *stage_t, *loc, *scale, *eps, *u, *obs;
+  DrawsLaunch d;
+  const float* obs;
   int64_t sb;
   const int32_t *members, *offsets;
   float *mean, *sd, *sd_subjects, *obs_mean, *l1;
   void* scratch;
   float clip_min;
-  int M, G, chunk, t_major, num_samples, grid, is_post, force_generic;
-  RngK rng{};
-  LabelSrc lab{};
+  int M, G, chunk, t_major;
 };
 // The scratch of one call (byte offsets, multiples of 16): the partial ranges cs [G + 1], the chunk table [n_partials] of 4 ints, the
 // chunks' bad-member flags [n_partials], then n_partials partials of partial_floats floats: [Q*C][5: v00, t1, t2, b1, b2][T] | obs sum [C][T].

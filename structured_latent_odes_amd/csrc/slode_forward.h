@@ -1,15 +1,19 @@
-// The fixed-grid forward pass the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
+// The fixed-grid forward pass and the draw loop the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
 // intervene_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip; no other translation unit includes this header): each phase ONCE --
-//   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads)
-//                      and the host functions that fill them from slode_shape / slode_layout
+//   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads),
+//                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort) and the host functions that
+//                      fill them from slode_shape / slode_layout / DrawsLaunch
 //   prior nets         fwd_prior_at: loc / log scale of one latent dim from the staged labels
 //   step coefficients  fwd_step_coeffs: x' = A x + b of one grid step for euler / midpoint / rk4, the a, d evaluator passed in;
-//                      fwd_step_table: thread <-> step, the table of a whole solve
+//                      fwd_step_table: thread <-> step, the table of a step range [n_lo, n_hi) of the grid (a whole solve: [0, T - 1))
 //   scan               fwd_scan: forward affine scan, one state component per wave pass
 //   label heads        fwd_label_logits: hidden layer and logits of one head on a half-wave
-//   staged weights     (recon, bounds, intervene) FWD_ROW, FwdLds / FwdSm, fwd_stage_weights, fwd_init_state, fwd_ad: the weights every
-//                      draw reuses live in the LDS; the a, d evaluator reads one 16-byte-aligned row per hidden unit
-//   windows            (forecast) fwd_step_table_range: the step table of a step range of a grid with its own tables
+//   staged weights     (every kernel but eval_stats) FWD_ROW, FwdLds / FwdSm, fwd_stage_weights, fwd_init_state, fwd_ad, fwd_step_table_staged:
+//                      the weights every draw reuses live in the LDS; the a, d evaluator reads one 16-byte-aligned row per hidden unit
+//   the draw loop       M1 fwd_draw_source: loc | scale of a trajectory, posterior or conditional prior, into the LDS pieces of
+//                      fwd_lds_loc_sc; M2 fwd_draw_z: z of draw k; M3-M5 fwd_solve: one solve of a step range from a given initial state;
+//                      M6 fwd_state_at, fwd_head_value: the state of a time point, one head value; the shifted moment triple [v0 | s1 | s2]:
+//                      fwd_moment_add, fwd_moment_store (M7)
 //   launch             fwd_generic, fwd_dispatch over the compile-time state dim {5, 8, 0}, fwd_launch
 // Every routine keeps the operation order of the kernels it came from: results are bitwise those of the separate copies.
 #pragma once
@@ -39,6 +43,15 @@ struct LabelHeadK {
   slode_aux aux[SLODE_MAX_AUX];
   int aux_w1[SLODE_MAX_AUX], aux_b1[SLODE_MAX_AUX], aux_w2[SLODE_MAX_AUX], aux_b2[SLODE_MAX_AUX], aux_c[SLODE_MAX_AUX];
 };
+// a call that walks ns draws per trajectory from one source: the posterior (loc / scale of the encoder launch) or the conditional prior
+struct DrawsK {
+  FwdK f;
+  PriorK pr;
+  int is_post, ns;
+  const float *loc, *scale, *eps, *u;
+  RngK rng;
+  LabelSrc lab;
+};
 
 inline void fwd_fill(FwdK& k, const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const float* stage_t) {
   k.B = s.B; k.T = s.T; k.C = s.C; k.L = s.L; k.S = s.S; k.H = s.H;
@@ -61,6 +74,11 @@ inline void fwd_fill(LabelHeadK& k, const slode_shape& s, const slode_layout& la
     k.aux[q] = s.aux[q]; k.aux_w1[q] = lay.aux_w1[q]; k.aux_b1[q] = lay.aux_b1[q]; k.aux_w2[q] = lay.aux_w2[q]; k.aux_b2[q] = lay.aux_b2[q];
     k.aux_c[q] = lay.aux_c[q];
   }
+}
+inline void fwd_fill(DrawsK& k, const DrawsLaunch& a) {
+  fwd_fill(k.f, a.s, a.lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, a.s, a.lay);
+  k.is_post = a.is_post; k.ns = a.num_samples;
+  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.rng = a.rng; k.lab = a.lab;
 }
 
 // ---- conditional prior nets -----------------------------------------------------------------------------------
@@ -131,16 +149,18 @@ __device__ __forceinline__ void fwd_step_coeffs(int method, float h, const float
   }
 }
 
-// the step table of one solve, thread <-> step: steps n_first, n_first + n_stride, ... into pa[n][s] / pb[n][s]
+// the step table of the steps [n_lo, n_hi) of the grid k.times / k.stage_t (a whole solve: n_lo = 0, n_hi = T - 1), thread <-> step: step
+// n_lo + i into pa[i][s] / pb[i][s], i = i_first, i_first + i_stride, ...
 template <int SM, class AD>
-__device__ __forceinline__ void fwd_step_table(const FwdK& k, int S, int n_first, int n_stride, float* pa, float* pb, const AD& ad) {
-  const int NS = k.T - 1;
-  for (int n = n_first; n < NS; n += n_stride) {
+__device__ __forceinline__ void fwd_step_table(const FwdK& k, int S, int n_lo, int n_hi, int i_first, int i_stride, float* pa, float* pb,
+                                               const AD& ad) {
+  for (int i = i_first; i < n_hi - n_lo; i += i_stride) {
+    const long long n = (long long)n_lo + i;
     float A[SM], bb[SM];
     fwd_step_coeffs<SM>(k.method, k.times[n + 1] - k.times[n], k.stage_t + n * k.R, ad, A, bb);
 #pragma unroll
     for (int s = 0; s < SM; ++s)
-      if (s < S) { pa[n * S + s] = A[s]; pb[n * S + s] = bb[s]; }
+      if (s < S) { pa[i * S + s] = A[s]; pb[i * S + s] = bb[s]; }
   }
 }
 
@@ -291,36 +311,94 @@ __device__ __forceinline__ void fwd_ad(const float* __restrict__ s_row, const fl
   for (int s = 0; s < SM; ++s) { a[s] = sigmoidf_fast(a[s]); d[s] = sigmoidf_fast(d[s]); }
 }
 
-// the staged form of the step table and the scan: one solve on all four waves
+// the staged form of the step table: the steps [n_lo, n_hi) on all four waves
 template <int SM>
-__device__ __forceinline__ void fwd_step_table_staged(const FwdK& k, const FwdSm& m, int S, int tid) {
+__device__ __forceinline__ void fwd_step_table_staged(const FwdK& k, const FwdSm& m, int S, int n_lo, int n_hi, int tid) {
   const float* s_row = m.row; const float* s_bgd = m.bgd;
   const int H = k.H;
-  fwd_step_table<SM>(k, S, tid, FWD_NT, m.A, m.B, [&](float t, float (&a)[SM], float (&d)[SM]) { fwd_ad<SM>(s_row, s_bgd, H, t, S, a, d); });
+  fwd_step_table<SM>(k, S, n_lo, n_hi, tid, FWD_NT, m.A, m.B, [&](float t, float (&a)[SM], float (&d)[SM]) { fwd_ad<SM>(s_row, s_bgd, H, t, S, a, d); });
 }
 
-// ---- a solve in windows (forecast) -------------------------------------------------------------------------------------
-// the step table of the steps [n_lo, n_hi) of a grid given by its own tables (times / stage_t of the WHOLE grid, read at the window's
-// offset), thread <-> step: step n_lo + i into pa[i][s] / pb[i][s], i = i_first, i_first + i_stride, ...
-template <int SM, class AD>
-__device__ __forceinline__ void fwd_step_table_range(int method, int R, const float* __restrict__ times, const float* __restrict__ stage_t,
-                                                     int S, int n_lo, int n_hi, int i_first, int i_stride, float* pa, float* pb, const AD& ad) {
-  for (int i = i_first; i < n_hi - n_lo; i += i_stride) {
-    const long long n = (long long)n_lo + i;
-    float A[SM], bb[SM];
-    fwd_step_coeffs<SM>(method, times[n + 1] - times[n], stage_t + n * R, ad, A, bb);
-#pragma unroll
-    for (int s = 0; s < SM; ++s)
-      if (s < S) { pa[i * S + s] = A[s]; pb[i * S + s] = bb[s]; }
+// ---- the draw loop ------------------------------------------------------------------------------------------
+// the LDS pieces loc | scale of one source of draws, carved where the kernel's own order of pieces has them
+struct LocScLds { int loc, sc; };
+inline LocScLds fwd_lds_loc_sc(LdsCarve& cv, const slode_shape& s) {
+  LocScLds o{};
+  o.loc = cv.take(s.L); o.sc = cv.take(s.L);
+  return o;
+}
+
+// M1, once per trajectory b: the labels into m.u (only the conditional prior nets read them); loc / scale of the posterior (from the
+// encoder launch) or of the conditional prior nets -- N(0, 1) on the dims outside every prior group -- into s_loc / s_sc, each read back
+// by its own thread alone.  Contains two barriers (before: the staged weights' writes and the previous trajectory's readers of m.u / s_loc /
+// s_sc; between the labels and the prior nets): call from workgroup-uniform control flow only.
+__device__ __forceinline__ void fwd_draw_source(const DrawsK& k, const FwdSm& m, float* s_loc, float* s_sc, int b, int tid) {
+  const int L = k.f.L;
+  __syncthreads();
+  if (!k.is_post && k.pr.n_groups > 0 && tid < k.pr.nu) m.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
+  __syncthreads();
+  if (tid < L) {
+    const int l = tid;
+    float loc, sc;
+    if (k.is_post) {
+      loc = k.loc[(long long)b * L + l]; sc = k.scale[(long long)b * L + l];
+    } else {
+      float pl, pls;
+      fwd_prior_at(k.pr, k.f.params, m.u, l, pl, pls);
+      loc = pl; sc = expf(pls);
+    }
+    s_loc[l] = loc; s_sc[l] = sc;
   }
 }
-// its staged form; the scan of a window is fwd_scan itself, whose initial state is an argument (x0 in window 0, the draw's carry afterwards)
+
+// M2: z of draw kk of trajectory b into m.z = loc + scale * eps, eps row kk * B + b of ONE drawing call or of the explicit [ns, B, L] tensor
+// (the caller's barrier follows)
+__device__ __forceinline__ void fwd_draw_z(const DrawsK& k, const FwdSm& m, const float* s_loc, const float* s_sc, int kk, int b, int tid) {
+  if (tid < k.f.L) m.z[tid] = fmaf(s_sc[tid], slode_eps_at(k.rng, k.eps, (long long)kk * k.f.B + b, k.f.L, tid), s_loc[tid]);
+}
+
+// M3 - M5, one solve of the steps [n_lo, n_hi) from the z in m.z (visible: the caller's barrier) on all four waves: fwd_init_state (the
+// units' rows of this z; x0), the step table, the scan from x_init -- m.x0 for a solve from the grid's start, a carried state otherwise.
+// Afterwards the state after step n_lo + i is m.A[i][.].  Contains fwd_init_state's barrier, one after the table and one after the scan:
+// call from workgroup-uniform control flow only.
 template <int SM>
-__device__ __forceinline__ void fwd_step_table_range_staged(const FwdK& k, const FwdSm& m, int S, int n_lo, int n_hi, int tid) {
-  const float* s_row = m.row; const float* s_bgd = m.bgd;
-  const int H = k.H;
-  fwd_step_table_range<SM>(k.method, k.R, k.times, k.stage_t, S, n_lo, n_hi, tid, FWD_NT, m.A, m.B,
-                           [&](float t, float (&a)[SM], float (&d)[SM]) { fwd_ad<SM>(s_row, s_bgd, H, t, S, a, d); });
+__device__ __forceinline__ void fwd_solve(const FwdK& k, const FwdSm& m, int S, const float* x_init, int n_lo, int n_hi, int tid) {
+  fwd_init_state<SM>(m, k.H, k.L, S, tid);
+  fwd_step_table_staged<SM>(k, m, S, n_lo, n_hi, tid);
+  __syncthreads();
+  fwd_scan(m.A, m.B, x_init, S, n_hi - n_lo, tid & 63, tid >> 6, FWD_NT / 64);
+  __syncthreads();
+}
+
+// M6: the state of point j of the solved range (j = 0: x0; else the scanned m.A[j - 1]) ...
+template <int SM>
+__device__ __forceinline__ void fwd_state_at(const FwdSm& m, int S, int j, float (&x)[SM]) {
+#pragma unroll
+  for (int s = 0; s < SM; ++s) x[s] = s < S ? (j == 0 ? m.x0[s] : m.A[(j - 1) * S + s]) : 0.f;
+}
+// ... and the value of head row qc = q * C + c on it
+template <int SM>
+__device__ __forceinline__ float fwd_head_value(const FwdSm& m, int S, int qc, const float (&x)[SM]) {
+  float v = 0.f;
+#pragma unroll
+  for (int s = 0; s < SM; ++s) if (s < S) v = fmaf(m.hw[qc * S + s], x[s], v);
+  return v;
+}
+
+// The running moments of one value over the draws, shifted by the first draw's value: m[0] = v0, m[P] = s1 = sum (v - v0), m[2 P] = s2 =
+// sum (v - v0)^2 (P: the slot stride of the kernel's table) -- no sum of v^2, whose fp32 rounding would exceed the variance of a
+// prior-pass curve.  One owner thread per value, draws in order.  Returns v - v0 (0 on the first draw).
+__device__ __forceinline__ float fwd_moment_add(float* m, int P, bool first, float v) {
+  if (first) { m[0] = v; m[P] = 0.f; m[2 * P] = 0.f; return 0.f; }
+  const float dv = v - m[0];
+  m[P] += dv; m[2 * P] = fmaf(dv, dv, m[2 * P]);
+  return dv;
+}
+// M7: mean = v0 + s1 / ns and sd = sqrt(max(0, s2 - s1^2 / ns) / ns) to element o of the outputs that were asked for (inv = 1 / ns)
+__device__ __forceinline__ void fwd_moment_store(const float* m, int P, float inv, float* mean, float* sd, long long o) {
+  const float s1 = m[P], s2 = m[2 * P];
+  if (mean) mean[o] = fmaf(s1, inv, m[0]);
+  if (sd) sd[o] = sqrtf(fmaxf(s2 - s1 * s1 * inv, 0.f) * inv);
 }
 
 // ---- launch ---------------------------------------------------------------------------------------------------------

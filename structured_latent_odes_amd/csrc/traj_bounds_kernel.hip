@@ -3,7 +3,8 @@
 // -- the main loss of the single row b on draw k -- kept apart, and their four summaries: the mean (-ELBO of the trajectory), the
 // importance-weighted bound -log(1/K sum_k exp(-loss)), the effective sample size of the weights, the mean negative log-likelihood.
 // One workgroup of four waves handles one trajectory at a time (persistent loop beyond the grid) and walks its draws k = 0 .. K - 1:
-// The forward phases B0 (weights), B3-B5, the prior nets of B1 and the logits of B7 are the shared ones of slode_forward.h.
+// The forward phases B0 (weights), B3-B5 (fwd_solve), the state and head values of B6, the prior nets of B1 and the logits of B7 are the
+// shared ones of slode_forward.h; B1 / B2 are this kernel's own: it keeps both distributions for the KL terms.
 //   B0  once per workgroup: the weights every draw reuses (fwd_stage_weights: [w_t | u_j | W_g | W_d] per hidden unit, the
 //       z-columns of the hidden layer and the init net, the init net's output layer, the head weights, the biases) and the likelihood
 //       scale table of the fold launch (1 / scale and log scale per (c, t)) into the LDS
@@ -11,9 +12,7 @@
 //       of thread l; the observation row into the LDS as [C][T] -- HBM is read once per trajectory, not once per draw
 //   per draw:
 //   B2  z = loc + scale * eps_k (row b of drawing call n + k, or of the explicit [K, B, L] tensor); log q - log p of thread l
-//   B3  time-invariant part of the hidden layer (into the unit's weight row) and the init net; x0
-//   B4  step coefficients x' = A x + b of every grid step (tests/kernel_math.py step_coeffs), thread <-> step, all four waves
-//   B5  forward affine scan: one state component per wave pass, a chunk of steps per lane, Kogge-Stone over the lanes' maps
+//   B3-B5  fwd_solve over the whole grid: the init net and x0, the step table, the forward affine scan
 //   B6  thread <-> time point: decoder heads + ALD / Gaussian log-likelihood against the staged observations
 //   B7  proc family: the main loss's label terms on z, a half-wave per label head (as phase E5 of eval_stats_kernel, use 2)
 //   B8  fixed-order sums over the workgroup of (log q - log p) and of the log-likelihood; thread 0 forms loss[k] and its likelihood part
@@ -101,7 +100,7 @@ __global__ void __launch_bounds__(TB_NT) traj_bounds_kernel(const TbK k) {
   const FwdK& f = k.f;
   const float* __restrict__ par = f.params;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hw = tid >> 5, j32 = tid & 31;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, H = f.H, C = f.C, Q = f.Q, NS = T - 1, CT = C * T, nd = k.nd;
+  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, CT = C * T, nd = k.nd;
   const FwdSm sm = fwd_sm(s_tb, k.o.f);
   float* s_obs = s_tb + k.o.obs;   // [C][T] the trajectory's observations
   float* s_inv = s_tb + k.o.inv;   // [C][T] 1 / likelihood scale
@@ -147,28 +146,17 @@ __global__ void __launch_bounds__(TB_NT) traj_bounds_kernel(const TbK k) {
         sm.z[tid] = z;
       }
       __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_red are done)
-      // ---- B3: u = W_z z + b_h into the units' rows; the init net's hidden layer ----
-      fwd_init_state<SM>(sm, H, L, S, tid);
-      // ---- B4: step coefficients ----
-      fwd_step_table_staged<SM>(f, sm, S, tid);
-      __syncthreads();
-      // ---- B5: forward affine scan, in place: x[n + 1][s] takes the slot of A[n][s] ----
-      fwd_scan(sm.A, sm.B, sm.x0, S, NS, lane, wave, TB_NT / 64);
-      __syncthreads();
+      fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // B3 - B5
       // ---- B6: heads + log-likelihood of the thread's time points ----
       float llt = 0.f;
       for (int t = tid; t < T; t += TB_NT) {
         float x[SM];
-#pragma unroll
-        for (int s = 0; s < SM; ++s) x[s] = s < S ? (t == 0 ? sm.x0[s] : sm.A[(t - 1) * S + s]) : 0.f;
+        fwd_state_at<SM>(sm, S, t, x);
         float ll = 0.f;
         for (int c = 0; c < C; ++c) {
           const float obv = s_obs[c * T + t], inv = s_inv[c * T + t], lg = s_lg[c * T + t];
           for (int q = 0; q < Q; ++q) {
-            float mu = 0.f;
-#pragma unroll
-            for (int s = 0; s < SM; ++s) if (s < S) mu = fmaf(sm.hw[(q * C + c) * S + s], x[s], mu);
-            const float r = obv - mu;
+            const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
             if (k.gauss) ll += -lg - TB_HL2PI - 0.5f * r * r * inv * inv;
             else ll += ((obv >= mu) ? k.tau[q] : 1.f - k.tau[q]) * (-lg - fabsf(r) * inv);
           }

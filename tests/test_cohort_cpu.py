@@ -155,7 +155,9 @@ LADDER = {
 
 def test_cohort_refusals_on_a_hand_filled_handle(tmp_path):
     """Every refusing configuration of slode_cohort_moments, posterior and prior, without a device: status, the words of the message and
-    the untouched drawing-call counter against LADDER."""
+    the untouched drawing-call counter against LADDER; and line by line -- status, counter and the full message, which check speaks first
+    when two conditions hold included -- against tests/golden/cohort_refusals.txt, recorded from the library before the draw-walking calls
+    shared one host tail."""
     import subprocess
     from structured_latent_odes_amd import _lib as L
     hipcc = "/opt/rocm/bin/hipcc"
@@ -170,6 +172,10 @@ def test_cohort_refusals_on_a_hand_filled_handle(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) > 90
+    want = open(os.path.join(ROOT, "tests", "golden", "cohort_refusals.txt")).read().splitlines()
+    for i, (g, w) in enumerate(zip(lines, want)):
+        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
+    assert len(lines) == len(want)
     seen = set()
     for line in lines:
         name, status, counter, msg = line.split(" | ", 3)
