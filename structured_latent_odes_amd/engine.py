@@ -225,18 +225,26 @@ class Engine:
             self._ws[(B, particles)] = w
         return w
 
-    def set_times(self, times: torch.Tensor) -> torch.Tensor:
-        """Bind the time grid (len T) and build the stage-time table on device."""
-        times = self._f32(times.to(self.device, torch.float32).contiguous(), "times")
-        if times.numel() != self.T:
-            raise ValueError("times has %d points, engine built for T=%d" % (times.numel(), self.T))
-        d = times[1:] - times[:-1]
+    def _check_grid(self, t: torch.Tensor):
+        """ValueError unless the grid ``t`` is one the solver takes (``set_times`` and ``forecast_grid``)."""
+        d = t[1:] - t[:-1]
         if not (bool((d > 0).all()) or bool((d < 0).all())):    # torchdiffeq odeint's own precondition (misc._check_timelike)
             raise ValueError("t must be strictly increasing or decreasing")
         if self.spec.solver in L.ADAPTIVE and not bool((d > 0).all()):
             # torchdiffeq integrates a decreasing grid in s = -t; the adaptive kernels here only walk forward in time
             # (dopri5_kernel.hip: dt > 0, outputs emitted while tj <= t1) and answer such a grid with NaN trajectories
             raise ValueError("solver=%r needs a strictly increasing time grid (decreasing grids: fixed-grid solvers only)" % self.spec.solver)
+
+    def _head_shape(self, rows: int, T: int = None):
+        """``(Q, rows, C, T)`` of a head-curve output: Q = 3 quantile heads, 1 for the Gaussian family; T: the bound grid's by default."""
+        return (1 if self.spec.gauss else 3, rows, self.spec.n_channels, self.T if T is None else T)
+
+    def set_times(self, times: torch.Tensor) -> torch.Tensor:
+        """Bind the time grid (len T) and build the stage-time table on device."""
+        times = self._f32(times.to(self.device, torch.float32).contiguous(), "times")
+        if times.numel() != self.T:
+            raise ValueError("times has %d points, engine built for T=%d" % (times.numel(), self.T))
+        self._check_grid(times)
         n = int(self.lib.slode_num_stage_times(C.byref(self.shape(1))))
         st = torch.empty(n, dtype=torch.float32, device=self.device)
         _check(self.lib, self.handle, self.lib.slode_stage_times(self.handle, C.byref(self.shape(1)), self._p(times), self._p(st), self._stream()))
@@ -362,8 +370,7 @@ class Engine:
     def decode_heads(self, params, x):
         B = x.shape[0]
         sp = self.spec
-        Q = 1 if sp.gauss else 3
-        mu = torch.empty(Q, B, sp.n_channels, self.T, dtype=torch.float32, device=self.device)
+        mu = torch.empty(self._head_shape(B), dtype=torch.float32, device=self.device)
         std = torch.empty(sp.n_channels, self.T, dtype=torch.float32, device=self.device)
         _check(self.lib, self.handle, self.lib.slode_decode_heads(
             self.handle, C.byref(self.shape(B)), C.byref(self.layout), self._p(params), self._p(self._f32(x, "x")), self._p(mu), self._p(std), self._stream()))
@@ -521,7 +528,7 @@ class Engine:
         ``draw_normal(num_samples * B).view(num_samples, B, L)`` yields).  Raises SlodeError naming the reason for what the kernel does not
         take (adaptive solver, ``particles`` > 1, strided posterior observations, measured arms, num_samples < 1, LDS budget): nothing is
         launched and no draw is consumed then."""
-        shp = (1 if self.spec.gauss else 3, B, self.spec.n_channels, self.T)
+        shp = self._head_shape(B)
         mean, sd = self._out(mean, "mean", shp), self._out(sd, "sd", shp)
         self._batch_call(self.lib.slode_recon_moments, params, batch, B, particles, 1 if is_post else 0, int(num_samples), self._p(mean), self._p(sd))
         return mean, sd
@@ -539,11 +546,7 @@ class Engine:
         n = tt.numel()
         if n < 2 or n > L.FORECAST_MAX_T:
             raise ValueError("times_out has %d points, outside [2, %d]" % (n, L.FORECAST_MAX_T))
-        d = tt[1:] - tt[:-1]
-        if not (bool((d > 0).all()) or bool((d < 0).all())):
-            raise ValueError("t must be strictly increasing or decreasing")
-        if self.spec.solver in L.ADAPTIVE and not bool((d > 0).all()):
-            raise ValueError("solver=%r needs a strictly increasing time grid (decreasing grids: fixed-grid solvers only)" % self.spec.solver)
+        self._check_grid(tt)
         ns = int(self.lib.slode_num_stage_times_n(C.byref(self.shape(1)), n))
         if ns < 1:
             _check(self.lib, None, -1)
@@ -572,7 +575,7 @@ class Engine:
         ``recon_moments`` refuses but its LDS budget; a bad T_out; a window that does not fit): nothing is launched or drawn then."""
         tt, st = self.forecast_grid(times_out)
         T_out = tt.numel()
-        shp = (1 if self.spec.gauss else 3, B, self.spec.n_channels, T_out)
+        shp = self._head_shape(B, T_out)
         mean, sd = self._out(mean, "mean", shp), self._out(sd, "sd", shp)
         if states or x_mean is not None or x_sd is not None:
             xs = (B, self.spec.ode_state_dim, T_out)
@@ -609,17 +612,16 @@ class Engine:
         M, G = members.numel(), int(G)
         if offsets.numel() != G + 1:
             raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
-        Q, Cn = 1 if self.spec.gauss else 3, self.spec.n_channels
-        shp = (Q, G, Cn, self.T)
+        shp = self._head_shape(G)
         mean = self._out(mean, "mean", shp)
         if sd is not None or "sd" in outputs:
             sd = self._out(sd, "sd", shp)
         if sd_subjects is not None or "sd_subjects" in outputs:
             sd_subjects = self._out(sd_subjects, "sd_subjects", shp)
         if obs_mean is not None or "obs_mean" in outputs:
-            obs_mean = self._out(obs_mean, "obs_mean", (G, Cn, self.T))
+            obs_mean = self._out(obs_mean, "obs_mean", shp[1:])
         if l1 is not None or "l1" in outputs:
-            l1 = self._out(l1, "l1", (G, Cn))
+            l1 = self._out(l1, "l1", shp[1:3])
         if scratch is None:    # (sized by the library's own arithmetic; a refusal there is raised as the call's would be)
             scratch = torch.empty((self.cohort_plan(B, M, G, max(int(num_samples), 1), chunk)[3] + 3) // 4, dtype=torch.float32, device=self.device)
         self._batch_call(self.lib.slode_cohort_moments, params, batch, B, 1, 1 if is_post else 0, int(num_samples), self._p(members),
@@ -656,7 +658,7 @@ class Engine:
         the kernel does not take (everything ``recon_moments(is_post=True)`` refuses; mask bits beyond the prior groups; a non-zero mask
         without counterfactual labels): nothing is launched and no draw is consumed then."""
         sp = self.spec
-        shp = (1 if sp.gauss else 3, B, sp.n_channels, self.T)
+        shp = self._head_shape(B)
         # (an output passed as False is not wanted: NULL in the C call, None in the result)
         outs = [None if t is False else self._out(t, name, shp)
                 for t, name in ((cf_mean, "cf_mean"), (cf_sd, "cf_sd"), (eff_mean, "eff_mean"), (eff_sd, "eff_sd"))]

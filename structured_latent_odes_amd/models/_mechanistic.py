@@ -220,12 +220,8 @@ class MechanisticBase(nn.Module):
         """Posterior (is_post) or prior reconstruction (mechanistic_cvs.py:298-323): returns the reference's dict."""
         b = self._bind()
         with torch.no_grad():
-            if is_post:
-                loc, scale = self.encoder.forward(observations)
-                z = b.engine.sample_normal(loc.contiguous(), scale.contiguous())
-            else:
-                ploc, pscale = self._prior_loc_scale(labels)      # [B, L]: conditional groups, then (0, 1) for z_epsilon
-                z = b.engine.sample_normal(ploc, pscale)
+            loc, scale = self._loc_scale(observations, is_post, labels)
+            z = b.engine.sample_normal(loc.contiguous(), scale.contiguous())
             if self.GAUSS:
                 solution_xt, mean, std = self.decoder.forward(z=z)
                 return {"l1": self.l1_func(mean, observations), "solution_xt": solution_xt, "mean": mean, "std": std, "z": z}
@@ -246,30 +242,75 @@ class MechanisticBase(nn.Module):
                                               None if e is None else e.to(torch.float32).contiguous(), particles=draws)
 
     @staticmethod
-    def _raise_unless_refused(err):
-        """Only a refusal (SLODE_EINVAL, status -1: nothing launched, nothing drawn) leads to a composed fallback: anything else is raised."""
-        if getattr(err, "status", None) != -1:
-            raise err
+    def _count(n, name="num_samples") -> int:
+        """The draw count of a call as an int; ValueError below 1."""
+        if int(n) < 1:
+            raise ValueError("%s must be >= 1, got %d" % (name, int(n)))
+        return int(n)
 
-    def _composed_moments(self, B, num_samples, eps, materialise, reduce, names=None):
-        """The chunk loop of a composed fallback: ``MOMENTS_CHUNK_ROWS // num_samples`` rows of the batch at a time,
-        ``materialise(lo, hi, eps[:, lo:hi])`` yields the per-draw curves of rows [lo, hi) (``{curve: ...}``) and ``reduce`` turns one
-        curve's into a tuple of ``[rows, C, T]`` tensors; returns ``{curve: tuple of [B, C, T]}``.  The noise is drawn once for the whole
-        batch (ONE drawing call, counter n -> n + 1, row k * B + b = draw k of trajectory b, as the engine call makes it) and sliced per
-        chunk, so the result does not depend on the chunking."""
-        rows = max(1, self.MOMENTS_CHUNK_ROWS // num_samples)
+    def _loc_scale(self, observations, is_post, labels):
+        """(loc, scale) [B, L] of the posterior q(z | x) (``is_post``: the encoder) or of the conditional prior p(z | labels)."""
+        return self.encoder.forward(observations) if is_post else self._prior_loc_scale(labels)
+
+    def _noise(self, ns, B, eps, device=None):
+        """``eps`` as ``[ns, B, L]``; None: ONE drawing call of the engine's generator (counter n -> n + 1, row k * B + b = draw k of
+        trajectory b, as the fused engine calls make it).  The one place of the eval-side API that draws ``ns`` rows per trajectory."""
         if eps is None:
-            eps = self._bind().engine.draw_normal(num_samples * B).view(num_samples, B, -1)
-        eps = eps.reshape(num_samples, B, -1)
-        names = names or self.MOMENT_HEADS[bool(self.GAUSS)]      # (names: the curves to reduce, where they are not the head curves alone)
-        parts = {n: [] for n in names}
+            eps = self._bind().engine.draw_normal(ns * B)
+        return (eps if device is None else eps.to(device)).reshape(ns, B, -1)
+
+    def _draws(self, loc, scale, ns, eps):
+        """``(eps, z)``, ``[ns, B, L]`` each: z = loc + scale * eps, with ``eps`` as ``_noise`` yields it."""
+        eps = self._noise(ns, loc.shape[0], eps, loc.device)
+        return eps, loc.unsqueeze(0) + scale.unsqueeze(0) * eps
+
+    def _decoded_draws(self, z):
+        """``decoder.forward`` on the draws ``z`` ``[ns, B, L]`` in one pass: ``{curve: [B, C, T, ns]}`` of every head curve."""
+        ns, B = z.shape[:2]
+        names = ("solution_xt", "mean", "std") if self.GAUSS else ("solution_xt", "mu_75", "mu_50", "mu_25", "std")
+        return {n: v.reshape(ns, B, v.shape[1], v.shape[2]).permute(1, 2, 3, 0).contiguous()
+                for n, v in zip(names, self.decoder.forward(z=z.reshape(ns * B, -1).contiguous())) if n not in ("solution_xt", "std")}
+
+    @staticmethod
+    def _fused_or_composed(fused, composed):
+        """``fused()``; where the engine refuses it (SlodeError with SLODE_EINVAL, status -1: nothing launched, nothing drawn), ``composed()``.
+        Any other engine error is raised."""
+        from .. import _lib as L
+        try:
+            return fused()
+        except L.SlodeError as err:
+            if getattr(err, "status", None) != -1:
+                raise
+        return composed()
+
+    def _chunks(self, observations, labels, ns, eps):
+        """The chunk walk of a composed route: ``(lo, hi, eps[:, lo:hi], rows [lo, hi) of the batch as keyword arguments)`` for
+        ``MOMENTS_CHUNK_ROWS // ns`` rows at a time.  The noise is drawn once for the whole batch, before chunking, and sliced per chunk,
+        so the result does not depend on the chunking."""
+        B = observations.shape[0]
+        eps = self._noise(ns, B, eps)
+        rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
         for lo in range(0, B, rows):
             hi = min(B, lo + rows)
-            res = materialise(lo, hi, eps[:, lo:hi])
+            yield lo, hi, eps[:, lo:hi], dict({k: v[lo:hi] for k, v in labels.items()}, observations=observations[lo:hi])
+
+    def _composed_moments(self, observations, labels, ns, eps, materialise, reduce, names=None):
+        """A composed fallback over ``_chunks``: ``materialise(lo, hi, eps chunk, batch chunk)`` yields the per-draw curves of rows [lo, hi)
+        (``{curve: ...}``) and ``reduce`` turns one curve's into a tuple of ``[rows, C, T]`` tensors; returns ``{curve: tuple of [B, C, T]}``."""
+        names = names or self.MOMENT_HEADS[bool(self.GAUSS)]      # (names: the curves to reduce, where they are not the head curves alone)
+        parts = {n: [] for n in names}
+        for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+            res = materialise(lo, hi, e, d)
             for n in names:
                 parts[n].append(reduce(res[n]))
             del res
         return {n: tuple(torch.cat(col, 0) for col in zip(*chunks)) for n, chunks in parts.items()}
+
+    @staticmethod
+    def _mean_sd(v):
+        """fp32 ``mean`` / ``std(unbiased=False)`` over the sample axis of ``[rows, C, T, ns]``."""
+        v = v.to(torch.float32)
+        return v.mean(dim=-1), v.std(dim=-1, unbiased=False)
 
     @staticmethod
     def _save_arrays(results_dir, named):
@@ -306,7 +347,7 @@ class MechanisticBase(nn.Module):
             bt = b.engine.make_batch(observations, self._label_tensors(labels, B), eps, particles=4 if eps is not None else 1)
             try:
                 return b.engine.eval_stats(b.flat, bt, B, is_post, out)
-            except L.SlodeError:      # ANY engine error leads to the unfused calls here, not a refusal (_raise_unless_refused) alone:
+            except L.SlodeError:      # ANY engine error leads to the unfused calls here, not a refusal (_fused_or_composed) alone:
                 pass                  # they name the same fault themselves, and the row is wanted wherever they can make it
         if eps is not None:
             raise ValueError("explicit eps is taken by the fused statistics call only; this configuration runs the unfused calls")
@@ -341,22 +382,8 @@ class MechanisticBase(nn.Module):
         draws, optional) makes the result reproducible."""
         self._bind()
         with torch.no_grad():
-            B, ns = observations.shape[0], int(num_samples)
-            if is_post:
-                loc, scale = self.encoder.forward(observations)
-            else:
-                loc, scale = self._prior_loc_scale(labels)
-            if eps is None:
-                eps = self._bind().engine.draw_normal(ns * B).view(ns, B, loc.shape[1])
-            z = loc.unsqueeze(0) + scale.unsqueeze(0) * eps.to(loc.device)               # [ns, B, L]
-            out = self.decoder.forward(z=z.reshape(ns * B, -1).contiguous())
-            names = ("solution_xt", "mean", "std") if self.GAUSS else ("solution_xt", "mu_75", "mu_50", "mu_25", "std")
-            res = {"z": z}
-            for name, val in zip(names, out):
-                if name in ("solution_xt", "std"):
-                    continue
-                res[name] = val.reshape(ns, B, val.shape[1], val.shape[2]).permute(1, 2, 3, 0).contiguous()   # [B, C, T, ns]
-            return res
+            _, z = self._draws(*self._loc_scale(observations, is_post, labels), int(num_samples), eps)      # [ns, B, L]
+            return {"z": z, **self._decoded_draws(z)}
 
     def save_recon_samples(self, results_dir: str, observations, is_post, num_samples: int, **labels):
         """Writes the arrays ``multiple_samples`` saves, under the reference's file names (``mu_50_post_sample.npy`` ...)."""
@@ -376,21 +403,14 @@ class MechanisticBase(nn.Module):
         ``[B, C, T, num_samples]`` tensor exists.  ``eps`` ``[num_samples, B, L]`` makes it reproducible; None draws one call of the
         engine's generator, the draw ``recon_samples`` makes.  Where the engine refuses (adaptive solver, strided observations,
         measured arms, LDS budget) the same dict is composed from ``recon_samples`` in chunks over B."""
-        from .. import _lib as L
         b = self._bind()
-        B, ns = observations.shape[0], int(num_samples)
-        if ns < 1:
-            raise ValueError("num_samples must be >= 1, got %d" % ns)
-        names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        try:
+        B, ns = observations.shape[0], self._count(num_samples)
+
+        def fused():
             mean, sd = b.engine.recon_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns)
-            return {n: (mean[q], sd[q]) for q, n in enumerate(names)}
-        except L.SlodeError as err:
-            self._raise_unless_refused(err)
-        # composed from ``recon_samples``, reduced in fp32 with ``mean`` / ``std(unbiased=False)`` over the sample axis
-        return self._composed_moments(
-            B, ns, eps, lambda lo, hi, e: self.recon_samples(observations[lo:hi], is_post, ns, eps=e, **{k: v[lo:hi] for k, v in labels.items()}),
-            lambda v: (v.to(torch.float32).mean(dim=-1), v.to(torch.float32).std(dim=-1, unbiased=False)))
+            return {n: (mean[q], sd[q]) for q, n in enumerate(self.MOMENT_HEADS[bool(self.GAUSS)])}
+        return self._fused_or_composed(fused, lambda: self._composed_moments(
+            observations, labels, ns, eps, lambda lo, hi, e, d: self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d), self._mean_sd))
 
     def save_recon_moments(self, results_dir: str, observations, is_post, num_samples: int, **labels):
         """Writes ``<curve>_<post|prior>_sample_mean.npy`` and ``..._sample_sd.npy`` (``[B, C, T]`` each) for every head curve: new names
@@ -452,43 +472,30 @@ class MechanisticBase(nn.Module):
         0``).  ONE engine call (``slode_cohort_moments``); ``chunk``: members folded per partial, 0 = the library's choice.  Where the engine
         refuses (adaptive solver, strided observations, measured arms, LDS budget, more than 1024 cohorts) the same dict is reduced from
         ``recon_samples`` in chunks of rows in fp64."""
-        from .. import _lib as L
         b = self._bind()
-        B, ns = observations.shape[0], int(num_samples)
-        if ns < 1:
-            raise ValueError("num_samples must be >= 1, got %d" % ns)
-        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        B, ns = observations.shape[0], self._count(num_samples)
         ids, keys, G, members, offsets, count = self._cohort_lists(observations, cohorts, num_cohorts, labels)
-        res = {"count": count, "keys": keys}
-        try:
+
+        def fused():
             mean, sd, sdb, om, l1 = b.engine.cohort_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, members,
                                                             offsets, G, chunk=chunk, clip_min=clip_min)
-            res.update({n: (mean[q], sd[q], sdb[q]) for q, n in enumerate(names)})
-            res.update(observations=om, l1=l1)
-            return res
-        except L.SlodeError as err:
-            self._raise_unless_refused(err)
-        res.update(self._cohort_composed(observations, is_post, ns, ids, G, count, eps, clip_min, labels))
-        return res
+            return dict({n: (mean[q], sd[q], sdb[q]) for q, n in enumerate(self.MOMENT_HEADS[bool(self.GAUSS)])}, observations=om, l1=l1)
+        return dict({"count": count, "keys": keys}, **self._fused_or_composed(
+            fused, lambda: self._cohort_composed(observations, is_post, ns, ids, G, count, eps, clip_min, labels)))
 
     def _cohort_composed(self, observations, is_post, ns, ids, G, count, eps, clip_min, labels):
         """The composed route: ``recon_samples`` of ``MOMENTS_CHUNK_ROWS // ns`` rows at a time (ONE drawing call for the whole batch, sliced
         per chunk), every row's draw mean and sum of squares added to its cohort's fp64 sums."""
         B, dev = observations.shape[0], observations.device
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        if eps is None:
-            eps = self._bind().engine.draw_normal(ns * B).view(ns, B, -1)
-        eps = eps.reshape(ns, B, -1)
         Cn, T = observations.shape[1], observations.shape[2]
         slot = torch.where(ids < 0, torch.full_like(ids, G), ids)           # (bucket G: the trajectories of no cohort)
         s1 = {n: torch.zeros(G + 1, Cn, T, dtype=torch.float64, device=dev) for n in names}
         sb2 = {n: torch.zeros_like(s1[n]) for n in names}
         sv2 = {n: torch.zeros_like(s1[n]) for n in names}
         so = torch.zeros(G + 1, Cn, T, dtype=torch.float64, device=dev).index_add_(0, slot, observations.to(torch.float64))
-        rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
-        for lo in range(0, B, rows):
-            hi = min(B, lo + rows)
-            got = self.recon_samples(observations[lo:hi], is_post, ns, eps=eps[:, lo:hi], **{k: v[lo:hi] for k, v in labels.items()})
+        for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+            got = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
             for n in names:
                 v = got[n].to(torch.float64)                                # [rows, C, T, ns]
                 if clip_min is not None:
@@ -562,13 +569,7 @@ class MechanisticBase(nn.Module):
         t = self._forecast_times(times_out)
         with torch.no_grad():
             B, ns = observations.shape[0], int(num_samples)
-            if is_post:
-                loc, scale = self.encoder.forward(observations)
-            else:
-                loc, scale = self._prior_loc_scale(labels)
-            if eps is None:
-                eps = b.engine.draw_normal(ns * B).view(ns, B, loc.shape[1])
-            z = loc.unsqueeze(0) + scale.unsqueeze(0) * eps.to(loc.device).reshape(ns, B, -1)        # [ns, B, L]
+            _, z = self._draws(*self._loc_scale(observations, is_post, labels), ns, eps)             # [ns, B, L]
             x = b.engine.ode_solve(b.flat, z.reshape(ns * B, -1).contiguous(), times=t)              # [ns * B, T_out, S]
             heads = b.engine.unpack(b.flat)
             res = {"z": z}
@@ -589,27 +590,22 @@ class MechanisticBase(nn.Module):
         ONE engine call (``slode_forecast_moments``), which walks the grid in windows of ``window`` steps (0: the library's choice).  Where
         the engine refuses (adaptive solver, strided observations, measured arms, the plan) the same dict is composed from
         ``forecast_samples`` in chunks over B."""
-        from .. import _lib as L
         b = self._bind()
-        B, ns = observations.shape[0], int(num_samples)
-        if ns < 1:
-            raise ValueError("num_samples must be >= 1, got %d" % ns)
+        B, ns = observations.shape[0], self._count(num_samples)
         t = self._forecast_times(times_out)
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        try:
+
+        def fused():
             mean, sd, xm, xs = b.engine.forecast_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, t,
                                                          states=states, window=window)
             res = {n: (mean[q], sd[q]) for q, n in enumerate(names)}
             if states:
                 res["solution_xt"] = (xm.permute(0, 2, 1), xs.permute(0, 2, 1))
             return res
-        except L.SlodeError as err:
-            self._raise_unless_refused(err)
-        return self._composed_moments(
-            B, ns, eps, lambda lo, hi, e: self.forecast_samples(observations[lo:hi], is_post, ns, t, eps=e, states=states,
-                                                                **{k: v[lo:hi] for k, v in labels.items()}),
-            lambda v: (v.to(torch.float32).mean(dim=-1), v.to(torch.float32).std(dim=-1, unbiased=False)),
-            names=names + (("solution_xt",) if states else ()))
+        return self._fused_or_composed(fused, lambda: self._composed_moments(
+            observations, labels, ns, eps,
+            lambda lo, hi, e, d: self.forecast_samples(is_post=is_post, num_samples=ns, times_out=t, eps=e, states=states, **d),
+            self._mean_sd, names=names + (("solution_xt",) if states else ())))
 
     def save_forecast_moments(self, results_dir: str, observations, is_post, num_samples: int, times_out, **labels):
         """Writes ``<curve>_<post|prior>_forecast_mean.npy`` / ``..._forecast_sd.npy`` (``[B, C, T_out]`` each) for every head curve and
@@ -643,9 +639,8 @@ class MechanisticBase(nn.Module):
         ploc_g(u') + pscale_g(u') eps inside them (``_prior_loc_scale`` on the swapped labels).  Composed from the encoder, the prior nets and
         ``decoder.forward`` on both latents; ``eps`` ``[num_samples, B, L]`` or None (one drawing call of the engine's generator)."""
         mask, swapped = self._intervened(intervene, labels)
-        b = self._bind()
+        self._bind()
         with torch.no_grad():
-            B, ns = observations.shape[0], int(num_samples)
             loc, scale = self.encoder.forward(observations)
             cloc, cscale = loc.clone(), scale.clone()
             if mask:
@@ -655,17 +650,9 @@ class MechanisticBase(nn.Module):
                         lo = self.z_off[zgroups[0]]
                         hi = lo + sum(self.z_dims[z] for z in zgroups)
                         cloc[:, lo:hi], cscale[:, lo:hi] = ploc[:, lo:hi], pscale[:, lo:hi]
-            if eps is None:
-                eps = b.engine.draw_normal(ns * B).view(ns, B, loc.shape[1])
-            e = eps.to(loc.device).reshape(ns, B, -1)
-            z_f = loc.unsqueeze(0) + scale.unsqueeze(0) * e
+            e, z_f = self._draws(loc, scale, int(num_samples), eps)
             z_cf = cloc.unsqueeze(0) + cscale.unsqueeze(0) * e
-            names = ("solution_xt", "mean", "std") if self.GAUSS else ("solution_xt", "mu_75", "mu_50", "mu_25", "std")
-            arms = []
-            for z in (z_f, z_cf):
-                out = self.decoder.forward(z=z.reshape(ns * B, -1).contiguous())
-                arms.append({n: v.reshape(ns, B, v.shape[1], v.shape[2]).permute(1, 2, 3, 0).contiguous()
-                             for n, v in zip(names, out) if n not in ("solution_xt", "std")})
+            arms = [self._decoded_draws(z) for z in (z_f, z_cf)]
             res = {n: (arms[0][n], arms[1][n]) for n in self.MOMENT_HEADS[bool(self.GAUSS)]}
             res["z"] = (z_f, z_cf)
             return res
@@ -680,30 +667,27 @@ class MechanisticBase(nn.Module):
         no ``[B, C, T, num_samples]`` tensor exists.  ``eps`` ``[num_samples, B, L]`` makes it reproducible; None draws one call of the
         engine's generator.  Where the engine refuses (adaptive solver, strided observations, measured arms, LDS budget) the same dict is
         composed from ``counterfactual_samples`` in chunks over B."""
-        from .. import _lib as L
-        B, ns = observations.shape[0], int(num_samples)
-        if ns < 1:
-            raise ValueError("num_samples must be >= 1, got %d" % ns)
+        B, ns = observations.shape[0], self._count(num_samples)
         mask, swapped = self._intervened(intervene, labels)
         b = self._bind()
-        names = self.MOMENT_HEADS[bool(self.GAUSS)]
         # every label tensor goes to the engine, the named ones with their counterfactual values: a prior group over several labels
         # (challenge, proc) reads all of its columns, whichever of them were named
         cf = self._label_tensors(swapped, B)
-        try:
+
+        def fused():
             cm, cs, em, es = b.engine.intervene_moments(b.flat, self._draws_batch(observations, labels, eps, ns), B, cf if mask else None, mask, ns)
-            return {n: {"cf": (cm[q], cs[q]), "effect": (em[q], es[q])} for q, n in enumerate(names)}
-        except L.SlodeError as err:
-            self._raise_unless_refused(err)
+            return {n: {"cf": (cm[q], cs[q]), "effect": (em[q], es[q])} for q, n in enumerate(self.MOMENT_HEADS[bool(self.GAUSS)])}
 
         def paired(arms):      # (factual, counterfactual) [rows, C, T, ns] -> moments of the counterfactual and of the paired difference
             f, c = (v.to(torch.float32) for v in arms)
             d = c - f
             return c.mean(dim=-1), c.std(dim=-1, unbiased=False), d.mean(dim=-1), d.std(dim=-1, unbiased=False)
-        res = self._composed_moments(
-            B, ns, eps, lambda lo, hi, e: self.counterfactual_samples(observations[lo:hi], ns, {k: swapped[k][lo:hi] for k in intervene}, eps=e,
-                                                                       **{k: v[lo:hi] for k, v in labels.items()}), paired)
-        return {n: {"cf": (v[0], v[1]), "effect": (v[2], v[3])} for n, v in res.items()}
+
+        def composed():
+            res = self._composed_moments(observations, labels, ns, eps, lambda lo, hi, e, d: self.counterfactual_samples(
+                num_samples=ns, intervene={k: swapped[k][lo:hi] for k in intervene}, eps=e, **d), paired)
+            return {n: {"cf": (v[0], v[1]), "effect": (v[2], v[3])} for n, v in res.items()}
+        return self._fused_or_composed(fused, composed)
 
     def save_intervention_moments(self, results_dir: str, observations, num_samples: int, intervene, **labels):
         """Writes ``<curve>_cf_<names>_sample_mean.npy`` / ``..._sample_sd.npy`` and ``<curve>_effect_<names>_sample_mean.npy`` /
@@ -728,9 +712,7 @@ class MechanisticBase(nn.Module):
         of call n + k, as a K-particle ELBO step draws).  What the engine refuses (adaptive solver, strided observations, measured arms,
         LDS budget) raises its SlodeError: no other call yields a per-trajectory loss to compose from."""
         b = self._bind()
-        B, K = observations.shape[0], int(num_draws)
-        if K < 1:
-            raise ValueError("num_draws must be >= 1, got %d" % K)
+        B, K = observations.shape[0], self._count(num_draws, "num_draws")
         bounds, loss = b.engine.traj_bounds(b.flat, self._draws_batch(observations, labels, eps, K), B, K)
         res = {n: bounds[:, i] for i, n in enumerate(self.BOUND_NAMES)}
         if return_draws:

@@ -196,35 +196,34 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     tail = "ELBO: best_epoch: {} post: {} prior: {}".format(best_epoch, test_post["elbo"], test_prior["elbo"])
     print(tail)
     logging.debug(tail)
+    out_dir = results_dir or "results_%s" % config.model
+    if sample_moments or cohort_curves or forecast_steps:      # (the stages that draw; a config without num_samples serves the others)
+        num_samples = int(getattr(config, "num_samples", 200))
     if sample_moments:
         d = batch_to_device(next(iter(test_b)), device, family)
-        out_dir = results_dir or "results_%s" % config.model
         for is_post in (True, False):
-            written = best_model.save_recon_moments(out_dir, is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), **d)
+            written = best_model.save_recon_moments(out_dir, is_post=is_post, num_samples=num_samples, **d)
             logging.debug("multiple_samples moments: %s", written)
     if cohort_curves:
         d = batch_to_device(next(iter(test_b)), device, family)
-        out_dir = results_dir or "results_%s" % config.model
         for is_post in (True, False):
-            res = best_model.cohort_moments(is_post=is_post, num_samples=int(getattr(config, "num_samples", 200)), cohorts=tuple(best_model.LABELS), **d)
+            res = best_model.cohort_moments(is_post=is_post, num_samples=num_samples, cohorts=tuple(best_model.LABELS), **d)
             written = best_model._save_arrays(out_dir, best_model._cohort_named(res, is_post))
             line = "l1_error_%s: %s" % ("post" if is_post else "prior", float(res["l1"][res["count"] > 0].mean()))
             print(line)
             logging.debug("%s (%s)", line, written)
     if test_bounds:
-        path = best_model.save_trajectory_bounds(results_dir or "results_%s" % config.model,
-                                                 (batch_to_device(b, device, family) for b in val_b), int(test_bounds))
+        path = best_model.save_trajectory_bounds(out_dir, (batch_to_device(b, device, family) for b in val_b), int(test_bounds))
         logging.debug("per-trajectory bounds: %s", path)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
         for b in val_b:
             d = batch_to_device(b, device, family)
-            for name, moments in best_model.forecast_moments(is_post=True, num_samples=int(getattr(config, "num_samples", 200)), times_out=t_out, **d).items():
+            for name, moments in best_model.forecast_moments(is_post=True, num_samples=num_samples, times_out=t_out, **d).items():
                 for kind, val in zip(("mean", "sd"), moments):
                     parts.setdefault("%s_post_forecast_%s.npy" % (name, kind), []).append(val)
-        written = best_model._save_arrays(results_dir or "results_%s" % config.model,
-                                          [(f, torch.cat(v, 0)) for f, v in parts.items()] + [("forecast_times.npy", t_out)])
+        written = best_model._save_arrays(out_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()] + [("forecast_times.npy", t_out)])
         logging.debug("forecast moments: %s", written)
     return var_model, best_model, best_epoch
 

@@ -3,66 +3,21 @@
 // tests/test_cohort_cpu.py holds the expected status and the words each message must carry.  No refusal touches HIP and a refused call
 // launches nothing, so this program makes NO call that would be taken: a taken call would launch.
 // Build (host pass only): hipcc -x hip --cuda-host-only -std=c++17 cohort_refusals.cpp -x none <package dir>/libslode.so
-#include "../../structured_latent_odes_amd/csrc/slode_common.h"
+#include "../refusals_common.h"
 
-#include <functional>
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 
-alignas(64) static float g_mem[64];   // stands for every device buffer: non-NULL, never read or written
-static float* const DEV = g_mem;
-static const size_t BIG = (size_t)1 << 40;   // workspace and scratch are "large enough" unless a case says otherwise
-
-struct Cfg {
-  slode_ctx ctx;
-  slode_shape s;
-  slode_batch b;
-  bool no_handle = false, no_shape = false, no_layout = false, no_params = false, no_batch = false;
-  const float *times = DEV, *stage_t = DEV;
+struct Cfg : BaseCfg {
   const int32_t *members = (const int32_t*)DEV, *offsets = (const int32_t*)DEV;
   float *mean = DEV, *sd = DEV, *sdb = DEV, *obs_mean = DEV, *l1 = DEV;
-  void *ws = DEV, *scratch = DEV;
-  size_t ws_bytes = BIG, scratch_bytes = BIG;
-  int draws = 2, is_post = 1, M = 3, G = 2, chunk = 0;
+  void* scratch = DEV;
+  size_t scratch_bytes = BIG;   // (the scratch too is "large enough" unless a case says otherwise)
+  int M = 3, G = 2, chunk = 0;
 };
 
-// B = 4, T = 86, C = 3 with the cvs prior groups (tests/eval_refusals/eval_refusals.cpp), dense [B,T,C] observations, two label tensors
-static Cfg base() {
-  Cfg c;
-  memset(&c.ctx, 0, sizeof(c.ctx));
-  c.ctx.num_cu = 256; c.ctx.enc_fuse = 1; c.ctx.rng_seed = 3;
-  memset(&c.s, 0, sizeof(c.s));
-  c.s.B = 4; c.s.T = 86; c.s.C = 3; c.s.L = 8; c.s.S = 5; c.s.H = 25; c.s.F = 10; c.s.K = 10; c.s.P = 5; c.s.Hc = 50;
-  c.s.n_u = 2; c.s.n_groups = 2; c.s.groups[0] = slode_group{0, 3, 0, 1}; c.s.groups[1] = slode_group{3, 3, 1, 1};
-  c.s.method = SLODE_RK4; c.s.likelihood = SLODE_ALD; c.s.quantile_diff = 0.475f; c.s.rtol = 1e-7f; c.s.atol = 1e-9f;
-  memset(&c.b, 0, sizeof(c.b));
-  c.b.obs = DEV; c.b.obs_strides[0] = (int64_t)c.s.C * c.s.T; c.b.obs_strides[1] = 1; c.b.obs_strides[2] = c.s.C;
-  c.b.n_labels = 2; c.b.label_width[0] = c.b.label_width[1] = 1; c.b.labels[0] = c.b.labels[1] = DEV;
-  return c;
-}
-
-static void run(const char* name, Cfg c) {
-  slode_layout lay;
-  slode_shape plain = base().s;   // (the layout of the unmodified shape where the case's own shape is not a valid one)
-  if (slode_layout_init(&c.s, &lay) != SLODE_OK) slode_layout_init(&plain, &lay);
-  c.ctx.rng_counter = 7;
-  slode_handle h = c.no_handle ? nullptr : &c.ctx;
-  const int rc = slode_cohort_moments(h, c.no_shape ? nullptr : &c.s, c.no_layout ? nullptr : &lay, c.no_params ? nullptr : DEV, c.times,
-                                      c.stage_t, c.no_batch ? nullptr : &c.b, c.is_post, c.draws, c.members, c.offsets, c.M, c.G, c.chunk,
-                                      -INFINITY, c.mean, c.sd, c.sdb, c.obs_mean, c.l1, c.scratch, c.scratch_bytes, c.ws, c.ws_bytes, nullptr);
-  printf("%s | %d | %llu | %s\n", name, rc, (unsigned long long)c.ctx.rng_counter, slode_last_error(h));
-}
-
-typedef std::function<void(Cfg&)> Edit;
-static void one(const char* name, const Edit& edit) { Cfg c = base(); edit(c); run(name, c); }
-// posterior and prior
-static void both(const char* name, const Edit& edit) {
-  char n[128];
-  for (int post : {1, 0}) {
-    snprintf(n, sizeof(n), "%s: %s", post ? "post" : "prior", name);
-    Cfg c = base(); c.is_post = post; edit(c); run(n, c);
-  }
+static int call(int, Cfg& c, const Head& a, const char**) {
+  return slode_cohort_moments(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.is_post, c.draws, c.members, c.offsets, c.M, c.G, c.chunk, -INFINITY,
+                              c.mean, c.sd, c.sdb, c.obs_mean, c.l1, c.scratch, c.scratch_bytes, c.ws, c.ws_bytes, nullptr);
 }
 
 int main() {

@@ -4,79 +4,34 @@
 // tests/golden/eval_refusals.txt holds these lines; tests/test_host_cpu.py compares.  No refusal touches HIP and a refused call
 // launches nothing, so this program makes NO call that would be taken: a taken call would launch.
 // Build (host pass only): hipcc -x hip --cuda-host-only -std=c++17 eval_refusals.cpp -x none <package dir>/libslode.so
-#include "../../structured_latent_odes_amd/csrc/slode_common.h"
-
-#include <functional>
-#include <stdio.h>
-#include <string.h>
-
-alignas(64) static float g_mem[64];   // stands for every device buffer: non-NULL, never read or written
-static float* const DEV = g_mem;
-static const size_t WS_BYTES = (size_t)1 << 40;   // the workspace is "large enough" unless a case says otherwise
+#include "../refusals_common.h"
 
 enum Call { STATS = 0, RECON = 1, BOUNDS = 2, INTERVENE = 3 };
 static const char* const CALL_NAME[] = {"eval_stats", "recon_moments", "traj_bounds", "intervene_moments"};
 
-struct Cfg {
-  slode_ctx ctx;
-  slode_shape s;
-  slode_batch b;
-  bool no_handle = false, no_shape = false, no_layout = false, no_params = false, no_batch = false;
-  const float *times = DEV, *stage_t = DEV;
+struct Cfg : BaseCfg {
   float *out = DEV, *second = DEV;   // out / mean / bounds / cf_mean, and sd / loss_kb / cf_sd
-  void* ws = DEV;
-  size_t ws_bytes = WS_BYTES;
-  int draws = 2, is_post = 1;
   unsigned int mask = 0;
   const float* cf[SLODE_MAX_LABELS] = {DEV, DEV, nullptr, nullptr};
   bool no_cf = false;
 };
-
-// B = 4, T = 86, C = 3 with the cvs prior groups (tests/test_host_cpu.py::_shape), dense [B,T,C] observations, two label tensors
-static Cfg base() {
-  Cfg c;
-  memset(&c.ctx, 0, sizeof(c.ctx));
-  c.ctx.num_cu = 256; c.ctx.enc_fuse = 1; c.ctx.rng_seed = 3;
-  memset(&c.s, 0, sizeof(c.s));
-  c.s.B = 4; c.s.T = 86; c.s.C = 3; c.s.L = 8; c.s.S = 5; c.s.H = 25; c.s.F = 10; c.s.K = 10; c.s.P = 5; c.s.Hc = 50;
-  c.s.n_u = 2; c.s.n_groups = 2; c.s.groups[0] = slode_group{0, 3, 0, 1}; c.s.groups[1] = slode_group{3, 3, 1, 1};
-  c.s.method = SLODE_RK4; c.s.likelihood = SLODE_ALD; c.s.quantile_diff = 0.475f; c.s.rtol = 1e-7f; c.s.atol = 1e-9f;
-  memset(&c.b, 0, sizeof(c.b));
-  c.b.obs = DEV; c.b.obs_strides[0] = (int64_t)c.s.C * c.s.T; c.b.obs_strides[1] = 1; c.b.obs_strides[2] = c.s.C;
-  c.b.n_labels = 2; c.b.label_width[0] = c.b.label_width[1] = 1; c.b.labels[0] = c.b.labels[1] = DEV;
-  return c;
-}
 // the proc-like shape whose tables exceed the LDS: T = 1024, S = 8, C = 4, dense [B,C,T] observations
 static void big_tables(Cfg& c) {
   c.s.T = 1024; c.s.S = 8; c.s.C = 4;
   c.b.obs_strides[0] = (int64_t)c.s.C * c.s.T; c.b.obs_strides[1] = c.s.T; c.b.obs_strides[2] = 1;
 }
 
-static void run(const char* name, int call, Cfg c) {
-  slode_layout lay;
-  slode_shape plain = base().s;   // (the layout of the unmodified shape where the case's own shape is not a valid one)
-  if (slode_layout_init(&c.s, &lay) != SLODE_OK) slode_layout_init(&plain, &lay);
-  c.ctx.rng_counter = 7;
-  slode_handle h = c.no_handle ? nullptr : &c.ctx;
-  const slode_shape* s = c.no_shape ? nullptr : &c.s;
-  const slode_layout* l = c.no_layout ? nullptr : &lay;
-  const float* p = c.no_params ? nullptr : DEV;
-  const slode_batch* b = c.no_batch ? nullptr : &c.b;
+static int call(int which, Cfg& c, const Head& a, const char** column) {
   const float* const* cf = c.no_cf ? nullptr : c.cf;
-  int rc = 0;
-  switch (call) {
-    case STATS: rc = slode_eval_stats(h, s, l, p, c.times, c.stage_t, b, c.is_post, c.out, c.ws, c.ws_bytes, nullptr); break;
-    case RECON: rc = slode_recon_moments(h, s, l, p, c.times, c.stage_t, b, c.is_post, c.draws, c.out, c.second, c.ws, c.ws_bytes, nullptr); break;
-    case BOUNDS: rc = slode_traj_bounds(h, s, l, p, c.times, c.stage_t, b, c.draws, c.out, c.second, c.ws, c.ws_bytes, nullptr); break;
-    default: rc = slode_intervene_moments(h, s, l, p, c.times, c.stage_t, b, cf, c.mask, c.draws, c.out, c.second, DEV, DEV, c.ws, c.ws_bytes, nullptr);
+  *column = CALL_NAME[which];
+  switch (which) {
+    case STATS: return slode_eval_stats(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.is_post, c.out, c.ws, c.ws_bytes, nullptr);
+    case RECON: return slode_recon_moments(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.is_post, c.draws, c.out, c.second, c.ws, c.ws_bytes, nullptr);
+    case BOUNDS: return slode_traj_bounds(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.draws, c.out, c.second, c.ws, c.ws_bytes, nullptr);
+    default: return slode_intervene_moments(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, cf, c.mask, c.draws, c.out, c.second, DEV, DEV, c.ws, c.ws_bytes, nullptr);
   }
-  printf("%s | %s | %d | %llu | %s\n", name, CALL_NAME[call], rc, (unsigned long long)c.ctx.rng_counter, slode_last_error(h));
 }
 
-typedef std::function<void(Cfg&)> Edit;
-static void each(const char* name, std::initializer_list<int> calls, const Edit& edit) {
-  for (int call : calls) { Cfg c = base(); edit(c); run(name, call, c); }
-}
 #define ALL {STATS, RECON, BOUNDS, INTERVENE}
 #define DRAWN {RECON, BOUNDS, INTERVENE}
 

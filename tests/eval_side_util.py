@@ -22,6 +22,16 @@ SHAPES = {
     "wide_head": ("cvs", dict(z_iext=17, z_rtpr=3, z_eps=2), 64, 5),              # a label head that reads 17 latent dims
 }
 BLOCK_EDGES = [1, 63, 64, 65, 255, 256, 257, 1023, 1025, 4097]
+DP5_TOL = dict(rtol=1e-7, atol=1e-9, per_trajectory=True)        # the engine's (torchdiffeq's) default tolerances
+
+
+def _p64(m):
+    return {k: v.detach().cpu().double().clone() for k, v in m.state_dict().items()}
+
+
+def _heads64(p, ospec, sol):
+    names = {"mean": "output_mean"} if ospec.gauss else {"mu_50": "output_q50", "mu_75": "output_q75", "mu_25": "output_q25"}
+    return {k: F.linear(sol, p["decoder.%s.0.weight" % n]).permute(0, 2, 1) for k, n in names.items()}
 
 
 def case_cpu(name, solver="rk4", seed=11):

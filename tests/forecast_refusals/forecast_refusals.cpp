@@ -4,64 +4,17 @@
 // tests/golden/forecast_refusals.txt holds these lines; tests/test_forecast_cpu.py compares.  No refusal touches HIP and a refused call
 // launches nothing, so this program makes NO call that would be taken: a taken call would launch.
 // Build (host pass only): hipcc -x hip --cuda-host-only -std=c++17 forecast_refusals.cpp -x none <package dir>/libslode.so
-#include "../../structured_latent_odes_amd/csrc/slode_common.h"
+#include "../refusals_common.h"
 
-#include <functional>
-#include <stdio.h>
-#include <string.h>
-
-alignas(64) static float g_mem[64];   // stands for every device buffer: non-NULL, never read or written
-static float* const DEV = g_mem;
-static const size_t WS_BYTES = (size_t)1 << 40;   // the workspace is "large enough" unless a case says otherwise
-
-struct Cfg {
-  slode_ctx ctx;
-  slode_shape s;
-  slode_batch b;
-  bool no_handle = false, no_shape = false, no_layout = false, no_params = false, no_batch = false;
-  const float *times = DEV, *stage_t = DEV, *times_out = DEV, *stage_t_out = DEV;
+struct Cfg : BaseCfg {
+  const float *times_out = DEV, *stage_t_out = DEV;
   float *mean = DEV, *sd = DEV, *x_mean = DEV, *x_sd = DEV;
-  void* ws = DEV;
-  size_t ws_bytes = WS_BYTES;
-  int draws = 2, is_post = 1, T_out = 95, window = 0;
+  int T_out = 95, window = 0;
 };
 
-// B = 4, T = 86, C = 3 with the cvs prior groups (tests/eval_refusals/eval_refusals.cpp), dense [B,T,C] observations, two label tensors
-static Cfg base() {
-  Cfg c;
-  memset(&c.ctx, 0, sizeof(c.ctx));
-  c.ctx.num_cu = 256; c.ctx.enc_fuse = 1; c.ctx.rng_seed = 3;
-  memset(&c.s, 0, sizeof(c.s));
-  c.s.B = 4; c.s.T = 86; c.s.C = 3; c.s.L = 8; c.s.S = 5; c.s.H = 25; c.s.F = 10; c.s.K = 10; c.s.P = 5; c.s.Hc = 50;
-  c.s.n_u = 2; c.s.n_groups = 2; c.s.groups[0] = slode_group{0, 3, 0, 1}; c.s.groups[1] = slode_group{3, 3, 1, 1};
-  c.s.method = SLODE_RK4; c.s.likelihood = SLODE_ALD; c.s.quantile_diff = 0.475f; c.s.rtol = 1e-7f; c.s.atol = 1e-9f;
-  memset(&c.b, 0, sizeof(c.b));
-  c.b.obs = DEV; c.b.obs_strides[0] = (int64_t)c.s.C * c.s.T; c.b.obs_strides[1] = 1; c.b.obs_strides[2] = c.s.C;
-  c.b.n_labels = 2; c.b.label_width[0] = c.b.label_width[1] = 1; c.b.labels[0] = c.b.labels[1] = DEV;
-  return c;
-}
-
-static void run(const char* name, Cfg c) {
-  slode_layout lay;
-  slode_shape plain = base().s;   // (the layout of the unmodified shape where the case's own shape is not a valid one)
-  if (slode_layout_init(&c.s, &lay) != SLODE_OK) slode_layout_init(&plain, &lay);
-  c.ctx.rng_counter = 7;
-  slode_handle h = c.no_handle ? nullptr : &c.ctx;
-  const int rc = slode_forecast_moments(h, c.no_shape ? nullptr : &c.s, c.no_layout ? nullptr : &lay, c.no_params ? nullptr : DEV, c.times,
-                                        c.stage_t, c.no_batch ? nullptr : &c.b, c.is_post, c.draws, c.times_out, c.stage_t_out, c.T_out, c.window,
-                                        c.mean, c.sd, c.x_mean, c.x_sd, c.ws, c.ws_bytes, nullptr);
-  printf("%s | %d | %llu | %s\n", name, rc, (unsigned long long)c.ctx.rng_counter, slode_last_error(h));
-}
-
-typedef std::function<void(Cfg&)> Edit;
-static void one(const char* name, const Edit& edit) { Cfg c = base(); edit(c); run(name, c); }
-// posterior and prior
-static void both(const char* name, const Edit& edit) {
-  char n[96];
-  for (int post : {1, 0}) {
-    snprintf(n, sizeof(n), "%s: %s", post ? "post" : "prior", name);
-    Cfg c = base(); c.is_post = post; edit(c); run(n, c);
-  }
+static int call(int, Cfg& c, const Head& a, const char**) {
+  return slode_forecast_moments(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.is_post, c.draws, c.times_out, c.stage_t_out, c.T_out, c.window,
+                                c.mean, c.sd, c.x_mean, c.x_sd, c.ws, c.ws_bytes, nullptr);
 }
 
 int main() {
@@ -122,7 +75,7 @@ int main() {
   both("unfit window + label columns 3", [](Cfg& c) { c.T_out = 5000; c.window = 4000; c.b.label_width[1] = 2; });
   // ---- slode_stage_times_n
   {
-    Cfg c = base();
+    Cfg c;
     slode_handle h = &c.ctx;
     c.ctx.rng_counter = 7;
     struct { const char* name; slode_handle h; const slode_shape* s; int n; const float* t; float* st; } cases[] = {
@@ -130,8 +83,7 @@ int main() {
         {"stage_times_n: n_times 1", h, &c.s, 1, DEV, DEV}, {"stage_times_n: n_times 2^20 + 1", h, &c.s, (1 << 20) + 1, DEV, DEV},
         {"stage_times_n: times NULL", h, &c.s, 95, nullptr, DEV}, {"stage_times_n: stage_t NULL", h, &c.s, 95, DEV, nullptr}};
     for (const auto& k : cases) {
-      const int rc = slode_stage_times_n(k.h, k.s, k.n, k.t, k.st, nullptr);
-      printf("%s | %d | %llu | %s\n", k.name, rc, (unsigned long long)c.ctx.rng_counter, slode_last_error(k.h));
+      report(k.name, nullptr, slode_stage_times_n(k.h, k.s, k.n, k.t, k.st, nullptr), c, k.h);
     }
   }
   return 0;

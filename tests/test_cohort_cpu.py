@@ -158,19 +158,8 @@ def test_cohort_refusals_on_a_hand_filled_handle(tmp_path):
     the untouched drawing-call counter against LADDER; and line by line -- status, counter and the full message, which check speaks first
     when two conditions hold included -- against tests/golden/cohort_refusals.txt, recorded from the library before the draw-walking calls
     shared one host tail."""
-    import subprocess
-    from structured_latent_odes_amd import _lib as L
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not present: the refusal program is not built")
-    lib = os.path.abspath(L.LIB_PATH)
-    exe = str(tmp_path / "cohort_refusals")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-Wall", "-O1", os.path.join(ROOT, "tests", "cohort_refusals", "cohort_refusals.cpp"),
-                        "-o", exe, "-x", "none", lib, "-Wl,-rpath," + os.path.dirname(lib)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = r.stdout.splitlines()
+    from tests.refusals_util import refusal_lines
+    lines = refusal_lines("cohort_refusals", tmp_path)
     assert len(lines) > 90
     want = open(os.path.join(ROOT, "tests", "golden", "cohort_refusals.txt")).read().splitlines()
     for i, (g, w) in enumerate(zip(lines, want)):

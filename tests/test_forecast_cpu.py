@@ -138,19 +138,8 @@ def test_forecast_refusals_match_the_recorded_ladder(tmp_path):
     """Every refusing configuration of slode_forecast_moments (posterior and prior) and of slode_stage_times_n on a hand-filled handle: no
     device, no HIP call, no call that would be taken.  Status, message and the untouched drawing-call counter, line by line against
     tests/golden/forecast_refusals.txt -- which check speaks first when two conditions hold included."""
-    import subprocess
-    from structured_latent_odes_amd import _lib as L
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not present: the refusal program is not built")
-    lib = os.path.abspath(L.LIB_PATH)
-    exe = str(tmp_path / "forecast_refusals")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-Wall", "-O1", os.path.join(ROOT, "tests", "forecast_refusals", "forecast_refusals.cpp"),
-                        "-o", exe, "-x", "none", lib, "-Wl,-rpath," + os.path.dirname(lib)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = r.stdout.splitlines()
+    from tests.refusals_util import refusal_lines
+    got = refusal_lines("forecast_refusals", tmp_path)
     want = open(os.path.join(ROOT, "tests", "golden", "forecast_refusals.txt")).read().splitlines()
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)

@@ -12,8 +12,9 @@ import torch
 from tests import cohort_util as CU
 from tests import eval_stats_util as EU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import ADAPTIVE, DEV, WIDTHS, _device_batch, _engine, _eps_dev
-from tests.test_gpu_recon_moments import _model, _moments
+from tests.eval_gpu_util import (ADAPTIVE, DEV, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _model_batches, _on_device, _padded,
+                                 _peak, _refused)
+from tests.eval_gpu_util import _recon_moments as _moments
 
 pytestmark = pytest.mark.gpu
 ALL = ("sd", "sd_subjects", "obs_mean", "l1")
@@ -275,23 +276,7 @@ def test_launches_and_graph_capture():
     scratch = torch.zeros(eng.cohort_plan(c["B"], members.numel(), G, 7, 3)[3] // 4, device=DEV)
     bt = eng.make_batch(obs_d, labels, eps, particles=7)
     call = lambda: eng.cohort_moments(flat, bt, c["B"], True, 7, members, offsets, G, 3, None, *out, scratch=scratch)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        call()
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = [x.clone() for x in out]
-    for x in out:
-        x.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        call()
-    torch.cuda.synchronize(DEV)
-    assert all(x.abs().sum().item() == 0.0 for x in out), "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want = _captured(call, out)
     assert all(_same(x, y) for x, y in zip(out, want)) and bool(torch.isfinite(out[0][:, :2]).all())     # (cohort 2 of these ids is empty: NaN)
 
 
@@ -305,17 +290,11 @@ def test_refusals_write_nothing_and_draw_nothing(monkeypatch):
 
     def refused(eng, match, obs=obs_d, ns=2, is_post=True, G=G, chunk=0, offsets=offsets, scratch=None, outputs=ALL):
         flat = eng.pack(c["p"])
-        eng.rng_seed(3)
-        eng.rng_set_counter(4)
-        eng.profile_enable(True)
         mean = torch.full((3, max(G, 1), 3, c["T"]), 7.0, device=DEV)
-        with pytest.raises(L.SlodeError, match=match):
-            eng.cohort_moments(flat, eng.make_batch(obs, labels, None), c["B"], is_post, ns, members, offsets, G, chunk=chunk, mean=mean,
-                               outputs=outputs, scratch=scratch)
+        _refused(eng, lambda: eng.cohort_moments(flat, eng.make_batch(obs, labels, None), c["B"], is_post, ns, members, offsets, G, chunk=chunk,
+                                                 mean=mean, outputs=outputs, scratch=scratch), match)
         torch.cuda.synchronize(DEV)
-        assert eng.rng_state() == (3, 0, 4) and bool((mean == 7.0).all())
-        with pytest.raises(L.SlodeError, match="no profiled step"):
-            eng.profile_read()
+        assert bool((mean == 7.0).all())
 
     eng = _engine(c, monkeypatch)
     some = torch.zeros(1 << 16, device=DEV)
@@ -325,17 +304,16 @@ def test_refusals_write_nothing_and_draw_nothing(monkeypatch):
     refused(eng, "chunk = 65", chunk=65)
     refused(eng, "G = 1025", G=1025, offsets=torch.zeros(1026, dtype=torch.int32, device=DEV))
     refused(eng, "scratch_bytes", scratch=torch.zeros(64, device=DEV))
-    padded = torch.zeros(c["B"], 3, c["T"] + 3, device=DEV)
-    padded[:, :, :c["T"]] = obs_d
-    refused(eng, "observation strides", obs=padded[:, :, :c["T"]], scratch=some)
-    refused(eng, "obs_mean / l1 need dense", obs=padded[:, :, :c["T"]], is_post=False, scratch=some)
+    padded = _padded(obs_d)
+    refused(eng, "observation strides", obs=padded, scratch=some)
+    refused(eng, "obs_mean / l1 need dense", obs=padded, is_post=False, scratch=some)
     for env in ({"SLODE_ODE_ALG": "1"}, {"SLODE_FOLD_NEXT": "1"}):
         refused(_engine(c, monkeypatch, env), "measured arms", scratch=some)
     refused(_engine(c, monkeypatch, {"SLODE_NO_FOLD": "1"}), "SLODE_NO_FOLD", scratch=some)
     # the prior without obs_mean / l1 reads no observations: their strides do not matter
     eng = _engine(c, monkeypatch)
     flat = eng.pack(c["p"])
-    got = _cohort(eng, flat, c, False, ids, G, outputs=("sd", "sd_subjects"), obs_d=padded[:, :, :c["T"]], labels=labels)
+    got = _cohort(eng, flat, c, False, ids, G, outputs=("sd", "sd_subjects"), obs_d=padded, labels=labels)
     want = CU.oracle_cohorts(c, False, ids, G)
     CU.check(got[:3] + (None, None), want, c["obs"], 3, "prior with padded observations")
     # tables beyond the LDS of one CU: T = 1024 with three heads
@@ -353,27 +331,16 @@ def test_memory_is_the_outputs_and_the_scratch(is_post):
     """After a warm-up call, the peak of torch.cuda.max_memory_allocated over the allocation before the call is the outputs plus the
     plan's scratch_bytes (and the member lists): the same at K = 8 and K = 200, and at chunk = 8 below slode_recon_moments' outputs for
     the same B."""
-    m, _ = _model("cvs")
-    batch = {k: v.to(DEV) for k, v in EU.model_state("cvs")[2][0].items()}                  # 24 trajectories
-    batch["observations"] = batch["observations"].permute(0, 2, 1).contiguous().permute(0, 2, 1)
+    m, batches = _model_batches("cvs")
+    batch = _on_device(batches[0], "cvs")                                                   # 24 trajectories
     eng = m._bind().engine
     B = batch["observations"].shape[0]
     ids = torch.arange(B, device=DEV) % 2
     m.cohort_moments(is_post=is_post, num_samples=8, cohorts=ids, chunk=8, **batch)
     eng.profile_enable(True)
-
-    def peak(fn):
-        torch.cuda.synchronize(DEV)
-        torch.cuda.reset_peak_memory_stats(DEV)
-        before = torch.cuda.memory_allocated(DEV)
-        out = fn()
-        torch.cuda.synchronize(DEV)
-        del out
-        return torch.cuda.max_memory_allocated(DEV) - before
-
     fused = []
     for ns in (8, 200):
-        fused.append(peak(lambda: m.cohort_moments(is_post=is_post, num_samples=ns, cohorts=ids, chunk=8, **batch)))
+        fused.append(_peak(lambda: m.cohort_moments(is_post=is_post, num_samples=ns, cohorts=ids, chunk=8, **batch)))
         assert [n for n, _ in eng.profile_read()][-1] == "cohort_merge"                   # the fused route, not the composition
     eng.profile_enable(False)
     G, Q, C, T = 2, 3, 3, 86
@@ -440,10 +407,7 @@ def test_model_level_call_is_total_over_what_the_engine_refuses(why, monkeypatch
     m, batch = _model("cvs", "dopri5" if why == "dopri5" else None, monkeypatch, {why: "1"} if why.startswith("SLODE") else None)
     eng = m._bind().engine
     if why == "strided":
-        obs = batch["observations"]
-        wide = torch.zeros(obs.shape[0], obs.shape[1], obs.shape[2] + 3, device=DEV)
-        wide[:, :, :obs.shape[2]] = obs
-        batch["observations"] = wide[:, :, :obs.shape[2]]
+        batch["observations"] = _padded(batch["observations"])
     ns = 6
     eng.rng_seed(11)
     got = m.cohort_moments(is_post=True, num_samples=ns, cohorts=("iext", "rtpr"), **batch)

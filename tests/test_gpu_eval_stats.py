@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from tests import eval_stats_util as EU
-from tests.eval_gpu_util import DEV, _device_batch, _engine
+from tests.eval_gpu_util import DEV, _captured, _device_batch, _engine, _model_batches, _padded
 
 pytestmark = pytest.mark.gpu
 
@@ -112,22 +112,7 @@ def test_launch_count_and_graph_capture():
 
     out = torch.zeros(L.EVAL_SLOTS, device=DEV)
     bt = eng.make_batch(obs_d, labels, eps4, particles=4)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        eng.eval_stats(flat, bt, c["B"], True, out)
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = out.clone()
-    out.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        eng.eval_stats(flat, bt, c["B"], True, out)
-    torch.cuda.synchronize(DEV)
-    assert out.abs().sum().item() == 0.0, "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want, = _captured(lambda: eng.eval_stats(flat, bt, c["B"], True, out), (out,))
     assert torch.equal(out, want), (out, want)
 
 
@@ -145,10 +130,8 @@ def test_refusals_by_name(monkeypatch):
     eng = _engine(c)
     with pytest.raises(L.SlodeError, match="particles = 2"):
         eng.eval_stats(flat, eng.make_batch(obs_d, labels, None), c["B"], True, out, particles=2)
-    padded = torch.zeros(c["B"], c["obs"].shape[1], c["T"] + 3, device=DEV)
-    padded[:, :, :c["T"]] = obs_d
     with pytest.raises(L.SlodeError, match="observation strides"):
-        eng.eval_stats(flat, eng.make_batch(padded[:, :, :c["T"]], labels, None), c["B"], True, out)
+        eng.eval_stats(flat, eng.make_batch(_padded(obs_d), labels, None), c["B"], True, out)
     assert eng.rng_state()[2] == n                          # a refused call draws nothing
     eng = _engine(c, monkeypatch, {"SLODE_ODE_ALG": "1"})
     with pytest.raises(L.SlodeError, match="measured arms"):
@@ -156,12 +139,7 @@ def test_refusals_by_name(monkeypatch):
 
 
 def _model(fam, solver=None):
-    twin, state, batches, times = EU.model_state(fam)
-    cfg = EU.model_config(fam)
-    if solver:
-        cfg.update(solver=solver)
-    m = importlib.import_module("structured_latent_odes_amd.models.mechanistic_" + fam).MechanisticModel(cfg, DEV, times.to(DEV))
-    m.load_state_dict(state)
+    m, batches = _model_batches(fam, solver)
     m._bind().engine.rng_seed(EU.MODEL_RNG_SEED)
     return m, batches
 
@@ -208,10 +186,7 @@ def test_model_level_call_is_total_over_what_the_engine_refuses():
         batch = {k: v.to(DEV) for k, v in batches[0].items()}
         batch = {k: (v.reshape(v.shape[0], -1) if k != "observations" else v) for k, v in batch.items()}
         if pad:
-            obs = batch["observations"]
-            wide = torch.zeros(obs.shape[0], obs.shape[1], obs.shape[2] + 3, device=DEV)
-            wide[:, :, :obs.shape[2]] = obs
-            batch["observations"] = wide[:, :, :obs.shape[2]]
+            batch["observations"] = _padded(batch["observations"])
         eng.rng_set_counter(0)
         row = m.eval_stats(is_post=True, num_particles=K, **batch).cpu()
         n_row = eng.rng_state()[2]

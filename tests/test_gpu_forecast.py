@@ -15,7 +15,7 @@ import torch
 from tests import eval_stats_util as EU
 from tests import forecast_util as FU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import DEV, ENV_KEYS, _device_batch, _engine, _eps_dev
+from tests.eval_gpu_util import DEV, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _refused
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -229,48 +229,24 @@ def test_launches_and_graph_capture():
     outs = [torch.zeros(3, B, 3, 50, device=DEV), torch.zeros(3, B, 3, 50, device=DEV), torch.zeros(B, S, 50, device=DEV), torch.zeros(B, S, 50, device=DEV)]
     bt = eng.make_batch(obs_d, labels, c["eps"].to(DEV).contiguous(), particles=7)
     eng.forecast_grid(c["times_out"])                                                   # (built before the capture: the call itself only enqueues)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        eng.forecast_moments(flat, bt, B, True, 7, c["times_out"], *outs, window=16)
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = [t.clone() for t in outs]
-    for t in outs:
-        t.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        eng.forecast_moments(flat, bt, B, True, 7, c["times_out"], *outs, window=16)
-    torch.cuda.synchronize(DEV)
-    assert all(t.abs().sum().item() == 0.0 for t in outs), "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want = _captured(lambda: eng.forecast_moments(flat, bt, B, True, 7, c["times_out"], *outs, window=16), outs)
     assert all(torch.equal(t, w) and float(w.abs().sum()) > 0 for t, w in zip(outs, want))
 
 
 # ---- refusals on a real handle -------------------------------------------------------------------------------------------------------------
 def test_refusals_write_nothing_and_draw_nothing(monkeypatch):
-    from structured_latent_odes_amd import _lib as L
     c = FU.build("cvs_ald", "rk4", B=5, ns=2, T_out=50)
     obs_d, labels = _device_batch(c)
 
     def refused(eng, match, times_out=None, window=0):
         flat = eng.pack(c["p"])
-        eng.rng_seed(3)
-        eng.rng_set_counter(4)
-        eng.profile_enable(True)
         t_out = c["times_out"] if times_out is None else times_out
         outs = [torch.full((3, 5, 3, t_out.numel()), NAN, device=DEV), torch.full((3, 5, 3, t_out.numel()), NAN, device=DEV),
                 torch.full((5, 5, t_out.numel()), NAN, device=DEV), torch.full((5, 5, t_out.numel()), NAN, device=DEV)]
-        with pytest.raises(L.SlodeError, match=match) as ei:
-            eng.forecast_moments(flat, eng.make_batch(obs_d, labels, None), 5, True, 2, t_out, *outs, window=window)
-        assert ei.value.status == -1
+        err = _refused(eng, lambda: eng.forecast_moments(flat, eng.make_batch(obs_d, labels, None), 5, True, 2, t_out, *outs, window=window), match)
+        assert err.status == -1
         torch.cuda.synchronize(DEV)
         assert all(bool(torch.isnan(t).all()) for t in outs)
-        assert eng.rng_state() == (3, 0, 4)
-        with pytest.raises(L.SlodeError, match="no profiled step"):
-            eng.profile_read()
 
     refused(_engine(c, monkeypatch, solver="dopri5"), "adaptive solver dopri5")
     eng = _engine(c, monkeypatch)
@@ -291,24 +267,6 @@ def test_refusals_write_nothing_and_draw_nothing(monkeypatch):
 
 
 # ---- model level -------------------------------------------------------------------------------------------------------------------------
-def _model(fam, solver=None, monkeypatch=None, env=None):
-    if monkeypatch is not None:
-        for k in ENV_KEYS:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in (env or {}).items():
-            monkeypatch.setenv(k, v)
-    twin, state, batches, times = EU.model_state(fam)
-    cfg = EU.model_config(fam)
-    if solver:
-        cfg.update(solver=solver)
-    m = importlib.import_module("structured_latent_odes_amd.models.mechanistic_" + fam).MechanisticModel(cfg, DEV, times.to(DEV))
-    m.load_state_dict(state)
-    batch = {k: v.to(DEV) for k, v in batches[2].items()}                                # 17 trajectories
-    if fam != "proc":
-        batch["observations"] = batch["observations"].permute(0, 2, 1).contiguous().permute(0, 2, 1)
-    return m, batch
-
-
 def _agree(got, want64, tag):
     for n in want64:
         RU.check(got[n][0], got[n][1], want64[n][0].cpu().numpy(), want64[n][1].cpu().numpy(), "%s %s" % (tag, n))
@@ -344,10 +302,7 @@ def test_model_level_call_is_total_over_what_the_engine_refuses(why, monkeypatch
     eng = m._bind().engine
     dense = dict(batch)
     if why == "strided":
-        obs = batch["observations"]
-        wide = torch.zeros(obs.shape[0], obs.shape[1], obs.shape[2] + 3, device=DEV)
-        wide[:, :, :obs.shape[2]] = obs
-        batch["observations"] = wide[:, :, :obs.shape[2]]
+        batch["observations"] = _padded(batch["observations"])
     names, ns, t_out = ("mu_50", "mu_75", "mu_25", "solution_xt"), 6, m.horizon_times(9)
     B, L = batch["observations"].shape[0], m.latent_dim
     eng.rng_seed(11)

@@ -11,9 +11,8 @@ import torch
 from tests import eval_stats_util as EU
 from tests import intervene_util as IU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _device_batch, _engine, _eps_dev
-from tests.test_gpu_recon_moments import SIZES, _model
-from tests.test_gpu_recon_moments import _moments as _recon_moments
+from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
+                                 _recon_moments, _refused)
 
 pytestmark = pytest.mark.gpu
 
@@ -192,21 +191,14 @@ def test_refusals_by_name(monkeypatch):
     obs_d, labels = _device_batch(c)
     cf = _split(c, IU.cf_labels(c["u"]))
 
-    def refused(eng, match, obs=obs_d, ns=2, particles=1, mask=1, cf_labels=cf, null_obs=False, error=L.SlodeError):
+    def refused(eng, match, obs=obs_d, ns=2, particles=1, mask=1, cf_labels=cf, null_obs=False, error=None):
         flat = eng.pack(c["p"])
-        eng.rng_seed(3)
-        eng.rng_set_counter(4)
-        eng.profile_enable(True)
         bt = eng.make_batch(obs, labels, None)
         if null_obs:
             bt.obs = None
-        with pytest.raises(error, match=match) as ei:
-            eng.intervene_moments(flat, bt, c["B"], cf_labels, mask, ns, particles=particles)
-        if error is L.SlodeError:
-            assert ei.value.status == -1 and "slode_intervene_moments" in str(ei.value)
-        assert eng.rng_state() == (3, 0, 4)
-        with pytest.raises(L.SlodeError, match="no profiled step"):
-            eng.profile_read()
+        err = _refused(eng, lambda: eng.intervene_moments(flat, bt, c["B"], cf_labels, mask, ns, particles=particles), match, error)
+        if error is None:
+            assert err.status == -1 and "slode_intervene_moments" in str(err)
 
     for solver in ADAPTIVE:
         refused(_engine(c, monkeypatch, solver=solver), "adaptive solver %s" % solver)
@@ -215,9 +207,7 @@ def test_refusals_by_name(monkeypatch):
     refused(eng, "num_samples = 0", ns=0)
     refused(eng, "exceeds 2\\^30 - 1 noise rows", ns=2 ** 30)                      # refused on the host: nothing sized by it is touched
     refused(eng, "batch->obs is NULL", null_obs=True)
-    padded = torch.zeros(c["B"], 3, c["T"] + 3, device=DEV)
-    padded[:, :, :c["T"]] = obs_d
-    refused(eng, "observation strides", obs=padded[:, :, :c["T"]])
+    refused(eng, "observation strides", obs=_padded(obs_d))
     refused(eng, "bits at or beyond n_groups = 2", mask=4)
     refused(eng, "bits at or beyond n_groups = 2", mask=1 << 31)
     refused(eng, "cf_labels is NULL", cf_labels=None)
@@ -253,10 +243,7 @@ def test_model_level_call_is_total_over_what_the_engine_refuses(why, monkeypatch
     m, batch = _model("cvs", "dopri5" if why == "dopri5" else None, monkeypatch, {why: "1"} if why.startswith("SLODE") else None)
     eng = m._bind().engine
     if why == "strided":
-        obs = batch["observations"]
-        wide = torch.zeros(obs.shape[0], obs.shape[1], obs.shape[2] + 3, device=DEV)
-        wide[:, :, :obs.shape[2]] = obs
-        batch["observations"] = wide[:, :, :obs.shape[2]]
+        batch["observations"] = _padded(batch["observations"])
     names, ns = ("mu_50", "mu_75", "mu_25"), 6
     swap = _swap("cvs", batch)
     eng.rng_seed(11)
@@ -292,23 +279,7 @@ def test_launches_and_graph_capture():
     outs = [torch.zeros(3, c["B"], 3, c["T"], device=DEV) for _ in range(4)]
     cf = _split(c, u_cf)
     bt = eng.make_batch(obs_d, labels, c["eps"].to(DEV).contiguous(), particles=7)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        eng.intervene_moments(flat, bt, c["B"], cf, 3, 7, *outs)
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = [t.clone() for t in outs]
-    for t in outs:
-        t.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        eng.intervene_moments(flat, bt, c["B"], cf, 3, 7, *outs)
-    torch.cuda.synchronize(DEV)
-    assert all(t.abs().sum().item() == 0.0 for t in outs), "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want = _captured(lambda: eng.intervene_moments(flat, bt, c["B"], cf, 3, 7, *outs), outs)
     assert _equal(outs, want)
 
 
@@ -320,22 +291,12 @@ def test_memory_does_not_scale_with_the_number_of_draws():
     swap = _swap("cvs", batch)
     m.intervention_moments(num_samples=8, intervene=swap, **batch)
     eng.profile_enable(True)
-
-    def peak(fn):
-        torch.cuda.synchronize(DEV)
-        torch.cuda.reset_peak_memory_stats(DEV)
-        before = torch.cuda.memory_allocated(DEV)
-        out = fn()
-        torch.cuda.synchronize(DEV)
-        del out
-        return torch.cuda.max_memory_allocated(DEV) - before
-
     fused = []
     for ns in (8, 200):
-        fused.append(peak(lambda: m.intervention_moments(num_samples=ns, intervene=swap, **batch)))
+        fused.append(_peak(lambda: m.intervention_moments(num_samples=ns, intervene=swap, **batch)))
         assert [n for n, _ in eng.profile_read()][-1] == "intervene_moments"       # the fused route, not the composition
     eng.profile_enable(False)
-    samples = peak(lambda: m.counterfactual_samples(num_samples=8, intervene=swap, **batch))
+    samples = _peak(lambda: m.counterfactual_samples(num_samples=8, intervene=swap, **batch))
     print("peak over the allocation before the call: fused ns=8 %d B, ns=200 %d B; counterfactual_samples ns=8 %d B" % (fused[0], fused[1], samples))
     assert fused[0] == fused[1]
     assert fused[1] < samples

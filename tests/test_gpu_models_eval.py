@@ -11,11 +11,11 @@ import torch.nn.functional as F
 
 from oracle import slode_oracle as O
 from tests import eval_side_util as V
+from tests.eval_side_util import DP5_TOL, _heads64, _p64
 
 pytestmark = pytest.mark.gpu
 
 CLASSES = [(f, g) for f in ("cvs", "proc", "challenge") for g in (False, True)]
-DP5_TOL = dict(rtol=1e-7, atol=1e-9, per_trajectory=True)        # the engine's (torchdiffeq's) default tolerances
 
 
 def _model(fam, gauss, solver="rk4", adjoint=True, B=None, seed=3):
@@ -43,10 +43,6 @@ def _model(fam, gauss, solver="rk4", adjoint=True, B=None, seed=3):
     return m, cfg, batch, ospec, u, times, dev
 
 
-def _p64(m):
-    return {k: v.detach().cpu().double().clone() for k, v in m.state_dict().items()}
-
-
 def _decode64(p, ospec, z, times, solver):
     """(solution, {name: curve}, std) of the oracle's decoder for z, fp64; dopri5 at the engine's default tolerances."""
     kw = DP5_TOL if solver == "dopri5" else {}
@@ -55,11 +51,6 @@ def _decode64(p, ospec, z, times, solver):
         return sol, {"mean": mean}, std
     sol, mu75, mu50, mu25, std = O.decoder_ald(p, z, times.double(), solver, **kw)
     return sol, {"mu_75": mu75, "mu_50": mu50, "mu_25": mu25}, std
-
-
-def _heads64(p, ospec, sol):
-    names = {"mean": "output_mean"} if ospec.gauss else {"mu_50": "output_q50", "mu_75": "output_q75", "mu_25": "output_q25"}
-    return {k: F.linear(sol, p["decoder.%s.0.weight" % n]).permute(0, 2, 1) for k, n in names.items()}
 
 
 @pytest.mark.parametrize("solver", ["rk4", "dopri5"])

@@ -13,22 +13,10 @@ import torch
 
 from tests import eval_stats_util as EU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _device_batch, _engine, _eps_dev
+from tests.eval_gpu_util import ADAPTIVE, DEV, SIZES, WIDTHS, _captured, _device_batch, _engine, _model, _padded, _peak, _refused
+from tests.eval_gpu_util import _recon_moments as _moments
 
 pytestmark = pytest.mark.gpu
-
-
-def _moments(eng, flat, c, is_post, eps="case", obs_d=None, labels=None, ns=None):
-    """Outputs pre-filled with NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q = 1 if c["ospec"].gauss else 3
-    mean = torch.full((Q, c["B"], c["obs"].shape[1], c["T"]), float("nan"), device=DEV)
-    sd = torch.full_like(mean, float("nan"))
-    eng.recon_moments(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, mean, sd)
-    return mean, sd
 
 
 @pytest.mark.parametrize("solver", EU.SOLVERS)
@@ -42,11 +30,6 @@ def test_moments_match_the_fp64_oracle(case, solver):
     for is_post in (True, False):
         mean, sd = _moments(eng, flat, c, is_post)
         RU.check(mean, sd, *RU.oracle_moments(c, is_post), "%s/%s/%s" % (case, solver, "post" if is_post else "prior"))
-
-
-SIZES = [("cvs_gauss", 63, 2, {}), ("cvs_gauss", 65, 7, {}), ("cvs_gauss", 255, 2, {}), ("cvs_gauss", 257, 1, {}), ("cvs_ald", 3, 200, {}),
-         ("proc_gauss", 65, 2, {"SLODE_ODE_LOOP": "1", "SLODE_ODE_GRID": "5"}), ("challenge_gauss", 2, 200, {}),
-         ("cvs_ald", 9, 7, {"SLODE_ODE_GENERIC": "1"}), ("proc_ald", 9, 2, {"SLODE_ODE_GENERIC": "1", "SLODE_ODE_LOOP": "1", "SLODE_ODE_GRID": "2"})]
 
 
 @pytest.mark.parametrize("case,B,ns,env", SIZES, ids=["%s-B%d-ns%d%s" % (c, B, ns, "-" + "-".join(k[10:].lower() for k in e) if e else "") for c, B, ns, e in SIZES])
@@ -125,24 +108,6 @@ def test_kernel_accumulation_on_curves_whose_sd_is_1e4_of_their_level(is_post):
     assert np.all(np.abs(mean - rm) <= 2 * bar_mean) and np.all(np.abs(sd - rs) <= 2 * bar_sd)
 
 
-def _model(fam, solver=None, monkeypatch=None, env=None):
-    if monkeypatch is not None:
-        for k in ENV_KEYS:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in (env or {}).items():
-            monkeypatch.setenv(k, v)
-    twin, state, batches, times = EU.model_state(fam)
-    cfg = EU.model_config(fam)
-    if solver:
-        cfg.update(solver=solver)
-    m = importlib.import_module("structured_latent_odes_amd.models.mechanistic_" + fam).MechanisticModel(cfg, DEV, times.to(DEV))
-    m.load_state_dict(state)
-    batch = {k: v.to(DEV) for k, v in batches[2].items()}                          # 17 trajectories
-    if fam != "proc":
-        batch["observations"] = batch["observations"].permute(0, 2, 1).contiguous().permute(0, 2, 1)
-    return m, batch
-
-
 def _reduce64(res, names):
     return {n: (res[n].double().mean(-1), res[n].double().std(-1, unbiased=False)) for n in names}
 
@@ -189,21 +154,11 @@ def test_memory_does_not_scale_with_the_number_of_draws(is_post):
     m.recon_moments(is_post=is_post, num_samples=8, **batch)
     fused = []
     eng.profile_enable(True)
-
-    def peak(fn):
-        torch.cuda.synchronize(DEV)
-        torch.cuda.reset_peak_memory_stats(DEV)
-        before = torch.cuda.memory_allocated(DEV)
-        out = fn()
-        torch.cuda.synchronize(DEV)
-        del out
-        return torch.cuda.max_memory_allocated(DEV) - before
-
     for ns in (8, 200):
-        fused.append(peak(lambda: m.recon_moments(is_post=is_post, num_samples=ns, **batch)))
+        fused.append(_peak(lambda: m.recon_moments(is_post=is_post, num_samples=ns, **batch)))
         assert [n for n, _ in eng.profile_read()][-1] == "recon_moments"           # the fused route, not the composition
     eng.profile_enable(False)
-    samples = peak(lambda: m.recon_samples(is_post=is_post, num_samples=8, **batch))
+    samples = _peak(lambda: m.recon_samples(is_post=is_post, num_samples=8, **batch))
     out_bytes = 2 * 3 * B * 3 * 86 * 4
     print("peak over the allocation before the call: fused ns=8 %d B, ns=200 %d B (outputs %d B); recon_samples ns=8 %d B" % (fused[0], fused[1], out_bytes, samples))
     assert fused[0] == fused[1]
@@ -218,23 +173,15 @@ def test_refusals_by_name(monkeypatch):
 
     def refused(eng, match, obs=obs_d, ns=2, particles=1, is_post=True):
         flat = eng.pack(c["p"])
-        eng.rng_seed(3)
-        eng.rng_set_counter(4)
-        eng.profile_enable(True)
-        with pytest.raises(L.SlodeError, match=match):
-            eng.recon_moments(flat, eng.make_batch(obs, labels, None), c["B"], is_post, ns, particles=particles)
-        assert eng.rng_state() == (3, 0, 4)
-        with pytest.raises(L.SlodeError, match="no profiled step"):
-            eng.profile_read()
+        _refused(eng, lambda: eng.recon_moments(flat, eng.make_batch(obs, labels, None), c["B"], is_post, ns, particles=particles), match)
 
     for solver in ADAPTIVE:
         refused(_engine(c, monkeypatch, solver=solver), "adaptive solver %s" % solver)
     eng = _engine(c, monkeypatch)
     refused(eng, "particles = 2", particles=2)
     refused(eng, "num_samples = 0", ns=0)
-    padded = torch.zeros(c["B"], 3, c["T"] + 3, device=DEV)
-    padded[:, :, :c["T"]] = obs_d
-    refused(eng, "observation strides", obs=padded[:, :, :c["T"]])
+    padded = _padded(obs_d)
+    refused(eng, "observation strides", obs=padded)
     for env in ({"SLODE_ODE_ALG": "1"}, {"SLODE_ODE_PACK": "4"}, {"SLODE_FOLD_NEXT": "1"}):
         refused(_engine(c, monkeypatch, env), "measured arms")
         refused(_engine(c, monkeypatch, env), "measured arms", is_post=False)
@@ -253,7 +200,7 @@ def test_refusals_by_name(monkeypatch):
     # the prior reads no observations: their strides do not matter
     eng = _engine(c, monkeypatch)
     flat = eng.pack(c["p"])
-    mean, sd = _moments(eng, flat, c, False, obs_d=padded[:, :, :c["T"]], labels=labels)
+    mean, sd = _moments(eng, flat, c, False, obs_d=padded, labels=labels)
     RU.check(mean, sd, *RU.oracle_moments(c, False), "prior with padded observations")
 
 
@@ -264,14 +211,11 @@ def test_model_level_call_is_total_over_what_the_engine_refuses(why, monkeypatch
     against the fp64 oracle at the existing dopri5 eval bar (test_recon_samples_at_200_samples): error against the tight fp64 solve
     (rtol 1e-10) < 3 x that of the fp64 restatement at the engine's tolerances + 1e-5, and within 1e-3; for the mean and for the sd."""
     from oracle import slode_oracle as O
-    from tests.test_gpu_models_eval import DP5_TOL, _heads64, _p64
+    from tests.eval_side_util import DP5_TOL, _heads64, _p64
     m, batch = _model("cvs", "dopri5" if why == "dopri5" else None, monkeypatch, {why: "1"} if why.startswith("SLODE") else None)
     eng = m._bind().engine
     if why == "strided":
-        obs = batch["observations"]
-        wide = torch.zeros(obs.shape[0], obs.shape[1], obs.shape[2] + 3, device=DEV)
-        wide[:, :, :obs.shape[2]] = obs
-        batch["observations"] = wide[:, :, :obs.shape[2]]
+        batch["observations"] = _padded(batch["observations"])
     names, ns = ("mu_50", "mu_75", "mu_25"), 6
     B, L = batch["observations"].shape[0], m.latent_dim
     eng.rng_seed(11)
@@ -330,23 +274,7 @@ def test_launches_and_graph_capture():
     mean = torch.zeros(Q, c["B"], 3, c["T"], device=DEV)
     sd = torch.zeros_like(mean)
     bt = eng.make_batch(obs_d, labels, eps, particles=7)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        eng.recon_moments(flat, bt, c["B"], True, 7, mean, sd)
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = (mean.clone(), sd.clone())
-    mean.zero_()
-    sd.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        eng.recon_moments(flat, bt, c["B"], True, 7, mean, sd)
-    torch.cuda.synchronize(DEV)
-    assert mean.abs().sum().item() == 0.0 and sd.abs().sum().item() == 0.0, "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want = _captured(lambda: eng.recon_moments(flat, bt, c["B"], True, 7, mean, sd), (mean, sd))
     assert torch.equal(mean, want[0]) and torch.equal(sd, want[1])
 
 

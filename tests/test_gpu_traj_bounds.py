@@ -1,7 +1,6 @@
 """GPU tests of the per-trajectory bounds (slode_traj_bounds / Engine.traj_bounds / MechanisticBase.trajectory_bounds /
 save_trajectory_bounds / --test-bounds) against the per-row fp64 oracle and against the fp64 reduction of the kernel's own per-draw losses.
 Bars: module docstring of tests/traj_bounds_util.py.  Outputs are pre-filled with NaN: every element must be written."""
-import importlib
 import os
 
 import numpy as np
@@ -10,8 +9,7 @@ import torch
 
 from tests import eval_stats_util as EU
 from tests import traj_bounds_util as TU
-from tests.eval_gpu_util import ADAPTIVE, _device_batch, _engine
-from tests.test_gpu_recon_moments import _model
+from tests.eval_gpu_util import ADAPTIVE, _captured, _device_batch, _engine, _model, _padded, _refused
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -125,22 +123,14 @@ def test_bitwise_reproducible_and_independent_of_the_grid_and_of_where_the_noise
 
 def test_refusals_by_name(monkeypatch):
     """Every refusal names its reason, draws nothing, launches nothing and writes nothing (rng_state, profile_read, outputs still NaN)."""
-    from structured_latent_odes_amd import _lib as L
     c = TU.build("cvs_ald", "rk4", K=2)
     obs_d, labels = _device_batch(c)
 
     def refused(eng, match, obs=obs_d, K=2, particles=1):
         flat = eng.pack(c["p"])
-        eng.rng_seed(3)
-        eng.rng_set_counter(4)
-        eng.profile_enable(True)
         bounds = torch.full((c["B"], 4), float("nan"), device=DEV)
         loss = torch.full((K, c["B"]), float("nan"), device=DEV)
-        with pytest.raises(L.SlodeError, match=match):
-            eng.traj_bounds(flat, eng.make_batch(obs, labels, None), c["B"], K, bounds, loss, particles=particles)
-        assert eng.rng_state() == (3, 0, 4)
-        with pytest.raises(L.SlodeError, match="no profiled step"):
-            eng.profile_read()
+        _refused(eng, lambda: eng.traj_bounds(flat, eng.make_batch(obs, labels, None), c["B"], K, bounds, loss, particles=particles), match)
         torch.cuda.synchronize(DEV)
         assert torch.isnan(bounds).all() and torch.isnan(loss).all()
 
@@ -149,9 +139,7 @@ def test_refusals_by_name(monkeypatch):
     eng = _engine(c, monkeypatch)
     refused(eng, "particles = 2", particles=2)
     refused(eng, "num_draws = 0", K=0)
-    padded = torch.zeros(c["B"], 3, c["T"] + 3, device=DEV)
-    padded[:, :, :c["T"]] = obs_d
-    refused(eng, "observation strides", obs=padded[:, :, :c["T"]])
+    refused(eng, "observation strides", obs=_padded(obs_d))
     refused(_engine(c, monkeypatch, {"SLODE_NO_FOLD": "1"}), "SLODE_NO_FOLD")
     for env in ({"SLODE_ODE_ALG": "1"}, {"SLODE_ODE_PACK": "4"}, {"SLODE_FOLD_NEXT": "1"}):
         refused(_engine(c, monkeypatch, env), "measured arms")
@@ -219,21 +207,5 @@ def test_launches_and_graph_capture():
     bounds = torch.zeros(c["B"], 4, device=DEV)
     loss = torch.zeros(7, c["B"], device=DEV)
     bt = eng.make_batch(obs_d, labels, c["eps"].to(DEV).contiguous(), particles=7)
-    side = torch.cuda.Stream(device=DEV)
-    side.wait_stream(torch.cuda.current_stream(DEV))
-    with torch.cuda.stream(side):
-        eng.traj_bounds(flat, bt, c["B"], 7, bounds, loss)
-    torch.cuda.current_stream(DEV).wait_stream(side)
-    torch.cuda.synchronize(DEV)
-    want = (bounds.clone(), loss.clone())
-    bounds.zero_()
-    loss.zero_()
-    torch.cuda.synchronize(DEV)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        eng.traj_bounds(flat, bt, c["B"], 7, bounds, loss)
-    torch.cuda.synchronize(DEV)
-    assert bounds.abs().sum().item() == 0.0 and loss.abs().sum().item() == 0.0, "capturing must not execute anything"
-    g.replay()
-    torch.cuda.synchronize(DEV)
+    want = _captured(lambda: eng.traj_bounds(flat, bt, c["B"], 7, bounds, loss), (bounds, loss))
     assert torch.equal(bounds, want[0]) and torch.equal(loss, want[1]) and want[0].abs().sum().item() > 0.0

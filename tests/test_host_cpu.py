@@ -247,19 +247,8 @@ def test_eval_side_refusals_match_the_recorded_ladder(tmp_path):
     hand-filled handle (tests/eval_refusals/eval_refusals.cpp: no device, no HIP call, no call that would be taken): status, message and
     the untouched drawing-call counter, line by line against tests/golden/eval_refusals.txt -- which check speaks first when two
     conditions hold included.  The file was recorded from the library before the four calls shared one host ladder."""
-    import subprocess
-    from structured_latent_odes_amd import _lib as L
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not present: the refusal program is not built")
-    lib = os.path.abspath(L.LIB_PATH)
-    exe = str(tmp_path / "eval_refusals")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-Wall", "-O1", os.path.join(ROOT, "tests", "eval_refusals", "eval_refusals.cpp"),
-                        "-o", exe, "-x", "none", lib, "-Wl,-rpath," + os.path.dirname(lib)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = r.stdout.splitlines()
+    from tests.refusals_util import refusal_lines
+    got = refusal_lines("eval_refusals", tmp_path)
     want = open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines()
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)

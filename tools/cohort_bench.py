@@ -10,36 +10,15 @@ of one fused call (chunk = 0) from slode_profile_read.  Prints one JSON line; --
 
     python tools/cohort_bench.py --out profiles/cohort_moments.json
 """
-import argparse
-import importlib
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import eval_bench as EB
 
 SHAPES = {
     "cvs_B1024_T200_rk4_G4": ("cvs", "mechanistic_cvs", "MechanisticModel", 1024, 200, 4, dict(z_iext_dim=3, z_rtpr_dim=3, z_epsilon_dim=2)),
     "proc_B1024_T100_rk4_G50": ("proc", "mechanistic_proc", "MechanisticModel", 1024, 100, 50, dict()),
 }
 CHUNKS = (0, 1, 8, 64)
-
-
-def _timed(fn, dev):
-    """(milliseconds between two device events around fn, peak allocation over the allocation before the call)."""
-    torch.cuda.synchronize(dev)
-    torch.cuda.reset_peak_memory_stats(dev)
-    before = torch.cuda.memory_allocated(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    del out
-    return e0.elapsed_time(e1), torch.cuda.max_memory_allocated(dev) - before
 
 
 def _segmented(m, res, obs, ids, G):
@@ -57,16 +36,8 @@ def _segmented(m, res, obs, ids, G):
 
 
 def run_shape(name, ns, rounds, dev):
-    from structured_latent_odes_amd import configs as CF
-    from structured_latent_odes_amd.synthetic import synthetic_batch
     fam, mod, cls, B, T, G, kw = SHAPES[name]
-    cfg = getattr(CF, "load_config_" + fam)()
-    cfg.update(seq_len=T, solver="rk4", num_particles=1, **kw)
-    torch.manual_seed(3)
-    obs, labels, times = synthetic_batch(fam, B, T, cfg.obs_dim, seed=7)
-    m = getattr(importlib.import_module("structured_latent_odes_amd.models." + mod), cls)(cfg, dev, times.to(dev))
-    batch = {"observations": obs.to(dev)}
-    batch.update({k: v.to(dev).reshape(B, -1) for k, v in labels.items()})
+    m, batch = EB.model_and_batch((fam, mod, cls, B, T, kw), dev)
     lab = {k: v for k, v in batch.items() if k != "observations"}
     ids = torch.arange(B, device=dev) % G
     count = torch.bincount(ids, minlength=G)
@@ -77,16 +48,8 @@ def run_shape(name, ns, rounds, dev):
     legs["samples"] = lambda post: m._cohort_composed(batch["observations"], post, ns, ids, G, count, None, None, lab)
     res = {"B": B, "T": T, "G": G, "num_samples": ns, "rounds": rounds, "default_chunk": eng.cohort_plan(B, B, G, ns)[0]}
     for post in (True, False):
-        for leg in legs.values():                                  # warm: workspaces, per-shape set-up, allocator
-            leg(post)
-        t, mem = {k: [] for k in legs}, {k: 0 for k in legs}
-        for _ in range(rounds):                                    # alternating legs
-            for k, leg in legs.items():
-                ms, peak = _timed(lambda: leg(post), dev)
-                t[k].append(ms)
-                mem[k] = max(mem[k], peak)
         key = "posterior" if post else "prior"
-        res[key] = {k: {"median_ms": statistics.median(v), "spread_ms": max(v) - min(v), "all_ms": v, "peak_bytes_over_before": mem[k]} for k, v in t.items()}
+        res[key] = EB.alternate({k: (lambda leg=leg: leg(post)) for k, leg in legs.items()}, rounds, dev)
         eng.profile_enable(True)
         m.cohort_moments(is_post=post, num_samples=ns, cohorts=ids, **batch)
         res[key]["fused_call_kernels_us"] = eng.profile_read()
@@ -94,21 +57,5 @@ def run_shape(name, ns, rounds, dev):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    out = {"tool": "cohort_bench", "device": torch.cuda.get_device_name(dev),
-           "shapes": {n: run_shape(n, a.samples, a.rounds, dev) for n in SHAPES}}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    EB.main("cohort_bench", SHAPES, run_shape, "--samples", 200)

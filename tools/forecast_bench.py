@@ -11,16 +11,9 @@ plan (window, LDS bytes) of each.  Prints one JSON line; --out writes it to a fi
 
     python tools/forecast_bench.py --out profiles/forecast_moments.json
 """
-import argparse
-import importlib
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import eval_bench as EB
 
 SHAPES = {
     "metric_cvs_B1024_T200_rk4": ("cvs", "mechanistic_cvs", "MechanisticModel", 1024, 200, dict(z_iext_dim=3, z_rtpr_dim=3, z_epsilon_dim=2)),
@@ -29,45 +22,14 @@ SHAPES = {
 MAX_COMPOSED_T = 1024     # slode_shape::T of slode_ode_solve_fwd
 
 
-def _timed(fn, dev):
-    torch.cuda.synchronize(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    del out
-    return e0.elapsed_time(e1)
-
-
-def _alternate(legs, rounds, dev):
-    """{leg: {median_ms, spread_ms, all_ms}}: every leg warmed twice, then the legs in turn, `rounds` times."""
-    for leg in legs.values():
-        leg()
-        leg()
-    t = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, leg in legs.items():
-            t[k].append(_timed(leg, dev))
-    return {k: {"median_ms": statistics.median(v), "spread_ms": max(v) - min(v), "all_ms": v} for k, v in t.items()}
-
-
 def run_shape(name, ns, rounds, dev):
-    from structured_latent_odes_amd import configs as CF
-    from structured_latent_odes_amd.synthetic import synthetic_batch
-    fam, mod, cls, B, T, kw = SHAPES[name]
-    cfg = getattr(CF, "load_config_" + fam)()
-    cfg.update(seq_len=T, solver="rk4", num_particles=1, **kw)
-    torch.manual_seed(3)
-    obs, labels, times = synthetic_batch(fam, B, T, cfg.obs_dim, seed=7)
-    m = getattr(importlib.import_module("structured_latent_odes_amd.models." + mod), cls)(cfg, dev, times.to(dev))
-    batch = {"observations": obs.to(dev)}
-    batch.update({k: v.to(dev).reshape(B, -1) for k, v in labels.items()})
+    m, batch = EB.model_and_batch(SHAPES[name], dev)
+    B, T = SHAPES[name][3:5]
     b = m._bind()
     eng, flat = b.engine, b.flat
     eps = torch.randn(ns, B, m.latent_dim, generator=torch.Generator().manual_seed(5)).to(dev)
     bt = m._draws_batch(batch["observations"], {k: v for k, v in batch.items() if k != "observations"}, eps, ns)
-    Q, C = (1 if m.GAUSS else 3), cfg.obs_dim
+    Q, C = (1 if m.GAUSS else 3), m.obs_dim
     t_same, t_long = m.horizon_times(0), m.horizon_times(3 * T)
     T_long = int(t_long.numel())
     eng.forecast_grid(t_same), eng.forecast_grid(t_long)
@@ -79,7 +41,7 @@ def run_shape(name, ns, rounds, dev):
                     "c_T_out_4T_window_256": eng.forecast_plan(B, T_long, ns, window=256)}}
     same = {"recon_moments": lambda: eng.recon_moments(flat, bt, B, True, ns, *out_recon),
             "a_forecast_T_out_T_window_0": lambda: eng.forecast_moments(flat, bt, B, True, ns, t_same, *out_same)}
-    res["same_grid"] = _alternate(same, rounds, dev)
+    res["same_grid"] = EB.alternate(same, rounds, dev, warm=2, peak=False)
     res["same_grid"]["mean_bitwise_equal"] = bool(torch.equal(out_same[0], out_recon[0]))
     res["same_grid"]["sd_bitwise_equal"] = bool(torch.equal(out_same[1], out_recon[1]))
     long = {"b_forecast_T_out_4T_window_0": lambda: eng.forecast_moments(flat, bt, B, True, ns, t_long, *out_long),
@@ -91,7 +53,7 @@ def run_shape(name, ns, rounds, dev):
             r = m.forecast_samples(is_post=True, num_samples=ns, times_out=t_long, eps=eps, **batch)
             return {n: (r[n].mean(dim=-1), r[n].std(dim=-1, unbiased=False)) for n in names}
         long["d_composed_T_out_4T"] = composed
-    res["long_grid"] = _alternate(long, rounds, dev)
+    res["long_grid"] = EB.alternate(long, rounds, dev, warm=2, peak=False)
     if T_long > MAX_COMPOSED_T:
         res["long_grid"]["d_composed_T_out_4T"] = "not available: T_out = %d exceeds the %d points slode_ode_solve_fwd takes" % (T_long, MAX_COMPOSED_T)
     eng.profile_enable(True)
@@ -104,22 +66,5 @@ def run_shape(name, ns, rounds, dev):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=64)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    out = {"tool": "forecast_bench", "device": torch.cuda.get_device_name(dev),
-           "shapes": {n: run_shape(n, a.samples, a.rounds, dev) for n in SHAPES}}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    EB.main("forecast_bench", SHAPES, run_shape, "--samples", 64)

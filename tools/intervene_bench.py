@@ -10,16 +10,9 @@ allocation before the call.  Also the kernels of one fused call from slode_profi
 
     python tools/intervene_bench.py --out profiles/intervene_moments.json
 """
-import argparse
-import importlib
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import eval_bench as EB
 
 SHAPES = {
     "metric_cvs_B1024_T200_rk4": ("cvs", "mechanistic_cvs", "MechanisticModel", 1024, 200, dict(z_iext_dim=3, z_rtpr_dim=3, z_epsilon_dim=2)),
@@ -27,31 +20,9 @@ SHAPES = {
 }
 
 
-def _timed(fn, dev):
-    """(milliseconds between two device events around fn, peak allocation over the allocation before the call)."""
-    torch.cuda.synchronize(dev)
-    torch.cuda.reset_peak_memory_stats(dev)
-    before = torch.cuda.memory_allocated(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    del out
-    return e0.elapsed_time(e1), torch.cuda.max_memory_allocated(dev) - before
-
-
 def run_shape(name, ns, rounds, dev):
-    from structured_latent_odes_amd import configs as CF
-    from structured_latent_odes_amd.synthetic import synthetic_batch
-    fam, mod, cls, B, T, kw = SHAPES[name]
-    cfg = getattr(CF, "load_config_" + fam)()
-    cfg.update(seq_len=T, solver="rk4", num_particles=1, **kw)
-    torch.manual_seed(3)
-    obs, labels, times = synthetic_batch(fam, B, T, cfg.obs_dim, seed=7)
-    m = getattr(importlib.import_module("structured_latent_odes_amd.models." + mod), cls)(cfg, dev, times.to(dev))
-    batch = {"observations": obs.to(dev)}
-    batch.update({k: v.to(dev).reshape(B, -1) for k, v in labels.items()})
+    m, batch = EB.model_and_batch(SHAPES[name], dev)
+    B, T = SHAPES[name][3:5]
     names = m.MOMENT_HEADS[bool(m.GAUSS)]
     swap = {l: torch.roll(batch[l], 1, 0) for _, ls, _ in m.PRIORS for l in ls}
 
@@ -67,16 +38,8 @@ def run_shape(name, ns, rounds, dev):
     legs = {"a_intervene_moments": lambda: m.intervention_moments(num_samples=ns, intervene=swap, **batch),
             "b_two_recon_moments": lambda: (m.recon_moments(is_post=True, num_samples=ns, **batch), m.recon_moments(is_post=True, num_samples=ns, **batch)),
             "c_composed_samples": composed}
-    for leg in legs.values():                                      # warm: workspaces, per-shape set-up, allocator
-        leg()
-    t, mem = {k: [] for k in legs}, {k: 0 for k in legs}
-    for _ in range(rounds):                                        # alternating legs
-        for k, leg in legs.items():
-            ms, peak = _timed(leg, dev)
-            t[k].append(ms)
-            mem[k] = max(mem[k], peak)
     res = {"B": B, "T": T, "num_samples": ns, "rounds": rounds, "intervened": sorted(swap)}
-    res["legs"] = {k: {"median_ms": statistics.median(v), "spread_ms": max(v) - min(v), "all_ms": v, "peak_bytes_over_before": mem[k]} for k, v in t.items()}
+    res["legs"] = EB.alternate(legs, rounds, dev)
     eng = m._bind().engine
     eng.profile_enable(True)
     m.intervention_moments(num_samples=ns, intervene=swap, **batch)
@@ -88,21 +51,5 @@ def run_shape(name, ns, rounds, dev):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=64)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    out = {"tool": "intervene_bench", "device": torch.cuda.get_device_name(dev),
-           "shapes": {n: run_shape(n, a.samples, a.rounds, dev) for n in SHAPES}}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    EB.main("intervene_bench", SHAPES, run_shape, "--samples", 64)

@@ -8,17 +8,12 @@ from slode_profile_read.  Prints one JSON line; --out writes it to a file.
     python tools/stats_pass_bench.py --out profiles/eval_stats_pass.json
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/stats_pass_bench.py --rounds 1      # the kernel's time on the profiler's clock
 """
-import argparse
-import importlib
-import json
-import os
 import statistics
-import sys
 import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import eval_bench as EB
 
 SHAPES = {
     "metric_cvs_B1024_T200_rk4": ("cvs", "mechanistic_cvs", "MechanisticModel", 1024, 200, dict(z_iext_dim=3, z_rtpr_dim=3, z_epsilon_dim=2)),
@@ -35,19 +30,11 @@ def _pass_us(fn, n_batches, dev):
 
 
 def run_shape(name, n_batches, rounds, dev):
-    from structured_latent_odes_amd import configs as CF
     from structured_latent_odes_amd import training as TR
     from structured_latent_odes_amd.svi import SVI
-    from structured_latent_odes_amd.synthetic import synthetic_batch
-    fam, mod, cls, B, T, kw = SHAPES[name]
-    cfg = getattr(CF, "load_config_" + fam)()
-    cfg.update(seq_len=T, solver="rk4", num_particles=1, **kw)
-    torch.manual_seed(3)
-    obs, labels, times = synthetic_batch(fam, B, T, cfg.obs_dim, seed=7)
-    m = getattr(importlib.import_module("structured_latent_odes_amd.models." + mod), cls)(cfg, dev, times.to(dev))
-    one = {"observations": obs.to(dev)}
-    one.update({k: v.to(dev) for k, v in labels.items()})
-    batches = [one] * n_batches                                    # already on the device: batch_to_device is a no-op copy
+    fam, B, T = SHAPES[name][0], *SHAPES[name][3:5]
+    m, one = EB.model_and_batch(SHAPES[name], dev)
+    batches = [one] * n_batches                                    # already on the device, labels [B, width]: batch_to_device is a no-op copy
     losses = [SVI(m.model, m.guide, None), SVI(m.model_meta, m.guide_meta, None)]
     legs = {"baseline": lambda post: TR.input_pred_stats(batches, m, losses, post, dev, fam),
             "fused": lambda post: TR.input_pred_stats_fused(batches, m, post, dev, fam)}
@@ -65,26 +52,11 @@ def run_shape(name, n_batches, rounds, dev):
             res[key]["baseline"]["median_us_per_batch"] - res[key]["fused"]["median_us_per_batch"] > res[key]["baseline"]["spread_us_per_batch"])
     eng = m._bind().engine
     eng.profile_enable(True)
-    m.eval_stats(is_post=True, **{k: (v.reshape(v.shape[0], -1) if k != "observations" else v) for k, v in one.items()})
+    m.eval_stats(is_post=True, **one)
     res["fused_call_kernels_us"] = eng.profile_read()
     eng.profile_enable(False)
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, default=50)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    out = {"tool": "stats_pass_bench", "device": torch.cuda.get_device_name(dev), "shapes": {n: run_shape(n, a.batches, a.rounds, dev) for n in SHAPES}}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    EB.main("stats_pass_bench", SHAPES, run_shape, "--batches", 50)
