@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 190 /* 0.1.9: slode_cohort_moments, slode_cohort_plan (0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 200 /* 0.2.0: slode_calibration, slode_calibration_plan (0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -40,6 +40,8 @@ extern "C" {
 #define SLODE_BOUND_SLOTS 4 /* floats of one slode_traj_bounds row */
 #define SLODE_COHORT_MAX_G 1024 /* most cohorts of one slode_cohort_moments call */
 #define SLODE_COHORT_MAX_CHUNK 64 /* most members one workgroup folds into one partial */
+#define SLODE_CALIBRATION_PHI2 0.97724986805182079f  /* Phi(2): the nominal level of mean + 2 s */
+#define SLODE_CALIBRATION_PHIM2 0.022750131948179195f /* Phi(-2): of mean - 2 s */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -519,6 +521,45 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
                          float* sd_subjects /* [Q,G,C,T] or NULL */, float* obs_mean /* [G,C,T] or NULL */, float* l1 /* [G,C] or NULL */,
                          void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- calibration: quantile coverage, pinball loss and band width by cohort as ONE call ------------------------------------------------------
+ * The ALD families train every head curve as a quantile (P(actual < pred) = tau); the Gauss families' recon reports mean +- 2 std under the
+ * same names.  Every family therefore has three curves v_0, v_1, v_2 per draw, channel and time point with nominal levels tau_0, tau_1, tau_2:
+ *   ALD    the heads mu_50, mu_75, mu_25 in head order; tau = 0.5, 0.5 + quantile_diff, 0.5 - quantile_diff
+ *   Gauss  mean, mean + 2 s, mean - 2 s with s = softplus(constant_std[c][t]), the scale of the likelihood; tau = 0.5, Phi(2), Phi(-2)
+ *          (SLODE_CALIBRATION_PHI2 / _PHIM2)
+ * The draws are EXACTLY those of slode_recon_moments / slode_cohort_moments for the same is_post; the cohorts (members, offsets, chunk) those
+ * of slode_cohort_moments.  For cohort g with n members and K = num_samples draws, y the member's observation at (c, t):
+ *   below[j][g][c][t]   int32: the (member, draw) pairs with y < v_j (strict: the complement of the reference's target.ge(pred))
+ *   inside[g][c][t]     int32: pairs with v_2 <= y < v_1
+ *   cross[g][c][t]      int32: pairs with v_2 > v_0 or v_0 > v_1 (quantile crossing; 0 by construction for the Gauss families)
+ *   pinball[j][g][c]    mean over members x draws x time of (y - v_j)(tau_j - [y < v_j])
+ *   width[g][c]         mean over members x draws x time of v_1 - v_2
+ * An empty cohort, or one with a member index outside [0, B): counts 0, float outputs NaN.  A NaN curve value compares false everywhere and
+ * makes the float outputs of its cohort NaN; nothing else is affected.  M K <= B K <= 2^30 - 1 (refused beyond): int32 holds every count.
+ * The integer outputs are a function of (parameters, inputs, noise, members, offsets) alone: bitwise equal across runs, launch grids, in-kernel
+ * vs explicit noise AND chunk sizes.  The float outputs (fp32 summands added in fp64 in a fixed order) are bitwise equal across runs, grids
+ * and the noise source; two chunk sizes agree to rounding.
+ *
+ * slode_calibration_plan: pure host arithmetic, the chunk rule of slode_cohort_plan (chunk == 0: a function of M alone); *n_partials =
+ * ceil(M / R) + G; *lds_bytes the dynamic LDS of the main kernel (budget 160 KiB); *scratch_bytes what slode_calibration needs at `scratch`. */
+int slode_calibration_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                           size_t* scratch_bytes);
+
+/* members / offsets / M / G / chunk / scratch: as slode_cohort_moments.  Launches (slode_profile_read): posterior "weff", "enc_fwd2", then
+ * "cohort_plan", "calibration", "calibration_merge"; the prior the last three.  Noise: as slode_recon_moments (batch->eps == NULL: ONE drawing
+ * call, counter n -> n + 1).  Enqueue only, capturable, a linear graph, no atomics.
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_recon_moments refuses
+ * for the same is_post (its LDS rung replaced by this call's own), with batch->obs NULL refused for BOTH is_post values; then members /
+ * offsets NULL with M > 0; M outside [0, B]; G outside [1, SLODE_COHORT_MAX_G]; chunk outside [0, SLODE_COHORT_MAX_CHUNK]; below NULL;
+ * observation strides other than dense [B,T,C] / [B,C,T] (the prior included); scratch NULL or misaligned; the LDS tables beyond 160 KiB; and
+ * with SLODE_ENOSPC scratch_bytes below the plan's figure. */
+int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                      const float* stage_t, const slode_batch* batch, int is_post, int num_samples,
+                      const int32_t* members /* device [M] */, const int32_t* offsets /* device [G + 1] */, int M, int G, int chunk,
+                      int32_t* below /* [3,G,C,T] */, int32_t* inside /* [G,C,T] or NULL */, int32_t* cross /* [G,C,T] or NULL */,
+                      float* pinball /* [3,G,C] or NULL */, float* width /* [G,C] or NULL */, void* scratch, size_t scratch_bytes,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data parallel with the small payload (one collective per step) -----------------------------------------------------
  * The encoder's chain rule is linear in G = g_pre^T [X | 1] (and the head layers' gradients in glat^T [hid | 1]): a rank only has to
  * contribute its shard's G, its head-layer products and its ODE-half gradient row with the loss scalar --
@@ -589,11 +630,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -10,6 +10,7 @@ MAX_GROUPS, MAX_HEADS, MAX_AUX, MAX_LABELS = 4, 3, 4, 4
 MAX_PARTICLES = 1024   # SLODE_MAX_PARTICLES
 EVAL_SLOTS = 8         # SLODE_EVAL_SLOTS: floats of one slode_eval_stats row [main, aux, L1 sum, hits of head 0..3, B]
 COHORT_MAX_G, COHORT_MAX_CHUNK = 1024, 64   # SLODE_COHORT_MAX_G, SLODE_COHORT_MAX_CHUNK
+CALIBRATION_PHI2, CALIBRATION_PHIM2 = 0.97724986805182079, 0.022750131948179195   # SLODE_CALIBRATION_PHI2 / _PHIM2: Phi(2), Phi(-2)
 FORECAST_MAX_T = 1 << 20   # SLODE_FORECAST_MAX_T: most points of an output grid (slode_stage_times_n, slode_forecast_moments)
 BOUND_SLOTS = 4        # SLODE_BOUND_SLOTS: floats of one slode_traj_bounds row [-ELBO, importance-weighted bound, effective sample size, mean NLL]
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
@@ -69,7 +70,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
            "slode_traj_bounds", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
-           "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments"]
+           "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
 
@@ -145,6 +146,9 @@ def load():
     lib.slode_cohort_plan.argtypes = [P(Shape), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_size_t), P(C.c_size_t)]
     lib.slode_cohort_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int,
                                          C.c_float, VP, VP, VP, VP, VP, VP, C.c_size_t, VP, C.c_size_t, VP]
+    lib.slode_calibration_plan.argtypes = lib.slode_cohort_plan.argtypes
+    lib.slode_calibration.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int,
+                                      VP, VP, VP, VP, VP, VP, C.c_size_t, VP, C.c_size_t, VP]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError here == the ABI in include/slode.h is not fully exported
     _lib = lib

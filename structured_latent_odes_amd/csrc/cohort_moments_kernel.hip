@@ -247,6 +247,11 @@ size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic) {
   return (size_t)cm_lds(s, fwd_generic(s, force_generic)).total * sizeof(float);
 }
 
+hipError_t slode_launch_cohort_plan(const int32_t* offsets, int M, int G, int R, int NP, int* cs, void* tab, hipStream_t stream) {
+  SLODE_LAUNCH("cohort_plan", cohort_plan_kernel, dim3(1), dim3(CM_NT), 0, stream, offsets, M, G, R, NP, cs, (int4*)tab);
+  return hipGetLastError();
+}
+
 hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream) {
   const slode_shape& s = a.d.s;
   const CohortScratch sc = slode_cohort_scratch(s, a.M, a.G, a.chunk);
@@ -259,7 +264,7 @@ hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t
   int4* tab = (int4*)(base + sc.tab);
   int* flags = (int*)(base + sc.flags);
   float* part = (float*)(base + sc.part);
-  SLODE_LAUNCH("cohort_plan", cohort_plan_kernel, dim3(1), dim3(CM_NT), 0, stream, a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab);
+  (void)slode_launch_cohort_plan(a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab, stream);
   CmK k{};
   fwd_fill(k.d, a.d);
   k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.sb = a.sb; k.PS = sc.partial_floats; k.clip = a.clip_min;

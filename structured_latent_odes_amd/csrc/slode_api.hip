@@ -1268,6 +1268,61 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
                    [&](hipStream_t st) { return slode_launch_cohort_moments(a, st); });
 }
 
+// ---- calibration: the draws of slode_recon_moments compared with the observations, counted by cohort (include/slode.h) ----
+int slode_calibration_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                           size_t* scratch_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: %s", bad);
+  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
+    return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL");
+  if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: num_samples = %d < 1", num_samples);
+  char why[128];
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: %s", why);
+  const size_t lds = slode_calibration_lds_bytes(*s, 0);
+  if (lds > SLODE_CALIBRATION_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, counts, fp64 sums, "
+                                       "observations, staged weights) exceed the budget of %d B", s->T, s->S, s->C, lds, SLODE_CALIBRATION_LDS_MAX);
+  const int R = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CalibrationScratch sc = slode_calibration_scratch(*s, M, G, R);
+  *chunk_out = R; *n_partials = sc.n_partials; *lds_bytes = lds; *scratch_bytes = sc.bytes;
+  return SLODE_OK;
+}
+
+// Refusals first -- slode_cohort_moments' for the same is_post, observations required on both sides; nothing launched, no draw consumed --
+// then, for the posterior, the fold + encoder launches of a forward-only step; then cohort_plan, calibration, calibration_merge.
+int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                      const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const int32_t* members,
+                      const int32_t* offsets, int M, int G, int chunk, int32_t* below, int32_t* inside, int32_t* cross, float* pinball,
+                      float* width, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+  DrawsCall d("slode_calibration", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+              "reduce recon_samples instead", "step table, counts, fp64 sums, observations, staged weights");
+  d.obs_null = "the curves are compared with observations (batch->obs is NULL)";
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "slode_calibration: members / offsets is NULL with M = %d", M);
+  char why[128];
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(h, SLODE_EINVAL, "slode_calibration: %s", why);
+  if (!below) return fail(h, SLODE_EINVAL, "slode_calibration: below is NULL");
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (os[0] != (long long)s->C * s->T || !(t_major || c_major))
+    return fail(h, SLODE_EINVAL, "slode_calibration: observation strides (%lld, %lld, %lld) are not taken: the comparisons need dense [B,T,C] or "
+                                 "[B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
+  if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "slode_calibration: scratch is NULL or not 16-byte aligned");
+  if ((rc = eval_lds(h, s, d, slode_calibration_lds_bytes(*s, h->ode_generic), SLODE_CALIBRATION_LDS_MAX)) != SLODE_OK) return rc;
+  CalibrationLaunch a{};
+  a.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CalibrationScratch sc = slode_calibration_scratch(*s, M, G, a.chunk);
+  if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "slode_calibration: scratch_bytes %zu B < required %zu B (slode_calibration_plan)", scratch_bytes, sc.bytes);
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, sc.n_partials);
+  a.obs = batch->obs; a.sb = os[0]; a.t_major = t_major && !c_major ? 1 : 0;
+  a.members = members; a.offsets = offsets; a.M = M; a.G = G;
+  a.below = below; a.inside = inside; a.cross = cross; a.pinball = pinball; a.width = width; a.scratch = scratch;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_calibration(a, st); });
+}
+
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {
   if (check_shape(s) || !lay) return 0;
   const int part = kind == SLODE_SVI_AUX ? lay->cstd - lay->aux_w1[0] : lay->n_params - lay->ode_begin;

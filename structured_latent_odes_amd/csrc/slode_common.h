@@ -654,6 +654,40 @@ inline int slode_cohort_default_chunk(int M) {
 hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic);
 
+// the plan launch of the cohort calls (cohort_moments_kernel.hip): offsets [G + 1] -> cs [G + 1] and the chunk table tab [NP] of 4 ints
+hipError_t slode_launch_cohort_plan(const int32_t* offsets, int M, int G, int R, int NP, int* cs, void* tab, hipStream_t stream);
+
+// Calibration pass (calibration_kernel.hip; slode_calibration): the draws of d compared with the observations, counted by cohort.  members /
+// offsets / chunk as in CohortMomentsLaunch; obs: dense rows of C*T floats (sb apart), t_major: [T][C] inside a row, else [C][T]; below
+// [3, G, C, T], inside / cross [G, C, T] int32, pinball [3, G, C], width [G, C] (all but below may be NULL).  scratch:
+// slode_calibration_scratch(..).bytes, 16-byte aligned.  Launches cohort_plan, calibration, calibration_merge.
+struct CalibrationLaunch {
+  DrawsLaunch d;
+  const float* obs;
+  int64_t sb;
+  const int32_t *members, *offsets;
+  int32_t *below, *inside, *cross;
+  float *pinball, *width;
+  void* scratch;
+  int M, G, chunk, t_major;
+};
+// The scratch of one call (byte offsets, multiples of 16): cs, the chunk table and the flags as in CohortScratch, then n_partials partials of
+// partial_bytes: fp64 sums [4: pinball 0..2, width][C][T] | int32 counts [5: below 0..2, inside, cross][C][T].
+struct CalibrationScratch { int n_partials; size_t partial_bytes, cs, tab, flags, part, bytes; };
+inline CalibrationScratch slode_calibration_scratch(const slode_shape& s, int M, int G, int R) {
+  CalibrationScratch o{};
+  const size_t CT = (size_t)s.C * s.T;
+  o.n_partials = (M + R - 1) / R + G;
+  o.partial_bytes = (4 * CT * sizeof(double) + 5 * CT * sizeof(int) + 15) & ~(size_t)15;
+  auto pad = [](size_t ints) { return ((ints + 3) & ~(size_t)3) * sizeof(int); };
+  o.cs = 0; o.tab = o.cs + pad((size_t)G + 1); o.flags = o.tab + (size_t)o.n_partials * 16; o.part = o.flags + pad((size_t)o.n_partials);
+  o.bytes = o.part + (size_t)o.n_partials * o.partial_bytes;
+  return o;
+}
+#define SLODE_CALIBRATION_LDS_MAX (160 * 1024)   // the LDS of one CU: staged weights, step table, counts, fp64 sums, observations and the scale table must fit
+hipError_t slode_launch_calibration(const CalibrationLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_calibration_lds_bytes(const slode_shape& s, int force_generic);
+
 #define SLODE_REDUCE_GROUPS 16
 struct ReduceLaunch {   // (filled by field name: everything not set is null / 0)
   slode_shape s;

@@ -1,7 +1,8 @@
 // The fixed-grid forward pass and the draw loop the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
-// intervene_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip; no other translation unit includes this header): each phase ONCE --
+// intervene_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip, calibration_kernel.hip; no other translation unit includes this
+// header): each phase ONCE --
 //   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads),
-//                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort) and the host functions that
+//                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort, calibration) and the host functions that
 //                      fill them from slode_shape / slode_layout / DrawsLaunch
 //   prior nets         fwd_prior_at: loc / log scale of one latent dim from the staged labels
 //   step coefficients  fwd_step_coeffs: x' = A x + b of one grid step for euler / midpoint / rk4, the a, d evaluator passed in;

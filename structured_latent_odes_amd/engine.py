@@ -629,6 +629,56 @@ class Engine:
                          self._p(sd_subjects), self._p(obs_mean), self._p(l1), self._p(self._f32(scratch, "scratch")), scratch.numel() * 4)
         return mean, sd, sd_subjects, obs_mean, l1
 
+    # ---- calibration: the draws of recon_moments compared with the observations, counted by cohort -----------------------------------
+    CALIBRATION_OUTPUTS = ("inside", "cross", "pinball", "width")
+
+    def calibration_plan(self, B: int, M: int, G: int, num_samples: int, chunk: int = 0):
+        """``slode_calibration_plan``: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes) of ``calibration`` for
+        these sizes; host arithmetic only, the chunk rule of ``cohort_plan``."""
+        r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_calibration_plan(C.byref(self.shape(B)), int(M), int(G), int(num_samples), int(chunk), C.byref(r),
+                                                               C.byref(n), C.byref(lds), C.byref(scr)))
+        return int(r.value), int(n.value), int(lds.value), int(scr.value)
+
+    def _out_i32(self, t, name: str, shp):
+        """An int32 output tensor of an eval-side call, allocated when None."""
+        if t is None:
+            return torch.empty(shp, dtype=torch.int32, device=self.device)
+        if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shp):
+            raise ValueError("%s must be a contiguous int32 tensor %s on %s" % (name, list(shp), self.device))
+        return t
+
+    def calibration(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, members, offsets, G: int, chunk: int = 0,
+                    below=None, inside=None, cross=None, pinball=None, width=None, outputs=CALIBRATION_OUTPUTS, scratch=None):
+        """slode_calibration: the three curves of every draw of ``recon_moments`` (ALD: mu_50, mu_75, mu_25; Gauss: mean, mean +- 2 s)
+        against the observations, by cohort -- ``(below, inside, cross, pinball, width)``: int32 counts of (member, draw) pairs with y < v_j
+        [3, G, C, T], with v_2 <= y < v_1 and with crossing curves [G, C, T]; the mean pinball loss [3, G, C] and the mean band width
+        [G, C], float32.  ``members`` / ``offsets`` / ``chunk`` / ``scratch`` as ``cohort_moments``; ``outputs`` names the optional outputs
+        to produce.  Enqueued on the current stream.  Raises SlodeError naming the reason for what the kernel does not take (everything
+        ``cohort_moments`` refuses; no observations; LDS budget): nothing is launched and no draw is consumed then."""
+        for name, t in (("members", members), ("offsets", offsets)):
+            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("%s must be a contiguous 1-d int32 tensor on %s" % (name, self.device))
+        M, G = members.numel(), int(G)
+        if offsets.numel() != G + 1:
+            raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
+        Cn, T = self._head_shape(G)[2:]
+        below = self._out_i32(below, "below", (3, G, Cn, T))
+        if inside is not None or "inside" in outputs:
+            inside = self._out_i32(inside, "inside", (G, Cn, T))
+        if cross is not None or "cross" in outputs:
+            cross = self._out_i32(cross, "cross", (G, Cn, T))
+        if pinball is not None or "pinball" in outputs:
+            pinball = self._out(pinball, "pinball", (3, G, Cn))
+        if width is not None or "width" in outputs:
+            width = self._out(width, "width", (G, Cn))
+        if scratch is None:    # (sized by the library's own arithmetic; a refusal there is raised as the call's would be)
+            scratch = torch.empty((self.calibration_plan(B, M, G, max(int(num_samples), 1), chunk)[3] + 3) // 4, dtype=torch.float32, device=self.device)
+        self._batch_call(self.lib.slode_calibration, params, batch, B, 1, 1 if is_post else 0, int(num_samples), self._p(members),
+                         self._p(offsets), M, G, int(chunk), self._p(below), self._p(inside), self._p(cross), self._p(pinball), self._p(width),
+                         self._p(self._f32(scratch, "scratch")), scratch.numel() * 4)
+        return below, inside, cross, pinball, width
+
     def traj_bounds(self, params, batch: L.Batch, B: int, num_draws: int, bounds=None, loss_kb=None, particles: int = 1):
         """slode_traj_bounds: per trajectory, from ``num_draws`` posterior draws, ``bounds`` float32 [B, L.BOUND_SLOTS] = [-ELBO (mean of
         the per-draw losses), importance-weighted bound -log(1/K sum exp(-loss)), effective sample size of the weights, mean negative

@@ -531,6 +531,151 @@ class MechanisticBase(nn.Module):
         return named + [("observations_cohort_mean.npy", res["observations"]), ("cohort_keys.npy", res["keys"]),
                         ("cohort_count.npy", res["count"]), ("l1_%s_cohort.npy" % tag, res["l1"])]
 
+    # ---- calibration: are the quantile curves quantiles?  Coverage, pinball loss, band width and crossings, by cohort -------------------
+    CALIBRATION_FILES = ("below", "below_t", "inside", "cross", "pinball", "width")
+
+    def calibration_nominal(self) -> torch.Tensor:
+        """``[3]`` float64: the nominal levels of the three curves -- ALD: 0.5, 0.5 + quantile_diff, 0.5 - quantile_diff (the heads mu_50,
+        mu_75, mu_25 are trained so that P(actual < pred) = tau); Gauss: 0.5, Phi(2), Phi(-2) (mean, mean + 2 s, mean - 2 s)."""
+        from .. import _lib as L
+        if self.GAUSS:
+            return torch.tensor([0.5, L.CALIBRATION_PHI2, L.CALIBRATION_PHIM2], dtype=torch.float64)
+        d = float(self.config.quantile_diff)
+        return torch.tensor([0.5, 0.5 + d, 0.5 - d], dtype=torch.float64)
+
+    def calibration(self, observations, is_post, num_samples: int, cohorts=None, eps=None, chunk: int = 0, num_cohorts=None, **labels):
+        """How the three curves of the family lie against the observations, per cohort (default: ONE cohort, the whole batch; else as
+        ``cohort_moments``: a ``[B]`` id tensor or a tuple of label names).  Curves v_0, v_1, v_2: ``mu_50, mu_75, mu_25``, or ``mean,
+        mean + 2 s, mean - 2 s`` (s = softplus(constant_std)) for the Gaussian family; their nominal levels under ``"nominal"`` ``[3]``.
+        Over the members of a cohort x ``num_samples`` draws (those of ``recon_moments``): ``"below"`` ``[3, G, C]`` / ``"below_t"``
+        ``[3, G, C, T]`` the fraction with ``y < v_j`` (calibrated: equal to nominal); ``"inside"`` / ``"inside_t"`` the fraction with
+        ``v_2 <= y < v_1``; ``"cross"`` / ``"cross_t"`` the fraction whose curves cross (``v_2 > v_0`` or ``v_0 > v_1``); ``"pinball"``
+        ``[3, G, C]`` the mean of ``(y - v_j)(tau_j - [y < v_j])``; ``"width"`` ``[G, C]`` the mean of ``v_1 - v_2``; ``"count"`` ``[G]``,
+        ``"keys"``; the raw int32 tensors under ``"counts"`` (``below`` ``[3, G, C, T]``, ``inside``, ``cross`` ``[G, C, T]``).  An empty
+        cohort has counts 0 and NaN elsewhere.  ONE engine call (``slode_calibration``): no ``[B, C, T, num_samples]`` tensor exists, and
+        the counts are exact whatever the launch grid or ``chunk``.  Where the engine refuses (adaptive solver, strided observations,
+        measured arms, more than 1024 cohorts) the same dict is composed from ``recon_samples`` in chunks of rows."""
+        b = self._bind()
+        B, ns = observations.shape[0], self._count(num_samples)
+        if cohorts is None:
+            cohorts, num_cohorts = torch.zeros(B, dtype=torch.int64, device=observations.device), 1
+        ids, keys, G, members, offsets, count = self._cohort_lists(observations, cohorts, num_cohorts, labels)
+
+        def fused():
+            return b.engine.calibration(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, members, offsets, G, chunk=chunk)
+        below, inside, cross, pinball, width = self._fused_or_composed(
+            fused, lambda: self._calibration_composed(observations, is_post, ns, ids, G, count, eps, labels))
+        T = observations.shape[2]
+        den = (count.to(torch.float64) * ns).reshape(G, 1, 1)                  # (0 for an empty cohort: its fractions are NaN)
+        res = {"nominal": self.calibration_nominal(), "pinball": pinball, "width": width, "count": count, "keys": keys,
+               "counts": {"below": below, "inside": inside, "cross": cross}}
+        for n, v in res["counts"].items():
+            res[n + "_t"] = v.to(torch.float64) / den
+            res[n] = v.to(torch.int64).sum(dim=-1).to(torch.float64) / (den[..., 0] * T)
+        return res
+
+    def _calibration_curves(self, got):
+        """The three curves ``[rows, C, T, ns]`` (fp32, as the decoder gives them) of one ``recon_samples`` result."""
+        if self.GAUSS:
+            w = 2.0 * torch.nn.functional.softplus(self.decoder.constant_std.detach()).to(got["mean"].dtype)[None, :, :, None]
+            return got["mean"], got["mean"] + w, got["mean"] - w
+        return got["mu_50"], got["mu_75"], got["mu_25"]
+
+    def _calibration_composed(self, observations, is_post, ns, ids, G, count, eps, labels):
+        """The composed route: ``recon_samples`` of ``MOMENTS_CHUNK_ROWS // ns`` rows at a time (ONE drawing call for the whole batch, sliced
+        per chunk); comparisons in torch, integer sums per cohort, the float summands (fp32, as the kernel forms them) added in fp64."""
+        dev = observations.device
+        Cn, T = observations.shape[1], observations.shape[2]
+        slot = torch.where(ids < 0, torch.full_like(ids, G), ids)           # (bucket G: the trajectories of no cohort)
+        tau = self.calibration_nominal().to(dev, torch.float32)
+        n_int = torch.zeros(5, G + 1, Cn, T, dtype=torch.int64, device=dev)
+        s_flt = torch.zeros(4, G + 1, Cn, dtype=torch.float64, device=dev)
+        bad = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+        for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+            v = self._calibration_curves(self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d))
+            y = d["observations"].to(torch.float32)[..., None]
+            lt = [y < vj for vj in v]
+            ind = lt + [(v[2] <= y) & lt[1], (v[2] > v[0]) | (v[0] > v[1])]
+            for j, m in enumerate(ind):
+                n_int[j].index_add_(0, slot[lo:hi], m.sum(dim=-1))
+            terms = [(y - v[j]) * torch.where(lt[j], tau[j] - 1.0, tau[j]) for j in range(3)] + [v[1] - v[2]]
+            for j, t in enumerate(terms):
+                s_flt[j].index_add_(0, slot[lo:hi], t.to(torch.float64).sum(dim=(-1, -2)))
+            bad.index_add_(0, slot[lo:hi], (torch.isnan(v[0]) | torch.isnan(v[1]) | torch.isnan(v[2])).flatten(1).any(dim=1).to(torch.int64))
+            del v, lt, ind, terms
+        den = (count.to(torch.float64) * ns * T).reshape(1, G, 1)
+        flt = s_flt[:, :G] / den
+        flt = torch.where(((count > 0) & (bad[:G] == 0)).reshape(1, G, 1), flt, torch.full_like(flt, float("nan"))).to(torch.float32)
+        n32 = n_int[:, :G].to(torch.int32)
+        return n32[:3].contiguous(), n32[3].contiguous(), n32[4].contiguous(), flt[:3].contiguous(), flt[3].contiguous()
+
+    def save_calibration(self, results_dir: str, batches, is_post, num_samples: int, cohorts=None):
+        """``calibration`` over a loader (an iterable of batch dicts: ``observations`` and the label tensors; a batch may carry its own
+        ``cohorts`` ids and ``eps``), the cohorts -- ids or label names, merged across batches by their keys -- pooled: the integer counts
+        added exactly (int64 on the host), the float means weighted by their point counts in fp64.  Writes ``calibration_{below,below_t,inside,cross,pinball,width}_
+        <post|prior>.npy`` (fractions ``[3, G, C]``, ``[3, G, C, T]``, ``[G, C]``, ``[G, C]``; means ``[3, G, C]``, ``[G, C]``),
+        ``calibration_nominal.npy`` and ``calibration_count.npy``; returns ``(paths, pooled result)``."""
+        import numpy as np
+        ns = self._count(num_samples)
+        pool = {}                                                              # key row (tuple) -> sums
+        for d in batches:
+            d = dict(d)
+            obs = d.pop("observations")
+            res = self.calibration(obs, is_post, ns, cohorts=d.pop("cohorts", cohorts), **d)
+            keys = res["keys"].cpu().numpy()
+            cnt = res["count"].cpu().numpy().astype(np.int64)
+            ints = {n: v.cpu().numpy().astype(np.int64) for n, v in res["counts"].items()}
+            pin, wid = res["pinball"].cpu().numpy().astype(np.float64), res["width"].cpu().numpy().astype(np.float64)
+            T = obs.shape[2]
+            for g in range(len(cnt)):
+                k = tuple(np.atleast_1d(keys[g]).tolist())
+                p = pool.setdefault(k, {"count": 0, "below": 0, "inside": 0, "cross": 0, "pin": np.zeros(pin.shape[::2]),
+                                        "wid": np.zeros(wid.shape[1:]), "pts": 0})
+                p["count"] += int(cnt[g])
+                for n in ("below", "inside", "cross"):
+                    p[n] = p[n] + (ints[n][:, g] if n == "below" else ints[n][g])
+                if cnt[g]:                                                     # (an empty cohort's NaN means carry no weight)
+                    w = int(cnt[g]) * ns * T
+                    p["pin"], p["wid"], p["pts"] = p["pin"] + w * pin[:, g], p["wid"] + w * wid[g], p["pts"] + w
+        if not pool:
+            raise ValueError("save_calibration: no batch")
+        order = sorted(pool)
+        cnt = np.array([pool[k]["count"] for k in order], dtype=np.int64)
+        below = np.stack([pool[k]["below"] for k in order], axis=1)           # [3, G, C, T]
+        inside, cross = (np.stack([pool[k][n] for k in order], axis=0) for n in ("inside", "cross"))
+        T = below.shape[-1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            den = (cnt * ns).astype(np.float64).reshape(-1, 1, 1)
+            pts = np.array([pool[k]["pts"] for k in order], dtype=np.float64)
+            out = {"below_t": below / den, "below": below.sum(-1) / (den[..., 0] * T), "inside": inside.sum(-1) / (den[..., 0] * T),
+                   "cross": cross.sum(-1) / (den[..., 0] * T),
+                   "pinball": np.stack([pool[k]["pin"] for k in order], axis=1) / pts.reshape(1, -1, 1),
+                   "width": np.stack([pool[k]["wid"] for k in order], axis=0) / pts.reshape(-1, 1)}
+        tag = "post" if is_post else "prior"
+        named = [("calibration_%s_%s.npy" % (n, tag), torch.from_numpy(np.ascontiguousarray(out[n]))) for n in self.CALIBRATION_FILES]
+        named += [("calibration_nominal.npy", self.calibration_nominal()), ("calibration_count.npy", torch.from_numpy(cnt))]
+        out.update(count=cnt, keys=np.array(order), nominal=self.calibration_nominal().numpy(),
+                   counts={"below": below, "inside": inside, "cross": cross})
+        return self._save_arrays(results_dir, named), out
+
+    @staticmethod
+    def calibration_line(res, tag: str) -> str:
+        """One line: nominal against empirical level per curve, band coverage, crossing share and pinball loss, pooled over the cohorts
+        (weighted by their counts) and averaged over the channels."""
+        import numpy as np
+        cnt = np.asarray(res["count"], dtype=np.float64)
+        w = cnt / max(cnt.sum(), 1.0)
+
+        def pooled(a, axis):
+            a = np.where(np.isnan(np.asarray(a, dtype=np.float64)), 0.0, np.asarray(a, dtype=np.float64))
+            return np.tensordot(a, w, axes=([axis], [0]))
+        below, pin = pooled(res["below"], 1).mean(-1), pooled(res["pinball"], 1).mean(-1)
+        nom = np.asarray(res["nominal"], dtype=np.float64)
+        levels = "  ".join("tau=%.4f:%.4f" % (nom[j], below[j]) for j in range(3))
+        return "calibration_%s: %s  band=%.4f (nominal %.4f)  crossing=%.4f  pinball=(%.6f,%.6f,%.6f)  width=%.6f" % (
+            tag, levels, pooled(res["inside"], 0).mean(), nom[1] - nom[2], pooled(res["cross"], 0).mean(), pin[0], pin[1], pin[2],
+            pooled(res["width"], 0).mean())
+
     # ---- forecast: the same draws, solved on an output grid of the caller's -- past the observed window, or finer than the training grid ----
     def horizon_times(self, extra_steps: int, refine: int = 1) -> torch.Tensor:
         """The training grid with each interval split in ``refine`` equal parts, followed by ``extra_steps`` steps of the (refined) last

@@ -111,7 +111,7 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
-          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False):
+          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -126,7 +126,10 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     order, written to ``results_dir`` under ``save_forecast_moments``' file names; 0 (the default): no such stage runs.
     cohort_curves: after training, the per-condition curves of the reference's evaluation notebooks on the first test batch -- cohorts
     from all of the family's labels, posterior and prior, config.num_samples draws (``save_cohort_moments``) -- and the notebooks' number,
-    printed as ``l1_error_post`` / ``l1_error_prior``: the mean of ``l1`` over non-empty cohorts and channels; off by default."""
+    printed as ``l1_error_post`` / ``l1_error_prior``: the mean of ``l1`` over non-empty cohorts and channels; off by default.
+    calibration: after training, the best model's calibration pass over the validation loader, posterior and prior, config.num_samples
+    draws, the whole loader as one cohort (``save_calibration``: coverage of every curve against its nominal level, band coverage, crossing
+    share, pinball loss), one printed line per side (``calibration_post: ...``); off by default."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -197,7 +200,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     print(tail)
     logging.debug(tail)
     out_dir = results_dir or "results_%s" % config.model
-    if sample_moments or cohort_curves or forecast_steps:      # (the stages that draw; a config without num_samples serves the others)
+    if sample_moments or cohort_curves or forecast_steps or calibration:      # (the stages that draw; a config without num_samples serves the others)
         num_samples = int(getattr(config, "num_samples", 200))
     if sample_moments:
         d = batch_to_device(next(iter(test_b)), device, family)
@@ -210,6 +213,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
             res = best_model.cohort_moments(is_post=is_post, num_samples=num_samples, cohorts=tuple(best_model.LABELS), **d)
             written = best_model._save_arrays(out_dir, best_model._cohort_named(res, is_post))
             line = "l1_error_%s: %s" % ("post" if is_post else "prior", float(res["l1"][res["count"] > 0].mean()))
+            print(line)
+            logging.debug("%s (%s)", line, written)
+    if calibration:
+        for is_post in (True, False):
+            written, res = best_model.save_calibration(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, num_samples)
+            line = best_model.calibration_line(res, "post" if is_post else "prior")
             print(line)
             logging.debug("%s (%s)", line, written)
     if test_bounds:
@@ -286,6 +295,9 @@ def build_parser():
     ap.add_argument("--cohort-curves", action="store_true",
                     help="after training: per-condition mean / sd curves, mean observations and the evaluation notebooks' l1_error on the first "
                          "test batch, posterior and prior (save_cohort_moments)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="after training: quantile coverage against the nominal levels, band coverage, crossing share and pinball loss of the best "
+                         "model over the validation loader, posterior and prior (save_calibration: calibration_*.npy)")
     return ap
 
 
@@ -304,6 +316,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
         kw["cohort_curves"] = True
+    if a.calibration:
+        kw["calibration"] = True
     if a.data_dir:
         got = real_batches(config, family, a.data_dir)
         kw["train_batches"], kw["val_batches"], kw["times"] = got[:3]
