@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 200 /* 0.2.0: slode_calibration, slode_calibration_plan (0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 210 /* 0.2.1: slode_label_evidence (0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -38,6 +38,8 @@ extern "C" {
 #define SLODE_MAX_PARTICLES 1024
 #define SLODE_EVAL_SLOTS 8 /* floats of one slode_eval_stats row */
 #define SLODE_BOUND_SLOTS 4 /* floats of one slode_traj_bounds row */
+#define SLODE_EVIDENCE_SLOTS 4 /* floats of one (trajectory, hypothesis) row of slode_label_evidence */
+#define SLODE_EVIDENCE_MAX_V 64 /* most hypotheses of one slode_label_evidence call */
 #define SLODE_COHORT_MAX_G 1024 /* most cohorts of one slode_cohort_moments call */
 #define SLODE_COHORT_MAX_CHUNK 64 /* most members one workgroup folds into one partial */
 #define SLODE_CALIBRATION_PHI2 0.97724986805182079f  /* Phi(2): the nominal level of mean + 2 s */
@@ -389,6 +391,40 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
                       const float* stage_t, const slode_batch* batch, int num_draws, float* bounds /* [B, SLODE_BOUND_SLOTS] */,
                       float* loss_kb /* [num_draws, B] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- label evidence: V label hypotheses scored per trajectory as ONE call (no reference counterpart: the reference predicts labels with the
+ * auxiliary heads q(label | z_g) alone; the conditional priors p(z_g | u_g) exist to ask "which input does the generative model believe produced
+ * these curves?", p(u | x) ~ p(u) p(x | u)) ------------------------------------------------------------------------------------------------------
+ * hyp_labels: batch->n_labels device pointers; tensor i is a dense [V, batch->label_width[i]] table shared by all trajectories, or NULL: label i
+ * is not hypothesised and every hypothesis keeps the trajectory's own tensor for it (the convention of cf_labels in slode_intervene_moments).
+ * Hypothesis v for trajectory b is the label row u_b with the columns of every non-NULL tensor replaced by row v of that tensor.
+ * loss[v][k][b] is the main loss of the single row b on draw k with its labels replaced by hypothesis v -- exactly what slode_traj_bounds writes
+ * to loss_kb[k][b] when called with those labels and the same noise; the draws are posterior draws z = loc(x_b) + scale(x_b) eps[k][b], which do
+ * not depend on the hypothesis: the encoder runs once, every draw is solved and decoded once, and a hypothesis costs its log p(z | u_v) (and, where
+ * the main model scores the labels, its label log-probabilities on logits that depend on z alone).  Written per (b, v), as ONE 16-byte store:
+ *   evidence[b][v][0]  mean over k of loss[v][k][b]: the -ELBO under hypothesis v
+ *   evidence[b][v][1]  -log(1/K sum_k exp(-loss[v][k][b])): the importance-weighted bound on -log p(x_b | u_v)
+ *   evidence[b][v][2]  effective sample size of those weights, in [1, K] -- per hypothesis: q(z | x) is a poor proposal for a wrong u, and the
+ *                      ESS says when the bound is one draw wide
+ *   evidence[b][v][3]  log_post = log_prior[v] - slot 1 - logsumexp_v'(log_prior[v'] - slot 1 [v']); log_prior == NULL: all 0.  Formed in fp64
+ *                      from the fp64 bounds before they are rounded, in the order v = 0 .. V - 1; exactly 0 at V = 1
+ * best[b] (or NULL): the arg-max over v of log_post, the lowest index on a tie.  loss_vkb (or NULL): every loss[v][k][b], [V, num_draws, B].
+ * Slots 0-2 of column v and loss_vkb[v] are bit for bit what slode_traj_bounds returns for that label set on the same noise (both kernels execute
+ * the same routines).  Noise: as slode_traj_bounds (batch->eps == NULL: drawing calls n .. n + K - 1, the counter left at n + K; else a dense
+ * [K, B, L] tensor).  The result is a function of (parameters, inputs, hypotheses, noise) alone: bitwise equal from run to run, for every grid,
+ * for in-kernel and explicit noise.  No atomics.  Enqueue only: no allocation, no synchronisation, no read-back; capturable as a linear graph.
+ * Three launches ("weff", "enc_fwd2", "label_evidence" in slode_profile_read).  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_traj_bounds refuses -- a
+ * NULL handle (before anything else); num_draws < 1 (and B x num_draws beyond 2^30 - 1 noise rows); adaptive solver; particles > 1; the measured
+ * arms; batch->obs NULL; observation strides the folded encoder path does not take or SLODE_NO_FOLD -- then: evidence NULL or not 16-byte aligned;
+ * V outside [1, SLODE_EVIDENCE_MAX_V]; hyp_labels NULL, or every entry NULL; batch->n_labels == 0; LDS tables (step table, observations, staged
+ * weights, the V prior rows 3 V L, the K V losses) beyond the budget of 160 KiB.  There is no composed fallback: the composed route is V
+ * slode_traj_bounds calls, which refuse the same shapes. */
+int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                         const float* stage_t, const slode_batch* batch, int num_draws, const float* const* hyp_labels, int V,
+                         const float* log_prior /* device [V] or NULL */, float* evidence /* [B, V, SLODE_EVIDENCE_SLOTS] */,
+                         int32_t* best /* [B] or NULL */, float* loss_vkb /* [V, num_draws, B] or NULL */, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- counterfactual curves as ONE call (no reference counterpart: the reference's recon takes the whole latent from the posterior or the whole
  * latent from the conditional prior; the structured latent exists to ask "what would THIS subject's curves have looked like under THAT input?") ----
  * For trajectory b and draw k, with ONE noise row eps[k][b][0..L) shared by both arms:
@@ -630,11 +666,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

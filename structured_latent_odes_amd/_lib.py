@@ -13,6 +13,8 @@ COHORT_MAX_G, COHORT_MAX_CHUNK = 1024, 64   # SLODE_COHORT_MAX_G, SLODE_COHORT_M
 CALIBRATION_PHI2, CALIBRATION_PHIM2 = 0.97724986805182079, 0.022750131948179195   # SLODE_CALIBRATION_PHI2 / _PHIM2: Phi(2), Phi(-2)
 FORECAST_MAX_T = 1 << 20   # SLODE_FORECAST_MAX_T: most points of an output grid (slode_stage_times_n, slode_forecast_moments)
 BOUND_SLOTS = 4        # SLODE_BOUND_SLOTS: floats of one slode_traj_bounds row [-ELBO, importance-weighted bound, effective sample size, mean NLL]
+EVIDENCE_SLOTS = 4     # SLODE_EVIDENCE_SLOTS: floats of one slode_label_evidence row [-ELBO, importance-weighted bound, effective sample size, log posterior]
+EVIDENCE_MAX_V = 64    # SLODE_EVIDENCE_MAX_V: most hypotheses of one slode_label_evidence call
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
 EULER, MIDPOINT, RK4, DOPRI5, BOSH3, FEHLBERG2, ADAPTIVE_HEUN = 0, 1, 2, 3, 4, 5, 6
 ALD, GAUSS = 0, 1
@@ -69,7 +71,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_initialize_state", "slode_prior_nets", "slode_label_heads", "slode_dopri5_step_counts", "slode_decode_heads_bwd",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
-           "slode_traj_bounds", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
+           "slode_traj_bounds", "slode_label_evidence", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
            "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
@@ -137,6 +139,7 @@ def load():
     lib.slode_eval_stats.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, VP, VP, C.c_size_t, VP]
     lib.slode_recon_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, VP, C.c_size_t, VP]
     lib.slode_traj_bounds.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, VP, VP, VP, C.c_size_t, VP]
+    lib.slode_label_evidence.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, P(VP), C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_intervene_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), P(VP), C.c_uint, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_num_stage_times_n.argtypes = [P(Shape), C.c_int]
     lib.slode_stage_times_n.argtypes = [VP, P(Shape), C.c_int, VP, VP, VP]

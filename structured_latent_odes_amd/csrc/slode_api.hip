@@ -845,7 +845,7 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
   return elbo_step_impl(h, s, lay, c);
 }
 
-// ---- what the eval-side calls (eval_stats, recon_moments, traj_bounds, intervene_moments, forecast_moments, cohort_moments) share ----
+// ---- what the eval-side calls (eval_stats, recon_moments, traj_bounds, label_evidence, intervene_moments, forecast_moments, cohort_moments) share ----
 // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
 static int eval_grid_for(const slode_ctx* h, int B) {
   long long g = B;
@@ -1069,6 +1069,48 @@ int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* 
   ClockScope clock_scope(h, true);
   if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
   HIP_TRY(h, slode_launch_traj_bounds(a, c.stream));
+  return SLODE_OK;
+}
+
+// V label hypotheses scored on the num_draws posterior draws of every trajectory (include/slode.h): slode_traj_bounds' refusals through the
+// same ladder, then the call's own -- nothing launched, no draw consumed -- then slode_traj_bounds' launches with the hypothesis kernel in
+// place of its own.  No composed fallback: the composed route is V slode_traj_bounds calls, which refuse the same shapes.
+int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                         const float* stage_t, const slode_batch* batch, int num_draws, const float* const* hyp_labels, int V,
+                         const float* log_prior, float* evidence, int32_t* best, float* loss_vkb, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  const EvalCall d{"slode_label_evidence", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
+                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
+                   " (and no SLODE_NO_FOLD)"};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (!evidence || ((uintptr_t)evidence & 15) != 0) return fail(h, SLODE_EINVAL, "slode_label_evidence: evidence is NULL or not 16-byte aligned");
+  if (V < 1 || V > SLODE_EVIDENCE_MAX_V) return fail(h, SLODE_EINVAL, "slode_label_evidence: V = %d out of range [1, %d]", V, SLODE_EVIDENCE_MAX_V);
+  if (!hyp_labels) return fail(h, SLODE_EINVAL, "slode_label_evidence: hyp_labels is NULL");
+  bool any = false;
+  for (int i = 0; i < batch->n_labels && i < SLODE_MAX_LABELS; ++i) any = any || hyp_labels[i] != nullptr;
+  if (batch->n_labels == 0) return fail(h, SLODE_EINVAL, "slode_label_evidence: the hypothesis tables take the widths of batch->labels (n_labels is 0)");
+  if (!any) return fail(h, SLODE_EINVAL, "slode_label_evidence: every entry of hyp_labels is NULL (no label is hypothesised)");
+  const size_t lds = slode_label_evidence_lds_bytes(*s, num_draws, V, h->ode_generic);
+  if (lds > SLODE_LABEL_EVIDENCE_LDS_MAX)
+    return fail(h, SLODE_EINVAL, "slode_label_evidence: the LDS tables of T = %d, S = %d, C = %d, num_draws = %d, V = %d (%zu B: step table, observations, "
+                                 "staged weights, the V prior rows, the num_draws x V losses) exceed the budget of %d B; fewer draws or hypotheses per call fit",
+                s->T, s->S, s->C, num_draws, V, lds, SLODE_LABEL_EVIDENCE_LDS_MAX);
+  LabelEvidenceLaunch a{};
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  a.hyp = a.lab;   // widths and offsets as the batch's
+  for (int i = 0; i < SLODE_MAX_LABELS; ++i) a.hyp.p[i] = i < a.lab.n ? hyp_labels[i] : nullptr;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = batch->obs_strides[0]; a.t_major = p.t_major ? 1 : 0;
+  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.sigtab = p.w.sigtab; a.log_prior = log_prior;
+  a.evidence = evidence; a.best = best; a.loss_vkb = loss_vkb;
+  a.num_draws = num_draws; a.V = V; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, s->B);
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_label_evidence(a, c.stream));
   return SLODE_OK;
 }
 

@@ -590,6 +590,26 @@ struct TrajBoundsLaunch {
 hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
+// Label evidence (label_evidence_kernel in traj_bounds_kernel.hip; slode_label_evidence): V label hypotheses scored on the num_draws posterior
+// draws of every trajectory.  The inputs of TrajBoundsLaunch (lab: the batch's label tensors, n >= 1) and hyp: the hypothesis tables, tensor i
+// dense [V, width i] or NULL (not hypothesised: the trajectory's own); log_prior [V] or NULL.  evidence [B, V, SLODE_EVIDENCE_SLOTS] (16-byte
+// aligned), best [B] or NULL, loss_vkb [V, num_draws, B] or NULL.
+struct LabelEvidenceLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *obs;
+  int64_t sb;
+  const float *loc, *scale, *eps, *sigtab, *log_prior;
+  float *evidence, *loss_vkb;
+  int32_t* best;
+  int num_draws, V, grid, t_major, force_generic;
+  RngK rng{};
+  LabelSrc lab{}, hyp{};
+};
+#define SLODE_LABEL_EVIDENCE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table, observations, staged weights, the V prior rows, the K x V losses must fit
+hipError_t slode_launch_label_evidence(const LabelEvidenceLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_label_evidence_lds_bytes(const slode_shape& s, int num_draws, int V, int force_generic);
+
 // Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over the paired posterior draws of d (is_post = 1; u unread, lab:
 // the batch's own labels, which the encoder launch takes) per trajectory, mean / sd [Q, B, C, T] of the curve under swapped labels and of its
 // difference to the factual curve; each of the four outputs may be NULL.  cf: the counterfactual label tensors (read in the columns of the

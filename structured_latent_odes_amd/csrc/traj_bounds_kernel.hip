@@ -20,6 +20,8 @@
 //       loss_kb with plain per-lane stores
 // Every sum runs in a fixed order that depends on (K, T, L) alone: the result is a function of (parameters, inputs, noise) -- bitwise equal
 // between runs, between one workgroup per trajectory and the persistent loop, between in-kernel and explicit noise.  No atomics.
+// The per-draw terms (B2's log q - log p, B6, B7's label log-probability) and B9 are inline routines, because this translation unit also
+// holds label_evidence_kernel (slode_label_evidence), which executes the same routines against V label hypotheses.
 #include "slode_forward.h"
 
 namespace {
@@ -54,9 +56,11 @@ __device__ __forceinline__ double tb_wave_sum_d(double v) {
 
 // B9: the K stored losses of one trajectory -> its four slots, in fp64; thread i takes draws i, i + 256, ... in that order, then a fixed
 // tree over the lanes and the waves.  Not inlined: the fp64 exp / log constants would otherwise be hoisted out of the draw loop and stay
-// live in registers through every phase of the kernel (30 VGPRs more in every instantiation).
+// live in registers through every phase of the kernel (30 VGPRs more in every instantiation).  row: the four slots' destination (global
+// memory for traj_bounds, the LDS for label_evidence, which replaces slot 3 before its own store); bound64 (or nullptr): slot 1 before it
+// is rounded.  A barrier must separate two calls (the second call's first partials overwrite what thread 0 of the first still reads).
 __device__ __noinline__ void tb_reduce_draws(const float* s_loss, const float* s_nll, double* s_dred, int nd, int B, int b,
-                                             float* __restrict__ bounds, float* __restrict__ loss_kb) {
+                                             float* row, float* __restrict__ loss_kb, double* bound64) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double sl = 0.0, sn = 0.0;
   float mn = 3.4028234664e38f;
@@ -85,10 +89,73 @@ __device__ __noinline__ void tb_reduce_draws(const float* s_loss, const float* s
     o.y = (float)(mnd - log(sw / dk));
     o.z = (float)(sw * sw / sw2);
     o.w = (float)(sn / dk);
-    *reinterpret_cast<f4_t*>(bounds + (long long)b * SLODE_BOUND_SLOTS) = o;   // the row's four slots: one 16-byte store
+    *reinterpret_cast<f4_t*>(row) = o;   // the row's four slots: one 16-byte store
+    if (bound64) *bound64 = mnd - log(sw / dk);
   }
   if (loss_kb)
     for (int q = tid; q < nd; q += TB_NT) loss_kb[(long long)q * B + b] = s_loss[q];
+}
+
+// ---- the per-draw terms traj_bounds_kernel and label_evidence_kernel both execute (the same routines: column v of the evidence is bit for
+// bit the bounds of that label set) ----
+// B2: log q(z | x) - log p(z | labels) of one latent dim: posterior loc / sc / nlsc = -log sc, prior pl / pls and ips = exp(-pls)
+__device__ __forceinline__ float tb_logq_minus_logp(float z, float loc, float sc, float nlsc, float pl, float pls, float ips) {
+  const float dz = (z - pl) * ips, zq = (z - loc) / sc;
+  return (nlsc - TB_HL2PI - 0.5f * zq * zq) - (-pls - TB_HL2PI - 0.5f * dz * dz);
+}
+
+// B6: decoder heads + ALD / Gaussian log-likelihood of the thread's time points tid, tid + 256, ... against the staged observations
+template <int SM>
+__device__ __forceinline__ float tb_loglik_points(const FwdSm& sm, int S, int T, int C, int Q, int gauss, const float (&tau)[3],
+                                                  const float* s_obs, const float* s_inv, const float* s_lg, int tid) {
+  float llt = 0.f;
+  for (int t = tid; t < T; t += TB_NT) {
+    float x[SM];
+    fwd_state_at<SM>(sm, S, t, x);
+    float ll = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float obv = s_obs[c * T + t], inv = s_inv[c * T + t], lg = s_lg[c * T + t];
+      for (int q = 0; q < Q; ++q) {
+        const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
+        if (gauss) ll += -lg - TB_HL2PI - 0.5f * r * r * inv * inv;
+        else ll += ((obv >= mu) ? tau[q] : 1.f - tau[q]) * (-lg - fabsf(r) * inv);
+      }
+    }
+    llt += ll;
+  }
+  return llt;
+}
+
+// B7: the log-probability of the label columns y[0 .. u_dim) of head a under its logits lg (no cross-lane operation)
+__device__ __forceinline__ float tb_label_logprob(const LabelHeadK& lh, const float* __restrict__ par, int a, const float (&lg)[8], const float* y) {
+  const slode_aux ax = lh.aux[a];
+  const int ud = ax.u_dim;
+  float lp = 0.f;
+  if (ax.kind == SLODE_AUX_SOFTMAX) {
+    float mx = -3.0e38f, se = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (q < ud) mx = fmaxf(mx, lg[q]);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (q < ud) se += expf(lg[q] - mx);
+    const float lse = mx + logf(se);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (q < ud) lp = fmaf(y[q], lg[q] - lse, lp);
+  } else if (ax.kind == SLODE_AUX_SIGMOID) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (q < ud) {
+      const float o = lg[q], yy = y[q];
+      const float sp_pos = (o > 0.f ? o : 0.f) + log1pf(expf(-fabsf(o)));
+      lp += yy * (o - sp_pos) + (1.f - yy) * (-sp_pos);
+    }
+  } else {   // EXPEXP: Laplace(exp(head 0), softplus(constant_std_*))
+    const float bsc = softplusf(par[lh.aux_c[a]]), ib = 1.f / bsc;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (q < ud) {
+      const float lc = expf(lg[q]), yy = y[q];
+      lp += -logf(2.f * bsc) - fabsf(yy - lc) * ib;
+    }
+  }
+  return lp;
 }
 
 // SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
@@ -141,66 +208,26 @@ __global__ void __launch_bounds__(TB_NT) traj_bounds_kernel(const TbK k) {
       float klt = 0.f;
       if (tid < L) {
         const float z = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
-        const float dz = (z - pl) * ips, zq = (z - loc) / sc;
-        klt = (nlsc - TB_HL2PI - 0.5f * zq * zq) - (-pls - TB_HL2PI - 0.5f * dz * dz);
+        klt = tb_logq_minus_logp(z, loc, sc, nlsc, pl, pls, ips);
         sm.z[tid] = z;
       }
       __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_red are done)
       fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // B3 - B5
       // ---- B6: heads + log-likelihood of the thread's time points ----
-      float llt = 0.f;
-      for (int t = tid; t < T; t += TB_NT) {
-        float x[SM];
-        fwd_state_at<SM>(sm, S, t, x);
-        float ll = 0.f;
-        for (int c = 0; c < C; ++c) {
-          const float obv = s_obs[c * T + t], inv = s_inv[c * T + t], lg = s_lg[c * T + t];
-          for (int q = 0; q < Q; ++q) {
-            const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
-            if (k.gauss) ll += -lg - TB_HL2PI - 0.5f * r * r * inv * inv;
-            else ll += ((obv >= mu) ? k.tau[q] : 1.f - k.tau[q]) * (-lg - fabsf(r) * inv);
-          }
-        }
-        llt += ll;
-      }
+      const float llt0 = tb_loglik_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, tid);
       // ---- B7: the main loss's label terms on z (proc); half-wave = head, lane = hidden unit ----
       if (LAB) {   // (every lane of a wave takes part in every sum)
         const bool on = hw < n_items;
         const int a = on ? hw : 0;
         const slode_aux ax = k.lh.aux[a];
-        const int ud = ax.u_dim;
         float lg[8];
         fwd_label_logits(k.lh, par, a, sm.z + ax.z_off, j32, lg);
-        float lp = 0.f;
-        if (ax.kind == SLODE_AUX_SOFTMAX) {
-          float mx = -3.0e38f, se = 0.f;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (q < ud) mx = fmaxf(mx, lg[q]);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (q < ud) se += expf(lg[q] - mx);
-          const float lse = mx + logf(se);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (q < ud) lp = fmaf(sm.u[ax.u_off + q], lg[q] - lse, lp);
-        } else if (ax.kind == SLODE_AUX_SIGMOID) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (q < ud) {
-            const float o = lg[q], y = sm.u[ax.u_off + q];
-            const float sp_pos = (o > 0.f ? o : 0.f) + log1pf(expf(-fabsf(o)));
-            lp += y * (o - sp_pos) + (1.f - y) * (-sp_pos);
-          }
-        } else {   // EXPEXP: Laplace(exp(head 0), softplus(constant_std_*))
-          const float bsc = softplusf(par[k.lh.aux_c[a]]), ib = 1.f / bsc;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (q < ud) {
-            const float lc = expf(lg[q]), y = sm.u[ax.u_off + q];
-            lp += -logf(2.f * bsc) - fabsf(y - lc) * ib;
-          }
-        }
+        const float lp = tb_label_logprob(k.lh, par, a, lg, sm.u + ax.u_off);
         if (on && j32 == 0) s_item[a] = -k.lh.aux_mult * lp;
       }
       // ---- B8: fixed-order sums over the workgroup; the draw's loss ----
       klt = wave_sum(klt);
-      llt = wave_sum(llt);
+      const float llt = wave_sum(llt0);
       if (lane == 0) { s_red[wave] = klt; s_red[4 + wave] = llt; }
       __syncthreads();
       if (tid == 0) {
@@ -212,7 +239,7 @@ __global__ void __launch_bounds__(TB_NT) traj_bounds_kernel(const TbK k) {
     }
     // ---- B9: the K stored values -> the four slots and loss_kb ----
     __syncthreads();
-    tb_reduce_draws(s_loss, s_nll, s_dred, nd, f.B, b, k.bounds, k.loss_kb);
+    tb_reduce_draws(s_loss, s_nll, s_dred, nd, f.B, b, k.bounds + (long long)b * SLODE_BOUND_SLOTS, k.loss_kb, nullptr);
   }
 }
 
@@ -226,6 +253,198 @@ TbLds tb_lds(const slode_shape& s, int nd, bool generic) {
   // the K losses and their likelihood parts come last; a K that cannot fit anyway counts as the whole budget (no overflow of the offsets)
   const int kd = nd < SLODE_TRAJ_BOUNDS_LDS_MAX / 4 ? nd : SLODE_TRAJ_BOUNDS_LDS_MAX / 4;
   o.loss = cv.take(kd); o.nll = cv.take(kd);
+  o.total = cv.n;
+  return o;
+}
+
+// ---- label evidence (slode_label_evidence): V label hypotheses scored on the K posterior draws of every trajectory ----------------------
+// loss[v][k][b] = the main loss of row b on draw k with its labels replaced by hypothesis v -- what traj_bounds_kernel gives for that label
+// set on the same noise, bit for bit -- and per (b, v): the mean, the importance-weighted bound, the ESS, the log-posterior over v.
+// The draws z_k ~ q(z | x_b), the solve, the heads, the likelihood and (proc) the label logits do not depend on the hypothesis; only
+// log p(z | u_v) and the label log-probabilities do.  One workgroup per trajectory (persistent loop beyond the grid), as traj_bounds_kernel:
+//   E0  = B0
+//   E1  once per trajectory: the V label rows u_v (the trajectory's own row with the columns of every hypothesised tensor replaced by row v
+//       of that tensor) into the LDS; the observation row; loc / scale of the posterior in the registers of lane l of EVERY wave; the V prior
+//       rows (ploc, pls, exp(-pls))[v][l] from fwd_prior_at on the staged u_v into the LDS
+//   per draw:
+//   E2  z = loc + scale * eps_k (B2's z); E3-E5 fwd_solve; E6 tb_loglik_points -- once
+//   E7  (LAB) the logits of the label heads once (fwd_label_logits, every lane then takes the bits of lane 0 of its half-wave: the lane
+//       traj_bounds_kernel stores from); lane j of the head's half-wave scores hypotheses j, j + 32 with tb_label_logprob against u_v
+//   E8  wave w takes the hypotheses v = w, w + 4, ...: lane l < L forms tb_logq_minus_logp against prior row v, wave_sum; the wave sums of
+//       the likelihood; then thread v forms loss[v][k]
+//   E9  per hypothesis tb_reduce_draws on its K losses (slots 0-2 and the fp64 bound into the LDS, loss_vkb[v] to memory), then thread 0
+//       forms the V log-posteriors and the arg-max in fp64 (le_posterior); thread v stores row (b, v) as ONE 16-byte store
+// Why column v has the bits of traj_bounds_kernel on label set v.  L <= SLODE_MAX_L = 64, so in traj_bounds_kernel every latent dim lives in
+// wave 0: the (log q - log p) partials of waves 1-3 are wave sums of +0 = +0, and its tree gives kl = (w0 + 0) + (0 + 0).  Here wave w
+// computes the same lanes' terms with the same routine from the same values (z read back from the LDS, loc / scale loaded by every wave,
+// the prior row formed by the same fwd_prior_at / expf) and the same wave_sum -- the bits of w0 -- and thread v adds the same three zeros.
+// The likelihood sums are the same code on the same draw.  The label terms come from the same logits (lane 0's) and tb_label_logprob, a
+// routine without cross-lane operations, so which lane runs it does not matter.  loss = kl - ll + items in the same order, and the K
+// losses go through the same tb_reduce_draws.  No atomics; every sum in a fixed order that depends on (K, V, T, L) alone.
+struct LeLds { FwdLds f; int obs, inv, lg, red, dred, nll, uh, prior, kl, item, ev, bd, loss, total; };
+
+struct LeK {
+  FwdK f;
+  PriorK pr;
+  LabelHeadK lh;
+  int gauss, nd, nv, t_major;
+  float tau[3];
+  const float* obs;
+  long long sb;
+  const float *loc, *scale, *eps, *sigtab, *log_prior;
+  float *evidence, *loss_vkb;
+  int32_t* best;
+  LeLds o;
+  RngK rng;
+  LabelSrc lab, hyp;   // hyp.p[i] == nullptr: label tensor i is not hypothesised (widths and offsets: lab's)
+};
+
+// column col of label row u_v of trajectory b
+__device__ __forceinline__ float le_label_at(const LabelSrc& hyp, const LabelSrc& ls, long long b, int v, int col) {
+  int i = 0;
+#pragma unroll
+  for (int q = 1; q < SLODE_MAX_LABELS; ++q) i = (q < ls.n && col >= ls.off[q]) ? q : i;
+  const int w = ls.off[i + 1] - ls.off[i], c = col - ls.off[i];
+  const float* hp = hyp.p[i];
+  return hp ? hp[(long long)v * w + c] : ls.p[i][b * w + c];
+}
+
+// E9, thread 0 alone: log_post[v] = t_v - logsumexp_v'(t_v'), t_v = log_prior[v] - bound[v], in fp64 from the unrounded bounds, in the
+// order v = 0 .. V - 1 (V = 1: t - (t + log(exp(0))) = 0 exactly) into slot 3 of the staged rows; the arg-max, the lowest index on a tie.
+// Not inlined, for the reason of tb_reduce_draws.
+__device__ __noinline__ void le_posterior(const double* s_bd, const float* __restrict__ log_prior, int V, float* s_ev, int32_t* best) {
+  double m = -1.0 / 0.0;
+  for (int v = 0; v < V; ++v) m = fmax(m, (log_prior ? (double)log_prior[v] : 0.0) - s_bd[v]);
+  double se = 0.0;
+  for (int v = 0; v < V; ++v) se += exp(((log_prior ? (double)log_prior[v] : 0.0) - s_bd[v]) - m);
+  const double lse = m + log(se);
+  double bv = -1.0 / 0.0;
+  int bi = 0;
+  for (int v = 0; v < V; ++v) {
+    const double p = ((log_prior ? (double)log_prior[v] : 0.0) - s_bd[v]) - lse;
+    s_ev[4 * v + 3] = (float)p;
+    if (p > bv) { bv = p; bi = v; }
+  }
+  if (best) *best = bi;
+}
+
+template <int SC, bool LAB>
+__global__ void __launch_bounds__(TB_NT) label_evidence_kernel(const LeK k) {
+  constexpr int SM = SC ? SC : SLODE_MAX_S;
+  extern __shared__ __attribute__((aligned(16))) float s_tb[];
+  const FwdK& f = k.f;
+  const float* __restrict__ par = f.params;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hw = tid >> 5, j32 = tid & 31;
+  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, CT = C * T, nd = k.nd, V = k.nv, nu = k.pr.nu;
+  const FwdSm sm = fwd_sm(s_tb, k.o.f);
+  float* s_obs = s_tb + k.o.obs;     // [C][T] the trajectory's observations
+  float* s_inv = s_tb + k.o.inv;     // [C][T] 1 / likelihood scale
+  float* s_lg = s_tb + k.o.lg;       // [C][T] log(scale) (Gauss) or log(2 scale) (ALD)
+  float* s_red = s_tb + k.o.red;     // [4 .. 8) per-wave sums of the log-likelihood
+  float* s_nll = s_tb + k.o.nll;     // [K] the draws' negative log-likelihood (the same for every hypothesis)
+  float* s_uh = s_tb + k.o.uh;       // [V][nu] the label rows u_v
+  float* s_pr = s_tb + k.o.prior;    // [V][3][L] ploc | pls | exp(-pls)
+  float* s_kl = s_tb + k.o.kl;       // [V] sum over l of (log q - log p_v) of the draw
+  float* s_item = s_tb + k.o.item;   // [V][SLODE_MAX_AUX] -46 x label log-prob of the draw against u_v, per head
+  float* s_ev = s_tb + k.o.ev;       // [V][4] the rows of the trajectory before their store
+  float* s_loss = s_tb + k.o.loss;   // [V][K] the per-draw losses
+  double* s_dred = reinterpret_cast<double*>(s_tb + k.o.dred);   // tb_reduce_draws' partials
+  double* s_bd = reinterpret_cast<double*>(s_tb + k.o.bd);       // [V] the importance-weighted bounds before they are rounded
+  const int n_items = LAB ? k.lh.n_aux : 0;
+
+  // ---- E0 ----
+  fwd_stage_weights<SM>(f, sm, S, tid);
+  for (int i = tid; i < CT; i += TB_NT) { s_inv[i] = k.sigtab[CT + i]; s_lg[i] = k.sigtab[2 * CT + i]; }
+
+  for (int b = blockIdx.x; b < f.B; b += gridDim.x) {
+    // ---- E1 ----
+    __syncthreads();   // (E0's writes; the previous trajectory's readers of every table are done)
+    for (int i = tid; i < V * nu; i += TB_NT) { const int v = i / nu; s_uh[i] = le_label_at(k.hyp, k.lab, b, v, i - v * nu); }
+    {
+      const float* ob = k.obs + (long long)b * k.sb;
+      for (int i = tid; i < CT; i += TB_NT) {
+        int c, t;
+        if (k.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
+        s_obs[c * T + t] = ob[i];
+      }
+    }
+    __syncthreads();
+    float loc = 0.f, sc = 1.f, nlsc = 0.f;   // lane l < L of every wave keeps its latent dim's posterior
+    if (lane < L) { loc = k.loc[(long long)b * L + lane]; sc = k.scale[(long long)b * L + lane]; nlsc = -logf(sc); }
+    for (int i = tid; i < V * L; i += TB_NT) {   // (read after the draw's first barrier)
+      const int v = i / L, l = i - v * L;
+      float pl, pls;
+      fwd_prior_at(k.pr, par, s_uh + v * nu, l, pl, pls);
+      s_pr[(v * 3) * L + l] = pl; s_pr[(v * 3 + 1) * L + l] = pls; s_pr[(v * 3 + 2) * L + l] = expf(-pls);
+    }
+    for (int kk = 0; kk < nd; ++kk) {
+      // ---- E2 ----
+      if (tid < L) sm.z[tid] = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
+      __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_kl / s_red are done)
+      fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // E3 - E5
+      // ---- E6 ----
+      const float llt0 = tb_loglik_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, tid);
+      // ---- E7 ----
+      if (LAB) {   // (every lane of a wave takes part in every sum)
+        const bool on = hw < n_items;
+        const int a = on ? hw : 0;
+        const slode_aux ax = k.lh.aux[a];
+        float lg[8];
+        fwd_label_logits(k.lh, par, a, sm.z + ax.z_off, j32, lg);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) lg[q] = __shfl(lg[q], lane & 32, 64);
+        for (int v = j32; v < V; v += 32) {
+          const float lp = tb_label_logprob(k.lh, par, a, lg, s_uh + v * nu + ax.u_off);
+          if (on) s_item[v * SLODE_MAX_AUX + a] = -k.lh.aux_mult * lp;
+        }
+      }
+      // ---- E8 ----
+      const float z = lane < L ? sm.z[lane] : 0.f;
+      for (int v = wave; v < V; v += TB_NT / 64) {   // (wave-uniform)
+        float klt = 0.f;
+        if (lane < L) klt = tb_logq_minus_logp(z, loc, sc, nlsc, s_pr[(v * 3) * L + lane], s_pr[(v * 3 + 1) * L + lane], s_pr[(v * 3 + 2) * L + lane]);
+        klt = wave_sum(klt);
+        if (lane == 0) s_kl[v] = klt;
+      }
+      const float llt = wave_sum(llt0);
+      if (lane == 0) s_red[4 + wave] = llt;
+      __syncthreads();
+      if (tid < V) {
+        const float kl = (s_kl[tid] + 0.f) + (0.f + 0.f), ll = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);   // (the tree of B8: header)
+        float loss = kl - ll;
+        for (int a = 0; a < n_items; ++a) loss += s_item[tid * SLODE_MAX_AUX + a];
+        s_loss[tid * nd + kk] = loss;
+        if (tid == 0) s_nll[kk] = -ll;
+      }
+    }
+    // ---- E9 ----
+    for (int v = 0; v < V; ++v) {
+      __syncthreads();   // (the draws' writes; the previous hypothesis' readers of s_dred are done)
+      tb_reduce_draws(s_loss + v * nd, s_nll, s_dred, nd, f.B, b, s_ev + 4 * v, k.loss_vkb ? k.loss_vkb + (long long)v * nd * f.B : nullptr, s_bd + v);
+    }
+    __syncthreads();
+    if (tid == 0) le_posterior(s_bd, k.log_prior, V, s_ev, k.best ? k.best + b : nullptr);
+    __syncthreads();
+    if (tid < V) {
+      typedef float f4_t __attribute__((ext_vector_type(4)));
+      reinterpret_cast<f4_t*>(k.evidence)[(long long)b * V + tid] = reinterpret_cast<const f4_t*>(s_ev)[tid];   // one 16-byte store
+    }
+  }
+}
+
+LeLds le_lds(const slode_shape& s, int nd, int V, bool generic) {
+  const int CT = s.C * s.T, cap = SLODE_LABEL_EVIDENCE_LDS_MAX / 4;
+  LdsCarve cv;
+  LeLds o{};
+  o.f = fwd_lds(cv, s, generic);
+  o.obs = cv.take(CT); o.inv = cv.take(CT); o.lg = cv.take(CT); o.red = cv.take(8);
+  o.dred = cv.take(24);   // 12 doubles (the offset is a multiple of 4 floats: 16-byte aligned)
+  const int vv = V < 1 ? 1 : (V > SLODE_EVIDENCE_MAX_V ? SLODE_EVIDENCE_MAX_V : V);
+  o.uh = cv.take(vv * (s.n_u > 0 ? s.n_u : 1)); o.prior = cv.take(vv * 3 * s.L); o.kl = cv.take(vv); o.item = cv.take(vv * SLODE_MAX_AUX);
+  o.ev = cv.take(vv * 4); o.bd = cv.take(vv * 2);
+  // the K likelihood parts and the V x K losses come last; sizes that cannot fit anyway count as the whole budget (no overflow of the offsets)
+  const long long kv = (long long)vv * (nd < 0 ? 0 : nd);
+  o.nll = cv.take(nd < cap ? (nd < 0 ? 0 : nd) : cap); o.loss = cv.take(kv < cap ? (int)kv : cap);
   o.total = cv.n;
   return o;
 }
@@ -253,6 +472,34 @@ hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t strea
     constexpr int SC = decltype(sc)::value;
     if (lab) fwd_launch("traj_bounds", traj_bounds_kernel<SC, true>, a.grid, lds, stream, k);
     else fwd_launch("traj_bounds", traj_bounds_kernel<SC, false>, a.grid, lds, stream, k);
+  });
+  return hipGetLastError();
+}
+
+size_t slode_label_evidence_lds_bytes(const slode_shape& s, int num_draws, int V, int force_generic) {
+  return (size_t)le_lds(s, num_draws, V, fwd_generic(s, force_generic)).total * sizeof(float);
+}
+
+hipError_t slode_launch_label_evidence(const LabelEvidenceLaunch& a, hipStream_t stream) {
+  const slode_shape& s = a.s;
+  const slode_layout& lay = a.lay;
+  LeK k{};
+  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay); fwd_fill(k.lh, s, lay);
+  k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.nd = a.num_draws; k.nv = a.V; k.t_major = a.t_major;
+  k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff;
+  k.obs = a.obs; k.sb = a.sb;
+  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.sigtab = a.sigtab; k.log_prior = a.log_prior;
+  k.evidence = a.evidence; k.loss_vkb = a.loss_vkb; k.best = a.best;
+  k.rng = a.rng; k.lab = a.lab; k.hyp = a.hyp; k.o = le_lds(s, a.num_draws, a.V, fwd_generic(s, a.force_generic));
+  const size_t lds = slode_label_evidence_lds_bytes(s, a.num_draws, a.V, a.force_generic);
+  if (lds > SLODE_LABEL_EVIDENCE_LDS_MAX || a.num_draws < 1 || a.V < 1 || a.V > SLODE_EVIDENCE_MAX_V || a.grid < 1 || s.n_aux > SLODE_MAX_AUX ||
+      a.lab.n < 1)
+    return hipErrorInvalidValue;
+  const bool lab = s.aux_in_main && s.n_aux > 0;
+  fwd_dispatch(s, a.force_generic, [&](auto sc) {
+    constexpr int SC = decltype(sc)::value;
+    if (lab) fwd_launch("label_evidence", label_evidence_kernel<SC, true>, a.grid, lds, stream, k);
+    else fwd_launch("label_evidence", label_evidence_kernel<SC, false>, a.grid, lds, stream, k);
   });
   return hipGetLastError();
 }

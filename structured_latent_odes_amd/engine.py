@@ -694,6 +694,38 @@ class Engine:
         self._batch_call(self.lib.slode_traj_bounds, params, batch, B, particles, K, self._p(bounds), self._p(loss_kb))
         return bounds, loss_kb
 
+    def label_evidence(self, params, batch: L.Batch, B: int, num_draws: int, hyp_labels, V: int, log_prior=None, evidence=None, best=None,
+                       loss_vkb=None, particles: int = 1):
+        """slode_label_evidence: ``V`` label hypotheses scored on the ``num_draws`` posterior draws of every trajectory in one call --
+        ``(evidence, best, loss_vkb)``: ``evidence`` float32 [B, V, L.EVIDENCE_SLOTS] = [-ELBO under hypothesis v, importance-weighted bound
+        on -log p(x_b | u_v), effective sample size of its weights, log posterior over v], ``best`` int32 [B], the arg-max of the log
+        posterior (lowest index on a tie), ``loss_vkb`` float32 [V, num_draws, B], the per-draw losses; enqueued on the current stream.
+        ``hyp_labels``: one entry per label tensor of ``make_batch``: a float32 [V, width] table shared by all trajectories, or None (the
+        label is not hypothesised: every hypothesis keeps the trajectory's own).  ``log_prior``: float32 [V] on the device, or None
+        (uniform).  Slots 0-2 of column v and ``loss_vkb[v]`` are bitwise what ``traj_bounds`` returns on the batch with those labels and
+        the same noise (the batch's eps: as ``traj_bounds``).  Raises SlodeError naming the reason for what the kernel does not take
+        (everything ``traj_bounds`` refuses; V outside [1, L.EVIDENCE_MAX_V]; no hypothesised label; LDS budget): nothing is launched and no
+        draw is consumed then; there is no composed fallback."""
+        K, V = int(num_draws), int(V)
+        if hyp_labels is None or len(hyp_labels) != int(batch.n_labels):
+            raise ValueError("hyp_labels needs one entry per label tensor of the batch (%d), got %s"
+                             % (int(batch.n_labels), "None" if hyp_labels is None else len(hyp_labels)))
+        ptrs = (C.c_void_p * L.MAX_LABELS)()
+        for i, t in enumerate(hyp_labels):
+            if t is None:
+                continue
+            if self._f32(t, "hyp label %d" % i).numel() != V * int(batch.label_width[i]):
+                raise ValueError("hyp label %d must be [%d, %d], got %s" % (i, V, int(batch.label_width[i]), tuple(t.shape)))
+            ptrs[i] = t.data_ptr()
+        if log_prior is not None and self._f32(log_prior, "log_prior").numel() != V:
+            raise ValueError("log_prior must hold V = %d values, got %s" % (V, tuple(log_prior.shape)))
+        evidence = self._out(evidence, "evidence", (B, max(V, 0), L.EVIDENCE_SLOTS))
+        best = self._out_i32(best, "best", (B,))
+        loss_vkb = self._out(loss_vkb, "loss_vkb", (max(V, 0), max(K, 0), B))
+        self._batch_call(self.lib.slode_label_evidence, params, batch, B, particles, K, ptrs, V, self._p(log_prior), self._p(evidence),
+                         self._p(best), self._p(loss_vkb))
+        return evidence, best, loss_vkb
+
     def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
                           eff_mean=None, eff_sd=None, particles: int = 1):
         """slode_intervene_moments: counterfactual curves from ``num_samples`` paired posterior draws per trajectory.  Both arms of a draw

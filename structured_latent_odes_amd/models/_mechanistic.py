@@ -879,3 +879,118 @@ class MechanisticBase(nn.Module):
         path = os.path.join(results_dir, "bounds_post.npy")
         np.save(path, table)
         return path
+
+    # ---- label evidence: which input does the generative model believe produced these curves? -------------------------------------------
+    EVIDENCE_NAMES = ("elbo", "iw_bound", "ess", "log_post")    # the slots of one slode_label_evidence row, in order
+
+    @classmethod
+    def label_grid(cls, **values):
+        """The Cartesian product of per-label value lists as hypothesis tables: ``label_grid(iext=[0, 1], rtpr=[0, 1])`` gives
+        ``{"iext": [4, 1], "rtpr": [4, 1]}`` (float32), the first name varying slowest.  A value may be a row of several columns
+        (``aR=torch.eye(3)``: three hypotheses for a label of width 3)."""
+        import itertools
+        if not values:
+            raise ValueError("label_grid needs at least one label")
+        for name in values:
+            if name not in cls.LABELS:
+                raise ValueError("label_grid: %r is not a label of the %s family (labels: %s)" % (name, cls.FAMILY, ", ".join(cls.LABELS)))
+        rows = {n: torch.as_tensor(v, dtype=torch.float32) for n, v in values.items()}
+        rows = {n: v.reshape(v.shape[0], -1) if v.dim() > 0 else v.reshape(1, 1) for n, v in rows.items()}
+        index = list(itertools.product(*(range(v.shape[0]) for v in rows.values())))
+        return {n: v[[ix[j] for ix in index]].contiguous() for j, (n, v) in enumerate(rows.items())}
+
+    @classmethod
+    def _hypothesis_tables(cls, hypotheses):
+        """``hypotheses`` = {label name: [V, width]} for a non-empty subset of ``LABELS`` as ``(V, {name: float32 [V, width]})``."""
+        if not hypotheses:
+            raise ValueError("hypotheses must name at least one label of the %s family (labels: %s)" % (cls.FAMILY, ", ".join(cls.LABELS)))
+        tabs, V = {}, None
+        for name, val in hypotheses.items():
+            if name not in cls.LABELS:
+                raise ValueError("hypotheses: %r is not a label of the %s family (labels: %s)" % (name, cls.FAMILY, ", ".join(cls.LABELS)))
+            t = torch.as_tensor(val).to(torch.float32)
+            t = t.reshape(t.shape[0], -1) if t.dim() > 0 else t.reshape(1, 1)
+            if V is not None and t.shape[0] != V:
+                raise ValueError("hypotheses[%r] has %d rows, the others %d: every table needs the same V" % (name, t.shape[0], V))
+            tabs[name], V = t.contiguous(), t.shape[0]
+        return V, tabs
+
+    @classmethod
+    def hypothesis_match(cls, hypotheses, **labels):
+        """``[B]`` int64: the index of the first hypothesis whose hypothesised columns equal the trajectory's own labels, -1 if none does."""
+        V, tabs = cls._hypothesis_tables(hypotheses)
+        B = next(iter(labels.values())).shape[0]
+        hit = None
+        for name, t in tabs.items():
+            own = labels[name].reshape(B, -1).to(torch.float32)
+            if own.shape[1] != t.shape[1]:
+                raise ValueError("hypotheses[%r] must be [V, %d], got %s" % (name, own.shape[1], tuple(t.shape)))
+            eq = (own[:, None, :] == t.to(own.device)[None, :, :]).all(dim=-1)             # [B, V]
+            hit = eq if hit is None else hit & eq
+        first = torch.argmax(hit.to(torch.int64), dim=1)
+        return torch.where(hit.any(dim=1), first, torch.full_like(first, -1))
+
+    def default_hypotheses(self, **labels):
+        """The hypotheses ``--label-evidence`` scores: cvs {0, 1}^2 over iext, rtpr; challenge {0, 1}^2 over symptoms, shedding; proc the
+        identity rows of aR x the identity rows of aS (widths from ``labels``), C12 / C6 left as each subject's own."""
+        if self.FAMILY == "proc":
+            B = labels["aR"].shape[0]
+            return self.label_grid(aR=torch.eye(labels["aR"].reshape(B, -1).shape[1]), aS=torch.eye(labels["aS"].reshape(B, -1).shape[1]))
+        return self.label_grid(**{l: [0.0, 1.0] for l in self.LABELS[:2]})
+
+    def label_evidence(self, observations, num_draws: int, hypotheses, log_prior=None, eps=None, return_draws: bool = False, **labels):
+        """The generative model's own answer to "which input produced these curves?", p(u | x) ~ p(u) p(x | u), for V label hypotheses
+        shared by all trajectories: ``hypotheses`` = {label name: [V, width]} for a non-empty subset of ``LABELS`` (``label_grid`` builds
+        the Cartesian product); a label that is not named keeps each trajectory's own value.  Per hypothesis, p(x | u_v) is estimated by the
+        importance-weighted bound over ``num_draws`` = K posterior draws z_k = loc(x) + scale(x) eps_k -- the bound ``trajectory_bounds``
+        gives for those labels, at the price of one encoder pass and K solves for all V.  Returns ``{"elbo", "iw_bound", "ess",
+        "log_post": [B, V]; "best": [B]`` (arg-max of log_post) ``; "match": [B]`` (the hypothesis that equals the trajectory's own labels,
+        -1 if none) ``}`` plus ``"loss": [V, K, B]`` with ``return_draws``.  The ESS is per hypothesis: q(z | x) is a poor proposal for a
+        wrong u, and an ESS near 1 says the bound rests on one draw.  ``log_prior``: ``[V]`` (None: uniform).  ``eps`` ``[K, B, L]`` makes
+        it reproducible; None takes drawing calls n .. n + K - 1 of the engine's generator, as ``trajectory_bounds``.  ONE engine call
+        (``slode_label_evidence``); what the engine refuses raises its SlodeError."""
+        b = self._bind()
+        B, K = observations.shape[0], self._count(num_draws, "num_draws")
+        V, tabs = self._hypothesis_tables(hypotheses)
+        dev = observations.device
+        hyp = [tabs[l].to(dev) if l in tabs else None for l in self.LABELS]
+        lp = None if log_prior is None else torch.as_tensor(log_prior).to(dev, torch.float32).reshape(-1).contiguous()
+        ev, best, loss = b.engine.label_evidence(b.flat, self._draws_batch(observations, labels, eps, K), B, K, hyp, V, log_prior=lp)
+        res = {n: ev[:, :, i] for i, n in enumerate(self.EVIDENCE_NAMES)}
+        res["best"] = best
+        res["match"] = self.hypothesis_match(tabs, **{l: labels[l] for l in tabs})
+        if return_draws:
+            res["loss"] = loss
+        return res
+
+    def save_label_evidence(self, results_dir: str, batches, num_draws: int, hypotheses):
+        """Runs ``label_evidence`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
+        ``evidence_post.npy`` (float32 ``[n, V, 4]``, the columns of ``EVIDENCE_NAMES``, trajectories in loader order), ``evidence_best.npy``
+        and ``evidence_match.npy`` (int32 ``[n]``) and ``evidence_hypotheses_<label>.npy`` (``[V, width]``) per hypothesised label.  One
+        read-back, at the end.  Returns the paths."""
+        V, tabs = self._hypothesis_tables(hypotheses)
+        rows, best, match = [], [], []
+        for d in batches:
+            r = self.label_evidence(num_draws=num_draws, hypotheses=tabs, **d)
+            rows.append(torch.stack([r[n] for n in self.EVIDENCE_NAMES], dim=2))
+            best.append(r["best"].to(torch.int32))
+            match.append(r["match"].to(torch.int32))
+        cat = lambda parts, shp, dt: torch.cat(parts, 0).cpu() if parts else torch.zeros(shp, dtype=dt)   # noqa: E731
+        named = [("evidence_post.npy", cat(rows, (0, V, len(self.EVIDENCE_NAMES)), torch.float32)),
+                 ("evidence_best.npy", cat(best, (0,), torch.int32)), ("evidence_match.npy", cat(match, (0,), torch.int32))]
+        named += [("evidence_hypotheses_%s.npy" % l, tabs[l]) for l in self.LABELS if l in tabs]
+        return self._save_arrays(results_dir, named)
+
+    @staticmethod
+    def label_evidence_line(post, best, match) -> str:
+        """One line from the files of ``save_label_evidence``: the share of subjects with best == match, the mean posterior mass exp(log_post)
+        on the matching hypothesis and the median ESS there, over the subjects whose own labels are among the hypotheses."""
+        import numpy as np
+        post, best, match = np.asarray(post), np.asarray(best), np.asarray(match)
+        on = match >= 0
+        if not on.any():
+            return "label_evidence: V=%d  no subject's labels are among the hypotheses (n=%d)" % (post.shape[1], len(match))
+        at = post[on, match[on]]
+        return "label_evidence: V=%d  matched=%d/%d  best==match=%.4f  mean_post_at_match=%.4f  median_ess_at_match=%.2f" % (
+            post.shape[1], int(on.sum()), len(match), float((best[on] == match[on]).mean()), float(np.exp(at[:, 3].astype(np.float64)).mean()),
+            float(np.median(at[:, 2])))

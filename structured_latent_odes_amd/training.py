@@ -111,7 +111,8 @@ def make_batches(config, family: str, n_batches: int, seed: int):
 def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: int = 7,
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
-          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False):
+          results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
+          label_evidence: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -129,7 +130,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     printed as ``l1_error_post`` / ``l1_error_prior``: the mean of ``l1`` over non-empty cohorts and channels; off by default.
     calibration: after training, the best model's calibration pass over the validation loader, posterior and prior, config.num_samples
     draws, the whole loader as one cohort (``save_calibration``: coverage of every curve against its nominal level, band coverage, crossing
-    share, pinball loss), one printed line per side (``calibration_post: ...``); off by default."""
+    share, pinball loss), one printed line per side (``calibration_post: ...``); off by default.
+    label_evidence = K > 0: after training, the best model's own label posterior p(u | x) ~ p(u) p(x | u) over the validation loader from K
+    posterior draws (``save_label_evidence`` on ``default_hypotheses``: ``evidence_post.npy`` [n, V, 4], ``evidence_best.npy``,
+    ``evidence_match.npy``, ``evidence_hypotheses_<label>.npy``) and one printed line (``label_evidence: ...``: the share of subjects whose
+    most probable hypothesis is their own labels, the mean posterior mass there, the median ESS there) beside the classifier accuracies;
+    0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -224,6 +230,13 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     if test_bounds:
         path = best_model.save_trajectory_bounds(out_dir, (batch_to_device(b, device, family) for b in val_b), int(test_bounds))
         logging.debug("per-trajectory bounds: %s", path)
+    if label_evidence:
+        first = batch_to_device(next(iter(val_b)), device, family)
+        hyp = best_model.default_hypotheses(**{l: first[l] for l in best_model.LABELS})
+        written = best_model.save_label_evidence(out_dir, (batch_to_device(b, device, family) for b in val_b), int(label_evidence), hyp)
+        line = best_model.label_evidence_line(*(np.load(f) for f in written[:3]))
+        print(line)
+        logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -289,6 +302,9 @@ def build_parser():
     ap.add_argument("--test-bounds", type=int, default=0, metavar="K",
                     help="after training: per-trajectory -ELBO, importance-weighted bound, ESS and NLL of the best model from K posterior draws over "
                          "the validation loader (save_trajectory_bounds: bounds_post.npy)")
+    ap.add_argument("--label-evidence", type=int, default=0, metavar="K",
+                    help="after training: the best model's own label posterior p(u | x) over the family's default hypotheses from K posterior draws "
+                         "over the validation loader (save_label_evidence: evidence_*.npy) and its agreement with the subjects' labels, one line")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -312,6 +328,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["sample_moments"] = True
     if a.test_bounds:
         kw["test_bounds"] = a.test_bounds
+    if a.label_evidence:
+        kw["label_evidence"] = a.label_evidence
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
