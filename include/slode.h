@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 210 /* 0.2.1: slode_label_evidence (0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 220 /* 0.2.2: slode_posterior_refine (0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -425,6 +425,38 @@ int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layou
                          int32_t* best /* [B] or NULL */, float* loss_vkb /* [V, num_draws, B] or NULL */, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- posterior refinement: per-trajectory ELBO ascent as ONE call (no reference counterpart: the reference's posterior is the encoder's one
+ * amortised pass; closing the amortisation gap for one subject, or fitting a subject whose record is only partly trusted or observed -- a prefix of
+ * the window, a dropped channel -- needs an optimiser on that subject's own q(z | x)) -----------------------------------------------------------
+ * Per trajectory b, with phi = (loc[L], rho[L]), scale = exp(rho), and num_draws noise rows eps[k][b] that are FIXED for the whole call:
+ *   F(phi) = 1/K sum_k loss_k,  loss_k = -(sum_{c,t,q} w[b][c][t] ll[c][t][q] + log p(z_k | labels) - log q(z_k)),  z_k = loc + exp(rho) eps[k][b]
+ * -- the per-draw loss of slode_traj_bounds with a weight w >= 0 on every likelihood term of (c, t).  mask: the weights, a tensor with the
+ * observations' strides (batch->obs_strides), or NULL: every weight 1, bit for bit what an all-ones mask gives.  The encoder still reads the whole
+ * observation block: the mask enters the objective alone.  phi_0 = the encoder's (loc, log scale); for j = 0 .. num_steps - 1: F_j and dF/dphi from
+ * the K draws (forward solve, then the reverse of it: likelihood gradient on the states, reverse affine scan, reverse of the step coefficients and
+ * of the a / d evaluator, the hidden layer, the init net, the KL terms), one Adam step with lr, beta = (0.9, 0.999), eps 1e-8 and bias
+ * correction; one more forward pass gives F_J.  Written: the BEST iterate (arg-min over j = 0 .. num_steps of F_j, the lowest j on a tie)
+ *   loc_out [B, L], scale_out [B, L]; elbo_out [B, 2] = (F_0, the best F): elbo_out[b][1] <= elbo_out[b][0] by construction; num_steps = 0
+ *   returns the encoder's loc / scale bit for bit and F_0 twice
+ *   grad0_out (or NULL) [B, 2 L] = dF_0 / d(loc, rho); trace_out (or NULL) [num_steps + 1, B] = every F_j; best_step (or NULL) [B] = the arg-min
+ * Noise: as slode_traj_bounds (batch->eps == NULL: drawing calls n .. n + K - 1, the counter left at n + K -- NOT n + K J; else a dense [K, B, L]
+ * tensor).  The whole iteration of a trajectory runs in one workgroup with weights, observations and every table on chip; every sum runs in a
+ * fixed order: the result is a function of (parameters, inputs, mask, noise) alone -- bitwise equal from run to run, for every grid, for
+ * in-kernel and explicit noise.  No atomics.  Enqueue only: no allocation, no synchronisation, no read-back; capturable as a linear graph.  Three
+ * launches ("weff", "enc_fwd2", "posterior_refine" in slode_profile_read).  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_traj_bounds refuses -- a
+ * NULL handle (before anything else); num_draws < 1 (and B x num_draws beyond 2^30 - 1 noise rows); adaptive solver; particles > 1; the measured
+ * arms; batch->obs NULL; observation strides the folded encoder path does not take or SLODE_NO_FOLD -- then: num_steps < 0; lr not finite or
+ * <= 0; loc_out / scale_out / elbo_out NULL; a shape whose main loss scores the labels (aux_in_main: the proc family -- the backward pass of the
+ * label heads is out of scope); LDS tables (step table and its kept copy 3 (T - 1) S, lambda T S, the stage-gradient table 2 S (T - 1) x stages,
+ * observations, weights and likelihood scales 4 C T, staged weights, the K per-draw losses) beyond the budget of 160 KiB.  There is no composed
+ * fallback: no other call differentiates the per-trajectory loss with respect to the posterior. */
+int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                           const float* stage_t, const slode_batch* batch, int num_draws, int num_steps, float lr,
+                           const float* mask /* as batch->obs, or NULL */, float* loc_out /* [B, L] */, float* scale_out /* [B, L] */,
+                           float* elbo_out /* [B, 2] */, float* grad0_out /* [B, 2 L] or NULL */, float* trace_out /* [num_steps + 1, B] or NULL */,
+                           int32_t* best_step /* [B] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- counterfactual curves as ONE call (no reference counterpart: the reference's recon takes the whole latent from the posterior or the whole
  * latent from the conditional prior; the structured latent exists to ask "what would THIS subject's curves have looked like under THAT input?") ----
  * For trajectory b and draw k, with ONE noise row eps[k][b][0..L) shared by both arms:
@@ -666,11 +698,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -71,7 +71,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_initialize_state", "slode_prior_nets", "slode_label_heads", "slode_dopri5_step_counts", "slode_decode_heads_bwd",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
-           "slode_traj_bounds", "slode_label_evidence", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
+           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
            "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
@@ -140,6 +140,8 @@ def load():
     lib.slode_recon_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, VP, C.c_size_t, VP]
     lib.slode_traj_bounds.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, VP, VP, VP, C.c_size_t, VP]
     lib.slode_label_evidence.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, P(VP), C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
+    lib.slode_posterior_refine.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, C.c_float, VP, VP, VP, VP, VP, VP, VP, VP,
+                                           C.c_size_t, VP]
     lib.slode_intervene_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), P(VP), C.c_uint, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_num_stage_times_n.argtypes = [P(Shape), C.c_int]
     lib.slode_stage_times_n.argtypes = [VP, P(Shape), C.c_int, VP, VP, VP]

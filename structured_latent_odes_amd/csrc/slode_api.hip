@@ -1114,6 +1114,43 @@ int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layou
   return SLODE_OK;
 }
 
+// num_steps Adam steps of every trajectory on its own (loc, log scale) against its num_draws-draw -ELBO (include/slode.h): slode_traj_bounds'
+// refusals through the same ladder, then the call's own -- nothing launched, no draw consumed -- then slode_traj_bounds' launches with the
+// refinement kernel in place of its own.  The noise rows are counted once: num_draws drawing calls, whatever num_steps.  No composed fallback.
+int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                           const float* stage_t, const slode_batch* batch, int num_draws, int num_steps, float lr, const float* mask,
+                           float* loc_out, float* scale_out, float* elbo_out, float* grad0_out, float* trace_out, int32_t* best_step,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  const EvalCall d{"slode_posterior_refine", "batch / loc_out / scale_out / elbo_out / times / stage_t / workspace",
+                   !batch || !loc_out || !scale_out || !elbo_out || !times || !stage_t || !workspace,
+                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
+                   " (and no SLODE_NO_FOLD)", "step table and its kept copy, lambda, the stage-gradient table, observations, weights, staged weights, the per-draw losses",
+                   "a shorter window or fewer draws per call fit", true};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (num_steps < 0) return fail(h, SLODE_EINVAL, "slode_posterior_refine: num_steps = %d < 0", num_steps);
+  if (!(lr > 0.f && lr < INFINITY)) return fail(h, SLODE_EINVAL, "slode_posterior_refine: lr = %g is not a finite positive step size", (double)lr);
+  if (s->aux_in_main && s->n_aux > 0)
+    return fail(h, SLODE_EINVAL, "slode_posterior_refine: the main loss of this shape scores the labels (aux_in_main: the proc family); the backward "
+                                 "pass of the label heads is out of scope");
+  if ((rc = eval_lds(h, s, d, slode_refine_lds_bytes(*s, num_draws, h->ode_generic), SLODE_REFINE_LDS_MAX)) != SLODE_OK) return rc;
+  RefineLaunch a{};
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.mask = mask; a.sb = batch->obs_strides[0];
+  a.t_major = p.t_major ? 1 : 0;
+  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab;
+  a.loc_out = loc_out; a.scale_out = scale_out; a.elbo_out = elbo_out; a.grad0_out = grad0_out; a.trace_out = trace_out; a.best_step = best_step;
+  a.lr = lr; a.num_draws = num_draws; a.num_steps = num_steps; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, s->B);
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_refine(a, c.stream));
+  return SLODE_OK;
+}
+
 // Paired-draw moments of the counterfactual curves and of their difference to the factual ones (include/slode.h): refusals first -- nothing
 // launched, no draw consumed -- then the fold + encoder launches of a forward-only step, then the one kernel that walks the draws of its
 // trajectories through both arms.

@@ -610,6 +610,26 @@ struct LabelEvidenceLaunch {
 hipError_t slode_launch_label_evidence(const LabelEvidenceLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_label_evidence_lds_bytes(const slode_shape& s, int num_draws, int V, int force_generic);
 
+// Posterior refinement (refine_kernel.hip; slode_posterior_refine): num_steps Adam steps of every trajectory on its own (loc, log scale) against
+// its num_draws-draw -ELBO.  The inputs of TrajBoundsLaunch and mask: the weights of the likelihood terms, laid out as obs (sb, t_major), or
+// NULL (all 1).  loc_out / scale_out [B, L], elbo_out [B, 2]; grad0_out [B, 2 L], trace_out [num_steps + 1, B], best_step [B] or NULL.
+struct RefineLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *obs, *mask;
+  int64_t sb;
+  const float *loc, *scale, *eps, *u, *sigtab;
+  float *loc_out, *scale_out, *elbo_out, *grad0_out, *trace_out;
+  int32_t* best_step;
+  float lr;
+  int num_draws, num_steps, grid, t_major, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+#define SLODE_REFINE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table and its kept copy, observations, weights, lambda, the stage-gradient table, staged weights, K losses must fit
+hipError_t slode_launch_refine(const RefineLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_refine_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
+
 // Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over the paired posterior draws of d (is_post = 1; u unread, lab:
 // the batch's own labels, which the encoder launch takes) per trajectory, mean / sd [Q, B, C, T] of the curve under swapped labels and of its
 // difference to the factual curve; each of the four outputs may be NULL.  cf: the counterfactual label tensors (read in the columns of the

@@ -726,6 +726,34 @@ class Engine:
                          self._p(best), self._p(loss_vkb))
         return evidence, best, loss_vkb
 
+    def posterior_refine(self, params, batch: L.Batch, B: int, num_draws: int, num_steps: int, lr: float = 0.05, mask=None, loc=None, scale=None,
+                         elbo=None, grad0=None, trace=None, best_step=None, particles: int = 1):
+        """slode_posterior_refine: every trajectory takes ``num_steps`` Adam steps (``lr``, beta = (0.9, 0.999), eps 1e-8, bias correction)
+        on its own (loc, log scale), starting from the encoder's, against its own -ELBO over ``num_draws`` noise rows that stay fixed for
+        the whole call, all inside one kernel -- ``(loc, scale, elbo, grad0, trace, best_step)``: the best iterate float32 [B, L] twice,
+        ``elbo`` [B, 2] = (the -ELBO at the encoder's posterior, the best one: never larger), ``grad0`` [B, 2 L] = the gradient at the
+        encoder's posterior with respect to (loc, log scale), ``trace`` [num_steps + 1, B] = the -ELBO of every iterate, ``best_step`` int32
+        [B] (``grad0`` / ``trace`` / ``best_step`` passed as False are not computed: None in their place).  ``mask``: float32 weights >= 0
+        of the likelihood terms, a tensor with the shape AND strides of the observations, or None (all 1; bitwise what an all-ones mask
+        gives); the encoder still reads every observation.  The batch's eps is [num_draws, B, L] (``make_batch(..., particles=num_draws)``)
+        or None (drawing calls n .. n + num_draws - 1, as ``traj_bounds``: the counter advances by num_draws, not by num_draws x num_steps).
+        Enqueued on the current stream.  Raises SlodeError naming the reason for what the kernel does not take (everything ``traj_bounds``
+        refuses; num_steps < 0; lr not finite and positive; a family whose main loss scores the labels: proc; LDS budget): nothing is
+        launched and no draw is consumed then; there is no composed fallback."""
+        K, J, Ld = int(num_draws), int(num_steps), self.spec.latent_dim
+        if mask is not None:
+            self._f32(mask, "mask", contiguous=False)
+            if tuple(mask.shape) != (B, self.spec.n_channels, self.T) or tuple(mask.stride()) != tuple(batch.obs_strides[i] for i in range(3)):
+                raise ValueError("mask must have the shape and the strides of the observations")
+        loc, scale = self._out(loc, "loc", (B, Ld)), self._out(scale, "scale", (B, Ld))
+        elbo = self._out(elbo, "elbo", (B, 2))
+        grad0 = None if grad0 is False else self._out(grad0, "grad0", (B, 2 * Ld))
+        trace = None if trace is False else self._out(trace, "trace", (max(J, 0) + 1, B))
+        best_step = None if best_step is False else self._out_i32(best_step, "best_step", (B,))
+        self._batch_call(self.lib.slode_posterior_refine, params, batch, B, particles, K, J, float(lr), self._p(mask), self._p(loc),
+                         self._p(scale), self._p(elbo), self._p(grad0), self._p(trace), self._p(best_step))
+        return loc, scale, elbo, grad0, trace, best_step
+
     def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
                           eff_mean=None, eff_sd=None, particles: int = 1):
         """slode_intervene_moments: counterfactual curves from ``num_samples`` paired posterior draws per trajectory.  Both arms of a draw

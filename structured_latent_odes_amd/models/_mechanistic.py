@@ -373,16 +373,18 @@ class MechanisticBase(nn.Module):
         out.copy_(torch.tensor(row, dtype=torch.float32))
         return out
 
-    def recon_samples(self, observations, is_post, num_samples: int, eps=None, **labels):
+    def recon_samples(self, observations, is_post, num_samples: int, eps=None, posterior=None, **labels):
         """``multiple_samples`` of the reference (training_proc.py:205-223, training_cvs.py / training_challenge.py alike): it calls
         ``recon`` ``num_samples`` times (config.num_samples = 200) and concatenates the quantile curves along a new last axis.
         Here the ``num_samples`` latent draws of the whole batch go through ONE ODE solve + ONE head launch
         (``num_samples * B`` trajectories).  Returns a dict of tensors shaped ``[B, C, T, num_samples]`` (``mu_25/mu_50/mu_75``, or
         ``mean`` for the Gaussian family) plus ``z`` ``[num_samples, B, L]``.  ``eps`` (``[num_samples, B, L]`` standard normal
-        draws, optional) makes the result reproducible."""
+        draws, optional) makes the result reproducible.  ``posterior`` = ``(loc, scale)`` ``[B, L]`` replaces the encoder's / the prior
+        nets' distribution (a refined posterior of ``refine_posterior``: its curves decoded); None (the default): unchanged."""
         self._bind()
         with torch.no_grad():
-            _, z = self._draws(*self._loc_scale(observations, is_post, labels), int(num_samples), eps)      # [ns, B, L]
+            loc, scale = self._loc_scale(observations, is_post, labels) if posterior is None else self._given_posterior(observations, posterior)
+            _, z = self._draws(loc, scale, int(num_samples), eps)      # [ns, B, L]
             return {"z": z, **self._decoded_draws(z)}
 
     def save_recon_samples(self, results_dir: str, observations, is_post, num_samples: int, **labels):
@@ -704,17 +706,20 @@ class MechanisticBase(nn.Module):
             raise ValueError("times_out must begin at the model's first time %r (the initial state belongs there), got %r" % (t0, float(t.reshape(-1)[0])))
         return t
 
-    def forecast_samples(self, observations, is_post, num_samples: int, times_out, eps=None, states: bool = False, **labels):
+    def forecast_samples(self, observations, is_post, num_samples: int, times_out, eps=None, states: bool = False, posterior=None, **labels):
         """The materialising form of ``forecast_moments``: the head curves of ``num_samples`` latent draws on ``times_out``, ``[B, C, T_out,
         num_samples]`` each (``mu_50 / mu_75 / mu_25``, or ``mean``), ``"solution_xt"`` ``[B, T_out, S, num_samples]`` with ``states``, plus
         ``z`` ``[num_samples, B, L]``.  Composed from the encoder or the prior nets, ONE ODE solve of ``num_samples * B`` trajectories on
         ``times_out`` (``Engine.ode_solve(times=...)``: any solver, T_out within what ``slode_ode_solve_fwd`` takes) and the head weights
-        as a torch matmul -- not ``slode_decode_heads``, whose std table is ``constant_std[C, T]`` of the training grid."""
+        as a torch matmul -- not ``slode_decode_heads``, whose std table is ``constant_std[C, T]`` of the training grid.  ``posterior`` =
+        ``(loc, scale)`` ``[B, L]`` replaces the encoder's / the prior nets' distribution (``refine_posterior``: a refined posterior
+        forecast); None (the default): unchanged."""
         b = self._bind()
         t = self._forecast_times(times_out)
         with torch.no_grad():
             B, ns = observations.shape[0], int(num_samples)
-            _, z = self._draws(*self._loc_scale(observations, is_post, labels), ns, eps)             # [ns, B, L]
+            loc, scale = self._loc_scale(observations, is_post, labels) if posterior is None else self._given_posterior(observations, posterior)
+            _, z = self._draws(loc, scale, ns, eps)             # [ns, B, L]
             x = b.engine.ode_solve(b.flat, z.reshape(ns * B, -1).contiguous(), times=t)              # [ns * B, T_out, S]
             heads = b.engine.unpack(b.flat)
             res = {"z": z}
@@ -879,6 +884,60 @@ class MechanisticBase(nn.Module):
         path = os.path.join(results_dir, "bounds_post.npy")
         np.save(path, table)
         return path
+
+    # ---- posterior refinement: per-trajectory ELBO ascent on (loc, log scale), the encoder's posterior as the start ------------------------
+    def _given_posterior(self, observations, posterior):
+        """``posterior`` = (loc, scale) as float32 ``[B, L]`` tensors on the observations' device."""
+        loc, scale = posterior
+        B = observations.shape[0]
+        loc, scale = (torch.as_tensor(t, dtype=torch.float32, device=observations.device).reshape(B, -1).contiguous() for t in (loc, scale))
+        if loc.shape != scale.shape or loc.shape[1] != self._bind().engine.spec.latent_dim:
+            raise ValueError("posterior must be (loc, scale), each [%d, %d], got %s and %s"
+                             % (B, self._bind().engine.spec.latent_dim, tuple(loc.shape), tuple(scale.shape)))
+        return loc, scale
+
+    def refine_posterior(self, observations, num_draws: int, num_steps: int, lr: float = 0.05, mask=None, eps=None, return_trace: bool = False,
+                         **labels):
+        """Closes the amortisation gap subject by subject: every trajectory takes ``num_steps`` Adam steps (``lr``) on its own (loc, log
+        scale), starting from the encoder's, against its own -ELBO over ``num_draws`` = K noise rows that stay fixed for the whole call --
+        ``{"loc": [B, L], "scale": [B, L], "elbo0": [B], "elbo": [B], "best_step": [B]}``: the best iterate, the -ELBO at the encoder's
+        posterior and at the best iterate (``elbo <= elbo0`` by construction), the step the best iterate was found at -- plus, with
+        ``return_trace``, ``"grad0": [B, 2 L]`` (the gradient at the encoder's posterior with respect to (loc, log scale)) and ``"trace":
+        [num_steps + 1, B]`` (the -ELBO of every iterate).  ``mask`` ``[B, C, T]`` (weights >= 0, or bool): the likelihood term of (c, t)
+        counts that much -- a prefix of the window (``mask[:, :, t0:] = 0``), a dropped channel -- while the encoder, which gives the
+        start, still reads the whole block; None: every weight 1.  ONE engine call (``slode_posterior_refine``): forward solve, backward pass
+        and optimiser of a trajectory run in one workgroup.  ``eps`` ``[K, B, L]`` makes it reproducible; None takes drawing calls n .. n + K
+        - 1 of the engine's generator, as ``trajectory_bounds`` does.  What the engine refuses (adaptive solver, strided observations,
+        measured arms, the proc family -- its main loss scores the labels, LDS budget) raises its SlodeError: there is no composed route.
+        Decode or forecast the result with ``recon_samples(posterior=(loc, scale))`` / ``forecast_samples(posterior=...)``."""
+        b = self._bind()
+        B, K = observations.shape[0], self._count(num_draws, "num_draws")
+        if mask is not None:    # the engine takes the weights in the observations' own layout
+            m = torch.as_tensor(mask, device=observations.device).to(torch.float32).expand(observations.shape)
+            mask = torch.empty_strided(observations.shape, observations.stride(), dtype=torch.float32, device=observations.device)
+            mask.copy_(m)
+        loc, scale, elbo, grad0, trace, best = b.engine.posterior_refine(
+            b.flat, self._draws_batch(observations, labels, eps, K), B, K, int(num_steps), lr, mask=mask,
+            grad0=None if return_trace else False, trace=None if return_trace else False)
+        res = {"loc": loc, "scale": scale, "elbo0": elbo[:, 0], "elbo": elbo[:, 1], "best_step": best}
+        if return_trace:
+            res["grad0"], res["trace"] = grad0, trace
+        return res
+
+    def save_refined_posterior(self, results_dir: str, batches, num_draws: int, num_steps: int, lr: float = 0.05):
+        """Runs ``refine_posterior`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors, optionally
+        ``mask``) and writes ``refined_loc.npy`` / ``refined_scale.npy`` (float32 ``[n, L]``) and ``refined_elbo.npy`` (float32 ``[n, 2]``:
+        the -ELBO before and after), the trajectories in loader order, beside the reference's result files.  One read-back, at the end.
+        Returns the three paths."""
+        parts = {"refined_loc.npy": [], "refined_scale.npy": [], "refined_elbo.npy": []}
+        for d in batches:
+            r = self.refine_posterior(num_draws=num_draws, num_steps=num_steps, lr=lr, **d)
+            parts["refined_loc.npy"].append(r["loc"])
+            parts["refined_scale.npy"].append(r["scale"])
+            parts["refined_elbo.npy"].append(torch.stack([r["elbo0"], r["elbo"]], dim=1))
+        if not parts["refined_loc.npy"]:
+            raise ValueError("save_refined_posterior: no batches")
+        return self._save_arrays(results_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()])
 
     # ---- label evidence: which input does the generative model believe produced these curves? -------------------------------------------
     EVIDENCE_NAMES = ("elbo", "iw_bound", "ess", "log_post")    # the slots of one slode_label_evidence row, in order

@@ -112,7 +112,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
-          label_evidence: int = 0):
+          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -135,6 +135,10 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     posterior draws (``save_label_evidence`` on ``default_hypotheses``: ``evidence_post.npy`` [n, V, 4], ``evidence_best.npy``,
     ``evidence_match.npy``, ``evidence_hypotheses_<label>.npy``) and one printed line (``label_evidence: ...``: the share of subjects whose
     most probable hypothesis is their own labels, the mean posterior mass there, the median ESS there) beside the classifier accuracies;
+    0 (the default): no such stage runs.
+    refine_steps = J > 0: after training, the best model's posterior refined subject by subject over the validation loader -- J Adam steps
+    per trajectory on its own (loc, log scale) against its ``refine_draws``-draw -ELBO (``save_refined_posterior``: ``refined_loc.npy``,
+    ``refined_scale.npy``, ``refined_elbo.npy`` [n, 2]) -- and one printed line (``refine_posterior: ...``: the mean -ELBO before and after);
     0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -237,6 +241,13 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
         line = best_model.label_evidence_line(*(np.load(f) for f in written[:3]))
         print(line)
         logging.debug("%s (%s)", line, written)
+    if refine_steps:
+        written = best_model.save_refined_posterior(out_dir, (batch_to_device(b, device, family) for b in val_b), int(refine_draws), int(refine_steps))
+        table = np.load([f for f in written if f.endswith("refined_elbo.npy")][0])
+        line = "refine_posterior: J=%d K=%d  n=%d  mean -ELBO before=%.4f after=%.4f" % (
+            int(refine_steps), int(refine_draws), table.shape[0], float(table[:, 0].mean()), float(table[:, 1].mean()))
+        print(line)
+        logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -305,6 +316,10 @@ def build_parser():
     ap.add_argument("--label-evidence", type=int, default=0, metavar="K",
                     help="after training: the best model's own label posterior p(u | x) over the family's default hypotheses from K posterior draws "
                          "over the validation loader (save_label_evidence: evidence_*.npy) and its agreement with the subjects' labels, one line")
+    ap.add_argument("--refine-steps", type=int, default=0, metavar="J",
+                    help="after training: the best model's posterior refined per subject over the validation loader, J Adam steps on (loc, log "
+                         "scale) against the subject's own -ELBO (save_refined_posterior: refined_*.npy), and the mean -ELBO before and after, one line")
+    ap.add_argument("--refine-draws", type=int, default=8, metavar="K", help="draws per subject of --refine-steps (fixed for the whole refinement)")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -330,6 +345,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["test_bounds"] = a.test_bounds
     if a.label_evidence:
         kw["label_evidence"] = a.label_evidence
+    if a.refine_steps:
+        kw["refine_steps"], kw["refine_draws"] = a.refine_steps, a.refine_draws
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
