@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 220 /* 0.2.2: slode_posterior_refine (0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 230 /* 0.2.3: slode_pointwise_density, slode_pointwise_plan (0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -457,6 +457,49 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
                            float* elbo_out /* [B, 2] */, float* grad0_out /* [B, 2 L] or NULL */, float* trace_out /* [num_steps + 1, B] or NULL */,
                            int32_t* best_step /* [B] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pointwise predictive density: per-point lppd and the WAIC terms from K latent draws as ONE call (no reference counterpart: the other
+ * eval-side calls reduce over the observation points or over the draws before anything leaves the chip; which time points and channels of a
+ * subject are surprising, the log predictive density of held-out points, and a predictive comparison of two fitted models -- WAIC / elpd -- need
+ * the density per point) ---------------------------------------------------------------------------------------------------------------------------
+ * For trajectory b, draw k and point i = (c, t), l_k[i] is the sum over the Q heads of the log-likelihood terms of that point (ALD: its three
+ * quantile heads; Gauss: its one head) on z_k = loc + scale eps[k][b].  With normalised draw weights w_k, point [3, B, C, T] holds the planes
+ *   point[0] lppd[i]    = log sum_k w_k exp(l_k[i])
+ *   point[1] mean_ll[i] = sum_k w_k l_k[i]
+ *   point[2] var_ll[i]  = sum_k w_k (l_k[i] - mean_ll[i])^2, the point's WAIC penalty (elpd_waic = lppd - var_ll)
+ * weights: SLODE_PW_POSTERIOR: w_k = 1 / K, the draws of q(z | x) as they come, one sweep, no KL term.  SLODE_PW_IMPORTANCE: w_k ~ exp(-loss_k),
+ * self-normalised, loss_k the per-draw loss of slode_traj_bounds (label terms included where the main loss has them) with the mask's weights on
+ * its likelihood terms: one sweep forms the K losses exactly as slode_traj_bounds does (mask NULL: loss_kb is bit for bit its loss_kb, slot 7 its
+ * ESS), the log-weights are formed in fp64 in a fixed order, and a second sweep redraws the same noise and folds the points.
+ * mask: a tensor with the observations' strides, or NULL (all ones; the same instructions).  It says which points count as observed: its weights
+ * multiply the likelihood terms inside loss_k (importance mode only), and it partitions the sums of summary into in (w > 0) and out (w == 0).
+ * The planes are written for every point, unweighted.  loc / scale ([B, L] each, both or neither): the posterior the draws come from, e.g. the
+ * output of slode_posterior_refine; NULL: the encoder's.  summary [B, SLODE_POINTWISE_SLOTS], 16-byte aligned, fp64 sums of the written plane
+ * values in a fixed order that depends on (C, T) alone, rounded once, as two 16-byte stores:
+ *   [0] sum_in lppd   [1] sum_in var_ll (p_waic)   [2] sum_in mean_ll   [3] n_in   [4] sum_out lppd   [5] sum_out mean_ll   [6] n_out
+ *   [7] effective sample size of the weights (exactly K in posterior mode)
+ * At K = 1: lppd == mean_ll bit for bit, var_ll == 0, the ESS 1.  loss_kb (or NULL; importance mode only): every loss[k][b], [num_draws, B].
+ * Noise: as slode_traj_bounds, in both modes (batch->eps == NULL: drawing calls n .. n + K - 1, the counter left at n + K; else a dense [K, B, L]
+ * tensor).  Every output is a function of (parameters, inputs, mask, posterior, noise) alone: bitwise equal from run to run, for every grid,
+ * for in-kernel and explicit noise.  No atomics.  Enqueue only: no allocation, no synchronisation, no read-back; capturable as a linear graph.
+ * Three launches ("weff", "enc_fwd2", "pointwise_density" in slode_profile_read; with loc / scale given the first two still run: they leave the
+ * likelihood scale table).  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_traj_bounds refuses -- a
+ * NULL handle (before anything else); num_draws < 1 (and B x num_draws beyond 2^30 - 1 noise rows); adaptive solver; particles > 1; the measured
+ * arms; batch->obs NULL; observation strides the folded encoder path does not take or SLODE_NO_FOLD -- then: weights outside {0, 1}; point or
+ * summary NULL, summary not 16-byte aligned; exactly one of loc / scale; loss_kb in posterior mode; LDS tables (step table 2 (T - 1) S,
+ * observations, mask and likelihood scales 4 C T, the point accumulators 7 C T, staged weights, in importance mode 5 K per-draw values) beyond
+ * the budget of 160 KiB.  slode_pointwise_plan: that figure for a shape, host arithmetic only.  There is no composed fallback. */
+#define SLODE_POINTWISE_SLOTS 8
+#define SLODE_PW_POSTERIOR 0
+#define SLODE_PW_IMPORTANCE 1
+int slode_pointwise_plan(const slode_shape* s, int num_draws, int weights, size_t* lds_bytes);
+int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, int num_draws, int weights,
+                            const float* mask /* as batch->obs, or NULL */, const float* loc /* [B, L] or NULL */,
+                            const float* scale /* [B, L] or NULL */, float* point /* [3, B, C, T]: lppd | mean_ll | var_ll */,
+                            float* summary /* [B, SLODE_POINTWISE_SLOTS] */, float* loss_kb /* [num_draws, B] or NULL */, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- counterfactual curves as ONE call (no reference counterpart: the reference's recon takes the whole latent from the posterior or the whole
  * latent from the conditional prior; the structured latent exists to ask "what would THIS subject's curves have looked like under THAT input?") ----
  * For trajectory b and draw k, with ONE noise row eps[k][b][0..L) shared by both arms:
@@ -698,11 +741,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -13,6 +13,9 @@ COHORT_MAX_G, COHORT_MAX_CHUNK = 1024, 64   # SLODE_COHORT_MAX_G, SLODE_COHORT_M
 CALIBRATION_PHI2, CALIBRATION_PHIM2 = 0.97724986805182079, 0.022750131948179195   # SLODE_CALIBRATION_PHI2 / _PHIM2: Phi(2), Phi(-2)
 FORECAST_MAX_T = 1 << 20   # SLODE_FORECAST_MAX_T: most points of an output grid (slode_stage_times_n, slode_forecast_moments)
 BOUND_SLOTS = 4        # SLODE_BOUND_SLOTS: floats of one slode_traj_bounds row [-ELBO, importance-weighted bound, effective sample size, mean NLL]
+POINTWISE_SLOTS = 8    # SLODE_POINTWISE_SLOTS: floats of one slode_pointwise_density summary row [sum_in lppd, sum_in var_ll, sum_in mean_ll, n_in, sum_out lppd, sum_out mean_ll, n_out, ESS]
+PW_POSTERIOR, PW_IMPORTANCE = 0, 1   # SLODE_PW_*: the draw weights of slode_pointwise_density
+POINTWISE_LDS_MAX = 160 * 1024       # SLODE_POINTWISE_LDS_MAX: the LDS budget of its kernel
 EVIDENCE_SLOTS = 4     # SLODE_EVIDENCE_SLOTS: floats of one slode_label_evidence row [-ELBO, importance-weighted bound, effective sample size, log posterior]
 EVIDENCE_MAX_V = 64    # SLODE_EVIDENCE_MAX_V: most hypotheses of one slode_label_evidence call
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
@@ -71,7 +74,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_initialize_state", "slode_prior_nets", "slode_label_heads", "slode_dopri5_step_counts", "slode_decode_heads_bwd",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
-           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
+           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_intervene_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
            "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
@@ -142,6 +145,8 @@ def load():
     lib.slode_label_evidence.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, P(VP), C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_posterior_refine.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, C.c_float, VP, VP, VP, VP, VP, VP, VP, VP,
                                            C.c_size_t, VP]
+    lib.slode_pointwise_plan.argtypes = [P(Shape), C.c_int, C.c_int, P(C.c_size_t)]
+    lib.slode_pointwise_density.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_intervene_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), P(VP), C.c_uint, C.c_int, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_num_stage_times_n.argtypes = [P(Shape), C.c_int]
     lib.slode_stage_times_n.argtypes = [VP, P(Shape), C.c_int, VP, VP, VP]

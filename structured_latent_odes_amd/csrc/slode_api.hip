@@ -1151,6 +1151,63 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
   return SLODE_OK;
 }
 
+// The LDS bytes of slode_pointwise_density for a shape, a draw count and a weighting (host arithmetic only; the compiled state dims, no
+// SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
+int slode_pointwise_plan(const slode_shape* s, int num_draws, int weights, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: %s", bad);
+  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: lds_bytes is NULL");
+  if (num_draws < 1) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: num_draws = %d < 1", num_draws);
+  if (weights != SLODE_PW_POSTERIOR && weights != SLODE_PW_IMPORTANCE)
+    return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: weights = %d is neither SLODE_PW_POSTERIOR (0) nor SLODE_PW_IMPORTANCE (1)", weights);
+  *lds_bytes = slode_pointwise_lds_bytes(*s, num_draws, weights, 0);
+  if (*lds_bytes > SLODE_POINTWISE_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: the LDS tables of T = %d, S = %d, C = %d, num_draws = %d (%zu B) exceed the budget of %d B",
+                s->T, s->S, s->C, num_draws, *lds_bytes, SLODE_POINTWISE_LDS_MAX);
+  return SLODE_OK;
+}
+
+// Per-point lppd, mean and variance of the log-likelihood over num_draws posterior draws, and their per-trajectory sums (include/slode.h):
+// slode_traj_bounds' refusals through the same ladder, then the call's own -- nothing launched, no draw consumed -- then slode_traj_bounds'
+// launches with the pointwise kernel in place of its own.  loc / scale given: the fold + encoder launches still run (they leave the
+// likelihood scale table); the kernel reads the caller's posterior instead of theirs.  No composed fallback.
+int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, int num_draws, int weights, const float* mask, const float* loc,
+                            const float* scale, float* point, float* summary, float* loss_kb, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  const bool imp = weights == SLODE_PW_IMPORTANCE;
+  const EvalCall d{"slode_pointwise_density", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
+                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
+                   " (and no SLODE_NO_FOLD)", "step table, observations, mask, staged weights, the point accumulators, the per-draw losses and weights",
+                   "a shorter window or (importance weights) fewer draws per call fit", imp};
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (weights != SLODE_PW_POSTERIOR && weights != SLODE_PW_IMPORTANCE)
+    return fail(h, SLODE_EINVAL, "slode_pointwise_density: weights = %d is neither SLODE_PW_POSTERIOR (0) nor SLODE_PW_IMPORTANCE (1)", weights);
+  if (!point || !summary || ((uintptr_t)summary & 15) != 0)
+    return fail(h, SLODE_EINVAL, "slode_pointwise_density: point / summary is NULL, or summary is not 16-byte aligned");
+  if ((loc == nullptr) != (scale == nullptr))
+    return fail(h, SLODE_EINVAL, "slode_pointwise_density: loc and scale replace the posterior together (%s is NULL)", loc ? "scale" : "loc");
+  if (loss_kb && !imp)
+    return fail(h, SLODE_EINVAL, "slode_pointwise_density: loss_kb is written in importance mode alone (SLODE_PW_POSTERIOR forms no per-draw loss)");
+  if ((rc = eval_lds(h, s, d, slode_pointwise_lds_bytes(*s, num_draws, weights, h->ode_generic), SLODE_POINTWISE_LDS_MAX)) != SLODE_OK) return rc;
+  PointwiseLaunch a{};
+  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.mask = mask; a.sb = batch->obs_strides[0];
+  a.t_major = p.t_major ? 1 : 0;
+  a.loc = loc ? loc : p.w.loc; a.scale = scale ? scale : p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab;
+  a.point = point; a.summary = summary; a.loss_kb = loss_kb;
+  a.num_draws = num_draws; a.weights = weights; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, s->B);
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
+  HIP_TRY(h, slode_launch_pointwise(a, c.stream));
+  return SLODE_OK;
+}
+
 // Paired-draw moments of the counterfactual curves and of their difference to the factual ones (include/slode.h): refusals first -- nothing
 // launched, no draw consumed -- then the fold + encoder launches of a forward-only step, then the one kernel that walks the draws of its
 // trajectories through both arms.

@@ -630,6 +630,25 @@ struct RefineLaunch {
 hipError_t slode_launch_refine(const RefineLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_refine_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
+// Pointwise predictive density (pointwise_kernel.hip; slode_pointwise_density): per point lppd / mean / variance of the log-likelihood over
+// the num_draws draws, point [3, B, C, T], and per trajectory summary [B, SLODE_POINTWISE_SLOTS] (16-byte aligned).  The inputs of
+// TrajBoundsLaunch; weights: SLODE_PW_POSTERIOR / SLODE_PW_IMPORTANCE; mask: laid out as obs (sb, t_major), or NULL (all 1); loc / scale: the
+// encoder launch's or the caller's; loss_kb [num_draws, B] or NULL (importance mode).
+struct PointwiseLaunch {
+  slode_shape s;
+  slode_layout lay;
+  const float *params, *times, *stage_t, *obs, *mask;
+  int64_t sb;
+  const float *loc, *scale, *eps, *u, *sigtab;
+  float *point, *summary, *loss_kb;
+  int num_draws, weights, grid, t_major, force_generic;
+  RngK rng{};
+  LabelSrc lab{};
+};
+#define SLODE_POINTWISE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table, observations, mask, staged weights, the point accumulators 7 C T, (importance) 5 K per-draw values must fit
+hipError_t slode_launch_pointwise(const PointwiseLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_pointwise_lds_bytes(const slode_shape& s, int num_draws, int weights, int force_generic);
+
 // Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over the paired posterior draws of d (is_post = 1; u unread, lab:
 // the batch's own labels, which the encoder launch takes) per trajectory, mean / sd [Q, B, C, T] of the curve under swapped labels and of its
 // difference to the factual curve; each of the four outputs may be NULL.  cf: the counterfactual label tensors (read in the columns of the

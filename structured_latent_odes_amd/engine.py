@@ -754,6 +754,46 @@ class Engine:
                          self._p(scale), self._p(elbo), self._p(grad0), self._p(trace), self._p(best_step))
         return loc, scale, elbo, grad0, trace, best_step
 
+    def pointwise_plan(self, B: int, num_draws: int, weights: int) -> int:
+        """``slode_pointwise_plan``: the dynamic LDS bytes of ``pointwise_density`` for this shape (host arithmetic only; raises SlodeError
+        where the call would refuse them at its LDS rung)."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_pointwise_plan(C.byref(self.shape(B)), int(num_draws), int(weights), C.byref(r)))
+        return int(r.value)
+
+    def pointwise_density(self, params, batch: L.Batch, B: int, num_draws: int, weights: int, mask=None, loc=None, scale=None, point=None,
+                          summary=None, loss_kb=None, particles: int = 1):
+        """slode_pointwise_density: per observation point (c, t), over ``num_draws`` posterior draws with normalised weights w_k, the log of
+        the mean density, the mean and the variance of the log density -- ``(point, summary, loss_kb)``: ``point`` float32 [3, B, C, T] =
+        lppd | mean_ll | var_ll (the WAIC penalty), ``summary`` float32 [B, L.POINTWISE_SLOTS] = [sum_in lppd, sum_in var_ll, sum_in
+        mean_ll, n_in, sum_out lppd, sum_out mean_ll, n_out, ESS of the weights], ``loss_kb`` float32 [num_draws, B] in importance mode
+        (None in posterior mode, or when passed as False).  ``weights``: L.PW_POSTERIOR (w_k = 1 / K) or L.PW_IMPORTANCE (w_k ~
+        exp(-loss_k), the per-draw losses of ``traj_bounds`` with the mask on their likelihood terms).  ``mask``: float32 weights >= 0, a
+        tensor with the shape AND strides of the observations, or None (all 1): which points count as observed -- the in / out partition
+        of the sums, and in importance mode the weights of the likelihood terms of loss_k; the planes are written for every point.
+        ``loc`` / ``scale``: float32 [B, L] each, both or neither -- the posterior the draws come from (``posterior_refine``'s output);
+        None: the encoder's.  The batch's eps: as ``traj_bounds`` ([num_draws, B, L], or None: the counter advances by num_draws).
+        Enqueued on the current stream.  Raises SlodeError naming the reason for what the kernel does not take (everything ``traj_bounds``
+        refuses; weights outside {0, 1}; one of loc / scale alone; loss_kb in posterior mode; LDS budget): nothing is launched and no draw
+        is consumed then; there is no composed fallback."""
+        K, Ld, Cn = int(num_draws), self.spec.latent_dim, self.spec.n_channels
+        if mask is not None:
+            self._f32(mask, "mask", contiguous=False)
+            if tuple(mask.shape) != (B, Cn, self.T) or tuple(mask.stride()) != tuple(batch.obs_strides[i] for i in range(3)):
+                raise ValueError("mask must have the shape and the strides of the observations")
+        for name, t in (("loc", loc), ("scale", scale)):
+            if t is not None and tuple(self._f32(t, name).shape) != (B, Ld):
+                raise ValueError("%s must be [%d, %d], got %s" % (name, B, Ld, tuple(t.shape)))
+        point = self._out(point, "point", (3, B, Cn, self.T))
+        summary = self._out(summary, "summary", (B, L.POINTWISE_SLOTS))
+        if loss_kb is False or (loss_kb is None and int(weights) != L.PW_IMPORTANCE):
+            loss_kb = None
+        else:
+            loss_kb = self._out(loss_kb, "loss_kb", (max(K, 0), B))
+        self._batch_call(self.lib.slode_pointwise_density, params, batch, B, particles, K, int(weights), self._p(mask), self._p(loc),
+                         self._p(scale), self._p(point), self._p(summary), self._p(loss_kb))
+        return point, summary, loss_kb
+
     def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
                           eff_mean=None, eff_sd=None, particles: int = 1):
         """slode_intervene_moments: counterfactual curves from ``num_samples`` paired posterior draws per trajectory.  Both arms of a draw

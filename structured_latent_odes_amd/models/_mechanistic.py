@@ -2,6 +2,7 @@
 [_Gauss].py).  The per-dataset modules only declare their label schema and attribute names."""
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Tuple
 
 import torch
@@ -938,6 +939,133 @@ class MechanisticBase(nn.Module):
         if not parts["refined_loc.npy"]:
             raise ValueError("save_refined_posterior: no batches")
         return self._save_arrays(results_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()])
+
+    # ---- pointwise predictive density: per-point lppd and the WAIC terms from K posterior draws ----------------------------------------------
+    POINTWISE_NAMES = ("lppd_in", "p_waic_in", "mean_ll_in", "n_in", "lppd_out", "mean_ll_out", "n_out", "ess")   # one summary row, in order
+    POINTWISE_WEIGHTS = {"posterior": 0, "importance": 1}
+
+    def _obs_layout(self, observations, mask):
+        """``mask`` (weights >= 0 or bool, broadcastable to the observations) as a float32 tensor with the observations' shape AND strides."""
+        m = torch.as_tensor(mask, device=observations.device).to(torch.float32).expand(observations.shape)
+        out = torch.empty_strided(observations.shape, observations.stride(), dtype=torch.float32, device=observations.device)
+        out.copy_(m)
+        return out
+
+    def pointwise_density(self, observations, num_draws: int, weights: str = "posterior", mask=None, posterior=None, eps=None,
+                          return_draws: bool = False, **labels):
+        """Where does the model fail, and which of two models predicts better?  Per observation point (c, t), over ``num_draws`` = K
+        posterior draws with normalised weights w_k: ``"lppd"`` = log sum_k w_k p(y | z_k), ``"mean_ll"`` = sum_k w_k log p(y | z_k),
+        ``"p_waic"`` = the weighted variance of log p(y | z_k) and ``"elpd_waic"`` = lppd - p_waic, ``[B, C, T]`` each; per trajectory
+        (``[B]`` each) ``"lppd_in"``, ``"p_waic_in"``, ``"mean_ll_in"``, ``"n_in"`` over the points the mask counts as observed (> 0),
+        ``"lppd_out"``, ``"mean_ll_out"``, ``"n_out"`` over the others, and ``"ess"``, the effective sample size of the weights; with
+        ``return_draws`` (importance weights) ``"loss"`` ``[K, B]``, the per-draw losses.  ``weights``: ``"posterior"`` (w_k = 1 / K, the
+        draws of q(z | x) as they come) or ``"importance"`` (w_k ~ exp(-loss_k), self-normalised; loss_k the per-draw loss of
+        ``trajectory_bounds`` with the mask on its likelihood terms).  ``mask`` ``[B, C, T]`` (weights >= 0, or bool; None: every point
+        observed); the planes cover every point either way.  ``posterior`` = (loc, scale) ``[B, L]`` replaces the encoder's: "fit on a
+        prefix, score the suffix" is ``refine_posterior(mask=prefix)`` and then this call with its (loc, scale) and the same mask, read at
+        ``"lppd_out"``.  ONE engine call (``slode_pointwise_density``); ``eps`` ``[K, B, L]`` makes it reproducible, None takes drawing
+        calls n .. n + K - 1 as ``trajectory_bounds`` does.  Where the engine refuses (adaptive solver, strided observations, measured
+        arms, LDS budget) the same dict is composed from ``recon_samples`` in chunks of ``MOMENTS_CHUNK_ROWS``, scored and folded in torch
+        fp64; importance weights of a family whose main loss scores the labels (proc) cannot be composed and raise ValueError."""
+        if weights not in self.POINTWISE_WEIGHTS:
+            raise ValueError("weights must be 'posterior' or 'importance', got %r" % (weights,))
+        b = self._bind()
+        B, K, imp = observations.shape[0], self._count(num_draws, "num_draws"), weights == "importance"
+        if return_draws and not imp:
+            raise ValueError("return_draws needs weights='importance': posterior weights form no per-draw loss")
+        if mask is not None:
+            mask = self._obs_layout(observations, mask)
+        post = None if posterior is None else self._given_posterior(observations, posterior)
+
+        def fused():
+            point, summary, loss = b.engine.pointwise_density(
+                b.flat, self._draws_batch(observations, labels, eps, K), B, K, self.POINTWISE_WEIGHTS[weights], mask=mask,
+                loc=None if post is None else post[0], scale=None if post is None else post[1], loss_kb=None if return_draws else False)
+            return point, summary, loss
+
+        point, summary, loss = self._fused_or_composed(fused, lambda: self._pointwise_composed(observations, K, imp, mask, post, eps, labels))
+        res = {"lppd": point[0], "mean_ll": point[1], "p_waic": point[2], "elpd_waic": point[0] - point[2]}
+        res.update({n: summary[:, i] for i, n in enumerate(self.POINTWISE_NAMES)})
+        if return_draws:
+            res["loss"] = loss
+        return res
+
+    def _pointwise_composed(self, observations, K, imp, mask, post, eps, labels):
+        """The composed route: ``(point [3, B, C, T], summary [B, 8], loss [K, B] or None)`` from the materialised curves of ``recon_samples``
+        (``MOMENTS_CHUNK_ROWS // K`` rows at a time, ONE drawing call for the whole batch), every point term and every fold in fp64."""
+        if imp and self.AUX and getattr(self._bind().engine.spec, "labels_in_main", False):
+            raise ValueError("pointwise_density: importance weights of the %s family cannot be composed (its main loss scores the labels on z; "
+                             "no unfused call returns those terms per draw): use weights='posterior' or a fixed-grid solver" % self.FAMILY)
+        f64 = torch.float64
+        sd = torch.nn.functional.softplus(self.decoder.constant_std.detach()).to(f64)[None, :, :, None]     # [1, C, T, 1]
+        d = float(self.config.quantile_diff)
+        planes, rows, losses = [], [], []
+        with torch.no_grad():
+            for lo, hi, e, batch in self._chunks(observations, labels, K, eps):
+                obs = batch["observations"]
+                pst = None if post is None else (post[0][lo:hi], post[1][lo:hi])
+                s = self.recon_samples(is_post=True, num_samples=K, eps=e, posterior=pst, **batch)
+                y = obs.to(f64)[..., None]
+                if self.GAUSS:
+                    ell = -torch.log(sd) - 0.5 * math.log(2.0 * math.pi) - 0.5 * ((y - s["mean"].to(f64)) / sd) ** 2
+                else:
+                    ell = 0.0
+                    for name, tau in (("mu_50", 0.5), ("mu_75", 0.5 + d), ("mu_25", 0.5 - d)):
+                        mu = s[name].to(f64)
+                        ell = ell + torch.where(y >= mu, torch.full_like(mu, tau), torch.full_like(mu, 1.0 - tau)) * (-torch.log(2.0 * sd) - (y - mu).abs() / sd)
+                w = torch.ones_like(y[..., 0]) if mask is None else mask[lo:hi].to(f64)                    # [rows, C, T]
+                if imp:
+                    loc, scale = (t.to(f64) for t in (self.encoder.forward(obs) if pst is None else pst))
+                    ploc, pscale = (t.to(f64) for t in self._prior_loc_scale({k: v for k, v in batch.items() if k != "observations"}))
+                    z = s["z"].to(f64)                                                                      # [K, rows, L]
+                    log_q = torch.distributions.Normal(loc, scale).log_prob(z).sum(-1)
+                    log_p = torch.distributions.Normal(ploc, pscale).log_prob(z).sum(-1)
+                    loss = -((w[..., None] * ell).sum((1, 2)).t() + log_p - log_q)                          # [K, rows]
+                    lw = torch.log_softmax(-loss, dim=0)
+                    losses.append(loss)
+                else:
+                    lw = torch.full((K, hi - lo), -math.log(K), dtype=f64, device=obs.device)
+                lwp = lw.t()[:, None, None, :]                                                              # [rows, 1, 1, K]
+                lppd = torch.logsumexp(lwp + ell, dim=-1)
+                mean = (lwp.exp() * ell).sum(-1)
+                var = (lwp.exp() * (ell - mean[..., None]) ** 2).sum(-1)
+                inn = (w > 0).to(f64)
+                out = 1.0 - inn
+                ess = 1.0 / (2.0 * lw).exp().sum(0)
+                rows.append(torch.stack([(lppd * inn).sum((1, 2)), (var * inn).sum((1, 2)), (mean * inn).sum((1, 2)), inn.sum((1, 2)),
+                                         (lppd * out).sum((1, 2)), (mean * out).sum((1, 2)), out.sum((1, 2)), ess], dim=1))
+                planes.append(torch.stack([lppd, mean, var]))
+                del s, ell
+        return (torch.cat(planes, 1).to(torch.float32), torch.cat(rows, 0).to(torch.float32),
+                torch.cat(losses, 1).to(torch.float32) if imp else None)
+
+    def save_pointwise_density(self, results_dir: str, batches, num_draws: int, weights: str = "posterior"):
+        """Runs ``pointwise_density`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors, optionally
+        ``mask`` / ``posterior``) and writes ``pointwise_lppd_<tag>.npy``, ``pointwise_p_waic_<tag>.npy``, ``pointwise_mean_ll_<tag>.npy``
+        (float32 ``[n, C, T]``) and ``waic_<tag>.npy`` (float32 ``[n, 8]``, the columns of ``POINTWISE_NAMES``), ``<tag>`` = ``post``
+        (posterior weights) or ``iw`` (importance weights), the trajectories in loader order, beside the reference's result files.  One
+        read-back, at the end.  Returns the four paths."""
+        tag = "post" if weights == "posterior" else "iw"
+        parts = {"pointwise_lppd_%s.npy" % tag: [], "pointwise_p_waic_%s.npy" % tag: [], "pointwise_mean_ll_%s.npy" % tag: [], "waic_%s.npy" % tag: []}
+        for d in batches:
+            r = self.pointwise_density(num_draws=num_draws, weights=weights, **d)
+            for f, v in zip(parts, (r["lppd"], r["p_waic"], r["mean_ll"], torch.stack([r[n] for n in self.POINTWISE_NAMES], dim=1))):
+                parts[f].append(v)
+        if not parts["waic_%s.npy" % tag]:
+            raise ValueError("save_pointwise_density: no batches")
+        return self._save_arrays(results_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()])
+
+    @staticmethod
+    def waic_line(table, p_waic, num_draws: int) -> str:
+        """The printed line of ``--waic``: total elpd_waic = sum (lppd_in - p_waic_in) and its standard error sqrt(n var_b(elpd_b)) over the
+        n trajectories, total p_waic, and the share of points with p_waic > 0.4 (the usual WAIC reliability warning).  ``table``: ``[n, 8]``
+        (``waic_post.npy``); ``p_waic``: ``[n, C, T]``."""
+        import numpy as np
+        table, p_waic = np.asarray(table, np.float64), np.asarray(p_waic, np.float64)
+        elpd = table[:, 0] - table[:, 1]
+        n = elpd.shape[0]
+        return "waic: K=%d  n=%d  elpd_waic=%.4f  se=%.4f  p_waic=%.4f  share(p_waic>0.4)=%.4f" % (
+            int(num_draws), n, elpd.sum(), float(np.sqrt(n * elpd.var())) if n else 0.0, table[:, 1].sum(), float((p_waic > 0.4).mean()) if p_waic.size else 0.0)
 
     # ---- label evidence: which input does the generative model believe produced these curves? -------------------------------------------
     EVIDENCE_NAMES = ("elbo", "iw_bound", "ess", "log_post")    # the slots of one slode_label_evidence row, in order

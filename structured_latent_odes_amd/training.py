@@ -112,7 +112,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
-          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8):
+          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -139,6 +139,10 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     refine_steps = J > 0: after training, the best model's posterior refined subject by subject over the validation loader -- J Adam steps
     per trajectory on its own (loc, log scale) against its ``refine_draws``-draw -ELBO (``save_refined_posterior``: ``refined_loc.npy``,
     ``refined_scale.npy``, ``refined_elbo.npy`` [n, 2]) -- and one printed line (``refine_posterior: ...``: the mean -ELBO before and after);
+    0 (the default): no such stage runs.
+    waic = K > 0: after training, the best model's pointwise predictive density over the validation loader from K posterior draws
+    (``save_pointwise_density``: ``pointwise_{lppd,p_waic,mean_ll}_post.npy`` [n, C, T], ``waic_post.npy`` [n, 8]) and one printed line
+    (``waic: ...``: total elpd_waic and its standard error over trajectories, total p_waic, the share of points with p_waic > 0.4);
     0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -248,6 +252,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
             int(refine_steps), int(refine_draws), table.shape[0], float(table[:, 0].mean()), float(table[:, 1].mean()))
         print(line)
         logging.debug("%s (%s)", line, written)
+    if waic:
+        written = best_model.save_pointwise_density(out_dir, (batch_to_device(b, device, family) for b in val_b), int(waic))
+        line = best_model.waic_line(np.load([f for f in written if os.path.basename(f).startswith("waic_")][0]),
+                                    np.load([f for f in written if "p_waic" in f][0]), int(waic))
+        print(line)
+        logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -320,6 +330,10 @@ def build_parser():
                     help="after training: the best model's posterior refined per subject over the validation loader, J Adam steps on (loc, log "
                          "scale) against the subject's own -ELBO (save_refined_posterior: refined_*.npy), and the mean -ELBO before and after, one line")
     ap.add_argument("--refine-draws", type=int, default=8, metavar="K", help="draws per subject of --refine-steps (fixed for the whole refinement)")
+    ap.add_argument("--waic", type=int, default=0, metavar="K",
+                    help="after training: the best model's pointwise predictive density over the validation loader from K posterior draws "
+                         "(save_pointwise_density: pointwise_*_post.npy, waic_post.npy) and its WAIC -- elpd_waic with its standard error, p_waic, "
+                         "the share of points with p_waic > 0.4 -- one line")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -347,6 +361,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["label_evidence"] = a.label_evidence
     if a.refine_steps:
         kw["refine_steps"], kw["refine_draws"] = a.refine_steps, a.refine_draws
+    if a.waic:
+        kw["waic"] = a.waic
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:

@@ -9,6 +9,7 @@ from structured_latent_odes_amd import _lib as L, engine as E
 lib = C.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "structured_latent_odes_amd", "libslode.so"))
 f_lds = getattr(lib, "_Z19slode_ode_lds_bytesRK11slode_shapeib"); f_lds.restype = C.c_size_t
 f_thr = getattr(lib, "_Z17slode_ode_threadsRK11slode_shape"); f_thr.restype = C.c_int
+L.load().slode_pointwise_plan.restype = C.c_int
 
 
 class _E(E.Engine):
@@ -22,3 +23,8 @@ for name, spec, T in (("cvs C1 rk4", E.cvs_spec(3, 3, 2, solver="rk4"), 200), ("
     nt = f_thr(C.byref(s))
     b = f_lds(C.byref(s), nt, C.c_bool(True))   # loop-free form (one workgroup per trajectory)
     print("%-18s threads %4d  LDS %6d B  -> %d workgroups/CU by LDS" % (name, nt, b, (160 * 1024) // b))
+    # the pointwise kernel's table (256 threads): posterior weights, and importance weights at K = 8 and K = 200
+    for tag, w, K in (("posterior", L.PW_POSTERIOR, 8), ("importance K=8", L.PW_IMPORTANCE, 8), ("importance K=200", L.PW_IMPORTANCE, 200)):
+        r = C.c_size_t(0)
+        assert L.load().slode_pointwise_plan(C.byref(s), K, w, C.byref(r)) == 0
+        print("%-18s pointwise %-16s LDS %6d B  -> %d workgroups/CU by LDS" % ("", tag, r.value, (160 * 1024) // r.value))
