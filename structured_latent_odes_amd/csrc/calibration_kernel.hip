@@ -247,30 +247,31 @@ size_t slode_calibration_lds_bytes(const slode_shape& s, int force_generic) {
 
 hipError_t slode_launch_calibration(const CalibrationLaunch& a, hipStream_t stream) {
   const slode_shape& s = a.d.s;
-  const CalibrationScratch sc = slode_calibration_scratch(s, a.M, a.G, a.chunk);
+  const CohortPart& c = a.c;
+  const CohortScratch sc = slode_cohort_scratch(c.M, c.G, c.chunk, slode_calibration_partial_bytes(s));
   const size_t lds = slode_calibration_lds_bytes(s, a.d.force_generic);
-  if (lds > SLODE_CALIBRATION_LDS_MAX || a.d.num_samples < 1 || a.d.grid < 1 || a.chunk < 1 || a.chunk > SLODE_COHORT_MAX_CHUNK || a.G < 1 ||
-      a.G > SLODE_COHORT_MAX_G || a.M < 0 || a.M > s.B || !a.below || !a.obs || !a.scratch || (a.M > 0 && (!a.members || !a.offsets)))
+  if (lds > SLODE_CALIBRATION_LDS_MAX || a.d.num_samples < 1 || a.d.grid < 1 || c.chunk < 1 || c.chunk > SLODE_COHORT_MAX_CHUNK || c.G < 1 ||
+      c.G > SLODE_COHORT_MAX_G || c.M < 0 || c.M > s.B || !a.below || !c.obs || !c.scratch || (c.M > 0 && (!c.members || !c.offsets)))
     return hipErrorInvalidValue;
-  char* base = (char*)a.scratch;
+  char* base = (char*)c.scratch;
   int* cs = (int*)(base + sc.cs);
   int4* tab = (int4*)(base + sc.tab);
   int* flags = (int*)(base + sc.flags);
   char* part = base + sc.part;
-  (void)slode_launch_cohort_plan(a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab, stream);
+  (void)slode_launch_cohort_plan(c.offsets, c.M, c.G, c.chunk, sc.n_partials, cs, tab, stream);
   CaK k{};
   fwd_fill(k.d, a.d);
-  k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.cstd = a.d.lay.cstd;
-  k.sb = a.sb; k.PS = (long long)sc.partial_bytes;
+  k.M = c.M; k.G = c.G; k.t_major = c.t_major; k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.cstd = a.d.lay.cstd;
+  k.sb = c.sb; k.PS = (long long)sc.partial_bytes;
   if (k.gauss) { k.tau[0] = 0.5f; k.tau[1] = SLODE_CALIBRATION_PHI2; k.tau[2] = SLODE_CALIBRATION_PHIM2; }
   else { k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff; }
-  k.obs = a.obs; k.members = a.members; k.cs = cs; k.tab = tab; k.flags = flags; k.part = part;
+  k.obs = c.obs; k.members = c.members; k.cs = cs; k.tab = tab; k.flags = flags; k.part = part;
   k.o = ca_lds(s, fwd_generic(s, a.d.force_generic));
   fwd_dispatch(s, a.d.force_generic, [&](auto scv) { fwd_launch("calibration", calibration_kernel<decltype(scv)::value>, a.d.grid, lds, stream, k); });
   CgK m{};
-  m.G = a.G; m.C = s.C; m.T = s.T; m.K = a.d.num_samples; m.PS = (long long)sc.partial_bytes;
+  m.G = c.G; m.C = s.C; m.T = s.T; m.K = a.d.num_samples; m.PS = (long long)sc.partial_bytes;
   m.cs = cs; m.tab = tab; m.flags = flags; m.part = part;
   m.below = a.below; m.inside = a.inside; m.cross = a.cross; m.pinball = a.pinball; m.width = a.width;
-  SLODE_LAUNCH("calibration_merge", calibration_merge_kernel, dim3(a.G * s.C), dim3(CG_NT), 0, stream, m);
+  SLODE_LAUNCH("calibration_merge", calibration_merge_kernel, dim3(c.G * s.C), dim3(CG_NT), 0, stream, m);
   return hipGetLastError();
 }

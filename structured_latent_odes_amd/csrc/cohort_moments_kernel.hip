@@ -254,27 +254,28 @@ hipError_t slode_launch_cohort_plan(const int32_t* offsets, int M, int G, int R,
 
 hipError_t slode_launch_cohort_moments(const CohortMomentsLaunch& a, hipStream_t stream) {
   const slode_shape& s = a.d.s;
-  const CohortScratch sc = slode_cohort_scratch(s, a.M, a.G, a.chunk);
+  const CohortPart& c = a.c;
+  const CohortScratch sc = slode_cohort_scratch(c.M, c.G, c.chunk, slode_cohort_partial_bytes(s));
   const size_t lds = slode_cohort_lds_bytes(s, a.d.force_generic);
-  if (lds > SLODE_COHORT_LDS_MAX || a.d.num_samples < 1 || a.d.grid < 1 || a.chunk < 1 || a.chunk > SLODE_COHORT_MAX_CHUNK || a.G < 1 ||
-      a.G > SLODE_COHORT_MAX_G || a.M < 0 || a.M > s.B || !a.mean || !a.scratch || (a.M > 0 && (!a.members || !a.offsets)))
+  if (lds > SLODE_COHORT_LDS_MAX || a.d.num_samples < 1 || a.d.grid < 1 || c.chunk < 1 || c.chunk > SLODE_COHORT_MAX_CHUNK || c.G < 1 ||
+      c.G > SLODE_COHORT_MAX_G || c.M < 0 || c.M > s.B || !a.mean || !c.scratch || (c.M > 0 && (!c.members || !c.offsets)))
     return hipErrorInvalidValue;
-  char* base = (char*)a.scratch;
+  char* base = (char*)c.scratch;
   int* cs = (int*)(base + sc.cs);
   int4* tab = (int4*)(base + sc.tab);
   int* flags = (int*)(base + sc.flags);
   float* part = (float*)(base + sc.part);
-  (void)slode_launch_cohort_plan(a.offsets, a.M, a.G, a.chunk, sc.n_partials, cs, tab, stream);
+  (void)slode_launch_cohort_plan(c.offsets, c.M, c.G, c.chunk, sc.n_partials, cs, tab, stream);
   CmK k{};
   fwd_fill(k.d, a.d);
-  k.M = a.M; k.G = a.G; k.t_major = a.t_major; k.sb = a.sb; k.PS = sc.partial_floats; k.clip = a.clip_min;
-  k.obs = a.obs; k.members = a.members; k.cs = cs; k.tab = tab; k.flags = flags; k.part = part;
+  k.M = c.M; k.G = c.G; k.t_major = c.t_major; k.sb = c.sb; k.PS = (long long)(sc.partial_bytes / sizeof(float)); k.clip = a.clip_min;
+  k.obs = c.obs; k.members = c.members; k.cs = cs; k.tab = tab; k.flags = flags; k.part = part;
   k.o = cm_lds(s, fwd_generic(s, a.d.force_generic));
   fwd_dispatch(s, a.d.force_generic, [&](auto scv) { fwd_launch("cohort_moments", cohort_moments_kernel<decltype(scv)::value>, a.d.grid, lds, stream, k); });
   CgK m{};
-  m.G = a.G; m.C = s.C; m.T = s.T; m.Q = k.d.f.Q; m.K = a.d.num_samples; m.has_obs = a.obs ? 1 : 0; m.PS = sc.partial_floats;
+  m.G = c.G; m.C = s.C; m.T = s.T; m.Q = k.d.f.Q; m.K = a.d.num_samples; m.has_obs = c.obs ? 1 : 0; m.PS = k.PS;
   m.cs = cs; m.tab = tab; m.flags = flags; m.part = part;
   m.mean = a.mean; m.sd = a.sd; m.sdb = a.sd_subjects; m.obs_mean = a.obs_mean; m.l1 = a.l1;
-  SLODE_LAUNCH("cohort_merge", cohort_merge_kernel, dim3(a.G * s.C), dim3(CM_NT), 0, stream, m);
+  SLODE_LAUNCH("cohort_merge", cohort_merge_kernel, dim3(c.G * s.C), dim3(CM_NT), 0, stream, m);
   return hipGetLastError();
 }

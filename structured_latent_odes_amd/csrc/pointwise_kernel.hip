@@ -9,8 +9,8 @@
 // One workgroup of four waves handles one trajectory at a time (persistent loop beyond the grid), the frame of traj_bounds_kernel:
 //   P0  = B0: staged weights, the likelihood scale table
 //   P1  once per trajectory: labels, observations and mask weights [C][T] (mask == NULL: all 1); posterior and prior of thread l
-//   importance mode, per draw:  P2 = B2, P3 - P5 fwd_solve, P6 the weighted log-likelihood (the expression of refine_kernel's R4: at weight 1 the
-//       sum of B6), P7 = B7, P8 = B8 -> s_loss[k]; then tb_reduce_draws (loss_kb, the ESS, the fp64 bound) and pw_weights:
+//   importance mode:  P2 - P8 = tb_draw_losses, traj_bounds_kernel's draw loop with the weighted log-likelihood (refine_kernel's R4: at
+//       weight 1 the sum of B6) -> s_loss[k]; then tb_reduce_draws (loss_kb, the ESS, the fp64 bound) and pw_weights:
 //       lw_k = (bound - log K) - loss_k in fp64 -> lw_k rounded to fp32 and w_k = exp(lw_k) kept in fp64
 //   per draw:  P9 z (the same noise rows), fwd_solve, the point fold: thread <-> time point t = tid, tid + 256, ...; for each of its C channels
 //       the thread alone owns the point's accumulators in the LDS tables [.][C][T]: running maximum M and sum s of a_k = lw_k + l_k (draw 0:
@@ -31,50 +31,19 @@ constexpr int PW_NT = FWD_NT;
 constexpr int PW_SUMS = 7;   // fp64 sums of the summary: slots 0 - 6
 
 // offsets (in floats, multiples of 4) of the pieces of the dynamic LDS region: the shared ones, then this kernel's own
-struct PwLds { FwdLds f; int obs, inv, lg, w, item, red, dred, row, bd, sum, pm, ps, p0, s1, s2, loss, nll, lw, wt, total; };
+struct PwLds { FwdLds f; ScoredLds s; int row, bd, sum, pm, ps, p0, s1, s2, loss, nll, lw, wt, total; };
 
 struct PwK {
   FwdK f;
   PriorK pr;
   LabelHeadK lh;
-  int gauss, nd, t_major, imp;
-  float tau[3];
+  ScoredK d;
+  int imp;
   float lw_u;    // posterior mode: -log K (K = 1: +0)
   double w_u;    //                 1 / K
-  const float *obs, *mask;
-  long long sb;
-  const float *loc, *scale, *eps, *u, *sigtab;
   float *point, *summary, *loss_kb;
   PwLds o;
-  RngK rng;
-  LabelSrc lab;
 };
-
-// P6: decoder heads + weighted ALD / Gaussian log-likelihood of the thread's time points (the loop of tb_loglik_points with the weighted
-// expressions of refine_kernel's R4: at w = 1 the same sum, bit for bit)
-template <int SM>
-__device__ __forceinline__ float pw_loglik_weighted(const FwdSm& sm, int S, int T, int C, int Q, int gauss, const float (&tau)[3],
-                                                    const float* s_obs, const float* s_inv, const float* s_lg, const float* s_w, int tid) {
-  float llt = 0.f;
-  for (int t = tid; t < T; t += PW_NT) {
-    float x[SM];
-    fwd_state_at<SM>(sm, S, t, x);
-    float ll = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float obv = s_obs[c * T + t], inv = s_inv[c * T + t], lg = s_lg[c * T + t], w = s_w[c * T + t];
-      for (int q = 0; q < Q; ++q) {
-        const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
-        if (gauss) ll += w * (-lg - TB_HL2PI - 0.5f * r * r * inv * inv);
-        else {
-          const float wq = (obv >= mu) ? tau[q] : 1.f - tau[q];
-          ll += (w * wq) * (-lg - fabsf(r) * inv);
-        }
-      }
-    }
-    llt += ll;
-  }
-  return llt;
-}
 
 // the point fold of one draw: l_k[i] of the thread's points (the addends of tb_loglik_points, summed over the heads of one channel) into the
 // accumulators of point i = c T + t, which this thread alone reads and writes.  lw / wt: the draw's log-weight (fp32) and weight (fp64).
@@ -167,16 +136,9 @@ __global__ void __launch_bounds__(PW_NT) pointwise_kernel(const PwK k) {
   constexpr int SM = SC ? SC : SLODE_MAX_S;
   extern __shared__ __attribute__((aligned(16))) float s_pw[];
   const FwdK& f = k.f;
-  const float* __restrict__ par = f.params;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hw = tid >> 5, j32 = tid & 31;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, CT = C * T, nd = k.nd;
+  const int tid = threadIdx.x, T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, nd = k.d.nd;
   const FwdSm sm = fwd_sm(s_pw, k.o.f);
-  float* s_obs = s_pw + k.o.obs;   // [C][T] the trajectory's observations
-  float* s_inv = s_pw + k.o.inv;   // [C][T] 1 / likelihood scale
-  float* s_lg = s_pw + k.o.lg;     // [C][T] log(scale) (Gauss) or log(2 scale) (ALD)
-  float* s_w = s_pw + k.o.w;       // [C][T] the mask weights
-  float* s_item = s_pw + k.o.item; // [n_aux] -46 x label log-prob of the draw, per head
-  float* s_red = s_pw + k.o.red;   // [2][4] per-wave sums of (log q - log p) and of the log-likelihood
+  const ScoredSm ss = scored_sm(s_pw, k.o.s);
   float* s_row = s_pw + k.o.row;   // [4] the four slots of tb_reduce_draws (slot 2: the ESS)
   float* s_pm = s_pw + k.o.pm;     // [C][T] running maximum of a_k
   float* s_ps = s_pw + k.o.ps;     // [C][T] sum of exp(a_k - M)
@@ -184,93 +146,45 @@ __global__ void __launch_bounds__(PW_NT) pointwise_kernel(const PwK k) {
   float* s_loss = s_pw + k.o.loss; // [K] the per-draw losses          (importance mode; the four K-tables are not carved otherwise)
   float* s_nll = s_pw + k.o.nll;   // [K] their negative log-likelihood parts
   float* s_lw = s_pw + k.o.lw;     // [K] the log-weights
-  double* s_dred = reinterpret_cast<double*>(s_pw + k.o.dred);   // tb_reduce_draws' partials
   double* s_bd = reinterpret_cast<double*>(s_pw + k.o.bd);       // [1] the importance-weighted bound before it is rounded
   double* s_sum = reinterpret_cast<double*>(s_pw + k.o.sum);     // [4][8] per-wave partials of the summary
   double* s_s1 = reinterpret_cast<double*>(s_pw + k.o.s1);       // [C][T] sum of w d
   double* s_s2 = reinterpret_cast<double*>(s_pw + k.o.s2);       // [C][T] sum of w d^2
   double* s_wt = reinterpret_cast<double*>(s_pw + k.o.wt);       // [K] the weights
-  const int n_items = LAB ? k.lh.n_aux : 0;
   const bool imp = k.imp != 0;
 
   // ---- P0 ----
   fwd_stage_weights<SM>(f, sm, S, tid);
-  for (int i = tid; i < CT; i += PW_NT) { s_inv[i] = k.sigtab[CT + i]; s_lg[i] = k.sigtab[2 * CT + i]; }
+  tb_stage_scales(k.d, ss, C * T, tid);
 
   for (int b = blockIdx.x; b < f.B; b += gridDim.x) {
     // ---- P1 ----
     __syncthreads();   // (P0's writes; the previous trajectory's readers of every table are done)
-    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
-    {   // the dense blocks of C*T observations and weights in memory order (coalesced), into [C][T]
-      const float* ob = k.obs + (long long)b * k.sb;
-      const float* mk = k.mask ? k.mask + (long long)b * k.sb : nullptr;
-      for (int i = tid; i < CT; i += PW_NT) {
-        int c, t;
-        if (k.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
-        s_obs[c * T + t] = ob[i];
-        s_w[c * T + t] = mk ? mk[i] : 1.f;
-      }
-    }
+    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.d.lab, k.d.u, k.pr.nu, b, tid);
+    tb_stage_obs<true>(k.d, ss, b, T, C, tid);
     __syncthreads();
-    float loc = 0.f, sc = 1.f, pl = 0.f, pls = 0.f, ips = 1.f, nlsc = 0.f;   // thread l < L keeps its latent dim's posterior and prior
-    if (tid < L) {
-      const int l = tid;
-      loc = k.loc[(long long)b * L + l]; sc = k.scale[(long long)b * L + l];
-      if (imp) { fwd_prior_at(k.pr, par, sm.u, l, pl, pls); ips = expf(-pls); nlsc = -logf(sc); }
-    }
+    TbDim q;   // thread l < L keeps its latent dim's posterior and (importance mode) prior
+    if (tid < L) tb_dim_load(q, k.d, k.pr, f.params, sm.u, b, L, tid, imp);
     float ess = (float)nd;
     if (imp) {   // (workgroup-uniform)
-      for (int kk = 0; kk < nd; ++kk) {
-        // ---- P2 ----
-        float klt = 0.f;
-        if (tid < L) {
-          const float z = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
-          klt = tb_logq_minus_logp(z, loc, sc, nlsc, pl, pls, ips);
-          sm.z[tid] = z;
-        }
-        __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_red are done)
-        fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // P3 - P5
-        // ---- P6 ----
-        const float llt0 = pw_loglik_weighted<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, s_w, tid);
-        // ---- P7 ----
-        if (LAB) {   // (every lane of a wave takes part in every sum)
-          const bool on = hw < n_items;
-          const int a = on ? hw : 0;
-          const slode_aux ax = k.lh.aux[a];
-          float lg[8];
-          fwd_label_logits(k.lh, par, a, sm.z + ax.z_off, j32, lg);
-          const float lp = tb_label_logprob(k.lh, par, a, lg, sm.u + ax.u_off);
-          if (on && j32 == 0) s_item[a] = -k.lh.aux_mult * lp;
-        }
-        // ---- P8 ----
-        klt = wave_sum(klt);
-        const float llt = wave_sum(llt0);
-        if (lane == 0) { s_red[wave] = klt; s_red[4 + wave] = llt; }
-        __syncthreads();
-        if (tid == 0) {
-          const float kl = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), ll = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-          float loss = kl - ll;
-          for (int a = 0; a < n_items; ++a) loss += s_item[a];
-          s_loss[kk] = loss; s_nll[kk] = -ll;
-        }
-      }
+      tb_draw_losses<SM, LAB, true>(f, k.lh, k.d, sm, ss, S, b, q, s_loss, s_nll, tid);   // P2 - P8
       __syncthreads();
-      tb_reduce_draws(s_loss, s_nll, s_dred, nd, f.B, b, s_row, k.loss_kb, s_bd);
+      tb_reduce_draws(s_loss, s_nll, ss.dred, nd, f.B, b, s_row, k.loss_kb, s_bd);
       __syncthreads();
       pw_weights(s_loss, s_bd, nd, s_lw, s_wt);
       ess = s_row[2];
     }
     // ---- P9: the draws again (importance) or for the first time (posterior), folded per point ----
     for (int kk = 0; kk < nd; ++kk) {
-      if (tid < L) sm.z[tid] = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
+      if (tid < L) sm.z[tid] = fmaf(q.sc, slode_eps_at(k.d.rng, k.d.eps, b, L, tid, kk, f.B), q.loc);
       __syncthreads();   // (also: pw_weights' writes; the previous draw's readers of s_A / s_x0 / s_row[.][1] are done)
       fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);
       const float lw = imp ? s_lw[kk] : k.lw_u;
       const double wt = imp ? s_wt[kk] : k.w_u;
-      pw_fold_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, s_pm, s_ps, s_p0, s_s1, s_s2, kk == 0, lw, wt, tid);
+      pw_fold_points<SM>(sm, S, T, C, Q, k.d.gauss, k.d.tau, ss.obs, ss.inv, ss.lg, s_pm, s_ps, s_p0, s_s1, s_s2, kk == 0, lw, wt, tid);
     }
     // ---- P10 ----
-    pw_finish(s_pm, s_ps, s_p0, s_s1, s_s2, s_w, s_sum, T, C, f.B, b, ess, k.point, k.summary);
+    pw_finish(s_pm, s_ps, s_p0, s_s1, s_s2, ss.w, s_sum, T, C, f.B, b, ess, k.point, k.summary);
   }
 }
 
@@ -279,8 +193,7 @@ PwLds pw_lds(const slode_shape& s, int nd, int imp, bool generic) {
   LdsCarve cv;
   PwLds o{};
   o.f = fwd_lds(cv, s, generic);
-  o.obs = cv.take(CT); o.inv = cv.take(CT); o.lg = cv.take(CT); o.w = cv.take(CT); o.item = cv.take(SLODE_MAX_AUX); o.red = cv.take(8);
-  o.dred = cv.take(24);   // 12 doubles (every offset is a multiple of 4 floats: 16-byte aligned)
+  o.s = scored_lds(cv, s, true, SLODE_MAX_AUX, 24);
   o.row = cv.take(4); o.bd = cv.take(2); o.sum = cv.take(64);
   o.pm = cv.take(CT); o.ps = cv.take(CT); o.p0 = cv.take(CT); o.s1 = cv.take(2 * CT); o.s2 = cv.take(2 * CT);
   // importance mode: the K losses, their likelihood parts, the log-weights and the fp64 weights come last; a K that cannot fit anyway
@@ -298,24 +211,21 @@ size_t slode_pointwise_lds_bytes(const slode_shape& s, int num_draws, int weight
 }
 
 hipError_t slode_launch_pointwise(const PointwiseLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
+  const ScoredLaunch& d = a.d;
+  const slode_shape& s = d.s;
   PwK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay); fwd_fill(k.lh, s, lay);
-  k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.nd = a.num_draws; k.t_major = a.t_major; k.imp = a.weights == SLODE_PW_IMPORTANCE ? 1 : 0;
-  k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff;
-  const size_t lds = slode_pointwise_lds_bytes(s, a.num_draws, k.imp, a.force_generic);
-  if (lds > SLODE_POINTWISE_LDS_MAX || a.num_draws < 1 || a.grid < 1 || s.n_aux > SLODE_MAX_AUX) return hipErrorInvalidValue;
-  k.lw_u = (float)(0.0 - log((double)a.num_draws)); k.w_u = 1.0 / (double)a.num_draws;
-  k.obs = a.obs; k.mask = a.mask; k.sb = a.sb;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.sigtab = a.sigtab;
+  fwd_fill(k.f, s, d.lay, d.params, d.times, d.stage_t); fwd_fill(k.pr, s, d.lay); fwd_fill(k.lh, s, d.lay); fwd_fill(k.d, d);
+  k.imp = a.weights == SLODE_PW_IMPORTANCE ? 1 : 0;
+  const size_t lds = slode_pointwise_lds_bytes(s, d.num_draws, k.imp, d.force_generic);
+  if (lds > SLODE_POINTWISE_LDS_MAX || d.num_draws < 1 || d.grid < 1 || s.n_aux > SLODE_MAX_AUX) return hipErrorInvalidValue;
+  k.lw_u = (float)(0.0 - log((double)d.num_draws)); k.w_u = 1.0 / (double)d.num_draws;
   k.point = a.point; k.summary = a.summary; k.loss_kb = k.imp ? a.loss_kb : nullptr;
-  k.rng = a.rng; k.lab = a.lab; k.o = pw_lds(s, a.num_draws, k.imp, fwd_generic(s, a.force_generic));
+  k.o = pw_lds(s, d.num_draws, k.imp, fwd_generic(s, d.force_generic));
   const bool lab = k.imp && s.aux_in_main && s.n_aux > 0;
-  fwd_dispatch(s, a.force_generic, [&](auto sc) {
+  fwd_dispatch(s, d.force_generic, [&](auto sc) {
     constexpr int SC = decltype(sc)::value;
-    if (lab) fwd_launch("pointwise_density", pointwise_kernel<SC, true>, a.grid, lds, stream, k);
-    else fwd_launch("pointwise_density", pointwise_kernel<SC, false>, a.grid, lds, stream, k);
+    if (lab) fwd_launch("pointwise_density", pointwise_kernel<SC, true>, d.grid, lds, stream, k);
+    else fwd_launch("pointwise_density", pointwise_kernel<SC, false>, d.grid, lds, stream, k);
   });
   return hipGetLastError();
 }

@@ -22,38 +22,26 @@
 //   after the K draws: F_j (the K losses summed in order in fp64), the best iterate (lowest j on a tie), one Adam step kept by thread l (in fp64).
 // Every sum runs in a fixed order that depends on (K, J, T, L, H) alone: the result is a function of (parameters, inputs, noise) -- bitwise
 // equal between runs, between one workgroup per trajectory and the persistent loop, between in-kernel and explicit noise.  No atomics.
-#include "slode_forward.h"
+#include "traj_terms.h"
 #include "refine_step.h"
 
 namespace {
 
 constexpr int RF_NT = FWD_NT;
-constexpr float RF_HL2PI = FWD_HL2PI;
 
 // offsets (in floats, multiples of 4) of the pieces of the dynamic LDS region: the shared ones, then this kernel's own
-struct RfLds { FwdLds f; int obs, inv, lg, w, ak, g, tab, part, gu, red, loss, fj, total; };
+struct RfLds { FwdLds f; ScoredLds s; int ak, g, tab, part, gu, loss, fj, total; };   // (s: no item, no dred)
 
 struct RfK {
   FwdK f;
   PriorK pr;
-  int gauss, nd, nj, t_major;
-  float tau[3];
+  ScoredK d;
+  int nj;
   float lr;
-  const float *obs, *mask;
-  long long sb;
-  const float *loc, *scale, *eps, *u, *sigtab;
   float *loc_out, *scale_out, *elbo_out, *grad0_out, *trace_out;
   int32_t* best_step;
   RfLds o;
-  RngK rng;
-  LabelSrc lab;
 };
-
-// log q(z | x) - log p(z | labels) of one latent dim (the expression of traj_bounds_kernel's B2)
-__device__ __forceinline__ float rf_logq_minus_logp(float z, float loc, float sc, float nlsc, float pl, float pls, float ips) {
-  const float dz = (z - pl) * ips, zq = (z - loc) / sc;
-  return (nlsc - RF_HL2PI - 0.5f * zq * zq) - (-pls - RF_HL2PI - 0.5f * dz * dz);
-}
 
 // R6: lambda_n = g_n + A_n lambda_{n+1} for n = NS - 1 .. 0 (lambda_NS = g_NS), in place over g [NS + 1][S]; ak: the step coefficients [NS][S].
 // fwd_scan on the reversed index m = NS - 1 - n: one state component per wave pass, a chunk of steps per lane, Kogge-Stone over the lanes' maps.
@@ -73,46 +61,6 @@ __device__ __forceinline__ void rf_rev_scan(float* g, const float* ak, int S, in
     float x = fmaf(Ae, g[NS * S + s], be);
     for (int m = m0; m < m1; ++m) { const int n = NS - 1 - m; x = fmaf(ak[n * S + s], x, g[n * S + s]); g[n * S + s] = x; }
   }
-}
-
-// R4: decoder heads + weighted ALD / Gaussian log-likelihood of the thread's time points tid, tid + 256, ... (the loop and the expressions of
-// traj_bounds_kernel's B6, every term times its weight: at w = 1 the same sum); bwd: g_x of those points into s_g [T][S]
-template <int SM>
-__device__ __forceinline__ float rf_loglik_points(const FwdSm& sm, int S, int T, int C, int Q, int gauss, const float (&tau)[3], const float* s_obs,
-                                                  const float* s_inv, const float* s_lg, const float* s_w, bool bwd, float* s_g, int tid) {
-  float llt = 0.f;
-  for (int t = tid; t < T; t += RF_NT) {
-    float x[SM], gx[SM];
-    fwd_state_at<SM>(sm, S, t, x);
-#pragma unroll
-    for (int s = 0; s < SM; ++s) gx[s] = 0.f;
-    float ll = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float obv = s_obs[c * T + t], inv = s_inv[c * T + t], lg = s_lg[c * T + t], w = s_w[c * T + t];
-      for (int q = 0; q < Q; ++q) {
-        const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
-        float gmu;   // w dll / dmu
-        if (gauss) {
-          ll += w * (-lg - RF_HL2PI - 0.5f * r * r * inv * inv);
-          gmu = w * (r * inv * inv);
-        } else {
-          const float wq = (obv >= mu) ? tau[q] : 1.f - tau[q];
-          ll += (w * wq) * (-lg - fabsf(r) * inv);
-          gmu = w * (inv * ((obv >= mu) ? tau[q] : -(1.f - tau[q])));
-        }
-        if (bwd) {
-#pragma unroll
-          for (int s = 0; s < SM; ++s) if (s < S) gx[s] = fmaf(-gmu, sm.hw[(q * C + c) * S + s], gx[s]);
-        }
-      }
-    }
-    if (bwd) {
-#pragma unroll
-      for (int s = 0; s < SM; ++s) if (s < S) s_g[t * S + s] = gx[s];
-    }
-    llt += ll;
-  }
-  return llt;
 }
 
 // R7: the reverse of the step table, thread <-> step: g_pre_a, g_pre_d of the nst stages of step n into tab[(n nst + r) 2 S + (s | S + s)]
@@ -159,46 +107,32 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
   constexpr int RW = FWD_ROW(SM);
   extern __shared__ __attribute__((aligned(16))) float s_rf[];
   const FwdK& f = k.f;
-  const float* __restrict__ par = f.params;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, H = f.H, CT = C * T, nd = k.nd, nj = k.nj, B = f.B;
+  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, H = f.H, nd = k.d.nd, nj = k.nj, B = f.B;
   const int nst = f.method == SLODE_RK4 ? 4 : f.R;   // stages of one step: euler 1, midpoint 2, rk4 4 (the last one the next step's first)
   const int nch = RF_NT / H, nsamp = (T - 1) * nst;
   const FwdSm sm = fwd_sm(s_rf, k.o.f);
-  float* s_obs = s_rf + k.o.obs;     // [C][T] the trajectory's observations
-  float* s_inv = s_rf + k.o.inv;     // [C][T] 1 / likelihood scale
-  float* s_lg = s_rf + k.o.lg;       // [C][T] log(scale) (Gauss) or log(2 scale) (ALD)
-  float* s_w = s_rf + k.o.w;         // [C][T] the weights of the likelihood terms
+  const ScoredSm ss = scored_sm(s_rf, k.o.s);
   float* s_ak = s_rf + k.o.ak;       // [T-1][S] the step coefficients A of the draw (the scan overwrites sm.A with the states)
   float* s_g = s_rf + k.o.g;         // [T][S] g_x, then lambda
   float* s_tab = s_rf + k.o.tab;     // [(T-1) nst][2 S] g_pre_a | g_pre_d
   float* s_part = s_rf + k.o.part;   // [H][nch] per-chunk partials of g_u
   float* s_gu = s_rf + k.o.gu;       // [2 H] g_u | the init net's hidden gradient
-  float* s_red = s_rf + k.o.red;     // [2][4] per-wave sums of (log q - log p) and of the log-likelihood
   float* s_loss = s_rf + k.o.loss;   // [K] the per-draw losses of the iteration
   float* s_fj = s_rf + k.o.fj;       // [1] F_j
 
   // ---- R0 ----
   fwd_stage_weights<SM>(f, sm, S, tid);
-  for (int i = tid; i < CT; i += RF_NT) { s_inv[i] = k.sigtab[CT + i]; s_lg[i] = k.sigtab[2 * CT + i]; }
+  tb_stage_scales(k.d, ss, C * T, tid);
 
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     // ---- R1 ----
     __syncthreads();   // (R0's writes; the previous trajectory's readers of every table are done)
-    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
-    {   // the dense blocks of C*T observations and weights in memory order (coalesced), into [C][T]
-      const float* ob = k.obs + (long long)b * k.sb;
-      const float* mk = k.mask ? k.mask + (long long)b * k.sb : nullptr;
-      for (int i = tid; i < CT; i += RF_NT) {
-        int c, t;
-        if (k.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
-        s_obs[c * T + t] = ob[i];
-        s_w[c * T + t] = mk ? mk[i] : 1.f;
-      }
-    }
+    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.d.lab, k.d.u, k.pr.nu, b, tid);
+    tb_stage_obs<true>(k.d, ss, b, T, C, tid);
     __syncthreads();
     // thread l < L keeps its latent dim: phi = (loc, rho), the prior, Adam's moments, the best iterate
-    float loc = 0.f, rho = 0.f, sc = 1.f, pl = 0.f, pls = 0.f, ips = 1.f;
+    TbDim q;   // (loc, sc: the iterate; nlsc = -rho)
     // (the optimiser's own arithmetic -- two parameters per thread, once per iteration -- runs in fp64 on fp64 master copies of phi: in fp32
     // the constants 0.001f and 1 - 0.999f alone disagree by 1.3e-5, a 7e-6 error of every step length, and the iterates drift from the
     // exact loop's by 5e-7 per step; the forward and backward passes take phi rounded to fp32)
@@ -206,22 +140,19 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
     float best_loc = 0.f, best_sc = 1.f, best_f = 0.f, f0 = 0.f;
     int best_j = 0;
     if (tid < L) {
-      loc = k.loc[(long long)b * L + tid]; sc = k.scale[(long long)b * L + tid];
-      fwd_prior_at(k.pr, par, sm.u, tid, pl, pls);
-      ips = expf(-pls); rho = logf(sc);
-      loc_d = (double)loc; rho_d = (double)rho;
+      tb_dim_load(q, k.d, k.pr, f.params, sm.u, b, L, tid, true);
+      loc_d = (double)q.loc; rho_d = (double)-q.nlsc;
     }
     for (int j = 0; j <= nj; ++j) {
       const bool bwd = j < nj || (j == 0 && k.grad0_out != nullptr);   // (workgroup-uniform)
-      const float nlsc = -rho;
       float g_loc = 0.f, g_rho = 0.f;
       for (int kk = 0; kk < nd; ++kk) {
         // ---- R2 ----
         float klt = 0.f, z = 0.f, eps = 0.f;
         if (tid < L) {
-          eps = slode_eps_at(k.rng, k.eps, b, L, tid, kk, B);
-          z = fmaf(sc, eps, loc);
-          klt = rf_logq_minus_logp(z, loc, sc, nlsc, pl, pls, ips);
+          eps = slode_eps_at(k.d.rng, k.d.eps, b, L, tid, kk, B);
+          z = fmaf(q.sc, eps, q.loc);
+          klt = tb_logq_minus_logp(z, q.loc, q.sc, q.nlsc, q.pl, q.pls, q.ips);
           sm.z[tid] = z;
         }
         __syncthreads();   // (also: the previous draw's readers of every table of the draw are done)
@@ -236,16 +167,9 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
         fwd_scan(sm.A, sm.B, sm.x0, S, T - 1, lane, wave, RF_NT / 64);
         __syncthreads();
         // ---- R4 ----
-        const float llt0 = rf_loglik_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, s_w, bwd, s_g, tid);
-        // ---- R5 ----
-        klt = wave_sum(klt);
-        const float llt = wave_sum(llt0);
-        if (lane == 0) { s_red[wave] = klt; s_red[4 + wave] = llt; }
-        __syncthreads();   // (also: R4's g_x)
-        if (tid == 0) {
-          const float kl = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), ll = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-          s_loss[kk] = kl - ll;
-        }
+        const float llt0 = tb_loglik_weighted<SM, true>(sm, S, T, C, Q, k.d.gauss, k.d.tau, ss, bwd, s_g, tid);
+        // ---- R5 (its barrier also publishes R4's g_x) ----
+        tb_draw_sums(klt, llt0, ss.red, nullptr, 0, s_loss + kk, nullptr);
         if (bwd) {
           // ---- R6 ----
           rf_rev_scan(s_g, s_ak, S, T - 1, lane, wave, RF_NT / 64);
@@ -288,9 +212,9 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
           if (tid < L) {
             float gz = 0.f;
             for (int r = 0; r < 2 * H; ++r) gz = fmaf(sm.w1[tid * 2 * H + r], s_gu[r], gz);
-            gz += (z - pl) * ips * ips;
+            gz += (z - q.pl) * q.ips * q.ips;
             g_loc += gz;
-            g_rho += gz * sc * eps - 1.f;
+            g_rho += gz * q.sc * eps - 1.f;
           }
         }
       }
@@ -306,7 +230,7 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
       __syncthreads();
       const float fj = s_fj[0];
       if (j == 0) f0 = fj;
-      if (j == 0 || fj < best_f) { best_f = fj; best_loc = loc; best_sc = sc; best_j = j; }
+      if (j == 0 || fj < best_f) { best_f = fj; best_loc = q.loc; best_sc = q.sc; best_j = j; }
       if (tid < L) {
         const float inv_k = 1.f / (float)nd;
         g_loc *= inv_k; g_rho *= inv_k;
@@ -319,8 +243,8 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
           const double c1 = 1.0 - b1t, c2 = 1.0 - b2t;
           loc_d -= lr * (m_l / c1) / (sqrt(v_l / c2) + 1e-8);
           rho_d -= lr * (m_r / c1) / (sqrt(v_r / c2) + 1e-8);
-          loc = (float)loc_d; rho = (float)rho_d;
-          sc = expf(rho);
+          q.loc = (float)loc_d; q.nlsc = -(float)rho_d;
+          q.sc = expf(-q.nlsc);
         }
       }
     }
@@ -333,13 +257,13 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
 }
 
 RfLds rf_lds(const slode_shape& s, int nd, bool generic) {
-  const int CT = s.C * s.T, nst = s.method == SLODE_RK4 ? 4 : (s.method == SLODE_MIDPOINT ? 2 : 1), cap = SLODE_REFINE_LDS_MAX / 4;
+  const int nst = s.method == SLODE_RK4 ? 4 : (s.method == SLODE_MIDPOINT ? 2 : 1), cap = SLODE_REFINE_LDS_MAX / 4;
   LdsCarve cv;
   RfLds o{};
   o.f = fwd_lds(cv, s, generic);
-  o.obs = cv.take(CT); o.inv = cv.take(CT); o.lg = cv.take(CT); o.w = cv.take(CT);
+  o.s = scored_lds(cv, s, true, 0, 0);
   o.ak = cv.take((s.T - 1) * s.S); o.g = cv.take(s.T * s.S); o.tab = cv.take((s.T - 1) * nst * 2 * s.S);
-  o.part = cv.take(RF_NT); o.gu = cv.take(2 * s.H); o.red = cv.take(8);
+  o.part = cv.take(RF_NT); o.gu = cv.take(2 * s.H);
   // the K losses come last; a K that cannot fit anyway counts as the whole budget (no overflow of the offsets)
   o.loss = cv.take(nd < cap ? (nd < 0 ? 0 : nd) : cap); o.fj = cv.take(4);
   o.total = cv.n;
@@ -353,25 +277,22 @@ size_t slode_refine_lds_bytes(const slode_shape& s, int num_draws, int force_gen
 }
 
 hipError_t slode_launch_refine(const RefineLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
+  const ScoredLaunch& d = a.d;
+  const slode_shape& s = d.s;
   RfK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay);
-  k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.nd = a.num_draws; k.nj = a.num_steps; k.t_major = a.t_major; k.lr = a.lr;
-  k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff;
-  k.obs = a.obs; k.mask = a.mask; k.sb = a.sb;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.sigtab = a.sigtab;
+  fwd_fill(k.f, s, d.lay, d.params, d.times, d.stage_t); fwd_fill(k.pr, s, d.lay); fwd_fill(k.d, d);
+  k.nj = a.num_steps; k.lr = a.lr;
   k.loc_out = a.loc_out; k.scale_out = a.scale_out; k.elbo_out = a.elbo_out; k.grad0_out = a.grad0_out; k.trace_out = a.trace_out;
   k.best_step = a.best_step;
-  k.rng = a.rng; k.lab = a.lab; k.o = rf_lds(s, a.num_draws, fwd_generic(s, a.force_generic));
-  const size_t lds = slode_refine_lds_bytes(s, a.num_draws, a.force_generic);
+  k.o = rf_lds(s, d.num_draws, fwd_generic(s, d.force_generic));
+  const size_t lds = slode_refine_lds_bytes(s, d.num_draws, d.force_generic);
   // the kernel's thread maps: 2 H threads for the two hidden layers, H x (256 / H) for the hidden-unit sums, L threads for the latent dims
-  if (lds > SLODE_REFINE_LDS_MAX || a.num_draws < 1 || a.num_steps < 0 || a.grid < 1 || s.T < 2 || s.H < 1 || 2 * s.H > RF_NT || s.L > RF_NT ||
+  if (lds > SLODE_REFINE_LDS_MAX || d.num_draws < 1 || a.num_steps < 0 || d.grid < 1 || s.T < 2 || s.H < 1 || 2 * s.H > RF_NT || s.L > RF_NT ||
       (s.aux_in_main && s.n_aux > 0))
     return hipErrorInvalidValue;
-  fwd_dispatch(s, a.force_generic, [&](auto sc) {
+  fwd_dispatch(s, d.force_generic, [&](auto sc) {
     constexpr int SC = decltype(sc)::value;
-    fwd_launch("posterior_refine", refine_kernel<SC>, a.grid, lds, stream, k);
+    fwd_launch("posterior_refine", refine_kernel<SC>, d.grid, lds, stream, k);
   });
   return hipGetLastError();
 }

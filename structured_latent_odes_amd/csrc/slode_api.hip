@@ -845,7 +845,8 @@ int slode_svi_step(slode_handle h, const slode_shape* s, const slode_layout* lay
   return elbo_step_impl(h, s, lay, c);
 }
 
-// ---- what the eval-side calls (eval_stats, recon_moments, traj_bounds, label_evidence, intervene_moments, forecast_moments, cohort_moments) share ----
+// ---- what the eval-side calls share: eval_stats; the moment family (recon_moments, intervene_moments, forecast_moments, cohort_moments,
+// calibration); the scored-draw family (traj_bounds, label_evidence, posterior_refine, pointwise_density) ----
 // one workgroup per trajectory up to 65,536 of them, then (and under SLODE_ODE_LOOP) a resident grid that loops
 static int eval_grid_for(const slode_ctx* h, int B) {
   long long g = B;
@@ -996,6 +997,38 @@ static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* l
   return run(c.stream);
 }
 
+// ---- the calls that score num_draws posterior draws of every trajectory against its observations (traj_bounds, label_evidence,
+// posterior_refine, pointwise_density) ----
+// Their EvalCall: the texts differ by the call's name, its pointer list and what its LDS figure counts (nullptr: an LDS rung of its own)
+struct ScoredCall : EvalCall {
+  ScoredCall(const char* name_, const char* pointers_, bool missing_, int num_draws, const char* tables = nullptr, const char* advice = nullptr,
+             bool per_draw = false)
+      : EvalCall{name_, pointers_, missing_, "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
+                 " (and no SLODE_NO_FOLD)", tables, advice, per_draw} {}
+};
+// The tail, after the call's own rungs and outputs: the label tensors, step_setup's checks and workspace, everything of ScoredLaunch (loc /
+// scale set on entry are kept: pointwise's caller-supplied posterior), the num_draws drawing calls counted once nothing can refuse the call
+// any more, the fold + encoder launches of a forward-only step, then launch(stream): the call's own kernel on a (what: its failure's speaker).
+extern "C++" template <class Launch>
+static int scored_run(slode_handle h, const slode_shape* s, const slode_layout* lay, const EvalCall& d, ScoredLaunch& a, const float* params,
+                      const float* times, const float* stage_t, const slode_batch* batch, void* workspace, size_t workspace_bytes, void* stream,
+                      const char* what, Launch&& launch) {
+  int rc = batch_labels(h, s, batch, &a.lab);
+  if (rc != SLODE_OK) return rc;
+  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
+  Step p{h, *s, *lay, c};
+  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
+  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = batch->obs_strides[0];
+  a.t_major = p.t_major ? 1 : 0;
+  if (!a.loc) { a.loc = p.w.loc; a.scale = p.w.scale; }
+  a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.num_draws = d.draws; a.force_generic = h->ode_generic;
+  a.grid = eval_grid_for(h, s->B);
+  ClockScope clock_scope(h, true);
+  if ((rc = forward_encode(p, d.draws, &a.rng)) != SLODE_OK) return rc;
+  const hipError_t e = launch(c.stream);
+  return e == hipSuccess ? SLODE_OK : fail(h, SLODE_EHIP, "%s: %s", what, hipGetErrorString(e));
+}
+
 // The statistics row of one batch (include/slode.h): refusals first -- nothing launched, no draw consumed -- then the fold + encoder launches
 // of a forward-only step, the fused kernel and the fixed-order reduction of its partial rows.
 int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
@@ -1049,27 +1082,17 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
 int slode_traj_bounds(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
                       const float* stage_t, const slode_batch* batch, int num_draws, float* bounds, float* loss_kb, void* workspace,
                       size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_traj_bounds", "batch / bounds / times / stage_t / workspace", !batch || !bounds || !times || !stage_t || !workspace,
-                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
-                   " (and no SLODE_NO_FOLD)", "step table, observations, staged weights, the per-draw losses", "fewer draws per call fit", true};
+  const ScoredCall d("slode_traj_bounds", "batch / bounds / times / stage_t / workspace", !batch || !bounds || !times || !stage_t || !workspace,
+                     num_draws, "step table, observations, staged weights, the per-draw losses", "fewer draws per call fit", true);
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK) return rc;
   if (((uintptr_t)bounds & 15) != 0) return fail(h, SLODE_EINVAL, "slode_traj_bounds: bounds must be 16-byte aligned");
   if ((rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if ((rc = eval_lds(h, s, d, slode_traj_bounds_lds_bytes(*s, num_draws, h->ode_generic), SLODE_TRAJ_BOUNDS_LDS_MAX)) != SLODE_OK) return rc;
   TrajBoundsLaunch a{};
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = batch->obs_strides[0]; a.t_major = p.t_major ? 1 : 0;
-  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab; a.bounds = bounds; a.loss_kb = loss_kb;
-  a.num_draws = num_draws; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_traj_bounds(a, c.stream));
-  return SLODE_OK;
+  a.bounds = bounds; a.loss_kb = loss_kb;
+  return scored_run(h, s, lay, d, a.d, params, times, stage_t, batch, workspace, workspace_bytes, stream, "slode_launch_traj_bounds(a, c.stream)",
+                    [&](hipStream_t st) { return slode_launch_traj_bounds(a, st); });
 }
 
 // V label hypotheses scored on the num_draws posterior draws of every trajectory (include/slode.h): slode_traj_bounds' refusals through the
@@ -1079,9 +1102,7 @@ int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layou
                          const float* stage_t, const slode_batch* batch, int num_draws, const float* const* hyp_labels, int V,
                          const float* log_prior, float* evidence, int32_t* best, float* loss_vkb, void* workspace, size_t workspace_bytes,
                          void* stream) {
-  const EvalCall d{"slode_label_evidence", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
-                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
-                   " (and no SLODE_NO_FOLD)"};
+  const ScoredCall d("slode_label_evidence", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_draws);
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (!evidence || ((uintptr_t)evidence & 15) != 0) return fail(h, SLODE_EINVAL, "slode_label_evidence: evidence is NULL or not 16-byte aligned");
@@ -1097,21 +1118,13 @@ int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layou
                                  "staged weights, the V prior rows, the num_draws x V losses) exceed the budget of %d B; fewer draws or hypotheses per call fit",
                 s->T, s->S, s->C, num_draws, V, lds, SLODE_LABEL_EVIDENCE_LDS_MAX);
   LabelEvidenceLaunch a{};
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  a.hyp = a.lab;   // widths and offsets as the batch's
-  for (int i = 0; i < SLODE_MAX_LABELS; ++i) a.hyp.p[i] = i < a.lab.n ? hyp_labels[i] : nullptr;
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.sb = batch->obs_strides[0]; a.t_major = p.t_major ? 1 : 0;
-  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.sigtab = p.w.sigtab; a.log_prior = log_prior;
-  a.evidence = evidence; a.best = best; a.loss_vkb = loss_vkb;
-  a.num_draws = num_draws; a.V = V; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_label_evidence(a, c.stream));
-  return SLODE_OK;
+  a.log_prior = log_prior; a.evidence = evidence; a.best = best; a.loss_vkb = loss_vkb; a.V = V;
+  return scored_run(h, s, lay, d, a.d, params, times, stage_t, batch, workspace, workspace_bytes, stream, "slode_launch_label_evidence(a, c.stream)",
+                    [&](hipStream_t st) {
+                      a.hyp = a.d.lab;   // widths and offsets as the batch's
+                      for (int i = 0; i < SLODE_MAX_LABELS; ++i) a.hyp.p[i] = i < a.d.lab.n ? hyp_labels[i] : nullptr;
+                      return slode_launch_label_evidence(a, st);
+                    });
 }
 
 // num_steps Adam steps of every trajectory on its own (loc, log scale) against its num_draws-draw -ELBO (include/slode.h): slode_traj_bounds'
@@ -1121,11 +1134,10 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
                            const float* stage_t, const slode_batch* batch, int num_draws, int num_steps, float lr, const float* mask,
                            float* loc_out, float* scale_out, float* elbo_out, float* grad0_out, float* trace_out, int32_t* best_step,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  const EvalCall d{"slode_posterior_refine", "batch / loc_out / scale_out / elbo_out / times / stage_t / workspace",
-                   !batch || !loc_out || !scale_out || !elbo_out || !times || !stage_t || !workspace,
-                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
-                   " (and no SLODE_NO_FOLD)", "step table and its kept copy, lambda, the stage-gradient table, observations, weights, staged weights, the per-draw losses",
-                   "a shorter window or fewer draws per call fit", true};
+  const ScoredCall d("slode_posterior_refine", "batch / loc_out / scale_out / elbo_out / times / stage_t / workspace",
+                     !batch || !loc_out || !scale_out || !elbo_out || !times || !stage_t || !workspace, num_draws,
+                     "step table and its kept copy, lambda, the stage-gradient table, observations, weights, staged weights, the per-draw losses",
+                     "a shorter window or fewer draws per call fit", true);
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (num_steps < 0) return fail(h, SLODE_EINVAL, "slode_posterior_refine: num_steps = %d < 0", num_steps);
@@ -1135,20 +1147,11 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
                                  "pass of the label heads is out of scope");
   if ((rc = eval_lds(h, s, d, slode_refine_lds_bytes(*s, num_draws, h->ode_generic), SLODE_REFINE_LDS_MAX)) != SLODE_OK) return rc;
   RefineLaunch a{};
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.mask = mask; a.sb = batch->obs_strides[0];
-  a.t_major = p.t_major ? 1 : 0;
-  a.loc = p.w.loc; a.scale = p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab;
+  a.d.mask = mask;
   a.loc_out = loc_out; a.scale_out = scale_out; a.elbo_out = elbo_out; a.grad0_out = grad0_out; a.trace_out = trace_out; a.best_step = best_step;
-  a.lr = lr; a.num_draws = num_draws; a.num_steps = num_steps; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_refine(a, c.stream));
-  return SLODE_OK;
+  a.lr = lr; a.num_steps = num_steps;
+  return scored_run(h, s, lay, d, a.d, params, times, stage_t, batch, workspace, workspace_bytes, stream, "slode_launch_refine(a, c.stream)",
+                    [&](hipStream_t st) { return slode_launch_refine(a, st); });
 }
 
 // The LDS bytes of slode_pointwise_density for a shape, a draw count and a weighting (host arithmetic only; the compiled state dims, no
@@ -1176,10 +1179,9 @@ int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_la
                             const float* scale, float* point, float* summary, float* loss_kb, void* workspace, size_t workspace_bytes,
                             void* stream) {
   const bool imp = weights == SLODE_PW_IMPORTANCE;
-  const EvalCall d{"slode_pointwise_density", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace,
-                   "num_draws", num_draws, "", "(the shape has one particle; the draws are num_draws)", "batch->obs is NULL",
-                   " (and no SLODE_NO_FOLD)", "step table, observations, mask, staged weights, the point accumulators, the per-draw losses and weights",
-                   "a shorter window or (importance weights) fewer draws per call fit", imp};
+  const ScoredCall d("slode_pointwise_density", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_draws,
+                     "step table, observations, mask, staged weights, the point accumulators, the per-draw losses and weights",
+                     "a shorter window or (importance weights) fewer draws per call fit", imp);
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
   if (weights != SLODE_PW_POSTERIOR && weights != SLODE_PW_IMPORTANCE)
@@ -1192,20 +1194,10 @@ int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_la
     return fail(h, SLODE_EINVAL, "slode_pointwise_density: loss_kb is written in importance mode alone (SLODE_PW_POSTERIOR forms no per-draw loss)");
   if ((rc = eval_lds(h, s, d, slode_pointwise_lds_bytes(*s, num_draws, weights, h->ode_generic), SLODE_POINTWISE_LDS_MAX)) != SLODE_OK) return rc;
   PointwiseLaunch a{};
-  if ((rc = batch_labels(h, s, batch, &a.lab)) != SLODE_OK) return rc;
-  const StepCall c = forward_call(params, times, stage_t, batch, a.lab, nullptr, workspace, workspace_bytes, stream);
-  Step p{h, *s, *lay, c};
-  if ((rc = forward_setup(p, d.name)) != SLODE_OK) return rc;
-  a.s = *s; a.lay = *lay; a.params = params; a.times = times; a.stage_t = stage_t; a.obs = c.obs; a.mask = mask; a.sb = batch->obs_strides[0];
-  a.t_major = p.t_major ? 1 : 0;
-  a.loc = loc ? loc : p.w.loc; a.scale = scale ? scale : p.w.scale; a.eps = c.eps; a.u = p.u; a.sigtab = p.w.sigtab;
-  a.point = point; a.summary = summary; a.loss_kb = loss_kb;
-  a.num_draws = num_draws; a.weights = weights; a.force_generic = h->ode_generic;
-  a.grid = eval_grid_for(h, s->B);
-  ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, num_draws, &a.rng)) != SLODE_OK) return rc;
-  HIP_TRY(h, slode_launch_pointwise(a, c.stream));
-  return SLODE_OK;
+  a.d.mask = mask; a.d.loc = loc; a.d.scale = scale;   // (both or neither: scored_run keeps them)
+  a.point = point; a.summary = summary; a.loss_kb = loss_kb; a.weights = weights;
+  return scored_run(h, s, lay, d, a.d, params, times, stage_t, batch, workspace, workspace_bytes, stream, "slode_launch_pointwise(a, c.stream)",
+                    [&](hipStream_t st) { return slode_launch_pointwise(a, st); });
 }
 
 // Paired-draw moments of the counterfactual curves and of their difference to the factual ones (include/slode.h): refusals first -- nothing
@@ -1349,22 +1341,64 @@ static const char* cohort_sizes(const slode_shape* s, int M, int G, int chunk, c
   return nullptr;
 }
 
+// the plan entry points: host arithmetic only (the compiled state dims, no SLODE_ODE_GENERIC)
+static int cohort_plan_for(const char* who, size_t (*lds_bytes_of)(const slode_shape&, int), int budget, const char* tables, size_t partial_bytes,
+                           const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                           size_t* scratch_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "%s: %s", who, bad);
+  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
+    return fail(nullptr, SLODE_EINVAL, "%s: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL", who);
+  if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "%s: num_samples = %d < 1", who, num_samples);
+  char why[128];
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "%s: %s", who, why);
+  const size_t lds = lds_bytes_of(*s, 0);
+  if (lds > (size_t)budget)
+    return fail(nullptr, SLODE_EINVAL, "%s: the LDS tables of T = %d, S = %d, C = %d (%zu B: %s) exceed the budget of %d B", who, s->T, s->S, s->C,
+                lds, tables, budget);
+  const int R = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CohortScratch sc = slode_cohort_scratch(M, G, R, partial_bytes);
+  *chunk_out = R; *n_partials = sc.n_partials; *lds_bytes = lds; *scratch_bytes = sc.bytes;
+  return SLODE_OK;
+}
 int slode_cohort_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
                       size_t* scratch_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: %s", bad);
-  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
-    return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL");
-  if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: num_samples = %d < 1", num_samples);
+  return cohort_plan_for("slode_cohort_plan", slode_cohort_lds_bytes, SLODE_COHORT_LDS_MAX, "step table, six-float table, observation sum, staged weights",
+                         s ? slode_cohort_partial_bytes(*s) : 0, s, M, G, num_samples, chunk, chunk_out, n_partials, lds_bytes, scratch_bytes);
+}
+int slode_calibration_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
+                           size_t* scratch_bytes) {
+  return cohort_plan_for("slode_calibration_plan", slode_calibration_lds_bytes, SLODE_CALIBRATION_LDS_MAX,
+                         "step table, counts, fp64 sums, observations, staged weights", s ? slode_calibration_partial_bytes(*s) : 0, s, M, G,
+                         num_samples, chunk, chunk_out, n_partials, lds_bytes, scratch_bytes);
+}
+
+// The argument rungs the two calls share, each group where the call's own ladder has it.  First: members / offsets, cohort_sizes ...
+static int cohort_index_args(slode_handle h, const char* who, const slode_shape* s, const int32_t* members, const int32_t* offsets, int M, int G, int chunk) {
+  if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "%s: members / offsets is NULL with M = %d", who, M);
   char why[128];
-  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: %s", why);
-  const size_t lds = slode_cohort_lds_bytes(*s, 0);
-  if (lds > SLODE_COHORT_LDS_MAX)
-    return fail(nullptr, SLODE_EINVAL, "slode_cohort_plan: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, six-float table, observation "
-                                       "sum, staged weights) exceed the budget of %d B", s->T, s->S, s->C, lds, SLODE_COHORT_LDS_MAX);
-  const int R = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
-  const CohortScratch sc = slode_cohort_scratch(*s, M, G, R);
-  *chunk_out = R; *n_partials = sc.n_partials; *lds_bytes = lds; *scratch_bytes = sc.bytes;
+  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(h, SLODE_EINVAL, "%s: %s", who, why);
+  return SLODE_OK;
+}
+// ... then (need_obs) the dense observation strides -- need: who reads them -- with c.t_major, and the scratch's alignment ...
+static int cohort_obs_args(slode_handle h, const char* who, const slode_shape* s, const slode_batch* batch, bool need_obs, const char* need,
+                           void* scratch, CohortPart& c) {
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (need_obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))
+    return fail(h, SLODE_EINVAL, "%s: observation strides (%lld, %lld, %lld) are not taken: %s need dense [B,T,C] or "
+                                 "[B,C,T] observations; reduce recon_samples instead", who, (long long)os[0], (long long)os[1], (long long)os[2], need);
+  if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "%s: scratch is NULL or not 16-byte aligned", who);
+  c.obs = need_obs ? batch->obs : nullptr; c.sb = os[0]; c.t_major = t_major && !c_major ? 1 : 0; c.scratch = scratch;
+  return SLODE_OK;
+}
+// ... and, after the LDS rung, the chunk and the scratch's size (plan: the entry point that gives it); n_partials: what the grid walks
+static int cohort_scratch_args(slode_handle h, const char* who, const char* plan, const int32_t* members, const int32_t* offsets, int M, int G,
+                               int chunk, size_t partial_bytes, size_t scratch_bytes, CohortPart& c, int* n_partials) {
+  c.members = members; c.offsets = offsets; c.M = M; c.G = G; c.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
+  const CohortScratch sc = slode_cohort_scratch(M, G, c.chunk, partial_bytes);
+  if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "%s: scratch_bytes %zu B < required %zu B (%s)", who, scratch_bytes, sc.bytes, plan);
+  *n_partials = sc.n_partials;
   return SLODE_OK;
 }
 
@@ -1378,52 +1412,24 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
                     "reduce recon_samples instead", "step table, six-float table, observation sum, staged weights");
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
-  if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "slode_cohort_moments: members / offsets is NULL with M = %d", M);
-  char why[128];
-  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(h, SLODE_EINVAL, "slode_cohort_moments: %s", why);
+  if ((rc = cohort_index_args(h, d.name, s, members, offsets, M, G, chunk)) != SLODE_OK) return rc;
   if (!mean) return fail(h, SLODE_EINVAL, "slode_cohort_moments: mean is NULL");
   const bool want_obs = obs_mean || l1;
   if (want_obs && !batch->obs) return fail(h, SLODE_EINVAL, "slode_cohort_moments: obs_mean / l1 need observations (batch->obs is NULL)");
-  const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (want_obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))
-    return fail(h, SLODE_EINVAL, "slode_cohort_moments: observation strides (%lld, %lld, %lld) are not taken: obs_mean / l1 need dense [B,T,C] or "
-                                 "[B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
-  if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "slode_cohort_moments: scratch is NULL or not 16-byte aligned");
-  if ((rc = eval_lds(h, s, d, slode_cohort_lds_bytes(*s, h->ode_generic), SLODE_COHORT_LDS_MAX)) != SLODE_OK) return rc;
   CohortMomentsLaunch a{};
-  a.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
-  const CohortScratch sc = slode_cohort_scratch(*s, M, G, a.chunk);
-  if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "slode_cohort_moments: scratch_bytes %zu B < required %zu B (slode_cohort_plan)", scratch_bytes, sc.bytes);
+  int n_partials = 0;
+  if ((rc = cohort_obs_args(h, d.name, s, batch, want_obs, "obs_mean / l1", scratch, a.c)) != SLODE_OK) return rc;
+  if ((rc = eval_lds(h, s, d, slode_cohort_lds_bytes(*s, h->ode_generic), SLODE_COHORT_LDS_MAX)) != SLODE_OK) return rc;
+  if ((rc = cohort_scratch_args(h, d.name, "slode_cohort_plan", members, offsets, M, G, chunk, slode_cohort_partial_bytes(*s), scratch_bytes, a.c,
+                                &n_partials)) != SLODE_OK) return rc;
   if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, sc.n_partials);
-  a.obs = want_obs ? batch->obs : nullptr; a.sb = os[0]; a.t_major = t_major && !c_major ? 1 : 0;
-  a.members = members; a.offsets = offsets; a.M = M; a.G = G; a.clip_min = clip_min;
-  a.mean = mean; a.sd = sd; a.sd_subjects = sd_subjects; a.obs_mean = obs_mean; a.l1 = l1; a.scratch = scratch;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, n_partials);
+  a.clip_min = clip_min; a.mean = mean; a.sd = sd; a.sd_subjects = sd_subjects; a.obs_mean = obs_mean; a.l1 = l1;
   return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
                    [&](hipStream_t st) { return slode_launch_cohort_moments(a, st); });
 }
 
 // ---- calibration: the draws of slode_recon_moments compared with the observations, counted by cohort (include/slode.h) ----
-int slode_calibration_plan(const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
-                           size_t* scratch_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: %s", bad);
-  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
-    return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL");
-  if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: num_samples = %d < 1", num_samples);
-  char why[128];
-  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: %s", why);
-  const size_t lds = slode_calibration_lds_bytes(*s, 0);
-  if (lds > SLODE_CALIBRATION_LDS_MAX)
-    return fail(nullptr, SLODE_EINVAL, "slode_calibration_plan: the LDS tables of T = %d, S = %d, C = %d (%zu B: step table, counts, fp64 sums, "
-                                       "observations, staged weights) exceed the budget of %d B", s->T, s->S, s->C, lds, SLODE_CALIBRATION_LDS_MAX);
-  const int R = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
-  const CalibrationScratch sc = slode_calibration_scratch(*s, M, G, R);
-  *chunk_out = R; *n_partials = sc.n_partials; *lds_bytes = lds; *scratch_bytes = sc.bytes;
-  return SLODE_OK;
-}
-
 // Refusals first -- slode_cohort_moments' for the same is_post, observations required on both sides; nothing launched, no draw consumed --
 // then, for the posterior, the fold + encoder launches of a forward-only step; then cohort_plan, calibration, calibration_merge.
 int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
@@ -1435,26 +1441,17 @@ int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* 
   d.obs_null = "the curves are compared with observations (batch->obs is NULL)";
   int rc = eval_args(h, s, lay, params, d);
   if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
-  if (M > 0 && (!members || !offsets)) return fail(h, SLODE_EINVAL, "slode_calibration: members / offsets is NULL with M = %d", M);
-  char why[128];
-  if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(h, SLODE_EINVAL, "slode_calibration: %s", why);
+  if ((rc = cohort_index_args(h, d.name, s, members, offsets, M, G, chunk)) != SLODE_OK) return rc;
   if (!below) return fail(h, SLODE_EINVAL, "slode_calibration: below is NULL");
-  const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (os[0] != (long long)s->C * s->T || !(t_major || c_major))
-    return fail(h, SLODE_EINVAL, "slode_calibration: observation strides (%lld, %lld, %lld) are not taken: the comparisons need dense [B,T,C] or "
-                                 "[B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
-  if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "slode_calibration: scratch is NULL or not 16-byte aligned");
-  if ((rc = eval_lds(h, s, d, slode_calibration_lds_bytes(*s, h->ode_generic), SLODE_CALIBRATION_LDS_MAX)) != SLODE_OK) return rc;
   CalibrationLaunch a{};
-  a.chunk = chunk > 0 ? chunk : slode_cohort_default_chunk(M);
-  const CalibrationScratch sc = slode_calibration_scratch(*s, M, G, a.chunk);
-  if (scratch_bytes < sc.bytes) return fail(h, SLODE_ENOSPC, "slode_calibration: scratch_bytes %zu B < required %zu B (slode_calibration_plan)", scratch_bytes, sc.bytes);
+  int n_partials = 0;
+  if ((rc = cohort_obs_args(h, d.name, s, batch, true, "the comparisons", scratch, a.c)) != SLODE_OK) return rc;
+  if ((rc = eval_lds(h, s, d, slode_calibration_lds_bytes(*s, h->ode_generic), SLODE_CALIBRATION_LDS_MAX)) != SLODE_OK) return rc;
+  if ((rc = cohort_scratch_args(h, d.name, "slode_calibration_plan", members, offsets, M, G, chunk, slode_calibration_partial_bytes(*s),
+                                scratch_bytes, a.c, &n_partials)) != SLODE_OK) return rc;
   if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, sc.n_partials);
-  a.obs = batch->obs; a.sb = os[0]; a.t_major = t_major && !c_major ? 1 : 0;
-  a.members = members; a.offsets = offsets; a.M = M; a.G = G;
-  a.below = below; a.inside = inside; a.cross = cross; a.pinball = pinball; a.width = width; a.scratch = scratch;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, n_partials);
+  a.below = below; a.inside = inside; a.cross = cross; a.pinball = pinball; a.width = width;
   return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
                    [&](hipStream_t st) { return slode_launch_calibration(a, st); });
 }

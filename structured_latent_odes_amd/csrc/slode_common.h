@@ -572,78 +572,69 @@ struct ReconMomentsLaunch {
 hipError_t slode_launch_recon_moments(const ReconMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_recon_moments_lds_bytes(const slode_shape& s, int force_generic);
 
-// Per-trajectory bounds from K draws (traj_bounds_kernel.hip; slode_traj_bounds): bounds [B, SLODE_BOUND_SLOTS] (16-byte aligned), loss_kb
-// [num_draws, B] or NULL.  loc / scale [B, L] from the encoder launch, sigtab from the fold launch; obs: dense rows of C*T floats (sb apart),
-// t_major: [T][C] inside a row, else [C][T].  Noise: rng.on: row b of drawing calls c2 .. c2 + num_draws - 1; else eps [num_draws, B, L].
-struct TrajBoundsLaunch {
+// What the calls that score num_draws posterior draws of every trajectory against its observations share (traj_bounds, label_evidence,
+// posterior_refine, pointwise_density).  loc / scale [B, L] from the encoder launch (pointwise: or the caller's), sigtab from the
+// fold launch; obs: dense rows of C*T floats (sb apart), t_major: [T][C] inside a row, else [C][T]; mask: the weights of the likelihood terms,
+// laid out as obs, or NULL (all 1; read by refine and pointwise alone).  Noise: rng.on: row b of drawing calls c2 .. c2 + num_draws - 1; else
+// eps [num_draws, B, L].
+struct ScoredLaunch {
   slode_shape s;
   slode_layout lay;
-  const float *params, *times, *stage_t, *obs;
+  const float *params, *times, *stage_t, *obs, *mask;
   int64_t sb;
   const float *loc, *scale, *eps, *u, *sigtab;
-  float *bounds, *loss_kb;
   int num_draws, grid, t_major, force_generic;
   RngK rng{};
   LabelSrc lab{};
+};
+
+// Per-trajectory bounds from K draws (traj_bounds_kernel.hip; slode_traj_bounds): bounds [B, SLODE_BOUND_SLOTS] (16-byte aligned), loss_kb
+// [num_draws, B] or NULL.
+struct TrajBoundsLaunch {
+  ScoredLaunch d;
+  float *bounds, *loss_kb;
 };
 #define SLODE_TRAJ_BOUNDS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, observations, staged weights, K losses) must fit
 hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
-// Label evidence (label_evidence_kernel in traj_bounds_kernel.hip; slode_label_evidence): V label hypotheses scored on the num_draws posterior
-// draws of every trajectory.  The inputs of TrajBoundsLaunch (lab: the batch's label tensors, n >= 1) and hyp: the hypothesis tables, tensor i
-// dense [V, width i] or NULL (not hypothesised: the trajectory's own); log_prior [V] or NULL.  evidence [B, V, SLODE_EVIDENCE_SLOTS] (16-byte
-// aligned), best [B] or NULL, loss_vkb [V, num_draws, B] or NULL.
+// Label evidence (label_evidence_kernel in traj_bounds_kernel.hip; slode_label_evidence): V label hypotheses scored on the draws of d (d.lab:
+// the batch's label tensors, n >= 1; d.u unread).  hyp: the hypothesis tables, tensor i dense [V, width i] or NULL (not hypothesised: the
+// trajectory's own); log_prior [V] or NULL.  evidence [B, V, SLODE_EVIDENCE_SLOTS] (16-byte aligned), best [B] or NULL, loss_vkb
+// [V, num_draws, B] or NULL.
 struct LabelEvidenceLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times, *stage_t, *obs;
-  int64_t sb;
-  const float *loc, *scale, *eps, *sigtab, *log_prior;
+  ScoredLaunch d;
+  const float* log_prior;
   float *evidence, *loss_vkb;
   int32_t* best;
-  int num_draws, V, grid, t_major, force_generic;
-  RngK rng{};
-  LabelSrc lab{}, hyp{};
+  int V;
+  LabelSrc hyp{};
 };
 #define SLODE_LABEL_EVIDENCE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table, observations, staged weights, the V prior rows, the K x V losses must fit
 hipError_t slode_launch_label_evidence(const LabelEvidenceLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_label_evidence_lds_bytes(const slode_shape& s, int num_draws, int V, int force_generic);
 
 // Posterior refinement (refine_kernel.hip; slode_posterior_refine): num_steps Adam steps of every trajectory on its own (loc, log scale) against
-// its num_draws-draw -ELBO.  The inputs of TrajBoundsLaunch and mask: the weights of the likelihood terms, laid out as obs (sb, t_major), or
-// NULL (all 1).  loc_out / scale_out [B, L], elbo_out [B, 2]; grad0_out [B, 2 L], trace_out [num_steps + 1, B], best_step [B] or NULL.
+// its -ELBO over the draws of d.  loc_out / scale_out [B, L], elbo_out [B, 2]; grad0_out [B, 2 L], trace_out [num_steps + 1, B], best_step [B]
+// or NULL.
 struct RefineLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times, *stage_t, *obs, *mask;
-  int64_t sb;
-  const float *loc, *scale, *eps, *u, *sigtab;
+  ScoredLaunch d;
   float *loc_out, *scale_out, *elbo_out, *grad0_out, *trace_out;
   int32_t* best_step;
   float lr;
-  int num_draws, num_steps, grid, t_major, force_generic;
-  RngK rng{};
-  LabelSrc lab{};
+  int num_steps;
 };
 #define SLODE_REFINE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table and its kept copy, observations, weights, lambda, the stage-gradient table, staged weights, K losses must fit
 hipError_t slode_launch_refine(const RefineLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_refine_lds_bytes(const slode_shape& s, int num_draws, int force_generic);
 
 // Pointwise predictive density (pointwise_kernel.hip; slode_pointwise_density): per point lppd / mean / variance of the log-likelihood over
-// the num_draws draws, point [3, B, C, T], and per trajectory summary [B, SLODE_POINTWISE_SLOTS] (16-byte aligned).  The inputs of
-// TrajBoundsLaunch; weights: SLODE_PW_POSTERIOR / SLODE_PW_IMPORTANCE; mask: laid out as obs (sb, t_major), or NULL (all 1); loc / scale: the
-// encoder launch's or the caller's; loss_kb [num_draws, B] or NULL (importance mode).
+// the draws of d, point [3, B, C, T], and per trajectory summary [B, SLODE_POINTWISE_SLOTS] (16-byte aligned).  weights: SLODE_PW_POSTERIOR /
+// SLODE_PW_IMPORTANCE; loss_kb [num_draws, B] or NULL (importance mode).
 struct PointwiseLaunch {
-  slode_shape s;
-  slode_layout lay;
-  const float *params, *times, *stage_t, *obs, *mask;
-  int64_t sb;
-  const float *loc, *scale, *eps, *u, *sigtab;
+  ScoredLaunch d;
   float *point, *summary, *loss_kb;
-  int num_draws, weights, grid, t_major, force_generic;
-  RngK rng{};
-  LabelSrc lab{};
+  int weights;
 };
 #define SLODE_POINTWISE_LDS_MAX (160 * 1024)   // the LDS of one CU: step table, observations, mask, staged weights, the point accumulators 7 C T, (importance) 5 K per-draw values must fit
 hipError_t slode_launch_pointwise(const PointwiseLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
@@ -675,33 +666,46 @@ struct ForecastMomentsLaunch {
 hipError_t slode_launch_forecast_moments(const ForecastMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the window's tables do not fit the LDS
 size_t slode_forecast_lds_bytes(const slode_shape& s, int num_samples, int want_states, int window, int force_generic);
 
-// Cohort moments (cohort_moments_kernel.hip; slode_cohort_moments): the draws of d folded by cohort.  members [M] / offsets
-// [G + 1] on the device; chunk = R in [1, SLODE_COHORT_MAX_CHUNK] (from the plan); obs: dense rows of C*T floats (sb apart), t_major: [T][C]
-// inside a row, else [C][T], NULL: no observation sum; mean / sd / sd_subjects [Q, G, C, T], obs_mean [G, C, T], l1 [G, C] (all but mean
-// may be NULL).  scratch: slode_cohort_scratch(..).bytes, 16-byte aligned.  Launches cohort_plan, cohort_moments, cohort_merge.
-struct CohortMomentsLaunch {
-  DrawsLaunch d;
+// What the two calls that fold the draws of d by cohort share (cohort_moments, calibration): members [M] / offsets [G + 1] on the device;
+// chunk = R in [1, SLODE_COHORT_MAX_CHUNK] (from the plan); obs: dense rows of C*T floats (sb apart), t_major: [T][C] inside a row, else
+// [C][T]; scratch: slode_cohort_scratch(..).bytes for the call's partial size, 16-byte aligned.
+struct CohortPart {
   const float* obs;
   int64_t sb;
   const int32_t *members, *offsets;
-  float *mean, *sd, *sd_subjects, *obs_mean, *l1;
   void* scratch;
-  float clip_min;
   int M, G, chunk, t_major;
 };
+// Cohort moments (cohort_moments_kernel.hip; slode_cohort_moments): c.obs NULL: no observation sum; mean / sd / sd_subjects [Q, G, C, T],
+// obs_mean [G, C, T], l1 [G, C] (all but mean may be NULL).  Launches cohort_plan, cohort_moments, cohort_merge.
+struct CohortMomentsLaunch {
+  DrawsLaunch d;
+  CohortPart c;
+  float *mean, *sd, *sd_subjects, *obs_mean, *l1;
+  float clip_min;
+};
 // The scratch of one call (byte offsets, multiples of 16): the partial ranges cs [G + 1], the chunk table [n_partials] of 4 ints, the
-// chunks' bad-member flags [n_partials], then n_partials partials of partial_floats floats: [Q*C][5: v00, t1, t2, b1, b2][T] | obs sum [C][T].
-// n_partials = ceil(M / R) + G bounds the chunk count sum_g ceil(n_g / R) of any disjoint cohorts of M members.
-struct CohortScratch { int n_partials; long long partial_floats; size_t cs, tab, flags, part, bytes; };
-inline CohortScratch slode_cohort_scratch(const slode_shape& s, int M, int G, int R) {
-  const long long Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+// chunks' bad-member flags [n_partials], then n_partials partials of partial_bytes.  n_partials = ceil(M / R) + G bounds the chunk count
+// sum_g ceil(n_g / R) of any disjoint cohorts of M members.
+struct CohortScratch { int n_partials; size_t partial_bytes, cs, tab, flags, part, bytes; };
+inline CohortScratch slode_cohort_scratch(int M, int G, int R, size_t partial_bytes) {
   CohortScratch o{};
   o.n_partials = (M + R - 1) / R + G;
-  o.partial_floats = ((5 * Q * s.C + s.C) * (long long)s.T + 3) & ~3LL;
+  o.partial_bytes = partial_bytes;
   auto pad = [](size_t ints) { return ((ints + 3) & ~(size_t)3) * sizeof(int); };
   o.cs = 0; o.tab = o.cs + pad((size_t)G + 1); o.flags = o.tab + (size_t)o.n_partials * 16; o.part = o.flags + pad((size_t)o.n_partials);
-  o.bytes = o.part + (size_t)o.n_partials * (size_t)o.partial_floats * sizeof(float);
+  o.bytes = o.part + (size_t)o.n_partials * partial_bytes;
   return o;
+}
+// a partial of cohort_moments: floats [Q*C][5: v00, t1, t2, b1, b2][T] | obs sum [C][T]
+inline size_t slode_cohort_partial_bytes(const slode_shape& s) {
+  const long long Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+  return (size_t)(((5 * Q * s.C + s.C) * (long long)s.T + 3) & ~3LL) * sizeof(float);
+}
+// a partial of calibration: fp64 sums [4: pinball 0..2, width][C][T] | int32 counts [5: below 0..2, inside, cross][C][T]
+inline size_t slode_calibration_partial_bytes(const slode_shape& s) {
+  const size_t CT = (size_t)s.C * s.T;
+  return (4 * CT * sizeof(double) + 5 * CT * sizeof(int) + 15) & ~(size_t)15;
 }
 // the default chunk: a pure function of M -- the smallest power of two <= 64 with ceil(M / R) <= 1024
 inline int slode_cohort_default_chunk(int M) {
@@ -716,33 +720,15 @@ size_t slode_cohort_lds_bytes(const slode_shape& s, int force_generic);
 // the plan launch of the cohort calls (cohort_moments_kernel.hip): offsets [G + 1] -> cs [G + 1] and the chunk table tab [NP] of 4 ints
 hipError_t slode_launch_cohort_plan(const int32_t* offsets, int M, int G, int R, int NP, int* cs, void* tab, hipStream_t stream);
 
-// Calibration pass (calibration_kernel.hip; slode_calibration): the draws of d compared with the observations, counted by cohort.  members /
-// offsets / chunk as in CohortMomentsLaunch; obs: dense rows of C*T floats (sb apart), t_major: [T][C] inside a row, else [C][T]; below
-// [3, G, C, T], inside / cross [G, C, T] int32, pinball [3, G, C], width [G, C] (all but below may be NULL).  scratch:
-// slode_calibration_scratch(..).bytes, 16-byte aligned.  Launches cohort_plan, calibration, calibration_merge.
+// Calibration pass (calibration_kernel.hip; slode_calibration): the draws of d compared with the observations c.obs, counted by cohort.  below
+// [3, G, C, T], inside / cross [G, C, T] int32, pinball [3, G, C], width [G, C] (all but below may be NULL).  Launches cohort_plan, calibration,
+// calibration_merge.
 struct CalibrationLaunch {
   DrawsLaunch d;
-  const float* obs;
-  int64_t sb;
-  const int32_t *members, *offsets;
+  CohortPart c;
   int32_t *below, *inside, *cross;
   float *pinball, *width;
-  void* scratch;
-  int M, G, chunk, t_major;
 };
-// The scratch of one call (byte offsets, multiples of 16): cs, the chunk table and the flags as in CohortScratch, then n_partials partials of
-// partial_bytes: fp64 sums [4: pinball 0..2, width][C][T] | int32 counts [5: below 0..2, inside, cross][C][T].
-struct CalibrationScratch { int n_partials; size_t partial_bytes, cs, tab, flags, part, bytes; };
-inline CalibrationScratch slode_calibration_scratch(const slode_shape& s, int M, int G, int R) {
-  CalibrationScratch o{};
-  const size_t CT = (size_t)s.C * s.T;
-  o.n_partials = (M + R - 1) / R + G;
-  o.partial_bytes = (4 * CT * sizeof(double) + 5 * CT * sizeof(int) + 15) & ~(size_t)15;
-  auto pad = [](size_t ints) { return ((ints + 3) & ~(size_t)3) * sizeof(int); };
-  o.cs = 0; o.tab = o.cs + pad((size_t)G + 1); o.flags = o.tab + (size_t)o.n_partials * 16; o.part = o.flags + pad((size_t)o.n_partials);
-  o.bytes = o.part + (size_t)o.n_partials * o.partial_bytes;
-  return o;
-}
 #define SLODE_CALIBRATION_LDS_MAX (160 * 1024)   // the LDS of one CU: staged weights, step table, counts, fp64 sums, observations and the scale table must fit
 hipError_t slode_launch_calibration(const CalibrationLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_calibration_lds_bytes(const slode_shape& s, int force_generic);

@@ -20,28 +20,23 @@
 //       loss_kb with plain per-lane stores
 // Every sum runs in a fixed order that depends on (K, T, L) alone: the result is a function of (parameters, inputs, noise) -- bitwise equal
 // between runs, between one workgroup per trajectory and the persistent loop, between in-kernel and explicit noise.  No atomics.
-// The per-draw terms (B2's log q - log p, B6, B7's label log-probability) and B9 are the routines of traj_terms.h: label_evidence_kernel below
-// (slode_label_evidence) executes them against V label hypotheses, pointwise_kernel.hip for its importance weights.
+// The frame (kernel arguments, LDS pieces, B0 / B1's staging), the draw loop B2 - B8 and B9 are the routines of traj_terms.h:
+// label_evidence_kernel below (slode_label_evidence) executes them against V label hypotheses, pointwise_kernel.hip
+// for its importance weights, refine_kernel.hip inside its iteration.
 #include "traj_terms.h"
 
 namespace {
 
 // offsets (in floats, multiples of 4) of the pieces of the dynamic LDS region: the shared ones, then this kernel's own
-struct TbLds { FwdLds f; int obs, inv, lg, item, red, dred, loss, nll, total; };
+struct TbLds { FwdLds f; ScoredLds s; int loss, nll, total; };
 
 struct TbK {
   FwdK f;
   PriorK pr;
   LabelHeadK lh;
-  int gauss, nd, t_major;
-  float tau[3];
-  const float* obs;
-  long long sb;
-  const float *loc, *scale, *eps, *u, *sigtab;
+  ScoredK d;
   float *bounds, *loss_kb;
   TbLds o;
-  RngK rng;
-  LabelSrc lab;
 };
 
 // SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
@@ -51,91 +46,36 @@ __global__ void __launch_bounds__(TB_NT) traj_bounds_kernel(const TbK k) {
   constexpr int SM = SC ? SC : SLODE_MAX_S;
   extern __shared__ __attribute__((aligned(16))) float s_tb[];
   const FwdK& f = k.f;
-  const float* __restrict__ par = f.params;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hw = tid >> 5, j32 = tid & 31;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, CT = C * T, nd = k.nd;
+  const int tid = threadIdx.x, T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C;
   const FwdSm sm = fwd_sm(s_tb, k.o.f);
-  float* s_obs = s_tb + k.o.obs;   // [C][T] the trajectory's observations
-  float* s_inv = s_tb + k.o.inv;   // [C][T] 1 / likelihood scale
-  float* s_lg = s_tb + k.o.lg;     // [C][T] log(scale) (Gauss) or log(2 scale) (ALD)
-  float* s_item = s_tb + k.o.item; // [n_aux] -46 x label log-prob of the draw, per head
-  float* s_red = s_tb + k.o.red;   // [2][4] per-wave sums of (log q - log p) and of the log-likelihood
+  const ScoredSm ss = scored_sm(s_tb, k.o.s);
   float* s_loss = s_tb + k.o.loss; // [K] the trajectory's per-draw losses
   float* s_nll = s_tb + k.o.nll;   // [K] their negative log-likelihood parts
-  double* s_dred = reinterpret_cast<double*>(s_tb + k.o.dred);   // [3][4] per-wave fp64 partials of B9 | [1] the minimum (as a double)
-  const int n_items = LAB ? k.lh.n_aux : 0;
 
   // ---- B0: the weights every draw reuses; the likelihood scale table ----
   fwd_stage_weights<SM>(f, sm, S, tid);
-  for (int i = tid; i < CT; i += TB_NT) { s_inv[i] = k.sigtab[CT + i]; s_lg[i] = k.sigtab[2 * CT + i]; }
+  tb_stage_scales(k.d, ss, C * T, tid);
 
   for (int b = blockIdx.x; b < f.B; b += gridDim.x) {
     // ---- B1 ----
     __syncthreads();   // (B0's writes; the previous trajectory's readers of s_u / s_obs / s_loss / s_nll are done)
-    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.lab, k.u, k.pr.nu, b, tid);
-    {   // the dense block of C*T observations in memory order (coalesced), into [C][T]
-      const float* ob = k.obs + (long long)b * k.sb;
-      for (int i = tid; i < CT; i += TB_NT) {
-        int c, t;
-        if (k.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
-        s_obs[c * T + t] = ob[i];
-      }
-    }
+    if (tid < k.pr.nu) sm.u[tid] = slode_label_at(k.d.lab, k.d.u, k.pr.nu, b, tid);
+    tb_stage_obs<false>(k.d, ss, b, T, C, tid);
     __syncthreads();
-    float loc = 0.f, sc = 1.f, pl = 0.f, pls = 0.f, ips = 1.f, nlsc = 0.f;   // thread l < L keeps its latent dim's posterior and prior
-    if (tid < L) {
-      const int l = tid;
-      loc = k.loc[(long long)b * L + l]; sc = k.scale[(long long)b * L + l];
-      fwd_prior_at(k.pr, par, sm.u, l, pl, pls);
-      ips = expf(-pls); nlsc = -logf(sc);
-    }
-    for (int kk = 0; kk < nd; ++kk) {
-      // ---- B2: draw kk = row b of drawing call n + kk; log q - log p ----
-      float klt = 0.f;
-      if (tid < L) {
-        const float z = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
-        klt = tb_logq_minus_logp(z, loc, sc, nlsc, pl, pls, ips);
-        sm.z[tid] = z;
-      }
-      __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_red are done)
-      fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // B3 - B5
-      // ---- B6: heads + log-likelihood of the thread's time points ----
-      const float llt0 = tb_loglik_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, tid);
-      // ---- B7: the main loss's label terms on z (proc); half-wave = head, lane = hidden unit ----
-      if (LAB) {   // (every lane of a wave takes part in every sum)
-        const bool on = hw < n_items;
-        const int a = on ? hw : 0;
-        const slode_aux ax = k.lh.aux[a];
-        float lg[8];
-        fwd_label_logits(k.lh, par, a, sm.z + ax.z_off, j32, lg);
-        const float lp = tb_label_logprob(k.lh, par, a, lg, sm.u + ax.u_off);
-        if (on && j32 == 0) s_item[a] = -k.lh.aux_mult * lp;
-      }
-      // ---- B8: fixed-order sums over the workgroup; the draw's loss ----
-      klt = wave_sum(klt);
-      const float llt = wave_sum(llt0);
-      if (lane == 0) { s_red[wave] = klt; s_red[4 + wave] = llt; }
-      __syncthreads();
-      if (tid == 0) {
-        const float kl = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]), ll = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-        float loss = kl - ll;
-        for (int a = 0; a < n_items; ++a) loss += s_item[a];
-        s_loss[kk] = loss; s_nll[kk] = -ll;
-      }
-    }
+    TbDim q;   // thread l < L keeps its latent dim's posterior and prior
+    if (tid < L) tb_dim_load(q, k.d, k.pr, f.params, sm.u, b, L, tid, true);
+    tb_draw_losses<SM, LAB, false>(f, k.lh, k.d, sm, ss, S, b, q, s_loss, s_nll, tid);   // B2 - B8
     // ---- B9: the K stored values -> the four slots and loss_kb ----
     __syncthreads();
-    tb_reduce_draws(s_loss, s_nll, s_dred, nd, f.B, b, k.bounds + (long long)b * SLODE_BOUND_SLOTS, k.loss_kb, nullptr);
+    tb_reduce_draws(s_loss, s_nll, ss.dred, k.d.nd, f.B, b, k.bounds + (long long)b * SLODE_BOUND_SLOTS, k.loss_kb, nullptr);
   }
 }
 
 TbLds tb_lds(const slode_shape& s, int nd, bool generic) {
-  const int CT = s.C * s.T;
   LdsCarve cv;
   TbLds o{};
   o.f = fwd_lds(cv, s, generic);
-  o.obs = cv.take(CT); o.inv = cv.take(CT); o.lg = cv.take(CT); o.item = cv.take(SLODE_MAX_AUX); o.red = cv.take(8);
-  o.dred = cv.take(24);   // 12 doubles (the offset is a multiple of 4 floats: 16-byte aligned)
+  o.s = scored_lds(cv, s, false, SLODE_MAX_AUX, 24);
   // the K losses and their likelihood parts come last; a K that cannot fit anyway counts as the whole budget (no overflow of the offsets)
   const int kd = nd < SLODE_TRAJ_BOUNDS_LDS_MAX / 4 ? nd : SLODE_TRAJ_BOUNDS_LDS_MAX / 4;
   o.loss = cv.take(kd); o.nll = cv.take(kd);
@@ -167,22 +107,19 @@ TbLds tb_lds(const slode_shape& s, int nd, bool generic) {
 // The likelihood sums are the same code on the same draw.  The label terms come from the same logits (lane 0's) and tb_label_logprob, a
 // routine without cross-lane operations, so which lane runs it does not matter.  loss = kl - ll + items in the same order, and the K
 // losses go through the same tb_reduce_draws.  No atomics; every sum in a fixed order that depends on (K, V, T, L) alone.
-struct LeLds { FwdLds f; int obs, inv, lg, red, dred, nll, uh, prior, kl, item, ev, bd, loss, total; };
+struct LeLds { FwdLds f; ScoredLds s; int nll, uh, prior, kl, ev, bd, loss, total; };   // (s.item: [V][SLODE_MAX_AUX])
 
 struct LeK {
   FwdK f;
   PriorK pr;
   LabelHeadK lh;
-  int gauss, nd, nv, t_major;
-  float tau[3];
-  const float* obs;
-  long long sb;
-  const float *loc, *scale, *eps, *sigtab, *log_prior;
+  ScoredK d;
+  int nv;
+  const float* log_prior;
   float *evidence, *loss_vkb;
   int32_t* best;
   LeLds o;
-  RngK rng;
-  LabelSrc lab, hyp;   // hyp.p[i] == nullptr: label tensor i is not hypothesised (widths and offsets: lab's)
+  LabelSrc hyp;   // hyp.p[i] == nullptr: label tensor i is not hypothesised (widths and offsets: d.lab's)
 };
 
 // column col of label row u_v of trajectory b
@@ -221,42 +158,39 @@ __global__ void __launch_bounds__(TB_NT) label_evidence_kernel(const LeK k) {
   const FwdK& f = k.f;
   const float* __restrict__ par = f.params;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hw = tid >> 5, j32 = tid & 31;
-  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, CT = C * T, nd = k.nd, V = k.nv, nu = k.pr.nu;
+  const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, nd = k.d.nd, V = k.nv, nu = k.pr.nu;
   const FwdSm sm = fwd_sm(s_tb, k.o.f);
-  float* s_obs = s_tb + k.o.obs;     // [C][T] the trajectory's observations
-  float* s_inv = s_tb + k.o.inv;     // [C][T] 1 / likelihood scale
-  float* s_lg = s_tb + k.o.lg;       // [C][T] log(scale) (Gauss) or log(2 scale) (ALD)
-  float* s_red = s_tb + k.o.red;     // [4 .. 8) per-wave sums of the log-likelihood
+  const ScoredSm ss = scored_sm(s_tb, k.o.s);
+  float* s_red = ss.red;             // [4 .. 8) per-wave sums of the log-likelihood
   float* s_nll = s_tb + k.o.nll;     // [K] the draws' negative log-likelihood (the same for every hypothesis)
   float* s_uh = s_tb + k.o.uh;       // [V][nu] the label rows u_v
   float* s_pr = s_tb + k.o.prior;    // [V][3][L] ploc | pls | exp(-pls)
   float* s_kl = s_tb + k.o.kl;       // [V] sum over l of (log q - log p_v) of the draw
-  float* s_item = s_tb + k.o.item;   // [V][SLODE_MAX_AUX] -46 x label log-prob of the draw against u_v, per head
+  float* s_item = ss.item;           // [V][SLODE_MAX_AUX] -46 x label log-prob of the draw against u_v, per head
   float* s_ev = s_tb + k.o.ev;       // [V][4] the rows of the trajectory before their store
   float* s_loss = s_tb + k.o.loss;   // [V][K] the per-draw losses
-  double* s_dred = reinterpret_cast<double*>(s_tb + k.o.dred);   // tb_reduce_draws' partials
   double* s_bd = reinterpret_cast<double*>(s_tb + k.o.bd);       // [V] the importance-weighted bounds before they are rounded
   const int n_items = LAB ? k.lh.n_aux : 0;
 
   // ---- E0 ----
   fwd_stage_weights<SM>(f, sm, S, tid);
-  for (int i = tid; i < CT; i += TB_NT) { s_inv[i] = k.sigtab[CT + i]; s_lg[i] = k.sigtab[2 * CT + i]; }
+  tb_stage_scales(k.d, ss, C * T, tid);
 
   for (int b = blockIdx.x; b < f.B; b += gridDim.x) {
     // ---- E1 ----
     __syncthreads();   // (E0's writes; the previous trajectory's readers of every table are done)
-    for (int i = tid; i < V * nu; i += TB_NT) { const int v = i / nu; s_uh[i] = le_label_at(k.hyp, k.lab, b, v, i - v * nu); }
-    {
-      const float* ob = k.obs + (long long)b * k.sb;
-      for (int i = tid; i < CT; i += TB_NT) {
+    for (int i = tid; i < V * nu; i += TB_NT) { const int v = i / nu; s_uh[i] = le_label_at(k.hyp, k.d.lab, b, v, i - v * nu); }
+    {   // (tb_stage_obs<false>, written out: as a routine it costs this kernel three VGPRs, and <5, -> would fall from 4 waves per SIMD to 3)
+      const float* ob = k.d.obs + (long long)b * k.d.sb;
+      for (int i = tid; i < C * T; i += TB_NT) {
         int c, t;
-        if (k.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
-        s_obs[c * T + t] = ob[i];
+        if (k.d.t_major) { t = i / C; c = i - t * C; } else { c = i / T; t = i - c * T; }
+        ss.obs[c * T + t] = ob[i];
       }
     }
     __syncthreads();
     float loc = 0.f, sc = 1.f, nlsc = 0.f;   // lane l < L of every wave keeps its latent dim's posterior
-    if (lane < L) { loc = k.loc[(long long)b * L + lane]; sc = k.scale[(long long)b * L + lane]; nlsc = -logf(sc); }
+    if (lane < L) { loc = k.d.loc[(long long)b * L + lane]; sc = k.d.scale[(long long)b * L + lane]; nlsc = -logf(sc); }
     for (int i = tid; i < V * L; i += TB_NT) {   // (read after the draw's first barrier)
       const int v = i / L, l = i - v * L;
       float pl, pls;
@@ -265,11 +199,11 @@ __global__ void __launch_bounds__(TB_NT) label_evidence_kernel(const LeK k) {
     }
     for (int kk = 0; kk < nd; ++kk) {
       // ---- E2 ----
-      if (tid < L) sm.z[tid] = fmaf(sc, slode_eps_at(k.rng, k.eps, b, L, tid, kk, f.B), loc);
+      if (tid < L) sm.z[tid] = fmaf(sc, slode_eps_at(k.d.rng, k.d.eps, b, L, tid, kk, f.B), loc);
       __syncthreads();   // (also: the previous draw's readers of s_A / s_x0 / s_row[.][1] / s_item / s_kl / s_red are done)
       fwd_solve<SM>(f, sm, S, sm.x0, 0, T - 1, tid);   // E3 - E5
       // ---- E6 ----
-      const float llt0 = tb_loglik_points<SM>(sm, S, T, C, Q, k.gauss, k.tau, s_obs, s_inv, s_lg, tid);
+      const float llt0 = tb_loglik_points<SM>(sm, S, T, C, Q, k.d.gauss, k.d.tau, ss.obs, ss.inv, ss.lg, tid);
       // ---- E7 ----
       if (LAB) {   // (every lane of a wave takes part in every sum)
         const bool on = hw < n_items;
@@ -306,7 +240,7 @@ __global__ void __launch_bounds__(TB_NT) label_evidence_kernel(const LeK k) {
     // ---- E9 ----
     for (int v = 0; v < V; ++v) {
       __syncthreads();   // (the draws' writes; the previous hypothesis' readers of s_dred are done)
-      tb_reduce_draws(s_loss + v * nd, s_nll, s_dred, nd, f.B, b, s_ev + 4 * v, k.loss_vkb ? k.loss_vkb + (long long)v * nd * f.B : nullptr, s_bd + v);
+      tb_reduce_draws(s_loss + v * nd, s_nll, ss.dred, nd, f.B, b, s_ev + 4 * v, k.loss_vkb ? k.loss_vkb + (long long)v * nd * f.B : nullptr, s_bd + v);
     }
     __syncthreads();
     if (tid == 0) le_posterior(s_bd, k.log_prior, V, s_ev, k.best ? k.best + b : nullptr);
@@ -319,14 +253,13 @@ __global__ void __launch_bounds__(TB_NT) label_evidence_kernel(const LeK k) {
 }
 
 LeLds le_lds(const slode_shape& s, int nd, int V, bool generic) {
-  const int CT = s.C * s.T, cap = SLODE_LABEL_EVIDENCE_LDS_MAX / 4;
+  const int cap = SLODE_LABEL_EVIDENCE_LDS_MAX / 4;
   LdsCarve cv;
   LeLds o{};
   o.f = fwd_lds(cv, s, generic);
-  o.obs = cv.take(CT); o.inv = cv.take(CT); o.lg = cv.take(CT); o.red = cv.take(8);
-  o.dred = cv.take(24);   // 12 doubles (the offset is a multiple of 4 floats: 16-byte aligned)
   const int vv = V < 1 ? 1 : (V > SLODE_EVIDENCE_MAX_V ? SLODE_EVIDENCE_MAX_V : V);
-  o.uh = cv.take(vv * (s.n_u > 0 ? s.n_u : 1)); o.prior = cv.take(vv * 3 * s.L); o.kl = cv.take(vv); o.item = cv.take(vv * SLODE_MAX_AUX);
+  o.s = scored_lds(cv, s, false, vv * SLODE_MAX_AUX, 24);
+  o.uh = cv.take(vv * (s.n_u > 0 ? s.n_u : 1)); o.prior = cv.take(vv * 3 * s.L); o.kl = cv.take(vv);
   o.ev = cv.take(vv * 4); o.bd = cv.take(vv * 2);
   // the K likelihood parts and the V x K losses come last; sizes that cannot fit anyway count as the whole budget (no overflow of the offsets)
   const long long kv = (long long)vv * (nd < 0 ? 0 : nd);
@@ -342,22 +275,19 @@ size_t slode_traj_bounds_lds_bytes(const slode_shape& s, int num_draws, int forc
 }
 
 hipError_t slode_launch_traj_bounds(const TrajBoundsLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
+  const ScoredLaunch& d = a.d;
+  const slode_shape& s = d.s;
   TbK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay); fwd_fill(k.lh, s, lay);
-  k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.nd = a.num_draws; k.t_major = a.t_major;
-  k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff;
-  k.obs = a.obs; k.sb = a.sb;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.u = a.u; k.sigtab = a.sigtab; k.bounds = a.bounds; k.loss_kb = a.loss_kb;
-  k.rng = a.rng; k.lab = a.lab; k.o = tb_lds(s, a.num_draws, fwd_generic(s, a.force_generic));
-  const size_t lds = slode_traj_bounds_lds_bytes(s, a.num_draws, a.force_generic);
-  if (lds > SLODE_TRAJ_BOUNDS_LDS_MAX || a.num_draws < 1 || a.grid < 1 || s.n_aux > SLODE_MAX_AUX) return hipErrorInvalidValue;
+  fwd_fill(k.f, s, d.lay, d.params, d.times, d.stage_t); fwd_fill(k.pr, s, d.lay); fwd_fill(k.lh, s, d.lay); fwd_fill(k.d, d);
+  k.bounds = a.bounds; k.loss_kb = a.loss_kb;
+  k.o = tb_lds(s, d.num_draws, fwd_generic(s, d.force_generic));
+  const size_t lds = slode_traj_bounds_lds_bytes(s, d.num_draws, d.force_generic);
+  if (lds > SLODE_TRAJ_BOUNDS_LDS_MAX || d.num_draws < 1 || d.grid < 1 || s.n_aux > SLODE_MAX_AUX) return hipErrorInvalidValue;
   const bool lab = s.aux_in_main && s.n_aux > 0;
-  fwd_dispatch(s, a.force_generic, [&](auto sc) {
+  fwd_dispatch(s, d.force_generic, [&](auto sc) {
     constexpr int SC = decltype(sc)::value;
-    if (lab) fwd_launch("traj_bounds", traj_bounds_kernel<SC, true>, a.grid, lds, stream, k);
-    else fwd_launch("traj_bounds", traj_bounds_kernel<SC, false>, a.grid, lds, stream, k);
+    if (lab) fwd_launch("traj_bounds", traj_bounds_kernel<SC, true>, d.grid, lds, stream, k);
+    else fwd_launch("traj_bounds", traj_bounds_kernel<SC, false>, d.grid, lds, stream, k);
   });
   return hipGetLastError();
 }
@@ -367,25 +297,21 @@ size_t slode_label_evidence_lds_bytes(const slode_shape& s, int num_draws, int V
 }
 
 hipError_t slode_launch_label_evidence(const LabelEvidenceLaunch& a, hipStream_t stream) {
-  const slode_shape& s = a.s;
-  const slode_layout& lay = a.lay;
+  const ScoredLaunch& d = a.d;
+  const slode_shape& s = d.s;
   LeK k{};
-  fwd_fill(k.f, s, lay, a.params, a.times, a.stage_t); fwd_fill(k.pr, s, lay); fwd_fill(k.lh, s, lay);
-  k.gauss = s.likelihood == SLODE_GAUSS ? 1 : 0; k.nd = a.num_draws; k.nv = a.V; k.t_major = a.t_major;
-  k.tau[0] = 0.5f; k.tau[1] = 0.5f + s.quantile_diff; k.tau[2] = 0.5f - s.quantile_diff;
-  k.obs = a.obs; k.sb = a.sb;
-  k.loc = a.loc; k.scale = a.scale; k.eps = a.eps; k.sigtab = a.sigtab; k.log_prior = a.log_prior;
-  k.evidence = a.evidence; k.loss_vkb = a.loss_vkb; k.best = a.best;
-  k.rng = a.rng; k.lab = a.lab; k.hyp = a.hyp; k.o = le_lds(s, a.num_draws, a.V, fwd_generic(s, a.force_generic));
-  const size_t lds = slode_label_evidence_lds_bytes(s, a.num_draws, a.V, a.force_generic);
-  if (lds > SLODE_LABEL_EVIDENCE_LDS_MAX || a.num_draws < 1 || a.V < 1 || a.V > SLODE_EVIDENCE_MAX_V || a.grid < 1 || s.n_aux > SLODE_MAX_AUX ||
-      a.lab.n < 1)
+  fwd_fill(k.f, s, d.lay, d.params, d.times, d.stage_t); fwd_fill(k.pr, s, d.lay); fwd_fill(k.lh, s, d.lay); fwd_fill(k.d, d);
+  k.nv = a.V; k.log_prior = a.log_prior; k.evidence = a.evidence; k.loss_vkb = a.loss_vkb; k.best = a.best; k.hyp = a.hyp;
+  k.o = le_lds(s, d.num_draws, a.V, fwd_generic(s, d.force_generic));
+  const size_t lds = slode_label_evidence_lds_bytes(s, d.num_draws, a.V, d.force_generic);
+  if (lds > SLODE_LABEL_EVIDENCE_LDS_MAX || d.num_draws < 1 || a.V < 1 || a.V > SLODE_EVIDENCE_MAX_V || d.grid < 1 || s.n_aux > SLODE_MAX_AUX ||
+      d.lab.n < 1)
     return hipErrorInvalidValue;
   const bool lab = s.aux_in_main && s.n_aux > 0;
-  fwd_dispatch(s, a.force_generic, [&](auto sc) {
+  fwd_dispatch(s, d.force_generic, [&](auto sc) {
     constexpr int SC = decltype(sc)::value;
-    if (lab) fwd_launch("label_evidence", label_evidence_kernel<SC, true>, a.grid, lds, stream, k);
-    else fwd_launch("label_evidence", label_evidence_kernel<SC, false>, a.grid, lds, stream, k);
+    if (lab) fwd_launch("label_evidence", label_evidence_kernel<SC, true>, d.grid, lds, stream, k);
+    else fwd_launch("label_evidence", label_evidence_kernel<SC, false>, d.grid, lds, stream, k);
   });
   return hipGetLastError();
 }

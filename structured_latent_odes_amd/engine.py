@@ -587,13 +587,34 @@ class Engine:
     # ---- cohort curves: the draws of recon_moments reduced by cohort -------------------------------------------------------------
     COHORT_OUTPUTS = ("sd", "sd_subjects", "obs_mean", "l1")
 
+    def _plan4(self, fn, B: int, M: int, G: int, num_samples: int, chunk: int):
+        """A plan entry point of the cohort calls: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes)."""
+        r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        _check(self.lib, None, fn(C.byref(self.shape(B)), int(M), int(G), int(num_samples), int(chunk), C.byref(r), C.byref(n), C.byref(lds),
+                                  C.byref(scr)))
+        return int(r.value), int(n.value), int(lds.value), int(scr.value)
+
+    def _cohort_index(self, members, offsets, G):
+        """The checks of the cohort index of ``cohort_moments`` / ``calibration``: (M, G)."""
+        for name, t in (("members", members), ("offsets", offsets)):
+            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("%s must be a contiguous 1-d int32 tensor on %s" % (name, self.device))
+        M, G = members.numel(), int(G)
+        if offsets.numel() != G + 1:
+            raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
+        return M, G
+
+    def _mask_like_obs(self, mask, batch: L.Batch, B: int):
+        """The mask of ``posterior_refine`` / ``pointwise_density``: None, or float32 with the shape and the strides of the observations."""
+        if mask is not None:
+            self._f32(mask, "mask", contiguous=False)
+            if tuple(mask.shape) != (B, self.spec.n_channels, self.T) or tuple(mask.stride()) != tuple(batch.obs_strides[i] for i in range(3)):
+                raise ValueError("mask must have the shape and the strides of the observations")
+
     def cohort_plan(self, B: int, M: int, G: int, num_samples: int, chunk: int = 0):
         """``slode_cohort_plan``: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes) of ``cohort_moments`` for
         these sizes; host arithmetic only."""
-        r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_cohort_plan(C.byref(self.shape(B)), int(M), int(G), int(num_samples), int(chunk), C.byref(r),
-                                                          C.byref(n), C.byref(lds), C.byref(scr)))
-        return int(r.value), int(n.value), int(lds.value), int(scr.value)
+        return self._plan4(self.lib.slode_cohort_plan, B, M, G, num_samples, chunk)
 
     def cohort_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, members, offsets, G: int, chunk: int = 0,
                        clip_min=None, mean=None, sd=None, sd_subjects=None, obs_mean=None, l1=None, outputs=COHORT_OUTPUTS, scratch=None):
@@ -606,12 +627,7 @@ class Engine:
         tensor of at least the plan's scratch bytes (allocated when None).  Enqueued on the current stream.  Raises SlodeError naming the
         reason for what the kernel does not take (everything ``recon_moments`` refuses; sizes out of range; obs_mean / l1 without dense
         observations; LDS budget): nothing is launched and no draw is consumed then."""
-        for name, t in (("members", members), ("offsets", offsets)):
-            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError("%s must be a contiguous 1-d int32 tensor on %s" % (name, self.device))
-        M, G = members.numel(), int(G)
-        if offsets.numel() != G + 1:
-            raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
+        M, G = self._cohort_index(members, offsets, G)
         shp = self._head_shape(G)
         mean = self._out(mean, "mean", shp)
         if sd is not None or "sd" in outputs:
@@ -635,10 +651,7 @@ class Engine:
     def calibration_plan(self, B: int, M: int, G: int, num_samples: int, chunk: int = 0):
         """``slode_calibration_plan``: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes) of ``calibration`` for
         these sizes; host arithmetic only, the chunk rule of ``cohort_plan``."""
-        r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_calibration_plan(C.byref(self.shape(B)), int(M), int(G), int(num_samples), int(chunk), C.byref(r),
-                                                               C.byref(n), C.byref(lds), C.byref(scr)))
-        return int(r.value), int(n.value), int(lds.value), int(scr.value)
+        return self._plan4(self.lib.slode_calibration_plan, B, M, G, num_samples, chunk)
 
     def _out_i32(self, t, name: str, shp):
         """An int32 output tensor of an eval-side call, allocated when None."""
@@ -656,12 +669,7 @@ class Engine:
         [G, C], float32.  ``members`` / ``offsets`` / ``chunk`` / ``scratch`` as ``cohort_moments``; ``outputs`` names the optional outputs
         to produce.  Enqueued on the current stream.  Raises SlodeError naming the reason for what the kernel does not take (everything
         ``cohort_moments`` refuses; no observations; LDS budget): nothing is launched and no draw is consumed then."""
-        for name, t in (("members", members), ("offsets", offsets)):
-            if t.device != self.device or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
-                raise ValueError("%s must be a contiguous 1-d int32 tensor on %s" % (name, self.device))
-        M, G = members.numel(), int(G)
-        if offsets.numel() != G + 1:
-            raise ValueError("offsets must have G + 1 = %d entries, got %d" % (G + 1, offsets.numel()))
+        M, G = self._cohort_index(members, offsets, G)
         Cn, T = self._head_shape(G)[2:]
         below = self._out_i32(below, "below", (3, G, Cn, T))
         if inside is not None or "inside" in outputs:
@@ -741,10 +749,7 @@ class Engine:
         refuses; num_steps < 0; lr not finite and positive; a family whose main loss scores the labels: proc; LDS budget): nothing is
         launched and no draw is consumed then; there is no composed fallback."""
         K, J, Ld = int(num_draws), int(num_steps), self.spec.latent_dim
-        if mask is not None:
-            self._f32(mask, "mask", contiguous=False)
-            if tuple(mask.shape) != (B, self.spec.n_channels, self.T) or tuple(mask.stride()) != tuple(batch.obs_strides[i] for i in range(3)):
-                raise ValueError("mask must have the shape and the strides of the observations")
+        self._mask_like_obs(mask, batch, B)
         loc, scale = self._out(loc, "loc", (B, Ld)), self._out(scale, "scale", (B, Ld))
         elbo = self._out(elbo, "elbo", (B, 2))
         grad0 = None if grad0 is False else self._out(grad0, "grad0", (B, 2 * Ld))
@@ -777,10 +782,7 @@ class Engine:
         refuses; weights outside {0, 1}; one of loc / scale alone; loss_kb in posterior mode; LDS budget): nothing is launched and no draw
         is consumed then; there is no composed fallback."""
         K, Ld, Cn = int(num_draws), self.spec.latent_dim, self.spec.n_channels
-        if mask is not None:
-            self._f32(mask, "mask", contiguous=False)
-            if tuple(mask.shape) != (B, Cn, self.T) or tuple(mask.stride()) != tuple(batch.obs_strides[i] for i in range(3)):
-                raise ValueError("mask must have the shape and the strides of the observations")
+        self._mask_like_obs(mask, batch, B)
         for name, t in (("loc", loc), ("scale", scale)):
             if t is not None and tuple(self._f32(t, name).shape) != (B, Ld):
                 raise ValueError("%s must be [%d, %d], got %s" % (name, B, Ld, tuple(t.shape)))

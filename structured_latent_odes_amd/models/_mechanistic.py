@@ -914,9 +914,7 @@ class MechanisticBase(nn.Module):
         b = self._bind()
         B, K = observations.shape[0], self._count(num_draws, "num_draws")
         if mask is not None:    # the engine takes the weights in the observations' own layout
-            m = torch.as_tensor(mask, device=observations.device).to(torch.float32).expand(observations.shape)
-            mask = torch.empty_strided(observations.shape, observations.stride(), dtype=torch.float32, device=observations.device)
-            mask.copy_(m)
+            mask = self._obs_layout(observations, mask)
         loc, scale, elbo, grad0, trace, best = b.engine.posterior_refine(
             b.flat, self._draws_batch(observations, labels, eps, K), B, K, int(num_steps), lr, mask=mask,
             grad0=None if return_trace else False, trace=None if return_trace else False)

@@ -1,5 +1,5 @@
-"""What the GPU tests of the six eval-side calls (test_gpu_eval_stats, test_gpu_recon_moments, test_gpu_traj_bounds, test_gpu_intervene,
-test_gpu_forecast, test_gpu_cohort) share: an engine for a seeded case (tests/eval_stats_util.py) with the handle's environment switches
+"""What the GPU tests of the ten eval-side calls (test_gpu_eval_stats, test_gpu_recon_moments, test_gpu_intervene, test_gpu_forecast,
+test_gpu_cohort, test_gpu_calibration, test_gpu_traj_bounds, test_gpu_label_evidence, test_gpu_refine, test_gpu_pointwise) share: an engine for a seeded case (tests/eval_stats_util.py) with the handle's environment switches
 under control, the case's batch on the device, the model of the model-level tests with its 17-trajectory batch, and the checks every call
 gets: refusal, capture and replay, peak allocation.  A plain module: not a conftest, not imported by the product."""
 import importlib
@@ -45,6 +45,11 @@ def _device_batch(c):
         labels.append(c["u"][:, o:o + w].contiguous().to(DEV))
         o += w
     return obs_d, labels
+
+
+def _lay(t, t_major):
+    """A host [B, C, T] tensor on the device in one of the two dense layouts: the [B,C,T] view of a contiguous [B,T,C] tensor, or contiguous."""
+    return t.permute(0, 2, 1).contiguous().to(DEV).permute(0, 2, 1) if t_major else t.to(DEV).contiguous()
 
 
 def _eps_dev(eps):

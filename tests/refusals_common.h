@@ -1,4 +1,5 @@
-// What the refusal programs (tests/eval_refusals, tests/forecast_refusals, tests/cohort_refusals) share.  Each calls entry points of
+// What the seven refusal programs (tests/eval_refusals, forecast_refusals, cohort_refusals, calibration_refusals, evidence_refusals,
+// refine_refusals, pointwise_refusals) share.  Each calls entry points of
 // libslode.so in every refusing configuration on a hand-filled handle -- no slode_create, no HIP call, no device -- and prints one line
 // per case:
 //   <case> | [<call> |] <status> | <rng_counter afterwards> | <slode_last_error>

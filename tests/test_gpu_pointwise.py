@@ -12,7 +12,8 @@ import torch
 from tests import eval_stats_util as EU
 from tests import pointwise_util as PU
 from tests import traj_bounds_util as TU
-from tests.eval_gpu_util import ADAPTIVE, _captured, _device_batch, _engine, _model, _padded, _refused
+from tests import refine_util as RU
+from tests.eval_gpu_util import ADAPTIVE, _captured, _device_batch, _engine, _lay, _model, _padded, _refused
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -21,7 +22,7 @@ POST, IMP = 0, 1
 
 def _like_obs(c, t):
     """A host [B, C, T] tensor on the device in the layout (the strides) of the case's observations (``_device_batch``)."""
-    return t.to(DEV).contiguous() if c["fam"] == "proc" else t.permute(0, 2, 1).contiguous().to(DEV).permute(0, 2, 1)
+    return _lay(t, c["fam"] != "proc")
 
 
 def _pw(eng, flat, c, weights, eps="case", K=None, obs_d=None, labels=None, mask=None, loc=None, scale=None, particles=1):
@@ -151,6 +152,25 @@ def test_mask(case):
     print("%s prefix mask: masked loss_kb error / bar %.3f" % (case, rl.max()))
     assert rl.max() <= 1.0 and not torch.equal(imp[2], _pw(eng, flat, c, IMP, obs_d=obs_d, labels=labels)[2])
     PU.check(imp[0], imp[1], want, PU.log_weights(4, B, loss), case + " prefix mask, importance", mask=mask.numpy())
+
+
+@pytest.mark.parametrize("t_major", [True, False], ids=["BTC", "BCT"])
+@pytest.mark.parametrize("case", ["cvs_ald", "challenge_gauss"])
+def test_masked_tie_to_posterior_refine(case, t_major):
+    """A prefix mask, explicit noise, B = 5, K = 3 (the sizes of tests/refine_util.py), both dense layouts: the -ELBO of posterior_refine at
+    J = 0 is bitwise the mean of the importance sweep's masked loss_kb -- both kernels execute one weighted log-likelihood routine
+    (tb_loglik_weighted) inside one draw frame.  An fp64 sum of three fp32 values is exact, so the order of the sum does not enter."""
+    c = RU.build(case)
+    B, K = c["B"], c["K"]
+    eng = _engine(c)
+    flat = eng.pack(c["p"])
+    w = _lay(RU.prefix_mask(c), t_major)
+    bt = eng.make_batch(_lay(c["obs"], t_major), _device_batch(c)[1], c["eps"].to(DEV).contiguous(), particles=K)
+    elbo = eng.posterior_refine(flat, bt, B, K, 0, mask=w, grad0=False, trace=False, best_step=False)[2]
+    loss = eng.pointwise_density(flat, bt, B, K, IMP, mask=w)[2]
+    want = (loss.double().sum(0) / K).float()
+    print("%s %s: largest |elbo0 - mean masked loss_kb| = %.3e" % (case, "BTC" if t_major else "BCT", (elbo[:, 0] - want).abs().max().item()))
+    assert torch.isfinite(want).all() and torch.equal(elbo[:, 0], want)
 
 
 def test_posterior_input():

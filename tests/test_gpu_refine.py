@@ -9,17 +9,12 @@ import pytest
 import torch
 
 from tests import refine_util as RU
-from tests.eval_gpu_util import _device_batch, _engine, _model, _refused
+from tests.eval_gpu_util import _device_batch, _engine, _lay, _model, _refused
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 CONFIGS = [(case, solver) for case in RU.CASES for solver in RU.SOLVERS]
 NAMES = ("loc", "scale", "elbo", "grad0", "trace", "best_step")
-
-
-def _lay(t, t_major):
-    """A host [B, C, T] tensor on the device in one of the two dense layouts: the [B,C,T] view of a contiguous [B,T,C] tensor, or contiguous."""
-    return t.permute(0, 2, 1).contiguous().to(DEV).permute(0, 2, 1) if t_major else t.to(DEV).contiguous()
 
 
 def _refine(eng, flat, c, J, eps="case", K=None, lr=RU.LR, w=None, t_major=True):
