@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 230 /* 0.2.3: slode_pointwise_density, slode_pointwise_plan (0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 240 /* 0.2.4: slode_latent_attribution, slode_attribution_plan (0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -44,6 +44,7 @@ extern "C" {
 #define SLODE_COHORT_MAX_CHUNK 64 /* most members one workgroup folds into one partial */
 #define SLODE_CALIBRATION_PHI2 0.97724986805182079f  /* Phi(2): the nominal level of mean + 2 s */
 #define SLODE_CALIBRATION_PHIM2 0.022750131948179195f /* Phi(-2): of mean - 2 s */
+#define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -535,6 +536,53 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
                             float* eff_mean /* [Q,B,C,T] or NULL */, float* eff_sd /* [Q,B,C,T] or NULL */, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- latent attribution as ONE call: per-block variance shares of the curves (no reference counterpart: the reference's latent is split into
+ * blocks tied to the labels -- the conditional prior groups -- and the subject's own rest, z_epsilon; the structure itself asks how much of the
+ * variation of a subject's curves comes from which block, at which channel and time) ----
+ * Both q(z | x) and p(z | u) are diagonal Gaussians, so the blocks are independent and the variance of a curve decomposes over them (Sobol /
+ * ANOVA).  The estimator is pick-freeze: redraw one set of blocks on fresh noise, keep the others, average the squared paired difference.
+ *   Blocks: bit g < n_groups of a mask is prior group g of the shape (slode_shape::groups); bit n_groups is the REST block, every latent dim
+ *   that no group covers.
+ *   Draws: the source is that of slode_recon_moments on the same side -- is_post: loc / scale from the encoder; else the conditional prior nets on
+ *   the batch's labels and N(0, 1) on the rest.  For trajectory b and draw k there are TWO noise rows, e (base) and e' (fresh):
+ *     base    z[l]   = loc[l] + scale[l] e[l]
+ *     arm a   z_a[l] = loc[l] + scale[l] (l in a block of arm_masks[a] ? e'[l] : e[l])
+ *   Every latent goes through the same fixed-grid solve and decoder heads.  For every head value (q, c, t):
+ *   mean, sd  mean and POPULATION sd (divisor num_samples) of the base curve: the quantity of slode_recon_moments, accumulated the same way;
+ *             either may be NULL
+ *   msd[a]    1 / (2 num_samples) sum_k (v_a,k - v_k)^2, the Jansen estimator.  A single block g in the mask: the block's TOTAL-EFFECT variance
+ *             E[Var(f | z_~g)].  Every block but g in the mask: sd^2 - msd estimates the block's FIRST-ORDER variance Var(E[f | z_g]) (estimator
+ *             noise can make it negative or larger than the total effect).  Every block in the mask: an independent estimate of sd^2.
+ *   mean, sd [Q, B, C, T], msd [n_arms, Q, B, C, T] (T contiguous) in the head order of slode_recon_moments (ALD: mu_50, mu_75, mu_25; Gauss:
+ *   mean).  arm_masks[a] == 0 is accepted and gives exactly 0: the arm runs the base's instructions on the base's z.  Nothing sized num_samples x
+ *   B x C x T is written anywhere: one workgroup walks the draws of its trajectory through the base and the arms and keeps the base moments, the
+ *   base values of the current draw and one sum of squares per arm on chip.
+ *   arm_masks: a HOST array [n_arms] (copied into the kernel arguments at the call; not read afterwards).
+ *   Noise: batch->eps == NULL: the base rows come from drawing call n of the handle's generator (row k * B + b, plus first_trajectory: exactly
+ *   slode_recon_moments' draw), the fresh rows from drawing call n + 1 at the same row; the counter is left at n + 2.  batch->eps != NULL: one dense
+ *   [2, num_samples, B, L] tensor, base then fresh.  The result is a function of (parameters, inputs, labels, noise, the arm's own mask) alone:
+ *   independent of the grid, of where the noise comes from and of which other arms are in the call, bitwise reproducible from run to run (every
+ *   value has one owner thread, which takes the draws in the order k = 0 .. num_samples - 1; no atomics).
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Posterior: three launches ("weff", "enc_fwd2", "latent_attribution"
+ * in slode_profile_read) on one stream; prior: "latent_attribution" alone.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments on that side
+ * but its LDS rung -- a NULL handle (before anything else); num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver
+ * (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; for the posterior,
+ * batch->obs NULL, observation strides the folded encoder path does not take or SLODE_NO_FOLD; for the prior, no label tensors -- and: n_arms
+ * outside [1, SLODE_ATTRIBUTION_MAX_ARMS]; arm_masks or msd NULL; a mask with bits beyond n_groups; the rest bit set when the groups cover all L
+ * dims; LDS tables (step table 2 (T - 1) S, base moments 3 Q C T, base values Q C T, arm sums n_arms Q C T, staged weights, 2 L; every piece a
+ * multiple of 16 B) beyond the budget of 160 KiB, naming n_arms with the figure of slode_attribution_plan. */
+
+/* The dynamic LDS bytes of slode_latent_attribution's kernel for (shape, n_arms): pure host arithmetic -- no handle, no HIP call, works on a machine
+ * without a GPU.  SLODE_EINVAL (the reason is the global text slode_last_error(NULL)) for a bad shape, n_arms outside
+ * [1, SLODE_ATTRIBUTION_MAX_ARMS] or tables beyond the budget (*lds_bytes is still written then, so a caller can split its arms over calls). */
+int slode_attribution_plan(const slode_shape* s, int n_arms, size_t* lds_bytes);
+int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                             const float* stage_t, const slode_batch* batch, int is_post, int num_samples,
+                             const unsigned int* arm_masks /* HOST array [n_arms], copied into the kernel arguments */, int n_arms,
+                             float* mean /* [Q,B,C,T] or NULL */, float* sd /* [Q,B,C,T] or NULL */,
+                             float* msd /* [n_arms,Q,B,C,T] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- forecast: the posterior (or prior) curves of a trained model on ANY output grid as ONE call (no reference counterpart: the reference solves
  * on the training grid alone; what one asks of a latent ODE first is what this subject's curves look like after the observed window, or on a
  * finer grid) ------------------------------------------------------------------------------------------------------------------------------------
@@ -741,11 +789,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -870,6 +870,7 @@ struct EvalCall {
   const char* lds_tables = nullptr;      // what the LDS figure counts, and the advice that ends that refusal (eval_lds)
   const char* lds_advice = nullptr;
   bool lds_per_draw = false;             // the LDS figure grows with the draw count: the refusal names it
+  const char* lds_extra = nullptr;       // another size the LDS figure grows with, as the refusal names it (", n_arms = 6")
 };
 // The shared refusal ladder, in this order.  First: handle, shape, layout, params; the call's own pointers ...
 static int eval_args(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const EvalCall& d) {
@@ -903,6 +904,7 @@ static int eval_lds(slode_handle h, const slode_shape* s, const EvalCall& d, siz
   if (lds <= (size_t)budget) return SLODE_OK;
   char per_draw[48] = "";
   if (d.lds_per_draw) snprintf(per_draw, sizeof(per_draw), ", %s = %d", d.draws_noun, d.draws);
+  else if (d.lds_extra) snprintf(per_draw, sizeof(per_draw), "%s", d.lds_extra);
   return fail(h, SLODE_EINVAL, "%s: the LDS tables of T = %d, S = %d, C = %d%s (%zu B: %s) exceed the budget of %d B; %s", d.name, s->T, s->S,
               s->C, per_draw, lds, d.lds_tables, budget, d.lds_advice);
 }
@@ -973,7 +975,8 @@ static void draws_fill(DrawsLaunch& a, slode_handle h, const slode_shape* s, con
 }
 // The tail: launch(stream) runs the call's own kernel(s) on a.  The prior: no observations, no encoder launches, nothing of the workspace but
 // its size.  The posterior: the fold + encoder launches of a forward-only step on the training grid times / stage_t, which leave loc /
-// scale in the workspace.  Either way the one drawing call is counted once nothing can refuse the call any more.
+// scale in the workspace.  Either way the call's drawing calls (a.rng_calls: one; latent_attribution: two) are counted once nothing can refuse
+// the call any more.
 extern "C++" template <class Launch>
 static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* lay, const EvalCall& d, DrawsLaunch& a, const float* times,
                      const float* stage_t, const slode_batch* batch, void* workspace, size_t workspace_bytes, void* stream, Launch&& launch) {
@@ -983,7 +986,7 @@ static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* l
   };
   if (!a.is_post) {
     if (workspace_bytes < slode_workspace_bytes(h, s)) return fail(h, SLODE_ENOSPC, "workspace %zu B < required %zu B", workspace_bytes, slode_workspace_bytes(h, s));
-    a.rng = take_draws(h, batch->eps, 1);
+    a.rng = take_draws(h, batch->eps, a.rng_calls);
     ClockScope clock_scope(h, true);
     return run((hipStream_t)stream);
   }
@@ -993,7 +996,7 @@ static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* l
   if (rc != SLODE_OK) return rc;
   a.loc = p.w.loc; a.scale = p.w.scale;
   ClockScope clock_scope(h, true);
-  if ((rc = forward_encode(p, 1, &a.rng)) != SLODE_OK) return rc;
+  if ((rc = forward_encode(p, a.rng_calls, &a.rng)) != SLODE_OK) return rc;
   return run(c.stream);
 }
 
@@ -1232,6 +1235,69 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
   a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd; a.group_mask = group_mask;
   return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
                    [&](hipStream_t st) { return slode_launch_intervene_moments(a, st); });
+}
+
+// ---- latent attribution: the draws of slode_recon_moments, every block of the latent redrawn in turn on a second noise row (include/slode.h) ----
+// the blocks of a shape: its prior groups, and the rest block (bit n_groups) when some latent dim lies in no group
+static bool attribution_has_rest(const slode_shape* s) {
+  for (int l = 0; l < s->L; ++l) {
+    bool in = false;
+    for (int g = 0; g < s->n_groups; ++g) in = in || (l >= s->groups[g].z_off && l < s->groups[g].z_off + s->groups[g].z_dim);
+    if (!in) return true;
+  }
+  return false;
+}
+
+// The LDS bytes of slode_latent_attribution for a shape and an arm count (host arithmetic only; the compiled state dims, no
+// SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
+int slode_attribution_plan(const slode_shape* s, int n_arms, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: %s", bad);
+  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: lds_bytes is NULL");
+  if (n_arms < 1 || n_arms > SLODE_ATTRIBUTION_MAX_ARMS)
+    return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: n_arms = %d out of range [1, %d]", n_arms, SLODE_ATTRIBUTION_MAX_ARMS);
+  *lds_bytes = slode_attribution_lds_bytes(*s, n_arms, 0);
+  if (*lds_bytes > SLODE_ATTRIBUTION_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: the LDS tables of T = %d, S = %d, C = %d, n_arms = %d (%zu B) exceed the budget of %d B",
+                s->T, s->S, s->C, n_arms, *lds_bytes, SLODE_ATTRIBUTION_LDS_MAX);
+  return SLODE_OK;
+}
+
+// Per-block variance shares of the head curves from pick-freeze draws (include/slode.h): refusals first -- slode_recon_moments' for the same
+// is_post without its LDS rung, then the call's own; nothing launched, no draw consumed -- then slode_recon_moments' launches with the
+// attribution kernel in place of its own, and two drawing calls (base, fresh) in place of one.
+int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                             const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const unsigned int* arm_masks,
+                             int n_arms, float* mean, float* sd, float* msd, void* workspace, size_t workspace_bytes, void* stream) {
+  DrawsCall d("slode_latent_attribution", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+              "reduce the attribution samples instead", nullptr);
+  char arms[32];
+  snprintf(arms, sizeof(arms), ", n_arms = %d", n_arms);
+  d.lds_tables = "step table, base moments, base values, arm sums, staged weights"; d.lds_advice = "fewer arms per call fit (slode_attribution_plan)";
+  d.lds_extra = arms;
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (n_arms < 1 || n_arms > SLODE_ATTRIBUTION_MAX_ARMS)
+    return fail(h, SLODE_EINVAL, "slode_latent_attribution: n_arms = %d out of range [1, %d]", n_arms, SLODE_ATTRIBUTION_MAX_ARMS);
+  if (!arm_masks || !msd) return fail(h, SLODE_EINVAL, "slode_latent_attribution: arm_masks / msd is NULL");
+  const bool rest = attribution_has_rest(s);
+  for (int a = 0; a < n_arms; ++a) {
+    if ((arm_masks[a] >> (s->n_groups + 1)) != 0)
+      return fail(h, SLODE_EINVAL, "slode_latent_attribution: arm_masks[%d] = 0x%x has bits beyond n_groups = %d (bit n_groups: the rest block)", a,
+                  arm_masks[a], s->n_groups);
+    if (!rest && ((arm_masks[a] >> s->n_groups) & 1u))
+      return fail(h, SLODE_EINVAL, "slode_latent_attribution: arm_masks[%d] = 0x%x names the rest block, but the %d prior groups cover all L = %d latent dims",
+                  a, arm_masks[a], s->n_groups, s->L);
+  }
+  if ((rc = eval_lds(h, s, d, slode_attribution_lds_bytes(*s, n_arms, h->ode_generic), SLODE_ATTRIBUTION_LDS_MAX)) != SLODE_OK) return rc;
+  AttributionLaunch a{};
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
+  a.d.rng_calls = 2;
+  a.mean = mean; a.sd = sd; a.msd = msd; a.n_arms = n_arms;
+  for (int i = 0; i < n_arms; ++i) a.masks[i] = arm_masks[i];
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_attribution(a, st); });
 }
 
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----

@@ -550,7 +550,7 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort; intervene: the posterior
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution; intervene: the posterior
 // alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
 // row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
 struct DrawsLaunch {
@@ -558,6 +558,7 @@ struct DrawsLaunch {
   slode_layout lay;
   const float *params, *times, *stage_t, *loc, *scale, *eps, *u;
   int num_samples, grid, is_post, force_generic;
+  int rng_calls = 1;   // drawing calls of the generator the call consumes (latent_attribution: 2, base and fresh)
   RngK rng{};
   LabelSrc lab{};
 };
@@ -653,6 +654,20 @@ struct InterveneMomentsLaunch {
 #define SLODE_INTERVENE_MOMENTS_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moments, factual values, staged weights) must fit
 hipError_t slode_launch_intervene_moments(const InterveneMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_intervene_moments_lds_bytes(const slode_shape& s, int force_generic);
+
+// Latent attribution (attribution_kernel.hip; slode_latent_attribution): over the pick-freeze draws of d per trajectory (two noise rows per
+// draw: rng.on: row k * B + b of drawing calls n and n + 1; else eps [2, num_samples, B, L], base then fresh), mean / sd [Q, B, C, T] of the
+// base curve (either may be NULL) and msd [n_arms, Q, B, C, T], half the mean squared paired difference of arm a (the blocks of masks[a]
+// redrawn on the fresh row) to the base.
+struct AttributionLaunch {
+  DrawsLaunch d;
+  float *mean, *sd, *msd;
+  unsigned int masks[SLODE_ATTRIBUTION_MAX_ARMS];
+  int n_arms;
+};
+#define SLODE_ATTRIBUTION_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, base moments, base values, arm sums, staged weights) must fit
+hipError_t slode_launch_attribution(const AttributionLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
+size_t slode_attribution_lds_bytes(const slode_shape& s, int n_arms, int force_generic);
 
 // Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
 // from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]

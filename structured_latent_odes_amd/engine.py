@@ -444,10 +444,11 @@ class Engine:
         return loss_out
 
     # ---- SVI.step(**batch) as one call: labels as the loader yields them, noise drawn in the kernels -----------------------------
-    def make_batch(self, obs, labels, eps=None, particles: int = 1) -> L.Batch:
+    def make_batch(self, obs, labels, eps=None, particles: int = 1, eps_shape=None) -> L.Batch:
         """slode_batch for `obs` [B, C, T] (any strides) and the label tensors in the model's concatenation order (each [B, width] or [B],
         float32, contiguous, on the device).  eps [B, L] ([particles, B, L] for particles > 1) or None (None: drawn in-kernel from the
-        handle's Philox stream, rng_seed: particle k is drawing call n + k).
+        handle's Philox stream, rng_seed: particle k is drawing call n + k).  ``eps_shape``: the shape a call with a noise tensor of its own
+        form expects instead (``latent_attribution``: [2, num_samples, B, L]); None: the shapes above.
         The batch carries raw device pointers; it also holds the tensors they point at (``tensors``), so a label tensor converted just
         for this batch lives until the batch does -- until the step that reads it is enqueued."""
         B = obs.shape[0]
@@ -472,8 +473,9 @@ class Engine:
         bt.n_labels = len(labels)
         if eps is not None:
             self._f32(eps, "eps")
-            if tuple(eps.shape) != self._eps_shape(B, int(particles)):
-                raise ValueError("eps must be %s, got %s" % (list(self._eps_shape(B, int(particles))), tuple(eps.shape)))
+            want = self._eps_shape(B, int(particles)) if eps_shape is None else tuple(int(n) for n in eps_shape)
+            if tuple(eps.shape) != want:
+                raise ValueError("eps must be %s, got %s" % (list(want), tuple(eps.shape)))
             bt.eps = eps.data_ptr()
         bt.tensors = (obs, *labels, eps)
         return bt
@@ -835,6 +837,43 @@ class Engine:
         self._batch_call(self.lib.slode_intervene_moments, params, batch, B, particles, ptrs, int(group_mask), int(num_samples),
                          *(self._p(t) for t in outs))
         return tuple(outs)
+
+    # ---- latent attribution: per-block variance shares of the curves from pick-freeze draws -------------------------------------------
+    def attribution_blocks(self) -> int:
+        """The number of latent blocks of the spec: its prior groups, plus the rest block (bit ``len(prior_groups)`` of a mask) when some
+        latent dim lies in no group."""
+        sp = self.spec
+        covered = sum(g.z_dim for g in sp.prior_groups)
+        return len(sp.prior_groups) + (1 if covered < sp.latent_dim else 0)
+
+    def attribution_plan(self, B: int, n_arms: int) -> int:
+        """``slode_attribution_plan``: the dynamic LDS bytes of ``latent_attribution`` for this shape and ``n_arms`` arms (host arithmetic
+        only; raises SlodeError where the call would refuse them at its LDS rung, or for n_arms outside [1, L.ATTRIBUTION_MAX_ARMS])."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_attribution_plan(C.byref(self.shape(B)), int(n_arms), C.byref(r)))
+        return int(r.value)
+
+    def latent_attribution(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, arm_masks, mean=None, sd=None, msd=None,
+                           particles: int = 1):
+        """slode_latent_attribution: pick-freeze draws per trajectory -- the base draw of ``recon_moments`` on the same side, and per arm a
+        the same draw with the latent blocks of ``arm_masks[a]`` redrawn on a second noise row (bit g: prior group g of the spec; bit
+        ``len(prior_groups)``: the rest dims no group covers).  Returns ``(mean, sd, msd)``: mean / population sd of the base curve, float32
+        [Q, B, C, T] each in the head order of ``recon_moments`` (either passed as False is not computed: None in its place), and ``msd``
+        float32 [n_arms, Q, B, C, T] = 1 / (2 num_samples) sum_k (v_a,k - v_k)^2 (a mask of 0 gives exactly 0); enqueued on the current
+        stream, nothing sized num_samples x B x C x T exists anywhere.  The batch's eps is [2, num_samples, B, L] (base, then fresh:
+        ``make_batch(..., eps_shape=...)``) or None (drawing calls n and n + 1 of the generator, row k * B + b each; the counter moves by
+        two).  Raises SlodeError naming the reason for what the kernel does not take (everything ``recon_moments`` refuses on that side;
+        n_arms outside [1, L.ATTRIBUTION_MAX_ARMS]; mask bits beyond the blocks; LDS budget): nothing is launched and no draw is consumed
+        then."""
+        masks = [int(m) for m in arm_masks]
+        A = len(masks)
+        shp = self._head_shape(B)
+        mean, sd = (None if t is False else self._out(t, name, shp) for t, name in ((mean, "mean"), (sd, "sd")))
+        msd = self._out(msd, "msd", (max(A, 0),) + tuple(shp))
+        arr = (C.c_uint * max(A, 1))(*[m & 0xFFFFFFFF for m in masks])
+        self._batch_call(self.lib.slode_latent_attribution, params, batch, B, particles, 1 if is_post else 0, int(num_samples), arr, A,
+                         self._p(mean), self._p(sd), self._p(msd))
+        return mean, sd, msd
 
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:

@@ -849,6 +849,171 @@ class MechanisticBase(nn.Module):
         return self._save_arrays(results_dir, (("%s_%s_%s_sample_%s.npy" % (name, arm, tag, kind), val) for name, arms in res.items()
                                                for arm in ("cf", "effect") for kind, val in zip(("mean", "sd"), arms[arm])))
 
+    # ---- latent attribution: how much of the variance of the curves comes from which latent block (pick-freeze / Jansen) ----------------
+    ATTRIBUTION_ARMS_PER_CALL = None      # most arms of one engine call; None: what the engine's plan says fits the LDS (at most 16)
+
+    def attribution_blocks(self):
+        """The latent blocks of the family by name, in bit order: every conditional-prior group (its latent groups joined by '+': ``iext``,
+        ``rtpr``; ``shedding+symptoms``; ``aR+aS+C12+C6``), then ``epsilon`` -- the dims no prior group covers -- when there are any."""
+        names = ["+".join(zg) for _, _, zg in self.PRIORS]
+        if sum(self.z_dims[z] for _, _, zg in self.PRIORS for z in zg) < self.latent_dim:
+            names.append("epsilon")
+        return names
+
+    def _block_dims(self, mask):
+        """bool ``[L]``: the latent dims of the blocks in ``mask`` (bit order of ``attribution_blocks``)."""
+        sel = torch.zeros(self.latent_dim, dtype=torch.bool)
+        rest = torch.ones(self.latent_dim, dtype=torch.bool)
+        for g, (_, _, zg) in enumerate(self.PRIORS):
+            lo = self.z_off[zg[0]]
+            hi = lo + sum(self.z_dims[z] for z in zg)
+            rest[lo:hi] = False
+            if (mask >> g) & 1:
+                sel[lo:hi] = True
+        return sel | rest if (mask >> len(self.PRIORS)) & 1 else sel
+
+    def _attribution_arms(self, blocks):
+        """``(blocks, masks, single, complement)``: the deduplicated arm masks of ``blocks`` (None: all of them) -- each single block, and
+        every block of the family but that one -- and per block the index of its two arms in ``masks``."""
+        known = self.attribution_blocks()
+        blocks = list(known) if blocks is None else list(blocks)
+        for name in blocks:
+            if name not in known:
+                raise ValueError("blocks: %r is not a latent block of the %s family (blocks: %s)" % (name, self.FAMILY, ", ".join(known)))
+        if not blocks:
+            raise ValueError("blocks names no latent block (blocks: %s)" % ", ".join(known))
+        every = (1 << len(known)) - 1
+        masks, single, comp = [], [], []
+        for name in blocks:
+            bit = 1 << known.index(name)
+            for m, idx in ((bit, single), (every ^ bit, comp)):
+                if m not in masks:
+                    masks.append(m)
+                idx.append(masks.index(m))
+        return blocks, masks, single, comp
+
+    def _attribution_result(self, blocks, single, comp, mean, var, msd):
+        """The dict of ``latent_attribution`` from mean / var ``[Q, B, C, T]`` and msd ``[A, Q, B, C, T]``."""
+        res = {"blocks": list(blocks)}
+        for q, n in enumerate(self.MOMENT_HEADS[bool(self.GAUSS)]):
+            total = torch.stack([msd[a][q] for a in single], 0)
+            first = torch.stack([var[q] - msd[a][q] for a in comp], 0)
+            den = var[q].double().sum(-1)
+            den = torch.where(den == 0, torch.full_like(den, float("nan")), den)
+            res[n] = {"mean": mean[q].to(torch.float32), "var": var[q].to(torch.float32), "total": total.to(torch.float32),
+                      "first": first.to(torch.float32), "total_index": total.double().sum(-1) / den, "first_index": first.double().sum(-1) / den}
+        return res
+
+    def latent_attribution(self, observations, is_post, num_samples: int, blocks=None, eps=None, **labels):
+        """How much of the variation of a subject's curves comes from which latent block, at which channel and time: the variance
+        (Sobol / ANOVA) decomposition of every head curve over the independent blocks of the latent -- the conditional-prior groups and
+        ``epsilon`` (``attribution_blocks``) -- under the posterior q(z | x) (``is_post``) or the conditional prior p(z | labels), estimated
+        by pick-freeze over ``num_samples`` draws: a base draw z = loc + scale e and, per arm, the same draw with some blocks redrawn on a
+        second noise row e'; msd = 1 / (2 ns) sum_k (v_arm,k - v_k)^2 (Jansen).  Returns ``{"blocks": [P names], "mu_50": {...}, "mu_75":
+        ..., "mu_25": ...}`` (``"mean"`` alone for the Gaussian family), per head curve
+
+        * ``"mean"``, ``"var"`` ``[B, C, T]``: mean and population variance of the base curve (the square of ``recon_moments``' sd);
+        * ``"total"`` ``[P, B, C, T]``: the block's total-effect variance E[Var(f | z_~g)] = msd of the arm that redraws the block alone;
+        * ``"first"`` ``[P, B, C, T]``: the block's first-order variance Var(E[f | z_g]) = var - msd of the arm that redraws every other
+          block.  NOT clipped: estimator noise can make it negative, or larger than ``total``;
+        * ``"total_index"``, ``"first_index"`` ``[P, B, C]`` float64: sum_t total / sum_t var (and first), NaN where sum_t var == 0.
+
+        ``blocks`` names the P blocks wanted (default: all).  Arms with equal masks are shared, so a two-block family needs two arms, and
+        there ``first_index[0] == 1 - total_index[1]``.  ONE engine call (``slode_latent_attribution``) where the arms fit the LDS, else the
+        fewest calls that do, all on the same noise: no ``[B, C, T, num_samples]`` tensor exists, and the split changes no bit.  ``eps``
+        ``[2, num_samples, B, L]`` (base, fresh) makes it reproducible; None takes drawing calls n and n + 1 of the engine's generator (the
+        counter ends at n + 2).  Where the engine refuses (adaptive solver, strided observations, measured arms, LDS budget) the same dict
+        is composed from ``_decoded_draws`` on every arm's latents in chunks over B, reduced in fp64."""
+        from .. import _lib as L
+        b = self._bind()
+        B, ns = observations.shape[0], self._count(num_samples)
+        blocks, masks, single, comp = self._attribution_arms(blocks)
+        if eps is not None:
+            eps = eps.to(torch.float32).reshape(2, ns, B, -1).contiguous()
+
+        def fused():
+            eng = b.engine
+            fit = min(len(masks), L.ATTRIBUTION_MAX_ARMS, self.ATTRIBUTION_ARMS_PER_CALL or L.ATTRIBUTION_MAX_ARMS)
+            while fit > 1:
+                try:
+                    eng.attribution_plan(B, fit)
+                    break
+                except L.SlodeError:
+                    fit -= 1
+            n_calls = -(-len(masks) // fit)
+            per = -(-len(masks) // n_calls)
+            bt = eng.make_batch(observations, self._label_tensors(labels, B), eps, particles=ns,
+                                eps_shape=None if eps is None else (2, ns, B, eng.spec.latent_dim))
+            n0 = None if eps is not None else eng.rng_state()[2]
+            mean = sd = None
+            parts = []
+            for i in range(0, len(masks), per):
+                if n0 is not None:
+                    eng.rng_set_counter(n0)        # every call on the same noise: drawing calls n0, n0 + 1
+                m, s, msd = eng.latent_attribution(b.flat, bt, B, is_post, ns, masks[i:i + per], mean=None if i == 0 else False,
+                                                   sd=None if i == 0 else False)
+                if i == 0:
+                    mean, sd = m, s
+                parts.append(msd)
+            return self._attribution_result(blocks, single, comp, mean, sd * sd, parts[0] if len(parts) == 1 else torch.cat(parts, 0))
+
+        def composed():
+            with torch.no_grad():
+                e0, e1 = (eps[0], eps[1]) if eps is not None else (self._noise(ns, B, None), self._noise(ns, B, None))
+                names = self.MOMENT_HEADS[bool(self.GAUSS)]
+                rows = max(1, self.MOMENTS_CHUNK_ROWS // ns)
+                cols = []
+                for lo in range(0, B, rows):
+                    hi = min(B, lo + rows)
+                    d = {k: v[lo:hi] for k, v in labels.items()}
+                    loc, scale = self._loc_scale(observations[lo:hi], is_post, d)
+                    a0, a1 = e0[:, lo:hi].to(loc.device), e1[:, lo:hi].to(loc.device)
+                    base = {n: v.double() for n, v in self._decoded_draws(loc.unsqueeze(0) + scale.unsqueeze(0) * a0).items()}
+                    mean = torch.stack([base[n].mean(-1) for n in names], 0)
+                    var = torch.stack([base[n].var(-1, unbiased=False) for n in names], 0)
+                    msd = []
+                    for m in masks:
+                        e = torch.where(self._block_dims(m).to(loc.device), a1, a0)
+                        arm = self._decoded_draws(loc.unsqueeze(0) + scale.unsqueeze(0) * e)
+                        msd.append(torch.stack([0.5 * ((arm[n].double() - base[n]) ** 2).mean(-1) for n in names], 0))
+                        del arm
+                    cols.append((mean, var, torch.stack(msd, 0)))
+                    del base
+                mean, var, msd = torch.cat([c[0] for c in cols], 1), torch.cat([c[1] for c in cols], 1), torch.cat([c[2] for c in cols], 2)
+                return self._attribution_result(blocks, single, comp, mean, var, msd)
+        return self._fused_or_composed(fused, composed)
+
+    def save_latent_attribution(self, results_dir: str, batches, is_post, num_samples: int):
+        """Runs ``latent_attribution`` (all blocks) over ``batches`` (an iterable of device batch dicts: ``observations`` + the label
+        tensors) and writes ``attribution_total_<post|prior>.npy`` / ``attribution_first_<post|prior>.npy``, float32 ``[Q, P, n, C, T]`` (head
+        curves in the engine's order, blocks, the trajectories in loader order), ``attribution_total_index_<post|prior>.npy`` /
+        ``attribution_first_index_<post|prior>.npy``, float64 ``[Q, P, n, C]``, and ``attribution_blocks.txt``, one block name per line.  One
+        read-back, at the end.  Returns the paths."""
+        import os
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        keys = ("total", "first", "total_index", "first_index")
+        parts = {k: [] for k in keys}
+        for d in batches:
+            r = self.latent_attribution(is_post=is_post, num_samples=num_samples, **d)
+            for k in keys:
+                parts[k].append(torch.stack([r[n][k] for n in names], 0))
+        tag = "post" if is_post else "prior"
+        written = self._save_arrays(results_dir, (("attribution_%s_%s.npy" % (k, tag), torch.cat(parts[k], 2)) for k in keys if parts[k]))
+        os.makedirs(results_dir, exist_ok=True)
+        path = os.path.join(results_dir, "attribution_blocks.txt")
+        with open(path, "w") as f:
+            f.write("\n".join(self.attribution_blocks()) + "\n")
+        return written + [path]
+
+    def attribution_line(self, total_index, first_index, tag):
+        """One printed line of a ``save_latent_attribution`` pass: per block, the mean over head curves, trajectories and channels of the
+        total and the first-order index (NaN entries -- curves without variance -- left out)."""
+        import numpy as np
+        t, f = (np.asarray(a, dtype=np.float64) for a in (total_index, first_index))
+        cells = ["%s total=%.3f first=%.3f" % (n, float(np.nanmean(t[:, p])), float(np.nanmean(f[:, p])))
+                 for p, n in enumerate(self.attribution_blocks())]
+        return "attribution_%s: n=%d  %s" % (tag, t.shape[2], "  ".join(cells))
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 

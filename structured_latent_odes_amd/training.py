@@ -112,7 +112,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
-          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0):
+          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -143,7 +143,11 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     waic = K > 0: after training, the best model's pointwise predictive density over the validation loader from K posterior draws
     (``save_pointwise_density``: ``pointwise_{lppd,p_waic,mean_ll}_post.npy`` [n, C, T], ``waic_post.npy`` [n, 8]) and one printed line
     (``waic: ...``: total elpd_waic and its standard error over trajectories, total p_waic, the share of points with p_waic > 0.4);
-    0 (the default): no such stage runs."""
+    0 (the default): no such stage runs.
+    attribution = K > 0: after training, the best model's latent attribution over the validation loader from K pick-freeze draws, posterior
+    and prior (``save_latent_attribution``: ``attribution_{total,first}[_index]_<post|prior>.npy``, ``attribution_blocks.txt``) and one
+    printed line per side (``attribution_post: ...``: per latent block, the mean total and first-order index); 0 (the default): no such
+    stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -258,6 +262,14 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                     np.load([f for f in written if "p_waic" in f][0]), int(waic))
         print(line)
         logging.debug("%s (%s)", line, written)
+    if attribution:
+        for is_post in (True, False):
+            tag = "post" if is_post else "prior"
+            written = best_model.save_latent_attribution(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(attribution))
+            line = best_model.attribution_line(np.load([f for f in written if f.endswith("attribution_total_index_%s.npy" % tag)][0]),
+                                               np.load([f for f in written if f.endswith("attribution_first_index_%s.npy" % tag)][0]), tag)
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -334,6 +346,10 @@ def build_parser():
                     help="after training: the best model's pointwise predictive density over the validation loader from K posterior draws "
                          "(save_pointwise_density: pointwise_*_post.npy, waic_post.npy) and its WAIC -- elpd_waic with its standard error, p_waic, "
                          "the share of points with p_waic > 0.4 -- one line")
+    ap.add_argument("--attribution", type=int, default=0, metavar="K",
+                    help="after training: the best model's latent attribution over the validation loader from K pick-freeze draws, posterior and "
+                         "prior (save_latent_attribution: attribution_*.npy, attribution_blocks.txt) -- per latent block, the mean total and "
+                         "first-order variance index of the curves, one line per side")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -363,6 +379,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["refine_steps"], kw["refine_draws"] = a.refine_steps, a.refine_draws
     if a.waic:
         kw["waic"] = a.waic
+    if a.attribution:
+        kw["attribution"] = a.attribution
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
