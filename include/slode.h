@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 240 /* 0.2.4: slode_latent_attribution, slode_attribution_plan (0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 250 /* 0.2.5: slode_curve_summary, slode_curve_summary_plan (0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -45,6 +45,7 @@ extern "C" {
 #define SLODE_CALIBRATION_PHI2 0.97724986805182079f  /* Phi(2): the nominal level of mean + 2 s */
 #define SLODE_CALIBRATION_PHIM2 0.022750131948179195f /* Phi(-2): of mean - 2 s */
 #define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
+#define SLODE_SUMMARY_SLOTS 8 /* functionals of one slode_curve_summary row: peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -583,6 +584,54 @@ int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_l
                              float* mean /* [Q,B,C,T] or NULL */, float* sd /* [Q,B,C,T] or NULL */,
                              float* msd /* [n_arms,Q,B,C,T] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- curve summaries as ONE call: peak, time to peak, area and threshold crossing of the head curves (no reference counterpart: what users of the
+ * three model families ask of a curve -- how high does it get and when, how much is there in total, does it cross a level, when first and for how
+ * long -- are non-linear functionals of a draw's WHOLE curve; the peak of the mean curve is not the mean of the peaks, so none of them follows from
+ * the moments of slode_recon_moments) ----
+ * For trajectory b, head curve q (the order of slode_recon_moments), channel c and draw k the curve is v_k(t_i), i = 0 .. T - 1, on the grid
+ * `times`, with the same bits as the values slode_recon_moments accumulates.  Trapezoid node weights, formed in fp32: w_0 = 0.5 (t_1 - t_0),
+ * w_i = 0.5 (t_{i+1} - t_{i-1}), w_{T-1} = 0.5 (t_{T-1} - t_{T-2}).  With the threshold thr[c] and sense (+1: "beyond" is v > thr[c]; -1:
+ * v < thr[c]) the SLODE_SUMMARY_SLOTS = 8 functionals of a draw are
+ *   0 peak         max_i v_i                       1 t_peak    t_i at the smallest i attaining the maximum
+ *   2 trough       min_i v_i                       3 t_trough  t_i at the smallest i attaining the minimum
+ *   4 auc          sum_i w_i v_i                   5 time_beyond  sum_i w_i [v_i beyond thr_c]
+ *   6 t_hit        t_i at the smallest i with v_i beyond thr_c (defined only for draws that cross)
+ *   7 crossed      1 if any v_i is beyond thr_c, else 0
+ *   mean, sd [Q, B, C, 8]: mean and POPULATION sd of each functional over the num_samples draws, accumulated shifted by the first draw's value as
+ *   in slode_recon_moments (sd may be NULL).  Slot 6 takes its moments over the crossing draws only (shifted by the first crossing draw, divided
+ *   by their count) and is NaN when no draw crosses; slot 7 therefore reads P(cross) and sqrt(p (1 - p)).  num_samples = 1: every sd that is not
+ *   NaN is exactly 0 and mean is that draw's functional.
+ *   p_beyond [Q, B, C, T] (T contiguous) or NULL: the share of draws with v_k(t_i) beyond thr_c -- int32 counts on chip (exact), divided once.
+ *   thr: a HOST array [C] (copied into the kernel arguments at the call; not read afterwards) or NULL: slots 5 - 7 are then written as NaN and
+ *   p_beyond must be NULL.
+ *   The sums of slots 4 and 5 have a fixed tree: time points t = l, l + 16, ... in increasing order on lane l of a 16-lane row, then the row's
+ *   lanes pairwise (xor 1, xor 2, half mirror, mirror).  Extremes and first indices are comparisons and selections: exact, the smallest index
+ *   wins ties.
+ *   Draws, sides, noise: those of slode_recon_moments -- is_post != 0: three launches ("weff", "enc_fwd2", "curve_summary" in slode_profile_read);
+ *   is_post == 0: "curve_summary" alone; batch->eps == NULL: ONE drawing call n (row k * B + b, plus first_trajectory), the counter left at n + 1;
+ *   else a dense [num_samples, B, L] tensor.  The result is a function of (parameters, inputs, labels, noise, thr, sense) alone: independent of the
+ *   grid and of where the noise comes from, bitwise reproducible from run to run (every output has one owner thread, which takes the draws in the
+ *   order k = 0 .. num_samples - 1; no atomics); mean / sd do not depend on whether sd or p_beyond is asked for.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments on that side
+ * but its LDS rung -- a NULL handle (before anything else); num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver
+ * (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; for the posterior,
+ * batch->obs NULL, observation strides the folded encoder path does not take or SLODE_NO_FOLD; for the prior, no label tensors -- and, after the
+ * observation rungs: mean NULL; sense not +1 / -1; a non-finite thr[c]; p_beyond without thr; LDS tables (step table 2 (T - 1) S, grid and node weights 2 T,
+ * value table Q C T, counts Q C T only with p_beyond, moment triples 3 Q C 8, staged weights, 2 L; every piece a multiple of 16 B) beyond the
+ * budget of 160 KiB, naming whether the figure is with or without p_beyond.  The caller then reduces slode_ode_solve_fwd + slode_decode_heads
+ * itself. */
+
+/* The dynamic LDS bytes of slode_curve_summary's kernel for a shape, with (want_p_beyond != 0) or without the counters of p_beyond: pure host
+ * arithmetic -- no handle, no HIP call, works on a machine without a GPU.  SLODE_EINVAL (the reason is the global text slode_last_error(NULL)) for
+ * a bad shape or tables beyond the budget (*lds_bytes is still written then, so a caller can drop p_beyond). */
+int slode_curve_summary_plan(const slode_shape* s, int want_p_beyond, size_t* lds_bytes);
+int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                        const float* stage_t, const slode_batch* batch, int is_post, int num_samples,
+                        const float* thr /* HOST [C] or NULL */, int sense,
+                        float* mean /* [Q,B,C,8] */, float* sd /* [Q,B,C,8] or NULL */, float* p_beyond /* [Q,B,C,T] or NULL */,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- forecast: the posterior (or prior) curves of a trained model on ANY output grid as ONE call (no reference counterpart: the reference solves
  * on the training grid alone; what one asks of a latent ODE first is what this subject's curves look like after the observed window, or on a
  * finer grid) ------------------------------------------------------------------------------------------------------------------------------------
@@ -789,11 +838,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -1300,6 +1300,53 @@ int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_l
                    [&](hipStream_t st) { return slode_launch_attribution(a, st); });
 }
 
+// ---- curve summaries: the draws of slode_recon_moments, eight functionals of every draw's whole curve (include/slode.h) ----
+// The LDS bytes of slode_curve_summary for a shape, with or without the p_beyond counters (host arithmetic only; the compiled state dims, no
+// SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
+int slode_curve_summary_plan(const slode_shape* s, int want_p_beyond, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: %s", bad);
+  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: lds_bytes is NULL");
+  *lds_bytes = slode_curve_summary_lds_bytes(*s, want_p_beyond, 0);
+  if (*lds_bytes > SLODE_CURVE_SUMMARY_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: the LDS tables of T = %d, S = %d, C = %d, %s p_beyond (%zu B) exceed the budget of %d B",
+                s->T, s->S, s->C, want_p_beyond ? "with" : "without", *lds_bytes, SLODE_CURVE_SUMMARY_LDS_MAX);
+  return SLODE_OK;
+}
+
+// Mean / sd over num_samples latent draws of the eight curve functionals (include/slode.h): refusals first -- slode_recon_moments' for the same
+// is_post without its LDS rung, then the call's own, then its LDS rung; nothing launched, no draw consumed -- then slode_recon_moments'
+// launches with the summary kernel in place of its own.
+int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                        const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const float* thr, int sense, float* mean,
+                        float* sd, float* p_beyond, void* workspace, size_t workspace_bytes, void* stream) {
+  DrawsCall d("slode_curve_summary", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+              "reduce recon_samples instead", nullptr);
+  d.lds_tables = "step table, grid and node weights, value table, counts, moment triples, staged weights";
+  d.lds_advice = "drop p_beyond (slode_curve_summary_plan) or reduce recon_samples instead";
+  d.lds_extra = ", with p_beyond";
+  if (!p_beyond) {
+    d.lds_tables = "step table, grid and node weights, value table, moment triples, staged weights";
+    d.lds_advice = "reduce recon_samples instead"; d.lds_extra = ", without p_beyond";
+  }
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (!mean) return fail(h, SLODE_EINVAL, "slode_curve_summary: mean is NULL");
+  if (sense != 1 && sense != -1) return fail(h, SLODE_EINVAL, "slode_curve_summary: sense = %d is neither +1 (beyond: above thr) nor -1 (below)", sense);
+  if (thr)
+    for (int c = 0; c < s->C; ++c)
+      if (!std::isfinite(thr[c])) return fail(h, SLODE_EINVAL, "slode_curve_summary: thr[%d] = %g is not finite", c, (double)thr[c]);
+  if (p_beyond && !thr) return fail(h, SLODE_EINVAL, "slode_curve_summary: p_beyond needs a threshold (thr is NULL)");
+  if ((rc = eval_lds(h, s, d, slode_curve_summary_lds_bytes(*s, p_beyond != nullptr, h->ode_generic), SLODE_CURVE_SUMMARY_LDS_MAX)) != SLODE_OK) return rc;
+  CurveSummaryLaunch a{};
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
+  a.mean = mean; a.sd = sd; a.p_beyond = p_beyond; a.has_thr = thr ? 1 : 0; a.sense = sense;
+  for (int c = 0; c < SLODE_MAX_C; ++c) a.thr[c] = (thr && c < s->C) ? thr[c] : 0.f;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_curve_summary(a, st); });
+}
+
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
 int slode_num_stage_times_n(const slode_shape* s, int n_times) {
   if (!s || n_times < 2 || n_times > SLODE_FORECAST_MAX_T) return SLODE_EINVAL;

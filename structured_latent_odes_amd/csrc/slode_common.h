@@ -550,7 +550,7 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution; intervene: the posterior
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary; intervene: the posterior
 // alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
 // row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
 struct DrawsLaunch {
@@ -668,6 +668,20 @@ struct AttributionLaunch {
 #define SLODE_ATTRIBUTION_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, base moments, base values, arm sums, staged weights) must fit
 hipError_t slode_launch_attribution(const AttributionLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_attribution_lds_bytes(const slode_shape& s, int n_arms, int force_generic);
+
+// Curve summaries (curve_summary_kernel.hip; slode_curve_summary): over the draws of d per trajectory, mean / sd [Q, B, C, SLODE_SUMMARY_SLOTS]
+// of eight functionals of every draw's whole curve (peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed; sd may be NULL) and
+// p_beyond [Q, B, C, T], the share of draws beyond thr[c] at every point (NULL: no counters in the LDS).  thr / sense travel by value;
+// has_thr == 0: the threshold slots 5-7 are NaN and p_beyond must be NULL.
+struct CurveSummaryLaunch {
+  DrawsLaunch d;
+  float *mean, *sd, *p_beyond;
+  float thr[SLODE_MAX_C];
+  int has_thr, sense;
+};
+#define SLODE_CURVE_SUMMARY_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, grid and node weights, value table, counts, moment triples, staged weights) must fit
+hipError_t slode_launch_curve_summary(const CurveSummaryLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
+size_t slode_curve_summary_lds_bytes(const slode_shape& s, int want_p_beyond, int force_generic);
 
 // Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
 // from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]

@@ -875,6 +875,39 @@ class Engine:
                          self._p(mean), self._p(sd), self._p(msd))
         return mean, sd, msd
 
+    # ---- curve summaries: peak, time to peak, area and threshold crossing of every draw's curve -----------------------------------------
+    def curve_summary_plan(self, B: int, want_p_beyond: bool) -> int:
+        """``slode_curve_summary_plan``: the dynamic LDS bytes of ``curve_summary`` for this shape, with or without the counters of
+        ``p_beyond`` (host arithmetic only; raises SlodeError where the call would refuse them at its LDS rung)."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_curve_summary_plan(C.byref(self.shape(B)), 1 if want_p_beyond else 0, C.byref(r)))
+        return int(r.value)
+
+    def curve_summary(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, thr, sense: int, mean, sd=None, p_beyond=None,
+                      particles: int = 1):
+        """slode_curve_summary: per trajectory, head curve and channel, the mean and the population sd over ``num_samples`` latent draws (those
+        of ``recon_moments`` on the same side and noise) of the ``L.SUMMARY_SLOTS`` functionals ``L.SUMMARY_NAMES`` of every draw's whole curve.
+        Returns ``(mean, sd, p_beyond)``: ``mean`` float32 [Q, B, C, 8] (None: allocated), ``sd`` likewise and ``p_beyond`` float32
+        [Q, B, C, T], the share of draws beyond the threshold at every point (each: None = not computed, True = allocated, or the tensor to
+        write).  ``thr``: None (slots 5 - 7 are NaN; ``p_beyond`` is refused) or C floats read on the host now; ``sense``: +1 (beyond: above
+        ``thr``) or -1 (below).  ``t_hit`` (slot 6) takes the crossing draws only and is NaN where none crosses.  Enqueued on the current
+        stream; nothing sized num_samples x B x C x T exists anywhere.  Raises SlodeError naming the reason for what the kernel does not take
+        (everything ``recon_moments`` refuses on that side; ``sense``; a non-finite threshold; ``p_beyond`` without one; LDS budget): nothing
+        is launched and no draw is consumed then."""
+        Q, _, Cn, T = self._head_shape(B)
+        mean = self._out(mean, "mean", (Q, B, Cn, L.SUMMARY_SLOTS))
+        sd = None if sd is None else self._out(None if sd is True else sd, "sd", (Q, B, Cn, L.SUMMARY_SLOTS))
+        p_beyond = None if p_beyond is None else self._out(None if p_beyond is True else p_beyond, "p_beyond", (Q, B, Cn, T))
+        arr = None
+        if thr is not None:
+            vals = [float(v) for v in (thr.detach().cpu().reshape(-1).tolist() if isinstance(thr, torch.Tensor) else thr)]
+            if len(vals) != Cn:
+                raise ValueError("thr must hold %d values (one per channel), got %d" % (Cn, len(vals)))
+            arr = (C.c_float * Cn)(*vals)
+        self._batch_call(self.lib.slode_curve_summary, params, batch, B, particles, 1 if is_post else 0, int(num_samples), arr, int(sense),
+                         self._p(mean), self._p(sd), self._p(p_beyond))
+        return mean, sd, p_beyond
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

@@ -1014,6 +1014,142 @@ class MechanisticBase(nn.Module):
                  for p, n in enumerate(self.attribution_blocks())]
         return "attribution_%s: n=%d  %s" % (tag, t.shape[2], "  ".join(cells))
 
+    # ---- curve summaries: peak, time to peak, area and threshold crossing of every draw's curve ------------------------------------------
+    SUMMARY_NAMES = ("peak", "t_peak", "trough", "t_trough", "auc", "time_beyond", "t_hit", "crossed")   # the slots of slode_curve_summary
+
+    @staticmethod
+    def _summary_sense(sense) -> int:
+        """``"above"`` / ``"below"`` (or +1 / -1) as the engine's +1 / -1; ValueError otherwise."""
+        if sense in ("above", 1):
+            return 1
+        if sense in ("below", -1):
+            return -1
+        raise ValueError("sense must be 'above' or 'below', got %r" % (sense,))
+
+    def _summary_weights(self, device):
+        """``(times, w)`` float32 [T] on ``device``: the grid and the trapezoid node weights w_0 = 0.5 (t_1 - t_0), w_i = 0.5 (t_{i+1} -
+        t_{i-1}), w_{T-1} = 0.5 (t_{T-1} - t_{T-2}), formed in fp32 as the kernel forms them."""
+        t = torch.as_tensor(self.times, dtype=torch.float32).reshape(-1).to(device)
+        i = torch.arange(t.numel(), device=device)
+        return t, 0.5 * (t[(i + 1).clamp(max=t.numel() - 1)] - t[(i - 1).clamp(min=0)])
+
+    def _summary_functionals(self, v, thr, sense):
+        """The eight functionals of the curves ``v`` ``[rows, C, T, ns]`` in torch, on the definitions of ``slode_curve_summary``:
+        ``(f [rows, C, ns, 8] float32, beyond [rows, C, T, ns] bool or None)``.  First indices are a masked ``min`` over the index (torch's
+        argmax tie rule is not relied on); ``t_hit`` of a draw that does not cross is NaN; ``thr`` None: slots 5 - 7 are NaN."""
+        v = v.to(torch.float32)
+        T = v.shape[2]
+        t, w = self._summary_weights(v.device)
+        idx = torch.arange(T, device=v.device).reshape(1, 1, T, 1)
+
+        def first(mask):
+            return torch.where(mask, idx, torch.full_like(idx, T)).amin(dim=2)
+        peak, trough = v.amax(dim=2), v.amin(dim=2)
+        t_peak, t_trough = t[first(v == peak.unsqueeze(2))], t[first(v == trough.unsqueeze(2))]
+        auc = (w.reshape(1, 1, T, 1) * v).sum(dim=2)
+        nan = torch.full_like(auc, float("nan"))
+        beyond = None
+        if thr is None:
+            tb, t_hit, crossed = nan, nan, nan
+        else:
+            th = torch.as_tensor(thr, dtype=torch.float32, device=v.device).reshape(1, -1, 1, 1)
+            beyond = v > th if sense > 0 else v < th
+            tb = (w.reshape(1, 1, T, 1) * beyond.to(torch.float32)).sum(dim=2)
+            ih = first(beyond)
+            crossed = (ih < T).to(torch.float32)
+            t_hit = torch.where(ih < T, t[ih.clamp(max=T - 1)], nan)
+        return torch.stack([peak, t_peak, trough, t_trough, auc, tb, t_hit, crossed], dim=-1), beyond
+
+    @staticmethod
+    def _summary_moments(f):
+        """``(mean, sd)`` ``[rows, C, 8]`` over the draw axis of ``f`` ``[rows, C, ns, 8]``: population sd; NaN entries (``t_hit`` of the
+        draws that do not cross) are left out, a slot with none left is NaN."""
+        ok = ~torch.isnan(f)
+        n = ok.sum(dim=2).to(f.dtype)
+        f0 = torch.where(ok, f, torch.zeros_like(f))
+        mean = f0.sum(dim=2) / n                                           # n = 0: 0 / 0 = NaN
+        dev = torch.where(ok, f - mean.unsqueeze(2), torch.zeros_like(f))
+        return mean, ((dev * dev).sum(dim=2) / n).sqrt()
+
+    def curve_summary(self, observations, is_post, num_samples: int, thresholds=None, sense="above", eps=None, pointwise: bool = False, **labels):
+        """What one asks of a curve -- how high does it get and when, how much is there in total, does it cross a level, when first and for
+        how long -- over ``num_samples`` latent draws: per head curve name (``mu_50``, ``mu_75``, ``mu_25``; ``mean`` for the Gaussian
+        family) a dict of ``(mean, sd)`` pairs, ``[B, C]`` each, under ``"peak"``, ``"t_peak"``, ``"trough"``, ``"t_trough"``, ``"auc"``
+        (trapezoid rule on the model's grid), ``"time_beyond"``, ``"t_hit"`` (over the draws that cross; NaN where none does) and
+        ``"crossed"`` (``P(cross)``, ``sqrt(p (1 - p))``); ``pointwise=True`` adds ``"p_beyond"`` ``[B, C, T]``, the share of draws beyond
+        the threshold at every point.  These are functionals of every draw's whole curve: the moments of ``recon_moments`` do not yield
+        them.  ``thresholds``: a length-C sequence or tensor, read on the host once (None: the three threshold entries are NaN and
+        ``pointwise`` is refused); ``sense``: ``"above"`` or ``"below"``.  ONE engine call (``slode_curve_summary``) on the draws of
+        ``recon_moments`` (same ``eps`` / generator use); where the engine refuses (adaptive solver, strided observations, measured arms,
+        LDS budget) the same dict is composed from ``recon_samples`` in chunks over B, the functionals in torch on the same definitions."""
+        b = self._bind()
+        B, ns, sn = observations.shape[0], self._count(num_samples), self._summary_sense(sense)
+        thr = None if thresholds is None else [float(x) for x in torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).tolist()]
+        if thr is not None and len(thr) != observations.shape[1]:
+            raise ValueError("thresholds must hold %d values (one per channel), got %d" % (observations.shape[1], len(thr)))
+        if pointwise and thr is None:
+            raise ValueError("pointwise=True needs thresholds")
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+
+        def pack(mean, sd, p):
+            return {n: dict({k: (mean[q][..., j], sd[q][..., j]) for j, k in enumerate(self.SUMMARY_NAMES)}, **({"p_beyond": p[q]} if pointwise else {}))
+                    for q, n in enumerate(names)}
+
+        def fused():
+            return pack(*b.engine.curve_summary(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, thr, sn, None, True,
+                                                True if pointwise else None))
+
+        def composed():
+            cols = {n: ([], [], []) for n in names}
+            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
+                for n in names:
+                    f, beyond = self._summary_functionals(res[n], thr, sn)
+                    m, s = self._summary_moments(f)
+                    cols[n][0].append(m); cols[n][1].append(s)
+                    if pointwise:
+                        count = beyond.to(torch.float32).sum(dim=-1)                 # exact; count / ns as the kernel divides it (a tensor
+                        cols[n][2].append(count / torch.full_like(count, float(ns)))     # divisor: a true division, not a reciprocal multiply)
+                del res
+            return pack([torch.cat(cols[n][0], 0) for n in names], [torch.cat(cols[n][1], 0) for n in names],
+                        [torch.cat(cols[n][2], 0) if pointwise else None for n in names])
+        return self._fused_or_composed(fused, composed)
+
+    def save_curve_summary(self, results_dir: str, batches, is_post, num_samples: int, thresholds=None, sense="above"):
+        """Runs ``curve_summary`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
+        ``summary_<curve>_<post|prior>_mean.npy`` / ``..._sd.npy``, float32 ``[n, C, 8]`` (the trajectories in loader order, the slots in
+        ``SUMMARY_NAMES`` order), and ``summary_slots.npy``, the slot names.  One read-back, at the end.  Returns the paths."""
+        import os
+        import numpy as np
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        parts = {(n, k): [] for n in names for k in (0, 1)}
+        for d in batches:
+            r = self.curve_summary(is_post=is_post, num_samples=num_samples, thresholds=thresholds, sense=sense, **d)
+            for n in names:
+                for k in (0, 1):
+                    parts[(n, k)].append(torch.stack([r[n][slot][k] for slot in self.SUMMARY_NAMES], -1))
+        tag = "post" if is_post else "prior"
+        written = self._save_arrays(results_dir, (("summary_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.cat(v, 0))
+                                                  for (n, k), v in parts.items() if v))
+        os.makedirs(results_dir, exist_ok=True)
+        path = os.path.join(results_dir, "summary_slots.npy")
+        np.save(path, np.array(self.SUMMARY_NAMES))
+        return written + [path]
+
+    def summary_line(self, mean, tag, with_threshold: bool):
+        """One printed line of a ``save_curve_summary`` pass from the central curve's ``mean`` array ``[n, C, 8]``: per channel, the mean over
+        trajectories of the mean peak, time to peak and AUC and, with thresholds, of ``P(cross)`` and ``t_hit`` (NaN entries left out)."""
+        import numpy as np
+        m = np.asarray(mean, dtype=np.float64)
+        cells = []
+        for c in range(m.shape[1]):
+            cell = "c%d peak=%.4g t_peak=%.4g auc=%.4g" % (c, m[:, c, 0].mean(), m[:, c, 1].mean(), m[:, c, 4].mean())
+            if with_threshold:
+                hit = m[:, c, 6]
+                cell += " p_cross=%.3f t_hit=%.4g" % (m[:, c, 7].mean(), float(np.nanmean(hit)) if np.isfinite(hit).any() else float("nan"))
+            cells.append(cell)
+        return "curve_summary_%s: n=%d  %s" % (tag, m.shape[0], "  ".join(cells))
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 

@@ -112,7 +112,8 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           train_batches: Optional[Sequence[dict]] = None, val_batches: Optional[Sequence[dict]] = None, times: Optional[torch.Tensor] = None,
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
-          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0):
+          label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
+          curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above"):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -147,7 +148,11 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     attribution = K > 0: after training, the best model's latent attribution over the validation loader from K pick-freeze draws, posterior
     and prior (``save_latent_attribution``: ``attribution_{total,first}[_index]_<post|prior>.npy``, ``attribution_blocks.txt``) and one
     printed line per side (``attribution_post: ...``: per latent block, the mean total and first-order index); 0 (the default): no such
-    stage runs."""
+    stage runs.
+    curve_summary = K > 0: after training, the best model's curve summaries over the validation loader from K draws, posterior and prior
+    (``save_curve_summary``: ``summary_<curve>_<post|prior>_{mean,sd}.npy`` [n, C, 8], ``summary_slots.npy``) and one printed line per side
+    (``curve_summary_post: ...``: per channel of the central curve, the mean peak, time to peak and AUC and, with ``summary_thresholds`` --
+    one level per channel, ``summary_sense`` "above" or "below" --, P(cross) and the mean t_hit); 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -270,6 +275,16 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                                np.load([f for f in written if f.endswith("attribution_first_index_%s.npy" % tag)][0]), tag)
             print(line)
             logging.debug("%s (%s)", line, written)
+    if curve_summary:
+        for is_post in (True, False):
+            tag = "post" if is_post else "prior"
+            written = best_model.save_curve_summary(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(curve_summary),
+                                                    thresholds=summary_thresholds, sense=summary_sense)
+            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
+            line = best_model.summary_line(np.load([f for f in written if f.endswith("summary_%s_%s_mean.npy" % (central, tag))][0]), tag,
+                                           summary_thresholds is not None)
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -350,6 +365,14 @@ def build_parser():
                     help="after training: the best model's latent attribution over the validation loader from K pick-freeze draws, posterior and "
                          "prior (save_latent_attribution: attribution_*.npy, attribution_blocks.txt) -- per latent block, the mean total and "
                          "first-order variance index of the curves, one line per side")
+    ap.add_argument("--curve-summary", type=int, default=0, metavar="K",
+                    help="after training: the best model's curve summaries over the validation loader from K draws, posterior and prior "
+                         "(save_curve_summary: summary_*.npy) -- per channel of the central curve, the mean peak, time to peak and AUC and, with "
+                         "--summary-thresholds, P(cross) and the mean first crossing time, one line per side")
+    ap.add_argument("--summary-thresholds", type=lambda v: [float(x) for x in v.split(",")], default=None, metavar="a,b,c[,d]",
+                    help="one level per channel for --curve-summary (default: none; the threshold entries are then NaN)")
+    ap.add_argument("--summary-sense", choices=("above", "below"), default="above",
+                    help="which side of --summary-thresholds counts as beyond (default: above)")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -381,6 +404,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["waic"] = a.waic
     if a.attribution:
         kw["attribution"] = a.attribution
+    if a.curve_summary:
+        kw["curve_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.curve_summary, a.summary_thresholds, a.summary_sense
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
