@@ -514,7 +514,7 @@ __global__ void __launch_bounds__(256) enc_bwd_lin_kernel(const float* __restric
     const int r16 = reg & 15, tile = reg >> 4;
     const int m = tile * 32 + (r16 & 3) + 8 * (r16 >> 2) + 4 * (ln >> 5);  // C/D map of the 32x32 MFMA
     const int i = i0 + (ln & 31);
-    if (m < Hc && i < NO) slab[(long long)m * NO + i] = v;
+    if (m < Hc && i < NO) st_out(slab + (long long)m * NO + i, v);
   }
 }
 

@@ -582,6 +582,9 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   static_assert(PK == 1 || (ONE && T_ > 0), "packed trajectories: shape-specialised loop-free forms only");
   static_assert(!ENCF || (ONE && T_ > 0 && ALG == 0 && (PK == 1 || SOFTB)), "fused encoder forward: shape-specialised loop-free product form only");
   static_assert(!SOFTB || (PK > 1 && ENCF), "per-trajectory barriers: the packed form with the shared encoder pass");
+  // Outputs the next launch reads go out write-through in the shape-specialised forms with a short latent, plain elsewhere: see st_out
+  // (slode_common.h) for the reason and profiles/written_through_profile.txt for config[2] with both policies.
+  constexpr bool WT = L_ > 0 && L_ <= 16;
   extern __shared__ __attribute__((aligned(16))) float smem_wg[];
   constexpr int NWT = PK > 1 ? ode_threads_for(T_ ? T_ : 1, Q_ ? Q_ : 1, C_ ? C_ : 1, S) / 64 : 1;   // waves per trajectory (PK > 1)
   const int wave_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -924,7 +927,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
       const float hv = tanhf(v + e_be);
       if ((lane & 3) == 0 && r < ERWP && mrow < k.Hc) {
         smem_wg[PK * m.total + t * 64 + mrow] = hv;
-        k.enc_hid_out[(long long)((int)blockIdx.x * PK + t) * k.Hc + mrow] = hv;
+        st_out<WT>(k.enc_hid_out + (long long)((int)blockIdx.x * PK + t) * k.Hc + mrow, hv);
       }
     }
     if (ENCF && PK == 1) {   // rows of this wave: one halving butterfly leaves the sum of row (lane >> 2) & 15 in every lane; tanh; saved
@@ -933,7 +936,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
       const float hv = tanhf(v + e_be);
       if ((lane & 3) == 0 && idx < ERW && mrow < k.Hc) {
         s_ehid[mrow] = hv;
-        if (b_first < k.B) k.enc_hid_out[(long long)b_first * k.Hc + mrow] = hv;
+        if (b_first < k.B) st_out<WT>(k.enc_hid_out + (long long)b_first * k.Hc + mrow, hv);
       }
     }
     STAMP(25);   // (encoder products reduced, tanh stored)
@@ -951,7 +954,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   if (BWD) {   // elements no phase owns (e.g. label-head parameters the main loss does not score): zero gradient
     float* sl = k.slabs + srow * k.slab_stride + 1;
     for (int z = 0; z < k.nz; ++z)
-      for (int i = k.zlo[z] + tid; i < k.zhi[z]; i += NT) sl[i] = 0.f;
+      for (int i = k.zlo[z] + tid; i < k.zhi[z]; i += NT) st_out<WT>(sl + i, 0.f);
   }
   __syncthreads();
   STAMP(14);
@@ -993,7 +996,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
     // slab (no LDS copy): written on the workgroup's first trajectory, added to on later ones (same owner, program order).
     float* const sl1 = k.slabs + srow * k.slab_stride + 1;
     const bool first_traj = ONE || b == vblk;
-    auto accum = [&](int idx, float v) { float* d = sl1 + idx; *d = first_traj ? v : (*d + v); };
+    auto accum = [&](int idx, float v) { float* d = sl1 + idx; st_out<WT>(d, first_traj ? v : (*d + v)); };
     if (COLDB && !ONE && b != vblk) {
       BAR();   // the previous trajectory's last readers of the work block (its encoder-head block) are done
       stage_cold();
@@ -1474,7 +1477,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
           if (BWD) {  // constant_std gradient: thread t owns slab entry (c, t); softplus'(x) = 1 - exp(-softplus(x))
             float* dst = k.slabs + srow * k.slab_stride + 1 + k.o_cstd + c * T + t;
             const float val = gsig * (use_tab ? t_ds[c] : 1.f - expf(-sig));
-            *dst = (ONE || b == vblk) ? val : (*dst + val);
+            st_out<WT>(dst, (ONE || b == vblk) ? val : (*dst + val));
           }
         }
         loss_acc -= ll;
@@ -1949,17 +1952,17 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
             const float sc = s_gls[L + l];
             const float gsc = fmaf(gz, s_gpl[L + l], -1.0f / sc);
             if (k.g_loc) {
-              k.g_loc[(b + pv) * L + l] = gz;
-              k.g_scale[(b + pv) * L + l] = gsc;
+              st_out<WT>(k.g_loc + (b + pv) * L + l, gz);
+              st_out<WT>(k.g_scale + (b + pv) * L + l, gsc);
             }
             if (k.g_pre) {  // hand (g_loc, g_scale * scale) to the head-backward block after the trajectory's last barrier
               s_gzl[l] = gz;
               s_gpl[L + l] = gsc * sc;
-              k.glat[(b + pv) * 128 + l] = gz;
-              k.glat[(b + pv) * 128 + 64 + l] = gsc * sc;
+              st_out<WT>(k.glat + (b + pv) * 128 + l, gz);
+              st_out<WT>(k.glat + (b + pv) * 128 + 64 + l, gsc * sc);
             }
           } else {
-            k.g_loc[(b + pv) * L + l] = gz;
+            st_out<WT>(k.g_loc + (b + pv) * L + l, gz);
           }
         }
         STAMP(19);
@@ -2050,7 +2053,7 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
           g1 = fmaf(k.enc_zls_w[l * Hc + mm], s_gpl[L + l], g1);
         }
       }
-      k.g_pre[(b + pv) * 64 + mm] = (g0 + g1) * (1.f - hv * hv);
+      st_out<WT>(k.g_pre + (b + pv) * 64 + mm, (g0 + g1) * (1.f - hv * hv));
     }
     if (!ONE && b + vgrid < k.B && tid >= 64 && tid < 128) {   // next trajectory's latent inputs (P0a is long past)
       const int bn = b + vgrid, t1 = tid - 64;
@@ -2078,11 +2081,11 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   if (tid == 0) {
     float loss = 0.f;
     for (int w = 0; w < (NT >> 6); ++w) loss += s_red[w];   // fixed order
-    if (k.slabs) slab[0] = loss;
+    if (k.slabs) st_out<WT>(slab, loss);
   }
   if (BWD) {
     if (!k.with_ll) {  // pure solve backward: the likelihood-only entries of the segment carry no gradient
-      for (int i = tid; i < C * T; i += NT) slab[1 + k.o_cstd + i] = 0.f;
+      for (int i = tid; i < C * T; i += NT) st_out<WT>(slab + 1 + k.o_cstd + i, 0.f);
     }
   }
   STAMP(11);

@@ -203,6 +203,25 @@ __device__ __forceinline__ float wave_sum16(float (&a)[16], int lane) {
   return r;
 }
 
+// Store of an output the NEXT launch reads: agent-scope (sc1, write-through), so the bytes are on their way to memory while the kernel
+// still computes and its end-of-kernel release finds no dirty L2 line of them.  The stored value is the same either way.  An owner that
+// later adds to its own store reads it back with a plain load (same thread, same address: program order).
+// It pays where the launch's whole output would otherwise sit dirty in L2 until the end AND the launch runs long enough to hide the
+// stores: a 4-byte write-through store is one fabric write each.  Measured (profiles/written_through_profile.txt): a gain in
+// ode_elbo_kernel at short latents (7.7 MB at the metric shape) and in the GEMM launch; a loss where the rows outgrow L2, which then
+// writes back as it goes (config[2]: 24 KB rows x 4096 workgroups), and in the short launches (fold, chain, aux_kernel).  WT = false is
+// the plain store, for a kernel that decides per instantiation (ode_elbo_kernel: by the latent size, the row size's compile-time proxy).
+// -DSLODE_PLAIN_OUT (make plainout) builds the earlier write-back policy for the A/B of tools/ab_libs.sh; never shipped.
+template <bool WT = true>
+__device__ __forceinline__ void st_out(float* p, float v) {
+#ifdef SLODE_PLAIN_OUT
+  *p = v;
+#else
+  if (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+#endif
+}
+
 // sum_{w < n} p[w * stride] with 16 loads in flight; fixed order (four round-robin partial sums, combined pairwise)
 __device__ __forceinline__ float strided_sum(const float* p, int stride, int n) {
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -376,7 +395,7 @@ __device__ __forceinline__ void slab_stage1_block(const Stage1& f, int bx, int g
   for (int c = threadIdx.x; c < SLODE_S1_COLS; c += 256) {
     const int ec = bx * SLODE_S1_COLS + c;
     if (ec < f.count)
-      f.out[(long long)g * f.stride + ec] = (s_p[c] + s_p[SLODE_S1_COLS + c]) + (s_p[2 * SLODE_S1_COLS + c] + s_p[3 * SLODE_S1_COLS + c]);
+      st_out(f.out + (long long)g * f.stride + ec, (s_p[c] + s_p[SLODE_S1_COLS + c]) + (s_p[2 * SLODE_S1_COLS + c] + s_p[3 * SLODE_S1_COLS + c]));
   }
 }
 
