@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 250 /* 0.2.5: slode_curve_summary, slode_curve_summary_plan (0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 260 /* 0.2.6: slode_recon_quantiles, slode_quantile_plan (0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -46,6 +46,7 @@ extern "C" {
 #define SLODE_CALIBRATION_PHIM2 0.022750131948179195f /* Phi(-2): of mean - 2 s */
 #define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
 #define SLODE_SUMMARY_SLOTS 8 /* functionals of one slode_curve_summary row: peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed */
+#define SLODE_QUANTILE_MAX_LEVELS 8 /* most levels of one slode_recon_quantiles call */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -632,6 +633,48 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
                         float* mean /* [Q,B,C,8] */, float* sd /* [Q,B,C,8] or NULL */, float* p_beyond /* [Q,B,C,T] or NULL */,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sample quantiles of the head curves as ONE call: the credible band, the envelope, the median over the draws (no reference counterpart: the
+ * reference saves the [B, C, T, num_samples] curves of multiple_samples and its users take np.percentile(samples, [2.5, 97.5], axis=-1) of them;
+ * mean +- 2 sd of slode_recon_moments is no substitute for the skewed prior-side curves) ----
+ * For trajectory b, head curve q (the order of slode_recon_moments), channel c and time point t let v_(0) <= ... <= v_(K-1) be the K = num_samples
+ * draw values, sorted -- the same bits as the values slode_recon_moments accumulates.  For a level p in [0, 1] (numpy's default "linear" definition;
+ * the ranks are formed on the host in fp64):
+ *   h = p (K - 1),  lo = floor(h),  hi = min(lo + 1, K - 1),  g = (float)(h - lo),
+ *   out[level, q, b, c, t] = fma(g, v_(hi) - v_(lo), v_(lo))     (fp32; the difference rounded on its own, then one fma)
+ * so a level with g == 0 (p = 0: the minimum, p = 1: the maximum, K = 1, p (K - 1) an integer) is one of the draw values exactly.  out is
+ * [n_levels, Q, B, C, T], T contiguous; n_levels <= SLODE_QUANTILE_MAX_LEVELS = 8; levels: a HOST array [n_levels] of doubles (read at the call;
+ * any order, duplicates allowed).
+ *   Depths: every needed rank r (lo of every level; hi where g != 0: an upper rank without weight is not read) is served from one of two sorted buffers per value, kept in the LDS: the depth_lo smallest draws so far (cost
+ *   r + 1) or the depth_hi largest (cost K - r), whichever costs less, the bottom one on a tie; depth_lo / depth_hi: the largest cost given to a
+ *   side; depth_lo + depth_hi >= K: every draw is kept (depth_lo = K, depth_hi = 0).  (0.025, 0.975) at K = 200: 6 + 6; (0, 1): 1 + 1; a median
+ *   at K = 200: 200.
+ *   Tiles: the buffers [depth][Q C][tile] hold `tile` time points; T > tile takes sweeps = ceil(T / tile) passes over the draws, each solving
+ *   the whole grid on the same noise.  tile = 0: the fewest sweeps that fit the LDS budget of 160 KiB, tile = ceil(T / sweeps); tile > 0: as given.
+ *   Draws, sides: those of slode_recon_moments -- is_post != 0: three launches ("weff", "enc_fwd2", "recon_quantiles" in slode_profile_read);
+ *   is_post == 0: "recon_quantiles" alone.  Noise: batch->eps == NULL: row k * B + b (plus first_trajectory) of drawing call n, as
+ *   slode_recon_moments; the counter is left at n + num_samples, whatever the number of sweeps; else a dense [num_samples, B, L] tensor.
+ *   The result is a function of (parameters, inputs, labels, noise, levels) alone: bitwise independent of the grid, of the tile and of where the
+ *   noise comes from (every output has one owner thread, which takes the draws in the order k = 0 .. num_samples - 1; no atomics).  Non-finite
+ *   curve values are not ordered: the outputs of such a (q, b, c, t) are unspecified.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments on that side
+ * but its LDS rung -- a NULL handle (before anything else); num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver
+ * (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; for the posterior,
+ * batch->obs NULL, observation strides the folded encoder path does not take or SLODE_NO_FOLD; for the prior, no label tensors -- and, after the
+ * observation rungs: out NULL; n_levels outside [1, 8]; levels NULL; a level outside [0, 1] or NaN; tile < 0 or tile > T; a given tile whose
+ * tables (step table 2 (T - 1) S, staged weights, 2 L, level table, buffers depth Q C tile; every piece a multiple of 16 B) exceed the budget;
+ * tile = 0 where not even one time point fits.  The caller then sorts slode_ode_solve_fwd + slode_decode_heads itself. */
+
+/* The plan of slode_recon_quantiles for (shape, num_samples, levels, tile): the tile it would use, the sweeps over the draws, the two depths and
+ * the kernel's dynamic LDS bytes: pure host arithmetic -- no handle, no HIP call, works on a machine without a GPU.  SLODE_EINVAL (the reason is
+ * the global text slode_last_error(NULL)) for a bad shape, a NULL output and everything the call refuses at its own rungs. */
+int slode_quantile_plan(const slode_shape* s, int num_samples, int n_levels, const double* levels /* HOST [n_levels] */, int tile, int* tile_out,
+                        int* sweeps, int* depth_lo, int* depth_hi, size_t* lds_bytes);
+int slode_recon_quantiles(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                          const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int n_levels,
+                          const double* levels /* HOST [n_levels] */, int tile, float* out /* [n_levels,Q,B,C,T] */, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- forecast: the posterior (or prior) curves of a trained model on ANY output grid as ONE call (no reference counterpart: the reference solves
  * on the training grid alone; what one asks of a latent ODE first is what this subject's curves look like after the observed window, or on a
  * finer grid) ------------------------------------------------------------------------------------------------------------------------------------
@@ -838,11 +881,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -1347,6 +1347,108 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
                    [&](hipStream_t st) { return slode_launch_curve_summary(a, st); });
 }
 
+// ---- sample quantiles: the draws of slode_recon_moments, order statistics of every value over the draws (include/slode.h) ----
+// The rank, depth and tile rules as data: what the plan reports and the launch takes.  why: the refusal.
+struct QuantilePlan { int tile, sweeps, depth_lo, depth_hi; size_t lds; int slot_lo[SLODE_QUANTILE_MAX_LEVELS], slot_hi[SLODE_QUANTILE_MAX_LEVELS]; float g[SLODE_QUANTILE_MAX_LEVELS]; };
+static int quantile_plan(const slode_shape& s, int K, int n_levels, const double* levels, int tile, int force_generic, QuantilePlan* p, char* why,
+                         size_t why_n) {
+  if (K < 1) { snprintf(why, why_n, "num_samples = %d < 1", K); return SLODE_EINVAL; }
+  if (n_levels < 1 || n_levels > SLODE_QUANTILE_MAX_LEVELS) {
+    snprintf(why, why_n, "n_levels = %d out of range [1, %d]", n_levels, SLODE_QUANTILE_MAX_LEVELS);
+    return SLODE_EINVAL;
+  }
+  if (!levels) { snprintf(why, why_n, "levels is NULL"); return SLODE_EINVAL; }
+  for (int i = 0; i < n_levels; ++i)
+    if (!(levels[i] >= 0.0 && levels[i] <= 1.0)) { snprintf(why, why_n, "levels[%d] = %g is not in [0, 1]", i, levels[i]); return SLODE_EINVAL; }
+  if (tile < 0 || tile > s.T) { snprintf(why, why_n, "tile = %d out of range [0, T = %d] (0: the library chooses)", tile, s.T); return SLODE_EINVAL; }
+  // ranks: numpy's "linear" definition, fp64; each rank from the side that costs less, the bottom on a tie
+  int r_lo[SLODE_QUANTILE_MAX_LEVELS], r_hi[SLODE_QUANTILE_MAX_LEVELS];
+  int m_lo = 0, m_hi = 0;
+  for (int i = 0; i < n_levels; ++i) {
+    const double hq = levels[i] * (double)(K - 1);
+    int lo = (int)std::floor(hq);
+    lo = lo < 0 ? 0 : (lo > K - 1 ? K - 1 : lo);
+    r_lo[i] = lo; r_hi[i] = lo + 1 < K ? lo + 1 : K - 1;
+    p->g[i] = (float)(hq - (double)lo);
+    if (p->g[i] == 0.f) r_hi[i] = lo;   // the upper rank has no weight: not needed (fma(0, 0, v_lo) = v_lo)
+    for (int r : {r_lo[i], r_hi[i]}) {
+      if (r + 1 <= K - r) m_lo = r + 1 > m_lo ? r + 1 : m_lo;
+      else m_hi = K - r > m_hi ? K - r : m_hi;
+    }
+  }
+  if (m_lo + m_hi >= K) { m_lo = K; m_hi = 0; }   // the buffers would meet: keep every draw, sorted
+  for (int i = 0; i < n_levels; ++i) {
+    p->slot_lo[i] = r_lo[i] < m_lo ? r_lo[i] : m_lo + (K - 1 - r_lo[i]);
+    p->slot_hi[i] = r_hi[i] < m_lo ? r_hi[i] : m_lo + (K - 1 - r_hi[i]);
+  }
+  for (int i = n_levels; i < SLODE_QUANTILE_MAX_LEVELS; ++i) { p->slot_lo[i] = p->slot_hi[i] = 0; p->g[i] = 0.f; }
+  p->depth_lo = m_lo; p->depth_hi = m_hi;
+  const int D = m_lo + m_hi, Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
+  const size_t budget = SLODE_RECON_QUANTILES_LDS_MAX;
+  auto bytes = [&](int tl) { return slode_recon_quantiles_lds_bytes(s, D, tl, force_generic); };
+  int tl = tile;
+  if (tile > 0) {
+    if (bytes(tl) > budget) {
+      snprintf(why, why_n, "tile = %d does not fit: the LDS tables of T = %d, S = %d, C = %d, depth = %d + %d (%zu B: step table, staged weights, level table, "
+               "sorted buffers [depth][%d][tile]) exceed the budget of %zu B; pass tile = 0 to let the library choose", tl, s.T, s.S, s.C, m_lo, m_hi,
+               bytes(tl), Q * s.C, budget);
+      return SLODE_EINVAL;
+    }
+  } else {
+    if (bytes(1) > budget) {
+      snprintf(why, why_n, "depth = %d + %d of num_samples = %d: the sorted buffers of one time point [depth][%d] do not fit beside the step table of T = %d, "
+               "S = %d (%zu B of a budget of %zu B); sort recon_samples instead", m_lo, m_hi, K, Q * s.C, s.T, s.S, bytes(1), budget);
+      return SLODE_EINVAL;
+    }
+    for (int sw = 1;; ++sw) {   // the fewest sweeps that fit (sw = T: tile = 1 fits)
+      tl = (s.T + sw - 1) / sw;
+      if (bytes(tl) <= budget) break;
+    }
+  }
+  p->tile = tl; p->sweeps = (s.T + tl - 1) / tl; p->lds = bytes(tl);
+  return SLODE_OK;
+}
+
+// The plan of slode_recon_quantiles for a shape, a draw count and a level set (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
+// SLODE_EINVAL where the call would refuse them at its own rungs.
+int slode_quantile_plan(const slode_shape* s, int num_samples, int n_levels, const double* levels, int tile, int* tile_out, int* sweeps,
+                        int* depth_lo, int* depth_hi, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: %s", bad);
+  if (!tile_out || !sweeps || !depth_lo || !depth_hi || !lds_bytes)
+    return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: tile_out / sweeps / depth_lo / depth_hi / lds_bytes is NULL");
+  QuantilePlan p{};
+  char why[448];
+  if (quantile_plan(*s, num_samples, n_levels, levels, tile, 0, &p, why, sizeof(why)) != SLODE_OK) return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: %s", why);
+  *tile_out = p.tile; *sweeps = p.sweeps; *depth_lo = p.depth_lo; *depth_hi = p.depth_hi; *lds_bytes = p.lds;
+  return SLODE_OK;
+}
+
+// Sample quantiles of the head curves over num_samples latent draws (include/slode.h): refusals first -- slode_recon_moments' for the same
+// is_post without its LDS rung, then the call's own (out, the levels, the tile, the plan's refusal as the LDS rung); nothing launched, no draw
+// consumed -- then slode_recon_moments' launches with the quantile kernel in place of its own.
+int slode_recon_quantiles(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                          const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int n_levels, const double* levels, int tile,
+                          float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const DrawsCall d("slode_recon_quantiles", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+                    "sort recon_samples instead", nullptr);
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (!out) return fail(h, SLODE_EINVAL, "slode_recon_quantiles: out is NULL");
+  ReconQuantilesLaunch a{};
+  QuantilePlan p{};
+  char why[448];
+  if (quantile_plan(*s, num_samples, n_levels, levels, tile, h->ode_generic, &p, why, sizeof(why)) != SLODE_OK)
+    return fail(h, SLODE_EINVAL, "slode_recon_quantiles: %s", why);
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
+  a.d.rng_calls = num_samples;   // the counter moves by num_samples whatever the number of sweeps; the noise: rows k * B + b of drawing call n
+  a.out = out; a.n_levels = n_levels; a.tile = p.tile; a.depth_lo = p.depth_lo; a.depth_hi = p.depth_hi;
+  for (int i = 0; i < SLODE_QUANTILE_MAX_LEVELS; ++i) { a.slot_lo[i] = p.slot_lo[i]; a.slot_hi[i] = p.slot_hi[i]; a.g[i] = p.g[i]; }
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_recon_quantiles(a, st); });
+}
+
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
 int slode_num_stage_times_n(const slode_shape* s, int n_times) {
   if (!s || n_times < 2 || n_times > SLODE_FORECAST_MAX_T) return SLODE_EINVAL;

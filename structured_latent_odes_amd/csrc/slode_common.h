@@ -569,7 +569,7 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary; intervene: the posterior
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary, quantiles; intervene: the posterior
 // alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
 // row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
 struct DrawsLaunch {
@@ -701,6 +701,21 @@ struct CurveSummaryLaunch {
 #define SLODE_CURVE_SUMMARY_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, grid and node weights, value table, counts, moment triples, staged weights) must fit
 hipError_t slode_launch_curve_summary(const CurveSummaryLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_curve_summary_lds_bytes(const slode_shape& s, int want_p_beyond, int force_generic);
+
+// Sample quantiles (recon_quantiles_kernel.hip; slode_recon_quantiles): over the draws of d per trajectory, out [n_levels, Q, B, C, T] =
+// fma(g, v[hi] - v[lo], v[lo]) of the sorted draw values, served from two sorted LDS buffers per value column: the depth_lo smallest
+// (slots 0 .. depth_lo - 1 = ranks 0 ..) and the depth_hi largest (slots depth_lo + j = rank K - 1 - j); slot_lo / slot_hi: the buffer slots
+// of the two ranks of a level; tile: time points per sweep over the draws (1 <= tile <= T).  All from quantile_plan (slode_api.hip).
+struct ReconQuantilesLaunch {
+  DrawsLaunch d;
+  float* out;
+  int n_levels, tile, depth_lo, depth_hi;
+  int slot_lo[SLODE_QUANTILE_MAX_LEVELS], slot_hi[SLODE_QUANTILE_MAX_LEVELS];
+  float g[SLODE_QUANTILE_MAX_LEVELS];
+};
+#define SLODE_RECON_QUANTILES_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, staged weights, level table, sorted buffers) must fit
+hipError_t slode_launch_recon_quantiles(const ReconQuantilesLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_recon_quantiles_lds_bytes(const slode_shape& s, int depth, int tile, int force_generic);
 
 // Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
 // from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]

@@ -908,6 +908,39 @@ class Engine:
                          self._p(mean), self._p(sd), self._p(p_beyond))
         return mean, sd, p_beyond
 
+    # ---- sample quantiles: order statistics of every curve value over the draws ------------------------------------------------------------
+    @staticmethod
+    def _levels(levels):
+        """``levels`` (a sequence or tensor of floats) as a C array of doubles and its length."""
+        vals = [float(v) for v in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
+        return (C.c_double * max(1, len(vals)))(*vals), len(vals)
+
+    def quantile_plan(self, B: int, num_samples: int, levels, tile: int = 0):
+        """``slode_quantile_plan``: ``(tile, sweeps, depth_lo, depth_hi, lds_bytes)`` of ``recon_quantiles`` for this shape, draw count and
+        level set -- the time points per sweep, the passes over the draws, the depths of the two sorted buffers and the kernel's dynamic
+        LDS bytes (host arithmetic only; raises SlodeError where the call would refuse them at its own rungs)."""
+        arr, n = self._levels(levels)
+        t, sw, lo, hi, nbytes = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_quantile_plan(C.byref(self.shape(B)), int(num_samples), n, arr, int(tile), C.byref(t), C.byref(sw),
+                                                            C.byref(lo), C.byref(hi), C.byref(nbytes)))
+        return int(t.value), int(sw.value), int(lo.value), int(hi.value), int(nbytes.value)
+
+    def recon_quantiles(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, levels, out=None, tile: int = 0, particles: int = 1):
+        """slode_recon_quantiles: per trajectory, head curve, channel and time point, the sample quantiles (numpy's "linear" definition) at
+        ``levels`` (at most ``L.QUANTILE_MAX_LEVELS`` values in [0, 1], any order) of the ``num_samples`` latent draws ``recon_moments``
+        walks on the same side and noise: ``out`` float32 [n_levels, Q, B, C, T] (None: allocated), returned.  A level whose rank is an
+        integer (0, 1, ...) is one of the draw values exactly.  ``tile``: time points per sweep over the draws, 0 = the library's choice
+        (``quantile_plan``).  Enqueued on the current stream; nothing sized num_samples x B x C x T exists anywhere.  The batch's eps is
+        [num_samples, B, L] or None (rows k * B + b of drawing call n; the counter moves to n + num_samples).  Raises SlodeError naming the
+        reason for what the kernel does not take (everything ``recon_moments`` refuses on that side; the level count; a level outside
+        [0, 1]; the tile; LDS budget): nothing is launched and no draw is consumed then."""
+        arr, n = self._levels(levels)
+        Q, _, Cn, T = self._head_shape(B)
+        out = self._out(out, "out", (max(n, 1), Q, B, Cn, T))
+        self._batch_call(self.lib.slode_recon_quantiles, params, batch, B, particles, 1 if is_post else 0, int(num_samples), n, arr, int(tile),
+                         self._p(out))
+        return out
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

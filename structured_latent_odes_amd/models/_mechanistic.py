@@ -1150,6 +1150,117 @@ class MechanisticBase(nn.Module):
             cells.append(cell)
         return "curve_summary_%s: n=%d  %s" % (tag, m.shape[0], "  ".join(cells))
 
+    # ---- sample quantiles: the credible band, the envelope, the median of every curve value over the draws ------------------------------
+    QUANTILE_MAX_LEVELS = 8     # SLODE_QUANTILE_MAX_LEVELS
+
+    @staticmethod
+    def _quantile_ranks(levels, K: int):
+        """``[(lo, hi, g)]`` per level for ``K`` sorted draws, numpy's default "linear" definition as ``slode_recon_quantiles`` forms it on the
+        host in fp64: h = q (K - 1), lo = floor(h), hi = min(lo + 1, K - 1), g = float32(h - lo) (returned as the Python float of that fp32)."""
+        import math
+        import struct
+        res = []
+        for q in levels:
+            h = float(q) * (K - 1)
+            lo = min(max(int(math.floor(h)), 0), K - 1)
+            res.append((lo, min(lo + 1, K - 1), struct.unpack("f", struct.pack("f", h - lo))[0]))
+        return res
+
+    def _sample_quantiles(self, v, levels):
+        """The quantiles at ``levels`` over the draw axis of the curves ``v`` ``[rows, C, T, ns]``: ``[Lv, rows, C, T]`` float32 -- a sort
+        along the draws and ``fma(g, v[hi] - v[lo], v[lo])`` on the ranks of ``_quantile_ranks`` (the difference rounded to fp32, the
+        multiply-add formed in fp64 and rounded once), the rule of ``slode_recon_quantiles``.  Not ``torch.quantile``: its interpolation is
+        not pinned and it limits the input size."""
+        s = torch.sort(v.to(torch.float32), dim=-1).values
+        out = []
+        for lo, hi, g in self._quantile_ranks(levels, s.shape[-1]):
+            v_lo, v_hi = s[..., lo], s[..., hi]
+            out.append((g * (v_hi - v_lo).to(torch.float64) + v_lo.to(torch.float64)).to(torch.float32))
+        return torch.stack(out, 0)
+
+    def recon_quantiles(self, observations, is_post, num_samples: int, levels=(0.025, 0.975), eps=None, tile: int = 0, max_sweeps: int = 2,
+                        **labels):
+        """What users of ``multiple_samples`` take first -- ``np.percentile(samples, [2.5, 97.5], axis=-1)``, the credible band around a
+        curve, the envelope, the median -- without the samples: ``{"levels": [Lv] (float64), "mu_50": [Lv, B, C, T], "mu_75": ..., "mu_25":
+        ...}`` (``"mean"`` for the Gaussian family), the sample quantiles (numpy's default "linear" definition) at ``levels`` (1 to 8 values
+        in [0, 1], any order) of every head curve value over ``num_samples`` latent draws.  ONE engine call (``slode_recon_quantiles``) on
+        the draws of ``recon_moments`` that keeps only the ranks it needs, sorted, on chip: no ``[B, C, T, num_samples]`` tensor exists.
+        A level whose rank is an integer (0: the minimum, 1: the maximum) is one of the draw values exactly.  ``eps`` ``[num_samples, B,
+        L]`` makes it reproducible; None: rows k * B + b of one drawing call of the engine's generator, the draw ``recon_samples`` makes,
+        and the counter moves by ``num_samples``.  ``tile``: time points per sweep over the draws (0: the engine's choice,
+        ``Engine.quantile_plan``).  The composed route -- ``recon_samples`` over chunks of trajectories, ``torch.sort`` along the draws, the
+        same rank rule -- is taken where the engine refuses (adaptive solver, strided observations, measured arms, LDS budget) or where
+        the plan needs more than ``max_sweeps`` sweeps (central levels at many draws keep every draw per value: from three sweeps on the
+        sort was measured faster)."""
+        b = self._bind()
+        B, ns = observations.shape[0], self._count(num_samples)
+        lv = [float(x) for x in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
+        if not 1 <= len(lv) <= self.QUANTILE_MAX_LEVELS:
+            raise ValueError("levels must hold 1 to %d values, got %d" % (self.QUANTILE_MAX_LEVELS, len(lv)))
+        if any(not 0.0 <= x <= 1.0 for x in lv):
+            raise ValueError("levels must lie in [0, 1], got %r" % (lv,))
+        T = int(self.times.numel())
+        if not 0 <= int(tile) <= T:
+            raise ValueError("tile must lie in [0, T = %d], got %d" % (T, int(tile)))
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+
+        def pack(out):
+            return dict({"levels": torch.tensor(lv, dtype=torch.float64)}, **{n: out[q] for q, n in enumerate(names)})
+
+        def fused():
+            return pack(b.engine.recon_quantiles(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, lv, None, int(tile))
+                        .unbind(1))
+
+        def composed():
+            n0 = b.engine.rng_state()[2] if eps is None else None
+            parts = {n: [] for n in names}
+            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
+                for n in names:
+                    parts[n].append(self._sample_quantiles(res[n], lv))
+                del res
+            if n0 is not None:
+                b.engine.rng_set_counter(n0 + ns)      # as the engine call leaves it
+            return pack([torch.cat(parts[n], 1) for n in names])
+
+        def planned():
+            if b.engine.quantile_plan(B, ns, lv, int(tile))[1] > int(max_sweeps):
+                return composed()
+            return fused()
+        return self._fused_or_composed(planned, composed)
+
+    def save_recon_quantiles(self, results_dir: str, batches, is_post, num_samples: int, levels=(0.025, 0.975)):
+        """Runs ``recon_quantiles`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
+        ``<curve>_<post|prior>_sample_quantiles.npy``, float32 ``[n, Lv, C, T]`` (the trajectories in loader order), for every head curve and
+        ``sample_quantile_levels.npy``, the levels.  One read-back, at the end.  Returns the paths."""
+        import os
+        import numpy as np
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        parts = {n: [] for n in names}
+        lv = None
+        for d in batches:
+            r = self.recon_quantiles(is_post=is_post, num_samples=num_samples, levels=levels, **d)
+            lv = r["levels"]
+            for n in names:
+                parts[n].append(r[n].transpose(0, 1))
+        tag = "post" if is_post else "prior"
+        written = self._save_arrays(results_dir, (("%s_%s_sample_quantiles.npy" % (n, tag), torch.cat(v, 0)) for n, v in parts.items() if v))
+        os.makedirs(results_dir, exist_ok=True)
+        path = os.path.join(results_dir, "sample_quantile_levels.npy")
+        np.save(path, np.asarray([] if lv is None else lv.tolist(), dtype=np.float64))
+        return written + [path]
+
+    @staticmethod
+    def quantile_line(quantiles, levels, observations, tag):
+        """One printed line of a ``save_recon_quantiles`` pass from the central curve's array ``[n, Lv, C, T]``, its levels and the
+        observations ``[n, C, T]``: the mean width of the band between the lowest and the highest level, and the share of observation
+        points inside it (bounds included)."""
+        import numpy as np
+        qv, lv, y = np.asarray(quantiles, dtype=np.float64), np.asarray(levels, dtype=np.float64), np.asarray(observations, dtype=np.float64)
+        lo, hi = qv[:, int(lv.argmin())], qv[:, int(lv.argmax())]
+        return "sample_quantiles_%s: n=%d  levels=[%g, %g]  mean_width=%.4g  inside=%.3f" % (
+            tag, qv.shape[0], lv.min(), lv.max(), (hi - lo).mean(), ((y >= lo) & (y <= hi)).mean())
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 

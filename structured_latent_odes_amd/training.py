@@ -113,7 +113,8 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           test_batches: Optional[Sequence[dict]] = None, fused_stats: bool = False, sample_moments: bool = False,
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
-          curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above"):
+          curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
+          quantile_levels=(0.025, 0.975)):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -152,7 +153,11 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     curve_summary = K > 0: after training, the best model's curve summaries over the validation loader from K draws, posterior and prior
     (``save_curve_summary``: ``summary_<curve>_<post|prior>_{mean,sd}.npy`` [n, C, 8], ``summary_slots.npy``) and one printed line per side
     (``curve_summary_post: ...``: per channel of the central curve, the mean peak, time to peak and AUC and, with ``summary_thresholds`` --
-    one level per channel, ``summary_sense`` "above" or "below" --, P(cross) and the mean t_hit); 0 (the default): no such stage runs."""
+    one level per channel, ``summary_sense`` "above" or "below" --, P(cross) and the mean t_hit); 0 (the default): no such stage runs.
+    sample_quantiles = K > 0: after training, the best model's sample quantiles at ``quantile_levels`` over the validation loader from K
+    draws, posterior and prior (``save_recon_quantiles``: ``<curve>_<post|prior>_sample_quantiles.npy`` [n, Lv, C, T],
+    ``sample_quantile_levels.npy``) and one printed line per side (``sample_quantiles_post: ...``: the mean width of the band between the
+    lowest and the highest level of the central curve and the share of observation points inside it); 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -285,6 +290,17 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                            summary_thresholds is not None)
             print(line)
             logging.debug("%s (%s)", line, written)
+    if sample_quantiles:
+        for is_post in (True, False):
+            tag = "post" if is_post else "prior"
+            written = best_model.save_recon_quantiles(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(sample_quantiles),
+                                                      levels=quantile_levels)
+            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
+            obs = np.concatenate([np.asarray(batch_to_device(b, "cpu", family)["observations"]) for b in val_b], 0)
+            line = best_model.quantile_line(np.load([f for f in written if f.endswith("%s_%s_sample_quantiles.npy" % (central, tag))][0]),
+                                            np.load([f for f in written if f.endswith("sample_quantile_levels.npy")][0]), obs, tag)
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -373,6 +389,12 @@ def build_parser():
                     help="one level per channel for --curve-summary (default: none; the threshold entries are then NaN)")
     ap.add_argument("--summary-sense", choices=("above", "below"), default="above",
                     help="which side of --summary-thresholds counts as beyond (default: above)")
+    ap.add_argument("--sample-quantiles", type=int, default=0, metavar="K",
+                    help="after training: the best model's sample quantiles of every head curve over the validation loader from K draws, posterior "
+                         "and prior (save_recon_quantiles: <curve>_<post|prior>_sample_quantiles.npy, sample_quantile_levels.npy) -- the mean band "
+                         "width and the share of observation points inside the band, one line per side")
+    ap.add_argument("--quantile-levels", type=lambda v: [float(x) for x in v.split(",")], default=[0.025, 0.975], metavar="a,b,...",
+                    help="the levels of --sample-quantiles, 1 to 8 values in [0, 1] (default: 0.025,0.975)")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -406,6 +428,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["attribution"] = a.attribution
     if a.curve_summary:
         kw["curve_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.curve_summary, a.summary_thresholds, a.summary_sense
+    if a.sample_quantiles:
+        kw["sample_quantiles"], kw["quantile_levels"] = a.sample_quantiles, a.quantile_levels
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
