@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 260 /* 0.2.6: slode_recon_quantiles, slode_quantile_plan (0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 270 /* 0.2.7: slode_mechanism_moments, slode_mechanism_plan (0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -47,6 +47,7 @@ extern "C" {
 #define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
 #define SLODE_SUMMARY_SLOTS 8 /* functionals of one slode_curve_summary row: peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed */
 #define SLODE_QUANTILE_MAX_LEVELS 8 /* most levels of one slode_recon_quantiles call */
+#define SLODE_MECHANISM_SLOTS 5 /* slots of slode_mechanism_moments: state, production, degradation, set_point, net_rate */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
 typedef enum slode_status {
@@ -675,6 +676,47 @@ int slode_recon_quantiles(slode_handle h, const slode_shape* s, const slode_layo
                           const double* levels /* HOST [n_levels] */, int tile, float* out /* [n_levels,Q,B,C,T] */, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- mechanism curves as ONE call: the moments of what the dynamics say at every grid point (no reference counterpart: the reference's
+ * dynamics are dx/dt = a(t, z) - d(t, z) x, production a and degradation d both sigmoid outputs of one hidden layer on (t, z) -- a / d is the
+ * moving set point a state relaxes towards, 1 / d its local time constant, a - d x the net rate -- yet only a - d x of one t per launch is
+ * exposed, slode_dynamics_eval) ----
+ * For trajectory b and draw k let x_i be the scheme's state at grid point i = 0 .. T - 1 (x_0 from the init net; the rest with the same bits as
+ * the states slode_recon_moments forms its head values from) and a, d the dynamics net at times[i]: each step's first stage time stage_t[i R]
+ * is bitwise times[i], stage_t[R (T - 1)] is bitwise times[T - 1].  The SLODE_MECHANISM_SLOTS = 5 slots of a draw, per state component s and
+ * grid point i, in fp32:
+ *   0 state        x_i[s]
+ *   1 production   a_s(times[i], z)
+ *   2 degradation  d_s(times[i], z)
+ *   3 set_point    a / d (one correctly rounded division)
+ *   4 net_rate     fmaf(-d, x_i[s], a): the vector field at the grid point
+ *   slots: a bit mask over the five; n_sel: its population count.  mean, sd [n_sel, B, S, T] (T contiguous; the selected slots in increasing
+ *   slot order): mean and POPULATION sd of each value over the num_samples draws, accumulated shifted by the first draw's value as in
+ *   slode_recon_moments (sd may be NULL).  num_samples = 1: sd is exactly 0 and mean is the draw's value.  Non-finite values are not
+ *   special-cased.
+ *   Draws, sides, noise: those of slode_recon_moments -- is_post != 0: three launches ("weff", "enc_fwd2", "mechanism_moments" in
+ *   slode_profile_read); is_post == 0: "mechanism_moments" alone; batch->eps == NULL: ONE drawing call n (row k * B + b, plus first_trajectory),
+ *   the counter left at n + 1; else a dense [num_samples, B, L] tensor.  The result is a function of (parameters, inputs, labels, noise) alone:
+ *   independent of the grid, of where the noise comes from and of which other slots are selected, bitwise reproducible from run to run (every
+ *   output has one owner thread, which takes the draws in the order k = 0 .. num_samples - 1; no atomics); mean does not depend on whether sd is
+ *   asked for.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments on that side
+ * but its LDS rung -- a NULL handle (before anything else); num_samples < 1 (and B x num_samples beyond 2^30 - 1 noise rows); adaptive solver
+ * (dopri5, bosh3, fehlberg2, adaptive_heun); particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; for the posterior,
+ * batch->obs NULL, observation strides the folded encoder path does not take or SLODE_NO_FOLD; for the prior, no label tensors -- and, after the
+ * observation rungs: mean NULL; slots == 0 or bits at or beyond SLODE_MECHANISM_SLOTS; LDS tables (step table 2 (T - 1) S, moment triples
+ * 3 S T per slot, capture table 2 T S, staged weights, 2 L; every piece and every slot's triples a multiple of 16 B) beyond the budget of 160 KiB, naming the slot count.
+ * The caller then selects fewer slots per call (the same noise gives the same bits) or composes slode_ode_solve_fwd and the dynamics net. */
+
+/* The dynamic LDS bytes of slode_mechanism_moments' kernel for a shape and a slot mask: pure host arithmetic -- no handle, no HIP call, works on
+ * a machine without a GPU.  SLODE_EINVAL (the reason is the global text slode_last_error(NULL)) for a bad shape, a bad mask or tables beyond the
+ * budget (*lds_bytes is still written then, so a caller can drop slots). */
+int slode_mechanism_plan(const slode_shape* s, unsigned int slots, size_t* lds_bytes);
+int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, int is_post, int num_samples, unsigned int slots,
+                            float* mean /* [n_sel,B,S,T] */, float* sd /* [n_sel,B,S,T] or NULL */,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- forecast: the posterior (or prior) curves of a trained model on ANY output grid as ONE call (no reference counterpart: the reference solves
  * on the training grid alone; what one asks of a latent ODE first is what this subject's curves look like after the observed window, or on a
  * finer grid) ------------------------------------------------------------------------------------------------------------------------------------
@@ -881,11 +923,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

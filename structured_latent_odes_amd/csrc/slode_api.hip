@@ -1449,6 +1449,52 @@ int slode_recon_quantiles(slode_handle h, const slode_shape* s, const slode_layo
                    [&](hipStream_t st) { return slode_launch_recon_quantiles(a, st); });
 }
 
+// ---- mechanism curves: the draws of slode_recon_moments, the moments of x, a, d, a / d and a - d x at every grid point (include/slode.h) ----
+// The LDS bytes of slode_mechanism_moments for a shape and a slot mask (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
+// SLODE_EINVAL when the call would refuse them at its mask or LDS rung.
+int slode_mechanism_plan(const slode_shape* s, unsigned int slots, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: %s", bad);
+  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: lds_bytes is NULL");
+  const int n_sel = __builtin_popcount(slots & ((1u << SLODE_MECHANISM_SLOTS) - 1));
+  *lds_bytes = slode_mechanism_lds_bytes(*s, n_sel, 0);
+  if (slots == 0 || (slots >> SLODE_MECHANISM_SLOTS))
+    return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: slots = 0x%x selects nothing or has bits at or beyond SLODE_MECHANISM_SLOTS = %d", slots,
+                SLODE_MECHANISM_SLOTS);
+  if (*lds_bytes > SLODE_MECHANISM_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: the LDS tables of T = %d, S = %d, slots = %d (%zu B) exceed the budget of %d B", s->T, s->S,
+                n_sel, *lds_bytes, SLODE_MECHANISM_LDS_MAX);
+  return SLODE_OK;
+}
+
+// Mean / sd over num_samples latent draws of the selected mechanism slots (include/slode.h): refusals first -- slode_recon_moments' for the same
+// is_post without its LDS rung, then the call's own (mean, the mask), then its LDS rung; nothing launched, no draw consumed -- then
+// slode_recon_moments' launches with the mechanism kernel in place of its own.
+int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, int is_post, int num_samples, unsigned int slots, float* mean, float* sd,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  DrawsCall d("slode_mechanism_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+              "compose slode_ode_solve_fwd and the dynamics net instead", nullptr);
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (!mean) return fail(h, SLODE_EINVAL, "slode_mechanism_moments: mean is NULL");
+  if (slots == 0 || (slots >> SLODE_MECHANISM_SLOTS))
+    return fail(h, SLODE_EINVAL, "slode_mechanism_moments: slots = 0x%x selects nothing or has bits at or beyond SLODE_MECHANISM_SLOTS = %d", slots,
+                SLODE_MECHANISM_SLOTS);
+  const int n_sel = __builtin_popcount(slots);
+  char extra[24];
+  snprintf(extra, sizeof(extra), ", slots = %d", n_sel);
+  d.lds_tables = "step table, moment triples, capture table, staged weights";
+  d.lds_advice = "fewer slots per call fit (slode_mechanism_plan)"; d.lds_extra = extra;
+  if ((rc = eval_lds(h, s, d, slode_mechanism_lds_bytes(*s, n_sel, h->ode_generic), SLODE_MECHANISM_LDS_MAX)) != SLODE_OK) return rc;
+  MechanismLaunch a{};
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
+  a.mean = mean; a.sd = sd; a.slots = slots;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_mechanism_moments(a, st); });
+}
+
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
 int slode_num_stage_times_n(const slode_shape* s, int n_times) {
   if (!s || n_times < 2 || n_times > SLODE_FORECAST_MAX_T) return SLODE_EINVAL;

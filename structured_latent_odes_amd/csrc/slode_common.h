@@ -569,7 +569,7 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary, quantiles; intervene: the posterior
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary, quantiles, mechanism; intervene: the posterior
 // alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
 // row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
 struct DrawsLaunch {
@@ -716,6 +716,18 @@ struct ReconQuantilesLaunch {
 #define SLODE_RECON_QUANTILES_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, staged weights, level table, sorted buffers) must fit
 hipError_t slode_launch_recon_quantiles(const ReconQuantilesLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_recon_quantiles_lds_bytes(const slode_shape& s, int depth, int tile, int force_generic);
+
+// Mechanism curves (mechanism_moments_kernel.hip; slode_mechanism_moments): over the draws of d per trajectory, mean / sd [n_sel, B, S, T] of the
+// slots selected by the bit mask `slots` (state, production, degradation, set_point, net_rate; n_sel: its population count, increasing slot
+// order) at every grid point.  sd may be NULL.
+struct MechanismLaunch {
+  DrawsLaunch d;
+  float *mean, *sd;
+  unsigned int slots;
+};
+#define SLODE_MECHANISM_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moment triples, capture table, staged weights) must fit
+hipError_t slode_launch_mechanism_moments(const MechanismLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: a bad mask / the tables do not fit the LDS
+size_t slode_mechanism_lds_bytes(const slode_shape& s, int n_sel, int force_generic);
 
 // Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
 // from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]

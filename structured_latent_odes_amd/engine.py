@@ -941,6 +941,32 @@ class Engine:
                          self._p(out))
         return out
 
+    # ---- mechanism curves: moments of the state, production, degradation, set point and net rate at every grid point ---------------------
+    def mechanism_plan(self, B: int, slots: int) -> int:
+        """``slode_mechanism_plan``: the dynamic LDS bytes of ``mechanism_moments`` for this shape and the slot mask ``slots`` (host arithmetic
+        only; raises SlodeError where the call would refuse them at its mask or LDS rung)."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_mechanism_plan(C.byref(self.shape(B)), int(slots), C.byref(r)))
+        return int(r.value)
+
+    def mechanism_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, slots: int, mean=None, sd=None):
+        """slode_mechanism_moments: per trajectory, state component and grid point, the mean and the population sd over ``num_samples`` latent
+        draws (those of ``recon_moments`` on the same side and noise) of the slots selected by the bit mask ``slots`` (bit i:
+        ``L.MECHANISM_NAMES[i]`` -- the state x, the production a and the degradation d of dx/dt = a - d x at the grid time, the set point
+        a / d, the net rate a - d x).  Returns ``(mean, sd)``: float32 [n_sel, B, S, T] each, the selected slots in increasing slot order
+        (``mean``, ``sd``: None = allocated, or the tensor to write; ``sd=False``: not computed, returned as None).  Enqueued on the current
+        stream; nothing sized num_samples x B x T x S exists anywhere.  Raises SlodeError naming the reason for what the kernel does not take
+        (everything ``recon_moments`` refuses on that side; an empty mask or bits beyond ``L.MECHANISM_SLOTS``; LDS budget): nothing is
+        launched and no draw is consumed then."""
+        slots = int(slots)
+        n_sel = max(1, bin(slots & ((1 << L.MECHANISM_SLOTS) - 1)).count("1"))
+        shp = (n_sel, B, self.spec.ode_state_dim, self.T)
+        mean = self._out(mean, "mean", shp)
+        sd = None if sd is False else self._out(sd, "sd", shp)
+        self._batch_call(self.lib.slode_mechanism_moments, params, batch, B, 1, 1 if is_post else 0, int(num_samples), slots & 0xffffffff,
+                         self._p(mean), self._p(sd))
+        return mean, sd
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

@@ -1261,8 +1261,102 @@ class MechanisticBase(nn.Module):
         return "sample_quantiles_%s: n=%d  levels=[%g, %g]  mean_width=%.4g  inside=%.3f" % (
             tag, qv.shape[0], lv.min(), lv.max(), (hi - lo).mean(), ((y >= lo) & (y <= hi)).mean())
 
+    # ---- mechanism curves: what the dynamics dx/dt = a - d x say at every grid point, over the draws --------------------------------------
+    MECHANISM_NAMES = ("state", "production", "degradation", "set_point", "net_rate")   # the slots of slode_mechanism_moments, bit i each
+    MECHANISM_SLOTS_PER_CALL = None      # most slots of one engine call; None: what the engine's plan says fits the LDS (at most 5)
+
+    def mechanism_moments(self, observations, is_post, num_samples: int, quantities=None, eps=None, **labels):
+        """Why the curves look as they do, in the model's own terms: the dynamics are dx/dt = a(t, z) - d(t, z) x, so a / d is the moving
+        set point each state relaxes towards, 1 / d its local time constant and a - d x the net rate.  Returns ``{"quantities": names,
+        name: (mean, sd), ...}``, mean and population sd over ``num_samples`` latent draws from the posterior q(z | x) (``is_post``) or the
+        conditional prior, ``[B, T, S]`` each (the layout of ``solution_xt``), for ``"state"`` (x at the grid points), ``"production"`` (a
+        at the grid times), ``"degradation"`` (d), ``"set_point"`` (a / d) and ``"net_rate"`` (a - d x); ``quantities`` names the ones
+        wanted (default: all five; an unknown name raises ``ValueError``).  ONE engine call (``slode_mechanism_moments``) on the draws of
+        ``recon_moments`` (same ``eps`` ``[num_samples, B, L]``, or one drawing call: the counter ends at n + 1) where the tables fit the
+        LDS, else the fewest calls that do, all on the same noise: no ``[num_samples, B, T, S]`` tensor exists, and the split changes no
+        bit.  Where the engine refuses (adaptive solver, strided observations, measured arms) the same dict is composed in chunks over B
+        from ``decoder.ode_model.solve_ODE`` and the torch modules ``dynamics.prod`` / ``dynamics.degr`` on ``cat([t_i, z])``."""
+        from .. import _lib as L
+        b = self._bind()
+        B, ns = observations.shape[0], self._count(num_samples)
+        wanted = tuple(self.MECHANISM_NAMES if quantities is None else quantities)
+        unknown = [q for q in wanted if q not in self.MECHANISM_NAMES]
+        if unknown or not wanted:
+            raise ValueError("quantities must name some of %r, got %r" % (self.MECHANISM_NAMES, quantities))
+        sel = sorted({self.MECHANISM_NAMES.index(q) for q in wanted})      # the engine stores the selected slots in increasing slot order
+
+        def pack(mean, sd):      # mean, sd: indexable by position in sel, [rows, T, S] each
+            at = {i: j for j, i in enumerate(sel)}
+            return dict({"quantities": wanted}, **{q: (mean[at[self.MECHANISM_NAMES.index(q)]], sd[at[self.MECHANISM_NAMES.index(q)]]) for q in wanted})
+
+        def fused():
+            eng = b.engine
+            fit = min(len(sel), self.MECHANISM_SLOTS_PER_CALL or L.MECHANISM_SLOTS)
+            while fit > 1:
+                try:
+                    eng.mechanism_plan(B, (1 << fit) - 1)      # the LDS figure depends on the slot count alone
+                    break
+                except L.SlodeError:
+                    fit -= 1
+            n_calls = -(-len(sel) // fit)
+            per = -(-len(sel) // n_calls)
+            bt = self._draws_batch(observations, labels, eps, ns)
+            n0 = None if eps is not None else eng.rng_state()[2]
+            means, sds = [], []
+            for i in range(0, len(sel), per):
+                if n0 is not None:
+                    eng.rng_set_counter(n0)        # every call on the same noise: drawing call n0
+                m, s = eng.mechanism_moments(b.flat, bt, B, is_post, ns, sum(1 << q for q in sel[i:i + per]))
+                means.extend(m.unbind(0)); sds.extend(s.unbind(0))
+            return pack([m.permute(0, 2, 1) for m in means], [s.permute(0, 2, 1) for s in sds])
+
+        def composed():
+            with torch.no_grad():
+                dyn = self.decoder.ode_model.dynamics
+                t = torch.as_tensor(self.times, dtype=torch.float32).reshape(-1)
+                cols = [([], []) for _ in sel]
+                for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                    obs = d.pop("observations")
+                    loc, scale = self._loc_scale(obs, is_post, d)
+                    z = (loc.unsqueeze(0) + scale.unsqueeze(0) * e.to(loc.device)).reshape(ns * (hi - lo), -1).to(torch.float32).contiguous()
+                    x = self.decoder.ode_model.solve_ODE(z).to(torch.float32)                                          # [ns * rows, T, S]
+                    tz = torch.cat([t.to(z.device).reshape(1, -1, 1).expand(z.shape[0], -1, 1), z.unsqueeze(1).expand(-1, t.numel(), -1)], dim=2)
+                    a, dg = dyn.prod(tz).to(torch.float32), dyn.degr(tz).to(torch.float32)                              # [ns * rows, T, S]
+                    vals = (lambda: x, lambda: a, lambda: dg, lambda: a / dg, lambda: a - dg * x)
+                    for j, q in enumerate(sel):
+                        v = vals[q]()
+                        m, s = self._mean_sd(v.reshape(ns, hi - lo, v.shape[1], v.shape[2]).permute(1, 2, 3, 0).contiguous())      # (contiguous draws: the sum's order does not depend on the chunk)
+                        cols[j][0].append(m); cols[j][1].append(s)
+                    del x, a, dg, tz
+                return pack([torch.cat(c[0], 0) for c in cols], [torch.cat(c[1], 0) for c in cols])
+        return self._fused_or_composed(fused, composed)
+
+    def save_mechanism_moments(self, results_dir: str, batches, is_post, num_samples: int):
+        """Runs ``mechanism_moments`` (all five quantities) over ``batches`` (an iterable of device batch dicts: ``observations`` + the label
+        tensors) and writes ``mechanism_<name>_<post|prior>_mean.npy`` / ``..._sd.npy``, float32 ``[n, T, S]`` (the trajectories in loader
+        order).  One read-back, at the end.  Returns the paths."""
+        parts = {(n, k): [] for n in self.MECHANISM_NAMES for k in (0, 1)}
+        for d in batches:
+            r = self.mechanism_moments(is_post=is_post, num_samples=num_samples, **d)
+            for n in self.MECHANISM_NAMES:
+                for k in (0, 1):
+                    parts[(n, k)].append(r[n][k])
+        tag = "post" if is_post else "prior"
+        return self._save_arrays(results_dir, (("mechanism_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.cat(v, 0))
+                                               for (n, k), v in parts.items() if v))
+
+    @staticmethod
+    def mechanism_line(res, tag):
+        """One printed line of a ``save_mechanism_moments`` pass from ``res`` = ``{name: mean array [n, T, S]}`` (``"production"``,
+        ``"degradation"``, ``"set_point"``): per state component, the mean over trajectories and time of the mean production, degradation
+        and set point."""
+        import numpy as np
+        a, d, sp = (np.asarray(res[k], dtype=np.float64) for k in ("production", "degradation", "set_point"))
+        cells = ["x%d a=%.4g d=%.4g a/d=%.4g" % (s, a[..., s].mean(), d[..., s].mean(), sp[..., s].mean()) for s in range(a.shape[-1])]
+        return "mechanism_%s: n=%d  %s" % (tag, a.shape[0], "  ".join(cells))
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
-    BOUND_NAMES = ("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
+    BOUND_NAMES =("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 
     def trajectory_bounds(self, observations, num_draws: int, eps=None, return_draws: bool = False, **labels):
         """Per trajectory, from ``num_draws`` = K posterior draws z_k = loc(x) + scale(x) eps_k: ``{"elbo": [B], "iw_bound": [B], "ess": [B],

@@ -114,7 +114,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
           curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
-          quantile_levels=(0.025, 0.975)):
+          quantile_levels=(0.025, 0.975), mechanism: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -157,7 +157,11 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     sample_quantiles = K > 0: after training, the best model's sample quantiles at ``quantile_levels`` over the validation loader from K
     draws, posterior and prior (``save_recon_quantiles``: ``<curve>_<post|prior>_sample_quantiles.npy`` [n, Lv, C, T],
     ``sample_quantile_levels.npy``) and one printed line per side (``sample_quantiles_post: ...``: the mean width of the band between the
-    lowest and the highest level of the central curve and the share of observation points inside it); 0 (the default): no such stage runs."""
+    lowest and the highest level of the central curve and the share of observation points inside it); 0 (the default): no such stage runs.
+    mechanism = K > 0: after training, the best model's mechanism curves over the validation loader from K draws, posterior and prior
+    (``save_mechanism_moments``: ``mechanism_<name>_<post|prior>_{mean,sd}.npy`` [n, T, S] for the state, production, degradation, set point
+    and net rate) and one printed line per side (``mechanism_post: ...``: per state component, the time-averaged mean production,
+    degradation and set point); 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -301,6 +305,14 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                             np.load([f for f in written if f.endswith("sample_quantile_levels.npy")][0]), obs, tag)
             print(line)
             logging.debug("%s (%s)", line, written)
+    if mechanism:
+        for is_post in (True, False):
+            tag = "post" if is_post else "prior"
+            written = best_model.save_mechanism_moments(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(mechanism))
+            line = best_model.mechanism_line({k: np.load([f for f in written if f.endswith("mechanism_%s_%s_mean.npy" % (k, tag))][0])
+                                              for k in ("production", "degradation", "set_point")}, tag)
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -395,6 +407,10 @@ def build_parser():
                          "width and the share of observation points inside the band, one line per side")
     ap.add_argument("--quantile-levels", type=lambda v: [float(x) for x in v.split(",")], default=[0.025, 0.975], metavar="a,b,...",
                     help="the levels of --sample-quantiles, 1 to 8 values in [0, 1] (default: 0.025,0.975)")
+    ap.add_argument("--mechanism", type=int, default=0, metavar="K",
+                    help="after training: the best model's mechanism curves over the validation loader from K draws, posterior and prior "
+                         "(save_mechanism_moments: mechanism_<name>_<post|prior>_{mean,sd}.npy) -- per state component, the time-averaged mean "
+                         "production, degradation and set point, one line per side")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -430,6 +446,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["curve_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.curve_summary, a.summary_thresholds, a.summary_sense
     if a.sample_quantiles:
         kw["sample_quantiles"], kw["quantile_levels"] = a.sample_quantiles, a.quantile_levels
+    if a.mechanism:
+        kw["mechanism"] = a.mechanism
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:
