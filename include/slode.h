@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 270 /* 0.2.7: slode_mechanism_moments, slode_mechanism_plan (0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 280 /* 0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels (0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -47,6 +47,7 @@ extern "C" {
 #define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
 #define SLODE_SUMMARY_SLOTS 8 /* functionals of one slode_curve_summary row: peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed */
 #define SLODE_QUANTILE_MAX_LEVELS 8 /* most levels of one slode_recon_quantiles call */
+#define SLODE_JOINT_BAND_MAX_LEVELS 8 /* most levels of one slode_joint_band call */
 #define SLODE_MECHANISM_SLOTS 5 /* slots of slode_mechanism_moments: state, production, degradation, set_point, net_rate */
 #define SLODE_FORECAST_MAX_T (1 << 20) /* most points of an output grid (slode_stage_times_n, slode_forecast_moments) */
 
@@ -717,6 +718,53 @@ int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_la
                             float* mean /* [n_sel,B,S,T] */, float* sd /* [n_sel,B,S,T] or NULL */,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- simultaneous (sup-t) credible bands as ONE call (no reference counterpart: a band drawn from per-point intervals -- mean +- z sd of
+ * slode_recon_moments, the quantiles of slode_recon_quantiles -- is read as "the curve lies in here with 95 % probability" and makes no such
+ * claim; how much less it holds depends on how correlated the curve is along time) ----
+ * For trajectory b, head curve q (the order of slode_recon_moments) and channel c let v_k(t) be the K = num_samples draw curves, m(t) and s(t)
+ * their mean and population sd -- the bits slode_recon_moments returns for the same noise, written to mean / sd [Q,B,C,T] -- and
+ *   dev_k = max over the participating t of  fl(fl(|v_k(t) - m(t)|) / s(t))      (fp32; a point takes part when s(t) > sd_floor; no point: 0)
+ * the largest standardised deviation of draw k.  dev_k <= sqrt(K - 1) whatever the model: below about K = 20 a 95 % value is a property of K.
+ * Per level p_j (levels: a HOST array [n_levels] of doubles in (0, 1], read at the call; any order, duplicates allowed; n_levels <=
+ * SLODE_JOINT_BAND_MAX_LEVELS = 8), formed on the host in fp64 (slode_joint_band_levels):
+ *   r_j = min(K, max(1, ceil(p_j K - 1e-9))),   z_j = Phi^-1((1 + p_j) / 2)  (p_j = 1: +inf)
+ *   crit [Q,B,C,n_levels]:  the r_j-th smallest of dev_0 .. dev_{K-1}, counted from 1 -- one of the deviations exactly; mean +- crit sd holds
+ *                           r_j of the K draws over the whole grid
+ *   joint [Q,B,C,n_levels] (or NULL):  #{k : dev_k <= (float)z_j} / K, the share of draws wholly inside the POINTWISE band mean +- z_j sd
+ *   obs_dev [Q,B,C,2] (or NULL):  [0] the deviation of the observed curve y(b, c, .) by the same formula (NaN without observations: the prior
+ *                           with batch->obs == NULL), [1] the number of participating time points, an int32 stored as float
+ *   dev_out [Q,B,C,num_samples] (or NULL):  dev_k itself
+ *   Two sweeps over the draws, the second on the same noise (the counter-based generator redraws it; eps is read twice); each solves the whole
+ *   grid.  Draws, sides: those of slode_recon_moments -- is_post != 0: three launches ("weff", "enc_fwd2", "joint_band" in slode_profile_read);
+ *   is_post == 0: "joint_band" alone.  Noise: batch->eps == NULL: ONE drawing call n (row k * B + b, plus first_trajectory), the counter left
+ *   where one slode_recon_moments call leaves it, whatever the sweeps; else a dense [num_samples, B, L] tensor.
+ *   The result is a function of (parameters, inputs, labels, noise, levels, sd_floor) alone: bitwise independent of the grid and of where the
+ *   noise comes from (every output has one owner thread; maxima and order statistics are selections; no atomics).  Non-finite curve values are
+ *   not ordered: the outputs of such a curve are unspecified.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: a NULL handle (before anything else);
+ * num_samples < 2 (the sd of one draw is 0); every further refusal of slode_recon_moments on that side but its LDS rung -- B x num_samples
+ * beyond 2^30 - 1 noise rows; adaptive solver; particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; for the
+ * posterior, batch->obs NULL, observation strides the folded encoder path does not take or SLODE_NO_FOLD; for the prior, no label tensors, and
+ * observations (optional there) that are not dense [B,T,C] or [B,C,T] -- and, after the observation rungs: mean / sd / crit NULL; n_levels
+ * outside [1, 8]; levels NULL; a level outside (0, 1] or NaN; sd_floor < 0 or not finite; LDS tables (step table 2 (T - 1) S, staged weights,
+ * the table 3 Q C T, the deviations Q C num_samples, 2 L; every piece a multiple of 16 B) beyond 160 KiB.  The caller then reduces
+ * slode_ode_solve_fwd + slode_decode_heads itself. */
+
+/* The kernel's dynamic LDS bytes for (shape, num_samples): pure host arithmetic -- no handle, no HIP call, works on a machine without a GPU.
+ * SLODE_EINVAL (the reason is the global text slode_last_error(NULL)) for a bad shape, num_samples < 2 or tables beyond the budget
+ * (*lds_bytes is still written then). */
+int slode_joint_band_plan(const slode_shape* s, int num_samples, size_t* lds_bytes);
+/* The ranks r_j (counted from 1) and half-widths z_j of slode_joint_band for num_samples draws, as the call forms them: host arithmetic.
+ * SLODE_EINVAL for num_samples < 2, n_levels outside [1, 8], a NULL pointer or a level outside (0, 1]. */
+int slode_joint_band_levels(int num_samples, int n_levels, const double* levels /* HOST [n_levels] */, int* ranks /* [n_levels] */,
+                            double* z /* [n_levels] */);
+int slode_joint_band(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                     const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int n_levels,
+                     const double* levels /* HOST [n_levels] */, float sd_floor, float* mean /* [Q,B,C,T] */, float* sd /* [Q,B,C,T] */,
+                     float* crit /* [Q,B,C,n_levels] */, float* joint /* [Q,B,C,n_levels] or NULL */, float* obs_dev /* [Q,B,C,2] or NULL */,
+                     float* dev_out /* [Q,B,C,num_samples] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- forecast: the posterior (or prior) curves of a trained model on ANY output grid as ONE call (no reference counterpart: the reference solves
  * on the training grid alone; what one asks of a latent ODE first is what this subject's curves look like after the observed window, or on a
  * finer grid) ------------------------------------------------------------------------------------------------------------------------------------
@@ -923,11 +971,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration / slode_joint_band launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -23,6 +23,8 @@ QUANTILE_MAX_LEVELS = 8   # SLODE_QUANTILE_MAX_LEVELS: most levels of one slode_
 RECON_QUANTILES_LDS_MAX = 160 * 1024   # SLODE_RECON_QUANTILES_LDS_MAX: the LDS budget of its kernel
 MECHANISM_SLOTS = 5      # SLODE_MECHANISM_SLOTS: slots of slode_mechanism_moments, one bit each in its mask
 MECHANISM_NAMES = ("state", "production", "degradation", "set_point", "net_rate")
+JOINT_BAND_MAX_LEVELS = 8   # SLODE_JOINT_BAND_MAX_LEVELS: most levels of one slode_joint_band call
+JOINT_BAND_LDS_MAX = 160 * 1024   # SLODE_JOINT_BAND_LDS_MAX: the LDS budget of its kernel
 ATTRIBUTION_MAX_ARMS = 16   # SLODE_ATTRIBUTION_MAX_ARMS: most arms (block masks) of one slode_latent_attribution call
 EVIDENCE_MAX_V = 64    # SLODE_EVIDENCE_MAX_V: most hypotheses of one slode_label_evidence call
 AUX_KINDS = {"sigmoid": 0, "softmax": 1, "expexp": 2}
@@ -81,7 +83,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_initialize_state", "slode_prior_nets", "slode_label_heads", "slode_dopri5_step_counts", "slode_decode_heads_bwd",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
-           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_intervene_moments", "slode_attribution_plan", "slode_latent_attribution", "slode_curve_summary_plan", "slode_curve_summary", "slode_quantile_plan", "slode_recon_quantiles", "slode_mechanism_plan", "slode_mechanism_moments", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
+           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_intervene_moments", "slode_attribution_plan", "slode_latent_attribution", "slode_curve_summary_plan", "slode_curve_summary", "slode_quantile_plan", "slode_recon_quantiles", "slode_mechanism_plan", "slode_mechanism_moments", "slode_joint_band_plan", "slode_joint_band_levels", "slode_joint_band", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
            "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
@@ -166,6 +168,10 @@ def load():
                                           C.c_size_t, VP]
     lib.slode_mechanism_plan.argtypes = [P(Shape), C.c_uint, P(C.c_size_t)]
     lib.slode_mechanism_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, C.c_uint, VP, VP, VP, C.c_size_t, VP]
+    lib.slode_joint_band_plan.argtypes = [P(Shape), C.c_int, P(C.c_size_t)]
+    lib.slode_joint_band_levels.argtypes = [C.c_int, C.c_int, P(C.c_double), P(C.c_int), P(C.c_double)]
+    lib.slode_joint_band.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, C.c_int, P(C.c_double), C.c_float, VP, VP, VP, VP, VP,
+                                     VP, VP, C.c_size_t, VP]
     lib.slode_num_stage_times_n.argtypes = [P(Shape), C.c_int]
     lib.slode_stage_times_n.argtypes = [VP, P(Shape), C.c_int, VP, VP, VP]
     lib.slode_forecast_plan.argtypes = [P(Shape), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_size_t)]

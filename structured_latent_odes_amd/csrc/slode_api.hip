@@ -1495,6 +1495,98 @@ int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_la
                    [&](hipStream_t st) { return slode_launch_mechanism_moments(a, st); });
 }
 
+// ---- simultaneous bands: the draws of slode_recon_moments twice, the quantiles of the draws' largest standardised deviation (include/slode.h) ----
+// z = Phi^-1((1 + p) / 2) = sqrt(2) erfinv(p) for p in (0, 1) in fp64: Winitzki's closed form as the start, then Halley steps on
+// erfc(x) = 1 - p with the C library's erfc (cubic convergence: the third step is already at rounding level)
+static double joint_band_z(double p) {
+  if (p >= 1.0) return INFINITY;
+  const double pi = 3.14159265358979323846, a = 0.147, q = 1.0 - p;
+  const double ln1 = std::log1p(-p * p), t = 2.0 / (pi * a) + 0.5 * ln1;
+  double x = std::sqrt(std::sqrt(t * t - ln1 / a) - t);
+  for (int it = 0; it < 4; ++it) {
+    const double u = (std::erfc(x) - q) / (-2.0 / std::sqrt(pi) * std::exp(-x * x));   // f / f'
+    x -= u / (1.0 + x * u);                                                            // f'' / f' = -2 x
+  }
+  return std::sqrt(2.0) * x;
+}
+// The level rules as data: what slode_joint_band_levels reports and the launch takes.  why: the refusal.
+static int joint_band_levels(int K, int n_levels, const double* levels, int* ranks, double* z, char* why, size_t why_n) {
+  if (K < 2) { snprintf(why, why_n, "num_samples = %d < 2 (the sd of one draw is 0)", K); return SLODE_EINVAL; }
+  if (n_levels < 1 || n_levels > SLODE_JOINT_BAND_MAX_LEVELS) {
+    snprintf(why, why_n, "n_levels = %d out of range [1, %d]", n_levels, SLODE_JOINT_BAND_MAX_LEVELS);
+    return SLODE_EINVAL;
+  }
+  if (!levels) { snprintf(why, why_n, "levels is NULL"); return SLODE_EINVAL; }
+  for (int i = 0; i < n_levels; ++i) {
+    if (!(levels[i] > 0.0 && levels[i] <= 1.0)) { snprintf(why, why_n, "levels[%d] = %g is not in (0, 1]", i, levels[i]); return SLODE_EINVAL; }
+    const double r = std::ceil(levels[i] * (double)K - 1e-9);
+    ranks[i] = r < 1.0 ? 1 : (r > (double)K ? K : (int)r);
+    z[i] = joint_band_z(levels[i]);
+  }
+  return SLODE_OK;
+}
+
+int slode_joint_band_levels(int num_samples, int n_levels, const double* levels, int* ranks, double* z) {
+  if (!ranks || !z) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_levels: ranks / z is NULL");
+  char why[160];
+  int r[SLODE_JOINT_BAND_MAX_LEVELS];
+  double zz[SLODE_JOINT_BAND_MAX_LEVELS];
+  if (joint_band_levels(num_samples, n_levels, levels, r, zz, why, sizeof(why)) != SLODE_OK) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_levels: %s", why);
+  for (int i = 0; i < n_levels; ++i) { ranks[i] = r[i]; z[i] = zz[i]; }
+  return SLODE_OK;
+}
+
+// The LDS bytes of slode_joint_band for a shape and a draw count (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
+// SLODE_EINVAL where the call would refuse them at its draw-count or LDS rung.
+int slode_joint_band_plan(const slode_shape* s, int num_samples, size_t* lds_bytes) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: %s", bad);
+  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: lds_bytes is NULL");
+  if (num_samples < 2) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: num_samples = %d < 2 (the sd of one draw is 0)", num_samples);
+  *lds_bytes = slode_joint_band_lds_bytes(*s, num_samples, 0);
+  if (*lds_bytes > SLODE_JOINT_BAND_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: the LDS tables of T = %d, S = %d, C = %d, num_samples = %d (%zu B: step table, staged "
+                                       "weights, moment / value table, deviations [%d][num_samples]) exceed the budget of %d B", s->T, s->S, s->C,
+                num_samples, *lds_bytes, (s->likelihood == SLODE_GAUSS ? 1 : 3) * s->C, SLODE_JOINT_BAND_LDS_MAX);
+  return SLODE_OK;
+}
+
+// Simultaneous bands over num_samples latent draws (include/slode.h): refusals first -- the draw count, slode_recon_moments' for the same is_post
+// without its LDS rung, then the call's own (outputs, levels, floor, the prior's optional observations), then its LDS rung; nothing launched,
+// no draw consumed -- then slode_recon_moments' launches with the band kernel in place of its own.
+int slode_joint_band(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                     const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int n_levels, const double* levels,
+                     float sd_floor, float* mean, float* sd, float* crit, float* joint, float* obs_dev, float* dev_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  DrawsCall d("slode_joint_band", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+              "reduce recon_samples instead", nullptr);
+  int rc = eval_args(h, s, lay, params, d);
+  if (rc != SLODE_OK) return rc;
+  if (num_samples < 2) return fail(h, SLODE_EINVAL, "slode_joint_band: num_samples = %d < 2 (the sd of one draw is 0)", num_samples);
+  if ((rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  if (!mean || !sd || !crit) return fail(h, SLODE_EINVAL, "slode_joint_band: mean / sd / crit is NULL");
+  JointBandLaunch a{};
+  char why[160];
+  double z[SLODE_JOINT_BAND_MAX_LEVELS];
+  if (joint_band_levels(num_samples, n_levels, levels, a.rank, z, why, sizeof(why)) != SLODE_OK) return fail(h, SLODE_EINVAL, "slode_joint_band: %s", why);
+  for (int i = 0; i < n_levels; ++i) a.z[i] = (float)z[i];
+  if (!(sd_floor >= 0.f) || std::isinf(sd_floor)) return fail(h, SLODE_EINVAL, "slode_joint_band: sd_floor = %g is negative or not finite", (double)sd_floor);
+  const int64_t* os = batch->obs_strides;
+  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
+  if (batch->obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))   // (the posterior: eval_refuse has refused these already)
+    return fail(h, SLODE_EINVAL, "slode_joint_band: observation strides (%lld, %lld, %lld) are not taken: the observed deviation needs dense "
+                                 "[B,T,C] or [B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
+  d.lds_tables = "step table, staged weights, moment / value table, deviations";
+  d.lds_advice = "fewer draws fit (slode_joint_band_plan), or reduce recon_samples instead"; d.lds_per_draw = true;
+  if ((rc = eval_lds(h, s, d, slode_joint_band_lds_bytes(*s, num_samples, h->ode_generic), SLODE_JOINT_BAND_LDS_MAX)) != SLODE_OK) return rc;
+  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);   // (rng_calls stays 1: the counter moves as slode_recon_moments moves it)
+  a.obs = batch->obs; a.t_major = t_major && !c_major ? 1 : 0; a.n_levels = n_levels; a.sd_floor = sd_floor;
+  a.mean = mean; a.sd = sd; a.crit = crit; a.joint = joint; a.obs_dev = obs_dev; a.dev_out = dev_out;
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
+                   [&](hipStream_t st) { return slode_launch_joint_band(a, st); });
+}
+
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
 int slode_num_stage_times_n(const slode_shape* s, int n_times) {
   if (!s || n_times < 2 || n_times > SLODE_FORECAST_MAX_T) return SLODE_EINVAL;

@@ -569,7 +569,7 @@ struct EvalLaunch {
 hipError_t slode_launch_eval(const EvalLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the step table does not fit the LDS
 size_t slode_eval_lds_bytes(const slode_shape& s);
 
-// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary, quantiles, mechanism; intervene: the posterior
+// What the calls that walk num_samples latent draws per trajectory from ONE source share (recon, forecast, cohort, attribution, curve summary, quantiles, mechanism, joint band; intervene: the posterior
 // alone).  is_post: loc / scale [B, L] from the encoder launch; else the kernel evaluates the conditional prior nets (u / lab).  Noise: rng.on:
 // row k * B + b of ONE drawing call; else eps [num_samples, B, L].  times / stage_t: the grid the kernel solves on.
 struct DrawsLaunch {
@@ -728,6 +728,24 @@ struct MechanismLaunch {
 #define SLODE_MECHANISM_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, moment triples, capture table, staged weights) must fit
 hipError_t slode_launch_mechanism_moments(const MechanismLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: a bad mask / the tables do not fit the LDS
 size_t slode_mechanism_lds_bytes(const slode_shape& s, int n_sel, int force_generic);
+
+// Simultaneous bands (joint_band_kernel.hip; slode_joint_band): over the draws of d per trajectory, twice on the same noise: mean / sd
+// [Q, B, C, T] as recon_moments; crit / joint [Q, B, C, n_levels]: the rank[j]-th smallest (from 1) of the draws' largest standardised
+// deviations and the share of them <= z[j]; obs_dev [Q, B, C, 2]: the observed curve's deviation | participating points; dev_out
+// [Q, B, C, num_samples]: the deviations.  joint, obs_dev, dev_out may be NULL.  obs: dense rows of C*T floats, t_major: [T][C] inside a
+// row, else [C][T]; NULL: no observed deviation (NaN).  A point takes part when its sd > sd_floor >= 0.
+struct JointBandLaunch {
+  DrawsLaunch d;
+  const float* obs;
+  int t_major, n_levels;
+  int rank[SLODE_JOINT_BAND_MAX_LEVELS];
+  float z[SLODE_JOINT_BAND_MAX_LEVELS];
+  float sd_floor;
+  float *mean, *sd, *crit, *joint, *obs_dev, *dev_out;
+};
+#define SLODE_JOINT_BAND_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, staged weights, moment / value table, deviations) must fit
+hipError_t slode_launch_joint_band(const JointBandLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_joint_band_lds_bytes(const slode_shape& s, int num_samples, int force_generic);
 
 // Forecast moments (forecast_moments_kernel.hip; slode_forecast_moments): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
 // from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan): mean / sd [Q, B, C, T_out]

@@ -1,5 +1,5 @@
 // The fixed-grid forward pass and the draw loop the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
-// intervene_moments_kernel.hip, attribution_kernel.hip, curve_summary_kernel.hip, recon_quantiles_kernel.hip, mechanism_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip, calibration_kernel.hip, refine_kernel.hip; no other translation unit includes this
+// intervene_moments_kernel.hip, attribution_kernel.hip, curve_summary_kernel.hip, recon_quantiles_kernel.hip, mechanism_moments_kernel.hip, joint_band_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip, calibration_kernel.hip, refine_kernel.hip; no other translation unit includes this
 // header): each phase ONCE --
 //   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads),
 //                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort, calibration) and the host functions that

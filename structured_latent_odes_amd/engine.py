@@ -967,6 +967,44 @@ class Engine:
                          self._p(mean), self._p(sd))
         return mean, sd
 
+    # ---- simultaneous bands: the quantiles over the draws of the largest standardised deviation of a whole curve -------------------------
+    def joint_band_plan(self, B: int, num_samples: int) -> int:
+        """``slode_joint_band_plan``: the dynamic LDS bytes of ``joint_band`` for this shape and draw count (host arithmetic only; raises
+        SlodeError where the call would refuse them at its draw-count or LDS rung)."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_joint_band_plan(C.byref(self.shape(B)), int(num_samples), C.byref(r)))
+        return int(r.value)
+
+    def joint_band_levels(self, num_samples: int, levels):
+        """``slode_joint_band_levels``: ``(ranks, z)`` of ``joint_band`` for ``num_samples`` draws as the call forms them on the host in
+        fp64 -- per level p the rank r = min(K, max(1, ceil(p K - 1e-9))), counted from 1, and z = Phi^-1((1 + p) / 2) (inf at p = 1)."""
+        arr, n = self._levels(levels)
+        ranks, z = (C.c_int * max(1, n))(), (C.c_double * max(1, n))()
+        _check(self.lib, None, self.lib.slode_joint_band_levels(int(num_samples), n, arr, ranks, z))
+        return [int(v) for v in ranks[:n]], [float(v) for v in z[:n]]
+
+    def joint_band(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, levels, sd_floor: float = 0.0, mean=None, sd=None,
+                   crit=None, joint=None, obs_dev=None, dev=None):
+        """slode_joint_band: per trajectory, head curve and channel, over the ``num_samples`` = K latent draws ``recon_moments`` walks on the
+        same side and noise: ``mean``, ``sd`` float32 [Q, B, C, T] (its bits), the deviations dev_k = max_t |v_k(t) - mean(t)| / sd(t) over
+        the points with sd > ``sd_floor``, and per level (1 to ``L.JOINT_BAND_MAX_LEVELS`` values in (0, 1], any order) ``crit`` [Q, B, C,
+        Lv], the r-th smallest deviation (``joint_band_levels``), and ``joint`` [Q, B, C, Lv], the share of draws with dev_k <= z: wholly
+        inside the pointwise band.  ``obs_dev`` [Q, B, C, 2]: the observed curve's deviation and the number of participating points.
+        ``dev``: None = not returned, True = allocated, or the tensor [Q, B, C, K] to write.  Returns ``(mean, sd, crit, joint, obs_dev,
+        dev)``.  Enqueued on the current stream; nothing sized K x B x C x T exists anywhere.  The batch's eps is [K, B, L] or None (one
+        drawing call, as ``recon_moments``).  Raises SlodeError naming the reason for what the kernel does not take (everything
+        ``recon_moments`` refuses on that side; K < 2; the level count; a level outside (0, 1]; a negative or non-finite floor; LDS budget):
+        nothing is launched and no draw is consumed then."""
+        arr, n = self._levels(levels)
+        Q, _, Cn, T = self._head_shape(B)
+        mean, sd = self._out(mean, "mean", (Q, B, Cn, T)), self._out(sd, "sd", (Q, B, Cn, T))
+        crit, joint = self._out(crit, "crit", (Q, B, Cn, max(n, 1))), self._out(joint, "joint", (Q, B, Cn, max(n, 1)))
+        obs_dev = self._out(obs_dev, "obs_dev", (Q, B, Cn, 2))
+        dev = None if dev is None else self._out(None if dev is True else dev, "dev", (Q, B, Cn, max(int(num_samples), 1)))
+        self._batch_call(self.lib.slode_joint_band, params, batch, B, 1, 1 if is_post else 0, int(num_samples), n, arr, float(sd_floor),
+                         self._p(mean), self._p(sd), self._p(crit), self._p(joint), self._p(obs_dev), self._p(dev))
+        return mean, sd, crit, joint, obs_dev, dev
+
     # ---- data parallel with the small payload: grad_partial -> all-reduce(payload) -> grad_apply (include/slode.h) ------------------
     def payload_floats(self, kind: int) -> int:
         return int(self.lib.slode_grad_payload_floats(C.byref(self.shape(1)), C.byref(self.layout), int(kind)))

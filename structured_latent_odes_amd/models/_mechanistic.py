@@ -1355,6 +1355,131 @@ class MechanisticBase(nn.Module):
         cells = ["x%d a=%.4g d=%.4g a/d=%.4g" % (s, a[..., s].mean(), d[..., s].mean(), sp[..., s].mean()) for s in range(a.shape[-1])]
         return "mechanism_%s: n=%d  %s" % (tag, a.shape[0], "  ".join(cells))
 
+    # ---- simultaneous (sup-t) credible bands: one critical value per curve, from the draws' largest standardised deviation ----------------
+    BAND_MAX_LEVELS = 8     # SLODE_JOINT_BAND_MAX_LEVELS
+
+    @staticmethod
+    def _band_levels(levels, K: int):
+        """``[(r, z)]`` per level for ``K`` draws, as ``slode_joint_band`` forms them on the host in fp64: the rank r = min(K, max(1,
+        ceil(level K - 1e-9))), counted from 1, and the pointwise half-width z = Phi^-1((1 + level) / 2) (inf at level 1)."""
+        import math
+        from statistics import NormalDist
+        return [(min(K, max(1, int(math.ceil(float(p) * K - 1e-9)))), math.inf if float(p) >= 1.0 else NormalDist().inv_cdf((1.0 + float(p)) / 2.0))
+                for p in levels]
+
+    def simultaneous_band(self, observations, is_post, num_samples: int, levels=(0.95,), sd_floor: float = 0.0, eps=None,
+                          return_draws: bool = False, **labels):
+        """The band that may be read as a statement about the WHOLE curve.  A band drawn from per-point intervals (``mean +- 1.96 sd`` of
+        ``recon_moments``, the quantiles of ``recon_quantiles``) holds each point with 95 % probability and the entire curve with less --
+        how much less depends on how correlated the curve is along time.  The simultaneous (sup-t) band is ``mean +- crit sd`` with ONE
+        number per curve: the level-quantile over the ``num_samples`` = K draws of dev_k = max_t |v_k(t) - mean(t)| / sd(t).  Returns
+        ``{"levels": [Lv] (float64), "mu_50": {...}, "mu_75": ..., "mu_25": ...}`` (``"mean"`` for the Gaussian family), per head curve a
+        dict with ``"mean"``, ``"sd"`` ``[B, C, T]`` (the tensors of ``recon_moments`` on the same noise), ``"crit"`` ``[Lv, B, C]`` (the
+        r-th smallest deviation, r = ceil(level K): one of the deviations exactly), ``"lower"`` / ``"upper"`` ``[Lv, B, C, T]`` (``mean -+
+        crit sd``), ``"pointwise_joint"`` ``[Lv, B, C]`` (the share of draws wholly inside the POINTWISE band ``mean +- z sd``, z =
+        Phi^-1((1 + level) / 2): what the naive band really holds), ``"obs_dev"`` ``[B, C]`` (the deviation of the observed curve),
+        ``"obs_inside"`` ``[Lv, B, C]`` (bool: ``obs_dev <= crit``, the observation leaves the band nowhere), ``"points"`` ``[B, C]`` (the
+        time points with ``sd > sd_floor``; the others take no part) and, with ``return_draws``, ``"dev"`` ``[K, B, C]``.  1 to 8 levels in
+        (0, 1], any order.  The deviation of a draw from its own sample mean is bounded by sqrt(K - 1) sample sds whatever the model:
+        below about K = 20 a 95 % critical value is a property of K, not of the model.  ONE engine call (``slode_joint_band``) that walks
+        the draws of ``recon_moments`` twice on the same noise: no ``[B, C, T, K]`` tensor exists.  ``eps`` ``[K, B, L]`` makes it
+        reproducible; None: one drawing call of the engine's generator, as ``recon_moments``.  Where the engine refuses (adaptive solver,
+        strided observations, measured arms, LDS budget) the same dict is composed from ``recon_samples`` in chunks over B: torch mean /
+        population std, the same division, ``amax`` over T, ``torch.sort`` over the draws, the same rank rule."""
+        import math
+        b = self._bind()
+        B, ns = observations.shape[0], self._count(num_samples)
+        if ns < 2:
+            raise ValueError("num_samples must be >= 2 (the sd of one draw is 0), got %d" % ns)
+        lv = [float(x) for x in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
+        if not 1 <= len(lv) <= self.BAND_MAX_LEVELS:
+            raise ValueError("levels must hold 1 to %d values, got %d" % (self.BAND_MAX_LEVELS, len(lv)))
+        if any(not 0.0 < x <= 1.0 for x in lv):
+            raise ValueError("levels must lie in (0, 1], got %r" % (lv,))
+        floor = float(sd_floor)
+        if not (floor >= 0.0 and math.isfinite(floor)):
+            raise ValueError("sd_floor must be finite and >= 0, got %r" % (sd_floor,))
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+
+        def pack(per_curve):      # per_curve[q] = (mean, sd [rows, C, T], crit, joint [rows, C, Lv], obs_dev, points [rows, C], dev [rows, C, K])
+            out = {"levels": torch.tensor(lv, dtype=torch.float64)}
+            for n, (mean, sd, crit, joint, odev, points, dev) in zip(names, per_curve):
+                crit, joint = crit.permute(2, 0, 1), joint.permute(2, 0, 1)
+                half = crit.unsqueeze(-1) * sd.unsqueeze(0)
+                out[n] = {"mean": mean, "sd": sd, "crit": crit, "lower": mean.unsqueeze(0) - half, "upper": mean.unsqueeze(0) + half,
+                          "pointwise_joint": joint, "obs_dev": odev, "obs_inside": odev.unsqueeze(0) <= crit, "points": points}
+                if return_draws:
+                    out[n]["dev"] = dev.permute(2, 0, 1)
+            return out
+
+        def fused():
+            mean, sd, crit, joint, odev, dev = b.engine.joint_band(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, lv,
+                                                                   floor, dev=True if return_draws else None)
+            return pack([(mean[q], sd[q], crit[q], joint[q], odev[q, ..., 0], odev[q, ..., 1], None if dev is None else dev[q])
+                         for q in range(len(names))])
+
+        def composed():
+            n0 = b.engine.rng_state()[2] if eps is None else None
+            rz = self._band_levels(lv, ns)
+            cols = {n: [] for n in names}
+            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
+                y = d["observations"].to(torch.float32)
+                for n in names:
+                    v = res[n].to(torch.float32)                                                       # [rows, C, T, ns]
+                    mean, sd = self._mean_sd(v)
+                    on = sd > floor
+                    neg = torch.full_like(sd, -1.0)
+                    e_k = torch.where(on.unsqueeze(-1), (v - mean.unsqueeze(-1)).abs() / sd.unsqueeze(-1), neg.unsqueeze(-1))
+                    dev = e_k.amax(dim=2).clamp_min(0.0)                                                # [rows, C, ns]
+                    odev = torch.where(on, (y.to(mean.device) - mean).abs() / sd, neg).amax(dim=2).clamp_min(0.0)
+                    srt = torch.sort(dev, dim=-1).values
+                    crit = torch.stack([srt[..., r - 1] for r, _ in rz], -1)
+                    joint = torch.stack([(dev <= torch.tensor(z, dtype=torch.float32)).sum(-1).to(torch.float32) / float(ns) for _, z in rz], -1)
+                    cols[n].append((mean, sd, crit, joint, odev, on.sum(dim=2).to(torch.float32), dev))
+                del res
+            if n0 is not None:
+                b.engine.rng_set_counter(n0 + 1)      # as the engine call leaves it
+            return pack([tuple(torch.cat(c, 0) for c in zip(*cols[n])) for n in names])
+        return self._fused_or_composed(fused, composed)
+
+    BAND_FILES = ("mean", "sd", "crit", "pointwise_joint", "obs_dev")
+
+    def save_simultaneous_band(self, results_dir: str, batches, is_post, num_samples: int, levels=(0.95,)):
+        """Runs ``simultaneous_band`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes,
+        for every head curve, ``<curve>_<post|prior>_band_{mean,sd}.npy`` ``[n, C, T]``, ``..._band_{crit,pointwise_joint}.npy``
+        ``[n, Lv, C]`` and ``..._band_obs_dev.npy`` ``[n, C]`` (the trajectories in loader order), and ``band_levels.npy``.  One
+        read-back, at the end.  Returns the paths."""
+        import os
+        import numpy as np
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        parts = {(n, k): [] for n in names for k in self.BAND_FILES}
+        lv = None
+        for d in batches:
+            r = self.simultaneous_band(is_post=is_post, num_samples=num_samples, levels=levels, **d)
+            lv = r["levels"]
+            for n in names:
+                for k in self.BAND_FILES:
+                    parts[(n, k)].append(r[n][k].transpose(0, 1) if k in ("crit", "pointwise_joint") else r[n][k])
+        tag = "post" if is_post else "prior"
+        written = self._save_arrays(results_dir, (("%s_%s_band_%s.npy" % (n, tag, k), torch.cat(v, 0)) for (n, k), v in parts.items() if v))
+        os.makedirs(results_dir, exist_ok=True)
+        path = os.path.join(results_dir, "band_levels.npy")
+        np.save(path, np.asarray([] if lv is None else lv.tolist(), dtype=np.float64))
+        return written + [path]
+
+    @classmethod
+    def band_line(cls, crit, joint, obs_dev, levels, tag):
+        """One printed line of a ``save_simultaneous_band`` pass from the central curve's arrays ``crit``, ``joint`` ``[n, Lv, C]`` and
+        ``obs_dev`` ``[n, C]`` and the levels: per level, the mean critical value beside the pointwise z, the mean share of draws wholly
+        inside the pointwise band, and the share of subject-channels whose observation lies wholly inside the simultaneous band."""
+        import numpy as np
+        cv, jv, ov = (np.asarray(a, dtype=np.float64) for a in (crit, joint, obs_dev))
+        lv = [float(x) for x in np.asarray(levels, dtype=np.float64).reshape(-1)]
+        cells = ["%g: crit=%.3f (z=%.3f) pointwise_joint=%.3f obs_inside=%.3f" % (p, cv[:, j].mean(), z, jv[:, j].mean(), (ov <= cv[:, j]).mean())
+                 for j, (p, (_, z)) in enumerate(zip(lv, cls._band_levels(lv, 2)))]
+        return "joint_band_%s: n=%d  levels=%s  %s" % (tag, cv.shape[0], "[" + ", ".join("%g" % p for p in lv) + "]", "  ".join(cells))
+
     # ---- per-trajectory bounds from K posterior draws: nothing summed over the batch -----------------------------------------------------
     BOUND_NAMES =("elbo", "iw_bound", "ess", "nll")     # the slots of one slode_traj_bounds row, in order
 

@@ -114,7 +114,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
           curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
-          quantile_levels=(0.025, 0.975), mechanism: int = 0):
+          quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,)):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -161,7 +161,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     mechanism = K > 0: after training, the best model's mechanism curves over the validation loader from K draws, posterior and prior
     (``save_mechanism_moments``: ``mechanism_<name>_<post|prior>_{mean,sd}.npy`` [n, T, S] for the state, production, degradation, set point
     and net rate) and one printed line per side (``mechanism_post: ...``: per state component, the time-averaged mean production,
-    degradation and set point); 0 (the default): no such stage runs."""
+    degradation and set point); 0 (the default): no such stage runs.
+    joint_band = K > 0: after training, the best model's simultaneous (sup-t) bands at ``band_levels`` over the validation loader from K
+    draws, posterior and prior (``save_simultaneous_band``: ``<curve>_<post|prior>_band_{mean,sd,crit,pointwise_joint,obs_dev}.npy``,
+    ``band_levels.npy``) and one printed line per side (``joint_band_post: ...``: per level of the central curve, the mean critical value
+    beside the pointwise z, the mean share of draws wholly inside the pointwise band and the share of subject-channels whose observation
+    lies wholly inside the simultaneous band); 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -313,6 +318,17 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                               for k in ("production", "degradation", "set_point")}, tag)
             print(line)
             logging.debug("%s (%s)", line, written)
+    if joint_band:
+        for is_post in (True, False):
+            tag = "post" if is_post else "prior"
+            written = best_model.save_simultaneous_band(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(joint_band),
+                                                        levels=band_levels)
+            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
+            crit, joint, odev = (np.load([f for f in written if f.endswith("%s_%s_band_%s.npy" % (central, tag, k))][0])
+                                 for k in ("crit", "pointwise_joint", "obs_dev"))
+            line = best_model.band_line(crit, joint, odev, np.load([f for f in written if f.endswith("band_levels.npy")][0]), tag)
+            print(line)
+            logging.debug("%s (%s)", line, written)
     if forecast_steps:
         t_out = best_model.horizon_times(int(forecast_steps))
         parts = {}
@@ -411,6 +427,13 @@ def build_parser():
                     help="after training: the best model's mechanism curves over the validation loader from K draws, posterior and prior "
                          "(save_mechanism_moments: mechanism_<name>_<post|prior>_{mean,sd}.npy) -- per state component, the time-averaged mean "
                          "production, degradation and set point, one line per side")
+    ap.add_argument("--joint-band", type=int, default=0, metavar="K",
+                    help="after training: the best model's simultaneous (sup-t) credible bands over the validation loader from K draws, posterior "
+                         "and prior (save_simultaneous_band: <curve>_<post|prior>_band_{mean,sd,crit,pointwise_joint,obs_dev}.npy, band_levels.npy) "
+                         "-- the mean critical value beside the pointwise z, the share of draws wholly inside the pointwise band and the share of "
+                         "observations wholly inside the simultaneous band, one line per side")
+    ap.add_argument("--band-levels", type=lambda v: [float(x) for x in v.split(",")], default=[0.95], metavar="a,b,...",
+                    help="the levels of --joint-band, 1 to 8 values in (0, 1] (default: 0.95)")
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
@@ -448,6 +471,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["sample_quantiles"], kw["quantile_levels"] = a.sample_quantiles, a.quantile_levels
     if a.mechanism:
         kw["mechanism"] = a.mechanism
+    if a.joint_band:
+        kw["joint_band"], kw["band_levels"] = a.joint_band, a.band_levels
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
     if a.cohort_curves:

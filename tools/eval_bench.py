@@ -1,5 +1,5 @@
 """What the benches of the eval-side calls (recon_moments_bench, intervene_bench, attribution_bench, forecast_bench, cohort_bench, calibration_bench,
-traj_bounds_bench, label_evidence_bench, refine_bench, pointwise_bench, summary_bench, quantile_bench, mechanism_bench and, for the model and the tail, stats_pass_bench) share: the model and its batch from a shape tuple, a call timed with device events, the
+traj_bounds_bench, label_evidence_bench, refine_bench, pointwise_bench, summary_bench, quantile_bench, mechanism_bench, joint_band_bench and, for the model and the tail, stats_pass_bench) share: the model and its batch from a shape tuple, a call timed with device events, the
 alternating-legs loop with its warm-up and summary, and the command line with its one JSON line."""
 import argparse
 import importlib
