@@ -14,7 +14,7 @@
 //       the fma sums of w v and of w [beyond] and the first index beyond; the row combines in four DPP steps (xor 1, xor 2, half mirror,
 //       mirror: row16_sum's order; an extreme prefers the smaller index on a tie), after which every lane holds all eight functionals.
 //       Lane j < 8 of the row owns the shifted moment triple of functional j (fwd_moment_add); slot 6 (t_hit) takes the crossing draws only.
-//   M7  once per trajectory: the owners store mean / sd [Q, B, C, 8]; the threads of M6a store p_beyond = cnt / ns with T contiguous
+//   M7  once per trajectory: the owners store mean / sd [Q, B, C, 8] (fwd_moment_store_pinned); the threads of M6a store p_beyond = cnt / ns with T contiguous
 // The summation tree of auc and time_beyond is therefore fixed: per lane a left-to-right fma chain over its points, then
 // ((l ^ 1) pair) -> ((l ^ 2) pair) -> half mirror -> mirror, each step adding two values that both partners hold, so every lane of the row ends
 // with the same bits.  Every output has ONE owner thread, which takes the draws in the fixed order: the result is a function of (parameters,
@@ -41,39 +41,18 @@ struct CsK {
 // thr[c] by selects among four values read once: the kernel arguments are never indexed by a run-time value
 __device__ __forceinline__ float cs_thr(float t0, float t1, float t2, float t3, int c) { return c == 0 ? t0 : (c == 1 ? t1 : (c == 2 ? t2 : t3)); }
 
-// one DPP move of an int (slode_common.h: dpp_f)
-template <int CTRL>
-__device__ __forceinline__ int cs_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
 // the extreme of a row with the smallest index attaining it: GT: the maximum, else the minimum.  Both partners of a step see the same pair of
 // (value, index) and pick the same one, so after the four steps every lane of the row holds the row's.
 template <bool GT, int CTRL>
 __device__ __forceinline__ void cs_ext_step(float& v, int& i) {
   const float ov = dpp_f<CTRL>(v);
-  const int oi = cs_dpp_i<CTRL>(i);
+  const int oi = dpp_i<CTRL>(i);
   const bool take = (GT ? ov > v : ov < v) || (ov == v && oi < i);
   v = take ? ov : v; i = take ? oi : i;
 }
 template <bool GT>
 __device__ __forceinline__ void cs_row_ext(float& v, int& i) {
   cs_ext_step<GT, 0xB1>(v, i); cs_ext_step<GT, 0x4E>(v, i); cs_ext_step<GT, 0x141>(v, i); cs_ext_step<GT, 0x140>(v, i);
-}
-__device__ __forceinline__ int cs_row_min(int i) {
-  i = min(i, cs_dpp_i<0xB1>(i)); i = min(i, cs_dpp_i<0x4E>(i)); i = min(i, cs_dpp_i<0x141>(i)); i = min(i, cs_dpp_i<0x140>(i));
-  return i;
-}
-
-// M7 of one functional: fwd_moment_store's formula with its operation order pinned -- mean = fma(s1, inv, v0); sd = sqrt(max(s2 - (s1 s1) inv, 0)
-// inv), every product and the difference rounded on its own (no contraction into an fma) -- so that the result is bitwise the numpy
-// restatement of the accumulation (tests/recon_moments_util.py: shifted_moments_f32), whatever the compiler would fuse
-__device__ __forceinline__ void cs_moment_store(const float* m, int P, float inv, float* mean, float* sd, long long o) {
-#pragma clang fp contract(off)
-  const float s1 = m[P], s2 = m[2 * P];
-  mean[o] = fmaf(s1, inv, m[0]);
-  if (sd) {
-    const float sq = s1 * s1, sub = sq * inv;
-    sd[o] = sqrtf(fmaxf(s2 - sub, 0.f) * inv);
-  }
 }
 
 // SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
@@ -152,7 +131,7 @@ __global__ void __launch_bounds__(CS_NT) curve_summary_kernel(const CsK k) {
         cs_row_ext<false>(vmin, imin);
         auc = row16_sum(auc);
         tb = row16_sum(tb);
-        ihit = cs_row_min(ihit);
+        ihit = row16_min_i(ihit);
         if (l16 < SLODE_SUMMARY_SLOTS) {
           const bool crossed = ihit < T;
           float fv;
@@ -179,9 +158,9 @@ __global__ void __launch_bounds__(CS_NT) curve_summary_kernel(const CsK k) {
       const float* m = s_mom + row * SLODE_SUMMARY_SLOTS + l16;
       const float nan = __builtin_nanf("");
       if (l16 >= 5 && !has_thr) { k.mean[o] = nan; if (k.sd) k.sd[o] = nan; }
-      else if (l16 != 6) cs_moment_store(m, P, inv, k.mean, k.sd, o);
+      else if (l16 != 6) fwd_moment_store_pinned(m, P, inv, k.mean, k.sd, o);
       else if (n_hit == 0) { k.mean[o] = nan; if (k.sd) k.sd[o] = nan; }
-      else cs_moment_store(m, P, 1.0f / (float)n_hit, k.mean, k.sd, o);
+      else fwd_moment_store_pinned(m, P, 1.0f / (float)n_hit, k.mean, k.sd, o);
     }
     if (counts)
       for (int t = tid; t < T; t += CS_NT)

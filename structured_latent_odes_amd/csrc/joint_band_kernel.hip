@@ -56,20 +56,6 @@ __device__ __forceinline__ float jb_dev(float v, float m, float s, float sd_floo
   return s > sd_floor ? d / s : -1.f;
 }
 
-template <int CTRL>
-__device__ __forceinline__ int jb_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-template <int CTRL>
-__device__ __forceinline__ float jb_max_step(float v) { const float o = dpp_f<CTRL>(v); return o > v ? o : v; }
-// the maximum of a row, valid in every lane of it (curve_summary's four steps; a selection: no bit depends on the order)
-__device__ __forceinline__ float jb_row_max(float v) {
-  v = jb_max_step<0xB1>(v); v = jb_max_step<0x4E>(v); v = jb_max_step<0x141>(v); v = jb_max_step<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ int jb_row_sum(int v) {
-  v += jb_dpp_i<0xB1>(v); v += jb_dpp_i<0x4E>(v); v += jb_dpp_i<0x141>(v); v += jb_dpp_i<0x140>(v);
-  return v;
-}
-
 // SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
 template <int SC>
 __global__ void __launch_bounds__(JB_NT) joint_band_kernel(const JbK k) {
@@ -128,8 +114,8 @@ __global__ void __launch_bounds__(JB_NT) joint_band_kernel(const JbK k) {
         mx = e > mx ? e : mx;
         np += s_row[t] > sd_floor ? 1 : 0;
       }
-      mx = jb_row_max(mx);
-      np = jb_row_sum(np);
+      mx = row16_max(mx);
+      np = row16_sum_i(np);
       if (l16 == 0) {
         const long long o = (((long long)rq * f.B + b) * C + rc) * 2;
         k.obs_dev[o] = has_obs ? (mx < 0.f ? 0.f : mx) : __builtin_nanf("");
@@ -161,7 +147,7 @@ __global__ void __launch_bounds__(JB_NT) joint_band_kernel(const JbK k) {
           mx = e0 > mx ? e0 : mx; mx = e1 > mx ? e1 : mx; mx = e2 > mx ? e2 : mx; mx = e3 > mx ? e3 : mx;
         }
         for (; t < T; t += 16) { const float e = v_row[t]; mx = e > mx ? e : mx; }
-        mx = jb_row_max(mx);
+        mx = row16_max(mx);
         if (l16 == 0) s_dev[row * ns + kk] = mx < 0.f ? 0.f : mx;
       }
     }

@@ -10,7 +10,7 @@
 //       whose turn point T - 1 is takes one fwd_ad at stage_t[R (T - 1)], bitwise times[T - 1], and no step; M5 fwd_scan
 //   M6  thread <-> time point: x_t from the scan, a, d from the capture table (the thread's own writes), the selected slots and their running
 //       moments (fwd_moment_add), table [n_sel][S][3][T]
-//   M7  once per trajectory: mm_moment_store (fwd_moment_store with its operation order pinned), written with T contiguous
+//   M7  once per trajectory: fwd_moment_store_pinned, written with T contiguous
 // The routines and the operation order of the solve are those of fwd_solve: the states are bitwise those of recon_moments on the same noise.
 // The moments of (slot, s, t) belong to ONE thread for the whole trajectory and take the draws in the fixed order k = 0 .. ns - 1: the
 // result is a function of (parameters, inputs, noise) alone -- independent of the grid and of which slots are asked for, bitwise
@@ -33,19 +33,6 @@ struct MmK {
 
 // floats of one slot's moment triples [S][3][T], rounded up to a multiple of four: a further slot costs exactly this much LDS
 __host__ __device__ inline int mm_slot_floats(int S, int T) { return (3 * S * T + 3) & ~3; }
-
-// M7 of one value: fwd_moment_store's formula with its operation order pinned -- mean = fma(s1, inv, v0); sd = sqrt(max(s2 - (s1 s1) inv, 0)
-// inv), every product and the difference rounded on its own (no contraction into an fma) -- so that the result is bitwise the numpy
-// restatement of the accumulation (tests/recon_moments_util.py: shifted_moments_f32), whatever the compiler would fuse
-__device__ __forceinline__ void mm_moment_store(const float* m, int P, float inv, float* mean, float* sd, long long o) {
-#pragma clang fp contract(off)
-  const float s1 = m[P], s2 = m[2 * P];
-  mean[o] = fmaf(s1, inv, m[0]);
-  if (sd) {
-    const float sq = s1 * s1, sub = sq * inv;
-    sd[o] = sqrtf(fmaxf(s2 - sub, 0.f) * inv);
-  }
-}
 
 // SC: ode_state_dim at compile time (5: cvs / challenge, 8: proc), 0: any S <= SLODE_MAX_S at run time
 template <int SC>
@@ -122,7 +109,7 @@ __global__ void __launch_bounds__(MM_NT) mechanism_moments_kernel(const MmK k) {
     for (int t = tid; t < T; t += MM_NT)
       for (int r = 0; r < rows; ++r) {
         const int j = r / S, s = r - j * S;
-        mm_moment_store(s_acc + j * slot_stride + (s * 3) * T + t, T, inv, k.mean, k.sd, (((long long)j * f.B + b) * S + s) * T + t);
+        fwd_moment_store_pinned(s_acc + j * slot_stride + (s * 3) * T + t, T, inv, k.mean, k.sd, (((long long)j * f.B + b) * S + s) * T + t);
       }
   }
 }

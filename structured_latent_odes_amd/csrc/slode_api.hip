@@ -857,6 +857,19 @@ static int eval_grid_for(const slode_ctx* h, int B) {
   }
   return (int)g;
 }
+// dense [B,T,C] or [B,C,T] observation strides; *t_major: the former (and not also the latter)
+static bool obs_dense(const slode_shape* s, const int64_t* os, bool* t_major) {
+  const bool tm = os[1] == 1 && os[2] == s->C, cm = os[2] == 1 && os[1] == s->T;
+  *t_major = tm && !cm;
+  return os[0] == (long long)s->C * s->T && (tm || cm);
+}
+// The opening of a plan entry point (host arithmetic only; no handle): the shape, then the outputs as the caller's message lists them
+static int plan_open(const char* who, const slode_shape* s, bool missing, const char* outputs) {
+  const char* bad = check_shape(s);
+  if (bad) return fail(nullptr, SLODE_EINVAL, "%s: %s", who, bad);
+  if (missing) return fail(nullptr, SLODE_EINVAL, "%s: %s is NULL", who, outputs);
+  return SLODE_OK;
+}
 // One of these calls as data: its name and the per-call pieces of the refusal texts they share.  A nullptr text: the
 // call does not make that check.
 struct EvalCall {
@@ -891,12 +904,17 @@ static int eval_refuse(slode_handle h, const slode_shape* s, const slode_batch* 
     return fail(h, SLODE_EINVAL, "%s cannot be combined with the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG", d.name);
   if (d.obs_null && !batch->obs) return fail(h, SLODE_EINVAL, "%s: %s", d.name, d.obs_null);
   const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (d.strides_tail && (h->no_fold || os[0] != (long long)s->C * s->T || !(t_major || c_major) || !(s->C == 3 || s->C == 4)))
+  bool t_major;
+  if (d.strides_tail && (h->no_fold || !obs_dense(s, os, &t_major) || !(s->C == 3 || s->C == 4)))
     return fail(h, SLODE_EINVAL, "%s: observation strides (%lld, %lld, %lld) are not taken: the folded encoder path needs dense "
                                  "[B,T,C] or [B,C,T] observations with C in {3, 4}%s",
                 d.name, (long long)os[0], (long long)os[1], (long long)os[2], d.strides_tail);
   return SLODE_OK;
+}
+// both, for the calls with no rung of their own between them (slode_traj_bounds: an alignment; slode_joint_band: its draw count)
+static int eval_open(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const slode_batch* batch, const EvalCall& d) {
+  const int rc = eval_args(h, s, lay, params, d);
+  return rc != SLODE_OK ? rc : eval_refuse(h, s, batch, d);
 }
 // ... then the LDS budget of a kernel that walks the draws of its trajectories (slode_*_lds_bytes against SLODE_*_LDS_MAX); the label
 // tensors (batch_labels) follow it, and step_setup's checks and workspace (forward_setup) come last
@@ -999,6 +1017,17 @@ static int draws_run(slode_handle h, const slode_shape* s, const slode_layout* l
   if ((rc = forward_encode(p, a.rng_calls, &a.rng)) != SLODE_OK) return rc;
   return run(c.stream);
 }
+// The three together, for any launch struct with a DrawsLaunch member d whose own fields (and d.rng_calls) the caller has set: labels, fill,
+// run of launch(a, stream).  grid_times / grid_stage_t: the grid the kernel solves on where it is not the training grid (forecast).
+extern "C++" template <class A>
+static int draws_close(slode_handle h, const slode_shape* s, const slode_layout* lay, const EvalCall& d, A& a, const float* params, const float* times,
+                       const float* stage_t, const slode_batch* batch, int is_post, int num_samples, int items, void* workspace, size_t workspace_bytes,
+                       void* stream, hipError_t (*launch)(const A&, hipStream_t), const float* grid_times = nullptr, const float* grid_stage_t = nullptr) {
+  const int rc = draws_labels(h, s, batch, d, is_post, &a.d.lab);
+  if (rc != SLODE_OK) return rc;
+  draws_fill(a.d, h, s, lay, params, grid_times ? grid_times : times, grid_times ? grid_stage_t : stage_t, batch, is_post, num_samples, items);
+  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream, [&](hipStream_t st) { return launch(a, st); });
+}
 
 // ---- the calls that score num_draws posterior draws of every trajectory against its observations (traj_bounds, label_evidence,
 // posterior_refine, pointwise_density) ----
@@ -1039,8 +1068,8 @@ int slode_eval_stats(slode_handle h, const slode_shape* s, const slode_layout* l
                      void* stream) {
   const EvalCall d{"slode_eval_stats", "batch / out", !batch || !out, nullptr, 0, "; run the unfused calls",
                    "(one particle only); run the unfused calls", nullptr, "; run the unfused calls"};
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (slode_eval_lds_bytes(*s) + 4096 > 160 * 1024)
     return fail(h, SLODE_EINVAL, "slode_eval_stats: T x S = %d x %d does not fit the step table into the LDS; run the unfused calls", s->T, s->S);
   EvalLaunch a{};
@@ -1068,15 +1097,13 @@ int slode_recon_moments(slode_handle h, const slode_shape* s, const slode_layout
                         size_t workspace_bytes, void* stream) {
   const DrawsCall d("slode_recon_moments", "batch / mean / times / stage_t / workspace", !batch || !mean || !times || !stage_t || !workspace,
                     num_samples, is_post, "reduce recon_samples instead", "step table, moments, staged weights");
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if ((rc = eval_lds(h, s, d, slode_recon_moments_lds_bytes(*s, h->ode_generic), SLODE_RECON_MOMENTS_LDS_MAX)) != SLODE_OK) return rc;
   ReconMomentsLaunch a{};
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
   a.mean = mean; a.sd = sd;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_recon_moments(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_recon_moments);
 }
 
 // Per-trajectory -ELBO, importance-weighted bound, effective sample size and mean negative log-likelihood from num_draws posterior draws
@@ -1106,8 +1133,8 @@ int slode_label_evidence(slode_handle h, const slode_shape* s, const slode_layou
                          const float* log_prior, float* evidence, int32_t* best, float* loss_vkb, void* workspace, size_t workspace_bytes,
                          void* stream) {
   const ScoredCall d("slode_label_evidence", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_draws);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (!evidence || ((uintptr_t)evidence & 15) != 0) return fail(h, SLODE_EINVAL, "slode_label_evidence: evidence is NULL or not 16-byte aligned");
   if (V < 1 || V > SLODE_EVIDENCE_MAX_V) return fail(h, SLODE_EINVAL, "slode_label_evidence: V = %d out of range [1, %d]", V, SLODE_EVIDENCE_MAX_V);
   if (!hyp_labels) return fail(h, SLODE_EINVAL, "slode_label_evidence: hyp_labels is NULL");
@@ -1141,8 +1168,8 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
                      !batch || !loc_out || !scale_out || !elbo_out || !times || !stage_t || !workspace, num_draws,
                      "step table and its kept copy, lambda, the stage-gradient table, observations, weights, staged weights, the per-draw losses",
                      "a shorter window or fewer draws per call fit", true);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (num_steps < 0) return fail(h, SLODE_EINVAL, "slode_posterior_refine: num_steps = %d < 0", num_steps);
   if (!(lr > 0.f && lr < INFINITY)) return fail(h, SLODE_EINVAL, "slode_posterior_refine: lr = %g is not a finite positive step size", (double)lr);
   if (s->aux_in_main && s->n_aux > 0)
@@ -1160,9 +1187,7 @@ int slode_posterior_refine(slode_handle h, const slode_shape* s, const slode_lay
 // The LDS bytes of slode_pointwise_density for a shape, a draw count and a weighting (host arithmetic only; the compiled state dims, no
 // SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
 int slode_pointwise_plan(const slode_shape* s, int num_draws, int weights, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: %s", bad);
-  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: lds_bytes is NULL");
+  if (int rc = plan_open("slode_pointwise_plan", s, !lds_bytes, "lds_bytes")) return rc;
   if (num_draws < 1) return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: num_draws = %d < 1", num_draws);
   if (weights != SLODE_PW_POSTERIOR && weights != SLODE_PW_IMPORTANCE)
     return fail(nullptr, SLODE_EINVAL, "slode_pointwise_plan: weights = %d is neither SLODE_PW_POSTERIOR (0) nor SLODE_PW_IMPORTANCE (1)", weights);
@@ -1185,8 +1210,8 @@ int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_la
   const ScoredCall d("slode_pointwise_density", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_draws,
                      "step table, observations, mask, staged weights, the point accumulators, the per-draw losses and weights",
                      "a shorter window or (importance weights) fewer draws per call fit", imp);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (weights != SLODE_PW_POSTERIOR && weights != SLODE_PW_IMPORTANCE)
     return fail(h, SLODE_EINVAL, "slode_pointwise_density: weights = %d is neither SLODE_PW_POSTERIOR (0) nor SLODE_PW_IMPORTANCE (1)", weights);
   if (!point || !summary || ((uintptr_t)summary & 15) != 0)
@@ -1211,8 +1236,8 @@ int slode_intervene_moments(slode_handle h, const slode_shape* s, const slode_la
                             float* cf_mean, float* cf_sd, float* eff_mean, float* eff_sd, void* workspace, size_t workspace_bytes, void* stream) {
   const DrawsCall d("slode_intervene_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, 1,
                     "reduce counterfactual samples instead", "step table, moments, factual values, staged weights");
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (s->n_groups < 32 && (group_mask >> s->n_groups) != 0)
     return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x has bits at or beyond n_groups = %d", group_mask, s->n_groups);
   if (group_mask != 0 && !cf_labels) return fail(h, SLODE_EINVAL, "slode_intervene_moments: group_mask = 0x%x needs the counterfactual labels (cf_labels is NULL)", group_mask);
@@ -1251,9 +1276,7 @@ static bool attribution_has_rest(const slode_shape* s) {
 // The LDS bytes of slode_latent_attribution for a shape and an arm count (host arithmetic only; the compiled state dims, no
 // SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
 int slode_attribution_plan(const slode_shape* s, int n_arms, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: %s", bad);
-  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: lds_bytes is NULL");
+  if (int rc = plan_open("slode_attribution_plan", s, !lds_bytes, "lds_bytes")) return rc;
   if (n_arms < 1 || n_arms > SLODE_ATTRIBUTION_MAX_ARMS)
     return fail(nullptr, SLODE_EINVAL, "slode_attribution_plan: n_arms = %d out of range [1, %d]", n_arms, SLODE_ATTRIBUTION_MAX_ARMS);
   *lds_bytes = slode_attribution_lds_bytes(*s, n_arms, 0);
@@ -1275,8 +1298,8 @@ int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_l
   snprintf(arms, sizeof(arms), ", n_arms = %d", n_arms);
   d.lds_tables = "step table, base moments, base values, arm sums, staged weights"; d.lds_advice = "fewer arms per call fit (slode_attribution_plan)";
   d.lds_extra = arms;
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (n_arms < 1 || n_arms > SLODE_ATTRIBUTION_MAX_ARMS)
     return fail(h, SLODE_EINVAL, "slode_latent_attribution: n_arms = %d out of range [1, %d]", n_arms, SLODE_ATTRIBUTION_MAX_ARMS);
   if (!arm_masks || !msd) return fail(h, SLODE_EINVAL, "slode_latent_attribution: arm_masks / msd is NULL");
@@ -1291,22 +1314,18 @@ int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_l
   }
   if ((rc = eval_lds(h, s, d, slode_attribution_lds_bytes(*s, n_arms, h->ode_generic), SLODE_ATTRIBUTION_LDS_MAX)) != SLODE_OK) return rc;
   AttributionLaunch a{};
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
   a.d.rng_calls = 2;
   a.mean = mean; a.sd = sd; a.msd = msd; a.n_arms = n_arms;
   for (int i = 0; i < n_arms; ++i) a.masks[i] = arm_masks[i];
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_attribution(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_attribution);
 }
 
 // ---- curve summaries: the draws of slode_recon_moments, eight functionals of every draw's whole curve (include/slode.h) ----
 // The LDS bytes of slode_curve_summary for a shape, with or without the p_beyond counters (host arithmetic only; the compiled state dims, no
 // SLODE_ODE_GENERIC): SLODE_EINVAL when the call would refuse them at its LDS rung.
 int slode_curve_summary_plan(const slode_shape* s, int want_p_beyond, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: %s", bad);
-  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: lds_bytes is NULL");
+  if (int rc = plan_open("slode_curve_summary_plan", s, !lds_bytes, "lds_bytes")) return rc;
   *lds_bytes = slode_curve_summary_lds_bytes(*s, want_p_beyond, 0);
   if (*lds_bytes > SLODE_CURVE_SUMMARY_LDS_MAX)
     return fail(nullptr, SLODE_EINVAL, "slode_curve_summary_plan: the LDS tables of T = %d, S = %d, C = %d, %s p_beyond (%zu B) exceed the budget of %d B",
@@ -1329,8 +1348,8 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
     d.lds_tables = "step table, grid and node weights, value table, moment triples, staged weights";
     d.lds_advice = "reduce recon_samples instead"; d.lds_extra = ", without p_beyond";
   }
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (!mean) return fail(h, SLODE_EINVAL, "slode_curve_summary: mean is NULL");
   if (sense != 1 && sense != -1) return fail(h, SLODE_EINVAL, "slode_curve_summary: sense = %d is neither +1 (beyond: above thr) nor -1 (below)", sense);
   if (thr)
@@ -1339,12 +1358,10 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
   if (p_beyond && !thr) return fail(h, SLODE_EINVAL, "slode_curve_summary: p_beyond needs a threshold (thr is NULL)");
   if ((rc = eval_lds(h, s, d, slode_curve_summary_lds_bytes(*s, p_beyond != nullptr, h->ode_generic), SLODE_CURVE_SUMMARY_LDS_MAX)) != SLODE_OK) return rc;
   CurveSummaryLaunch a{};
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
   a.mean = mean; a.sd = sd; a.p_beyond = p_beyond; a.has_thr = thr ? 1 : 0; a.sense = sense;
   for (int c = 0; c < SLODE_MAX_C; ++c) a.thr[c] = (thr && c < s->C) ? thr[c] : 0.f;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_curve_summary(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_curve_summary);
 }
 
 // ---- sample quantiles: the draws of slode_recon_moments, order statistics of every value over the draws (include/slode.h) ----
@@ -1413,10 +1430,7 @@ static int quantile_plan(const slode_shape& s, int K, int n_levels, const double
 // SLODE_EINVAL where the call would refuse them at its own rungs.
 int slode_quantile_plan(const slode_shape* s, int num_samples, int n_levels, const double* levels, int tile, int* tile_out, int* sweeps,
                         int* depth_lo, int* depth_hi, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: %s", bad);
-  if (!tile_out || !sweeps || !depth_lo || !depth_hi || !lds_bytes)
-    return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: tile_out / sweeps / depth_lo / depth_hi / lds_bytes is NULL");
+  if (int rc = plan_open("slode_quantile_plan", s, !tile_out || !sweeps || !depth_lo || !depth_hi || !lds_bytes, "tile_out / sweeps / depth_lo / depth_hi / lds_bytes")) return rc;
   QuantilePlan p{};
   char why[448];
   if (quantile_plan(*s, num_samples, n_levels, levels, tile, 0, &p, why, sizeof(why)) != SLODE_OK) return fail(nullptr, SLODE_EINVAL, "slode_quantile_plan: %s", why);
@@ -1432,30 +1446,26 @@ int slode_recon_quantiles(slode_handle h, const slode_shape* s, const slode_layo
                           float* out, void* workspace, size_t workspace_bytes, void* stream) {
   const DrawsCall d("slode_recon_quantiles", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
                     "sort recon_samples instead", nullptr);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (!out) return fail(h, SLODE_EINVAL, "slode_recon_quantiles: out is NULL");
   ReconQuantilesLaunch a{};
   QuantilePlan p{};
   char why[448];
   if (quantile_plan(*s, num_samples, n_levels, levels, tile, h->ode_generic, &p, why, sizeof(why)) != SLODE_OK)
     return fail(h, SLODE_EINVAL, "slode_recon_quantiles: %s", why);
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
   a.d.rng_calls = num_samples;   // the counter moves by num_samples whatever the number of sweeps; the noise: rows k * B + b of drawing call n
   a.out = out; a.n_levels = n_levels; a.tile = p.tile; a.depth_lo = p.depth_lo; a.depth_hi = p.depth_hi;
   for (int i = 0; i < SLODE_QUANTILE_MAX_LEVELS; ++i) { a.slot_lo[i] = p.slot_lo[i]; a.slot_hi[i] = p.slot_hi[i]; a.g[i] = p.g[i]; }
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_recon_quantiles(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_recon_quantiles);
 }
 
 // ---- mechanism curves: the draws of slode_recon_moments, the moments of x, a, d, a / d and a - d x at every grid point (include/slode.h) ----
 // The LDS bytes of slode_mechanism_moments for a shape and a slot mask (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
 // SLODE_EINVAL when the call would refuse them at its mask or LDS rung.
 int slode_mechanism_plan(const slode_shape* s, unsigned int slots, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: %s", bad);
-  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_mechanism_plan: lds_bytes is NULL");
+  if (int rc = plan_open("slode_mechanism_plan", s, !lds_bytes, "lds_bytes")) return rc;
   const int n_sel = __builtin_popcount(slots & ((1u << SLODE_MECHANISM_SLOTS) - 1));
   *lds_bytes = slode_mechanism_lds_bytes(*s, n_sel, 0);
   if (slots == 0 || (slots >> SLODE_MECHANISM_SLOTS))
@@ -1475,8 +1485,8 @@ int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_la
                             void* workspace, size_t workspace_bytes, void* stream) {
   DrawsCall d("slode_mechanism_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
               "compose slode_ode_solve_fwd and the dynamics net instead", nullptr);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (!mean) return fail(h, SLODE_EINVAL, "slode_mechanism_moments: mean is NULL");
   if (slots == 0 || (slots >> SLODE_MECHANISM_SLOTS))
     return fail(h, SLODE_EINVAL, "slode_mechanism_moments: slots = 0x%x selects nothing or has bits at or beyond SLODE_MECHANISM_SLOTS = %d", slots,
@@ -1488,11 +1498,9 @@ int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_la
   d.lds_advice = "fewer slots per call fit (slode_mechanism_plan)"; d.lds_extra = extra;
   if ((rc = eval_lds(h, s, d, slode_mechanism_lds_bytes(*s, n_sel, h->ode_generic), SLODE_MECHANISM_LDS_MAX)) != SLODE_OK) return rc;
   MechanismLaunch a{};
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);
   a.mean = mean; a.sd = sd; a.slots = slots;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_mechanism_moments(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_mechanism_moments);
 }
 
 // ---- simultaneous bands: the draws of slode_recon_moments twice, the quantiles of the draws' largest standardised deviation (include/slode.h) ----
@@ -1539,9 +1547,7 @@ int slode_joint_band_levels(int num_samples, int n_levels, const double* levels,
 // The LDS bytes of slode_joint_band for a shape and a draw count (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
 // SLODE_EINVAL where the call would refuse them at its draw-count or LDS rung.
 int slode_joint_band_plan(const slode_shape* s, int num_samples, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: %s", bad);
-  if (!lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: lds_bytes is NULL");
+  if (int rc = plan_open("slode_joint_band_plan", s, !lds_bytes, "lds_bytes")) return rc;
   if (num_samples < 2) return fail(nullptr, SLODE_EINVAL, "slode_joint_band_plan: num_samples = %d < 2 (the sd of one draw is 0)", num_samples);
   *lds_bytes = slode_joint_band_lds_bytes(*s, num_samples, 0);
   if (*lds_bytes > SLODE_JOINT_BAND_LDS_MAX)
@@ -1572,19 +1578,17 @@ int slode_joint_band(slode_handle h, const slode_shape* s, const slode_layout* l
   for (int i = 0; i < n_levels; ++i) a.z[i] = (float)z[i];
   if (!(sd_floor >= 0.f) || std::isinf(sd_floor)) return fail(h, SLODE_EINVAL, "slode_joint_band: sd_floor = %g is negative or not finite", (double)sd_floor);
   const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (batch->obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))   // (the posterior: eval_refuse has refused these already)
+  bool t_major;
+  if (!obs_dense(s, os, &t_major) && batch->obs)   // (the posterior: eval_refuse has refused these already)
     return fail(h, SLODE_EINVAL, "slode_joint_band: observation strides (%lld, %lld, %lld) are not taken: the observed deviation needs dense "
                                  "[B,T,C] or [B,C,T] observations; reduce recon_samples instead", (long long)os[0], (long long)os[1], (long long)os[2]);
   d.lds_tables = "step table, staged weights, moment / value table, deviations";
   d.lds_advice = "fewer draws fit (slode_joint_band_plan), or reduce recon_samples instead"; d.lds_per_draw = true;
   if ((rc = eval_lds(h, s, d, slode_joint_band_lds_bytes(*s, num_samples, h->ode_generic), SLODE_JOINT_BAND_LDS_MAX)) != SLODE_OK) return rc;
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, s->B);   // (rng_calls stays 1: the counter moves as slode_recon_moments moves it)
-  a.obs = batch->obs; a.t_major = t_major && !c_major ? 1 : 0; a.n_levels = n_levels; a.sd_floor = sd_floor;
+  a.obs = batch->obs; a.t_major = t_major ? 1 : 0; a.n_levels = n_levels; a.sd_floor = sd_floor;
   a.mean = mean; a.sd = sd; a.crit = crit; a.joint = joint; a.obs_dev = obs_dev; a.dev_out = dev_out;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_joint_band(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_joint_band);   // (rng_calls stays 1: the counter moves as slode_recon_moments moves it)
 }
 
 // ---- forecast: the solve grid is the call's own argument (include/slode.h) ----
@@ -1645,9 +1649,7 @@ static int forecast_plan(const slode_shape& s, int T_out, int ns, int states, in
 }
 
 int slode_forecast_plan(const slode_shape* s, int T_out, int num_samples, int want_states, int window, int* window_out, size_t* lds_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "slode_forecast_plan: %s", bad);
-  if (!window_out || !lds_bytes) return fail(nullptr, SLODE_EINVAL, "slode_forecast_plan: window_out / lds_bytes is NULL");
+  if (int rc = plan_open("slode_forecast_plan", s, !window_out || !lds_bytes, "window_out / lds_bytes")) return rc;
   if (T_out < 2 || T_out > SLODE_FORECAST_MAX_T) return fail(nullptr, SLODE_EINVAL, "slode_forecast_plan: T_out = %d out of range [2, %d]", T_out, SLODE_FORECAST_MAX_T);
   if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "slode_forecast_plan: num_samples = %d < 1", num_samples);
   if (window < 0) return fail(nullptr, SLODE_EINVAL, "slode_forecast_plan: window = %d < 0", window);
@@ -1666,8 +1668,8 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
                            size_t workspace_bytes, void* stream) {
   const DrawsCall d("slode_forecast_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
                     "reduce forecast_samples instead", nullptr);
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if (!times_out || !stage_t_out) return fail(h, SLODE_EINVAL, "slode_forecast_moments: times_out / stage_t_out is NULL");
   if (T_out < 2 || T_out > SLODE_FORECAST_MAX_T)
     return fail(h, SLODE_EINVAL, "slode_forecast_moments: T_out = %d out of range [2, %d]", T_out, SLODE_FORECAST_MAX_T);
@@ -1678,11 +1680,9 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
   char why[384];
   if (forecast_plan(*s, T_out, num_samples, (x_mean || x_sd) ? 1 : 0, window, h->ode_generic, &a.window, &lds, why, sizeof(why)) != SLODE_OK)
     return fail(h, SLODE_EINVAL, "slode_forecast_moments: %s", why);
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times_out, stage_t_out, batch, is_post, num_samples, s->B);   // (the kernel solves on the output grid)
   a.T_out = T_out; a.mean = mean; a.sd = sd; a.x_mean = x_mean; a.x_sd = x_sd;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_forecast_moments(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_forecast_moments, times_out, stage_t_out);   // (the kernel solves on the output grid)
 }
 
 // ---- cohort curves: the draws of slode_recon_moments reduced by cohort (include/slode.h) ----
@@ -1698,10 +1698,7 @@ static const char* cohort_sizes(const slode_shape* s, int M, int G, int chunk, c
 static int cohort_plan_for(const char* who, size_t (*lds_bytes_of)(const slode_shape&, int), int budget, const char* tables, size_t partial_bytes,
                            const slode_shape* s, int M, int G, int num_samples, int chunk, int* chunk_out, int* n_partials, size_t* lds_bytes,
                            size_t* scratch_bytes) {
-  const char* bad = check_shape(s);
-  if (bad) return fail(nullptr, SLODE_EINVAL, "%s: %s", who, bad);
-  if (!chunk_out || !n_partials || !lds_bytes || !scratch_bytes)
-    return fail(nullptr, SLODE_EINVAL, "%s: chunk_out / n_partials / lds_bytes / scratch_bytes is NULL", who);
+  if (int rc = plan_open(who, s, !chunk_out || !n_partials || !lds_bytes || !scratch_bytes, "chunk_out / n_partials / lds_bytes / scratch_bytes")) return rc;
   if (num_samples < 1) return fail(nullptr, SLODE_EINVAL, "%s: num_samples = %d < 1", who, num_samples);
   char why[128];
   if (cohort_sizes(s, M, G, chunk, why, sizeof(why))) return fail(nullptr, SLODE_EINVAL, "%s: %s", who, why);
@@ -1737,12 +1734,12 @@ static int cohort_index_args(slode_handle h, const char* who, const slode_shape*
 static int cohort_obs_args(slode_handle h, const char* who, const slode_shape* s, const slode_batch* batch, bool need_obs, const char* need,
                            void* scratch, CohortPart& c) {
   const int64_t* os = batch->obs_strides;
-  const bool t_major = os[1] == 1 && os[2] == s->C, c_major = os[2] == 1 && os[1] == s->T;
-  if (need_obs && (os[0] != (long long)s->C * s->T || !(t_major || c_major)))
+  bool t_major;
+  if (!obs_dense(s, os, &t_major) && need_obs)
     return fail(h, SLODE_EINVAL, "%s: observation strides (%lld, %lld, %lld) are not taken: %s need dense [B,T,C] or "
                                  "[B,C,T] observations; reduce recon_samples instead", who, (long long)os[0], (long long)os[1], (long long)os[2], need);
   if (!scratch || ((uintptr_t)scratch & 15)) return fail(h, SLODE_EINVAL, "%s: scratch is NULL or not 16-byte aligned", who);
-  c.obs = need_obs ? batch->obs : nullptr; c.sb = os[0]; c.t_major = t_major && !c_major ? 1 : 0; c.scratch = scratch;
+  c.obs = need_obs ? batch->obs : nullptr; c.sb = os[0]; c.t_major = t_major ? 1 : 0; c.scratch = scratch;
   return SLODE_OK;
 }
 // ... and, after the LDS rung, the chunk and the scratch's size (plan: the entry point that gives it); n_partials: what the grid walks
@@ -1763,8 +1760,8 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
                          float* obs_mean, float* l1, void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
   const DrawsCall d("slode_cohort_moments", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
                     "reduce recon_samples instead", "step table, six-float table, observation sum, staged weights");
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if ((rc = cohort_index_args(h, d.name, s, members, offsets, M, G, chunk)) != SLODE_OK) return rc;
   if (!mean) return fail(h, SLODE_EINVAL, "slode_cohort_moments: mean is NULL");
   const bool want_obs = obs_mean || l1;
@@ -1775,11 +1772,9 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
   if ((rc = eval_lds(h, s, d, slode_cohort_lds_bytes(*s, h->ode_generic), SLODE_COHORT_LDS_MAX)) != SLODE_OK) return rc;
   if ((rc = cohort_scratch_args(h, d.name, "slode_cohort_plan", members, offsets, M, G, chunk, slode_cohort_partial_bytes(*s), scratch_bytes, a.c,
                                 &n_partials)) != SLODE_OK) return rc;
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, n_partials);
   a.clip_min = clip_min; a.mean = mean; a.sd = sd; a.sd_subjects = sd_subjects; a.obs_mean = obs_mean; a.l1 = l1;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_cohort_moments(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, n_partials, workspace, workspace_bytes, stream,
+                     slode_launch_cohort_moments);
 }
 
 // ---- calibration: the draws of slode_recon_moments compared with the observations, counted by cohort (include/slode.h) ----
@@ -1792,8 +1787,8 @@ int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* 
   DrawsCall d("slode_calibration", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
               "reduce recon_samples instead", "step table, counts, fp64 sums, observations, staged weights");
   d.obs_null = "the curves are compared with observations (batch->obs is NULL)";
-  int rc = eval_args(h, s, lay, params, d);
-  if (rc != SLODE_OK || (rc = eval_refuse(h, s, batch, d)) != SLODE_OK) return rc;
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
   if ((rc = cohort_index_args(h, d.name, s, members, offsets, M, G, chunk)) != SLODE_OK) return rc;
   if (!below) return fail(h, SLODE_EINVAL, "slode_calibration: below is NULL");
   CalibrationLaunch a{};
@@ -1802,11 +1797,9 @@ int slode_calibration(slode_handle h, const slode_shape* s, const slode_layout* 
   if ((rc = eval_lds(h, s, d, slode_calibration_lds_bytes(*s, h->ode_generic), SLODE_CALIBRATION_LDS_MAX)) != SLODE_OK) return rc;
   if ((rc = cohort_scratch_args(h, d.name, "slode_calibration_plan", members, offsets, M, G, chunk, slode_calibration_partial_bytes(*s),
                                 scratch_bytes, a.c, &n_partials)) != SLODE_OK) return rc;
-  if ((rc = draws_labels(h, s, batch, d, is_post, &a.d.lab)) != SLODE_OK) return rc;
-  draws_fill(a.d, h, s, lay, params, times, stage_t, batch, is_post, num_samples, n_partials);
   a.below = below; a.inside = inside; a.cross = cross; a.pinball = pinball; a.width = width;
-  return draws_run(h, s, lay, d, a.d, times, stage_t, batch, workspace, workspace_bytes, stream,
-                   [&](hipStream_t st) { return slode_launch_calibration(a, st); });
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, n_partials, workspace, workspace_bytes, stream,
+                     slode_launch_calibration);
 }
 
 size_t slode_grad_payload_floats(const slode_shape* s, const slode_layout* lay, int kind) {

@@ -150,6 +150,24 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += dpp_f<0x140>(v);
   return v;
 }
+// the same move of an int, and the row's maximum, int sum and int minimum in row16_sum's four steps (the maximum and the minimum are
+// selections: no bit depends on the order)
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+template <int CTRL>
+__device__ __forceinline__ float dpp_max_step(float v) { const float o = dpp_f<CTRL>(v); return o > v ? o : v; }
+__device__ __forceinline__ float row16_max(float v) {
+  v = dpp_max_step<0xB1>(v); v = dpp_max_step<0x4E>(v); v = dpp_max_step<0x141>(v); v = dpp_max_step<0x140>(v);
+  return v;
+}
+__device__ __forceinline__ int row16_sum_i(int v) {
+  v += dpp_i<0xB1>(v); v += dpp_i<0x4E>(v); v += dpp_i<0x141>(v); v += dpp_i<0x140>(v);
+  return v;
+}
+__device__ __forceinline__ int row16_min_i(int i) {
+  i = min(i, dpp_i<0xB1>(i)); i = min(i, dpp_i<0x4E>(i)); i = min(i, dpp_i<0x141>(i)); i = min(i, dpp_i<0x140>(i));
+  return i;
+}
 // sum over each half-wave (lanes 0..31, lanes 32..63), valid in every lane of the half: the row's four DPP adds, then v_permlane16_swap
 // hands every row the sum of the other row of its half
 __device__ __forceinline__ float half_wave_sum(float v) {

@@ -1,6 +1,8 @@
-// The fixed-grid forward pass and the draw loop the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip, traj_bounds_kernel.hip,
-// intervene_moments_kernel.hip, attribution_kernel.hip, curve_summary_kernel.hip, recon_quantiles_kernel.hip, mechanism_moments_kernel.hip, joint_band_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip, calibration_kernel.hip, refine_kernel.hip; no other translation unit includes this
-// header): each phase ONCE --
+// The fixed-grid forward pass and the draw loop the eval-side kernels share (eval_kernel.hip, recon_moments_kernel.hip,
+// intervene_moments_kernel.hip, forecast_moments_kernel.hip, cohort_moments_kernel.hip, calibration_kernel.hip; the five whole-curve kernels
+// attribution_kernel.hip, curve_summary_kernel.hip, recon_quantiles_kernel.hip, mechanism_moments_kernel.hip, joint_band_kernel.hip; and,
+// through traj_terms.h, traj_bounds_kernel.hip, pointwise_kernel.hip, refine_kernel.hip; no other translation unit includes this header):
+// each phase ONCE --
 //   kernel arguments   FwdK (dims, solver, the init / dynamics / head offsets), PriorK (conditional prior nets), LabelHeadK (label heads),
 //                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort, calibration) and the host functions that
 //                      fill them from slode_shape / slode_layout / DrawsLaunch
@@ -14,7 +16,8 @@
 //   the draw loop       M1 fwd_draw_source: loc | scale of a trajectory, posterior or conditional prior, into the LDS pieces of
 //                      fwd_lds_loc_sc; M2 fwd_draw_z: z of draw k; M3-M5 fwd_solve: one solve of a step range from a given initial state;
 //                      M6 fwd_state_at, fwd_head_value: the state of a time point, one head value; the shifted moment triple [v0 | s1 | s2]:
-//                      fwd_moment_add, fwd_moment_store (M7)
+//                      fwd_moment_add, fwd_moment_store (M7), fwd_moment_store_pinned (M7 of the kernels whose moments the tests restate
+//                      bit for bit in numpy)
 //   launch             fwd_generic, fwd_dispatch over the compile-time state dim {5, 8, 0}, fwd_launch
 // Every routine keeps the operation order of the kernels it came from: results are bitwise those of the separate copies.
 #pragma once
@@ -400,6 +403,18 @@ __device__ __forceinline__ void fwd_moment_store(const float* m, int P, float in
   const float s1 = m[P], s2 = m[2 * P];
   if (mean) mean[o] = fmaf(s1, inv, m[0]);
   if (sd) sd[o] = sqrtf(fmaxf(s2 - s1 * s1 * inv, 0.f) * inv);
+}
+// M7 with the operation order pinned -- mean = fma(s1, inv, v0); sd = sqrt(max(s2 - (s1 s1) inv, 0) inv), every product and the difference
+// rounded on its own (no contraction into an fma) -- so that the result is bitwise the numpy restatement of the accumulation
+// (tests/recon_moments_util.py: shifted_moments_f32), whatever the compiler would fuse.  The mean is always stored.
+__device__ __forceinline__ void fwd_moment_store_pinned(const float* m, int P, float inv, float* mean, float* sd, long long o) {
+#pragma clang fp contract(off)
+  const float s1 = m[P], s2 = m[2 * P];
+  mean[o] = fmaf(s1, inv, m[0]);
+  if (sd) {
+    const float sq = s1 * s1, sub = sq * inv;
+    sd[o] = sqrtf(fmaxf(s2 - sub, 0.f) * inv);
+  }
 }
 
 // ---- launch ---------------------------------------------------------------------------------------------------------

@@ -589,6 +589,12 @@ class Engine:
     # ---- cohort curves: the draws of recon_moments reduced by cohort -------------------------------------------------------------
     COHORT_OUTPUTS = ("sd", "sd_subjects", "obs_mean", "l1")
 
+    def _plan_bytes(self, fn, B: int, *args) -> int:
+        """A plan entry point whose one figure is the dynamic LDS bytes (host arithmetic only; SlodeError where it refuses)."""
+        r = C.c_size_t(0)
+        _check(self.lib, None, fn(C.byref(self.shape(B)), *[int(a) for a in args], C.byref(r)))
+        return int(r.value)
+
     def _plan4(self, fn, B: int, M: int, G: int, num_samples: int, chunk: int):
         """A plan entry point of the cohort calls: (members per partial, bound on the partials, dynamic LDS bytes, scratch bytes)."""
         r, n, lds, scr = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
@@ -764,9 +770,7 @@ class Engine:
     def pointwise_plan(self, B: int, num_draws: int, weights: int) -> int:
         """``slode_pointwise_plan``: the dynamic LDS bytes of ``pointwise_density`` for this shape (host arithmetic only; raises SlodeError
         where the call would refuse them at its LDS rung)."""
-        r = C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_pointwise_plan(C.byref(self.shape(B)), int(num_draws), int(weights), C.byref(r)))
-        return int(r.value)
+        return self._plan_bytes(self.lib.slode_pointwise_plan, B, num_draws, weights)
 
     def pointwise_density(self, params, batch: L.Batch, B: int, num_draws: int, weights: int, mask=None, loc=None, scale=None, point=None,
                           summary=None, loss_kb=None, particles: int = 1):
@@ -849,9 +853,7 @@ class Engine:
     def attribution_plan(self, B: int, n_arms: int) -> int:
         """``slode_attribution_plan``: the dynamic LDS bytes of ``latent_attribution`` for this shape and ``n_arms`` arms (host arithmetic
         only; raises SlodeError where the call would refuse them at its LDS rung, or for n_arms outside [1, L.ATTRIBUTION_MAX_ARMS])."""
-        r = C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_attribution_plan(C.byref(self.shape(B)), int(n_arms), C.byref(r)))
-        return int(r.value)
+        return self._plan_bytes(self.lib.slode_attribution_plan, B, n_arms)
 
     def latent_attribution(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, arm_masks, mean=None, sd=None, msd=None,
                            particles: int = 1):
@@ -879,9 +881,7 @@ class Engine:
     def curve_summary_plan(self, B: int, want_p_beyond: bool) -> int:
         """``slode_curve_summary_plan``: the dynamic LDS bytes of ``curve_summary`` for this shape, with or without the counters of
         ``p_beyond`` (host arithmetic only; raises SlodeError where the call would refuse them at its LDS rung)."""
-        r = C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_curve_summary_plan(C.byref(self.shape(B)), 1 if want_p_beyond else 0, C.byref(r)))
-        return int(r.value)
+        return self._plan_bytes(self.lib.slode_curve_summary_plan, B, bool(want_p_beyond))
 
     def curve_summary(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, thr, sense: int, mean, sd=None, p_beyond=None,
                       particles: int = 1):
@@ -945,9 +945,7 @@ class Engine:
     def mechanism_plan(self, B: int, slots: int) -> int:
         """``slode_mechanism_plan``: the dynamic LDS bytes of ``mechanism_moments`` for this shape and the slot mask ``slots`` (host arithmetic
         only; raises SlodeError where the call would refuse them at its mask or LDS rung)."""
-        r = C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_mechanism_plan(C.byref(self.shape(B)), int(slots), C.byref(r)))
-        return int(r.value)
+        return self._plan_bytes(self.lib.slode_mechanism_plan, B, slots)
 
     def mechanism_moments(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, slots: int, mean=None, sd=None):
         """slode_mechanism_moments: per trajectory, state component and grid point, the mean and the population sd over ``num_samples`` latent
@@ -971,9 +969,7 @@ class Engine:
     def joint_band_plan(self, B: int, num_samples: int) -> int:
         """``slode_joint_band_plan``: the dynamic LDS bytes of ``joint_band`` for this shape and draw count (host arithmetic only; raises
         SlodeError where the call would refuse them at its draw-count or LDS rung)."""
-        r = C.c_size_t(0)
-        _check(self.lib, None, self.lib.slode_joint_band_plan(C.byref(self.shape(B)), int(num_samples), C.byref(r)))
-        return int(r.value)
+        return self._plan_bytes(self.lib.slode_joint_band_plan, B, num_samples)
 
     def joint_band_levels(self, num_samples: int, levels):
         """``slode_joint_band_levels``: ``(ranks, z)`` of ``joint_band`` for ``num_samples`` draws as the call forms them on the host in

@@ -2,6 +2,7 @@
 [_Gauss].py).  The per-dataset modules only declare their label schema and attribute names."""
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Tuple
 
@@ -325,6 +326,82 @@ class MechanisticBase(nn.Module):
             np.save(path, val.cpu().numpy())
             written.append(path)
         return written
+
+    # ---- what the whole-curve calls share (latent_attribution, curve_summary, recon_quantiles, mechanism_moments, simultaneous_band) ----
+    @staticmethod
+    def _levels_list(levels, most: int, open_at_zero: bool):
+        """``levels`` (a sequence, or a tensor read on the host once) as a list of floats: 1 to ``most`` values in [0, 1] -- in (0, 1] with
+        ``open_at_zero`` -- or ValueError."""
+        lv = [float(x) for x in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
+        if not 1 <= len(lv) <= most:
+            raise ValueError("levels must hold 1 to %d values, got %d" % (most, len(lv)))
+        if any(not ((0.0 < x if open_at_zero else 0.0 <= x) and x <= 1.0) for x in lv):
+            raise ValueError("levels must lie in %s, got %r" % ("(0, 1]" if open_at_zero else "[0, 1]", lv))
+        return lv
+
+    @staticmethod
+    def _fewest_calls(n_items: int, cap: int, plan):
+        """``n_items`` items (arms, slots) in the fewest engine calls that fit the LDS, as even as that number allows: ``[(lo, hi)]``.
+        ``plan(n)`` raises SlodeError where a call of n items does not fit (one item is not asked: the call itself refuses it); ``cap``:
+        the most items of one call."""
+        from .. import _lib as L
+        fit = min(n_items, cap)
+        while fit > 1:
+            try:
+                plan(fit)
+                break
+            except L.SlodeError:
+                fit -= 1
+        n_calls = -(-n_items // fit)
+        per = -(-n_items // n_calls)
+        return [(lo, min(lo + per, n_items)) for lo in range(0, n_items, per)]
+
+    @staticmethod
+    def _on_the_same_noise(eng, eps, slices, call):
+        """``[call(lo, hi)]`` over ``slices``, every call rewound to the drawing call the first begins at (``eps`` given: nothing to rewind),
+        so the counter ends where ONE call leaves it and the split changes no bit."""
+        n0 = None if eps is not None else eng.rng_state()[2]
+        out = []
+        for lo, hi in slices:
+            if n0 is not None:
+                eng.rng_set_counter(n0)
+            out.append(call(lo, hi))
+        return out
+
+    @contextlib.contextmanager
+    def _counter_moves_by(self, moved: int, eps):
+        """Around a composed route that stands in for an engine call which moves the generator's counter by ``moved``: whatever the route
+        draws, the counter ends at n + ``moved`` (``eps`` given: the generator is not used)."""
+        eng = self._bind().engine
+        n0 = eng.rng_state()[2] if eps is None else None
+        yield
+        if n0 is not None:
+            eng.rng_set_counter(n0 + moved)
+
+    def _save_over_batches(self, results_dir, batches, call, rows, dim: int = 0, side=None):
+        """``call(**batch)`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors); ``rows(result)``
+        yields the batch's ``(file name, tensor)`` pairs, which are concatenated along ``dim`` (the trajectories, in loader order) and
+        written with ONE read-back, at the end; then the side file ``side`` = ``(file name, write(path, last result or None))``.  Returns
+        the paths."""
+        import os
+        parts, r = {}, None
+        for d in batches:
+            r = call(**d)
+            for fname, t in rows(r):
+                parts.setdefault(fname, []).append(t)
+        written = self._save_arrays(results_dir, ((fname, torch.cat(v, dim)) for fname, v in parts.items()))
+        if side is not None:
+            os.makedirs(results_dir, exist_ok=True)
+            path = os.path.join(results_dir, side[0])
+            side[1](path, r)
+            written.append(path)
+        return written
+
+    @staticmethod
+    def _save_levels(path, r):
+        """The side file of a call with levels: the float64 ``"levels"`` of its last result (no batch: an empty array)."""
+        import numpy as np
+        np.save(path, np.asarray([] if r is None else r["levels"].tolist(), dtype=np.float64))
 
     # ---- the statistics row of one batch (training.input_pred_stats_fused) -------------------------------------------------
     def eval_stat_slots(self) -> Dict[str, int]:
@@ -933,28 +1010,13 @@ class MechanisticBase(nn.Module):
 
         def fused():
             eng = b.engine
-            fit = min(len(masks), L.ATTRIBUTION_MAX_ARMS, self.ATTRIBUTION_ARMS_PER_CALL or L.ATTRIBUTION_MAX_ARMS)
-            while fit > 1:
-                try:
-                    eng.attribution_plan(B, fit)
-                    break
-                except L.SlodeError:
-                    fit -= 1
-            n_calls = -(-len(masks) // fit)
-            per = -(-len(masks) // n_calls)
+            slices = self._fewest_calls(len(masks), min(L.ATTRIBUTION_MAX_ARMS, self.ATTRIBUTION_ARMS_PER_CALL or L.ATTRIBUTION_MAX_ARMS),
+                                        lambda n: eng.attribution_plan(B, n))
             bt = eng.make_batch(observations, self._label_tensors(labels, B), eps, particles=ns,
                                 eps_shape=None if eps is None else (2, ns, B, eng.spec.latent_dim))
-            n0 = None if eps is not None else eng.rng_state()[2]
-            mean = sd = None
-            parts = []
-            for i in range(0, len(masks), per):
-                if n0 is not None:
-                    eng.rng_set_counter(n0)        # every call on the same noise: drawing calls n0, n0 + 1
-                m, s, msd = eng.latent_attribution(b.flat, bt, B, is_post, ns, masks[i:i + per], mean=None if i == 0 else False,
-                                                   sd=None if i == 0 else False)
-                if i == 0:
-                    mean, sd = m, s
-                parts.append(msd)
+            got = self._on_the_same_noise(eng, eps, slices, lambda lo, hi: eng.latent_attribution(      # (drawing calls n0, n0 + 1 every time)
+                b.flat, bt, B, is_post, ns, masks[lo:hi], mean=None if lo == 0 else False, sd=None if lo == 0 else False))
+            (mean, sd, _), parts = got[0], [g[2] for g in got]
             return self._attribution_result(blocks, single, comp, mean, sd * sd, parts[0] if len(parts) == 1 else torch.cat(parts, 0))
 
         def composed():
@@ -989,21 +1051,16 @@ class MechanisticBase(nn.Module):
         curves in the engine's order, blocks, the trajectories in loader order), ``attribution_total_index_<post|prior>.npy`` /
         ``attribution_first_index_<post|prior>.npy``, float64 ``[Q, P, n, C]``, and ``attribution_blocks.txt``, one block name per line.  One
         read-back, at the end.  Returns the paths."""
-        import os
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        keys = ("total", "first", "total_index", "first_index")
-        parts = {k: [] for k in keys}
-        for d in batches:
-            r = self.latent_attribution(is_post=is_post, num_samples=num_samples, **d)
-            for k in keys:
-                parts[k].append(torch.stack([r[n][k] for n in names], 0))
         tag = "post" if is_post else "prior"
-        written = self._save_arrays(results_dir, (("attribution_%s_%s.npy" % (k, tag), torch.cat(parts[k], 2)) for k in keys if parts[k]))
-        os.makedirs(results_dir, exist_ok=True)
-        path = os.path.join(results_dir, "attribution_blocks.txt")
-        with open(path, "w") as f:
-            f.write("\n".join(self.attribution_blocks()) + "\n")
-        return written + [path]
+
+        def blocks(path, _):
+            with open(path, "w") as f:
+                f.write("\n".join(self.attribution_blocks()) + "\n")
+        return self._save_over_batches(
+            results_dir, batches, lambda **d: self.latent_attribution(is_post=is_post, num_samples=num_samples, **d),
+            lambda r: (("attribution_%s_%s.npy" % (k, tag), torch.stack([r[n][k] for n in names], 0))
+                       for k in ("total", "first", "total_index", "first_index")), dim=2, side=("attribution_blocks.txt", blocks))
 
     def attribution_line(self, total_index, first_index, tag):
         """One printed line of a ``save_latent_attribution`` pass: per block, the mean over head curves, trajectories and channels of the
@@ -1119,22 +1176,14 @@ class MechanisticBase(nn.Module):
         """Runs ``curve_summary`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
         ``summary_<curve>_<post|prior>_mean.npy`` / ``..._sd.npy``, float32 ``[n, C, 8]`` (the trajectories in loader order, the slots in
         ``SUMMARY_NAMES`` order), and ``summary_slots.npy``, the slot names.  One read-back, at the end.  Returns the paths."""
-        import os
         import numpy as np
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        parts = {(n, k): [] for n in names for k in (0, 1)}
-        for d in batches:
-            r = self.curve_summary(is_post=is_post, num_samples=num_samples, thresholds=thresholds, sense=sense, **d)
-            for n in names:
-                for k in (0, 1):
-                    parts[(n, k)].append(torch.stack([r[n][slot][k] for slot in self.SUMMARY_NAMES], -1))
         tag = "post" if is_post else "prior"
-        written = self._save_arrays(results_dir, (("summary_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.cat(v, 0))
-                                                  for (n, k), v in parts.items() if v))
-        os.makedirs(results_dir, exist_ok=True)
-        path = os.path.join(results_dir, "summary_slots.npy")
-        np.save(path, np.array(self.SUMMARY_NAMES))
-        return written + [path]
+        return self._save_over_batches(
+            results_dir, batches, lambda **d: self.curve_summary(is_post=is_post, num_samples=num_samples, thresholds=thresholds, sense=sense, **d),
+            lambda r: (("summary_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.stack([r[n][slot][k] for slot in self.SUMMARY_NAMES], -1))
+                       for n in names for k in (0, 1)),
+            side=("summary_slots.npy", lambda path, _: np.save(path, np.array(self.SUMMARY_NAMES))))
 
     def summary_line(self, mean, tag, with_threshold: bool):
         """One printed line of a ``save_curve_summary`` pass from the central curve's ``mean`` array ``[n, C, 8]``: per channel, the mean over
@@ -1194,11 +1243,7 @@ class MechanisticBase(nn.Module):
         sort was measured faster)."""
         b = self._bind()
         B, ns = observations.shape[0], self._count(num_samples)
-        lv = [float(x) for x in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
-        if not 1 <= len(lv) <= self.QUANTILE_MAX_LEVELS:
-            raise ValueError("levels must hold 1 to %d values, got %d" % (self.QUANTILE_MAX_LEVELS, len(lv)))
-        if any(not 0.0 <= x <= 1.0 for x in lv):
-            raise ValueError("levels must lie in [0, 1], got %r" % (lv,))
+        lv = self._levels_list(levels, self.QUANTILE_MAX_LEVELS, open_at_zero=False)
         T = int(self.times.numel())
         if not 0 <= int(tile) <= T:
             raise ValueError("tile must lie in [0, T = %d], got %d" % (T, int(tile)))
@@ -1212,15 +1257,13 @@ class MechanisticBase(nn.Module):
                         .unbind(1))
 
         def composed():
-            n0 = b.engine.rng_state()[2] if eps is None else None
             parts = {n: [] for n in names}
-            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
-                res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
-                for n in names:
-                    parts[n].append(self._sample_quantiles(res[n], lv))
-                del res
-            if n0 is not None:
-                b.engine.rng_set_counter(n0 + ns)      # as the engine call leaves it
+            with self._counter_moves_by(ns, eps):
+                for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                    res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
+                    for n in names:
+                        parts[n].append(self._sample_quantiles(res[n], lv))
+                    del res
             return pack([torch.cat(parts[n], 1) for n in names])
 
         def planned():
@@ -1233,22 +1276,12 @@ class MechanisticBase(nn.Module):
         """Runs ``recon_quantiles`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
         ``<curve>_<post|prior>_sample_quantiles.npy``, float32 ``[n, Lv, C, T]`` (the trajectories in loader order), for every head curve and
         ``sample_quantile_levels.npy``, the levels.  One read-back, at the end.  Returns the paths."""
-        import os
-        import numpy as np
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        parts = {n: [] for n in names}
-        lv = None
-        for d in batches:
-            r = self.recon_quantiles(is_post=is_post, num_samples=num_samples, levels=levels, **d)
-            lv = r["levels"]
-            for n in names:
-                parts[n].append(r[n].transpose(0, 1))
         tag = "post" if is_post else "prior"
-        written = self._save_arrays(results_dir, (("%s_%s_sample_quantiles.npy" % (n, tag), torch.cat(v, 0)) for n, v in parts.items() if v))
-        os.makedirs(results_dir, exist_ok=True)
-        path = os.path.join(results_dir, "sample_quantile_levels.npy")
-        np.save(path, np.asarray([] if lv is None else lv.tolist(), dtype=np.float64))
-        return written + [path]
+        return self._save_over_batches(
+            results_dir, batches, lambda **d: self.recon_quantiles(is_post=is_post, num_samples=num_samples, levels=levels, **d),
+            lambda r: (("%s_%s_sample_quantiles.npy" % (n, tag), r[n].transpose(0, 1)) for n in names),
+            side=("sample_quantile_levels.npy", self._save_levels))
 
     @staticmethod
     def quantile_line(quantiles, levels, observations, tag):
@@ -1291,24 +1324,12 @@ class MechanisticBase(nn.Module):
 
         def fused():
             eng = b.engine
-            fit = min(len(sel), self.MECHANISM_SLOTS_PER_CALL or L.MECHANISM_SLOTS)
-            while fit > 1:
-                try:
-                    eng.mechanism_plan(B, (1 << fit) - 1)      # the LDS figure depends on the slot count alone
-                    break
-                except L.SlodeError:
-                    fit -= 1
-            n_calls = -(-len(sel) // fit)
-            per = -(-len(sel) // n_calls)
+            slices = self._fewest_calls(len(sel), self.MECHANISM_SLOTS_PER_CALL or L.MECHANISM_SLOTS,
+                                        lambda n: eng.mechanism_plan(B, (1 << n) - 1))      # the LDS figure depends on the slot count alone
             bt = self._draws_batch(observations, labels, eps, ns)
-            n0 = None if eps is not None else eng.rng_state()[2]
-            means, sds = [], []
-            for i in range(0, len(sel), per):
-                if n0 is not None:
-                    eng.rng_set_counter(n0)        # every call on the same noise: drawing call n0
-                m, s = eng.mechanism_moments(b.flat, bt, B, is_post, ns, sum(1 << q for q in sel[i:i + per]))
-                means.extend(m.unbind(0)); sds.extend(s.unbind(0))
-            return pack([m.permute(0, 2, 1) for m in means], [s.permute(0, 2, 1) for s in sds])
+            got = self._on_the_same_noise(eng, eps, slices, lambda lo, hi: eng.mechanism_moments(      # (drawing call n0 every time)
+                b.flat, bt, B, is_post, ns, sum(1 << q for q in sel[lo:hi])))
+            return pack([m.permute(0, 2, 1) for g in got for m in g[0].unbind(0)], [s.permute(0, 2, 1) for g in got for s in g[1].unbind(0)])
 
         def composed():
             with torch.no_grad():
@@ -1335,15 +1356,10 @@ class MechanisticBase(nn.Module):
         """Runs ``mechanism_moments`` (all five quantities) over ``batches`` (an iterable of device batch dicts: ``observations`` + the label
         tensors) and writes ``mechanism_<name>_<post|prior>_mean.npy`` / ``..._sd.npy``, float32 ``[n, T, S]`` (the trajectories in loader
         order).  One read-back, at the end.  Returns the paths."""
-        parts = {(n, k): [] for n in self.MECHANISM_NAMES for k in (0, 1)}
-        for d in batches:
-            r = self.mechanism_moments(is_post=is_post, num_samples=num_samples, **d)
-            for n in self.MECHANISM_NAMES:
-                for k in (0, 1):
-                    parts[(n, k)].append(r[n][k])
         tag = "post" if is_post else "prior"
-        return self._save_arrays(results_dir, (("mechanism_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.cat(v, 0))
-                                               for (n, k), v in parts.items() if v))
+        return self._save_over_batches(
+            results_dir, batches, lambda **d: self.mechanism_moments(is_post=is_post, num_samples=num_samples, **d),
+            lambda r: (("mechanism_%s_%s_%s.npy" % (n, tag, ("mean", "sd")[k]), r[n][k]) for n in self.MECHANISM_NAMES for k in (0, 1)))
 
     @staticmethod
     def mechanism_line(res, tag):
@@ -1391,11 +1407,7 @@ class MechanisticBase(nn.Module):
         B, ns = observations.shape[0], self._count(num_samples)
         if ns < 2:
             raise ValueError("num_samples must be >= 2 (the sd of one draw is 0), got %d" % ns)
-        lv = [float(x) for x in (levels.detach().cpu().reshape(-1).tolist() if isinstance(levels, torch.Tensor) else levels)]
-        if not 1 <= len(lv) <= self.BAND_MAX_LEVELS:
-            raise ValueError("levels must hold 1 to %d values, got %d" % (self.BAND_MAX_LEVELS, len(lv)))
-        if any(not 0.0 < x <= 1.0 for x in lv):
-            raise ValueError("levels must lie in (0, 1], got %r" % (lv,))
+        lv = self._levels_list(levels, self.BAND_MAX_LEVELS, open_at_zero=True)
         floor = float(sd_floor)
         if not (floor >= 0.0 and math.isfinite(floor)):
             raise ValueError("sd_floor must be finite and >= 0, got %r" % (sd_floor,))
@@ -1419,27 +1431,25 @@ class MechanisticBase(nn.Module):
                          for q in range(len(names))])
 
         def composed():
-            n0 = b.engine.rng_state()[2] if eps is None else None
             rz = self._band_levels(lv, ns)
             cols = {n: [] for n in names}
-            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
-                res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
-                y = d["observations"].to(torch.float32)
-                for n in names:
-                    v = res[n].to(torch.float32)                                                       # [rows, C, T, ns]
-                    mean, sd = self._mean_sd(v)
-                    on = sd > floor
-                    neg = torch.full_like(sd, -1.0)
-                    e_k = torch.where(on.unsqueeze(-1), (v - mean.unsqueeze(-1)).abs() / sd.unsqueeze(-1), neg.unsqueeze(-1))
-                    dev = e_k.amax(dim=2).clamp_min(0.0)                                                # [rows, C, ns]
-                    odev = torch.where(on, (y.to(mean.device) - mean).abs() / sd, neg).amax(dim=2).clamp_min(0.0)
-                    srt = torch.sort(dev, dim=-1).values
-                    crit = torch.stack([srt[..., r - 1] for r, _ in rz], -1)
-                    joint = torch.stack([(dev <= torch.tensor(z, dtype=torch.float32)).sum(-1).to(torch.float32) / float(ns) for _, z in rz], -1)
-                    cols[n].append((mean, sd, crit, joint, odev, on.sum(dim=2).to(torch.float32), dev))
-                del res
-            if n0 is not None:
-                b.engine.rng_set_counter(n0 + 1)      # as the engine call leaves it
+            with self._counter_moves_by(1, eps):
+                for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                    res = self.recon_samples(is_post=is_post, num_samples=ns, eps=e, **d)
+                    y = d["observations"].to(torch.float32)
+                    for n in names:
+                        v = res[n].to(torch.float32)                                                       # [rows, C, T, ns]
+                        mean, sd = self._mean_sd(v)
+                        on = sd > floor
+                        neg = torch.full_like(sd, -1.0)
+                        e_k = torch.where(on.unsqueeze(-1), (v - mean.unsqueeze(-1)).abs() / sd.unsqueeze(-1), neg.unsqueeze(-1))
+                        dev = e_k.amax(dim=2).clamp_min(0.0)                                                # [rows, C, ns]
+                        odev = torch.where(on, (y.to(mean.device) - mean).abs() / sd, neg).amax(dim=2).clamp_min(0.0)
+                        srt = torch.sort(dev, dim=-1).values
+                        crit = torch.stack([srt[..., r - 1] for r, _ in rz], -1)
+                        joint = torch.stack([(dev <= torch.tensor(z, dtype=torch.float32)).sum(-1).to(torch.float32) / float(ns) for _, z in rz], -1)
+                        cols[n].append((mean, sd, crit, joint, odev, on.sum(dim=2).to(torch.float32), dev))
+                    del res
             return pack([tuple(torch.cat(c, 0) for c in zip(*cols[n])) for n in names])
         return self._fused_or_composed(fused, composed)
 
@@ -1450,23 +1460,12 @@ class MechanisticBase(nn.Module):
         for every head curve, ``<curve>_<post|prior>_band_{mean,sd}.npy`` ``[n, C, T]``, ``..._band_{crit,pointwise_joint}.npy``
         ``[n, Lv, C]`` and ``..._band_obs_dev.npy`` ``[n, C]`` (the trajectories in loader order), and ``band_levels.npy``.  One
         read-back, at the end.  Returns the paths."""
-        import os
-        import numpy as np
         names = self.MOMENT_HEADS[bool(self.GAUSS)]
-        parts = {(n, k): [] for n in names for k in self.BAND_FILES}
-        lv = None
-        for d in batches:
-            r = self.simultaneous_band(is_post=is_post, num_samples=num_samples, levels=levels, **d)
-            lv = r["levels"]
-            for n in names:
-                for k in self.BAND_FILES:
-                    parts[(n, k)].append(r[n][k].transpose(0, 1) if k in ("crit", "pointwise_joint") else r[n][k])
         tag = "post" if is_post else "prior"
-        written = self._save_arrays(results_dir, (("%s_%s_band_%s.npy" % (n, tag, k), torch.cat(v, 0)) for (n, k), v in parts.items() if v))
-        os.makedirs(results_dir, exist_ok=True)
-        path = os.path.join(results_dir, "band_levels.npy")
-        np.save(path, np.asarray([] if lv is None else lv.tolist(), dtype=np.float64))
-        return written + [path]
+        return self._save_over_batches(
+            results_dir, batches, lambda **d: self.simultaneous_band(is_post=is_post, num_samples=num_samples, levels=levels, **d),
+            lambda r: (("%s_%s_band_%s.npy" % (n, tag, k), r[n][k].transpose(0, 1) if k in ("crit", "pointwise_joint") else r[n][k])
+                       for n in names for k in self.BAND_FILES), side=("band_levels.npy", self._save_levels))
 
     @classmethod
     def band_line(cls, crit, joint, obs_dev, levels, tag):

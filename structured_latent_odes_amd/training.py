@@ -281,52 +281,26 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                     np.load([f for f in written if "p_waic" in f][0]), int(waic))
         print(line)
         logging.debug("%s (%s)", line, written)
-    if attribution:
-        for is_post in (True, False):
-            tag = "post" if is_post else "prior"
-            written = best_model.save_latent_attribution(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(attribution))
-            line = best_model.attribution_line(np.load([f for f in written if f.endswith("attribution_total_index_%s.npy" % tag)][0]),
-                                               np.load([f for f in written if f.endswith("attribution_first_index_%s.npy" % tag)][0]), tag)
-            print(line)
-            logging.debug("%s (%s)", line, written)
-    if curve_summary:
-        for is_post in (True, False):
-            tag = "post" if is_post else "prior"
-            written = best_model.save_curve_summary(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(curve_summary),
-                                                    thresholds=summary_thresholds, sense=summary_sense)
-            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
-            line = best_model.summary_line(np.load([f for f in written if f.endswith("summary_%s_%s_mean.npy" % (central, tag))][0]), tag,
-                                           summary_thresholds is not None)
-            print(line)
-            logging.debug("%s (%s)", line, written)
-    if sample_quantiles:
-        for is_post in (True, False):
-            tag = "post" if is_post else "prior"
-            written = best_model.save_recon_quantiles(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(sample_quantiles),
-                                                      levels=quantile_levels)
-            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
-            obs = np.concatenate([np.asarray(batch_to_device(b, "cpu", family)["observations"]) for b in val_b], 0)
-            line = best_model.quantile_line(np.load([f for f in written if f.endswith("%s_%s_sample_quantiles.npy" % (central, tag))][0]),
-                                            np.load([f for f in written if f.endswith("sample_quantile_levels.npy")][0]), obs, tag)
-            print(line)
-            logging.debug("%s (%s)", line, written)
-    if mechanism:
-        for is_post in (True, False):
-            tag = "post" if is_post else "prior"
-            written = best_model.save_mechanism_moments(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(mechanism))
-            line = best_model.mechanism_line({k: np.load([f for f in written if f.endswith("mechanism_%s_%s_mean.npy" % (k, tag))][0])
-                                              for k in ("production", "degradation", "set_point")}, tag)
-            print(line)
-            logging.debug("%s (%s)", line, written)
-    if joint_band:
-        for is_post in (True, False):
-            tag = "post" if is_post else "prior"
-            written = best_model.save_simultaneous_band(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(joint_band),
-                                                        levels=band_levels)
-            central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
-            crit, joint, odev = (np.load([f for f in written if f.endswith("%s_%s_band_%s.npy" % (central, tag, k))][0])
-                                 for k in ("crit", "pointwise_joint", "obs_dev"))
-            line = best_model.band_line(crit, joint, odev, np.load([f for f in written if f.endswith("band_levels.npy")][0]), tag)
+    # the whole-curve passes, posterior and prior each: (flag value = draws, save method, its keyword arguments, the printed line from
+    # load(file-name ending), the central curve's name and the side's tag)
+    curve_passes = (
+        (attribution, "save_latent_attribution", {}, lambda m, load, central, tag: m.attribution_line(
+            load("attribution_total_index_%s.npy" % tag), load("attribution_first_index_%s.npy" % tag), tag)),
+        (curve_summary, "save_curve_summary", dict(thresholds=summary_thresholds, sense=summary_sense), lambda m, load, central, tag: m.summary_line(
+            load("summary_%s_%s_mean.npy" % (central, tag)), tag, summary_thresholds is not None)),
+        (sample_quantiles, "save_recon_quantiles", dict(levels=quantile_levels), lambda m, load, central, tag: m.quantile_line(
+            load("%s_%s_sample_quantiles.npy" % (central, tag)), load("sample_quantile_levels.npy"),
+            np.concatenate([np.asarray(batch_to_device(b, "cpu", family)["observations"]) for b in val_b], 0), tag)),
+        (mechanism, "save_mechanism_moments", {}, lambda m, load, central, tag: m.mechanism_line(
+            {k: load("mechanism_%s_%s_mean.npy" % (k, tag)) for k in ("production", "degradation", "set_point")}, tag)),
+        (joint_band, "save_simultaneous_band", dict(levels=band_levels), lambda m, load, central, tag: m.band_line(
+            *(load("%s_%s_band_%s.npy" % (central, tag, k)) for k in ("crit", "pointwise_joint", "obs_dev")), load("band_levels.npy"), tag)),
+    )
+    for flag, save, kwargs, line_of in curve_passes:
+        for is_post in (True, False) if flag else ():
+            written = getattr(best_model, save)(out_dir, (batch_to_device(b, device, family) for b in val_b), is_post, int(flag), **kwargs)
+            line = line_of(best_model, lambda ending: np.load([f for f in written if f.endswith(ending)][0]),
+                           best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0], "post" if is_post else "prior")
             print(line)
             logging.debug("%s (%s)", line, written)
     if forecast_steps:

@@ -26,43 +26,14 @@ static int call(int which, Cfg& c, const Head& a, const char** column) {
                                   c.ws_bytes, nullptr);
 }
 
-static void pair(const char* name, const Edit& edit) {
-  for (int post : {1, 0}) { Cfg c; c.is_post = post; edit(c); run(name, c); }
-}
-static void post(const char* name, const Edit& edit) { one(name, edit); }
-static void prior(const char* name, const Edit& edit) { Cfg c; c.is_post = 0; edit(c); run(name, c); }
-// (the plan takes no handle: its reason is the global text, which a NULL handle reads)
-static void plan(const char* name, const Edit& edit) { Cfg c; c.no_handle = true; edit(c); run(name, c, 1); }
 
 int main() {
-  // ---- NULL pointers
-  pair("handle NULL", [](Cfg& c) { c.no_handle = true; });
-  pair("shape NULL", [](Cfg& c) { c.no_shape = true; });
-  pair("layout NULL", [](Cfg& c) { c.no_layout = true; });
-  pair("params NULL", [](Cfg& c) { c.no_params = true; });
-  pair("batch NULL", [](Cfg& c) { c.no_batch = true; });
-  pair("times NULL", [](Cfg& c) { c.times = nullptr; });
-  pair("stage_t NULL", [](Cfg& c) { c.stage_t = nullptr; });
-  pair("workspace NULL", [](Cfg& c) { c.ws = nullptr; });
-  pair("bad shape", [](Cfg& c) { c.s.T = 1; });
+  ladder_pointers();
   // ---- the draw count
   pair("num_samples 0", [](Cfg& c) { c.draws = 0; });
   pair("num_samples 2^30", [](Cfg& c) { c.draws = 1 << 30; });
-  // ---- what the fused kernels do not take
-  for (int m : {SLODE_DOPRI5, SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN}) {
-    char name[64];
-    snprintf(name, sizeof(name), "adaptive method %d", m);
-    pair(name, [m](Cfg& c) { c.s.method = m; });
-  }
-  pair("particles 2", [](Cfg& c) { c.s.particles = 2; });
-  pair("fold_on", [](Cfg& c) { c.ctx.fold_on = 1; });
-  pair("ode_pack", [](Cfg& c) { c.ctx.ode_pack = 4; });
-  pair("ode_alg", [](Cfg& c) { c.ctx.ode_alg = 1; });
-  // ---- the observations: the posterior alone reads them
-  post("obs NULL", [](Cfg& c) { c.b.obs = nullptr; });
-  post("padded strides", [](Cfg& c) { c.b.obs_strides[0] += 8; });
-  post("channel-major strides of another T", [](Cfg& c) { c.b.obs_strides[1] = c.s.T + 1; c.b.obs_strides[2] = 1; });
-  post("no_fold", [](Cfg& c) { c.ctx.no_fold = 1; });
+  ladder_not_taken();
+  ladder_post_obs();
   // ---- the call's own rungs
   pair("n_arms 0", [](Cfg& c) { c.n_arms = 0; });
   pair("n_arms -3", [](Cfg& c) { c.n_arms = -3; });
@@ -75,20 +46,12 @@ int main() {
   pair("no groups: the rest block is bit 0, bits beyond it", [](Cfg& c) { c.s.n_groups = 0; c.s.n_u = 0; c.b.n_labels = 0; });
   pair("LDS: T 1024", [](Cfg& c) { c.s.T = 1024; c.b.obs_strides[0] = 3072; c.ws_bytes = 64; });
   pair("LDS: T 500, n_arms 16", [](Cfg& c) { c.s.T = 500; c.b.obs_strides[0] = 1500; c.n_arms = 16; for (int i = 6; i < 16; ++i) c.masks[i] = 7u; c.ws_bytes = 64; });
-  // ---- the label tensors
-  pair("label columns 3, n_u 2", [](Cfg& c) { c.b.label_width[1] = 2; });
-  pair("n_labels 5", [](Cfg& c) { c.b.n_labels = 5; });
-  pair("label tensor 1 NULL", [](Cfg& c) { c.b.labels[1] = nullptr; });
-  prior("no label tensors", [](Cfg& c) { c.b.n_labels = 0; });
+  ladder_labels();
   // ---- the workspace
   pair("workspace too small", [](Cfg& c) { c.ws_bytes = 64; });
   pair("mean and sd NULL, mask 0 among the arms; workspace too small", [](Cfg& c) { c.mean = nullptr; c.sd = nullptr; c.masks[0] = 0u; c.ws_bytes = 64; });
   // ---- two conditions at once: the earlier rung speaks
-  pair("params NULL + batch NULL", [](Cfg& c) { c.no_params = true; c.no_batch = true; });
-  pair("times NULL + num_samples 0", [](Cfg& c) { c.times = nullptr; c.draws = 0; });
-  pair("num_samples 0 + adaptive", [](Cfg& c) { c.draws = 0; c.s.method = SLODE_DOPRI5; });
-  pair("adaptive + particles 2", [](Cfg& c) { c.s.method = SLODE_BOSH3; c.s.particles = 2; });
-  post("ode_alg + obs NULL", [](Cfg& c) { c.ctx.ode_alg = 2; c.b.obs = nullptr; });
+  ladder_two_at_once(0);
   post("no_fold + n_arms 0", [](Cfg& c) { c.ctx.no_fold = 1; c.n_arms = 0; });
   pair("n_arms 17 + arm_masks NULL", [](Cfg& c) { c.n_arms = 17; c.arm_masks = nullptr; });
   pair("msd NULL + mask bit 3", [](Cfg& c) { c.msd = nullptr; c.masks[0] = 8u; });
@@ -103,9 +66,6 @@ int main() {
   plan("n_arms 17", [](Cfg& c) { c.n_arms = 17; });
   plan("LDS: T 1024", [](Cfg& c) { c.s.T = 1024; });
   plan("LDS: T 500, n_arms 16", [](Cfg& c) { c.s.T = 500; c.n_arms = 16; });
-  // the memory that stands for every output: never written
-  bool clean = true;
-  for (float v : g_mem) clean = clean && v == 0.f;
-  printf("memory that stands for the outputs | %s\n", clean ? "untouched" : "WRITTEN");
+  memory_untouched();
   return 0;
 }

@@ -41,48 +41,20 @@ static int call(int which, Cfg& c, const Head& a, const char** column) {
                           c.sd_floor, c.mean, c.sd, c.crit, c.joint, c.obs_dev, c.dev_out, c.ws, c.ws_bytes, nullptr);
 }
 
-static void pair(const char* name, const Edit& edit) {
-  for (int post : {1, 0}) { Cfg c; c.is_post = post; edit(c); run(name, c); }
-}
-static void post(const char* name, const Edit& edit) { one(name, edit); }
-static void prior(const char* name, const Edit& edit) { Cfg c; c.is_post = 0; edit(c); run(name, c); }
-// (the plan and the level rule take no handle: their reason is the global text, which a NULL handle reads)
-static void plan(const char* name, const Edit& edit) { Cfg c; c.no_handle = true; edit(c); run(name, c, 1); }
+// (the level rule takes no handle, as the plan)
 static void levels(const char* name, const Edit& edit) { Cfg c; c.no_handle = true; edit(c); run(name, c, 2); }
 
 // T = 1024, S = 5, C = 3: the step table is 40 KB and the moment / value table 108 KB; the deviations take 36 B per draw
 static void big(Cfg& c) { c.s.T = 1024; c.b.obs_strides[0] = 3072; }
 
 int main() {
-  // ---- NULL pointers
-  pair("handle NULL", [](Cfg& c) { c.no_handle = true; });
-  pair("shape NULL", [](Cfg& c) { c.no_shape = true; });
-  pair("layout NULL", [](Cfg& c) { c.no_layout = true; });
-  pair("params NULL", [](Cfg& c) { c.no_params = true; });
-  pair("batch NULL", [](Cfg& c) { c.no_batch = true; });
-  pair("times NULL", [](Cfg& c) { c.times = nullptr; });
-  pair("stage_t NULL", [](Cfg& c) { c.stage_t = nullptr; });
-  pair("workspace NULL", [](Cfg& c) { c.ws = nullptr; });
-  pair("bad shape", [](Cfg& c) { c.s.T = 1; });
+  ladder_pointers();
   // ---- the draw count
   pair("num_samples 0", [](Cfg& c) { c.draws = 0; });
   pair("num_samples 1", [](Cfg& c) { c.draws = 1; });
   pair("num_samples 2^30", [](Cfg& c) { c.draws = 1 << 30; });
-  // ---- what the fused kernels do not take
-  for (int m : {SLODE_DOPRI5, SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN}) {
-    char name[64];
-    snprintf(name, sizeof(name), "adaptive method %d", m);
-    pair(name, [m](Cfg& c) { c.s.method = m; });
-  }
-  pair("particles 2", [](Cfg& c) { c.s.particles = 2; });
-  pair("fold_on", [](Cfg& c) { c.ctx.fold_on = 1; });
-  pair("ode_pack", [](Cfg& c) { c.ctx.ode_pack = 4; });
-  pair("ode_alg", [](Cfg& c) { c.ctx.ode_alg = 1; });
-  // ---- the observations: the posterior needs them ...
-  post("obs NULL", [](Cfg& c) { c.b.obs = nullptr; });
-  post("padded strides", [](Cfg& c) { c.b.obs_strides[0] += 8; });
-  post("channel-major strides of another T", [](Cfg& c) { c.b.obs_strides[1] = c.s.T + 1; c.b.obs_strides[2] = 1; });
-  post("no_fold", [](Cfg& c) { c.ctx.no_fold = 1; });
+  ladder_not_taken();
+  ladder_post_obs();   // (the posterior needs the observations ...)
   // ---- the call's own rungs
   pair("mean NULL", [](Cfg& c) { c.mean = nullptr; });
   pair("sd NULL", [](Cfg& c) { c.sd = nullptr; });
@@ -104,22 +76,14 @@ int main() {
   pair("LDS: 2^29 draws", [](Cfg& c) { c.s.B = 1; c.b.obs_strides[0] = 258; c.draws = 1 << 29; c.ws_bytes = 64; });
   pair("T 1024, 8 draws, run-time S build: fits; workspace too small", [](Cfg& c) { big(c); c.draws = 8; c.ctx.ode_generic = 1; c.ws_bytes = 64; });
   pair("T 1024, 8 draws: fits; workspace too small", [](Cfg& c) { big(c); c.draws = 8; c.ws_bytes = 64; });
-  // ---- the label tensors
-  pair("label columns 3, n_u 2", [](Cfg& c) { c.b.label_width[1] = 2; });
-  pair("n_labels 5", [](Cfg& c) { c.b.n_labels = 5; });
-  pair("label tensor 1 NULL", [](Cfg& c) { c.b.labels[1] = nullptr; });
-  prior("no label tensors", [](Cfg& c) { c.b.n_labels = 0; });
+  ladder_labels();
   // ---- the workspace
   pair("workspace too small", [](Cfg& c) { c.ws_bytes = 64; });
   pair("joint, obs_dev, dev_out NULL; workspace too small", [](Cfg& c) { c.joint = c.obs_dev = c.dev_out = nullptr; c.ws_bytes = 64; });
   prior("obs NULL; workspace too small", [](Cfg& c) { c.b.obs = nullptr; c.ws_bytes = 64; });
   pair("level 1, eight levels; workspace too small", [](Cfg& c) { c.n_levels = 8; c.ws_bytes = 64; });
   // ---- two conditions at once: the earlier rung speaks
-  pair("params NULL + batch NULL", [](Cfg& c) { c.no_params = true; c.no_batch = true; });
-  pair("times NULL + num_samples 1", [](Cfg& c) { c.times = nullptr; c.draws = 1; });
-  pair("num_samples 1 + adaptive", [](Cfg& c) { c.draws = 1; c.s.method = SLODE_DOPRI5; });
-  pair("adaptive + particles 2", [](Cfg& c) { c.s.method = SLODE_BOSH3; c.s.particles = 2; });
-  post("ode_alg + obs NULL", [](Cfg& c) { c.ctx.ode_alg = 2; c.b.obs = nullptr; });
+  ladder_two_at_once(1);
   post("no_fold + mean NULL", [](Cfg& c) { c.ctx.no_fold = 1; c.mean = nullptr; });
   pair("crit NULL + n_levels 0", [](Cfg& c) { c.crit = nullptr; c.n_levels = 0; });
   pair("level 0 + sd_floor -1", [](Cfg& c) { c.levels[0] = 0.0; c.sd_floor = -1.f; });
@@ -140,9 +104,6 @@ int main() {
   levels("levels NULL", [](Cfg& c) { c.no_levels = true; });
   levels("level 0", [](Cfg& c) { c.levels[1] = 0.0; });
   levels("level -0.5", [](Cfg& c) { c.levels[0] = -0.5; });
-  // the memory that stands for every output: never written
-  bool clean = true;
-  for (float v : g_mem) clean = clean && v == 0.f;
-  printf("memory that stands for the outputs | %s\n", clean ? "untouched" : "WRITTEN");
+  memory_untouched();
   return 0;
 }

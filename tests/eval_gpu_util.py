@@ -1,9 +1,13 @@
-"""What the GPU tests of the ten eval-side calls (test_gpu_eval_stats, test_gpu_recon_moments, test_gpu_intervene, test_gpu_forecast,
-test_gpu_cohort, test_gpu_calibration, test_gpu_traj_bounds, test_gpu_label_evidence, test_gpu_refine, test_gpu_pointwise) share: an engine for a seeded case (tests/eval_stats_util.py) with the handle's environment switches
-under control, the case's batch on the device, the model of the model-level tests with its 17-trajectory batch, and the checks every call
-gets: refusal, capture and replay, peak allocation.  A plain module: not a conftest, not imported by the product."""
+"""What the GPU tests of the fifteen eval-side calls (test_gpu_eval_stats, test_gpu_recon_moments, test_gpu_intervene, test_gpu_forecast,
+test_gpu_cohort, test_gpu_calibration, test_gpu_traj_bounds, test_gpu_label_evidence, test_gpu_refine, test_gpu_pointwise, and the
+whole-curve calls' test_gpu_attribution, test_gpu_summary, test_gpu_quantiles, test_gpu_mechanism, test_gpu_band) share: an engine for a
+seeded case (tests/eval_stats_util.py) with the handle's environment switches under control, the case's batch on the device, the model of
+the model-level tests with its 17-trajectory batch, the checks every call gets -- refusal, capture and replay, peak allocation -- and what
+the whole-curve tests compare with: the kernel's own curve of every draw, the model's own curves, bitwise agreement, the count of engine
+calls.  A plain module: not a conftest, not imported by the product."""
 import importlib
 
+import numpy as np
 import pytest
 import torch
 
@@ -155,3 +159,29 @@ def _captured(call, outs):
     g.replay()
     torch.cuda.synchronize(DEV)
     return want
+
+
+# ---- the whole-curve calls (attribution, summary, quantiles, mechanism, band) ---------------------------------------------------------------
+def _same(a, b, equal_nan):
+    """Bitwise agreement of two numpy arrays: dtype, shape, every element; ``equal_nan``: whether a NaN agrees with a NaN."""
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=equal_nan)
+
+
+def _per_draw_curves(eng, flat, c, is_post, obs_d, labels):
+    """[K, Q, B, C, T] fp32: the kernel's own curve of every draw -- recon_moments with num_samples = 1 on that draw's noise row."""
+    eps = c["eps"].to(DEV)
+    return np.stack([_recon_moments(eng, flat, c, is_post, eps=eps[k].contiguous(), obs_d=obs_d, labels=labels, ns=1)[0].cpu().numpy()
+                     for k in range(eps.shape[0])])
+
+
+def _model_curves(m, batch, is_post, eps, heads_axis=0):
+    """[Q, ns, B, C, T] fp64 (``heads_axis`` = 1: [ns, Q, B, C, T]): the model's own decoder on the same draws (recon_samples)."""
+    res = m.recon_samples(is_post=is_post, num_samples=eps.shape[0], eps=eps, **batch)
+    return np.stack([res[n].double().permute(3, 0, 1, 2).cpu().numpy() for n in m.MOMENT_HEADS[bool(m.GAUSS)]], heads_axis)
+
+
+def _count_calls(monkeypatch, eng, name, note=lambda args: 1):
+    """The list that takes ``note(positional arguments)`` of every call of the engine method ``name`` from now on."""
+    calls, real = [], getattr(eng, name)
+    monkeypatch.setattr(eng, name, lambda *a, **k: (calls.append(note(a)), real(*a, **k))[1])
+    return calls

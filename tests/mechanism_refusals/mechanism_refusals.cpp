@@ -26,46 +26,17 @@ static int call(int which, Cfg& c, const Head& a, const char** column) {
   return slode_mechanism_moments(a.h, a.s, a.l, a.p, c.times, c.stage_t, a.b, c.is_post, c.draws, c.slots, c.mean, c.sd, c.ws, c.ws_bytes, nullptr);
 }
 
-static void pair(const char* name, const Edit& edit) {
-  for (int post : {1, 0}) { Cfg c; c.is_post = post; edit(c); run(name, c); }
-}
-static void post(const char* name, const Edit& edit) { one(name, edit); }
-static void prior(const char* name, const Edit& edit) { Cfg c; c.is_post = 0; edit(c); run(name, c); }
-// (the plan takes no handle: its reason is the global text, which a NULL handle reads)
-static void plan(const char* name, const Edit& edit) { Cfg c; c.no_handle = true; edit(c); run(name, c, 1); }
 
 // T = 1024, S = 5, C = 3: the step table and the capture table are 40 KB each and one slot's moment triples 60 KB -- one slot fits, two do not
 static void big(Cfg& c) { c.s.T = 1024; c.b.obs_strides[0] = 3072; }
 
 int main() {
-  // ---- NULL pointers
-  pair("handle NULL", [](Cfg& c) { c.no_handle = true; });
-  pair("shape NULL", [](Cfg& c) { c.no_shape = true; });
-  pair("layout NULL", [](Cfg& c) { c.no_layout = true; });
-  pair("params NULL", [](Cfg& c) { c.no_params = true; });
-  pair("batch NULL", [](Cfg& c) { c.no_batch = true; });
-  pair("times NULL", [](Cfg& c) { c.times = nullptr; });
-  pair("stage_t NULL", [](Cfg& c) { c.stage_t = nullptr; });
-  pair("workspace NULL", [](Cfg& c) { c.ws = nullptr; });
-  pair("bad shape", [](Cfg& c) { c.s.T = 1; });
+  ladder_pointers();
   // ---- the draw count
   pair("num_samples 0", [](Cfg& c) { c.draws = 0; });
   pair("num_samples 2^30", [](Cfg& c) { c.draws = 1 << 30; });
-  // ---- what the fused kernels do not take
-  for (int m : {SLODE_DOPRI5, SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN}) {
-    char name[64];
-    snprintf(name, sizeof(name), "adaptive method %d", m);
-    pair(name, [m](Cfg& c) { c.s.method = m; });
-  }
-  pair("particles 2", [](Cfg& c) { c.s.particles = 2; });
-  pair("fold_on", [](Cfg& c) { c.ctx.fold_on = 1; });
-  pair("ode_pack", [](Cfg& c) { c.ctx.ode_pack = 4; });
-  pair("ode_alg", [](Cfg& c) { c.ctx.ode_alg = 1; });
-  // ---- the observations: the posterior alone reads them
-  post("obs NULL", [](Cfg& c) { c.b.obs = nullptr; });
-  post("padded strides", [](Cfg& c) { c.b.obs_strides[0] += 8; });
-  post("channel-major strides of another T", [](Cfg& c) { c.b.obs_strides[1] = c.s.T + 1; c.b.obs_strides[2] = 1; });
-  post("no_fold", [](Cfg& c) { c.ctx.no_fold = 1; });
+  ladder_not_taken();
+  ladder_post_obs();
   // ---- the call's own rungs
   pair("mean NULL", [](Cfg& c) { c.mean = nullptr; });
   pair("slots 0", [](Cfg& c) { c.slots = 0; });
@@ -75,20 +46,12 @@ int main() {
   pair("LDS: T 1024, two slots", [](Cfg& c) { big(c); c.slots = 0x12; c.ws_bytes = 64; });
   pair("T 1024, one slot, run-time S build: fits; workspace too small",[](Cfg& c) { big(c); c.slots = 0x8; c.ctx.ode_generic = 1; c.ws_bytes = 64; });
   pair("T 1024, one slot: fits; workspace too small", [](Cfg& c) { big(c); c.slots = 0x8; c.ws_bytes = 64; });
-  // ---- the label tensors
-  pair("label columns 3, n_u 2", [](Cfg& c) { c.b.label_width[1] = 2; });
-  pair("n_labels 5", [](Cfg& c) { c.b.n_labels = 5; });
-  pair("label tensor 1 NULL", [](Cfg& c) { c.b.labels[1] = nullptr; });
-  prior("no label tensors", [](Cfg& c) { c.b.n_labels = 0; });
+  ladder_labels();
   // ---- the workspace
   pair("workspace too small", [](Cfg& c) { c.ws_bytes = 64; });
   pair("sd NULL, one slot; workspace too small", [](Cfg& c) { c.sd = nullptr; c.slots = 1; c.ws_bytes = 64; });
   // ---- two conditions at once: the earlier rung speaks
-  pair("params NULL + batch NULL", [](Cfg& c) { c.no_params = true; c.no_batch = true; });
-  pair("times NULL + num_samples 0", [](Cfg& c) { c.times = nullptr; c.draws = 0; });
-  pair("num_samples 0 + adaptive", [](Cfg& c) { c.draws = 0; c.s.method = SLODE_DOPRI5; });
-  pair("adaptive + particles 2", [](Cfg& c) { c.s.method = SLODE_BOSH3; c.s.particles = 2; });
-  post("ode_alg + obs NULL", [](Cfg& c) { c.ctx.ode_alg = 2; c.b.obs = nullptr; });
+  ladder_two_at_once(0);
   post("no_fold + mean NULL", [](Cfg& c) { c.ctx.no_fold = 1; c.mean = nullptr; });
   pair("mean NULL + slots 0", [](Cfg& c) { c.mean = nullptr; c.slots = 0; });
   pair("slots bit 7 + LDS", [](Cfg& c) { c.slots = 0x9f; big(c); });
@@ -102,9 +65,6 @@ int main() {
   plan("slots bit 5", [](Cfg& c) { c.slots = 0x21; });
   plan("LDS: T 1024, five slots", [](Cfg& c) { big(c); });
   plan("LDS: T 1024, two slots", [](Cfg& c) { big(c); c.slots = 0x3; });
-  // the memory that stands for every output: never written
-  bool clean = true;
-  for (float v : g_mem) clean = clean && v == 0.f;
-  printf("memory that stands for the outputs | %s\n", clean ? "untouched" : "WRITTEN");
+  memory_untouched();
   return 0;
 }

@@ -47,6 +47,7 @@ import torch.nn.functional as F
 
 from oracle import slode_oracle as O
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 
 NAMES = ("state", "production", "degradation", "set_point", "net_rate")
@@ -223,10 +224,5 @@ def plan_bytes(T, S, C, L, H, n_u, gauss, n_sel):
     """The hand count of the kernel's LDS tables in bytes, every piece rounded to 16 B: the shared pieces (step table 2 (T - 1) S, the
     H rows of 2 + 2 S floats rounded to four, w1 2 H L, b1 2 H, w2 H S + S, head weights Q C S, biases 2 S, z L, labels max(n_u, 1), h0 H,
     x0 S), the moment table n_sel r4(3 S T), loc | scale, the capture table 2 T S."""
-    def r4(n):
-        return (n + 3) & ~3
-    Q = 1 if gauss else 3
-    row = (2 + 2 * S + 3) & ~3
-    shared = (2 * r4((T - 1) * S) + r4(H * row) + r4(L * 2 * H) + r4(2 * H) + r4(H * S + S) + r4(Q * C * S) + r4(2 * S) + r4(L) + r4(max(n_u, 1))
-              + r4(H) + r4(S))
-    return 4 * (shared + n_sel * r4(3 * S * T) + 2 * r4(L) + r4(2 * T * S))
+    r4 = LU.r4
+    return 4 * (LU.fwd_shared_floats(T, S, C, L, H, n_u, gauss) + n_sel * r4(3 * S * T) + 2 * r4(L) + r4(2 * T * S))

@@ -8,6 +8,7 @@ order statistic is 1-Lipschitz in the sup norm over the draws, so the per-value 
 largest draw value as its scale."""
 import numpy as np
 
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 
 U = 2.0 ** -24
@@ -68,19 +69,12 @@ def oracle_bar(draws64):
     return RU.MEAN_BAR * np.maximum(1.0, np.abs(draws64).max(0))
 
 
-def _r4(n):
-    return (n + 3) & ~3
-
-
 def fixed_floats(spec, T):
     """The floats of the kernel's LDS pieces that do not depend on the plan: the shared forward pieces (step table 2 (T - 1) S, one row of
     2 + 2 S floats rounded up to four per hidden unit, the transposed first layers L x 2 H, their biases 2 H, the init net's output layer
     H S + S, the head weights Q C S, the dynamics biases 2 S, z, the labels, the init net's hidden layer, x0), loc | scale and the level table
     3 x 8; every piece rounded up to 16 bytes."""
-    S, H, Ld, Cn, Q = spec.ode_state_dim, spec.ode_hidden_dim, spec.latent_dim, spec.n_channels, 1 if spec.gauss else 3
-    row = (2 + 2 * S + 3) & ~3
-    return (2 * _r4((T - 1) * S) + _r4(H * row) + _r4(Ld * 2 * H) + _r4(2 * H) + _r4(H * S + S) + _r4(Q * Cn * S) + _r4(2 * S) + _r4(Ld)
-            + _r4(max(spec.n_u, 1)) + _r4(H) + _r4(S) + 2 * _r4(Ld) + _r4(3 * MAX_LEVELS))
+    return LU.spec_shared_floats(spec, T) + 2 * LU.r4(spec.latent_dim) + LU.r4(3 * MAX_LEVELS)
 
 
 def plan(spec, T, K, levels, tile=0):
@@ -90,7 +84,7 @@ def plan(spec, T, K, levels, tile=0):
     QC = (1 if spec.gauss else 3) * spec.n_channels
 
     def nbytes(tl):
-        return 4 * (fixed_floats(spec, T) + _r4((m_lo + m_hi) * QC * tl))
+        return 4 * (fixed_floats(spec, T) + LU.r4((m_lo + m_hi) * QC * tl))
     if tile > 0:
         tl = tile
         if nbytes(tl) > LDS_MAX:

@@ -1,7 +1,8 @@
-// What the seven refusal programs (tests/eval_refusals, forecast_refusals, cohort_refusals, calibration_refusals, evidence_refusals,
-// refine_refusals, pointwise_refusals) share.  Each calls entry points of
-// libslode.so in every refusing configuration on a hand-filled handle -- no slode_create, no HIP call, no device -- and prints one line
-// per case:
+// What the twelve refusal programs share: tests/eval_refusals, forecast_refusals, cohort_refusals, calibration_refusals, evidence_refusals,
+// refine_refusals, pointwise_refusals, and the five of the whole-curve calls -- attribution_refusals, summary_refusals, quantile_refusals,
+// mechanism_refusals, band_refusals -- which also share the ladder of slode_recon_moments as sections (the end of this file).  Each calls
+// entry points of libslode.so in every refusing configuration on a hand-filled handle -- no slode_create, no HIP call, no device -- and
+// prints one line per case:
 //   <case> | [<call> |] <status> | <rng_counter afterwards> | <slode_last_error>
 // A program defines `struct Cfg : BaseCfg` (what its call takes besides), `call` (its one call expression) and its case table in main.
 #pragma once
@@ -95,4 +96,77 @@ static void both(const char* name, const Edit& edit) {
 template <class C = Cfg>
 static void each(const char* name, std::initializer_list<int> calls, const Edit& edit) {
   for (int which : calls) { C c; edit(c); run(name, c, which); }
+}
+
+// ---- the five programs of the whole-curve calls: every line carries the <call> column (post / prior / plan) and a case has one name on
+// both sides.  call 0: the call itself; call 1: its plan, which takes no handle (its reason is the global text, which a NULL handle reads).
+template <class C = Cfg>
+static void pair(const char* name, const Edit& edit) {
+  for (int post : {1, 0}) { C c; c.is_post = post; edit(c); run(name, c); }
+}
+template <class C = Cfg>
+static void post(const char* name, const Edit& edit) { one(name, edit); }
+template <class C = Cfg>
+static void prior(const char* name, const Edit& edit) { C c; c.is_post = 0; edit(c); run(name, c); }
+template <class C = Cfg>
+static void plan(const char* name, const Edit& edit) { C c; c.no_handle = true; edit(c); run(name, c, 1); }
+
+// The ladder of slode_recon_moments without its LDS rung, in sections: a program calls each where its lines stand, its own rungs between them.
+template <class C = Cfg>
+static void ladder_pointers() {
+  pair("handle NULL", [](C& c) { c.no_handle = true; });
+  pair("shape NULL", [](C& c) { c.no_shape = true; });
+  pair("layout NULL", [](C& c) { c.no_layout = true; });
+  pair("params NULL", [](C& c) { c.no_params = true; });
+  pair("batch NULL", [](C& c) { c.no_batch = true; });
+  pair("times NULL", [](C& c) { c.times = nullptr; });
+  pair("stage_t NULL", [](C& c) { c.stage_t = nullptr; });
+  pair("workspace NULL", [](C& c) { c.ws = nullptr; });
+  pair("bad shape", [](C& c) { c.s.T = 1; });
+}
+// what the fused kernels do not take
+template <class C = Cfg>
+static void ladder_not_taken() {
+  for (int m : {SLODE_DOPRI5, SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN}) {
+    char name[64];
+    snprintf(name, sizeof(name), "adaptive method %d", m);
+    pair(name, [m](C& c) { c.s.method = m; });
+  }
+  pair("particles 2", [](C& c) { c.s.particles = 2; });
+  pair("fold_on", [](C& c) { c.ctx.fold_on = 1; });
+  pair("ode_pack", [](C& c) { c.ctx.ode_pack = 4; });
+  pair("ode_alg", [](C& c) { c.ctx.ode_alg = 1; });
+}
+// the observations: the posterior reads them
+template <class C = Cfg>
+static void ladder_post_obs() {
+  post("obs NULL", [](C& c) { c.b.obs = nullptr; });
+  post("padded strides", [](C& c) { c.b.obs_strides[0] += 8; });
+  post("channel-major strides of another T", [](C& c) { c.b.obs_strides[1] = c.s.T + 1; c.b.obs_strides[2] = 1; });
+  post("no_fold", [](C& c) { c.ctx.no_fold = 1; });
+}
+template <class C = Cfg>
+static void ladder_labels() {
+  pair("label columns 3, n_u 2", [](C& c) { c.b.label_width[1] = 2; });
+  pair("n_labels 5", [](C& c) { c.b.n_labels = 5; });
+  pair("label tensor 1 NULL", [](C& c) { c.b.labels[1] = nullptr; });
+  prior("no label tensors", [](C& c) { c.b.n_labels = 0; });
+}
+// two conditions at once, up to the observations: the earlier rung speaks.  low: the largest draw count the call refuses as too small
+template <class C = Cfg>
+static void ladder_two_at_once(int low) {
+  char name[64];
+  pair("params NULL + batch NULL", [](C& c) { c.no_params = true; c.no_batch = true; });
+  snprintf(name, sizeof(name), "times NULL + num_samples %d", low);
+  pair(name, [low](C& c) { c.times = nullptr; c.draws = low; });
+  snprintf(name, sizeof(name), "num_samples %d + adaptive", low);
+  pair(name, [low](C& c) { c.draws = low; c.s.method = SLODE_DOPRI5; });
+  pair("adaptive + particles 2", [](C& c) { c.s.method = SLODE_BOSH3; c.s.particles = 2; });
+  post("ode_alg + obs NULL", [](C& c) { c.ctx.ode_alg = 2; c.b.obs = nullptr; });
+}
+// the last line: the memory that stands for every output was never written
+static void memory_untouched() {
+  bool clean = true;
+  for (float v : g_mem) clean = clean && v == 0.f;
+  printf("memory that stands for the outputs | %s\n", clean ? "untouched" : "WRITTEN");
 }

@@ -13,7 +13,9 @@ import pytest
 import torch
 
 from tests import attribution_util as AU
+from tests import draws_ladder_util as DL
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,23 +61,6 @@ def test_engine_signature():
     assert "eps_shape" in inspect.signature(Engine.make_batch).parameters
 
 
-def _host_engine(case):
-    """An Engine that only knows its shape: what the plans need."""
-    from structured_latent_odes_amd import _lib as L, engine as E
-    fam, kw, _, T = EU.CASES[case]
-
-    class _E(E.Engine):
-        def __init__(self, spec, T):
-            self.spec, self.T, self._shapes = spec, T, {}
-            self.lib = L.load()
-
-    return _E({"cvs": E.cvs_spec, "challenge": E.challenge_spec, "proc": E.proc_spec}[fam](solver="rk4", **kw), T)
-
-
-def _r4(n):
-    return (n + 3) & ~3
-
-
 @pytest.mark.parametrize("case", list(EU.CASES))
 def test_plan_against_a_hand_count_of_the_tables(case):
     """slode_attribution_plan for the six model shapes: the shared forward pieces (step table 2 (T - 1) S, one row of 2 + 2 S floats rounded
@@ -83,14 +68,12 @@ def test_plan_against_a_hand_count_of_the_tables(case):
     weights Q C S, the dynamics biases 2 S, z, the labels, the init net's hidden layer, x0), then base moments 3 Q C T, base values Q C T, arm
     sums A Q C T and loc | scale; every piece rounded up to 16 bytes.  One more arm costs exactly Q C T floats."""
     from structured_latent_odes_amd import _lib as L
-    eng = _host_engine(case)
+    eng = LU.host_engine(case)
     sp, T = eng.spec, eng.T
-    S, H, Ld, Cn, Q = sp.ode_state_dim, sp.ode_hidden_dim, sp.latent_dim, sp.n_channels, 1 if sp.gauss else 3
-    row = (2 + 2 * S + 3) & ~3
-    shared = (2 * _r4((T - 1) * S) + _r4(H * row) + _r4(Ld * 2 * H) + _r4(2 * H) + _r4(H * S + S) + _r4(Q * Cn * S) + _r4(2 * S) + _r4(Ld)
-              + _r4(max(sp.n_u, 1)) + _r4(H) + _r4(S))
+    Ld, Cn, Q = sp.latent_dim, sp.n_channels, 1 if sp.gauss else 3
+    shared = LU.spec_shared_floats(sp, T)
     for A in (1, 2, 6, 16):
-        want = 4 * (shared + _r4(3 * Q * Cn * T) + _r4(Q * Cn * T) + _r4(A * Q * Cn * T) + 2 * _r4(Ld))
+        want = 4 * (shared + LU.r4(3 * Q * Cn * T) + LU.r4(Q * Cn * T) + LU.r4(A * Q * Cn * T) + 2 * LU.r4(Ld))
         if want <= 160 * 1024:
             assert eng.attribution_plan(8, A) == want, (case, A)
         else:
@@ -105,18 +88,8 @@ def test_plan_against_a_hand_count_of_the_tables(case):
 # case -> call column, status and the words its message must carry, written from include/slode.h in rung order
 _N = "slode_latent_attribution"
 _BOTH, _POST, _PRIOR, _PLAN = ("post", "prior"), ("post",), ("prior",), ("plan",)
-LADDER = [
-    ("handle NULL", _BOTH, -1, ["handle is NULL"]), ("shape NULL", _BOTH, -1, ["shape is NULL"]), ("layout NULL", _BOTH, -1, ["layout is NULL"]),
-    ("params NULL", _BOTH, -1, ["params is NULL"]), ("batch NULL", _BOTH, -1, [_N, "batch", "is NULL"]), ("times NULL", _BOTH, -1, [_N, "times", "is NULL"]),
-    ("stage_t NULL", _BOTH, -1, [_N, "stage_t", "is NULL"]), ("workspace NULL", _BOTH, -1, [_N, "workspace", "is NULL"]),
-    ("bad shape", _BOTH, -1, ["T out of range"]), ("num_samples 0", _BOTH, -1, [_N, "num_samples = 0 < 1"]),
-    ("num_samples 2^30", _BOTH, -1, [_N, "B x num_samples", "2^30 - 1"]),
-    ("adaptive method 3", _BOTH, -1, [_N, "adaptive solver dopri5"]), ("adaptive method 4", _BOTH, -1, [_N, "adaptive solver bosh3"]),
-    ("adaptive method 5", _BOTH, -1, [_N, "adaptive solver fehlberg2"]), ("adaptive method 6", _BOTH, -1, [_N, "adaptive solver adaptive_heun"]),
-    ("particles 2", _BOTH, -1, [_N, "particles = 2"]), ("fold_on", _BOTH, -1, [_N, "measured arms"]), ("ode_pack", _BOTH, -1, [_N, "measured arms"]),
-    ("ode_alg", _BOTH, -1, [_N, "measured arms"]), ("obs NULL", _POST, -1, [_N, "batch->obs is NULL"]),
-    ("padded strides", _POST, -1, [_N, "observation strides (266, 1, 3)"]),
-    ("channel-major strides of another T", _POST, -1, [_N, "observation strides (258, 87, 1)"]), ("no_fold", _POST, -1, [_N, "SLODE_NO_FOLD"]),
+_HEAD, _LABELS, _TWO = DL.shared_rungs(_N, "batch / times / stage_t / workspace", "reduce the attribution samples instead")
+LADDER = _HEAD + [
     ("n_arms 0", _BOTH, -1, [_N, "n_arms = 0", "[1, 16]"]), ("n_arms -3", _BOTH, -1, [_N, "n_arms = -3"]), ("n_arms 17", _BOTH, -1, [_N, "n_arms = 17"]),
     ("arm_masks NULL", _BOTH, -1, [_N, "arm_masks", "is NULL"]), ("msd NULL", _BOTH, -1, [_N, "msd", "is NULL"]),
     ("mask bit 3, n_groups 2", _BOTH, -1, [_N, "arm_masks[2] = 0x8", "beyond n_groups = 2"]),
@@ -125,14 +98,10 @@ LADDER = [
     ("no groups: the rest block is bit 0, bits beyond it", _BOTH, -1, [_N, "beyond n_groups = 0"]),
     ("LDS: T 1024", _BOTH, -1, [_N, "LDS tables", "T = 1024", "n_arms = 6", "163840", "fewer arms per call"]),
     ("LDS: T 500, n_arms 16", _BOTH, -1, [_N, "LDS tables", "T = 500", "n_arms = 16 (384000 B"]),
-    ("label columns 3, n_u 2", _BOTH, -1, ["label tensors have 3 columns"]), ("n_labels 5", _BOTH, -1, ["n_labels out of range"]),
-    ("label tensor 1 NULL", _BOTH, -1, ["label tensor 1 is NULL"]), ("no label tensors", _PRIOR, -1, [_N, "the prior needs the label tensors"]),
-    ("workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
+] + _LABELS + [
     ("mean and sd NULL, mask 0 among the arms; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
-    # two conditions at once: the earlier rung speaks
-    ("params NULL + batch NULL", _BOTH, -1, ["params is NULL"]), ("times NULL + num_samples 0", _BOTH, -1, ["is NULL"]),
-    ("num_samples 0 + adaptive", _BOTH, -1, ["num_samples = 0"]), ("adaptive + particles 2", _BOTH, -1, ["adaptive solver bosh3"]),
-    ("ode_alg + obs NULL", _POST, -1, ["measured arms"]), ("no_fold + n_arms 0", _POST, -1, ["observation strides"]),
+] + _TWO + [                                                                          # two conditions at once: the earlier rung speaks
+    ("no_fold + n_arms 0", _POST, -1, ["observation strides"]),
     ("n_arms 17 + arm_masks NULL", _BOTH, -1, ["n_arms = 17"]), ("msd NULL + mask bit 3", _BOTH, -1, ["arm_masks / msd is NULL"]),
     ("mask bit 3 + LDS", _BOTH, -1, ["arm_masks[1] = 0x9"]), ("LDS + label columns 3", _BOTH, -1, ["LDS tables"]),
     ("label columns 3 + workspace too small", _BOTH, -1, ["label tensors have 3 columns"]),
@@ -151,32 +120,7 @@ def test_attribution_refusals_on_a_hand_filled_handle(tmp_path):
     tests/golden/attribution_refusals.txt; the rungs shared with slode_recon_moments carry the texts tests/golden/eval_refusals.txt records
     for it on that side, the call's name, its list of required pointers and its advice apart; the call's LDS figure is the plan's; and the
     memory that stands for the outputs untouched."""
-    from tests.refusals_util import refusal_lines
-    lines = refusal_lines("attribution_refusals", tmp_path)
-    assert lines[-1] == "memory that stands for the outputs | untouched"
-    want = open(os.path.join(ROOT, "tests", "golden", "attribution_refusals.txt")).read().splitlines()
-    for i, (g, w) in enumerate(zip(lines, want)):
-        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
-    expect = [(name, col, status, words) for name, cols, status, words in LADDER for col in cols]
-    assert len(lines) == len(want) == len(expect) + 1
-    recon = {}
-    for line in open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines():
-        parts = line.split(" | ", 4)
-        if len(parts) == 5 and parts[1] == "recon_moments":
-            recon[parts[0]] = parts[4]
-    shared, figures = 0, {}
-    for line, (name, col, status, words) in zip(lines[:-1], expect):
-        got_name, got_col, got_status, counter, msg = line.split(" | ", 4)
-        assert (got_name, got_col) == (name, col) and int(got_status) == status and counter == "7", line      # refused, and nothing drawn
-        for w in words:
-            assert w in msg, (name, w, msg)
-        if name.startswith("LDS: "):
-            figures.setdefault(name, set()).add(re.search(r"\((\d+) B", msg).group(1))
-        key = name.replace("num_samples", "draws")
-        if col != "plan" and key in recon and "LDS" not in name and "workspace too small" not in name:
-            shared += 1
-            theirs = recon[key].replace("slode_recon_moments", _N).replace("batch / mean / ", "batch / ").replace("reduce recon_samples instead", "reduce the attribution samples instead")
-            assert msg == theirs, (name, msg, recon[key])
+    _, shared, figures = DL.check_ladder("attribution_refusals", tmp_path, LADDER, _N, "reduce the attribution samples instead")
     assert all(len(v) == 1 for v in figures.values()) and len(figures) == 2                # the call names the plan's figure
     assert shared >= 50
 
@@ -364,6 +308,31 @@ def test_blocks_and_arm_lists():
     with pytest.raises(ValueError, match="num_samples"):
         m.latent_attribution(torch.zeros(2, 3, 10), True, 0, iext=torch.zeros(2, 1), rtpr=torch.zeros(2, 1))
     assert m._b.engine.calls == [] and m._b.engine.batches == [] and m._b.engine.draws == []
+
+
+def test_fewest_calls_that_fit():
+    """The split of latent_attribution's arms and mechanism_moments' slots on its own: for 1 to 6 items, a cap of 1 to 6 per call and a plan
+    that takes up to 1 to 6 (one item is never planned: the call itself refuses it), the slices cover every item once and in order, none
+    is larger than the cap or than what the plan takes, no smaller number of calls would do, and the sizes differ by at most one."""
+    from structured_latent_odes_amd import _lib as L
+    from structured_latent_odes_amd.models._mechanistic import MechanisticBase
+
+    for n in range(1, 7):
+        for cap in range(1, 7):
+            for takes in range(1, 7):
+                asked = []
+
+                def plan(k):
+                    asked.append(k)
+                    if k > takes:
+                        raise L.SlodeError("libslode call failed (-1)")
+                slices = MechanisticBase._fewest_calls(n, cap, plan)
+                most = min(n, cap, takes)
+                assert [i for lo, hi in slices for i in range(lo, hi)] == list(range(n)), (n, cap, takes, slices)
+                sizes = [hi - lo for lo, hi in slices]
+                assert min(sizes) >= 1 and max(sizes) <= most and max(sizes) - min(sizes) <= 1, (n, cap, takes, slices)
+                assert len(slices) == -(-n // most), (n, cap, takes, slices)                # fewer calls would need a larger one
+                assert 1 not in asked and all(k <= min(n, cap) for k in asked)
 
 
 @pytest.mark.parametrize("gauss", [False, True])

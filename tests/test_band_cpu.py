@@ -14,7 +14,9 @@ import pytest
 import torch
 
 from tests import band_util as BU
+from tests import draws_ladder_util as DL
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 from tests import summary_util as SU
 
@@ -77,19 +79,6 @@ def test_engine_and_model_signatures():
 
 
 # ---- the plan -----------------------------------------------------------------------------------------------------------------------------
-def _host_engine(case, T=None):
-    """An Engine that only knows its shape: what the plans need."""
-    from structured_latent_odes_amd import _lib as L, engine as E
-    fam, kw, _, T0 = EU.CASES[case]
-
-    class _E(E.Engine):
-        def __init__(self, spec, T):
-            self.spec, self.T, self._shapes = spec, T, {}
-            self.lib = L.load()
-
-    return _E({"cvs": E.cvs_spec, "challenge": E.challenge_spec, "proc": E.proc_spec}[fam](solver="rk4", **kw), T or T0)
-
-
 def _hand_count(eng, K):
     sp = eng.spec
     return BU.plan_bytes(eng.T, sp.ode_state_dim, sp.n_channels, sp.latent_dim, sp.ode_hidden_dim, sp.n_u, sp.gauss, K)
@@ -99,7 +88,7 @@ def _hand_count(eng, K):
 def test_plan_against_a_hand_count_of_the_tables(case):
     """Every case: the plan is the hand count (BU.plan_bytes); one more draw costs 4 Q C bytes up to the rounding of the table to 16 B; B
     does not enter."""
-    eng = _host_engine(case)
+    eng = LU.host_engine(case)
     QC = (1 if eng.spec.gauss else 3) * eng.spec.n_channels
     got = {K: eng.joint_band_plan(8, K) for K in (2, 4, 7, 8, 33, 200)}
     for K, b in got.items():
@@ -113,7 +102,7 @@ def test_smallest_draw_count_the_plan_refuses(T):
     """cvs (S = 5, C = 3, three heads) at T = 200 and T = 1024: the smallest K whose hand count exceeds the budget is refused by name with
     that figure, one fewer is taken, and a refusal still writes the bytes."""
     from structured_latent_odes_amd import _lib as L
-    eng = _host_engine("cvs_ald", T=T)
+    eng = LU.host_engine("cvs_ald", T=T)
     K = 2
     while _hand_count(eng, K) <= BUDGET:
         K += 1
@@ -135,7 +124,7 @@ def test_rank_rule_and_z_with_hand_values():
     """r = min(K, max(1, ceil(level K - 1e-9))) and z = Phi^-1((1 + level) / 2): the library's, the model layer's and BU's restatement agree
     at K in {2, 7, 20, 200} x levels {0.5, 0.9, 0.95, 1.0}; hand values; the fp32 half-widths the kernel compares with are the same bits."""
     from structured_latent_odes_amd.models._mechanistic import MechanisticBase
-    eng = _host_engine("cvs_ald")
+    eng = LU.host_engine("cvs_ald")
     levels = (0.5, 0.9, 0.95, 1.0)
     hand = {2: [1, 2, 2, 2], 7: [4, 7, 7, 7], 20: [10, 18, 19, 20], 200: [100, 180, 190, 200]}
     z_hand = [0.6744897501960817, 1.6448536269514722, 1.959963984540054, math.inf]
@@ -176,18 +165,9 @@ def test_band_refusals_on_a_hand_filled_handle(tmp_path):
     workspace) with the generator's counter untouched; the reasons the issue names carry their words; the rungs shared with
     slode_recon_moments carry its texts, the name and the pointer list apart; the LDS figures are the hand count's; the memory that stands
     for the outputs is untouched."""
-    from tests.refusals_util import refusal_lines
-    lines = refusal_lines("band_refusals", tmp_path)
-    assert lines[-1] == "memory that stands for the outputs | untouched"
-    want = open(os.path.join(ROOT, "tests", "golden", "band_refusals.txt")).read().splitlines()
-    for i, (g, w) in enumerate(zip(lines, want)):
-        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
-    assert len(lines) == len(want) >= 120
-    recon = {}
-    for line in open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines():
-        parts = line.split(" | ", 4)
-        if len(parts) == 5 and parts[1] == "recon_moments":
-            recon[parts[0]] = parts[4]
+    lines = DL.golden_lines("band_refusals", tmp_path)
+    assert len(lines) >= 120
+    recon = DL.recon_texts(_N)
     seen, shared = set(), 0
     for line in lines[:-1]:
         name, col, status, counter, msg = line.split(" | ", 4)
@@ -202,9 +182,9 @@ def test_band_refusals_on_a_hand_filled_handle(tmp_path):
         if key in recon and "LDS" not in name and "workspace too small" not in name and "NULL" not in name.replace("handle NULL", "") \
                 and name not in ("num_samples 0", "num_samples 1") and not (col == "prior" and "strides" in name):
             shared += 1
-            assert msg == recon[key].replace("slode_recon_moments", _N).replace("batch / mean / ", "batch / "), (name, msg, recon[key])
+            assert msg == recon[key], (name, msg, recon[key])
     assert set(NAMED) <= seen
-    big, small = _host_engine("cvs_ald", T=1024), _host_engine("cvs_ald", T=86)
+    big, small = LU.host_engine("cvs_ald", T=1024), LU.host_engine("cvs_ald", T=86)
     sp = small.spec
     assert _hand_count(big, 400) == 169952
     assert BU.plan_bytes(86, 5, 3, 8, 25, 2, False, 4100) == 164352                       # the shape of tests/refusals_common.h

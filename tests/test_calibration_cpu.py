@@ -14,6 +14,7 @@ import torch
 
 from tests import calibration_util as KU
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUDGET = 160 * 1024
@@ -58,16 +59,15 @@ def _pieces(s):
     scale table C T for the Gauss likelihood, loc / scale): each rounded up to 4 floats."""
     gauss = s.likelihood == 1
     Q = 1 if gauss else 3
-    row = (2 + 2 * s.S + 3) & ~3                                                          # w_t | u_j | W_g[S] | W_d[S], 16-byte rows
-    fwd = [(s.T - 1) * s.S, (s.T - 1) * s.S, s.H * row, s.L * 2 * s.H, 2 * s.H, s.H * s.S + s.S, Q * s.C * s.S, 2 * s.S, s.L, max(s.n_u, 1), s.H, s.S]
+    fwd = LU.fwd_shared_pieces(s.T, s.S, s.C, s.L, s.H, s.n_u, s.likelihood == 1)
     CT = s.C * s.T
-    return [(n + 3) & ~3 for n in fwd + [8 * CT, 5 * CT, CT, CT if gauss else 0, s.L, s.L]]
+    return fwd + [LU.r4(n) for n in (8 * CT, 5 * CT, CT, CT if gauss else 0, s.L, s.L)]
 
 
 def _hand_scratch(s, M, G, R):
     """(n_partials, bytes): cs [G + 1] ints, the chunk table [n_partials][4] ints, the flags [n_partials] ints, each padded to 16 B, then
     n_partials partials of 4 C T doubles + 5 C T ints, padded to 16 B."""
-    pad = lambda n: (n + 3) & ~3
+    pad = LU.r4
     NP = -(-M // R) + G
     return NP, 4 * (pad(G + 1) + 4 * NP + pad(NP)) + NP * ((52 * s.C * s.T + 15) & ~15)
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import cohort_util as CU
+from tests import lds_util as LU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUDGET = 160 * 1024
@@ -53,16 +54,15 @@ def _pieces(s):
     """Floats of every LDS piece of cohort_moments_kernel, from the issue's map (FwdLds + 6 Q C T + C T + loc / scale): each rounded up
     to 4 floats."""
     Q = 1 if s.likelihood == 1 else 3
-    row = (2 + 2 * s.S + 3) & ~3                                                          # w_t | u_j | W_g[S] | W_d[S], 16-byte rows
-    fwd = [(s.T - 1) * s.S, (s.T - 1) * s.S, s.H * row, s.L * 2 * s.H, 2 * s.H, s.H * s.S + s.S, Q * s.C * s.S, 2 * s.S, s.L, max(s.n_u, 1), s.H, s.S]
-    return [(n + 3) & ~3 for n in fwd + [6 * Q * s.C * s.T, s.C * s.T, s.L, s.L]]
+    fwd = LU.fwd_shared_pieces(s.T, s.S, s.C, s.L, s.H, s.n_u, s.likelihood == 1)
+    return fwd + [LU.r4(n) for n in (6 * Q * s.C * s.T, s.C * s.T, s.L, s.L)]
 
 
 def _hand_scratch(s, M, G, R):
     """(n_partials, bytes): cs [G + 1] ints, the chunk table [n_partials][4] ints, the flags [n_partials] ints, each padded to 16 B, then
     n_partials partials of (5 Q C + C) T floats."""
     Q = 1 if s.likelihood == 1 else 3
-    pad = lambda n: (n + 3) & ~3
+    pad = LU.r4
     NP = -(-M // R) + G
     return NP, 4 * (pad(G + 1) + 4 * NP + pad(NP) + NP * pad((5 * Q * s.C + s.C) * s.T))
 

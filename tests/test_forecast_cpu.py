@@ -13,6 +13,7 @@ import torch
 
 from tests import eval_stats_util as EU
 from tests import forecast_util as FU
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,11 +53,9 @@ def _shape(proc=False, **kw):
 def _pieces(s, ns, states, W):
     """Floats of every LDS piece of the kernel for a window of W steps, counted from the issue's map: each rounded up to 4 floats."""
     Q = 1 if s.likelihood == 1 else 3
-    row = (2 + 2 * s.S + 3) & ~3                                                          # w_t | u_j | W_g[S] | W_d[S], 16-byte rows
-    fixed = [s.H * row, s.L * 2 * s.H, 2 * s.H, s.H * s.S + s.S, Q * s.C * s.S, 2 * s.S, s.L, max(s.n_u, 1), s.H, s.S,   # staged weights
-             s.L, s.L, ns * s.S]                                                          # loc | scale, carry[ns][S]
+    staged = LU.fwd_shared_pieces(s.T, s.S, s.C, s.L, s.H, s.n_u, s.likelihood == 1)[2:]    # (the step table is the window's: below)
     window = [W * s.S, W * s.S, 3 * Q * s.C * (W + 1)] + ([3 * s.S * (W + 1)] if states else [])
-    return [(n + 3) & ~3 for n in fixed + window]
+    return staged + [LU.r4(n) for n in [s.L, s.L, ns * s.S] + window]              # loc | scale, carry[ns][S], the window's tables
 
 
 def _hand_bytes(s, ns, states, W):

@@ -11,8 +11,8 @@ import torch
 from tests import attribution_util as AU
 from tests import eval_stats_util as EU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
-                                 _recon_moments, _refused)
+from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _padded,
+                                 _peak, _recon_moments, _refused)
 
 pytestmark = pytest.mark.gpu
 
@@ -292,9 +292,7 @@ def test_composed_route_where_the_engine_refuses(why, monkeypatch):
     dense = dict(batch)
     if why == "strided":
         batch["observations"] = _padded(batch["observations"])
-    calls = []
-    real = eng.latent_attribution
-    monkeypatch.setattr(eng, "latent_attribution", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "latent_attribution")
     eng.rng_seed(11)
     eng.rng_set_counter(2)
     drawn = m.latent_attribution(is_post=True, num_samples=ns, **batch)

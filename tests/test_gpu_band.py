@@ -24,8 +24,8 @@ from tests import eval_stats_util as EU
 from tests import mechanism_util as MU
 from tests import recon_moments_util as RU
 from tests import summary_util as SU
-from tests.eval_gpu_util import (ADAPTIVE, DEV, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
-                                 _recon_moments, _refused, _set_env)
+from tests.eval_gpu_util import (ADAPTIVE, DEV, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _model_curves, _padded, _peak,
+                                 _per_draw_curves, _recon_moments, _refused, _same as _same_arrays, _set_env)
 
 pytestmark = pytest.mark.gpu
 FILL = BU.FILL
@@ -55,15 +55,7 @@ def _band(eng, flat, c, is_post, levels=LEVELS, floor=0.0, eps="case", ns=None, 
     return dict(mean=mean, sd=sd, crit=crit, joint=joint, obs_dev=odev[..., 0], points=odev[..., 1], dev=dev)
 
 
-def _same(a, b):
-    return a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
-
-
-def _own_curves(eng, flat, c, is_post, obs_d, labels):
-    """[K, Q, B, C, T] fp32: the kernel's own curve of every draw -- recon_moments with num_samples = 1 on that draw's noise row."""
-    eps = c["eps"].to(DEV)
-    return np.stack([_recon_moments(eng, flat, c, is_post, eps=eps[k].contiguous(), obs_d=obs_d, labels=labels, ns=1)[0].cpu().numpy()
-                     for k in range(eps.shape[0])])
+_same = functools.partial(_same_arrays, equal_nan=True)
 
 
 def _check_exact(r, curves, y, levels, floor, tag):
@@ -89,7 +81,7 @@ def _per_draw(case, is_post, ns=7):
     eng = _engine(c)
     flat = eng.pack(c["p"])
     obs_d, labels = _device_batch(c)
-    return c, eng, flat, _own_curves(eng, flat, c, is_post, obs_d, labels), _band(eng, flat, c, is_post, obs_d=obs_d, labels=labels)
+    return c, eng, flat, _per_draw_curves(eng, flat, c, is_post, obs_d, labels), _band(eng, flat, c, is_post, obs_d=obs_d, labels=labels)
 
 
 @functools.lru_cache(maxsize=None)
@@ -130,7 +122,7 @@ def test_exact_at_33_draws():
     flat = eng.pack(c["p"])
     obs_d, labels = _device_batch(c)
     for is_post in (True, False):
-        _check_exact(_band(eng, flat, c, is_post, obs_d=obs_d, labels=labels), _own_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(),
+        _check_exact(_band(eng, flat, c, is_post, obs_d=obs_d, labels=labels), _per_draw_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(),
                      LEVELS, 0.0, ("K = 33", is_post))
 
 
@@ -219,7 +211,7 @@ def test_sd_floor():
         want = (sds > floor).sum(-1)
         assert np.array_equal(r["points"], want.astype(np.float32)) and set(np.unique(want)) == {0, c["T"]}
         assert np.all(want[:, :7] == c["T"]) and np.all(want[:, 7:] == 0)
-        curves = _own_curves(eng, flat, c, is_post, obs_d, labels)
+        curves = _per_draw_curves(eng, flat, c, is_post, obs_d, labels)
         _check_exact(r, curves, c["obs"].numpy(), LEVELS, floor, ("floor", is_post))
         _check_oracle(r, v, y, LEVELS, floor, "floor %s" % is_post)
         assert np.all(r["dev"][:, 7:] == 0.0) and np.all(r["crit"][:, 7:] == 0.0) and np.all(r["obs_dev"][:, 7:] == 0.0) and np.all(r["joint"][:, 7:] == 1.0)
@@ -308,7 +300,7 @@ def test_grid_lengths(fam, T, monkeypatch):
     obs_d, labels = _device_batch(c)
     for is_post in (True, False):
         r = _band(eng, flat, c, is_post, obs_d=obs_d, labels=labels)
-        _check_exact(r, _own_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(), LEVELS, 0.0, (fam, T, is_post))
+        _check_exact(r, _per_draw_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(), LEVELS, 0.0, (fam, T, is_post))
         mean, sd = _recon_moments(eng, flat, c, is_post, obs_d=obs_d, labels=labels)
         assert _same(r["mean"], mean.cpu().numpy()) and _same(r["sd"], sd.cpu().numpy()) and np.all(r["points"] <= T)
 
@@ -326,7 +318,7 @@ def test_batch_and_draw_count_edges(case, B, ns, env, monkeypatch):
     obs_d, labels = _device_batch(c)
     for is_post in (True, False):
         r = _band(eng, flat, c, is_post, obs_d=obs_d, labels=labels)
-        _check_exact(r, _own_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(), LEVELS, 0.0, (case, B, ns, is_post))
+        _check_exact(r, _per_draw_curves(eng, flat, c, is_post, obs_d, labels), c["obs"].numpy(), LEVELS, 0.0, (case, B, ns, is_post))
         if ns == 2:
             assert np.abs(r["dev"] - 1.0).max() <= 1e-3
 
@@ -436,12 +428,6 @@ def test_launches_and_graph_capture():
 
 
 # ---- 8. the model layer -------------------------------------------------------------------------------------------------------------------------
-def _model_curves(m, batch, is_post, eps):
-    """[Q, ns, B, C, T] fp64: the model's own decoder on the same draws (recon_samples)."""
-    res = m.recon_samples(is_post=is_post, num_samples=eps.shape[0], eps=eps, **batch)
-    return np.stack([res[n].double().permute(3, 0, 1, 2).cpu().numpy() for n in m.MOMENT_HEADS[bool(m.GAUSS)]])
-
-
 def _as_engine_outputs(res, names, with_dev=True):
     """The model's dict in the layout of ``_band``."""
     g = lambda k: np.stack([res[n][k].cpu().numpy() for n in names])
@@ -517,9 +503,7 @@ def test_composed_route_where_the_engine_refuses(why, monkeypatch):
     dense = dict(batch)
     if why == "strided":
         batch["observations"] = _padded(batch["observations"])
-    calls = []
-    real = eng.joint_band
-    monkeypatch.setattr(eng, "joint_band", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "joint_band")
     eng.rng_seed(11)
     eng.rng_set_counter(2)
     eps = eng.rng_normal(2, ns * B).view(ns, B, -1)

@@ -17,8 +17,8 @@ import torch
 from tests import eval_stats_util as EU
 from tests import mechanism_util as MU
 from tests import recon_moments_util as RU
-from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
-                                 _recon_moments, _refused, _set_env)
+from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
+                                 _recon_moments, _refused, _same as _same_arrays, _set_env)
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it: every element must be written
@@ -50,8 +50,7 @@ def _mech(eng, flat, c, is_post, slots=MU.ALL, eps="case", ns=None, sd=True, obs
     return outs[0].cpu().numpy(), (outs[1].cpu().numpy() if sd else None)
 
 
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+_same = functools.partial(_same_arrays, equal_nan=True)
 
 
 def _take(arr, slots):
@@ -223,9 +222,7 @@ def test_noise_grid_and_slot_independence(case, monkeypatch):
 def test_forced_split_in_the_model_call_is_bitwise_the_single_call(monkeypatch):
     m, batch = _model("cvs")
     eng = m._bind().engine
-    calls = []
-    real = eng.mechanism_moments
-    monkeypatch.setattr(eng, "mechanism_moments", lambda *a, **k: (calls.append(a[5]), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "mechanism_moments", lambda a: a[5])
     for is_post in (True, False):
         eng.rng_seed(5)
         eng.rng_set_counter(2)
@@ -366,9 +363,7 @@ def _composed_run(why):
         dense = dict(batch)
         if why == "strided":
             batch["observations"] = _padded(batch["observations"])
-        calls = []
-        real = eng.mechanism_moments
-        mp.setattr(eng, "mechanism_moments", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+        calls = _count_calls(mp, eng, "mechanism_moments")
         eng.rng_seed(11)
         eng.rng_set_counter(2)
         eps = eng.rng_normal(2, ns * B).view(ns, B, -1)

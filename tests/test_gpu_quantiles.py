@@ -15,8 +15,8 @@ from tests import eval_stats_util as EU
 from tests import quantile_util as QU
 from tests import recon_moments_util as RU
 from tests import summary_util as SU
-from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
-                                 _recon_moments, _refused)
+from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model,
+                                 _model_curves, _padded, _peak, _per_draw_curves, _recon_moments, _refused, _same as _same_arrays)
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it: every element must be written
@@ -38,8 +38,7 @@ def _quantiles(eng, flat, c, is_post, levels, eps="case", ns=None, tile=0, obs_d
     return res
 
 
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+_same = functools.partial(_same_arrays, equal_nan=False)
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,9 +49,7 @@ def _per_draw(case, is_post):
     eng = _engine(c)
     flat = eng.pack(c["p"])
     obs_d, labels = _device_batch(c)
-    eps = c["eps"].to(DEV)
-    curves = [_recon_moments(eng, flat, c, is_post, eps=eps[k].contiguous(), obs_d=obs_d, labels=labels, ns=1)[0].cpu().numpy() for k in range(7)]
-    return c, eng, flat, np.stack(curves)
+    return c, eng, flat, _per_draw_curves(eng, flat, c, is_post, obs_d, labels)
 
 
 PER_DRAW = ["cvs_ald", "proc_gauss", "challenge_gauss"]
@@ -237,12 +234,6 @@ def test_launches_and_graph_capture():
 
 
 # ---- the model layer ---------------------------------------------------------------------------------------------------------------------
-def _model_curves(m, batch, is_post, eps):
-    """[ns, Q, B, C, T] fp64: the model's own decoder on the same draws (recon_samples)."""
-    res = m.recon_samples(is_post=is_post, num_samples=eps.shape[0], eps=eps, **batch)
-    return np.stack([res[n].double().permute(3, 0, 1, 2).cpu().numpy() for n in m.MOMENT_HEADS[bool(m.GAUSS)]], 1)
-
-
 def _check_model(res, m, v, levels, tag):
     """The dict against np.quantile of the decoder's curves v [ns, Q, B, C, T] of the same draws, within the bar of test 3: recon_samples'
     curves come from the decoder's kernels (slode_ode_solve_fwd + slode_decode_heads), another fp32 evaluation of the same curve, each
@@ -266,7 +257,7 @@ def test_model_level_dict_keys_and_shapes(fam):
         eng.rng_seed(21)
         eng.rng_set_counter(3)
         eps = eng.rng_normal(3, ns * B).view(ns, B, -1)
-        v = _model_curves(m, batch, is_post, eps)
+        v = _model_curves(m, batch, is_post, eps, heads_axis=1)
         eng.profile_enable(True)
         res = m.recon_quantiles(is_post=is_post, num_samples=ns, levels=levels, **batch)
         assert [k for k, _ in eng.profile_read()] == (["weff", "enc_fwd2", "recon_quantiles"] if is_post else ["recon_quantiles"])
@@ -292,13 +283,11 @@ def test_composed_route_where_the_engine_refuses(why, monkeypatch):
     dense = dict(batch)
     if why == "strided":
         batch["observations"] = _padded(batch["observations"])
-    calls = []
-    real = eng.recon_quantiles
-    monkeypatch.setattr(eng, "recon_quantiles", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "recon_quantiles")
     eng.rng_seed(11)
     eng.rng_set_counter(2)
     eps = eng.rng_normal(2, ns * B).view(ns, B, -1)
-    v = _model_curves(m, batch, True, eps)
+    v = _model_curves(m, batch, True, eps, heads_axis=1)
     drawn = m.recon_quantiles(is_post=True, num_samples=ns, levels=levels, **batch)
     assert eng.rng_state() == (11, 0, 2 + ns) and len(calls) == 1                     # refused once, then composed
     given = m.recon_quantiles(is_post=True, num_samples=ns, levels=levels, eps=eps, **batch)
@@ -324,12 +313,10 @@ def test_max_sweeps_switch(monkeypatch):
     batch["observations"] = batch["observations"].permute(0, 2, 1).contiguous().permute(0, 2, 1)
     sweeps = eng.quantile_plan(B, ns, (0.5,))[1]
     assert sweeps > 2
-    calls = []
-    real = eng.recon_quantiles
-    monkeypatch.setattr(eng, "recon_quantiles", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "recon_quantiles")
     eng.rng_seed(5)
     eps = eng.rng_normal(0, ns * B).view(ns, B, -1)
-    v = _model_curves(m, batch, True, eps)
+    v = _model_curves(m, batch, True, eps, heads_axis=1)
     composed = m.recon_quantiles(is_post=True, num_samples=ns, levels=(0.5,), eps=eps, **batch)
     assert calls == []
     fused = m.recon_quantiles(is_post=True, num_samples=ns, levels=(0.5,), eps=eps, max_sweeps=sweeps, **batch)

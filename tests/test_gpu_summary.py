@@ -16,8 +16,8 @@ import torch
 from tests import eval_stats_util as EU
 from tests import recon_moments_util as RU
 from tests import summary_util as SU
-from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
-                                 _recon_moments, _refused)
+from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model,
+                                 _model_curves, _padded, _peak, _per_draw_curves, _refused, _same as _same_arrays)
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it (NaN is a value the call writes): every element must be written
@@ -40,8 +40,7 @@ def _summary(eng, flat, c, is_post, thr, sense=1, eps="case", ns=None, sd=True, 
     return out
 
 
-def _same(a, b):
-    return a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
+_same = functools.partial(_same_arrays, equal_nan=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,13 +53,9 @@ def _per_draw(case, is_post):
     obs_d, labels = _device_batch(c)
     thr = SU.thresholds(SU.oracle_draws(c, is_post))
     eps = c["eps"].to(DEV)
-    curves, f = [], {1: [], -1: []}
-    for k in range(7):
-        e = eps[k].contiguous()
-        curves.append(_recon_moments(eng, flat, c, is_post, eps=e, obs_d=obs_d, labels=labels, ns=1)[0].cpu().numpy())
-        for sense in (1, -1):
-            f[sense].append(_summary(eng, flat, c, is_post, thr, sense, eps=e, ns=1, obs_d=obs_d, labels=labels))
-    return c, eng, flat, thr, np.stack(curves), f
+    f = {sense: [_summary(eng, flat, c, is_post, thr, sense, eps=eps[k].contiguous(), ns=1, obs_d=obs_d, labels=labels) for k in range(7)]
+         for sense in (1, -1)}
+    return c, eng, flat, thr, _per_draw_curves(eng, flat, c, is_post, obs_d, labels), f
 
 
 PER_DRAW = ["cvs_ald", "proc_gauss", "challenge_gauss"]
@@ -270,12 +265,6 @@ def test_refusals_by_name(monkeypatch):
 
 
 # ---- the model layer ---------------------------------------------------------------------------------------------------------------------
-def _model_curves(m, batch, is_post, eps):
-    """[Q, ns, B, C, T] fp64: the model's own decoder on the same draws (recon_samples)."""
-    res = m.recon_samples(is_post=is_post, num_samples=eps.shape[0], eps=eps, **batch)
-    return np.stack([res[n].double().permute(3, 0, 1, 2).cpu().numpy() for n in m.MOMENT_HEADS[bool(m.GAUSS)]])
-
-
 def _check_model(res, m, v, thr, sense, tag, per_draw=None):
     """The dict against the decoder's curves v [Q, ns, B, C, T] of the same draws: continuous slots by the bars, counts by the count rule
     (two fp32 evaluations, each within the bar of the truth: the decoder's curves stand in for the oracle at twice the bar -- here the
@@ -329,9 +318,7 @@ def test_composed_route_where_the_engine_refuses(why, monkeypatch):
     dense = dict(batch)
     if why == "strided":
         batch["observations"] = _padded(batch["observations"])
-    calls = []
-    real = eng.curve_summary
-    monkeypatch.setattr(eng, "curve_summary", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    calls = _count_calls(monkeypatch, eng, "curve_summary")
     eng.rng_seed(11)
     eng.rng_set_counter(2)
     eps = eng.rng_normal(2, ns * B).view(ns, B, -1)

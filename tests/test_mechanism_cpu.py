@@ -13,7 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import draws_ladder_util as DL
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 from tests import mechanism_util as MU
 from tests import recon_moments_util as RU
 
@@ -70,23 +72,6 @@ def test_engine_and_model_signatures():
 
 
 # ---- the plan -----------------------------------------------------------------------------------------------------------------------------
-def _host_engine(case, T=None):
-    """An Engine that only knows its shape: what the plans need."""
-    from structured_latent_odes_amd import _lib as L, engine as E
-    fam, kw, _, T0 = EU.CASES[case]
-
-    class _E(E.Engine):
-        def __init__(self, spec, T):
-            self.spec, self.T, self._shapes = spec, T, {}
-            self.lib = L.load()
-
-    return _E({"cvs": E.cvs_spec, "challenge": E.challenge_spec, "proc": E.proc_spec}[fam](solver="rk4", **kw), T or T0)
-
-
-def _r4(n):
-    return (n + 3) & ~3
-
-
 def _hand_count(eng, n_sel):
     sp = eng.spec
     return MU.plan_bytes(eng.T, sp.ode_state_dim, sp.n_channels, sp.latent_dim, sp.ode_hidden_dim, sp.n_u, sp.gauss, n_sel)
@@ -99,33 +84,33 @@ MASKS = (0x01, 0x08, 0x0a, 0x15, 0x1e, 0x1f)
 def test_plan_against_a_hand_count_of_the_tables(case):
     """Every case, several masks: the plan is the hand count (MU.plan_bytes) for the mask's population count, depends on the count alone, and
     one slot costs exactly 4 r4(3 S T) bytes."""
-    eng = _host_engine(case)
+    eng = LU.host_engine(case)
     S, T = eng.spec.ode_state_dim, eng.T
     got = {m: eng.mechanism_plan(8, m) for m in MASKS}
     for m, b in got.items():
         n = bin(m).count("1")
         assert b == _hand_count(eng, n) <= 160 * 1024, (case, hex(m))
-        assert b - got[0x01] == (n - 1) * 4 * _r4(3 * S * T), (case, hex(m))                 # the cost of one slot, exactly
+        assert b - got[0x01] == (n - 1) * 4 * LU.r4(3 * S * T), (case, hex(m))                 # the cost of one slot, exactly
     assert got[0x15] == eng.mechanism_plan(8, 0x07)
     assert eng.mechanism_plan(1, 0x1f) == eng.mechanism_plan(1024, 0x1f)                   # one workgroup per trajectory: B does not enter
 
 
 def test_one_slot_costs_one_moment_table():
     """3 S T is a multiple of four on cvs at T = 200 (S = 5): every further slot adds exactly 4 r4(3 S T) = 12 S T bytes."""
-    eng = _host_engine("cvs_ald")
+    eng = LU.host_engine("cvs_ald")
     assert (eng.spec.ode_state_dim, eng.T) == (5, 200)
     sizes = [eng.mechanism_plan(8, (1 << n) - 1) for n in range(1, 6)]
-    assert [b - a for a, b in zip(sizes, sizes[1:])] == [4 * _r4(3 * 5 * 200)] * 4 == [12000] * 4
+    assert [b - a for a, b in zip(sizes, sizes[1:])] == [4 * LU.r4(3 * 5 * 200)] * 4 == [12000] * 4
 
 
 def test_plan_of_a_shape_that_fits_one_slot_and_not_five():
     """cvs at T = 1024: the step table and the capture table are 2 x 5 x 1024 x 4 B = 40 KB each, one slot's triples 60 KB: one slot fits,
     five do not -- both figures computed here -- and a refusal still writes the bytes."""
     from structured_latent_odes_amd import _lib as L
-    eng = _host_engine("cvs_ald", T=1024)
+    eng = LU.host_engine("cvs_ald", T=1024)
     assert (eng.spec.ode_state_dim, eng.spec.gauss) == (5, False)
     one, five = _hand_count(eng, 1), _hand_count(eng, 5)
-    assert five - one == 4 * 4 * _r4(3 * 5 * 1024) and one <= 160 * 1024 < five
+    assert five - one == 4 * 4 * LU.r4(3 * 5 * 1024) and one <= 160 * 1024 < five
     assert eng.mechanism_plan(8, 0x10) == one
     with pytest.raises(L.SlodeError, match=r"T = 1024, S = 5, slots = 5 \(%d B\) exceed the budget of 163840 B" % five):
         eng.mechanism_plan(8, 0x1f)
@@ -143,18 +128,8 @@ _N = "slode_mechanism_moments"
 _P = "slode_mechanism_plan"
 _BOTH, _POST, _PRIOR, _PLAN = ("post", "prior"), ("post",), ("prior",), ("plan",)
 _ADVICE = "compose slode_ode_solve_fwd and the dynamics net instead"
-LADDER = [
-    ("handle NULL", _BOTH, -1, ["handle is NULL"]), ("shape NULL", _BOTH, -1, ["shape is NULL"]), ("layout NULL", _BOTH, -1, ["layout is NULL"]),
-    ("params NULL", _BOTH, -1, ["params is NULL"]), ("batch NULL", _BOTH, -1, [_N, "batch", "is NULL"]), ("times NULL", _BOTH, -1, [_N, "times", "is NULL"]),
-    ("stage_t NULL", _BOTH, -1, [_N, "stage_t", "is NULL"]), ("workspace NULL", _BOTH, -1, [_N, "workspace", "is NULL"]),
-    ("bad shape", _BOTH, -1, ["T out of range"]), ("num_samples 0", _BOTH, -1, [_N, "num_samples = 0 < 1"]),
-    ("num_samples 2^30", _BOTH, -1, [_N, "B x num_samples", "2^30 - 1"]),
-    ("adaptive method 3", _BOTH, -1, [_N, "adaptive solver dopri5", _ADVICE]), ("adaptive method 4", _BOTH, -1, [_N, "adaptive solver bosh3"]),
-    ("adaptive method 5", _BOTH, -1, [_N, "adaptive solver fehlberg2"]), ("adaptive method 6", _BOTH, -1, [_N, "adaptive solver adaptive_heun"]),
-    ("particles 2", _BOTH, -1, [_N, "particles = 2"]), ("fold_on", _BOTH, -1, [_N, "measured arms"]), ("ode_pack", _BOTH, -1, [_N, "measured arms"]),
-    ("ode_alg", _BOTH, -1, [_N, "measured arms"]), ("obs NULL", _POST, -1, [_N, "batch->obs is NULL"]),
-    ("padded strides", _POST, -1, [_N, "observation strides (266, 1, 3)", _ADVICE]),
-    ("channel-major strides of another T", _POST, -1, [_N, "observation strides (258, 87, 1)"]), ("no_fold", _POST, -1, [_N, "SLODE_NO_FOLD"]),
+_HEAD, _LABELS, _TWO = DL.shared_rungs(_N, "batch / times / stage_t / workspace", _ADVICE)
+LADDER = _HEAD + [
     ("mean NULL", _BOTH, -1, [_N + ": mean is NULL"]), ("slots 0", _BOTH, -1, [_N + ": slots = 0x0 selects nothing"]),
     ("slots bit 5", _BOTH, -1, [_N + ": slots = 0x20", "bits at or beyond SLODE_MECHANISM_SLOTS = 5"]),
     ("slots all + bit 31", _BOTH, -1, [_N + ": slots = 0x8000001f"]),
@@ -163,13 +138,10 @@ LADDER = [
     ("LDS: T 1024, two slots", _BOTH, -1, [_N, "slots = 2 (208800 B"]),
     ("T 1024, one slot, run-time S build: fits; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
     ("T 1024, one slot: fits; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
-    ("label columns 3, n_u 2", _BOTH, -1, ["label tensors have 3 columns"]), ("n_labels 5", _BOTH, -1, ["n_labels out of range"]),
-    ("label tensor 1 NULL", _BOTH, -1, ["label tensor 1 is NULL"]), ("no label tensors", _PRIOR, -1, [_N, "the prior needs the label tensors"]),
-    ("workspace too small", _BOTH, -3, ["workspace 64 B < required"]), ("sd NULL, one slot; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
-    # two conditions at once: the earlier rung speaks
-    ("params NULL + batch NULL", _BOTH, -1, ["params is NULL"]), ("times NULL + num_samples 0", _BOTH, -1, ["is NULL"]),
-    ("num_samples 0 + adaptive", _BOTH, -1, ["num_samples = 0"]), ("adaptive + particles 2", _BOTH, -1, ["adaptive solver bosh3"]),
-    ("ode_alg + obs NULL", _POST, -1, ["measured arms"]), ("no_fold + mean NULL", _POST, -1, ["observation strides"]),
+] + _LABELS + [
+    ("sd NULL, one slot; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
+] + _TWO + [                                                                          # two conditions at once: the earlier rung speaks
+    ("no_fold + mean NULL", _POST, -1, ["observation strides"]),
     ("mean NULL + slots 0", _BOTH, -1, ["mean is NULL"]), ("slots bit 7 + LDS", _BOTH, -1, ["slots = 0x9f"]),
     ("LDS + label columns 3", _BOTH, -1, ["LDS tables"]), ("label columns 3 + workspace too small", _BOTH, -1, ["label tensors have 3 columns"]),
     # the plan (its counter column: the bytes it wrote)
@@ -187,40 +159,13 @@ def test_mechanism_refusals_on_a_hand_filled_handle(tmp_path):
     tests/golden/mechanism_refusals.txt; the rungs shared with slode_recon_moments carry the texts tests/golden/eval_refusals.txt records
     for it on that side, the call's name, its list of required pointers and its advice apart; the call's LDS figures are the plan's and
     the hand count's; a refused plan has written its bytes; and the memory that stands for the outputs is untouched."""
-    from tests.refusals_util import refusal_lines
-    lines = refusal_lines("mechanism_refusals", tmp_path)
-    assert lines[-1] == "memory that stands for the outputs | untouched"
-    want = open(os.path.join(ROOT, "tests", "golden", "mechanism_refusals.txt")).read().splitlines()
-    for i, (g, w) in enumerate(zip(lines, want)):
-        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
-    expect = [(name, col, status, words) for name, cols, status, words in LADDER for col in cols]
-    assert len(lines) == len(want) == len(expect) + 1
-    recon = {}
-    for line in open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines():
-        parts = line.split(" | ", 4)
-        if len(parts) == 5 and parts[1] == "recon_moments":
-            recon[parts[0]] = parts[4]
-    shared, figures = 0, {}
-    for line, (name, col, status, words) in zip(lines[:-1], expect):
-        got_name, got_col, got_status, counter, msg = line.split(" | ", 4)
-        assert (got_name, got_col) == (name, col) and int(got_status) == status, line
-        for w in words:
-            assert w in msg, (name, w, msg)
-        if col == "plan":
-            assert int(counter) == PLAN_BYTES.get(name, int(counter)) and (name not in ("slots 0", "slots bit 5") or int(counter) > 0), line
-            continue
-        assert counter == "7", line                                                      # refused, and nothing drawn
-        if name.startswith("LDS: "):
-            figures[name] = int(re.search(r"\((\d+) B", msg).group(1))
-        key = name.replace("num_samples", "draws")
-        if key in recon and "LDS" not in name and "workspace too small" not in name and "mean NULL" not in name:
-            shared += 1
-            theirs = recon[key].replace("slode_recon_moments", _N).replace("batch / mean / ", "batch / ").replace("reduce recon_samples instead", _ADVICE)
-            assert msg == theirs, (name, msg, recon[key])
-    eng = _host_engine("cvs_ald", T=1024)
+    def plan_line(name, counter, line):      # (the plan's counter column: the bytes it wrote, refused or not)
+        assert counter == PLAN_BYTES.get(name, counter) and (name not in ("slots 0", "slots bit 5") or counter > 0), line
+    _, shared, figures = DL.check_ladder("mechanism_refusals", tmp_path, LADDER, _N, _ADVICE, plan_line=plan_line, not_shared=("mean NULL",))
+    figures = {k: int(*v) for k, v in figures.items()}
+    eng = LU.host_engine("cvs_ald", T=1024)
     assert figures == {"LDS: T 1024, five slots": PLAN_BYTES["LDS: T 1024, five slots"] == _hand_count(eng, 5) and _hand_count(eng, 5),
                        "LDS: T 1024, two slots": _hand_count(eng, 2)}
-    print("%d lines, %d of them word for word slode_recon_moments' texts" % (len(lines), shared))
     assert shared >= 40
 
 

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import eval_stats_util as EU
+from tests import draws_ladder_util as DL
+from tests import lds_util as LU
 from tests import quantile_util as QU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,24 +119,11 @@ def test_integer_ranks_are_exact():
 
 
 # ---- the plan's ladder -----------------------------------------------------------------------------------------------------------------------
-def _host_engine(case, T=None):
-    """An Engine that only knows its shape: what the plans need."""
-    from structured_latent_odes_amd import _lib as L, engine as E
-    fam, kw, _, T0 = EU.CASES[case]
-
-    class _E(E.Engine):
-        def __init__(self, spec, T):
-            self.spec, self.T, self._shapes = spec, T, {}
-            self.lib = L.load()
-
-    return _E({"cvs": E.cvs_spec, "challenge": E.challenge_spec, "proc": E.proc_spec}[fam](solver="rk4", **kw), T or T0)
-
-
 @pytest.mark.parametrize("K", KS)
 @pytest.mark.parametrize("case", ["cvs_ald", "proc_ald", "challenge_gauss"])
 def test_plan_against_the_restated_rule(case, K):
     from structured_latent_odes_amd import _lib as L
-    eng = _host_engine(case)
+    eng = LU.host_engine(case)
     T = eng.T
     for name, levels in QU.LEVEL_SETS.items():
         for tile in (0, 1, T):
@@ -156,7 +144,7 @@ def test_plan_against_the_restated_rule(case, K):
 
 def test_plan_of_the_metric_shape():
     """cvs, T = 200: the band at K = 200 keeps 12 values per column and fits in one sweep; the median keeps all 200 and needs several."""
-    eng = _host_engine("cvs_ald", T=200)
+    eng = LU.host_engine("cvs_ald", T=200)
     band, median = eng.quantile_plan(1024, 200, (0.025, 0.975)), eng.quantile_plan(1024, 200, (0.5,))
     assert band[:4] == (200, 1, 6, 6) and median[2:4] == (200, 0) and median[1] > 8
     print("cvs T=200 K=200: band %s, median %s" % (band, median))
@@ -167,19 +155,8 @@ _N = "slode_recon_quantiles"
 _BOTH, _POST, _PRIOR, _PLAN = ("post", "prior"), ("post",), ("prior",), ("plan",)
 _BIG = "T 1024, S 8, C 4, median of"
 _WS = ["workspace 64 B < required"]
-LADDER = [
-    ("handle NULL", _BOTH, -1, ["handle is NULL"]), ("shape NULL", _BOTH, -1, ["shape is NULL"]), ("layout NULL", _BOTH, -1, ["layout is NULL"]),
-    ("params NULL", _BOTH, -1, ["params is NULL"]), ("batch NULL", _BOTH, -1, [_N, "batch", "is NULL"]), ("times NULL", _BOTH, -1, [_N, "times", "is NULL"]),
-    ("stage_t NULL", _BOTH, -1, [_N, "stage_t", "is NULL"]), ("workspace NULL", _BOTH, -1, [_N, "workspace", "is NULL"]),
-    ("bad shape", _BOTH, -1, ["T out of range"]), ("num_samples 0", _BOTH, -1, [_N, "num_samples = 0 < 1"]),
-    ("num_samples 2^30", _BOTH, -1, [_N, "B x num_samples", "2^30 - 1"]),
-    ("adaptive method 3", _BOTH, -1, [_N, "adaptive solver dopri5", "sort recon_samples instead"]),
-    ("adaptive method 4", _BOTH, -1, [_N, "adaptive solver bosh3"]),
-    ("adaptive method 5", _BOTH, -1, [_N, "adaptive solver fehlberg2"]), ("adaptive method 6", _BOTH, -1, [_N, "adaptive solver adaptive_heun"]),
-    ("particles 2", _BOTH, -1, [_N, "particles = 2"]), ("fold_on", _BOTH, -1, [_N, "measured arms"]), ("ode_pack", _BOTH, -1, [_N, "measured arms"]),
-    ("ode_alg", _BOTH, -1, [_N, "measured arms"]), ("obs NULL", _POST, -1, [_N, "batch->obs is NULL"]),
-    ("padded strides", _POST, -1, [_N, "observation strides (266, 1, 3)", "sort recon_samples instead"]),
-    ("channel-major strides of another T", _POST, -1, [_N, "observation strides (258, 87, 1)"]), ("no_fold", _POST, -1, [_N, "SLODE_NO_FOLD"]),
+_HEAD, _LABELS, _TWO = DL.shared_rungs(_N, "batch / times / stage_t / workspace", "sort recon_samples instead")
+LADDER = _HEAD + [
     ("out NULL", _BOTH, -1, [_N, "out is NULL"]), ("n_levels 0", _BOTH, -1, [_N, "n_levels = 0 out of range [1, 8]"]),
     ("n_levels 9", _BOTH, -1, [_N, "n_levels = 9 out of range [1, 8]"]), ("levels NULL", _BOTH, -1, [_N, "levels is NULL"]),
     ("levels[1] 1.5", _BOTH, -1, [_N, "levels[1] = 1.5 is not in [0, 1]"]), ("levels[0] -0.001", _BOTH, -1, [_N, "levels[0] = -0.001 is not in [0, 1]"]),
@@ -191,13 +168,9 @@ LADDER = [
                                               "sort recon_samples instead"]),
     ("%s 1024, tile 0: fits; workspace too small" % _BIG, _BOTH, -3, _WS),
     ("unordered and duplicate levels: taken; workspace too small", _BOTH, -3, _WS),
-    ("label columns 3, n_u 2", _BOTH, -1, ["label tensors have 3 columns"]), ("n_labels 5", _BOTH, -1, ["n_labels out of range"]),
-    ("label tensor 1 NULL", _BOTH, -1, ["label tensor 1 is NULL"]), ("no label tensors", _PRIOR, -1, [_N, "the prior needs the label tensors"]),
-    ("workspace too small", _BOTH, -3, _WS),
-    # two conditions at once: the earlier rung speaks
-    ("params NULL + batch NULL", _BOTH, -1, ["params is NULL"]), ("times NULL + num_samples 0", _BOTH, -1, ["is NULL"]),
-    ("num_samples 0 + adaptive", _BOTH, -1, ["num_samples = 0"]), ("adaptive + particles 2", _BOTH, -1, ["adaptive solver bosh3"]),
-    ("ode_alg + obs NULL", _POST, -1, ["measured arms"]), ("no_fold + out NULL", _POST, -1, ["observation strides"]),
+] + _LABELS + [
+] + _TWO + [                                                                          # two conditions at once: the earlier rung speaks
+    ("no_fold + out NULL", _POST, -1, ["observation strides"]),
     ("out NULL + n_levels 0", _BOTH, -1, ["out is NULL"]), ("n_levels 9 + levels[0] NaN", _BOTH, -1, ["n_levels = 9"]),
     ("levels[0] NaN + tile -1", _BOTH, -1, ["levels[0] = nan"]), ("tile -1 + LDS", _BOTH, -1, ["tile = -1 out of range [0, T = 1024]"]),
     ("LDS + label columns 3", _BOTH, -1, ["depth = 4096 + 0"]), ("label columns 3 + workspace too small", _BOTH, -1, ["label tensors have 3 columns"]),
@@ -217,34 +190,8 @@ def test_quantile_refusals_on_a_hand_filled_handle(tmp_path):
     tests/golden/quantile_refusals.txt; the rungs shared with slode_recon_moments carry the texts tests/golden/eval_refusals.txt records for
     it on that side, the call's name, its list of required pointers and its advice apart; the call's LDS figures are the plan's; and the
     memory that stands for the outputs untouched."""
-    from tests.refusals_util import refusal_lines
-    lines = refusal_lines("quantile_refusals", tmp_path)
-    assert lines[-1] == "memory that stands for the outputs | untouched"
-    want = open(os.path.join(ROOT, "tests", "golden", "quantile_refusals.txt")).read().splitlines()
-    for i, (g, w) in enumerate(zip(lines, want)):
-        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
-    expect = [(name, col, status, words) for name, cols, status, words in LADDER for col in cols]
-    assert len(lines) == len(want) == len(expect) + 1
-    recon = {}
-    for line in open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines():
-        parts = line.split(" | ", 4)
-        if len(parts) == 5 and parts[1] == "recon_moments":
-            recon[parts[0]] = parts[4]
-    shared, figures = 0, {}
-    for line, (name, col, status, words) in zip(lines[:-1], expect):
-        got_name, got_col, got_status, counter, msg = line.split(" | ", 4)
-        assert (got_name, got_col) == (name, col) and int(got_status) == status and counter == "7", line      # refused, and nothing drawn
-        for w in words:
-            assert w in msg, (name, w, msg)
-        if name.startswith("LDS: "):
-            figures.setdefault(name, set()).add(re.search(r"\((\d+) B", msg).group(1))
-        key = name.replace("num_samples", "draws")
-        if col != "plan" and key in recon and "LDS" not in name and "workspace too small" not in name:
-            shared += 1
-            assert msg == recon[key].replace("slode_recon_moments", _N).replace("batch / mean / ", "batch / ").replace("reduce recon_samples", "sort recon_samples"), \
-                (name, msg, recon[key])
+    _, shared, figures = DL.check_ladder("quantile_refusals", tmp_path, LADDER, _N, "sort recon_samples instead")
     assert len(figures) == 2 and all(len(v) == 1 for v in figures.values())            # the call's figures are the plan's
-    print("%d lines, %d of them word for word slode_recon_moments' texts" % (len(lines), shared))
     assert shared >= 40
 
 

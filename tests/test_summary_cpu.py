@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import draws_ladder_util as DL
 from tests import eval_stats_util as EU
+from tests import lds_util as LU
 from tests import recon_moments_util as RU
 from tests import summary_util as SU
 
@@ -61,52 +63,32 @@ def test_engine_signature():
     assert list(inspect.signature(Engine.curve_summary_plan).parameters) == ["self", "B", "want_p_beyond"]
 
 
-def _host_engine(case, T=None):
-    """An Engine that only knows its shape: what the plans need."""
-    from structured_latent_odes_amd import _lib as L, engine as E
-    fam, kw, _, T0 = EU.CASES[case]
-
-    class _E(E.Engine):
-        def __init__(self, spec, T):
-            self.spec, self.T, self._shapes = spec, T, {}
-            self.lib = L.load()
-
-    return _E({"cvs": E.cvs_spec, "challenge": E.challenge_spec, "proc": E.proc_spec}[fam](solver="rk4", **kw), T or T0)
-
-
-def _r4(n):
-    return (n + 3) & ~3
-
-
 def _hand_count(eng, want_p):
     """The shared forward pieces (step table 2 (T - 1) S, one row of 2 + 2 S floats rounded up to four per hidden unit, the transposed first
     layers L x 2 H, their biases 2 H, the init net's output layer H S + S, the head weights Q C S, the dynamics biases 2 S, z, the labels, the
     init net's hidden layer, x0), loc | scale, then the grid T and the node weights T, the value table Q C T, the counts Q C T only with p_beyond, and the
     moment triples 3 Q C 8; every piece rounded up to 16 bytes."""
     sp, T = eng.spec, eng.T
-    S, H, Ld, Cn, Q = sp.ode_state_dim, sp.ode_hidden_dim, sp.latent_dim, sp.n_channels, 1 if sp.gauss else 3
-    row = (2 + 2 * S + 3) & ~3
-    shared = (2 * _r4((T - 1) * S) + _r4(H * row) + _r4(Ld * 2 * H) + _r4(2 * H) + _r4(H * S + S) + _r4(Q * Cn * S) + _r4(2 * S) + _r4(Ld)
-              + _r4(max(sp.n_u, 1)) + _r4(H) + _r4(S))
-    return 4 * (shared + 2 * _r4(Ld) + 2 * _r4(T) + _r4(Q * Cn * T) * (2 if want_p else 1) + _r4(3 * Q * Cn * 8))
+    Ld, Cn, Q = sp.latent_dim, sp.n_channels, 1 if sp.gauss else 3
+    return 4 * (LU.spec_shared_floats(sp, T) + 2 * LU.r4(Ld) + 2 * LU.r4(T) + LU.r4(Q * Cn * T) * (2 if want_p else 1) + LU.r4(3 * Q * Cn * 8))
 
 
 @pytest.mark.parametrize("case", list(EU.CASES))
 def test_plan_against_a_hand_count_of_the_tables(case):
-    eng = _host_engine(case)
+    eng = LU.host_engine(case)
     sp = eng.spec
     with_p, without = eng.curve_summary_plan(8, True), eng.curve_summary_plan(8, False)
     assert with_p == _hand_count(eng, True) and without == _hand_count(eng, False)
-    assert with_p - without == 4 * _r4((1 if sp.gauss else 3) * sp.n_channels * eng.T)         # the counters cost exactly one Q C T table
+    assert with_p - without == 4 * LU.r4((1 if sp.gauss else 3) * sp.n_channels * eng.T)         # the counters cost exactly one Q C T table
 
 
 def test_plan_of_a_shape_that_fits_only_without_the_counters():
     """T = 1024, S = 8, ALD, C = 4 (proc): the step table alone is 2 x 1023 x 8 x 4 B = 64 KB and the two Q C T tables are 48 KB each."""
     from structured_latent_odes_amd import _lib as L
-    eng = _host_engine("proc_ald", T=1024)
+    eng = LU.host_engine("proc_ald", T=1024)
     sp = eng.spec
     assert (sp.ode_state_dim, sp.n_channels, sp.gauss) == (8, 4, False)
-    assert 2 * _r4(1023 * 8) * 4 == 65472 and _r4(12 * 1024) * 4 == 48 * 1024
+    assert 2 * LU.r4(1023 * 8) * 4 == 65472 and LU.r4(12 * 1024) * 4 == 48 * 1024
     without, want = eng.curve_summary_plan(8, False), _hand_count(eng, True)
     assert without == _hand_count(eng, False) <= 160 * 1024 < want
     with pytest.raises(L.SlodeError, match=r"T = 1024, S = 8, C = 4, with p_beyond \(%d B\) exceed the budget of 163840 B" % want):
@@ -117,33 +99,18 @@ def test_plan_of_a_shape_that_fits_only_without_the_counters():
 _N = "slode_curve_summary"
 _BOTH, _POST, _PRIOR, _PLAN = ("post", "prior"), ("post",), ("prior",), ("plan",)
 _BIG = "T 1024, S 8, C 4"
-LADDER = [
-    ("handle NULL", _BOTH, -1, ["handle is NULL"]), ("shape NULL", _BOTH, -1, ["shape is NULL"]), ("layout NULL", _BOTH, -1, ["layout is NULL"]),
-    ("params NULL", _BOTH, -1, ["params is NULL"]), ("batch NULL", _BOTH, -1, [_N, "batch", "is NULL"]), ("times NULL", _BOTH, -1, [_N, "times", "is NULL"]),
-    ("stage_t NULL", _BOTH, -1, [_N, "stage_t", "is NULL"]), ("workspace NULL", _BOTH, -1, [_N, "workspace", "is NULL"]),
-    ("bad shape", _BOTH, -1, ["T out of range"]), ("num_samples 0", _BOTH, -1, [_N, "num_samples = 0 < 1"]),
-    ("num_samples 2^30", _BOTH, -1, [_N, "B x num_samples", "2^30 - 1"]),
-    ("adaptive method 3", _BOTH, -1, [_N, "adaptive solver dopri5", "reduce recon_samples instead"]),
-    ("adaptive method 4", _BOTH, -1, [_N, "adaptive solver bosh3"]),
-    ("adaptive method 5", _BOTH, -1, [_N, "adaptive solver fehlberg2"]), ("adaptive method 6", _BOTH, -1, [_N, "adaptive solver adaptive_heun"]),
-    ("particles 2", _BOTH, -1, [_N, "particles = 2"]), ("fold_on", _BOTH, -1, [_N, "measured arms"]), ("ode_pack", _BOTH, -1, [_N, "measured arms"]),
-    ("ode_alg", _BOTH, -1, [_N, "measured arms"]), ("obs NULL", _POST, -1, [_N, "batch->obs is NULL"]),
-    ("padded strides", _POST, -1, [_N, "observation strides (266, 1, 3)", "reduce recon_samples instead"]),
-    ("channel-major strides of another T", _POST, -1, [_N, "observation strides (258, 87, 1)"]), ("no_fold", _POST, -1, [_N, "SLODE_NO_FOLD"]),
+_HEAD, _LABELS, _TWO = DL.shared_rungs(_N, "batch / times / stage_t / workspace", "reduce recon_samples instead")
+LADDER = _HEAD + [
     ("mean NULL", _BOTH, -1, [_N, "mean is NULL"]), ("sense 0", _BOTH, -1, [_N, "sense = 0"]), ("sense 2", _BOTH, -1, [_N, "sense = 2"]),
     ("thr[1] NaN", _BOTH, -1, [_N, "thr[1] = nan is not finite"]), ("thr[2] inf", _BOTH, -1, [_N, "thr[2] = inf is not finite"]),
     ("thr[3] NaN beyond C = 3: not read; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
     ("p_beyond without thr", _BOTH, -1, [_N, "p_beyond needs a threshold"]),
     ("LDS: %s, with p_beyond" % _BIG, _BOTH, -1, [_N, "LDS tables", "T = 1024, S = 8, C = 4, with p_beyond (178464 B", "counts", "drop p_beyond"]),
     ("%s, without p_beyond: fits; workspace too small" % _BIG, _BOTH, -3, ["workspace 64 B < required"]),
-    ("label columns 3, n_u 2", _BOTH, -1, ["label tensors have 3 columns"]), ("n_labels 5", _BOTH, -1, ["n_labels out of range"]),
-    ("label tensor 1 NULL", _BOTH, -1, ["label tensor 1 is NULL"]), ("no label tensors", _PRIOR, -1, [_N, "the prior needs the label tensors"]),
-    ("workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
+] + _LABELS + [
     ("sd, p_beyond and thr NULL, sense -1; workspace too small", _BOTH, -3, ["workspace 64 B < required"]),
-    # two conditions at once: the earlier rung speaks
-    ("params NULL + batch NULL", _BOTH, -1, ["params is NULL"]), ("times NULL + num_samples 0", _BOTH, -1, ["is NULL"]),
-    ("num_samples 0 + adaptive", _BOTH, -1, ["num_samples = 0"]), ("adaptive + particles 2", _BOTH, -1, ["adaptive solver bosh3"]),
-    ("ode_alg + obs NULL", _POST, -1, ["measured arms"]), ("no_fold + mean NULL", _POST, -1, ["observation strides"]),
+] + _TWO + [                                                                          # two conditions at once: the earlier rung speaks
+    ("no_fold + mean NULL", _POST, -1, ["observation strides"]),
     ("mean NULL + sense 0", _BOTH, -1, ["mean is NULL"]), ("sense 0 + thr[0] NaN", _BOTH, -1, ["sense = 0"]),
     ("thr[0] NaN + LDS", _BOTH, -1, ["thr[0] = nan"]), ("p_beyond without thr + LDS", _BOTH, -1, ["p_beyond needs a threshold"]),
     ("LDS + label columns 3", _BOTH, -1, ["LDS tables"]), ("label columns 3 + workspace too small", _BOTH, -1, ["label tensors have 3 columns"]),
@@ -160,33 +127,8 @@ def test_summary_refusals_on_a_hand_filled_handle(tmp_path):
     tests/golden/summary_refusals.txt; the rungs shared with slode_recon_moments carry the texts tests/golden/eval_refusals.txt records for
     it on that side, the call's name and its list of required pointers apart (the advice is the same); the call's LDS figure is the plan's;
     and the memory that stands for the outputs untouched."""
-    from tests.refusals_util import refusal_lines
-    lines = refusal_lines("summary_refusals", tmp_path)
-    assert lines[-1] == "memory that stands for the outputs | untouched"
-    want = open(os.path.join(ROOT, "tests", "golden", "summary_refusals.txt")).read().splitlines()
-    for i, (g, w) in enumerate(zip(lines, want)):
-        assert g == w, "line %d:\n  got  %s\n  want %s" % (i + 1, g, w)
-    expect = [(name, col, status, words) for name, cols, status, words in LADDER for col in cols]
-    assert len(lines) == len(want) == len(expect) + 1
-    recon = {}
-    for line in open(os.path.join(ROOT, "tests", "golden", "eval_refusals.txt")).read().splitlines():
-        parts = line.split(" | ", 4)
-        if len(parts) == 5 and parts[1] == "recon_moments":
-            recon[parts[0]] = parts[4]
-    shared, figures = 0, set()
-    for line, (name, col, status, words) in zip(lines[:-1], expect):
-        got_name, got_col, got_status, counter, msg = line.split(" | ", 4)
-        assert (got_name, got_col) == (name, col) and int(got_status) == status and counter == "7", line      # refused, and nothing drawn
-        for w in words:
-            assert w in msg, (name, w, msg)
-        if name.startswith("LDS: "):
-            figures.add(re.search(r"\((\d+) B", msg).group(1))
-        key = name.replace("num_samples", "draws")
-        if col != "plan" and key in recon and "LDS" not in name and "workspace too small" not in name:
-            shared += 1
-            assert msg == recon[key].replace("slode_recon_moments", _N).replace("batch / mean / ", "batch / "), (name, msg, recon[key])
-    assert figures == {"178464"}                                                       # the call's figure is the plan's
-    print("%d lines, %d of them word for word slode_recon_moments' texts" % (len(lines), shared))
+    _, shared, figures = DL.check_ladder("summary_refusals", tmp_path, LADDER, _N, "reduce recon_samples instead")
+    assert set().union(*figures.values()) == {"178464"}                                # the call's figure is the plan's
     assert shared >= 50
 
 

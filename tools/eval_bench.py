@@ -1,6 +1,8 @@
-"""What the benches of the eval-side calls (recon_moments_bench, intervene_bench, attribution_bench, forecast_bench, cohort_bench, calibration_bench,
-traj_bounds_bench, label_evidence_bench, refine_bench, pointwise_bench, summary_bench, quantile_bench, mechanism_bench, joint_band_bench and, for the model and the tail, stats_pass_bench) share: the model and its batch from a shape tuple, a call timed with device events, the
-alternating-legs loop with its warm-up and summary, and the command line with its one JSON line."""
+"""What the benches of the eval-side calls share -- the moment calls' recon_moments_bench, intervene_bench, forecast_bench, cohort_bench,
+calibration_bench; the scored-draw calls' traj_bounds_bench, label_evidence_bench, refine_bench, pointwise_bench; the whole-curve calls'
+attribution_bench, summary_bench, quantile_bench, mechanism_bench, joint_band_bench; and, for the model and the tail, stats_pass_bench:
+the model and its batch from a shape tuple, a call timed with device events, the alternating-legs loop with its warm-up and summary, and
+the command line with its one JSON line."""
 import argparse
 import importlib
 import json
