@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_
       k.sigtab[i] = sig;
       k.sigtab[k.CT + i] = 1.0f / sig;
       k.sigtab[2 * k.CT + i] = k.gauss ? logf(sig) : logf(2.f * sig);
-      k.sigtab[3 * k.CT + i] = 1.f - expf(-sig);
+      k.sigtab[3 * k.CT + i] = softplus_gradf(sig);
     }
   } else {
     // one wave per hidden unit m: rowsum[m][f] for every f, then b_eff[m]

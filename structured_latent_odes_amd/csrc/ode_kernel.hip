@@ -1474,9 +1474,9 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
               s_st[(q * C + c) * T + t] = gmu;
             }
           }
-          if (BWD) {  // constant_std gradient: thread t owns slab entry (c, t); softplus'(x) = 1 - exp(-softplus(x))
+          if (BWD) {  // constant_std gradient: thread t owns slab entry (c, t); softplus'(x) = 1 - exp(-softplus(x)) (softplus_gradf)
             float* dst = k.slabs + srow * k.slab_stride + 1 + k.o_cstd + c * T + t;
-            const float val = gsig * (use_tab ? t_ds[c] : 1.f - expf(-sig));
+            const float val = gsig * (use_tab ? t_ds[c] : softplus_gradf(sig));
             st_out<WT>(dst, (ONE || b == vblk) ? val : (*dst + val));
           }
         }
