@@ -7,13 +7,22 @@
 // rtol*max(|y0|,|y1|))), factor clamp [0.2, 10] with safety 0.9, quartic dense output through (y0, y_mid, y1, f0, f1)) --
 // validated at solution level against the oracle's per-trajectory restatement and scipy RK45.
 //
-// Mapping: EIGHT LANES PER TRAJECTORY (8 trajectories per wave), lane g = state component g.  An adaptive solve is one long
-// dependent chain per trajectory, so its latency -- not the FLOPs -- sets the kernel time.  The chain is kept short by the structure
-// of the dynamics net: its hidden layer is relu(w_t t + u_j), so the head pre-activations are piecewise linear in t and a lane
-// reads value and slope of its two heads from a per-trajectory table of the H + 1 linear segments (load_units / eval_ad): one
-// evaluation of the coefficients is 4 compares per lane, an OR butterfly over the group on the DPP crossbar, a popcount, one LDS row,
-// 2 fmas and one sigmoid pair -- branch-free, the evaluations of a step independent of each other; all the Runge-Kutta arithmetic is
-// scalar per lane.
+// Mapping: a LANE GROUP is eight lanes, lane g = state component g.  An adaptive solve is one long dependent chain per trajectory, so
+// its latency -- not the FLOPs -- sets the kernel time.  The chain is kept short by the structure of the dynamics net: its hidden layer is
+// relu(w_t t + u_j), so the head pre-activations are piecewise linear in t and a lane reads value and slope of its two heads from a
+// per-trajectory table of the H + 1 linear segments (load_units / eval_ad): one evaluation of the coefficients is 4 compares per lane, an
+// OR butterfly over the group on the DPP crossbar, a popcount, one LDS row, 2 fmas and one sigmoid pair -- branch-free, the evaluations of
+// a step independent of each other; all the Runge-Kutta arithmetic is scalar per lane.
+//
+// The forward solve (`dopri5_fwd_kernel<M, S, H, LPT>`) gives a trajectory LPT = 8, 16, 32 or 64 lanes: NG = LPT / 8 lane groups, lane =
+// 8 e + g.  One group puts B = 4096 trajectories on 512 waves: half the SIMDs idle, every wave a lone dependent chain of ~350 instructions
+// per attempted step, its trip count the MAXIMUM over its eight trajectories.  With more groups the step's stage times are evaluated SIDE
+// BY SIDE (ceil(NT / NG) table look-ups per lane instead of NT) and gathered -- a DPP row rotation for two groups, ds_bpermute for four and
+// eight -- and every group then runs the Runge-Kutta combination, the error norm and the controller on the same values: the same
+// operations in the same order at every width, so the accepted steps, the records and the outputs are bit for bit the same.  More waves
+// (1024 / 2048 / 4096 at B = 4096) with fewer instructions each; what the measurement says about the widths is in DESIGN 3.3 (LPT = 64
+// turns the latency problem into an equally large throughput problem: every lane group repeats the combination, and the scalar
+// bookkeeping of 16 waves per CU saturates the issue slots).  The reverse sweep runs one group per trajectory.
 //
 // The same kernels run torchdiffeq's other adaptive Runge-Kutta pairs -- bosh3, fehlberg2, adaptive_heun -- which share the solver class
 // and everything above but the tableau and the order: the kernels are templates on a constexpr tableau type (Dopri5 / SmallRk<...>
@@ -33,10 +42,11 @@
 
 namespace {
 
-constexpr int G = 8;            // lanes per trajectory
-constexpr int DNT = 128;        // threads per workgroup (B = 4096: 256 workgroups, one per CU)
-constexpr int TPB = DNT / G;    // trajectories per workgroup
+constexpr int G = 8;            // lanes per lane group: one per state component
 constexpr int JL = 4;           // hidden units per lane (H <= 32)
+// threads per workgroup of the forward solve at LPT lanes per trajectory (LPT = 8: B = 4096 is 256 workgroups, one per CU); a workgroup
+// holds fwd_threads(LPT) / LPT trajectories
+constexpr int fwd_threads(int lpt) { return lpt == G ? 128 : 256; }
 
 struct DpK {
   int B, T, L;
@@ -576,6 +586,24 @@ __device__ __forceinline__ float group_rms_fast(float v, bool own) { return sqrt
 template <int S>
 __device__ __forceinline__ float group_rms_fast(float v, bool own) { return __builtin_amdgcn_sqrtf(group_add(own ? v * v : 0.f) * (1.0f / S)); }
 #endif
+// the dense output at tq in [t, t + dt]: the quartic y + x (cd + x (cc + x (cb + x ca))) at x = (tq - t) / dt, rdt = DP5_RCP(dt)
+__device__ __forceinline__ float dense_eval(float tq, float t, float dt, float rdt, float y, float ca, float cb, float cc, float cd) {
+#ifdef SLODE_DP5_PRECISE
+  const double xq = ((double)tq - (double)t) / (double)dt;
+  return (float)((double)y + xq * ((double)cd + xq * ((double)cc + xq * ((double)cb + xq * (double)ca))));
+#else
+  const float xq = (tq - t) * rdt;
+  return y + xq * (cd + xq * (cc + xq * (cb + xq * ca)));
+#endif
+}
+// the controller's 0.9 ratio^(-1/p), rp = 1 / p
+__device__ __forceinline__ float safe_factor(float ratio, float rp) {
+#ifdef SLODE_DP5_PRECISE
+  return 0.9f * powf(ratio, -rp);
+#else
+  return 0.9f * __builtin_amdgcn_exp2f(-rp * __builtin_amdgcn_logf(ratio));   // (v_log_f32 is log2)
+#endif
+}
 
 // The set-up's result -- the workgroup's whole GroupLds block (segment tables, switching times, their order, head tables) and the init
 // net's pre-activations -- goes to global memory for the reverse sweep, which rebuilds exactly these tables for exactly these sixteen
@@ -637,158 +665,14 @@ __device__ __forceinline__ void latent_store(const DpK& k, long long bb, bool li
   }
 }
 
-template <class M, int S, int H>
-__global__ void __launch_bounds__(DNT) dopri5_kernel(const DpK k) {
-  static_assert(S <= G && H <= G * JL && H <= 32, "one state component and JL hidden units per lane; unit bits in one word");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, g = tid & (G - 1), slot = tid >> 3, b = blockIdx.x * TPB + slot, L = k.L, T = k.T;
-  GroupLds<H> m;
-  const int LP = (L + 3) & ~3;
-  float* s_z = m.carve(smem, TPB);      // [TPB][LP]
-  float* s_times = s_z + TPB * LP;      // [T]
-  const bool live = b < k.B, own = g < S;
-  const long long bb = live ? b : 0;
-  LatentRegs<G> zr;
-  latent_request<G>(k, bb, g, L, zr);
-  UnitRegs<H> ur;
-  units_request<S, H>(k.wh, k.bh, k.wg, k.wd, k.w1, k.b1, k.times, T, s_times, L, tid, DNT, m, ur);   // every set-up operand: one round trip
-  InitRegs<S, H> ir;
-  init_request<S, H>(k.w2, k.b2, g, ir);
-  latent_store<G>(k, bb, live, g, L, LP, s_z + slot * LP, zr);
-  Units w;
-  float pre0[JL];
-  load_units<S, H>(ur, k.bg, k.bd, s_z + slot * LP, L, tid, DNT, s_times, T, m, w, pre0);
-  if (k.tabs) dump_tables<H>(k.tabs, smem, pre0, slot, g, true, tid, DNT);
-  // The controller only integrates forward in time: a grid that is not strictly increasing (torchdiffeq accepts a decreasing one by
-  // integrating in -t; this engine rejects it -- Engine.set_times raises, and a caller that comes through the bare C ABI gets NaN
-  // trajectories, hence a NaN loss, instead of a quietly extrapolated dense output) fails the solve for the whole workgroup.
-  int bad_grid = 0;
-  for (int i = tid; i + 1 < T; i += DNT) bad_grid |= !(s_times[i + 1] > s_times[i]);
-  bad_grid = __syncthreads_or(bad_grid);
-  const float t_first = s_times[0];
-  const float4* tab = m.tab + slot * (H + 1) * G;
-  const float* ctr = m.ctr + slot * 32;
-  float y = init_state<S, H>(ir, pre0, g, own);
-  const int gs = own ? g : 0;
-  float* xo = k.x + bb * T * S;
-  if (live && own) xo[gs] = y;
-  const float rtol = k.rtol, atol = k.atol;
-  float t = t_first;
-  float a, d;
-  eval_ad<H>(t, w, g, own, tab, ctr, a, d);
-  float fcur = a - d * y;
-  // Hairer's initial step (torchdiffeq _select_initial_step, order 4)
-  float dt;
-  {
-    const float sc = atol + fabsf(y) * rtol;
-    const float d0 = group_rms<S>(y / sc, own), d1 = group_rms<S>(fcur / sc, own);
-    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-    const float y1 = fmaf(h0, fcur, y);
-    eval_ad<H>(t + h0, w, g, own, tab, ctr, a, d);
-    const float f1 = a - d * y1;
-    const float d2 = group_rms<S>((f1 - fcur) / sc, own) / h0;
-    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), M::RP);
-    dt = fminf(100.f * h0, h1);
-  }
-  float* rrec = k.rec + bb * (S + 2);                      // this trajectory's record of the next accepted step
-  const long long rstride = (long long)k.B * (S + 2);
-  int j = 1;
-  int steps = bad_grid ? k.max_steps : 0, nacc = 0;
-  float tj = s_times[j < T ? j : T - 1];   // the next output time, read ahead of its use
-  // every lane leaves the loop: either all outputs written or max_steps reached (the missing outputs are then NaN).  The butterflies
-  // inside eval_ad / group_rms sit at the top level of the loop body: all 64 lanes execute them.
-  while (__any(live && j < T && steps < k.max_steps)) {
-    const bool act = live && j < T && steps < k.max_steps;
-    ++steps;
-    // The state must take the step the clock takes: t + dt is rounded to fp32, so the attempt uses that representable increment as its dt.
-    // Otherwise every accepted step advances y by dt and t by fl(t + dt) - t -- half an ulp of t apart, 1e-4 of a small step late in the
-    // grid -- and a low-order method's thousands of steps add that up to a time drift (adaptive_heun, rtol 1e-6: 2e-5 in the solution).
-    // (The expression must be evaluated as written: never build this file with -ffast-math / -fassociative-math, which fold it to dt.)
-    { const float dq = (t + dt) - t; dt = dq > 0.f ? dq : dt; }
-    // the NT evaluation times of the step are known up front: NT independent table look-ups
-    float te[M::NT];
-#pragma unroll
-    for (int i = 0; i < M::NT; ++i) te[i] = t + dt * M::C[i];
-    float av[M::NT], dv[M::NT];
-    int rv[M::NT];
-    eval_ad_batch<H, M::NT>(te, w, g, own, tab, ctr, av, dv, rv);
-    typename M::K kk;
-    float y1, e;
-    M::step(dt, y, fcur, av, dv, kk, y1, e);
-    const float ratio = group_rms_fast<S>(e * DP5_RCP(atol + rtol * fmaxf(fabsf(y), fabsf(y1))), own);
-    // a step at the resolution floor of fp32 time is accepted regardless (torchdiffeq would raise 'underflow in dt')
-    const bool accept = act && (ratio <= 1.f || dt <= 16.f * 1.1920929e-7f * fmaxf(fabsf(t), 1.f));
-    if (accept) {
-      const float t1 = t + dt;
-      if (k.rec && nacc < k.kmax) {
-        if (g == 0) { rrec[0] = t; rrec[1] = dt; }
-        if (own) rrec[2 + gs] = y;
-      }
-      rrec += rstride;   // (the record of step nacc sits at rec + (nacc B + b)(S + 2): advanced, not multiplied out, per accepted step)
-      ++nacc;
-      const float k7 = M::klast(kk);   // f(t + dt, y1): the next step's first stage
-      if (j < T && tj <= t1) {
-        const float ymid = M::ymid(dt, y, kk);
-        const float ca = 2.f * dt * (k7 - fcur) - 8.f * (y1 + y) + 16.f * ymid;
-        const float cb = dt * (5.f * fcur - 3.f * k7) + 18.f * y + 14.f * y1 - 32.f * ymid;
-        const float cc = dt * (k7 - 4.f * fcur) - 11.f * y - 5.f * y1 + 16.f * ymid;
-        const float cd = dt * fcur;
-        const float rdt = DP5_RCP(dt);
-        while (j < T && tj <= t1) {
-#ifdef SLODE_DP5_PRECISE
-          const double xq = ((double)tj - (double)t) / (double)dt;
-          if (own) xo[j * S + gs] = (float)((double)y + xq * ((double)cd + xq * ((double)cc + xq * ((double)cb + xq * (double)ca))));
-#else
-          const float xq = (tj - t) * rdt;
-          if (own) xo[j * S + gs] = y + xq * (cd + xq * (cc + xq * (cb + xq * ca)));
-#endif
-          ++j;
-          tj = s_times[j < T ? j : T - 1];
-        }
-      }
-      t = t1;
-      y = y1;
-      fcur = k7;
-    }
-    if (act) {
-      float factor;
-      if (ratio == 0.f) factor = 10.f;
-      else {
-#ifdef SLODE_DP5_PRECISE
-        const float safe = 0.9f * powf(ratio, -M::RP);
-#else
-        const float safe = 0.9f * __builtin_amdgcn_exp2f(-M::RP * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/p) (v_log_f32 is log2)
-#endif
-        factor = fminf(10.f, fmaxf(safe, ratio < 1.f ? 1.f : 0.2f));
-      }
-      dt *= factor;
-    }
-  }
-  if (live) {
-    if (k.nrec && g == 0) k.nrec[b] = (j < T) ? -1 : nacc;
-    // max_steps exhausted (or a grid the controller cannot walk): the outputs that were never reached are NaN, so every consumer --
-    // the scorer's loss with or without gradients (SVI.evaluate_loss has no backward kernel to look at nrec), a bare solve -- fails
-    // loudly instead of scoring a trajectory that was not integrated to the end
-    for (; j < T; ++j)
-      if (own) xo[j * S + gs] = __builtin_nanf("");
-  }
-}
-
-// ---- LPT = 16 / 32 / 64 lanes per trajectory (round 4) ---------------------------------------------------------------------------------
-// The eight-lanes-per-trajectory kernel above puts B = 4096 trajectories on 512 waves: half the SIMDs idle, every wave a lone dependent
-// chain of ~350 instructions per attempted step, its trip count the MAXIMUM over its eight trajectories.  Here a trajectory has NG = LPT / 8
-// lane groups, lane = 8 e + g: the step's five stage times are evaluated SIDE BY SIDE by the groups (ceil(5 / NG) table look-ups per lane
-// instead of five), gathered with ten ds_bpermute, and every group then runs the Runge-Kutta combination, the error norm and the controller
-// on the same values -- the same operations in the same order as above, so the accepted steps, the records and the outputs are bit for bit
-// those of the eight-lane kernel.  More waves (1024 / 2048 / 4096 at B = 4096) with fewer instructions each; what the measurement says
-// about the three widths is in DESIGN 3.3 (LPT = 64 turns the latency problem into an equally large throughput problem: every lane group
-// repeats the combination, and the scalar bookkeeping of 16 waves per CU saturates the issue slots).
-constexpr int WNTH = 256;         // threads per workgroup: WNTH / LPT trajectories
+// The forward solve, LPT lanes per trajectory (the mapping is at the top of the file).  What an LPT arm may differ in: how the stage values
+// reach every lane group, and which group writes which output -- never an operation on the trajectory's values or their order.
 template <class M, int S, int H, int LPT>
-__global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
+__global__ void __launch_bounds__(fwd_threads(LPT)) dopri5_fwd_kernel(const DpK k) {
   static_assert(S <= G && H <= G * JL && H <= 32, "one state component and JL hidden units per lane; unit bits in one word");
-  static_assert(LPT == 16 || LPT == 32 || LPT == 64, "lane groups of eight inside a wave");
-  constexpr int NT = M::NT, NG = LPT / G, NR = (NT + NG - 1) / NG, WTP = WNTH / LPT;   // lane groups, evaluation rounds, trajectories per workgroup
+  static_assert(LPT == 8 || LPT == 16 || LPT == 32 || LPT == 64, "lane groups of eight inside a wave");
+  constexpr int NTH = fwd_threads(LPT), WTP = NTH / LPT;              // threads, trajectories per workgroup
+  constexpr int NT = M::NT, NG = LPT / G, NR = (NT + NG - 1) / NG;    // lane groups, evaluation rounds
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, g = lane & (G - 1), e = (lane & (LPT - 1)) >> 3, slot = tid / LPT, b = blockIdx.x * WTP + slot;
   const int L = k.L, T = k.T;
@@ -801,16 +685,20 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
   LatentRegs<LPT> zr;
   latent_request<LPT>(k, bb, lane & (LPT - 1), L, zr);
   UnitRegs<H> ur;
-  units_request<S, H>(k.wh, k.bh, k.wg, k.wd, k.w1, k.b1, k.times, T, s_times, L, tid, WNTH, m, ur);
+  units_request<S, H>(k.wh, k.bh, k.wg, k.wd, k.w1, k.b1, k.times, T, s_times, L, tid, NTH, m, ur);   // every set-up operand: one round trip
   InitRegs<S, H> ir;
   init_request<S, H>(k.w2, k.b2, g, ir);
   latent_store<LPT>(k, bb, live, lane & (LPT - 1), L, LP, s_z + slot * LP, zr);
   Units w;
   float pre0[JL];
-  load_units<S, H, LPT>(ur, k.bg, k.bd, s_z + slot * LP, L, tid, WNTH, s_times, T, m, w, pre0);
-  if (LPT == 16 && k.tabs) dump_tables<H>(k.tabs, smem, pre0, slot, g, e == 0, tid, WNTH);   // (sixteen trajectories per workgroup, as the reverse sweep)
+  load_units<S, H, LPT>(ur, k.bg, k.bd, s_z + slot * LP, L, tid, NTH, s_times, T, m, w, pre0);
+  // the tables go to the reverse sweep where a workgroup holds the reverse sweep's sixteen trajectories (tab_floats)
+  if (WTP == 16 && k.tabs) dump_tables<H>(k.tabs, smem, pre0, slot, g, e == 0, tid, NTH);
+  // The controller only integrates forward in time: a grid that is not strictly increasing (torchdiffeq accepts a decreasing one by
+  // integrating in -t; this engine rejects it -- Engine.set_times raises, and a caller that comes through the bare C ABI gets NaN
+  // trajectories, hence a NaN loss, instead of a quietly extrapolated dense output) fails the solve for the whole workgroup.
   int bad_grid = 0;
-  for (int i = tid; i + 1 < T; i += WNTH) bad_grid |= !(s_times[i + 1] > s_times[i]);
+  for (int i = tid; i + 1 < T; i += NTH) bad_grid |= !(s_times[i + 1] > s_times[i]);
   bad_grid = __syncthreads_or(bad_grid);
   const float t_first = s_times[0];
   const float4* tab = m.tab + slot * (H + 1) * G;
@@ -842,9 +730,9 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
   int j = 1;
   int steps = bad_grid ? k.max_steps : 0, nacc = 0;
   float tj = s_times[j < T ? j : T - 1];   // the next output time, read ahead of its use
-  float tj1 = s_times[min(j + 1, T - 1)];  // (sixteen lanes per trajectory: and the one after)
+  float tj1 = s_times[min(j + 1, T - 1)];  // (two lane groups: and the one after; unused, hence not read, at the other widths)
   // new stage time i (dopri5: t + dt {1/5, 3/10, 4/5, 8/9, 1}; stages 6 and 7 share the last) is evaluated by lane group i % NG in round i / NG
-  const int base = ((lane & ~(LPT - 1)) + g) << 2;   // ds_bpermute byte index of lane (this trajectory, group 0, component g)
+  const int base = ((lane & ~(LPT - 1)) + g) << 2;   // ds_bpermute byte index of lane (this trajectory, group 0, component g); four and eight groups
   // every lane leaves the loop: either all outputs written or max_steps reached (the missing outputs are then NaN).  The butterflies inside
   // eval_ad / group_rms and the gathers sit at the top level of the loop body: all 64 lanes execute them.
   while (__any(live && j < T && steps < k.max_steps)) {
@@ -855,6 +743,7 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
     // grid -- and a low-order method's thousands of steps add that up to a time drift (adaptive_heun, rtol 1e-6: 2e-5 in the solution).
     // (The expression must be evaluated as written: never build this file with -ffast-math / -fassociative-math, which fold it to dt.)
     { const float dq = (t + dt) - t; dt = dq > 0.f ? dq : dt; }
+    // the NT evaluation times of the step are known up front: NT independent table look-ups, NR per lane group
     float te5[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) te5[i] = t + dt * M::C[i];
@@ -870,7 +759,11 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
     }
     eval_ad_batch<H, NR>(ter, w, g, own, tab, ctr, ar, dr, rr);   // the rounds' table reads in one batch (one LDS round trip per attempt)
     float av[NT], dv[NT];
-    if (LPT == 16) {
+    if (NG == 1) {
+      // one lane group evaluated every stage time itself
+#pragma unroll
+      for (int i = 0; i < NT; ++i) { av[i] = ar[i]; dv[i] = dr[i]; }
+    } else if (NG == 2) {
       // two lane groups = the two halves of a DPP row: the other group's value is one row rotation by eight lanes away (no LDS round trip)
 #pragma unroll
       for (int r = 0; r < NT / 2; ++r) {
@@ -899,7 +792,7 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
         if (g == 0) { rrec[0] = t; rrec[1] = dt; }
         if (own) rrec[2 + gs] = y;
       }
-      rrec += rstride;
+      rrec += rstride;   // (the record of step nacc sits at rec + (nacc B + b)(S + 2): advanced, not multiplied out, per accepted step)
       ++nacc;
       const float k7 = M::klast(kk);   // f(t + dt, y1): the next step's first stage
       if (j < T && tj <= t1) {
@@ -909,34 +802,22 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
         const float cc = dt * (k7 - 4.f * fcur) - 11.f * y - 5.f * y1 + 16.f * ymid;
         const float cd = dt * fcur;
         const float rdt = DP5_RCP(dt);
-        if (LPT == 16) {
+        if (NG == 2) {
           // the step's outputs two at a time: lane group e evaluates and writes output j + e (half the trips of the one-at-a-time loop)
           while (j < T && tj <= t1) {
             const float tq = e ? tj1 : tj;
             const bool in = j + e < T && tq <= t1;
-#ifdef SLODE_DP5_PRECISE
-            const double xq = ((double)tq - (double)t) / (double)dt;
-            if (own && in) xo[(j + e) * S + gs] = (float)((double)y + xq * ((double)cd + xq * ((double)cc + xq * ((double)cb + xq * (double)ca))));
-#else
-            const float xq = (tq - t) * rdt;
-            if (own && in) xo[(j + e) * S + gs] = y + xq * (cd + xq * (cc + xq * (cb + xq * ca)));
-#endif
+            if (own && in) xo[(j + e) * S + gs] = dense_eval(tq, t, dt, rdt, y, ca, cb, cc, cd);
             j += (j + 1 < T && tj1 <= t1) ? 2 : 1;
             tj = s_times[min(j, T - 1)];
             tj1 = s_times[min(j + 1, T - 1)];
           }
         } else {
-        while (j < T && tj <= t1) {
-#ifdef SLODE_DP5_PRECISE
-          const double xq = ((double)tj - (double)t) / (double)dt;
-          if (wr) xo[j * S + gs] = (float)((double)y + xq * ((double)cd + xq * ((double)cc + xq * ((double)cb + xq * (double)ca))));
-#else
-          const float xq = (tj - t) * rdt;
-          if (wr) xo[j * S + gs] = y + xq * (cd + xq * (cc + xq * (cb + xq * ca)));
-#endif
-          ++j;
-          tj = s_times[j < T ? j : T - 1];
-        }
+          while (j < T && tj <= t1) {
+            if (wr) xo[j * S + gs] = dense_eval(tj, t, dt, rdt, y, ca, cb, cc, cd);
+            ++j;
+            tj = s_times[j < T ? j : T - 1];
+          }
         }
       }
       t = t1;
@@ -946,20 +827,16 @@ __global__ void __launch_bounds__(WNTH) dopri5_lpt_kernel(const DpK k) {
     if (act) {
       float factor;
       if (ratio == 0.f) factor = 10.f;
-      else {
-#ifdef SLODE_DP5_PRECISE
-        const float safe = 0.9f * powf(ratio, -M::RP);
-#else
-        const float safe = 0.9f * __builtin_amdgcn_exp2f(-M::RP * __builtin_amdgcn_logf(ratio));   // 0.9 ratio^(-1/p) (v_log_f32 is log2)
-#endif
-        factor = fminf(10.f, fmaxf(safe, ratio < 1.f ? 1.f : 0.2f));
-      }
+      else factor = fminf(10.f, fmaxf(safe_factor(ratio, M::RP), ratio < 1.f ? 1.f : 0.2f));
       dt *= factor;
     }
   }
   if (live) {
     if (k.nrec && (lane & (LPT - 1)) == 0) k.nrec[b] = (j < T) ? -1 : nacc;
-    for (; j < T; ++j)   // max_steps exhausted (or a grid the controller cannot walk): the outputs that were never reached are NaN
+    // max_steps exhausted (or a grid the controller cannot walk): the outputs that were never reached are NaN, so every consumer --
+    // the scorer's loss with or without gradients (SVI.evaluate_loss has no backward kernel to look at nrec), a bare solve -- fails
+    // loudly instead of scoring a trajectory that was not integrated to the end
+    for (; j < T; ++j)
       if (wr) xo[j * S + gs] = __builtin_nanf("");
   }
 }
@@ -1671,35 +1548,28 @@ int slode_dopri5_kmax(const slode_shape& s) {
   return (int)(kmax < 64 ? 64 : (kmax > 2048 ? 2048 : kmax));
 }
 
-// (S, H) in {(5, 25), (8, 25)}.  dopri5: 8, 16, 32 or 64 lanes per trajectory; the small pairs: 8 or 16 (hipErrorNotSupported otherwise --
-// slode_dp5_lanes_ok refuses the rest before anything is launched)
-template <class M>
-static hipError_t launch_fwd(const slode_shape& s, const DpK& k, int lpt, hipStream_t stream) {
-  if (lpt == 16 || lpt == 32 || lpt == 64) {
-    const int wtp = WNTH / lpt, grid = (s.B + wtp - 1) / wtp;
-    const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(wtp) + (size_t)wtp * ((s.L + 3) & ~3) + (size_t)s.T);
-#define SLODE_DP5_LPT(SS, LL) SLODE_LAUNCH("dopri5_fwd", (dopri5_lpt_kernel<M, SS, 25, LL>), dim3(grid), dim3(WNTH), lds, stream, k)
-    if constexpr (M::method == SLODE_DOPRI5) {
-      if (s.S == 5) { if (lpt == 16) SLODE_DP5_LPT(5, 16); else if (lpt == 32) SLODE_DP5_LPT(5, 32); else SLODE_DP5_LPT(5, 64); }
-      else { if (lpt == 16) SLODE_DP5_LPT(8, 16); else if (lpt == 32) SLODE_DP5_LPT(8, 32); else SLODE_DP5_LPT(8, 64); }
-    } else {
-      if (lpt != 16) return hipErrorNotSupported;
-      if (s.S == 5) SLODE_DP5_LPT(5, 16); else SLODE_DP5_LPT(8, 16);
-    }
-#undef SLODE_DP5_LPT
-    return hipGetLastError();
-  }
-  if (lpt != 8) return hipErrorNotSupported;
-  const int grid = (s.B + TPB - 1) / TPB;
-  const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(TPB) + (size_t)TPB * ((s.L + 3) & ~3) + (size_t)s.T);
-  if (s.S == 5) SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<M, 5, 25>), dim3(grid), dim3(DNT), lds, stream, k);
-  else SLODE_LAUNCH("dopri5_fwd", (dopri5_kernel<M, 8, 25>), dim3(grid), dim3(DNT), lds, stream, k);
-  return hipGetLastError();
-}
-
+// dopri5: 8, 16, 32 or 64 lanes per trajectory; the small pairs: 8 or 16 (the callers refuse the rest before anything is launched)
 int slode_dp5_lanes_ok(int method, int lpt) {
   if (lpt == 8 || lpt == 16) return 1;
   return method == SLODE_DOPRI5 && (lpt == 32 || lpt == 64);
+}
+
+// (S, H) in {(5, 25), (8, 25)}; a width the method does not have: hipErrorNotSupported
+template <class M>
+static hipError_t launch_fwd(const slode_shape& s, const DpK& k, int lpt, hipStream_t stream) {
+  if (!slode_dp5_lanes_ok(M::method, lpt)) return hipErrorNotSupported;
+  const int nth = fwd_threads(lpt), wtp = nth / lpt, grid = (s.B + wtp - 1) / wtp;
+  const size_t lds = sizeof(float) * ((size_t)GroupLds<25>::floats(wtp) + (size_t)wtp * ((s.L + 3) & ~3) + (size_t)s.T);
+#define SLODE_DP5_FWD(SS, LL) SLODE_LAUNCH("dopri5_fwd", (dopri5_fwd_kernel<M, SS, 25, LL>), dim3(grid), dim3(nth), lds, stream, k)
+#define SLODE_DP5_FWD_S(LL) do { if (s.S == 5) SLODE_DP5_FWD(5, LL); else SLODE_DP5_FWD(8, LL); } while (0)
+  if (lpt == 8) SLODE_DP5_FWD_S(8);
+  else if (lpt == 16) SLODE_DP5_FWD_S(16);
+  else if constexpr (M::method == SLODE_DOPRI5) {   // (the widths only dopri5 has: slode_dp5_lanes_ok)
+    if (lpt == 32) SLODE_DP5_FWD_S(32); else SLODE_DP5_FWD_S(64);
+  }
+#undef SLODE_DP5_FWD_S
+#undef SLODE_DP5_FWD
+  return hipGetLastError();
 }
 
 hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, const float* p, const float* times, const float* z,
@@ -1716,7 +1586,7 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
   k.rtol = s.rtol > 0.f ? s.rtol : 1e-7f;
   k.atol = s.atol > 0.f ? s.atol : 1e-9f;
   k.max_steps = 20000;
-  const int lpt = rec ? rec->w64 : 8;    // lanes per trajectory of the forward solve: 8 (the round-2 kernel), 16, 32 or 64 -- all the same bits
+  const int lpt = rec ? rec->w64 : 8;    // lanes per trajectory of the forward solve: 8, 16, 32 or 64 -- all the same bits
   if (s.H != 25 || (s.S != 5 && s.S != 8)) return hipErrorInvalidValue;
   switch (s.method) {
     case SLODE_DOPRI5: return launch_fwd<Dopri5>(s, k, lpt, stream);

@@ -881,7 +881,7 @@ hipError_t slode_launch_dynamics_eval(const slode_shape& s, const slode_layout& 
 // adaptive solve with step records (training): z = loc + scale * eps is formed in the kernel and written to z_out
 // rng.on: eps is drawn by the forward kernel and written to eps_out, which the scorer and the reverse sweep then read as `eps`
 struct DopriRec { const float *loc, *scale, *eps; float* z_out; float* rec; int* nrec; int kmax; RngK rng{}; float* eps_out = nullptr;
-                  int w64 = 8;   // lanes per trajectory of the forward solve: 8 (dopri5_kernel), 16 / 32 / 64 (dopri5_lpt_kernel); SLODE_DP5_LPT
+                  int w64 = 8;   // lanes per trajectory of the forward solve (dopri5_fwd_kernel's LPT): 8, 16, 32 or 64; SLODE_DP5_LPT
                   float* tabs = nullptr;   // [rows][slode_dopri5_tab_floats]: the forward kernel's per-workgroup tables, handed to the reverse sweep
                   int data_rows = 0;       // particles: the shape's B counts K * data_rows virtual trajectories (0: B data rows, one particle);
                                            // loc / scale (and the reverse sweep's enc_hid) have data_rows rows, everything else B

@@ -251,7 +251,7 @@ def main_step(p, spec, obs, u, eps, times):
 
 
 # ---- adaptive Dormand-Prince: per-trajectory controller with step records, and the reverse sweep over the records -----------
-# (csrc/dopri5_kernel.hip: dopri5_kernel / dopri5_bwd_kernel; one trajectory at a time here)
+# (csrc/dopri5_kernel.hip: dopri5_fwd_kernel / dopri5_bwd_kernel; one trajectory at a time here)
 _DP_A = [[1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
          [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]]
 _DP_C = [0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0]                      # six distinct stage times (stages 6 and 7 share t + dt)

@@ -135,7 +135,7 @@ def test_elbo_step_against_oracle(method, mode):
 @pytest.mark.parametrize("fam", ["cvs", "proc"])
 @pytest.mark.parametrize("method", NEW)
 def test_sixteen_lanes_equal_eight_lanes_bitwise(method, fam, monkeypatch):
-    """The 16-lane forward kernel against the 8-lane one (SLODE_DP5_LPT=8, read in slode_create): trajectories, step counts, -ELBO and
+    """The forward kernel (dopri5_fwd_kernel) at 16 lanes per trajectory against 8 (SLODE_DP5_LPT=8, read in slode_create): trajectories, step counts, -ELBO and
     every gradient element bit for bit.  SLODE_DP5_LPT=32 / 64 are dopri5 only: the step refuses them for the new methods."""
     from structured_latent_odes_amd._lib import SlodeError
     dev = torch.device("cuda:0")

@@ -513,8 +513,8 @@ def test_dopri5_elbo_step_at_default_tolerances(fam, mode):
 @pytest.mark.parametrize("fam", ["cvs", "proc"])
 def test_dopri5_wider_lane_groups_equal_the_eight_lane_kernel_bitwise(fam, lpt, monkeypatch):
     """Round 4: the forward adaptive solve with 16 / 32 / 64 lanes per trajectory (lane = stage evaluation x state component: the stage times
-    of a step side by side, dopri5_lpt_kernel) instead of eight.  Same operations in the same order: trajectories, step counts, -ELBO and
-    every gradient element are bit for bit those of the eight-lane kernel (SLODE_DP5_LPT=8), in the bare solve and in the training step;
+    of a step side by side, dopri5_fwd_kernel's LPT) instead of eight.  Same operations in the same order: trajectories, step counts, -ELBO and
+    every gradient element are bit for bit those of the same kernel at eight lanes (SLODE_DP5_LPT=8), in the bare solve and in the training step;
     ragged batch (B not a multiple of the trajectories per workgroup)."""
     from structured_latent_odes_amd import engine as E
     dev = torch.device("cuda:0")

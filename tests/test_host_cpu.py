@@ -154,6 +154,28 @@ def test_no_kernel_spills_or_parks_registers():
     assert "no VGPR spills, no AGPR parking" in r.stdout
 
 
+def test_clock_tools_find_their_anchors_in_the_dopri5_source():
+    """tools/dp5_fwd_clk_build.py and tools/dp5_clk_build.py put cycle stamps into dopri5_kernel.hip by replacing lines of its text: every
+    such line must still be in the source (the patch step asserts each one and needs no compiler), and the build step must take its
+    sources and flags from csrc/Makefile -- a hand-kept list went stale without anybody noticing."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    try:
+        import dp5_clk_build
+        import dp5_fwd_clk_build
+    finally:
+        sys.path.pop(0)
+    src = dp5_clk_build.kernel_source()
+    for tool, stamps in ((dp5_fwd_clk_build, ("CLK(8)", "acc[5] += c1 - c0", "dp5fwd lpt %d wg %d")), (dp5_clk_build, ("CLK();", "dp5bwd wg %d K %d"))):
+        text = tool.patched_source()
+        assert len(text) > len(src) and all(s in text and s not in src for s in stamps), tool.__name__
+    _, flags, srcs = dp5_clk_build.makefile_build()
+    mk = open(os.path.join(root, "structured_latent_odes_amd", "csrc", "Makefile")).read()
+    assert dp5_clk_build.KERNEL in srcs and all(f in mk for f in srcs) and "--offload-arch=gfx950" in flags and "-ffp-contract=on" in flags
+    assert sorted(srcs) == sorted(f for f in os.listdir(os.path.join(root, "structured_latent_odes_amd", "csrc")) if f.endswith(".hip") and not f.startswith("_"))
+
+
 def test_chain_hand_off_is_write_through_in_the_isa():
     """enc_chain_kernel hands its per-unit conv rows to the last block to arrive with RELAXED agent-scope atomics: sc1 (write-through)
     stores, drained before the arrival count, and sc1 (L1-bypassing) loads in the reader -- no acquire fence on the fast path

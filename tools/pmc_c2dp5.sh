@@ -17,7 +17,7 @@ for sub in ("sq", "mem"):
     for f in fs:
         for r in csv.DictReader(open(f)):
             full = r["Kernel_Name"]
-            kn = next((x for x in ("ode_elbo_kernel", "dopri5_kernel", "dopri5_lpt_kernel", "dopri5_bwd_kernel", "enc_fwd2_kernel", "weff_kernel", "enc_bwd_lin", "gemm", "enc_chain_kernel") if x in full), full[:40])
+            kn = next((x for x in ("ode_elbo_kernel", "dopri5_fwd_kernel", "dopri5_bwd_kernel", "enc_fwd2_kernel", "weff_kernel", "enc_bwd_lin", "gemm", "enc_chain_kernel") if x in full), full[:40])
             acc[kn][r["Counter_Name"]].append(float(r["Counter_Value"]))
     print("==", sub)
     for kn, d in acc.items():
