@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 280 /* 0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels (0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 290 /* 0.2.9: slode_pointwise_loo, slode_loo_plan (0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels; 0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -505,6 +505,41 @@ int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_la
                             float* summary /* [B, SLODE_POINTWISE_SLOTS] */, float* loss_kb /* [num_draws, B] or NULL */, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- PSIS leave-one-out: per-point elpd_loo and the Pareto khat from K latent draws as ONE call (no reference counterpart; the remedy for the
+ * points where WAIC's p_waic is large, and the per-point diagnostic of whether a model comparison can be trusted: Vehtari, Gelman & Gabry 2017) ----
+ * l_k[i] is slode_pointwise_density's per-draw log-density of point i = (c, t); posterior weights only.  The importance ratio of draw k for
+ * leaving out point i is 1 / p(y_i | z_k).  point [3, B, C, T] holds the planes
+ *   point[0] elpd_loo[i] = log sum_k w_k exp(l_k[i]), w_k the normalised Pareto-smoothed ratios
+ *   point[1] khat[i]     = the fitted shape of the generalised Pareto tail; +inf where no smoothing was possible
+ *   point[2] lppd[i]     = bit for bit plane 0 of slode_pointwise_density(SLODE_PW_POSTERIOR) on the same inputs and noise
+ * per point: M = min(ceil(min(0.2 K, 3 sqrt K)), K - 1) (host, fp64); sorted l_(0) <= l_(1) <= ..., a_(j) = l_(0) - l_(j), cut = max(a_(M), log
+ * DBL_MIN); the tail is the ranks j < M with a_(j) > cut strictly, n of them; n < 5: no smoothing, khat = +inf.  Else x = exp(a) - exp(cut) over
+ * the tail, ascending; the generalised Pareto fit of Zhang & Stephens (2009) on m = 30 + floor(sqrt n) grid points with the prior of Vehtari et
+ * al. (khat = (n k + 5) / (n + 10)); the tail's log-ratios replaced in rank order by s_j = min(log(sigma expm1(-khat log1p(-p_j)) / khat +
+ * exp(cut)), 0), p_j = (j - 0.5) / n; a non-finite fit leaves the tail and gives khat = +inf.  Then
+ *   elpd_loo = log((K - n) e^{l_(0)} + sum_j e^{s_j + l_(j)}) - log(sum_{not tail} e^{a_k} + sum_j e^{s_j}).
+ * All of this runs in fp64 on chip, from the M + 1 smallest l_k of the point, which the kernel keeps sorted (tail_out, or NULL: [M + 1, B, C, T],
+ * ascending along the first axis); sum_{not tail} e^{a_k} is the kept non-tail ranks in fp64 plus an fp32 running logsumexp(-l_k) over the K - M - 1
+ * draws outside the kept values (no difference of sums: at khat > 1 one ratio dominates the total).
+ * tile: time points per sweep over the draws (0: the fewest sweeps whose tables fit the LDS budget of 160 KiB; slode_loo_plan reports the
+ * choice, the sweeps, the depth M + 1 and the LDS bytes: host arithmetic only).  Every sweep redraws the same noise and solves the whole grid: the
+ * outputs are bitwise independent of the tile, the grid and of where the noise comes from.  mask, loc / scale, batch->eps, the counter (n -> n + K,
+ * once): as slode_pointwise_density in posterior mode; the mask partitions the summary and never touches the planes.  summary [B, SLODE_LOO_SLOTS],
+ * 16-byte aligned, fp64 sums of the written plane values in a fixed order that depends on (C, T) alone, rounded once:
+ *   [0] sum_in elpd_loo   [1] sum_in lppd   [2] n_in   [3] #in{khat > 0.7} (+inf counts)   [4] max_in khat (-inf: no point in)
+ *   [5] sum_out elpd_loo  [6] sum_out lppd  [7] n_out
+ * No atomics.  Enqueue only; capturable as a linear graph.  Three launches ("weff", "enc_fwd2", "pointwise_loo" in slode_profile_read).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written: everything slode_pointwise_density
+ * refuses in posterior mode up to the observation strides; then point or summary NULL, summary not 16-byte aligned; exactly one of loc / scale;
+ * tile < 0 or > T; a tile, or a num_draws, whose tables do not fit the LDS.  The model layer composes where the call refuses. */
+#define SLODE_LOO_SLOTS 8
+int slode_loo_plan(const slode_shape* s, int num_draws, int tile, int* tile_out, int* sweeps, int* depth, size_t* lds_bytes);
+int slode_pointwise_loo(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                        const float* stage_t, const slode_batch* batch, int num_draws, const float* mask /* as batch->obs, or NULL */,
+                        const float* loc /* [B, L] or NULL */, const float* scale /* [B, L] or NULL */, int tile,
+                        float* point /* [3, B, C, T]: elpd_loo | khat | lppd */, float* summary /* [B, SLODE_LOO_SLOTS] */,
+                        float* tail_out /* [M + 1, B, C, T] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- counterfactual curves as ONE call (no reference counterpart: the reference's recon takes the whole latent from the posterior or the whole
  * latent from the conditional prior; the structured latent exists to ask "what would THIS subject's curves have looked like under THAT input?") ----
  * For trajectory b and draw k, with ONE noise row eps[k][b][0..L) shared by both arms:
@@ -971,11 +1006,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration / slode_joint_band launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_pointwise_loo / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration / slode_joint_band launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "pointwise_loo", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

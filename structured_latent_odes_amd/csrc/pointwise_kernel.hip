@@ -57,12 +57,7 @@ __device__ __forceinline__ void pw_fold_points(const FwdSm& sm, int S, int T, in
     for (int c = 0; c < C; ++c) {
       const int i = c * T + t;
       const float obv = s_obs[i], inv = s_inv[i], lg = s_lg[i];
-      float l = 0.f;
-      for (int q = 0; q < Q; ++q) {
-        const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
-        if (gauss) l += -lg - TB_HL2PI - 0.5f * r * r * inv * inv;
-        else l += ((obv >= mu) ? tau[q] : 1.f - tau[q]) * (-lg - fabsf(r) * inv);
-      }
+      const float l = tb_point_loglik<SM>(sm, S, C, Q, c, gauss, tau, obv, inv, lg, x);
       const float a = lw + l;
       if (first) { s_pm[i] = a; s_ps[i] = 1.f; s_p0[i] = l; s_s1[i] = 0.0; s_s2[i] = 0.0; }
       else {

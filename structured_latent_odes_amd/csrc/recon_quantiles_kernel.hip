@@ -36,25 +36,6 @@ struct RqK {
   RqLds o;
 };
 
-// one value into a sorted buffer of depth m (slot stride P) that holds min(kk, m) values: BOTTOM: the smallest so far, ascending; else the
-// largest so far, descending
-template <bool BOTTOM>
-__device__ __forceinline__ void rq_insert(float* buf, int P, int m, int kk, float v) {
-  int j = kk;
-  if (kk >= m) {
-    const float last = buf[(m - 1) * P];
-    if (!(BOTTOM ? v < last : v > last)) return;
-    j = m - 1;
-  }
-  while (j > 0) {
-    const float prev = buf[(j - 1) * P];
-    if (!(BOTTOM ? prev > v : prev < v)) break;
-    buf[j * P] = prev;
-    --j;
-  }
-  buf[j * P] = v;
-}
-
 // M7 of one level: the interpolation with its operation order pinned -- the difference rounded on its own, then one fma -- so that the result
 // is bitwise the numpy restatement (tests/quantile_util.py: select), whatever the compiler would fuse
 __device__ __forceinline__ float rq_lerp(float v_lo, float v_hi, float g) {
@@ -99,8 +80,8 @@ __global__ void __launch_bounds__(RQ_NT) recon_quantiles_kernel(const RqK k) {
           for (int qc = 0; qc < QC; ++qc) {
             const float v = fwd_head_value<SM>(sm, S, qc, x);
             float* col = s_buf + qc * tile + tl;
-            rq_insert<true>(col, P, m_lo, kk, v);
-            if (m_hi > 0) rq_insert<false>(col + m_lo * P, P, m_hi, kk, v);
+            fwd_sorted_insert<true>(col, P, m_lo, kk, v);
+            if (m_hi > 0) fwd_sorted_insert<false>(col + m_lo * P, P, m_hi, kk, v);
           }
         }
       }

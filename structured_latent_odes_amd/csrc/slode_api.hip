@@ -1228,6 +1228,77 @@ int slode_pointwise_density(slode_handle h, const slode_shape* s, const slode_la
                     [&](hipStream_t st) { return slode_launch_pointwise(a, st); });
 }
 
+// ---- PSIS leave-one-out: the draws of slode_pointwise_density in posterior mode, the smoothed leave-one-out estimate per point (include/slode.h) ----
+// The tail-length, depth and tile rules as data: what the plan reports and the launch takes.  why: the refusal.
+struct LooPlan { int tile, sweeps, depth; size_t lds; };
+static int loo_plan(const slode_shape& s, int K, int tile, int force_generic, LooPlan* p, char* why, size_t why_n) {
+  if (K < 1) { snprintf(why, why_n, "num_draws = %d < 1", K); return SLODE_EINVAL; }
+  if (tile < 0 || tile > s.T) { snprintf(why, why_n, "tile = %d out of range [0, T = %d] (0: the library chooses)", tile, s.T); return SLODE_EINVAL; }
+  // M = min(ceil(min(0.2 K, 3 sqrt K)), K - 1) in fp64; the kernel keeps the M + 1 smallest log-densities of every point
+  const double mk = std::ceil(std::fmin(0.2 * (double)K, 3.0 * std::sqrt((double)K)));
+  const int M = mk < (double)(K - 1) ? (int)mk : K - 1, D = M + 1;
+  p->depth = D;
+  const size_t budget = SLODE_LOO_LDS_MAX;
+  auto bytes = [&](int tl) { return slode_pointwise_loo_lds_bytes(s, D, tl, force_generic); };
+  int tl = tile;
+  if (tile > 0) {
+    if (bytes(tl) > budget) {
+      snprintf(why, why_n, "tile = %d does not fit: the LDS tables of T = %d, S = %d, C = %d, num_draws = %d (%zu B: step table, observations, mask, staged "
+               "weights, per point of the tile two (max, sum) pairs and the %d smallest log-densities) exceed the budget of %zu B; pass tile = 0 to let the "
+               "library choose", tl, s.T, s.S, s.C, K, bytes(tl), D, budget);
+      return SLODE_EINVAL;
+    }
+  } else {
+    if (bytes(1) > budget) {
+      snprintf(why, why_n, "num_draws = %d keeps the %d smallest log-densities of every point: the tables of one time point [%d][%d] do not fit beside the "
+               "step table and the observations of T = %d, S = %d, C = %d (%zu B of a budget of %zu B); fewer draws or a shorter window fit", K, D, D + 4, s.C,
+               s.T, s.S, s.C, bytes(1), budget);
+      return SLODE_EINVAL;
+    }
+    for (int sw = 1;; ++sw) {   // the fewest sweeps that fit (sw = T: tile = 1 fits)
+      tl = (s.T + sw - 1) / sw;
+      if (bytes(tl) <= budget) break;
+    }
+  }
+  p->tile = tl; p->sweeps = (s.T + tl - 1) / tl; p->lds = bytes(tl);
+  return SLODE_OK;
+}
+
+// The plan of slode_pointwise_loo for a shape and a draw count (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
+// SLODE_EINVAL where the call would refuse them at its own rungs.
+int slode_loo_plan(const slode_shape* s, int num_draws, int tile, int* tile_out, int* sweeps, int* depth, size_t* lds_bytes) {
+  if (int rc = plan_open("slode_loo_plan", s, !tile_out || !sweeps || !depth || !lds_bytes, "tile_out / sweeps / depth / lds_bytes")) return rc;
+  LooPlan p{};
+  char why[512];
+  if (loo_plan(*s, num_draws, tile, 0, &p, why, sizeof(why)) != SLODE_OK) return fail(nullptr, SLODE_EINVAL, "slode_loo_plan: %s", why);
+  *tile_out = p.tile; *sweeps = p.sweeps; *depth = p.depth; *lds_bytes = p.lds;
+  return SLODE_OK;
+}
+
+// Per-point PSIS leave-one-out elpd, Pareto khat and lppd over num_draws posterior draws, and their per-trajectory sums (include/slode.h):
+// slode_pointwise_density's refusals in posterior mode through the same ladder, then the call's own (point / summary, loc / scale, the plan's
+// refusal as the LDS rung) -- nothing launched, no draw consumed -- then its launches with the leave-one-out kernel in place of its own.  The
+// noise rows are counted once: num_draws drawing calls, whatever the number of sweeps.
+int slode_pointwise_loo(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times, const float* stage_t,
+                        const slode_batch* batch, int num_draws, const float* mask, const float* loc, const float* scale, int tile, float* point,
+                        float* summary, float* tail_out, void* workspace, size_t workspace_bytes, void* stream) {
+  const ScoredCall d("slode_pointwise_loo", "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_draws);
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
+  if (!point || !summary || ((uintptr_t)summary & 15) != 0)
+    return fail(h, SLODE_EINVAL, "slode_pointwise_loo: point / summary is NULL, or summary is not 16-byte aligned");
+  if ((loc == nullptr) != (scale == nullptr))
+    return fail(h, SLODE_EINVAL, "slode_pointwise_loo: loc and scale replace the posterior together (%s is NULL)", loc ? "scale" : "loc");
+  LooPlan p{};
+  char why[512];
+  if (loo_plan(*s, num_draws, tile, h->ode_generic, &p, why, sizeof(why)) != SLODE_OK) return fail(h, SLODE_EINVAL, "slode_pointwise_loo: %s", why);
+  PointwiseLooLaunch a{};
+  a.d.mask = mask; a.d.loc = loc; a.d.scale = scale;   // (both or neither: scored_run keeps them)
+  a.point = point; a.summary = summary; a.tail_out = tail_out; a.tile = p.tile; a.depth = p.depth;
+  return scored_run(h, s, lay, d, a.d, params, times, stage_t, batch, workspace, workspace_bytes, stream, "slode_launch_pointwise_loo(a, c.stream)",
+                    [&](hipStream_t st) { return slode_launch_pointwise_loo(a, st); });
+}
+
 // Paired-draw moments of the counterfactual curves and of their difference to the factual ones (include/slode.h): refusals first -- nothing
 // launched, no draw consumed -- then the fold + encoder launches of a forward-only step, then the one kernel that walks the draws of its
 // trajectories through both arms.

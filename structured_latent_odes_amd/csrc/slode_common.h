@@ -682,6 +682,19 @@ struct PointwiseLaunch {
 hipError_t slode_launch_pointwise(const PointwiseLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
 size_t slode_pointwise_lds_bytes(const slode_shape& s, int num_draws, int weights, int force_generic);
 
+// PSIS leave-one-out (pointwise_loo_kernel.hip; slode_pointwise_loo): per point elpd_loo / khat / lppd over the draws of d (posterior weights),
+// point [3, B, C, T], per trajectory summary [B, SLODE_LOO_SLOTS] (16-byte aligned), tail_out [depth, B, C, T] or NULL: the depth = M + 1
+// smallest per-draw log-densities of every point, ascending.  tile: time points per sweep over the draws (1 <= tile <= T).  depth and tile from
+// loo_plan (slode_api.hip).
+struct PointwiseLooLaunch {
+  ScoredLaunch d;
+  float *point, *summary, *tail_out;
+  int tile, depth;
+};
+#define SLODE_LOO_LDS_MAX (160 * 1024)   // the LDS of one CU: step table, observations, mask, staged weights, and per point of a tile the two (max, sum) pairs and the M + 1 kept values must fit
+hipError_t slode_launch_pointwise_loo(const PointwiseLooLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_pointwise_loo_lds_bytes(const slode_shape& s, int depth, int tile, int force_generic);
+
 // Counterfactual curves (intervene_moments_kernel.hip; slode_intervene_moments): over the paired posterior draws of d (is_post = 1; u unread, lab:
 // the batch's own labels, which the encoder launch takes) per trajectory, mean / sd [Q, B, C, T] of the curve under swapped labels and of its
 // difference to the factual curve; each of the four outputs may be NULL.  cf: the counterfactual label tensors (read in the columns of the

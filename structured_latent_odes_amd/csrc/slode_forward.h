@@ -417,6 +417,25 @@ __device__ __forceinline__ void fwd_moment_store_pinned(const float* m, int P, f
   }
 }
 
+// one value into a sorted LDS buffer of depth m (slot stride P) that holds min(kk, m) values: BOTTOM: the smallest so far, ascending; else the
+// largest so far, descending (recon_quantiles_kernel's M6, pointwise_loo_kernel's tail buffer)
+template <bool BOTTOM>
+__device__ __forceinline__ void fwd_sorted_insert(float* buf, int P, int m, int kk, float v) {
+  int j = kk;
+  if (kk >= m) {
+    const float last = buf[(m - 1) * P];
+    if (!(BOTTOM ? v < last : v > last)) return;
+    j = m - 1;
+  }
+  while (j > 0) {
+    const float prev = buf[(j - 1) * P];
+    if (!(BOTTOM ? prev > v : prev < v)) break;
+    buf[j * P] = prev;
+    --j;
+  }
+  buf[j * P] = v;
+}
+
 // ---- launch ---------------------------------------------------------------------------------------------------------
 // the run-time-S instantiation serves every state dim without a compiled one, and every shape under SLODE_ODE_GENERIC
 inline bool fwd_generic(const slode_shape& s, int force_generic) { return force_generic || !(s.S == 5 || s.S == 8); }

@@ -1,5 +1,5 @@
 // What the kernels that score the K latent draws of a trajectory share (traj_bounds_kernel and label_evidence_kernel in traj_bounds_kernel.hip,
-// pointwise_kernel.hip, refine_kernel.hip), each piece ONCE: the kernel-argument part ScoredK and its fill from ScoredLaunch, the
+// pointwise_kernel.hip, pointwise_loo_kernel.hip, refine_kernel.hip), each piece ONCE: the kernel-argument part ScoredK and its fill from ScoredLaunch, the
 // LDS pieces of the frame (scored_lds / scored_sm), the staging of the scale table and of a trajectory's observations (and mask), the
 // posterior and prior of a latent dim, and the per-draw routines: log q - log p of a latent dim, the log-likelihood of a thread's time
 // points (plain and weighted), the label log-probability of a head, the workgroup sums that form a draw's loss, the whole draw loop of
@@ -155,6 +155,20 @@ __device__ __forceinline__ float tb_loglik_points(const FwdSm& sm, int S, int T,
     llt += ll;
   }
   return llt;
+}
+
+// B6 of ONE point: l[i] of point i = (c, t), the addends of tb_loglik_points for channel c summed over the Q heads, from the state x at t
+// (pointwise_kernel's and pointwise_loo_kernel's point folds: the same routine, the same bits)
+template <int SM>
+__device__ __forceinline__ float tb_point_loglik(const FwdSm& sm, int S, int C, int Q, int c, int gauss, const float (&tau)[3], float obv, float inv,
+                                                 float lg, const float (&x)[SM]) {
+  float l = 0.f;
+  for (int q = 0; q < Q; ++q) {
+    const float mu = fwd_head_value<SM>(sm, S, q * C + c, x), r = obv - mu;
+    if (gauss) l += -lg - TB_HL2PI - 0.5f * r * r * inv * inv;
+    else l += ((obv >= mu) ? tau[q] : 1.f - tau[q]) * (-lg - fabsf(r) * inv);
+  }
+  return l;
 }
 
 // B7: the log-probability of the label columns y[0 .. u_dim) of head a under its logits lg (no cross-lane operation)

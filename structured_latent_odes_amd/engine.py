@@ -802,6 +802,43 @@ class Engine:
                          self._p(scale), self._p(point), self._p(summary), self._p(loss_kb))
         return point, summary, loss_kb
 
+    def loo_plan(self, B: int, num_draws: int, tile: int = 0):
+        """``slode_loo_plan``: ``(tile, sweeps, depth, lds_bytes)`` of ``pointwise_loo`` for this shape and draw count -- time points per
+        sweep over the draws, the number of sweeps, the depth M + 1 of the kept sorted tail (M = min(ceil(min(0.2 K, 3 sqrt K)), K - 1))
+        and the dynamic LDS bytes; host arithmetic only.  ``tile`` = 0: the fewest sweeps that fit.  Raises SlodeError where the call
+        would refuse them at its own rungs."""
+        t, sw, d, lds = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_loo_plan(C.byref(self.shape(B)), int(num_draws), int(tile), C.byref(t), C.byref(sw), C.byref(d),
+                                                       C.byref(lds)))
+        return int(t.value), int(sw.value), int(d.value), int(lds.value)
+
+    def pointwise_loo(self, params, batch: L.Batch, B: int, num_draws: int, mask=None, loc=None, scale=None, tile: int = 0, point=None,
+                      summary=None, tail=None, particles: int = 1):
+        """slode_pointwise_loo: Pareto-smoothed importance-sampling leave-one-out from the ``num_draws`` posterior draws of
+        ``pointwise_density`` (posterior weights) -- ``(point, summary, tail)``: ``point`` float32 [3, B, C, T] = elpd_loo | khat | lppd
+        (``lppd`` bit for bit ``pointwise_density``'s plane 0; ``khat`` = +inf where no smoothing was possible), ``summary`` float32 [B,
+        L.LOO_SLOTS] = [sum_in elpd_loo, sum_in lppd, n_in, the number of points in with khat > 0.7, their largest khat, sum_out
+        elpd_loo, sum_out lppd, n_out], ``tail`` float32 [M + 1, B, C, T], the kept smallest per-draw log-densities of every point,
+        ascending (``tail=True``: allocated; a tensor: written; None: not produced).  ``mask`` / ``loc`` / ``scale`` / the batch's eps:
+        as ``pointwise_density``; the counter advances by num_draws whatever the number of sweeps.  ``tile``: time points per sweep (0:
+        the library's choice, ``loo_plan``); no output bit depends on it.  Enqueued on the current stream.  Raises SlodeError naming the
+        reason for what the kernel does not take (everything ``pointwise_density`` refuses in posterior mode; one of loc / scale alone;
+        tile outside [0, T]; a draw count whose tables do not fit the LDS): nothing is launched and no draw is consumed then."""
+        K, Ld, Cn = int(num_draws), self.spec.latent_dim, self.spec.n_channels
+        self._mask_like_obs(mask, batch, B)
+        for name, t in (("loc", loc), ("scale", scale)):
+            if t is not None and tuple(self._f32(t, name).shape) != (B, Ld):
+                raise ValueError("%s must be [%d, %d], got %s" % (name, B, Ld, tuple(t.shape)))
+        point = self._out(point, "point", (3, B, Cn, self.T))
+        summary = self._out(summary, "summary", (B, L.LOO_SLOTS))
+        if tail is not None and tail is not False:
+            tail = self._out(None if tail is True else tail, "tail", (self.loo_plan(B, K, tile)[2], B, Cn, self.T))
+        else:
+            tail = None
+        self._batch_call(self.lib.slode_pointwise_loo, params, batch, B, particles, K, self._p(mask), self._p(loc), self._p(scale), int(tile),
+                         self._p(point), self._p(summary), self._p(tail))
+        return point, summary, tail
+
     def intervene_moments(self, params, batch: L.Batch, B: int, cf_labels, group_mask: int, num_samples: int, cf_mean=None, cf_sd=None,
                           eff_mean=None, eff_sd=None, particles: int = 1):
         """slode_intervene_moments: counterfactual curves from ``num_samples`` paired posterior draws per trajectory.  Both arms of a draw

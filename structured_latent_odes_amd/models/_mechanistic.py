@@ -1695,6 +1695,180 @@ class MechanisticBase(nn.Module):
         return "waic: K=%d  n=%d  elpd_waic=%.4f  se=%.4f  p_waic=%.4f  share(p_waic>0.4)=%.4f" % (
             int(num_draws), n, elpd.sum(), float(np.sqrt(n * elpd.var())) if n else 0.0, table[:, 1].sum(), float((p_waic > 0.4).mean()) if p_waic.size else 0.0)
 
+    # ---- PSIS leave-one-out: per-point elpd_loo and the Pareto khat from K posterior draws ------------------------------------------------
+    LOO_NAMES = ("elpd_loo_in", "lppd_in", "n_in", "n_bad_in", "khat_max_in", "elpd_loo_out", "lppd_out", "n_out")   # one summary row, in order
+    LOO_FIT_ELEMENTS = 1 << 24      # composed route: most fp64 elements of the [points, grid, tail] table of one chunk of points
+
+    @staticmethod
+    def loo_tail_length(num_draws: int) -> int:
+        """M = min(ceil(min(0.2 K, 3 sqrt K)), K - 1): the number of largest importance ratios the generalised Pareto tail is fitted to."""
+        K = int(num_draws)
+        return min(int(math.ceil(min(0.2 * K, 3.0 * math.sqrt(K)))), K - 1)
+
+    @classmethod
+    def _psis_loo(cls, ell):
+        """``(elpd_loo, khat, tail)`` of per-draw log-densities ``ell`` ``[..., K]`` (fp64), vectorised over the points: the rule of
+        ``slode_pointwise_loo`` (include/slode.h) -- sort, the tail above the cutoff, the Zhang & Stephens fit with the prior of Vehtari
+        et al., the smoothed log-ratios in rank order, the self-normalised estimate.  ``tail``: the M + 1 smallest values, ascending,
+        ``[M + 1, ...]``."""
+        f64 = torch.float64
+        shp, K = ell.shape[:-1], ell.shape[-1]
+        M = cls.loo_tail_length(K)
+        ls = torch.sort(ell.reshape(-1, K).to(f64), dim=-1).values
+        N = ls.shape[0]
+        a = ls[:, :1] - ls                                                    # [N, K], 0 at rank 0, non-increasing
+        cut = a[:, M].clamp_min(math.log(2.2250738585072014e-308))
+        ec = cut.exp()
+        in_tail = a[:, :M] > cut[:, None]                                     # [N, M]: the ranks of the tail (a prefix)
+        n = in_tail.sum(1)
+        khat = torch.full((N,), float("inf"), dtype=f64, device=ell.device)
+        logw = a.clone()
+        fit = n >= 5
+        if M >= 5 and bool(fit.any()):
+            rows = max(1, cls.LOO_FIT_ELEMENTS // ((30 + int(math.isqrt(M))) * M))
+            idx = fit.nonzero().reshape(-1)
+            for lo in range(0, idx.numel(), rows):
+                sel = idx[lo:lo + rows]
+                nn, msk, e = n[sel], in_tail[sel], ec[sel]
+                nf = nn.to(f64)
+                x = torch.where(msk, a[sel, :M].exp() - e[:, None], torch.zeros((), dtype=f64, device=ell.device))   # [R, M] by rank (descending x)
+                xq = x.gather(1, (nn - torch.floor(nf / 4.0 + 0.5).long())[:, None])[:, 0]       # x_[floor(n / 4 + 0.5) - 1], ascending order
+                xn = 1.0 - e                                                                         # x_[n - 1]: rank 0
+                m = 30 + torch.floor(nf.sqrt()).long()
+                j = torch.arange(1, 30 + int(math.isqrt(M)) + 1, dtype=f64, device=ell.device)[None, :]
+                on = j <= m[:, None].to(f64)
+                b = (1.0 - (m[:, None].to(f64) / (j - 0.5)).sqrt()) / (3.0 * xq[:, None]) + 1.0 / xn[:, None]      # [R, J]
+                kj = (torch.log1p(-b[:, :, None] * x[:, None, :]) * msk[:, None, :]).sum(-1) / nf[:, None]
+                L = nf[:, None] * (torch.log(-b / kj) - kj - 1.0)
+                w = torch.softmax(torch.where(on, L, torch.full_like(L, float("-inf"))), dim=1)       # 1 / sum_j' exp(L_j' - L_j)
+                w = torch.where(w >= 10.0 * 2.0 ** -52, w, torch.zeros_like(w))
+                w = w / w.sum(1, keepdim=True)
+                bs = (w * torch.where(on, b, torch.zeros_like(b))).sum(1)
+                ks = (torch.log1p(-bs[:, None] * x) * msk).sum(1) / nf
+                sigma = -ks / bs
+                kh = (nf * ks + 5.0) / (nf + 10.0)
+                ok = torch.isfinite(kh) & torch.isfinite(sigma)
+                r = torch.arange(M, dtype=f64, device=ell.device)[None, :]
+                p = ((nf[:, None] - r) - 0.5) / nf[:, None]                                         # rank r <-> ascending index n - r
+                p = torch.where(msk, p, torch.full_like(p, 0.5))
+                s = torch.log(sigma[:, None] * torch.expm1(-kh[:, None] * torch.log1p(-p)) / kh[:, None] + e[:, None]).clamp_max(0.0)
+                put = msk & ok[:, None]
+                lw = logw[sel]
+                lw[:, :M] = torch.where(put, s, lw[:, :M])
+                logw[sel] = lw
+                khat[sel] = torch.where(ok, kh, khat[sel])
+        elpd = torch.logsumexp(logw + ls, dim=1) - torch.logsumexp(logw, dim=1)
+        return elpd.reshape(shp), khat.reshape(shp), ls[:, :M + 1].t().reshape((M + 1,) + tuple(shp))
+
+    def pointwise_loo(self, observations, num_draws: int, mask=None, posterior=None, eps=None, tile: int = 0, max_sweeps: int = 2,
+                      return_tail: bool = False, **labels):
+        """The remedy where ``pointwise_density`` warns that WAIC is unreliable, and the honest comparison of two fitted models:
+        Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman & Gabry 2017) from ``num_draws`` = K posterior draws.  Per
+        observation point (c, t), ``[B, C, T]`` each: ``"elpd_loo"``, the log predictive density of the point with that point left
+        out; ``"khat"``, the shape of the generalised Pareto tail of its importance ratios -- the estimate can be trusted below 0.5, is
+        usable up to 0.7, and +inf says the tail was too short to smooth (K < 21, or ties); ``"lppd"`` (bit for bit
+        ``pointwise_density``'s) and ``"p_loo"`` = lppd - elpd_loo.  Per trajectory (``[B]`` each): ``"elpd_loo_in"``, ``"lppd_in"``,
+        ``"n_in"``, ``"n_bad_in"`` (points with khat > 0.7) and ``"khat_max_in"`` over the points the mask counts as observed (> 0),
+        ``"elpd_loo_out"``, ``"lppd_out"``, ``"n_out"`` over the others; with ``return_tail`` ``"tail"`` ``[M + 1, B, C, T]``, the
+        smallest per-draw log-densities of every point, ascending.  ``mask`` / ``posterior`` / ``eps``: as ``pointwise_density``
+        (posterior weights); the counter moves by K.  ONE engine call (``slode_pointwise_loo``) that keeps only those M + 1 values per
+        point, sorted, on chip: no ``[B, C, T, K]`` tensor exists.  ``tile``: time points per sweep over the draws (0: the engine's
+        choice, ``Engine.loo_plan``).  The composed route -- ``recon_samples`` over chunks of trajectories, the point terms and the
+        smoothing in torch fp64 -- is taken where the engine refuses (adaptive solver, strided observations, measured arms, LDS
+        budget) or where the plan needs more than ``max_sweeps`` sweeps."""
+        b = self._bind()
+        B, K = observations.shape[0], self._count(num_draws, "num_draws")
+        T = int(self.times.numel())
+        if not 0 <= int(tile) <= T:
+            raise ValueError("tile must lie in [0, T = %d], got %d" % (T, int(tile)))
+        if mask is not None:
+            mask = self._obs_layout(observations, mask)
+        post = None if posterior is None else self._given_posterior(observations, posterior)
+
+        def fused():
+            return b.engine.pointwise_loo(b.flat, self._draws_batch(observations, labels, eps, K), B, K, mask=mask,
+                                          loc=None if post is None else post[0], scale=None if post is None else post[1], tile=int(tile),
+                                          tail=True if return_tail else None)
+
+        def composed():
+            return self._loo_composed(observations, K, mask, post, eps, labels)
+
+        def planned():
+            if b.engine.loo_plan(B, K, int(tile))[1] > int(max_sweeps):
+                return composed()
+            return fused()
+        point, summary, tail = self._fused_or_composed(planned, composed)
+        res = {"elpd_loo": point[0], "khat": point[1], "lppd": point[2], "p_loo": point[2] - point[0]}
+        res.update({n: summary[:, i] for i, n in enumerate(self.LOO_NAMES)})
+        if return_tail:
+            res["tail"] = tail
+        return res
+
+    def _loo_composed(self, observations, K, mask, post, eps, labels):
+        """The composed route: ``(point [3, B, C, T], summary [B, 8], tail [M + 1, B, C, T])`` from the materialised curves of
+        ``recon_samples`` (``MOMENTS_CHUNK_ROWS // K`` rows at a time), every point term, fold and fit in fp64.  The generator's counter
+        ends where the engine call leaves it: at n + K."""
+        f64 = torch.float64
+        sd = torch.nn.functional.softplus(self.decoder.constant_std.detach()).to(f64)[None, :, :, None]     # [1, C, T, 1]
+        d = float(self.config.quantile_diff)
+        planes, rows, tails = [], [], []
+        with torch.no_grad(), self._counter_moves_by(K, eps):
+            for lo, hi, e, batch in self._chunks(observations, labels, K, eps):
+                obs = batch["observations"]
+                pst = None if post is None else (post[0][lo:hi], post[1][lo:hi])
+                s = self.recon_samples(is_post=True, num_samples=K, eps=e, posterior=pst, **batch)
+                y = obs.to(f64)[..., None]
+                if self.GAUSS:
+                    ell = -torch.log(sd) - 0.5 * math.log(2.0 * math.pi) - 0.5 * ((y - s["mean"].to(f64)) / sd) ** 2
+                else:
+                    ell = 0.0
+                    for name, tau in (("mu_50", 0.5), ("mu_75", 0.5 + d), ("mu_25", 0.5 - d)):
+                        mu = s[name].to(f64)
+                        ell = ell + torch.where(y >= mu, torch.full_like(mu, tau), torch.full_like(mu, 1.0 - tau)) * (-torch.log(2.0 * sd) - (y - mu).abs() / sd)
+                del s
+                elpd, khat, tail = self._psis_loo(ell)
+                lppd = torch.logsumexp(ell, dim=-1) - math.log(K)
+                del ell
+                plane = torch.stack([elpd, khat, lppd]).to(torch.float32)                                   # the sums: of the rounded planes
+                pe, pk, pl = plane[0].to(f64), plane[1].to(f64), plane[2].to(f64)
+                inn = (torch.ones_like(pe) if mask is None else mask[lo:hi].to(f64)) > 0
+                out = ~inn
+                zero = torch.zeros((), dtype=f64, device=obs.device)
+                rows.append(torch.stack([torch.where(inn, pe, zero).sum((1, 2)), torch.where(inn, pl, zero).sum((1, 2)), inn.sum((1, 2)).to(f64),
+                                         (inn & (pk > 0.7)).sum((1, 2)).to(f64),
+                                         torch.where(inn, pk, torch.full_like(pk, float("-inf"))).amax((1, 2)),
+                                         torch.where(out, pe, zero).sum((1, 2)), torch.where(out, pl, zero).sum((1, 2)), out.sum((1, 2)).to(f64)], dim=1))
+                planes.append(plane)
+                tails.append(tail.to(torch.float32))
+        return torch.cat(planes, 1), torch.cat(rows, 0).to(torch.float32), torch.cat(tails, 1)
+
+    def save_pointwise_loo(self, results_dir: str, batches, num_draws: int):
+        """Runs ``pointwise_loo`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors, optionally
+        ``mask`` / ``posterior``) and writes ``pointwise_elpd_loo_post.npy``, ``pointwise_khat_post.npy`` (float32 ``[n, C, T]``) and
+        ``loo_post.npy`` (float32 ``[n, 8]``, the columns of ``LOO_NAMES``), the trajectories in loader order.  One read-back, at the
+        end.  Returns the three paths."""
+        parts = {"pointwise_elpd_loo_post.npy": [], "pointwise_khat_post.npy": [], "loo_post.npy": []}
+        for d in batches:
+            r = self.pointwise_loo(num_draws=num_draws, **d)
+            for f, v in zip(parts, (r["elpd_loo"], r["khat"], torch.stack([r[n] for n in self.LOO_NAMES], dim=1))):
+                parts[f].append(v)
+        if not parts["loo_post.npy"]:
+            raise ValueError("save_pointwise_loo: no batches")
+        return self._save_arrays(results_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()])
+
+    @staticmethod
+    def loo_line(table, khat, num_draws: int) -> str:
+        """The printed line of ``--loo``: total elpd_loo = sum elpd_loo_in and its standard error sqrt(n var_b(elpd_b)) over the n
+        trajectories, total p_loo = sum (lppd_in - elpd_loo_in), and the shares of points with khat > 0.7 and with khat > 0.5.
+        ``table``: ``[n, 8]`` (``loo_post.npy``); ``khat``: ``[n, C, T]``."""
+        import numpy as np
+        table, khat = np.asarray(table, np.float64), np.asarray(khat, np.float64)
+        elpd = table[:, 0]
+        n = elpd.shape[0]
+        return "loo: K=%d  n=%d  elpd_loo=%.4f  se=%.4f  p_loo=%.4f  share(khat>0.7)=%.4f  share(khat>0.5)=%.4f" % (
+            int(num_draws), n, elpd.sum(), float(np.sqrt(n * elpd.var())) if n else 0.0, (table[:, 1] - table[:, 0]).sum(),
+            float((khat > 0.7).mean()) if khat.size else 0.0, float((khat > 0.5).mean()) if khat.size else 0.0)
+
     # ---- label evidence: which input does the generative model believe produced these curves? -------------------------------------------
     EVIDENCE_NAMES = ("elbo", "iw_bound", "ess", "log_post")    # the slots of one slode_label_evidence row, in order
 

@@ -114,7 +114,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
           curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
-          quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,)):
+          quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,), loo: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -145,6 +145,9 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     waic = K > 0: after training, the best model's pointwise predictive density over the validation loader from K posterior draws
     (``save_pointwise_density``: ``pointwise_{lppd,p_waic,mean_ll}_post.npy`` [n, C, T], ``waic_post.npy`` [n, 8]) and one printed line
     (``waic: ...``: total elpd_waic and its standard error over trajectories, total p_waic, the share of points with p_waic > 0.4);
+    loo = K > 0: after training, the best model's PSIS leave-one-out over the validation loader from K posterior draws
+    (``save_pointwise_loo``: ``pointwise_{elpd_loo,khat}_post.npy`` [n, C, T], ``loo_post.npy`` [n, 8]) and one printed line (``loo: ...``:
+    total elpd_loo and its standard error over trajectories, total p_loo, the shares of points with khat > 0.7 and > 0.5);
     0 (the default): no such stage runs.
     attribution = K > 0: after training, the best model's latent attribution over the validation loader from K pick-freeze draws, posterior
     and prior (``save_latent_attribution``: ``attribution_{total,first}[_index]_<post|prior>.npy``, ``attribution_blocks.txt``) and one
@@ -281,6 +284,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                                     np.load([f for f in written if "p_waic" in f][0]), int(waic))
         print(line)
         logging.debug("%s (%s)", line, written)
+    if loo:
+        written = best_model.save_pointwise_loo(out_dir, (batch_to_device(b, device, family) for b in val_b), int(loo))
+        line = best_model.loo_line(np.load([f for f in written if os.path.basename(f) == "loo_post.npy"][0]),
+                                   np.load([f for f in written if "khat" in f][0]), int(loo))
+        print(line)
+        logging.debug("%s (%s)", line, written)
     # the whole-curve passes, posterior and prior each: (flag value = draws, save method, its keyword arguments, the printed line from
     # load(file-name ending), the central curve's name and the side's tag)
     curve_passes = (
@@ -379,6 +388,10 @@ def build_parser():
                     help="after training: the best model's pointwise predictive density over the validation loader from K posterior draws "
                          "(save_pointwise_density: pointwise_*_post.npy, waic_post.npy) and its WAIC -- elpd_waic with its standard error, p_waic, "
                          "the share of points with p_waic > 0.4 -- one line")
+    ap.add_argument("--loo", type=int, default=0, metavar="K",
+                    help="after training: the best model's PSIS leave-one-out over the validation loader from K posterior draws "
+                         "(save_pointwise_loo: pointwise_{elpd_loo,khat}_post.npy, loo_post.npy) -- elpd_loo with its standard error, p_loo, "
+                         "the shares of points with khat > 0.7 and > 0.5 -- one line")
     ap.add_argument("--attribution", type=int, default=0, metavar="K",
                     help="after training: the best model's latent attribution over the validation loader from K pick-freeze draws, posterior and "
                          "prior (save_latent_attribution: attribution_*.npy, attribution_blocks.txt) -- per latent block, the mean total and "
@@ -437,6 +450,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["refine_steps"], kw["refine_draws"] = a.refine_steps, a.refine_draws
     if a.waic:
         kw["waic"] = a.waic
+    if a.loo:
+        kw["loo"] = a.loo
     if a.attribution:
         kw["attribution"] = a.attribution
     if a.curve_summary:

@@ -28,3 +28,9 @@ for name, spec, T in (("cvs C1 rk4", E.cvs_spec(3, 3, 2, solver="rk4"), 200), ("
         r = C.c_size_t(0)
         assert L.load().slode_pointwise_plan(C.byref(s), K, w, C.byref(r)) == 0
         print("%-18s pointwise %-16s LDS %6d B  -> %d workgroups/CU by LDS" % ("", tag, r.value, (160 * 1024) // r.value))
+    # the leave-one-out kernel's tables (256 threads): the library's own tile, the sweeps and the depth M + 1 of the kept tail
+    for K in (8, 64, 200, 1024):
+        t, sw, d, r = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+        assert L.load().slode_loo_plan(C.byref(s), K, 0, C.byref(t), C.byref(sw), C.byref(d), C.byref(r)) == 0
+        print("%-18s loo K=%-4d depth %3d  tile %3d  sweeps %d  LDS %6d B  -> %d workgroups/CU by LDS"
+              % ("", K, d.value, t.value, sw.value, r.value, (160 * 1024) // r.value))
