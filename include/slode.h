@@ -644,7 +644,8 @@ int slode_latent_attribution(slode_handle h, const slode_shape* s, const slode_l
  *   p_beyond must be NULL.
  *   The sums of slots 4 and 5 have a fixed tree: time points t = l, l + 16, ... in increasing order on lane l of a 16-lane row, then the row's
  *   lanes pairwise (xor 1, xor 2, half mirror, mirror).  Extremes and first indices are comparisons and selections: exact, the smallest index
- *   wins ties.
+ *   wins ties.  A curve that is constant in time has t_peak = t_trough = t_0; against a threshold equal to its value it is beyond in neither
+ *   sense (the comparison is strict): time_beyond = crossed = 0, t_hit NaN, p_beyond 0.
  *   Draws, sides, noise: those of slode_recon_moments -- is_post != 0: three launches ("weff", "enc_fwd2", "curve_summary" in slode_profile_read);
  *   is_post == 0: "curve_summary" alone; batch->eps == NULL: ONE drawing call n (row k * B + b, plus first_trajectory), the counter left at n + 1;
  *   else a dense [num_samples, B, L] tensor.  The result is a function of (parameters, inputs, labels, noise, thr, sense) alone: independent of the
@@ -759,7 +760,9 @@ int slode_mechanism_moments(slode_handle h, const slode_shape* s, const slode_la
  * For trajectory b, head curve q (the order of slode_recon_moments) and channel c let v_k(t) be the K = num_samples draw curves, m(t) and s(t)
  * their mean and population sd -- the bits slode_recon_moments returns for the same noise, written to mean / sd [Q,B,C,T] -- and
  *   dev_k = max over the participating t of  fl(fl(|v_k(t) - m(t)|) / s(t))      (fp32; a point takes part when s(t) > sd_floor; no point: 0)
- * the largest standardised deviation of draw k.  dev_k <= sqrt(K - 1) whatever the model: below about K = 20 a 95 % value is a property of K.
+ * the largest standardised deviation of draw k.  A curve whose draws coincide at every t (s = 0 everywhere) has no participating point at
+ * sd_floor = 0: dev_k = 0 for every k, crit = 0, joint = 1 at every level, obs_dev = (0, 0) whatever the observations.
+ * dev_k <= sqrt(K - 1) whatever the model: below about K = 20 a 95 % value is a property of K.
  * Per level p_j (levels: a HOST array [n_levels] of doubles in (0, 1], read at the call; any order, duplicates allowed; n_levels <=
  * SLODE_JOINT_BAND_MAX_LEVELS = 8), formed on the host in fp64 (slode_joint_band_levels):
  *   r_j = min(K, max(1, ceil(p_j K - 1e-9))),   z_j = Phi^-1((1 + p_j) / 2)  (p_j = 1: +inf)
@@ -910,6 +913,8 @@ int slode_cohort_moments(slode_handle h, const slode_shape* s, const slode_layou
  *   cross[g][c][t]      int32: pairs with v_2 > v_0 or v_0 > v_1 (quantile crossing; 0 by construction for the Gauss families)
  *   pinball[j][g][c]    mean over members x draws x time of (y - v_j)(tau_j - [y < v_j])
  *   width[g][c]         mean over members x draws x time of v_1 - v_2
+ * An observation EQUAL to a curve value (either sign of zero against a curve that is exactly 0.0 included) is not below it: it counts in no
+ * below[j], is inside only through v_2 <= y, and its pinball summand is 0; curves that are equal do not cross.
  * An empty cohort, or one with a member index outside [0, B): counts 0, float outputs NaN.  A NaN curve value compares false everywhere and
  * makes the float outputs of its cohort NaN; nothing else is affected.  M K <= B K <= 2^30 - 1 (refused beyond): int32 holds every count.
  * The integer outputs are a function of (parameters, inputs, noise, members, offsets) alone: bitwise equal across runs, launch grids, in-kernel

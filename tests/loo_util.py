@@ -16,20 +16,23 @@ def tail_len(K):
 
 def gpd_fit(x):
     """(khat, sigma) of the ascending positive tail x (fp64): the profile of Zhang & Stephens on m = 30 + floor(sqrt n) grid points, weights
-    below 10 ulp dropped, and the prior (n k + 5) / (n + 10)."""
-    x = np.asarray(x, np.float64)
-    n = x.size
-    m = 30 + int(math.floor(math.sqrt(n)))
-    j = np.arange(1, m + 1, dtype=np.float64)
-    b = (1.0 - np.sqrt(m / (j - 0.5))) / (3.0 * x[int(n / 4.0 + 0.5) - 1]) + 1.0 / x[n - 1]
-    k = np.log1p(-b[:, None] * x[None, :]).mean(1)
-    L = n * (np.log(-b / k) - k - 1.0)
-    w = 1.0 / np.exp(L[None, :] - L[:, None]).sum(1)
-    keep = w >= 10.0 * 2.0 ** -52
-    w = w[keep] / w[keep].sum()
-    bs = float((w * b[keep]).sum())
-    ks = float(np.log1p(-bs * x).mean())
-    return (n * ks + 5.0) / (n + 10.0), -ks / bs
+    below 10 ulp dropped, and the prior (n k + 5) / (n + 10).  In numpy scalars with the floating-point flags ignored, as the kernel's fp64
+    runs: a tail that spans 300 decades (x_[n/4] denormal: 1 / (3 x) overflows, every profile value is NaN, no weight is kept, b* = 0 / 0)
+    gives a non-finite (khat, sigma) and raises nothing; the caller's rule for that is the kernel's -- unsmoothed, khat = +inf."""
+    with np.errstate(all="ignore"):
+        x = np.asarray(x, np.float64)
+        n = x.size
+        m = 30 + int(math.floor(math.sqrt(n)))
+        j = np.arange(1, m + 1, dtype=np.float64)
+        b = (1.0 - np.sqrt(m / (j - 0.5))) / (3.0 * x[int(n / 4.0 + 0.5) - 1]) + 1.0 / x[n - 1]
+        k = np.log1p(-b[:, None] * x[None, :]).mean(1)
+        L = n * (np.log(-b / k) - k - 1.0)
+        w = 1.0 / np.exp(L[None, :] - L[:, None]).sum(1)
+        keep = w >= 10.0 * 2.0 ** -52
+        w = w[keep] / w[keep].sum()
+        bs = np.float64((w * b[keep]).sum())
+        ks = np.float64(np.log1p(-bs * x).mean())
+        return (n * ks + 5.0) / (n + 10.0), -ks / bs
 
 
 def psis_point(l):

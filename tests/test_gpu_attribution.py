@@ -13,22 +13,9 @@ from tests import eval_stats_util as EU
 from tests import recon_moments_util as RU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _padded,
                                  _peak, _recon_moments, _refused)
+from tests.eval_gpu_util import _attr
 
 pytestmark = pytest.mark.gpu
-
-
-def _attr(eng, flat, c, is_post, masks, eps="case", obs_d=None, labels=None, ns=None):
-    """Engine.latent_attribution on the case's batch; outputs pre-filled with NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = c["eps2"].to(DEV).contiguous() if isinstance(eps, str) else eps
-    Q, B, L = 1 if c["ospec"].gauss else 3, c["B"], c["ospec"].latent_dim
-    mean = torch.full((Q, B, c["obs"].shape[1], c["T"]), float("nan"), device=DEV)
-    sd = torch.full_like(mean, float("nan"))
-    msd = torch.full((len(masks),) + tuple(mean.shape), float("nan"), device=DEV)
-    bt = eng.make_batch(obs_d, labels, e, particles=ns, eps_shape=None if e is None else (2, ns, B, L))
-    return eng.latent_attribution(flat, bt, B, is_post, ns, masks, mean, sd, msd)
 
 
 def _equal(a, b):

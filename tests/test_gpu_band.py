@@ -26,6 +26,7 @@ from tests import recon_moments_util as RU
 from tests import summary_util as SU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _model_curves, _padded, _peak,
                                  _per_draw_curves, _recon_moments, _refused, _same as _same_arrays, _set_env)
+from tests.eval_gpu_util import _band, _band_check_exact as _check_exact, _band_check_oracle as _check_oracle, _band_outs as _outs
 
 pytestmark = pytest.mark.gpu
 FILL = BU.FILL
@@ -33,45 +34,7 @@ LEVELS = (0.95, 0.5, 1.0, 0.1)
 CASES = ["cvs_ald", "proc_gauss", "challenge_gauss", "proc_ald"]
 
 
-def _outs(Q, B, Cn, T, Lv, ns):
-    return [torch.full(shp, FILL, device=DEV) for shp in ((Q, B, Cn, T), (Q, B, Cn, T), (Q, B, Cn, Lv), (Q, B, Cn, Lv), (Q, B, Cn, 2), (Q, B, Cn, ns))]
-
-
-def _band(eng, flat, c, is_post, levels=LEVELS, floor=0.0, eps="case", ns=None, obs_d=None, labels=None, null_obs=False):
-    """Engine.joint_band on the case's batch -> dict of numpy arrays (crit / joint [Q, B, C, Lv], dev [Q, B, C, K], obs_dev / points
-    [Q, B, C]); every output pre-filled with FILL and fully written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q, Cn = (1 if c["ospec"].gauss else 3), c["obs"].shape[1]
-    outs = _outs(Q, c["B"], Cn, c["T"], len(levels), ns)
-    bt = eng.make_batch(obs_d, labels, e, particles=ns)
-    if null_obs:
-        bt.obs = None
-    eng.joint_band(flat, bt, c["B"], is_post, ns, list(levels), floor, *outs)
-    mean, sd, crit, joint, odev, dev = (t.cpu().numpy() for t in outs)
-    assert not any((t == FILL).any() for t in (mean, sd, crit, joint, odev, dev)), "an output element was not written"
-    return dict(mean=mean, sd=sd, crit=crit, joint=joint, obs_dev=odev[..., 0], points=odev[..., 1], dev=dev)
-
-
 _same = functools.partial(_same_arrays, equal_nan=True)
-
-
-def _check_exact(r, curves, y, levels, floor, tag):
-    """Every output of one call against the numpy restatement on the kernel's own curves, the call's own mean and sd: exactly."""
-    dev, pts = BU.dev_f32(curves, r["mean"], r["sd"], floor)
-    assert _same(r["dev"], np.ascontiguousarray(np.moveaxis(dev, 0, -1))), (tag, "dev", np.argwhere(r["dev"] != np.moveaxis(dev, 0, -1))[:4])
-    crit, joint = BU.crit_joint(dev, levels)
-    assert _same(r["crit"], crit), (tag, "crit")
-    assert _same(r["joint"], joint), (tag, "joint")
-    assert np.array_equal(r["points"], pts.astype(np.float32)), (tag, "points")
-    if y is not None:
-        odev, _ = BU.dev_f32(np.broadcast_to(RU._f32(y), r["mean"].shape)[None], r["mean"], r["sd"], floor)
-        assert _same(r["obs_dev"], odev[0]), (tag, "obs_dev")
-    ranks = BU.level_rule(levels, curves.shape[0])[0]
-    for j, rk in enumerate(ranks):                                              # one of the stored deviations, by its rank
-        assert np.array_equal(r["crit"][..., j], np.sort(r["dev"], -1)[..., rk - 1]), (tag, j)
 
 
 @functools.lru_cache(maxsize=None)
@@ -127,43 +90,6 @@ def test_exact_at_33_draws():
 
 
 # ---- 3. against the fp64 oracle ----------------------------------------------------------------------------------------------------------------
-def _check_oracle(r, v, y, levels, floor, tag, share_at=None):
-    """One call's outputs against the oracle's draws v [Q, K, B, C, T] (BU.oracle_dev / BU.dev_bar per head curve).  Returns the worst
-    error / bar of the deviations and of the critical values, and the largest near share at the levels of ``levels`` in BU.COUNT_LEVELS."""
-    K = v.shape[1]
-    ranks, z = BU.level_rule(levels, K)
-    worst_dev = worst_crit = worst_obs = near_share = 0.0
-    for q in range(v.shape[0]):
-        o = BU.oracle_dev(v[q], y, floor)
-        on = o["sd"] > floor
-        bar = BU.dev_bar(o, on)                                                             # [K, B, C]
-        assert np.array_equal(r["points"][q], o["points"].astype(np.float32)), (tag, q, "points")
-        got = np.moveaxis(r["dev"][q].astype(np.float64), -1, 0)
-        ok = bar > 0
-        worst_dev = max(worst_dev, float((np.abs(got - o["dev"])[ok] / bar[ok]).max()) if ok.any() else 0.0)
-        assert np.all(np.abs(got - o["dev"]) <= bar), (tag, q, "dev")
-        scale = np.maximum(1.0, np.abs(o["mean"]))
-        with np.errstate(divide="ignore", invalid="ignore"):                               # (y is exact: one MEAN_BAR, from the mean)
-            obar = np.where(on, (RU.MEAN_BAR * scale + o["obs_dev"][..., None] * RU.SD_BAR * scale) / o["sd"], 0.0).max(-1)
-        eo = np.abs(r["obs_dev"][q] - o["obs_dev"])
-        worst_obs = max(worst_obs, float((eo[obar > 0] / obar[obar > 0]).max()) if (obar > 0).any() else 0.0)
-        assert np.all(eo <= obar), (tag, q, "obs_dev")
-        srt, cbar = np.sort(o["dev"], 0), bar.max(0)
-        for j, (rk, zj) in enumerate(zip(ranks, z)):
-            ec = np.abs(r["crit"][q, ..., j] - srt[rk - 1])
-            worst_crit = max(worst_crit, float((ec[cbar > 0] / cbar[cbar > 0]).max()) if (cbar > 0).any() else 0.0)
-            assert np.all(ec <= cbar), (tag, q, j, "crit")
-            counts = np.rint(r["joint"][q, ..., j].astype(np.float64) * K)
-            assert np.array_equal(RU._f32(counts) / np.float32(K), r["joint"][q, ..., j]), (tag, "joint is count / K")
-            nr = np.abs(o["dev"] - zj) <= bar
-            assert np.all(np.abs(counts - (o["dev"] <= zj).sum(0)) <= nr.sum(0)), (tag, q, j, "joint")
-            if levels[j] in BU.COUNT_LEVELS:
-                near_share = max(near_share, float(nr.mean()))
-            if share_at is not None and levels[j] == share_at:
-                assert float(nr.mean()) <= BU.NEAR_SHARE and np.all(counts == K), (tag, q, j, float(nr.mean()))
-    return worst_dev, worst_crit, worst_obs, near_share
-
-
 @pytest.mark.parametrize("ns", [7, 33])
 @pytest.mark.parametrize("case", CASES)
 def test_against_the_fp64_oracle(case, ns):

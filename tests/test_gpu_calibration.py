@@ -16,48 +16,10 @@ from tests import recon_moments_util as RU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _model_batches, _on_device,
                                  _padded, _peak, _refused)
 from tests.eval_gpu_util import _recon_moments as _moments
+from tests.eval_gpu_util import _calib, _calib_invariants as _invariants, _calib_own_curves as _own_curves, _cohort_lists as _lists
 
 pytestmark = pytest.mark.gpu
 ALL = ("inside", "cross", "pinball", "width")
-
-
-def _lists(ids, G):
-    members, offsets = KU.member_lists(ids, G)
-    return torch.from_numpy(members).to(DEV), torch.from_numpy(offsets).to(DEV)
-
-
-def _invariants(got, ids, G, ns, gauss):
-    """0 <= below <= count ns; inside <= count ns; Gauss: below[2] <= below[0] <= below[1] cell by cell, inside == below[1] - below[2],
-    cross == 0."""
-    below, inside, cross = got[:3]
-    cap = torch.tensor([int((np.asarray(ids) == g).sum()) * ns for g in range(G)], dtype=torch.int32, device=DEV).view(G, 1, 1)
-    assert bool((below >= 0).all()) and bool((below <= cap).all())
-    if inside is not None:
-        assert bool((inside >= 0).all()) and bool((inside <= cap).all()) and bool((inside <= below[1]).all())
-    if cross is not None:
-        assert bool((cross >= 0).all()) and bool((cross <= cap).all())
-    if gauss:
-        assert bool((below[2] <= below[0]).all()) and bool((below[0] <= below[1]).all())
-        assert inside is None or torch.equal(inside, below[1] - below[2])
-        assert cross is None or int(cross.abs().max()) == 0
-
-
-def _calib(eng, flat, c, is_post, ids, G, chunk=3, eps="case", ns=None, outputs=ALL, obs_d=None, labels=None, scratch=None, gauss=None):
-    """(below, inside, cross, pinball, width); the outputs asked for pre-filled with -1 / NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    C, T = c["obs"].shape[1], c["T"]
-    out = dict(below=torch.full((3, G, C, T), -1, dtype=torch.int32, device=DEV))
-    for name, shp, fill in (("inside", (G, C, T), -1), ("cross", (G, C, T), -1), ("pinball", (3, G, C), None), ("width", (G, C), None)):
-        if name in outputs:
-            out[name] = torch.full(shp, -1, dtype=torch.int32, device=DEV) if fill is not None else torch.full(shp, float("nan"), device=DEV)
-    members, offsets = _lists(ids, G)
-    got = eng.calibration(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, members, offsets, G, chunk=chunk,
-                          outputs=outputs, scratch=scratch, **out)
-    _invariants(got, ids, G, ns, c["ospec"].gauss if gauss is None else gauss)       # (gauss=False: NaN curves break the Gauss ordering)
-    return got
 
 
 def _same(x, y):
@@ -122,17 +84,6 @@ def test_constructed_observations_match_the_fp64_oracle(case):
 
 
 # ---- 2. the kernels' own per-draw values ---------------------------------------------------------------------------------------------------
-def _own_curves(eng, flat, c, is_post, eps, obs_d, labels):
-    """[3, K, B, C, T] fp32: the kernels' own value of every curve of every draw -- K recon_moments calls with num_samples = 1 (mean = the
-    draw); Gauss: mean + / - 2 s in fp32 with s the decode kernel's softplus(constant_std)."""
-    heads = np.stack([_moments(eng, flat, c, is_post, eps=eps[k].contiguous(), obs_d=obs_d, labels=labels, ns=1)[0].cpu().numpy() for k in range(eps.shape[0])], 1)
-    if not c["ospec"].gauss:
-        return heads                                                                       # [Q = 3, K, B, C, T]
-    s = eng.decode_heads(flat, torch.zeros(1, c["T"], c["S"], device=DEV))[1].cpu().numpy()
-    w = np.float32(2.0) * s
-    return np.stack([heads[0], heads[0] + w, heads[0] - w]).astype(np.float32)
-
-
 @pytest.mark.parametrize("case", ["cvs_ald", "proc_gauss"])
 def test_counts_are_those_of_the_kernels_own_curves(case):
     """The per-draw fp32 curves of ns = 1 recon_moments calls compared in numpy with the observations, against the counts of ONE ns = 7

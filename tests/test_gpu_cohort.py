@@ -15,49 +15,15 @@ from tests import recon_moments_util as RU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _model_batches, _on_device, _padded,
                                  _peak, _refused)
 from tests.eval_gpu_util import _recon_moments as _moments
+from tests.eval_gpu_util import _cohort, _cohort_ids as _ids, _cohort_lists as _lists, _cohort_per_draw as _per_draw, _cohort_truth as _truth
 
 pytestmark = pytest.mark.gpu
 ALL = ("sd", "sd_subjects", "obs_mean", "l1")
 
 
-def _lists(ids, G):
-    members, offsets = CU.member_lists(ids, G)
-    return torch.from_numpy(members).to(DEV), torch.from_numpy(offsets).to(DEV)
-
-
-def _cohort(eng, flat, c, is_post, ids, G, chunk=3, eps="case", ns=None, clip=None, outputs=ALL, obs_d=None, labels=None, scratch=None):
-    """(mean, sd, sd_subjects, obs_mean, l1); every output asked for is pre-filled with NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q, C, T = 1 if c["ospec"].gauss else 3, c["obs"].shape[1], c["T"]
-    nan = lambda *shp: torch.full(shp, float("nan"), device=DEV)
-    out = dict(mean=nan(Q, G, C, T))
-    for name, shp in (("sd", (Q, G, C, T)), ("sd_subjects", (Q, G, C, T)), ("obs_mean", (G, C, T)), ("l1", (G, C))):
-        if name in outputs:
-            out[name] = nan(*shp)
-    members, offsets = _lists(ids, G)
-    return eng.cohort_moments(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, members, offsets, G, chunk=chunk,
-                              clip_min=clip, outputs=outputs, scratch=scratch, **out)
-
-
 def _same(x, y):
     """Bitwise equal, the NaN of an empty cohort equal to itself."""
     return torch.equal(torch.nan_to_num(x, nan=-7.0), torch.nan_to_num(y, nan=-7.0))
-
-
-def _ids(mode, B, seed=2):
-    """(ids, G): "three": three cohorts and a tenth of the trajectories in none, interleaved; "one": G = 1; "singletons": G = B;
-    "none": M = 0 with G = 2."""
-    if mode == "one":
-        return np.zeros(B, np.int64), 1
-    if mode == "singletons":
-        return np.arange(B), B
-    if mode == "none":
-        return np.full(B, -1), 2
-    r = np.random.RandomState(seed)
-    return r.choice([-1, 0, 1, 2], size=B, p=[0.1, 0.5, 0.3, 0.1]), 3
 
 
 # ---- the fp64 oracle ---------------------------------------------------------------------------------------------------------------------
@@ -125,27 +91,6 @@ def test_sizes_and_instantiations(case, B, ns, chunk, mode, env, outputs, monkey
 
 
 # ---- against the kernel's own per-draw values, and against slode_recon_moments ------------------------------------------------------------
-def _per_draw(eng, flat, c, is_post, eps, obs_d, labels):
-    """[B, K, Q, C, T] fp32: the kernel's own value of every draw -- K calls with num_samples = 1 and singleton cohorts (mean = the draw)."""
-    B = c["B"]
-    ids, G = _ids("singletons", B)
-    vals = [_cohort(eng, flat, c, is_post, ids, G, chunk=1, eps=eps[k].contiguous(), ns=1, outputs=(), obs_d=obs_d, labels=labels)[0].cpu().numpy()
-            for k in range(eps.shape[0])]
-    return np.stack(vals).transpose(2, 0, 1, 3, 4)                                        # [K, Q, B, C, T] -> [B, K, Q, C, T]
-
-
-def _truth(vals, ids, G, R):
-    """Per cohort: fp64 (mean, sd, sd_subjects) of the per-draw values, D of the chunking, stacked [Q, G, C, T] (NaN: empty)."""
-    out = [np.full((vals.shape[2], G) + vals.shape[3:], np.nan) for _ in range(4)]
-    for g in range(G):
-        sel = np.flatnonzero(ids == g)
-        if sel.size:
-            v = vals[sel].astype(np.float64)
-            for o, x in zip(out, CU.moments64(v) + (CU.chunk_spread(v, R),)):
-                o[:, g] = x
-    return out
-
-
 @pytest.mark.parametrize("is_post", [False, True])
 def test_kernel_accumulation_on_curves_whose_sd_is_1e4_of_their_level(is_post):
     """As test_gpu_recon_moments' case of the same name: noise scaled by 3e-5, the kernel's own fp32 value of every draw from K calls with

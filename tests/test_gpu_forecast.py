@@ -16,32 +16,10 @@ from tests import eval_stats_util as EU
 from tests import forecast_util as FU
 from tests import recon_moments_util as RU
 from tests.eval_gpu_util import DEV, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _refused
+from tests.eval_gpu_util import _forecast
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
-
-
-def _forecast(eng, flat, c, is_post, window=0, eps="case", states=True, sd=True, x_mean=True, x_sd=True, times_out=None, ns=None, obs_d=None, labels=None):
-    """(mean, sd, x_mean, x_sd), NaN-prefilled; an output switched off is passed as NULL and comes back as None."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    t_out = c["times_out"] if times_out is None else times_out
-    Q, B, T_out = 1 if c["ospec"].gauss else 3, c["B"], t_out.numel()
-    mean = torch.full((Q, B, c["obs"].shape[1], T_out), NAN, device=DEV)
-    outs = [mean, torch.full_like(mean, NAN) if sd else None,
-            torch.full((B, c["S"], T_out), NAN, device=DEV) if states and x_mean else None,
-            torch.full((B, c["S"], T_out), NAN, device=DEV) if states and x_sd else None]
-    tt, st = eng.forecast_grid(t_out)
-    bt = eng.make_batch(obs_d, labels, e, particles=ns)
-    ws = eng.workspace(B)
-    eng._guard(flat, ws)
-    from structured_latent_odes_amd.engine import _check
-    _check(eng.lib, eng.handle, eng.lib.slode_forecast_moments(
-        eng.handle, C.byref(eng.shape(B)), C.byref(eng.layout), eng._p(flat), eng._p(eng._times), eng._p(eng._stage_t), C.byref(bt), 1 if is_post else 0, ns, eng._p(tt), eng._p(st),
-        T_out, int(window), *(eng._p(t) for t in outs), eng._p(ws), ws.numel() * 4, eng._stream()))
-    return tuple(outs)
 
 
 def _check_oracle(got, c, is_post, tag, eps=None):

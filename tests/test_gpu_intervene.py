@@ -13,29 +13,9 @@ from tests import intervene_util as IU
 from tests import recon_moments_util as RU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
                                  _recon_moments, _refused)
+from tests.eval_gpu_util import _iv, _label_split as _split
 
 pytestmark = pytest.mark.gpu
-
-
-def _split(c, u):
-    """A [B, n_u] label matrix as the family's label tensors, one by one, on the device."""
-    out, o = [], 0
-    for w in WIDTHS[c["fam"]]:
-        out.append(u[:, o:o + w].contiguous().to(DEV))
-        o += w
-    return out
-
-
-def _iv(eng, flat, c, mask, u_cf, eps="case", obs_d=None, labels=None, ns=None):
-    """Outputs pre-filled with NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q = 1 if c["ospec"].gauss else 3
-    outs = [torch.full((Q, c["B"], c["obs"].shape[1], c["T"]), float("nan"), device=DEV) for _ in range(4)]
-    cf = None if u_cf is None else _split(c, u_cf)
-    return eng.intervene_moments(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], cf, mask, ns, *outs)
 
 
 def _equal(a, b):

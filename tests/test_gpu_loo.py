@@ -13,67 +13,11 @@ import torch
 from tests import eval_stats_util as EU
 from tests import loo_util as LU
 from tests import pointwise_util as PU
-from tests.eval_gpu_util import ADAPTIVE, _captured, _device_batch, _engine, _lay, _model, _padded, _peak, _refused
+from tests.eval_gpu_util import (ADAPTIVE, _captured, _check_fit, _check_own_sums, _density, _device_batch, _engine, _lay, _loo, _model, _own_l, _padded,
+                                 _peak, _refused)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def _loo(eng, flat, c, K=None, eps="case", obs_d=None, labels=None, mask=None, loc=None, scale=None, tile=0, tail=True):
-    """Engine.pointwise_loo on the case's batch; outputs pre-filled with NaN: every element must be written."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    K = c["K"] if K is None else K
-    e = c["eps"] if isinstance(eps, str) else eps
-    if e is not None:
-        e = (e[0] if K == 1 and e.dim() == 3 else e).to(DEV).contiguous()
-    B, Cn, T = c["obs"].shape
-    point = torch.full((3, B, Cn, T), float("nan"), device=DEV)
-    summary = torch.full((B, 8), float("nan"), device=DEV)
-    tl = torch.full((LU.tail_len(K) + 1, B, Cn, T), float("nan"), device=DEV) if tail else None
-    eng.pointwise_loo(flat, eng.make_batch(obs_d, labels, e, particles=max(K, 1)), B, K, mask=mask, loc=loc, scale=scale, tile=tile, point=point,
-                      summary=summary, tail=tl)
-    return point, summary, tl
-
-
-def _density(eng, flat, c, eps, K, obs_d, labels, **kw):
-    B = c["B"]
-    e = (eps[0] if K == 1 else eps).to(DEV).contiguous()
-    return eng.pointwise_density(flat, eng.make_batch(obs_d, labels, e, particles=K), B, K, 0, loss_kb=False, **kw)[0]
-
-
-def _own_l(eng, flat, c, obs_d, labels, **kw):
-    """[K, B, C, T] fp32: the kernel's own l_k -- plane 0 of pointwise_density with one draw on that draw's noise row."""
-    return np.stack([_density(eng, flat, c, c["eps"][k:k + 1], 1, obs_d, labels, **kw)[0].cpu().numpy() for k in range(c["eps"].shape[0])])
-
-
-def _check_own_sums(point, summary, mask=None):
-    """The eight slots against the fp64 sums of the call's own planes: 2^-23 |sum| (+ 2^-50 of the magnitudes); counts and the max exact."""
-    got, gs = point.double().cpu().numpy(), summary.double().cpu().numpy()
-    inn = np.ones(got.shape[1:], bool) if mask is None else np.asarray(mask) > 0
-    for j, (v, sel) in ((0, (got[0], inn)), (1, (got[2], inn)), (5, (got[0], ~inn)), (6, (got[2], ~inn))):
-        s, mag = np.where(sel, v, 0.0).sum((1, 2)), np.where(sel, np.abs(v), 0.0).sum((1, 2))
-        assert np.all(np.abs(gs[:, j] - s) <= 2.0 ** -23 * np.abs(s) + 2.0 ** -50 * mag), ("slot", j, gs[:, j], s)
-    assert np.array_equal(gs[:, 2], inn.sum((1, 2))) and np.array_equal(gs[:, 7], (~inn).sum((1, 2)))
-    assert np.array_equal(gs[:, 3], ((got[1] > 0.7) & inn).sum((1, 2)))
-    assert np.array_equal(gs[:, 4], np.where(inn, got[1], -np.inf).max((1, 2)))
-
-
-def _check_fit(point, l, tag):
-    """elpd_loo and khat against the restatement on the kernel's own l: K 2^-23 max(1, |v|) for elpd_loo (the fp32 running sums), the
-    restatement's own sensitivity to 2^-24 |l| for khat.  Returns the worst error-to-bar ratios."""
-    K = l.shape[0]
-    e, k = LU.psis(l)
-    got = point.double().cpu().numpy()
-    re = np.abs(got[0] - e) / (K * 2.0 ** -23 * np.maximum(1.0, np.abs(e)))
-    kb = LU.khat_bar(l, 2.0 ** -24 * np.abs(l))
-    assert np.array_equal(np.isinf(got[1]), np.isinf(k)), tag
-    fin = np.isfinite(k) & np.isfinite(kb)
-    rk = np.abs(np.where(fin, got[1], 0.0) - np.where(fin, k, 0.0)) / np.where(fin, kb, 1.0)
-    print("%s: error / bar: elpd_loo %.3f, khat %.3f (khat in [%.3f, %.3f], %d of %d points smoothed)"
-          % (tag, re.max(), rk.max(), np.min(k), np.max(np.where(np.isfinite(k), k, -np.inf)), int(np.isfinite(k).sum()), k.size))
-    assert re.max() <= 1.0 and rk.max() <= 1.0, (tag, re.max(), rk.max())
-    return re.max(), rk.max()
 
 
 @pytest.mark.parametrize("K", [1, 4, 20, 21, 64])

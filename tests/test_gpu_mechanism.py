@@ -19,6 +19,7 @@ from tests import mechanism_util as MU
 from tests import recon_moments_util as RU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model, _padded, _peak,
                                  _recon_moments, _refused, _same as _same_arrays, _set_env)
+from tests.eval_gpu_util import _mech
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it: every element must be written
@@ -26,28 +27,6 @@ GUARD = 7.25               # and stand between guard words, which must stay
 NG = 64
 BOUNDED = 0x17             # state, production, degradation, net_rate
 WHICH = {"conditioned": MU.ALL, "as_built": BOUNDED}      # the cases of MU.build: all five slots; RU.build's as they are: the bounded four
-
-
-def _mech(eng, flat, c, is_post, slots=MU.ALL, eps="case", ns=None, sd=True, obs_d=None, labels=None):
-    """Engine.mechanism_moments on the case's batch -> numpy (mean, sd) [n_sel, B, S, T]; sd None where not asked.  The outputs lie in
-    one buffer each, pre-filled, with NG guard words on either side."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    shp = (bin(slots).count("1"), c["B"], c["S"], c["T"])
-    n = int(np.prod(shp))
-    bufs = [torch.full((n + 2 * NG,), GUARD, device=DEV) for _ in range(2 if sd else 1)]
-    outs = [b[NG:NG + n].view(shp) for b in bufs]
-    for o in outs:
-        o.fill_(FILL)
-    got = eng.mechanism_moments(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, slots, outs[0], outs[1] if sd else False)
-    assert got[0] is outs[0] and (got[1] is outs[1] if sd else got[1] is None)
-    for b in bufs:
-        h = b.cpu().numpy()
-        assert np.all(h[:NG] == GUARD) and np.all(h[NG + n:] == GUARD), "a guard word was written"
-        assert not (h[NG:NG + n] == FILL).any(), "an output element was not written"
-    return outs[0].cpu().numpy(), (outs[1].cpu().numpy() if sd else None)
 
 
 _same = functools.partial(_same_arrays, equal_nan=True)

@@ -17,25 +17,11 @@ from tests import recon_moments_util as RU
 from tests import summary_util as SU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model,
                                  _model_curves, _padded, _peak, _per_draw_curves, _recon_moments, _refused, _same as _same_arrays)
+from tests.eval_gpu_util import _quantiles
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it: every element must be written
 SETS = list(QU.LEVEL_SETS)
-
-
-def _quantiles(eng, flat, c, is_post, levels, eps="case", ns=None, tile=0, obs_d=None, labels=None):
-    """Engine.recon_quantiles on the case's batch -> numpy [Lv, Q, B, C, T]."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q, Cn = (1 if c["ospec"].gauss else 3), c["obs"].shape[1]
-    out = torch.full((len(levels), Q, c["B"], Cn, c["T"]), FILL, device=DEV)
-    got = eng.recon_quantiles(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, levels, out, tile)
-    assert got is out
-    res = out.cpu().numpy()
-    assert not (res == FILL).any(), "an output element was not written"
-    return res
 
 
 _same = functools.partial(_same_arrays, equal_nan=False)

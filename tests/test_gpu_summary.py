@@ -18,26 +18,10 @@ from tests import recon_moments_util as RU
 from tests import summary_util as SU
 from tests.eval_gpu_util import (ADAPTIVE, DEV, ENV_KEYS, SIZES, WIDTHS, _captured, _count_calls, _device_batch, _engine, _eps_dev, _model,
                                  _model_curves, _padded, _peak, _per_draw_curves, _refused, _same as _same_arrays)
+from tests.eval_gpu_util import _summary
 
 pytestmark = pytest.mark.gpu
 FILL = -12345.5            # the outputs are pre-filled with it (NaN is a value the call writes): every element must be written
-
-
-def _summary(eng, flat, c, is_post, thr, sense=1, eps="case", ns=None, sd=True, p=True, obs_d=None, labels=None):
-    """Engine.curve_summary on the case's batch -> numpy (mean, sd, p_beyond), None where not asked."""
-    if obs_d is None:
-        obs_d, labels = _device_batch(c)
-    ns = ns or c["ns"]
-    e = _eps_dev(c["eps"]) if isinstance(eps, str) else eps
-    Q, Cn = (1 if c["ospec"].gauss else 3), c["obs"].shape[1]
-    mean = torch.full((Q, c["B"], Cn, 8), FILL, device=DEV)
-    sd_t = torch.full_like(mean, FILL) if sd else None
-    pb = torch.full((Q, c["B"], Cn, c["T"]), FILL, device=DEV) if p else None
-    eng.curve_summary(flat, eng.make_batch(obs_d, labels, e, particles=ns), c["B"], is_post, ns, None if thr is None else [float(x) for x in thr], sense,
-                      mean, sd_t, pb)
-    out = tuple(None if t is None else t.cpu().numpy() for t in (mean, sd_t, pb))
-    assert all(t is None or not (t == FILL).any() for t in out), "an output element was not written"
-    return out
 
 
 _same = functools.partial(_same_arrays, equal_nan=True)

@@ -168,6 +168,55 @@ def test_fit_recovers_the_shape_of_an_exact_pareto_tail(k_true):
     assert abs(est.mean() - target) <= 4.0 * sd / math.sqrt(200) + 5.0 / n
 
 
+def _harmonic(l):
+    """The plain importance-sampling estimate -log mean_k exp(-l_k), shifted by the smallest l."""
+    l = np.asarray(l, np.float64)
+    return l.min() - math.log(np.exp(-(l - l.min())).mean())
+
+
+def test_a_tail_that_spans_300_decades_is_left_unsmoothed():
+    """x = [9.09e-309, 4.44e-304, 2.14e-293, 2.99e-264, 1.0] (a challenge_gauss point under the `fitted` regime): x_[n/4] is denormal,
+    1 / (3 x) overflows and b* is 0 / 0.  gpd_fit returns a non-finite pair and raises nothing; psis_point follows the kernel's rule --
+    isfinite(khat) && isfinite(sigma), otherwise unsmoothed with khat = +inf -- so elpd_loo is the plain importance-sampling estimate."""
+    x = np.array([9.09e-309, 4.44e-304, 2.14e-293, 2.99e-264, 1.0])
+    kh, sigma = LU.gpd_fit(x)
+    assert not (np.isfinite(kh) and np.isfinite(sigma))
+    tiny = np.finfo(np.float64).tiny
+    K = 21                                                                                # M = 5: the shortest tail that is fitted at all
+    a = np.concatenate([[0.0], np.log(x[:4] + tiny)[::-1], np.linspace(-800.0, -5000.0, K - 5)])   # rank order; ranks 5 .. under the clamp
+    assert np.all(np.diff(a) < 0) and a[5] < LU.LOG_DBL_MIN < a[4]
+    l = -3.0 - a
+    tail = (np.exp(a[:5]) - tiny)[::-1]
+    assert np.allclose(tail[:4], x[:4], rtol=1e-2) and tail[4] == 1.0                     # the quoted tail, to its three digits
+    for order in (np.arange(K), np.random.default_rng(1).permutation(K)):
+        e, k, n = LU.psis_point(l[order])
+        assert n == 5 and k == np.inf
+        assert abs(e - _harmonic(l)) <= 1e-12 * abs(e)
+
+
+def test_the_clamp_decides_the_tail_where_the_ratios_span_more_than_708_nat():
+    """K = 64 (M = 13): a generalised Pareto tail whose log-ratios are rescaled to span 1100 nat.  The cutoff a_M lies under log DBL_MIN, so
+    cut = log DBL_MIN and n = #{a > log DBL_MIN} < M; the fit runs on exp(a) - DBL_MIN of those ranks alone; draws under the clamp can move
+    further down without changing n, khat or elpd_loo (exp(a) of such a draw is below one fp64 ulp of the largest ratio)."""
+    K, M = 64, 13
+    g = np.random.default_rng(9)
+    r = np.log1p(LU.gpd_sample(0.7, 1.0, K, g))                                           # ascending log-ratios, rank 0 last
+    a = (r - r[-1])[::-1]                                                                 # rank order: a_0 = 0 >= a_1 >= ...
+    a = a * (1100.0 / -a[M])
+    n_want = int((a[:M] > LU.LOG_DBL_MIN).sum())
+    assert a[M] < LU.LOG_DBL_MIN and 5 <= n_want < M
+    l = 2.5 - a
+    e, k, n = LU.psis_point(l[g.permutation(K)])
+    assert n == n_want and np.isfinite(k) and np.isfinite(e)
+    kh, _ = LU.gpd_fit((np.exp(a[:n]) - np.finfo(np.float64).tiny)[::-1])
+    assert k == kh
+    assert e <= LU.lppd(l[:, None])[0] + 1e-12 * abs(e)
+    lower = l.copy()
+    lower[n:] += np.linspace(50.0, 5000.0, K - n)                                         # every draw under the clamp, further down
+    e2, k2, n2 = LU.psis_point(lower)
+    assert (n2, k2) == (n, k) and abs(e2 - e) <= 1e-13 * abs(e)
+
+
 # ---- the Python layer, on an engine double --------------------------------------------------------------------------------------------------
 class _Eng:
     spec = type("S", (), {"latent_dim": 4, "labels_in_main": False})()
