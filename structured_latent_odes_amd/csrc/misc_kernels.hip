@@ -1,12 +1,13 @@
 // Small kernels around the hot path: stage-time table, fixed-order slab reduction, decoder heads, Adam.
 #include "slode_common.h"
+#include "fixed_step.h"
 
 namespace {
 
 // Times at which the fixed-grid solvers evaluate f, with torchdiffeq's fp32 arithmetic (t0 + dt * c, separate
 // multiply and add: no FMA contraction).  Call site replaced: models/blackbox_ode.py:41-45.
 __global__ void stage_times_kernel(const float* __restrict__ times, float* __restrict__ out, int T, int method) {
-  const int R = method == SLODE_EULER ? 1 : (method == SLODE_MIDPOINT ? 2 : 3);
+  const int R = fixed_step_times(method);
   const int nt = R * (T - 1) + 1;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (slode_is_adaptive(method)) { if (i == 0) out[0] = times[T - 1]; return; }
@@ -256,7 +257,7 @@ __global__ void adam_kernel(long long n, const float* __restrict__ g, const Adam
 }  // namespace
 
 hipError_t slode_launch_stage_times(const slode_shape& s, const float* times, float* stage_t, hipStream_t stream) {
-  const int R = s.method == SLODE_EULER ? 1 : (s.method == SLODE_MIDPOINT ? 2 : 3);
+  const int R = fixed_step_times(s.method);
   const int nt = R * (s.T - 1) + 1;
   hipLaunchKernelGGL(stage_times_kernel, dim3((nt + 255) / 256), dim3(256), 0, stream, times, stage_t, s.T, s.method);
   return hipGetLastError();

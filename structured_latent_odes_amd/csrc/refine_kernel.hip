@@ -14,7 +14,7 @@
 //   R5  fixed-order sums over the workgroup -> loss_k
 //   backward (j < J, or j == 0 when grad0 is asked for):
 //   R6  reverse affine scan lambda_n = g_n + A_n lambda_{n+1}, in place over g_x (rf_rev_scan: fwd_scan on the reversed index)
-//   R7  thread <-> step: gA = lambda_{n+1} x_n, gb = lambda_{n+1}; a, d of the step's stages re-evaluated (fwd_ad); rf_step_bwd -> ga[r], gd[r];
+//   R7  thread <-> step: gA = lambda_{n+1} x_n, gb = lambda_{n+1}; a, d of the step's stages re-evaluated (fwd_ad); step_bwd (fixed_step.h) -> ga[r], gd[r];
 //       g_pre_a = ga a (1 - a), g_pre_d = gd d (1 - d) into the table [steps x stages][2 S]
 //   R8  thread <-> (hidden unit j, chunk): sum over the chunk's samples of [h_j > 0] sum_s (g_pre_a W_g + g_pre_d W_d); per-chunk partials
 //   R9  thread j: g_u[j], the chunks in order; thread H + j: the init net's hidden unit from g_o = lambda_0 x0 (1 - x0)
@@ -23,7 +23,6 @@
 // Every sum runs in a fixed order that depends on (K, J, T, L, H) alone: the result is a function of (parameters, inputs, noise) -- bitwise
 // equal between runs, between one workgroup per trajectory and the persistent loop, between in-kernel and explicit noise.  No atomics.
 #include "traj_terms.h"
-#include "refine_step.h"
 
 namespace {
 
@@ -88,7 +87,7 @@ __device__ __forceinline__ void rf_step_table_bwd(const FwdK& k, const FwdSm& sm
         const float lam = s_g[(n + 1) * S + s];
         const float as[4] = {a[0][s], a[1][s], a[2][s], a[3][s]}, ds[4] = {d[0][s], d[1][s], d[2][s], d[3][s]};
         float ga[4], gd[4];
-        rf_step_bwd(k.method, h, as, ds, lam * x[s], lam, ga, gd);
+        step_bwd(k.method, h, as, ds, lam * x[s], lam, ga, gd);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (r < nst) {
@@ -109,7 +108,7 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
   const FwdK& f = k.f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = f.T, L = f.L, S = SC ? SC : f.S, C = f.C, Q = f.Q, H = f.H, nd = k.d.nd, nj = k.nj, B = f.B;
-  const int nst = f.method == SLODE_RK4 ? 4 : f.R;   // stages of one step: euler 1, midpoint 2, rk4 4 (the last one the next step's first)
+  const int nst = fixed_step_evals(f.method, f.R);   // stages of one step: euler 1, midpoint 2, rk4 4 (the last one the next step's first)
   const int nch = RF_NT / H, nsamp = (T - 1) * nst;
   const FwdSm sm = fwd_sm(s_rf, k.o.f);
   const ScoredSm ss = scored_sm(s_rf, k.o.s);
@@ -257,7 +256,7 @@ __global__ void __launch_bounds__(RF_NT) refine_kernel(const RfK k) {
 }
 
 RfLds rf_lds(const slode_shape& s, int nd, bool generic) {
-  const int nst = s.method == SLODE_RK4 ? 4 : (s.method == SLODE_MIDPOINT ? 2 : 1), cap = SLODE_REFINE_LDS_MAX / 4;
+  const int nst = fixed_step_evals(s.method), cap = SLODE_REFINE_LDS_MAX / 4;
   LdsCarve cv;
   RfLds o{};
   o.f = fwd_lds(cv, s, generic);

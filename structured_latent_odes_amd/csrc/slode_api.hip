@@ -1,5 +1,6 @@
 // C ABI of libslode.so (include/slode.h): validation, parameter layout, workspace carving, launch orchestration.
 #include "slode_common.h"
+#include "fixed_step.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -51,7 +52,6 @@ static bool is_adaptive(int method) { return slode_is_adaptive(method); }
 // particles of a step (slode_shape::particles; 0 and 1 both mean one)
 static int particles_of(const slode_shape& s) { return s.particles > 1 ? s.particles : 1; }
 
-static int stages_per_step(int method) { return method == SLODE_EULER ? 1 : (method == SLODE_MIDPOINT ? 2 : 3); }
 
 static const char* check_shape(const slode_shape* s) {
   if (!s) return "shape is NULL";
@@ -204,7 +204,7 @@ int slode_layout_init(const slode_shape* s, slode_layout* lay) {
 int slode_num_stage_times(const slode_shape* s) {
   if (!s || s->T < 2) return SLODE_EINVAL;
   if (is_adaptive(s->method)) return 1;  // adaptive: no table (a 1-element dummy keeps callers uniform)
-  return stages_per_step(s->method) * (s->T - 1) + 1;
+  return fixed_step_times(s->method) * (s->T - 1) + 1;
 }
 
 }  // extern "C"
@@ -1666,7 +1666,7 @@ int slode_joint_band(slode_handle h, const slode_shape* s, const slode_layout* l
 int slode_num_stage_times_n(const slode_shape* s, int n_times) {
   if (!s || n_times < 2 || n_times > SLODE_FORECAST_MAX_T) return SLODE_EINVAL;
   if (is_adaptive(s->method)) return 1;
-  return stages_per_step(s->method) * (n_times - 1) + 1;
+  return fixed_step_times(s->method) * (n_times - 1) + 1;
 }
 
 // slode_stage_times for a grid of n_times points: the same launcher on a shape copy with T = n_times (it reads T and method alone)

@@ -7,7 +7,8 @@
 //                      DrawsK (FwdK, PriorK and where the draws of a call come from: recon, cohort, calibration) and the host functions that
 //                      fill them from slode_shape / slode_layout / DrawsLaunch
 //   prior nets         fwd_prior_at: loc / log scale of one latent dim from the staged labels
-//   step coefficients  fwd_step_coeffs: x' = A x + b of one grid step for euler / midpoint / rk4, the a, d evaluator passed in;
+//   step coefficients  fwd_step_coeffs (fixed_step.h, beside the training kernel's step_fwd): x' = A x + b of one grid step for euler /
+//                      midpoint / rk4, the a, d evaluator passed in;
 //                      fwd_step_table: thread <-> step, the table of a step range [n_lo, n_hi) of the grid (a whole solve: [0, T - 1))
 //   scan               fwd_scan: forward affine scan, one state component per wave pass
 //   label heads        fwd_label_logits: hidden layer and logits of one head on a half-wave
@@ -23,6 +24,7 @@
 #pragma once
 #include <type_traits>
 #include "slode_common.h"
+#include "fixed_step.h"
 
 namespace {   // (internal linkage: every including translation unit has its own copy, as before)
 
@@ -59,7 +61,7 @@ struct DrawsK {
 
 inline void fwd_fill(FwdK& k, const slode_shape& s, const slode_layout& lay, const float* params, const float* times, const float* stage_t) {
   k.B = s.B; k.T = s.T; k.C = s.C; k.L = s.L; k.S = s.S; k.H = s.H;
-  k.method = s.method; k.R = s.method == SLODE_EULER ? 1 : (s.method == SLODE_MIDPOINT ? 2 : 3);
+  k.method = s.method; k.R = fixed_step_times(s.method);
   k.Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
   k.init_w1 = lay.init_w1; k.init_b1 = lay.init_b1; k.init_w2 = lay.init_w2; k.init_b2 = lay.init_b2;
   k.dyn_wh = lay.dyn_wh; k.dyn_bh = lay.dyn_bh; k.dyn_wg = lay.dyn_wg; k.dyn_bg = lay.dyn_bg; k.dyn_wd = lay.dyn_wd; k.dyn_bd = lay.dyn_bd;
@@ -109,50 +111,6 @@ __device__ __forceinline__ bool fwd_prior_at(const PriorK& k, const float* __res
 }
 
 // ---- step coefficients ------------------------------------------------------------------------------------------
-// x' = A x + b of one grid step of size h (f = a(t, z) - d(t, z) x: tests/kernel_math.py step_coeffs); st: the step's stage times;
-// ad(t, a, d): the caller's evaluator of a(t, z), d(t, z) -- eval_stats reads the weights from global memory, the others from the LDS rows
-template <int SM, class AD>
-__device__ __forceinline__ void fwd_step_coeffs(int method, float h, const float* st, const AD& ad, float (&A)[SM], float (&bb)[SM]) {
-  float a[SM], d[SM];
-  ad(st[0], a, d);
-  if (method == SLODE_EULER) {
-#pragma unroll
-    for (int s = 0; s < SM; ++s) { A[s] = 1.f - h * d[s]; bb[s] = h * a[s]; }
-  } else if (method == SLODE_MIDPOINT) {
-    float m[SM], c[SM];
-#pragma unroll
-    for (int s = 0; s < SM; ++s) { m[s] = 1.f - 0.5f * h * d[s]; c[s] = 0.5f * h * a[s]; }
-    ad(st[1], a, d);
-#pragma unroll
-    for (int s = 0; s < SM; ++s) { A[s] = 1.f - h * d[s] * m[s]; bb[s] = h * (a[s] - d[s] * c[s]); }
-  } else {   // torchdiffeq's rk4: the 3/8 rule
-    const float third = 1.0f / 3.0f, h3 = h * third;
-    float p1[SM], q1[SM], p2[SM], q2[SM], c[SM], m[SM];
-#pragma unroll
-    for (int s = 0; s < SM; ++s) { p1[s] = a[s]; q1[s] = -d[s]; c[s] = h3 * p1[s]; m[s] = 1.f + h3 * q1[s]; }
-    ad(st[1], a, d);
-#pragma unroll
-    for (int s = 0; s < SM; ++s) {
-      p2[s] = a[s] - d[s] * c[s]; q2[s] = -d[s] * m[s];
-      c[s] = h * (p2[s] - p1[s] * third); m[s] = 1.f + h * (q2[s] - q1[s] * third);
-    }
-    ad(st[2], a, d);
-#pragma unroll
-    for (int s = 0; s < SM; ++s) {
-      const float p3 = a[s] - d[s] * c[s], q3 = -d[s] * m[s];
-      c[s] = h * (p1[s] - p2[s] + p3); m[s] = 1.f + h * (q1[s] - q2[s] + q3);
-      A[s] = q1[s] + 3.f * (q2[s] + q3); bb[s] = p1[s] + 3.f * (p2[s] + p3);   // (partial sums: q4 / p4 follow)
-    }
-    ad(st[3], a, d);
-    const float G = h * 0.125f;
-#pragma unroll
-    for (int s = 0; s < SM; ++s) {
-      const float p4 = a[s] - d[s] * c[s], q4 = -d[s] * m[s];
-      A[s] = 1.f + G * (A[s] + q4); bb[s] = G * (bb[s] + p4);
-    }
-  }
-}
-
 // the step table of the steps [n_lo, n_hi) of the grid k.times / k.stage_t (a whole solve: n_lo = 0, n_hi = T - 1), thread <-> step: step
 // n_lo + i into pa[i][s] / pb[i][s], i = i_first, i_first + i_stride, ...
 template <int SM, class AD>

@@ -1,19 +1,16 @@
 """CPU tests of the posterior refinement: the C ABI of slode_posterior_refine, its refusal ladder on a hand-filled handle
-(tests/refine_refusals/refine_refusals.cpp), the kernel's reverse step routine on the host (tests/refine_step/refine_step.cpp) against
-tests/kernel_math.py::step_coeffs_bwd, and the test infrastructure the GPU tests rest on (tests/refine_util.py): the weighted likelihood, the
+(tests/refine_refusals/refine_refusals.cpp), and the test infrastructure the GPU tests rest on (tests/refine_util.py): the weighted likelihood, the
 reference gradient against finite differences, the transcription of the kernel's backward formulas against autograd, and every condition the
 GPU tests ask of the kernel shown to hold for the reference alone."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import slode_oracle as O
-from tests import kernel_math as KM
 from tests import refine_util as RU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,41 +97,6 @@ def test_refine_refusals_on_a_hand_filled_handle(tmp_path):
             assert msg == bounds[name].replace("slode_traj_bounds", _N).replace("batch / bounds / ", "batch / loc_out / scale_out / elbo_out / "), \
                 (name, msg, bounds[name])
     assert shared >= 25
-
-
-def test_reverse_step_routine_of_the_kernel_matches_step_coeffs_bwd(tmp_path):
-    """rf_step_bwd (csrc/refine_step.h), compiled for the host and run on 60 random steps per method in fp32, against
-    tests/kernel_math.py::step_coeffs_bwd in fp64: within 1e-5 of the largest stage gradient of the step (a, d in (0, 1), |g| ~ 1, h in
-    (0.05, 0.5): fp32 rounding of a few dozen operations), and exactly 0 in the stages the method does not have."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not present: the host program is not built")
-    exe = str(tmp_path / "refine_step")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-Wall", "-O1", os.path.join(ROOT, "tests", "refine_step", "refine_step.cpp"),
-                        "-o", exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rng = np.random.default_rng(5)
-    rows, lines = [], []
-    for mi, method in enumerate(("euler", "midpoint", "rk4")):
-        for _ in range(60):
-            v = np.concatenate([[rng.uniform(0.05, 0.5)], rng.uniform(0.02, 0.98, 8), rng.normal(size=2)]).astype(np.float32)
-            rows.append((method, v.astype(np.float64)))
-            lines.append("%d " % mi + " ".join("%.9g" % x for x in v))
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = np.array([[float(x) for x in ln.split()] for ln in r.stdout.splitlines()])
-    assert got.shape == (180, 8)
-    worst = 0.0
-    for (method, v), g in zip(rows, got):
-        h, a, d, gA, gb = v[0], v[1:5].reshape(4, 1), v[5:9].reshape(4, 1), v[9:10], v[10:11]
-        _, _, cache = KM.step_coeffs(method, h, a, d)
-        ga, gd = KM.step_coeffs_bwd(method, h, a, d, cache, gA, gb)
-        want = np.concatenate([ga[:, 0], gd[:, 0]])
-        nst = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-        assert np.all(g[nst:4] == 0.0) and np.all(g[4 + nst:] == 0.0) and np.all(want[nst:4] == 0.0)
-        worst = max(worst, np.abs(g - want).max() / np.abs(want).max())
-    print("rf_step_bwd against step_coeffs_bwd: worst error / largest stage gradient %.2e" % worst)
-    assert worst <= 1e-5
 
 
 @pytest.mark.parametrize("case", RU.CASES)
