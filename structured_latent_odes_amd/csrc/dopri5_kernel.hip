@@ -1581,8 +1581,7 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
   k.rng = RngK{}; k.eps_out = nullptr; k.tabs = nullptr;
   if (rec) { k.loc = rec->loc; k.scale = rec->scale; k.eps = rec->eps; k.z_out = rec->z_out; k.rec = rec->rec; k.nrec = rec->nrec; k.kmax = rec->kmax;
              k.rng = rec->rng; k.eps_out = rec->eps_out; k.tabs = rec->tabs; }
-  k.w1 = p + lay.init_w1; k.b1 = p + lay.init_b1; k.w2 = p + lay.init_w2; k.b2 = p + lay.init_b2;
-  k.wh = p + lay.dyn_wh; k.bh = p + lay.dyn_bh; k.wg = p + lay.dyn_wg; k.bg = p + lay.dyn_bg; k.wd = p + lay.dyn_wd; k.bd = p + lay.dyn_bd;
+  slode_solver_tensors(k, p, lay);
   k.rtol = s.rtol > 0.f ? s.rtol : 1e-7f;
   k.atol = s.atol > 0.f ? s.atol : 1e-9f;
   k.max_steps = 20000;
@@ -1599,14 +1598,9 @@ hipError_t slode_launch_dopri5(const slode_shape& s, const slode_layout& lay, co
 
 template <class M>
 static hipError_t launch_bwd(const slode_shape& s, const DpBK& k, int grid, size_t lds, hipStream_t stream) {
-  using grp::BNT;
-  if (s.S == 5) {
-    (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<M, 5, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<M, 5, 25>), dim3(grid), dim3(BNT), lds, stream, k);
-  } else {
-    (void)hipFuncSetAttribute((const void*)grp::dopri5_bwd_kernel<M, 8, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SLODE_LAUNCH("dopri5_bwd", (grp::dopri5_bwd_kernel<M, 8, 25>), dim3(grid), dim3(BNT), lds, stream, k);
-  }
+  auto fn = s.S == 5 ? grp::dopri5_bwd_kernel<M, 5, 25> : grp::dopri5_bwd_kernel<M, 8, 25>;
+  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  SLODE_LAUNCH("dopri5_bwd", fn, dim3(grid), dim3(grp::BNT), lds, stream, k);
   return hipGetLastError();
 }
 
@@ -1621,13 +1615,9 @@ hipError_t slode_launch_dopri5_bwd(const slode_shape& s, const slode_layout& lay
   k.B = s.B; k.T = s.T; k.L = s.L; k.kmax = rec.kmax; k.drop_z = drop_z;
   k.Bd = rec.data_rows > 0 ? rec.data_rows : s.B;
   k.times = times; k.z = rec.z_out; k.gx = gx; k.rec = rec.rec; k.nrec = rec.nrec;
-  k.w1 = p + lay.init_w1; k.b1 = p + lay.init_b1; k.w2 = p + lay.init_w2; k.b2 = p + lay.init_b2;
-  k.wh = p + lay.dyn_wh; k.bh = p + lay.dyn_bh; k.wg = p + lay.dyn_wg; k.bg = p + lay.dyn_bg; k.wd = p + lay.dyn_wd; k.bd = p + lay.dyn_bd;
+  slode_solver_tensors(k, p, lay);
   k.slabs = slabs; k.slab_stride = slab_stride; k.nseg = lay.ode_end - lay.ode_begin;
-  const int ob = lay.ode_begin;
-  k.o_w1 = lay.init_w1 - ob; k.o_b1 = lay.init_b1 - ob; k.o_w2 = lay.init_w2 - ob; k.o_b2 = lay.init_b2 - ob;
-  k.o_wh = lay.dyn_wh - ob; k.o_bh = lay.dyn_bh - ob; k.o_wg = lay.dyn_wg - ob; k.o_bg = lay.dyn_bg - ob;
-  k.o_wd = lay.dyn_wd - ob; k.o_bd = lay.dyn_bd - ob;
+  slode_solver_offsets(k, lay);
   {
     using namespace grp;
     const int grid = slode_dopri5_rows(s);

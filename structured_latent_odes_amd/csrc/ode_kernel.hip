@@ -28,6 +28,7 @@
 //     idle work block for P0 and read from global memory in P7 (ode_cold_global) -- 4 workgroups per CU instead of 2.
 #include "slode_common.h"
 #include "fixed_step.h"
+#include "ode_select.h"   // (and with it ode_layout.h: LdsMap, lds_map, ode_threads_for, ode_block_bound)
 #include <cstdlib>
 #include <vector>
 
@@ -113,104 +114,6 @@ struct OdeK {
   RngK rng;       // on: the guide's noise is drawn here (Philox, slode_common.h) instead of read from eps
   LabelSrc lab;   // n > 0: label columns from the loader's separate tensors instead of the dense u matrix
 };
-
-struct LdsMap {  // offsets in floats
-  int ts, sig, A, x, lam, st, stn, ax, ct, gm, hp, tau, ps, ord, sgs, ewt, epre, epre0, esw, ms, sf, par, uu, auxh, auxd, auxgo, z, gzl, gpl, gls, u, wt, pre0,
-      hid0, x0, go, gp0, gu, red, pf, meta, total;
-};
-
-__host__ __device__ constexpr int pad4(int n) { return (n + 3) & ~3; }
-// samples by which NQ = nthreads / 2S chunks of ceil(nt / NQ) samples overhang the stage-time table; 0 when that is more than 8 rows
-__host__ __device__ constexpr int ode_pad_rows(int nt, int nthreads, int S) {
-  const int nq = nthreads / (2 * S), cl = (nt + nq - 1) / nq, over = nq * cl - nt;
-  return over <= 8 ? over : 0;
-}
-__host__ __device__ constexpr bool ode_full_chunks(int nt, int nthreads, int S) {
-  const int nq = nthreads / (2 * S), cl = (nt + nq - 1) / nq;
-  return nq * cl - nt <= 8;
-}
-__host__ __device__ inline int imax2(int a, int b) { return a > b ? a : b; }
-// Long latents (L >= 32: the proc family's 50): only the parameters the solver phases re-read stay in LDS -- [init b1 | W2 | b2] and
-// [dyn b_h | W_g | b_g | W_d | b_d] -- the prior nets, the L-wide rows of the init net and of the hidden layer and the label heads are
-// read from global memory (L2 / L1 hits: every workgroup reads the same 20 KB) by the few phases that touch them once per trajectory.
-// 22 KB of LDS per workgroup less: 4 workgroups per CU instead of 2 for BASELINE config[2]'s shapes.
-__host__ __device__ constexpr bool ode_cold_global(int L_) { return L_ >= 32; }
-__host__ __device__ constexpr int ode_hot_r1(int S, int H) { return H + S * H + S; }            // b1 | W2 | b2
-__host__ __device__ constexpr int ode_hot_r2(int S, int H) { return H + 2 * (S * H + S); }      // b_h | W_g | b_g | W_d | b_d
-__host__ __device__ constexpr int ode_hot_floats(int S, int H) { return ode_hot_r1(S, H) + ode_hot_r2(S, H); }
-
-// `one`: loop-free form (one workgroup per trajectory): softplus(constant_std) stays in registers, no s_sig.
-// The block A | x | lam | st is one work region: besides the scan operands it holds, at different times, the piecewise-linear table of
-// the dynamics heads (P1), the stage-0 exchange rows / dLoss/dmu (P1, P3), the per-sample gradient rows G[nt][2S] (P5 -> P6) and the
-// staged encoder head weights (P7).
-// `scorer`: the shape-specialised solver-free scorer (ALG 3) touches neither the scan operands A / lam, nor the sample rows, the chunk
-// sums, GM | GT or the event arrays: they get no space (their offsets alias what follows; nothing reads or writes them).
-__host__ __device__ inline LdsMap lds_map(int T, int S, int H, int C, int L, int Q, int nt, int npar, int nthreads, int naux, bool one,
-                                          bool scorer = false) {
-  LdsMap m;
-  int o = 0;
-  if (scorer) {
-    m.ts = o; o += pad4(nt);
-    m.sig = o; o += one ? 0 : pad4(C * T);
-    m.ax = pad4(T * S);
-    m.A = o; m.lam = o;                 // (unused)
-    m.x = o; o += m.ax;
-    m.st = o; m.stn = pad4(Q * C * T); o += m.stn;   // dLoss/dmu [Q*C][T]
-    m.ct = o; m.gm = o;                 // (unused)
-    m.hp = o; o += pad4(4 * Q * C * S);
-    m.tau = m.ps = m.ord = m.sgs = m.ewt = m.epre = m.epre0 = m.esw = m.ms = m.sf = o;   // (unused)
-  } else {
-  // P6 reads the sample rows in chunks of CL = ceil(nt / NQ) samples: when the last chunk overhangs the table by a few samples, zero
-  // pad rows (and pad stage times) make every chunk full, and the contraction needs no bounds at all (ode_pad_rows)
-  const int padr = ode_pad_rows(nt, nthreads, S);
-  m.ts = o; o += pad4(nt + padr);
-  m.sig = o; o += one ? 0 : pad4(C * T);
-  const int tabn = (H + 1) * 4 * S;   // table rows [H+1][V (2S) | slope (2S)]
-  m.ax = imax2(pad4(T * S), pad4((tabn + 2) / 3));
-  m.A = o; o += m.ax;
-  m.x = o; o += m.ax;
-  m.lam = o; o += m.ax;
-  int stn = imax2(((2 * S + 4) & ~3) * T, Q * C * T);   // stage-0 exchange rows [T][SP]; dLoss/dmu [Q*C][T]
-  stn = imax2(stn, (nt + padr) * 2 * S - 3 * m.ax);     // G rows (+ pad rows) overlay the whole block
-  m.st = o; m.stn = pad4(stn); o += m.stn;
-  m.ct = o; o += pad4((nthreads / (2 * S) + 1) * 4 * S);   // chunk sums [NQ (+1: total)][sum g (2S) | sum g t (2S)]
-  m.gm = o; o += 2 * 2 * S * 32;                        // GM | GT: [2][2S][32] (unit H = the constant-1 unit)
-  m.hp = o; o += pad4(4 * Q * C * S);                   // head-weight partials [hsplit][Q*C*S]
-  m.tau = o; o += 32;
-  m.ps = o; o += 32;
-  m.ord = o; o += 32;
-  m.sgs = o; o += 32;
-  m.ewt = o; o += 32;
-  m.epre = o; o += 32;
-  m.epre0 = o; o += 32;
-  m.esw = o; o += 32 * 2 * S;                           // events in table order: sign * W[c][unit], [32][2S]
-  m.ms = o; o += 32;
-  m.sf = o; o += 32;
-  }
-  m.uu = o; o += SLODE_MAX_NU;
-  m.z = o; o += pad4(L);
-  m.gzl = o; o += pad4(L);
-  m.gpl = o; o += pad4(2 * L);  // [d(-log p)/d prior loc | eps]
-  m.gls = o; o += pad4(2 * L);  // [d(-log p)/d prior log-scale | guide scale]
-  m.u = o; o += 32;
-  m.wt = o; o += 32;
-  m.pre0 = o; o += 32;
-  m.hid0 = o; o += 32;
-  m.x0 = o; o += 8;
-  m.go = o; o += 8;
-  m.gp0 = o; o += 32;
-  m.gu = o; o += 32;
-  m.red = o; o += 16;
-  m.pf = o; o += 3 * pad4(L);
-  m.meta = o; o += pad4(L) * 8;   // per latent dim: prior-net offsets (ints), see setup
-  // everything above depends on (T, S, C, L, Q, method, nthreads) only: compile-time offsets in the shape-specialised instantiations
-  m.auxh = o; o += naux * 32;   // label heads scored in the main loss only
-  m.auxd = o; o += naux * 32;
-  m.auxgo = o; o += pad4(naux * 12);
-  m.par = o; o += pad4(npar);      // [priors | init net | dynamics | heads]: the gradient of every element goes straight to the slab
-  m.total = o;
-  return m;
-}
 
 // a(t), d(t): models/blackbox_ode.py:97-109 with the z-part of the hidden pre-activation (s_u) hoisted.
 // The 2*S*H head weights arrive as SGPR operands (s_load through the constant address space), ONE ROW AHEAD of the row being
@@ -406,25 +309,6 @@ __device__ __forceinline__ void block_affine_scan(const float* __restrict__ s_A,
       s_v[(REV ? i : i + 1) * S + s] = y;
     }
   }
-}
-
-__host__ __device__ constexpr int ode_threads_for(int T, int Q, int C, int S) {
-  // waves >= 1 carry the head-gradient role (one (q,c,s) entry per thread) next to the adjoint scan on wave 0
-  const int nt = ((T + 63) / 64) * 64, need = 64 + ((Q * C * S + 63) / 64) * 64;
-  return nt < need ? need : nt;
-}
-
-// Register budget = 512 / (waves per SIMD the declared block size forces).  Loop-free forms fit 128 (S = 5) / 168-256 (S = 8, short
-// grids) without spilling.  The persistent-loop forms hoist kernel-argument loads and need more: the specialised ones declare their
-// exact block size, the generic ones cap the grid length they accept (512 threads) -- NO instantiation may spill a VGPR
-// (tools/check_spills.py).
-__host__ __device__ constexpr int ode_max_threads(int S, int T_, int C_, int Q_, bool one, bool bwd) {
-  if (!one && bwd) return T_ > 0 ? ode_threads_for(T_, Q_, C_, S) : 512;
-  return (S > 5 || (T_ > 0 && T_ <= 128)) ? 768 : 1024;
-}
-
-__host__ __device__ constexpr int ode_block_bound(int S, int T_, int C_, int Q_, bool one, bool bwd, int pk) {
-  return pk > 1 ? pk * ode_threads_for(T_ ? T_ : 1, Q_ ? Q_ : 1, C_ ? C_ : 1, S) : ode_max_threads(S, T_, C_, Q_, one, bwd);
 }
 
 // Kernel algorithm variants (ALG).  The dynamics net never sees the state and its hidden layer is relu(w_t t + u_j(z)): every unit is
@@ -1980,62 +1864,30 @@ ode_elbo_kernel(const float* __restrict__ pl_stage_t, const float* __restrict__ 
   STAMP(11);
 }
 
-template <int S, int H, bool BWD, int T_, int C_, int L_, int Q_, int M_, bool RA, bool ONE, int ALG, int PK = 1, bool ENCF = false, bool SOFTB = false>
-hipError_t launch_one(const OdeK& k, int grid, int nthreads, size_t lds, hipStream_t stream) {
-  auto fn = ode_elbo_kernel<S, H, BWD, T_, C_, L_, Q_, M_, RA, ONE, ALG, PK, ENCF, SOFTB>;
-  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (PK > 1 && k.particles > 1) return hipErrorInvalidValue;   // (refused by the caller: the packed forms take one particle)
-  SLODE_LAUNCH("ode_elbo", fn, dim3(grid, k.particles), dim3(nthreads), lds, stream, k.stage_t, k.pseg, k.loc ? k.loc : k.z_in, k.loc ? k.scale : nullptr,
-               k.eps, k.u, k.sigtab ? k.sigtab : k.cstd, k);
-  return hipGetLastError();
-}
-
-// one = loop-free form (every trajectory has its own workgroup); ra = reference_adjoint backward
-template <int S, int H, int T_ = 0, int C_ = 0, int L_ = 0, int Q_ = 0, int M_ = -1>
-hipError_t launch_sh(const OdeK& k, int grid, int nthreads, size_t lds, bool bwd, bool one, bool ra, hipStream_t stream) {
-  if (!bwd) return launch_one<S, H, false, T_, C_, L_, Q_, M_, false, false, 0>(k, grid, nthreads, lds, stream);
-  if (one) {
-    if (ra) return launch_one<S, H, true, T_, C_, L_, Q_, M_, true, true, 0>(k, grid, nthreads, lds, stream);
-    return launch_one<S, H, true, T_, C_, L_, Q_, M_, false, true, 0>(k, grid, nthreads, lds, stream);
+// the launch step: ode_dispatch (ode_select.h) names the instantiation of a variant, this launches it
+template <int S, int H, bool BWD, int T_, int C_, int L_, int Q_, int M_, bool RA, bool ONE, int ALG, int PK, bool ENCF, bool SOFTB>
+struct LaunchOne {
+  static hipError_t run(const OdeK& k, const OdeVariant& v, hipStream_t stream) {
+    auto fn = ode_elbo_kernel<S, H, BWD, T_, C_, L_, Q_, M_, RA, ONE, ALG, PK, ENCF, SOFTB>;
+    (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds);
+    if (PK > 1 && k.particles > 1) return hipErrorInvalidValue;   // (refused by the caller: the packed forms take one particle)
+    SLODE_LAUNCH("ode_elbo", fn, dim3(v.grid, k.particles), dim3(v.nthreads), v.lds, stream, k.stage_t, k.pseg, k.loc ? k.loc : k.z_in,
+                 k.loc ? k.scale : nullptr, k.eps, k.u, k.sigtab ? k.sigtab : k.cstd, k);
+    return hipGetLastError();
   }
-  if (ra) return launch_one<S, H, true, T_, C_, L_, Q_, M_, true, false, 0>(k, grid, nthreads, lds, stream);
-  return launch_one<S, H, true, T_, C_, L_, Q_, M_, false, false, 0>(k, grid, nthreads, lds, stream);
-}
+};
 
 }  // namespace
 
-// shapes whose loop-free backward kernel has an instantiation that runs the encoder forward itself (ENCF): the metric shape
-bool slode_ode_can_fuse_encoder(const slode_shape& s, bool bwd, int grid) {
-  const int Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
-  return bwd && grid == s.B && s.H == 25 && s.S == 5 && s.T == 200 && s.C == 3 && s.L == 8 && Q == 3 && s.method == SLODE_RK4 && s.Hc <= 52;
-}
+int slode_ode_threads(const slode_shape& s) { return ode_threads_for(s.T, ode_heads(s), s.C, s.S); }
 
-int slode_ode_threads(const slode_shape& s) {
-  return ode_threads_for(s.T, s.likelihood == SLODE_GAUSS ? 1 : 3, s.C, s.S);
-}
-
-static int n_stage(const slode_shape& s) {
-  const int R = fixed_step_times(s.method);
-  return R * (s.T - 1) + 1;
-}
-
-// the shape-specialised instantiations with a long latent keep only the hot parameter ranges in LDS (ode_cold_global): BASELINE config[2]
-static bool static_cold(const slode_shape& s, bool force_generic) {
-  const int Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
-  return !force_generic && s.H == 25 && s.S == 8 && s.T == 100 && s.C == 4 && s.L == 50 && Q == 3 &&
-         (s.method == SLODE_RK4 || s.method == SLODE_EULER) && ode_cold_global(s.L);
-}
-static int lds_npar(const slode_shape& s, const slode_layout& lay, bool force_generic, bool ext) {   // (occupancy estimates only)
-  const bool st = static_cold(s, force_generic) && (ext ? s.method == SLODE_EULER : s.method == SLODE_RK4);
-  return st ? ode_hot_floats(s.S, s.H) : lay.cstd - lay.ode_begin;
-}
-
+// (occupancy estimates only: the product form of the shape's launch, without the handle's arms)
 size_t slode_ode_lds_bytes(const slode_shape& s, int nthreads, bool one) {
   slode_layout lay;
   slode_layout_init(&s, &lay);
-  const int Q = s.likelihood == SLODE_GAUSS ? 1 : 3;
-  const LdsMap m = lds_map(s.T, s.S, s.H, s.C, s.L, Q, n_stage(s), lds_npar(s, lay, false, false), nthreads, s.aux_in_main ? s.n_aux : 0, one);
-  return (size_t)m.total * sizeof(float);
+  // the shape-specialised instantiations with a long latent keep only the hot parameter ranges in LDS (ode_cold_global): BASELINE config[2]
+  const int npar = ode_shape_is(s, ODE_C2) && ode_cold_global(s.L) ? ode_hot_floats(s.S, s.H) : lay.cstd - lay.ode_begin;
+  return sizeof(float) * (size_t)lds_map(s.T, s.S, s.H, s.C, s.L, ode_heads(s), ode_stage_times(s), npar, nthreads, s.aux_in_main ? s.n_aux : 0, one).total;
 }
 
 hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, size_t errlen) {
@@ -2044,7 +1896,7 @@ hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, s
   OdeK k;
   k.B = s.B; k.T = s.T; k.C = s.C; k.L = s.L; k.nu = s.n_u; k.ng = s.n_groups; k.method = s.method;
   k.R = fixed_step_times(s.method);
-  k.nt = n_stage(s);
+  k.nt = ode_stage_times(s);
   k.gauss = s.likelihood == SLODE_GAUSS;
   k.Q = k.gauss ? 1 : 3;
   k.uses_next = s.method == SLODE_RK4;
@@ -2059,15 +1911,12 @@ hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, s
     k.o_ploc_w[g] = lay.ploc_w[g] - ob; k.o_ploc_b[g] = lay.ploc_b[g] - ob;
     k.o_pls_w[g] = lay.pls_w[g] - ob;   k.o_pls_b[g] = lay.pls_b[g] - ob;
   }
-  k.w1 = p + lay.init_w1; k.b1 = p + lay.init_b1; k.w2 = p + lay.init_w2; k.b2 = p + lay.init_b2;
-  k.wh = p + lay.dyn_wh; k.bh = p + lay.dyn_bh; k.wg = p + lay.dyn_wg; k.bg = p + lay.dyn_bg;
-  k.wd = p + lay.dyn_wd; k.bd = p + lay.dyn_bd;
+  slode_solver_tensors(k, p, lay);
   for (int q = 0; q < SLODE_MAX_HEADS; ++q) { k.head[q] = p + lay.head_w[q]; k.o_head[q] = lay.head_w[q] - ob; }
   k.cstd = p + lay.cstd;
   k.sigtab = a.sigtab;
-  k.o_w1 = lay.init_w1 - ob; k.o_b1 = lay.init_b1 - ob; k.o_w2 = lay.init_w2 - ob; k.o_b2 = lay.init_b2 - ob;
-  k.o_wh = lay.dyn_wh - ob; k.o_bh = lay.dyn_bh - ob; k.o_wg = lay.dyn_wg - ob; k.o_bg = lay.dyn_bg - ob;
-  k.o_wd = lay.dyn_wd - ob; k.o_bd = lay.dyn_bd - ob; k.o_cstd = lay.cstd - ob;
+  slode_solver_offsets(k, lay);
+  k.o_cstd = lay.cstd - ob;
   k.nseg = lay.ode_end - lay.ode_begin;
   k.npar = lay.cstd - lay.ode_begin;
   k.n_aux = (a.with_ll && s.aux_in_main) ? s.n_aux : 0; k.U = s.U; k.aux_mult = s.aux_mult;
@@ -2091,8 +1940,6 @@ hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, s
   if (k.lab.n > 0 && !k.u) k.u = k.lab.p[0];   // (non-null = "this launch has labels"; the reads go through the accessor)
   if (k.rng.on && !k.eps) k.eps = k.loc;       // (never dereferenced: a valid address for the preloaded argument)
 
-  const int nthreads = slode_ode_threads(s);
-  const bool bwd = a.backward != 0;
   {
     // which elements of the segment [ode_begin, cstd) a backward launch writes (owner threads in P6 (C) / P7); the rest carry no
     // gradient in this launch and are written as zeros: e.g. the label heads when the main loss does not score them, the unused
@@ -2125,100 +1972,10 @@ hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, s
       i = j;
     }
   }
-  // loop-free form when every trajectory has its own workgroup (the grid policy is the caller's: ode_grid_for)
-  const bool one = bwd && a.grid == s.B && !a.force_loop;
-  const bool ra = bwd && s.grad_mode == SLODE_GRAD_REFERENCE_ADJOINT;
-  // which launches take a long-latent shape-specialised instantiation (cold parameters in global memory, ode_cold_global) -- decided
-  // here, ONCE, for the LDS size and for the dispatch below
-  const bool shape_c2 = s.H == 25 && s.S == 8 && s.T == 100 && s.C == 4 && s.L == 50 && k.Q == 3;
-  bool aux16 = true;   // the scorer's cold-parameter path keeps a label head's weight row in 16 registers
-  for (int q = 0; q < s.n_aux; ++q) aux16 = aux16 && s.aux[q].z_dim <= 16;
-  const bool static_scorer = a.x_ext && !a.force_generic && a.alg == 0 && !ra && shape_c2 && aux16 && s.method == SLODE_EULER && (!bwd || one);
-  bool static_c2 = !a.x_ext && !a.force_generic && a.alg == 0 && shape_c2 && s.method == SLODE_RK4;
-  if (static_c2) {
-    // its cold parameter ranges [priors | W_1], W_z and the label heads are staged in the idle work block A | x | lam | st during P0
-    // (COLDB): they must fit (they do for the reference's proc config: 4713 of 4768 floats); another split of the same dims may not
-    const LdsMap mc = lds_map(s.T, s.S, s.H, s.C, s.L, k.Q, k.nt, ode_hot_floats(s.S, s.H), nthreads, k.n_aux_lds, one);
-    const int cold = k.o_b1 + s.H * (1 + s.L) + (k.n_aux > 0 ? k.npar - k.o_aux_w1[0] : 0);
-    if (cold > 3 * mc.ax + mc.stn || k.o_b1 < 0) static_c2 = false;
-  }
-  const int npar_lds = (static_scorer || static_c2) ? ode_hot_floats(s.S, s.H) : k.npar;
-  const size_t lds = sizeof(float) * (size_t)lds_map(s.T, s.S, s.H, s.C, s.L, k.Q, k.nt, npar_lds, nthreads, k.n_aux_lds, one).total;
-  {
-    const LdsMap m = lds_map(s.T, s.S, s.H, s.C, s.L, k.Q, k.nt, npar_lds, nthreads, k.n_aux_lds, one);
-    // z_loc.weight | z_loc.bias | z_scale.0.weight must be one block of the flat vector and fit the stage buffer
-    k.stage_encw = (k.g_pre != nullptr && 2 * s.L * s.Hc + s.L <= m.stn && lay.zloc_b == lay.zloc_w + s.L * s.Hc &&
-                    lay.zls_w == lay.zloc_b + s.L) ? 1 : 0;
-  }
-  if (lds > 160 * 1024) {
-    snprintf(err, errlen, "ode kernel needs %zu B of LDS (> 160 KiB): T=%d S=%d too large", lds, s.T, s.S);
-    return hipErrorInvalidValue;
-  }
-  {
-    const int cap = ode_max_threads(s.S, 0, 0, 0, one, bwd);   // the generic instantiation's declared block size
-    if (nthreads > cap) {
-      snprintf(err, errlen, "ode kernel: ode_state_dim %d with %s supports at most %d time points (got T=%d)", s.S,
-               (one || !bwd) ? "one workgroup per trajectory" : "the persistent-loop grid (B > 65536)", cap, s.T);
-      return hipErrorInvalidValue;
-    }
-  }
-  // measured A/B arms: direct evaluation of the dynamics heads, MFMA contraction -- metric shape, exact gradients, loop-free
-  if (a.alg != 0 && bwd) {
-    if (!(s.H == 25 && s.S == 5 && s.T == 200 && s.C == 3 && s.L == 8 && k.Q == 3 && s.method == SLODE_RK4 && one && !ra && !a.x_ext)) {
-      snprintf(err, errlen, "ode kernel variant %d is instantiated for the metric shape only (cvs T=200 L=8 rk4, exact gradients, B <= 65536)", a.alg);
-      return hipErrorInvalidValue;
-    }
-    if (a.alg == 1) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 1>(k, a.grid, nthreads, lds, stream);
-    if (a.alg == 2) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 2>(k, a.grid, nthreads, lds, stream);
-    snprintf(err, errlen, "unknown ode kernel variant %d", a.alg);
-    return hipErrorInvalidValue;
-  }
-  // fused encoder forward (metric shape, loop-free, folded encoder path): the caller skipped the enc_fwd2 launch
-  if (a.enc_fuse) {
-    if (!slode_ode_can_fuse_encoder(s, bwd, a.grid) || a.alg != 0 || a.x_ext || a.force_generic || a.force_loop || (a.pack && a.pack < 10)) {
-      snprintf(err, errlen, "ode kernel: the fused encoder forward has no instantiation for this launch");
-      return hipErrorInvalidValue;
-    }
-    // packed forms with the shared encoder pass and per-trajectory barriers (SOFTB): pack = 12 / 14 -> 2 / 4 trajectories per workgroup
-    const int pk = a.pack == 14 ? 4 : (a.pack == 12 ? 2 : 1);
-    const size_t lds_pk = (size_t)pk * lds + (size_t)pk * 256 + 64;
-    if (pk > 1 && s.B % pk == 0 && lds_pk <= 160 * 1024) {
-      if (pk == 4) {
-        if (ra) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, true, true, 0, 4, true, true>(k, a.grid / 4, nthreads * 4, lds_pk, stream);
-        return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 0, 4, true, true>(k, a.grid / 4, nthreads * 4, lds_pk, stream);
-      }
-      if (ra) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, true, true, 0, 2, true, true>(k, a.grid / 2, nthreads * 2, lds_pk, stream);
-      return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 0, 2, true, true>(k, a.grid / 2, nthreads * 2, lds_pk, stream);
-    }
-    if (ra) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, true, true, 0, 1, true>(k, a.grid, nthreads, lds + 256, stream);
-    return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 0, 1, true>(k, a.grid, nthreads, lds + 256, stream);
-  }
-  // packed form: four trajectories per workgroup (metric shape, loop-free, batch a multiple of four)
-  if (a.pack == 4 && one && a.alg == 0 && !a.x_ext && !a.force_generic && s.B % 4 == 0 && 4 * lds <= 160 * 1024 &&
-      s.H == 25 && s.S == 5 && s.T == 200 && s.C == 3 && s.L == 8 && k.Q == 3 && s.method == SLODE_RK4) {
-    if (ra) return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, true, true, 0, 4>(k, a.grid / 4, nthreads * 4, 4 * lds, stream);
-    return launch_one<5, 25, true, 200, 3, 8, 3, SLODE_RK4, false, true, 0, 4>(k, a.grid / 4, nthreads * 4, 4 * lds, stream);
-  }
-  // the scorer of BASELINE config[2] as written (proc, dopri5): shape-specialised, solver phases compiled out
-  if (static_scorer) {
-    const size_t lds_sc = sizeof(float) * (size_t)lds_map(s.T, s.S, s.H, s.C, s.L, k.Q, k.nt, npar_lds, nthreads, k.n_aux_lds, one, true).total;
-    if (!bwd) return launch_one<8, 25, false, 100, 4, 50, 3, SLODE_EULER, false, false, 3>(k, a.grid, nthreads, lds_sc, stream);
-    if (one) return launch_one<8, 25, true, 100, 4, 50, 3, SLODE_EULER, false, true, 3>(k, a.grid, nthreads, lds_sc, stream);
-  }
-  // shape-specialised instantiations (compile-time LDS offsets, loop bounds, solver): the BASELINE.json shapes and the reference default
-  if (s.H == 25 && !a.x_ext && !a.force_generic) {
-#define SLODE_STATIC(SS, TT, CC, LL, QQ, MM)                                                              \
-    if (s.S == SS && s.T == TT && s.C == CC && s.L == LL && k.Q == QQ && s.method == MM)                  \
-      return launch_sh<SS, 25, TT, CC, LL, QQ, MM>(k, a.grid, nthreads, lds, bwd, one, ra, stream)
-    SLODE_STATIC(5, 200, 3, 8, 3, SLODE_RK4);        // configs [1] / [3]: cvs, latent 3+3+2, ALD
-    SLODE_STATIC(5, 100, 3, 4, 3, SLODE_RK4);        // config [0]: cvs, latent 1+1+2
-    if (static_c2) return launch_sh<8, 25, 100, 4, 50, 3, SLODE_RK4>(k, a.grid, nthreads, lds, bwd, one, ra, stream);   // config [2] shapes: proc, fixed grid
-    SLODE_STATIC(5, 300, 4, 15, 1, SLODE_RK4);       // config [4]: challenge, Gauss
-    SLODE_STATIC(5, 86, 3, 15, 3, SLODE_MIDPOINT);   // reference default: training_cvs.py, config_cvs.py
-#undef SLODE_STATIC
-  }
-  if (s.H == 25 && s.S == 5) return launch_sh<5, 25>(k, a.grid, nthreads, lds, bwd, one, ra, stream);
-  if (s.H == 25 && s.S == 8) return launch_sh<8, 25>(k, a.grid, nthreads, lds, bwd, one, ra, stream);
-  snprintf(err, errlen, "ode kernel is instantiated for (ode_state_dim, ode_hidden_dim) in {(5,25),(8,25)}; got (%d,%d)", s.S, s.H);
-  return hipErrorInvalidValue;
+  const OdeVariant v = ode_select(a, k.npar, k.n_aux_lds, err, errlen);
+  if (!v.ok) return hipErrorInvalidValue;
+  // z_loc.weight | z_loc.bias | z_scale.0.weight must be one block of the flat vector and fit the stage buffer
+  k.stage_encw = (k.g_pre != nullptr && 2 * s.L * s.Hc + s.L <= v.stn && lay.zloc_b == lay.zloc_w + s.L * s.Hc &&
+                  lay.zls_w == lay.zloc_b + s.L) ? 1 : 0;
+  return ode_dispatch<LaunchOne>(v, k, v, stream);
 }

@@ -1,6 +1,7 @@
 // C ABI of libslode.so (include/slode.h): validation, parameter layout, workspace carving, launch orchestration.
 #include "slode_common.h"
 #include "fixed_step.h"
+#include "ode_select.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -645,8 +646,8 @@ static int step_encode(Step& p, FoldLaunch& fl, bool* enc_fused) {
   if (c.phase == STEP_APPLY) { fl.gslabs = c.payload; fl.n_gslabs = 1; return SLODE_OK; }
   fl.gslabs = w.gslabs; fl.n_gslabs = w.gsplit; fl.sigtab = w.sigtab;   // (the aux step does not read the table; the next main step may)
   // the loop-free ODE kernel of the metric shape runs the encoder forward of its own trajectories (ode_kernel.hip, ENCF): fold only
-  *enc_fused = !p.aux && !p.dp5 && p.bwd && h->enc_fuse && !h->ode_loop && !h->ode_generic && h->ode_alg == 0 &&
-               (h->ode_pack == 0 || h->ode_pack >= 10) && !c.x_out && slode_ode_can_fuse_encoder(s, p.bwd, w.ode_grid);
+  *enc_fused = !p.aux && h->enc_fuse && !c.x_out &&
+               ode_takes_encf(s, p.bwd, w.ode_grid, p.dp5, h->ode_loop, h->ode_generic, h->ode_alg, h->ode_pack);   // (dp5: score_ode's launch has x_ext)
   fl.skip_enc = *enc_fused ? 1 : 0;
   return fold_fwd(h, c, fl, *enc_fused);
 }

@@ -474,7 +474,7 @@ struct OdeLaunch {
   int ext_skip = 0;               // 1: the scorer does not write the zeros of the slab row's solver-side range [init net | dynamics] --
                                   // only when the consumer of the rows (stage 1 of the fused tail, Stage1::zr_*) does not read them
   int force_loop = 0, force_generic = 0, alg = 0;   // handle flags (slode_ctx)
-  int enc_fuse = 0;      // 1: the kernel runs the encoder forward of its trajectories itself (ENCF; slode_ode_can_fuse_encoder), from
+  int enc_fuse = 0;      // 1: the kernel runs the encoder forward of its trajectories itself (ENCF; ode_takes_encf, ode_select.h), from
   const float *enc_weff = nullptr, *enc_beff = nullptr;   // the fold launch's W_eff [Hc][C*T] / b_eff [Hc]; obs must be dense rows (sb == C*T)
   float* enc_hid_out = nullptr;                          // saved tanh [B][Hc]
   int pack = 0;          // 4: four trajectories per workgroup where the shape has such an instantiation (ode_kernel.hip, PK)
@@ -485,7 +485,18 @@ struct OdeLaunch {
 hipError_t slode_launch_ode(const OdeLaunch& a, hipStream_t stream, char* err, size_t errlen);
 size_t slode_ode_lds_bytes(const slode_shape& s, int nthreads, bool one = false);
 int slode_ode_threads(const slode_shape& s);
-bool slode_ode_can_fuse_encoder(const slode_shape& s, bool bwd, int grid);
+
+// The solver-side tensors [init net | dynamics] of a kernel-argument struct (OdeK, DpK, DpBK): pointers into the flat parameter vector ...
+template <class K> inline void slode_solver_tensors(K& k, const float* p, const slode_layout& lay) {
+  k.w1 = p + lay.init_w1; k.b1 = p + lay.init_b1; k.w2 = p + lay.init_w2; k.b2 = p + lay.init_b2;
+  k.wh = p + lay.dyn_wh; k.bh = p + lay.dyn_bh; k.wg = p + lay.dyn_wg; k.bg = p + lay.dyn_bg; k.wd = p + lay.dyn_wd; k.bd = p + lay.dyn_bd;
+}
+// ... and offsets relative to lay.ode_begin (accumulator / slab index = 1 + offset)
+template <class K> inline void slode_solver_offsets(K& k, const slode_layout& lay) {
+  const int ob = lay.ode_begin;
+  k.o_w1 = lay.init_w1 - ob; k.o_b1 = lay.init_b1 - ob; k.o_w2 = lay.init_w2 - ob; k.o_b2 = lay.init_b2 - ob;
+  k.o_wh = lay.dyn_wh - ob; k.o_bh = lay.dyn_bh - ob; k.o_wg = lay.dyn_wg - ob; k.o_bg = lay.dyn_bg - ob; k.o_wd = lay.dyn_wd - ob; k.o_bd = lay.dyn_bd - ob;
+}
 
 struct EncLaunch {
   slode_shape s;

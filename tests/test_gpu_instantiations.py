@@ -1,8 +1,9 @@
 """Every compiled instantiation of the fused ODE/ELBO kernel is a parity-test case.
 
-The launcher (csrc/ode_kernel.hip, slode_launch_ode) picks, for a backward launch, one of
-    {five shape-specialised instantiations, generic}  x  {loop-free, persistent loop}  x  {exact, reference_adjoint}
-and for a forward-only launch {specialised, generic}.  Round 1 shipped persistent-loop kernels no test reached, one of which was
+The selection (csrc/ode_select.h: ode_select, called by slode_launch_ode) picks, for a backward launch, one of
+    {the five named shapes of its table ode_shapes, generic}  x  {loop-free, persistent loop}  x  {exact, reference_adjoint}
+and for a forward-only launch {specialised, generic}; which instantiation a given launch takes, with how many bytes of LDS, is checked
+row by row on the CPU (tests/test_ode_select_cpu.py), and here every one of them runs.  Round 1 shipped persistent-loop kernels no test reached, one of which was
 wrong (a compiler-placed VGPR spill under the wrong EXEC mask: DESIGN 3.1).  Here every combination runs against the fp64 oracle:
   * loop-free: one workgroup per trajectory (the default up to 65,536 trajectories);
   * persistent loop: forced through the handle flags SLODE_ODE_LOOP + SLODE_ODE_GRID=5 (read once at slode_create), so that each of 5
@@ -22,7 +23,7 @@ from oracle import slode_oracle as O
 pytestmark = pytest.mark.gpu
 
 SHAPES = {
-    # the launcher's SLODE_STATIC list (ode_kernel.hip): (family, spec kwargs, T)
+    # the named shapes of ode_shapes (csrc/ode_select.h), in its order: (family, spec kwargs, T)
     "c1_cvs_T200_L8_rk4": ("cvs", dict(z_iext=3, z_rtpr=3, z_eps=2, solver="rk4"), 200),
     "c0_cvs_T100_L4_rk4": ("cvs", dict(z_iext=1, z_rtpr=1, z_eps=2, solver="rk4"), 100),
     "c2_proc_T100_L50_rk4": ("proc", dict(z_g=10, z_eps=10, solver="rk4"), 100),
