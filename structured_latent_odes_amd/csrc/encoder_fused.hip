@@ -13,6 +13,7 @@
 // Requires each trajectory's C*T observations to be one dense block (sb == C*T, {sc, st} == {1, C} or {T, 1}); other strides
 // use the layer-by-layer kernels of encoder_kernels.hip.
 #include "slode_common.h"
+#include "fold_math.h"
 
 typedef const __attribute__((address_space(4))) float* cptr;
 
@@ -55,32 +56,41 @@ __device__ __forceinline__ int kappa_of(const FoldK& k, int c, int t) { return k
 
 // ---- fold: W_eff, rowsum, b_eff, w' ---------------------------------------------------------------------------------
 constexpr int WPB = 128;   // W_eff outputs per block of weff_kernel
-constexpr int WFG = 4;     // threads per output (filter groups): 8 waves per CU instead of 4 -- the output loop is latency-bound
+constexpr int WFG = FOLD_WFG;   // threads per output (filter groups): one quad
 constexpr int WNT = WPB * WFG;
+#ifndef SLODE_FOLD_TW
+#define SLODE_FOLD_TW 2
+#endif
+// weff_kernel: a quad produces TW consecutive time points of one (m, c) from one register window of taps (fold_math.h); a block keeps its
+// WPB outputs -- WIB = WPB / TW quads of work, the other waves only stage -- so that the ~250 blocks still cover the 256 CUs.  TW = 2 by
+// measurement at the metric shape (profiles/fold_window_ab.log: 1, 2 and 4 all beat the one-output loop once the staged rows are padded;
+// 2 leaves one producing wave per SIMD and has the shortest and steadiest launch, 8 leaves one wave per CU and loses)
+constexpr int TW = SLODE_FOLD_TW;
+constexpr int WIB = WPB / TW;
+static_assert(TW == 1 || TW == 2 || TW == 4 || TW == 8, "TW: a power of two up to 8");
+static_assert((WIB * WFG) % 64 == 0, "whole waves produce outputs: the quads' DPP adds need their four lanes");
 // One output W_eff[m][kappa(c, t)] by the four lanes of a quad (fh = lane of the quad = group of filters; fixed order: the quad's partial
-// sums meet in two DPP adds).  wlm: row m of lin.weight [F][n_pool]; s_wp: w' [F][C][JM].  Shared by weff_kernel and by the in-launch fold
-// of enc_chain_kernel: the same operations in the same order, hence the same bits.
+// sums meet in two DPP adds).  wlm: row m of lin.weight [F][n_pool]; s_wp: w' [F][C][JM].  The in-launch fold of enc_chain_kernel; the
+// arithmetic is fold_math.h's, which weff_kernel runs in its windowed shape: the same operations in the same order, hence the same bits.
 template <int JM>
 __device__ __forceinline__ float weff_out(const FoldK& k, const float* __restrict__ wlm, const float* __restrict__ s_wp, int c, int t, int fh) {
-  const int C = k.C, fper = (k.F + WFG - 1) / WFG;
-  float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll 2
-  for (int f = fh * fper; f < min(k.F, (fh + 1) * fper); ++f) {
-    const float* wl = wlm + f * k.n_pool;
-    const float* wp = s_wp + (f * C + c) * JM;
-    float v[JM];
-#pragma unroll
-    for (int j = 0; j < JM; ++j) v[j] = wl[min(max(t - j, 0), k.n_pool - 1)];   // unconditional, clamped
-#pragma unroll
-    for (int j = 0; j < JM; j += 2) {
-      acc0 = fmaf((t - j >= 0 && t - j < k.n_pool) ? v[j] : 0.f, wp[j], acc0);
-      if (j + 1 < JM) acc1 = fmaf((t - j - 1 >= 0 && t - j - 1 < k.n_pool) ? v[j + 1] : 0.f, wp[j + 1], acc1);
-    }
-  }
-  float r = acc0 + acc1;
+  float r = fold_out_partial<JM>(k.F, k.C, k.n_pool, wlm, s_wp, c, t, fh);
   r += dpp_f<0xB1>(r);   // quad_perm [1,0,3,2]
   r += dpp_f<0x4E>(r);   // quad_perm [2,3,0,1]
   return r;
+}
+// TW outputs W_eff[m][kappa(c, t0 .. t0 + TW - 1)] by the four lanes of a quad.  PADDED: wlm is the block's zero-padded LDS copy of the
+// row (filters `stride` apart); else the row in global memory (stride n_pool).
+template <int JM, bool PADDED>
+__device__ __forceinline__ void weff_window(int F, int C, int n_pool, int stride, const float* __restrict__ wlm, const float* __restrict__ s_wp,
+                                            int c, int t0, int fh, float (&r)[TW]) {
+  static_assert(fold_window_batch(14) == SLODE_MAX_F / WFG, "one batch of reads holds every filter a lane can own");
+  fold_window_partial<JM, TW, fold_window_batch(JM), PADDED>(F, C, n_pool, stride, wlm, s_wp, c, t0, fh, r);
+#pragma unroll
+  for (int w = 0; w < TW; ++w) {
+    r[w] += dpp_f<0xB1>(r[w]);   // quad_perm [1,0,3,2]
+    r[w] += dpp_f<0x4E>(r[w]);   // quad_perm [2,3,0,1]
+  }
 }
 // One wave: rowsum[m][f] for every f, then b_eff[m] (wlm: row m of lin.weight; conv_b / lin_b_m: the biases to fold in).  Shared likewise.
 __device__ __forceinline__ void rowsum_beff_wave(const FoldK& k, const float* __restrict__ wlm, int m, int lane, const float* __restrict__ conv_b,
@@ -105,43 +115,64 @@ __device__ __forceinline__ void rowsum_beff_wave(const FoldK& k, const float* __
   if (lane == 0) k.beff[m] = be;
 }
 
-template <int JM>  // compile-time bound on J = K + P - 1 (14 for every reference config)
-// (pl_*: the pointers of the kernel's first loads as leading arguments -- preloaded into SGPRs at wave launch, see ode_elbo_kernel)
-__global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_conv_w, const float* __restrict__ pl_lin_w, const FoldK k,
-                                                   const int stage_rows) {
+// JM: compile-time bound on J = K + P - 1 (14 for every reference config); STAGED: the block's lin.weight rows fit the LDS
+template <int JM, bool STAGED>
+// (pl_*: what the kernel's first loads need as leading arguments -- preloaded into SGPRs at wave launch, see ode_elbo_kernel: the two
+// pointers and the shape, so that a W_eff block requests its rows without a round trip to the argument block first; k's copies of the
+// shape hold the same values and are not read on that path)
+__global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_conv_w, const float* __restrict__ pl_lin_w, const int T, const int C,
+                                                   const int F, const int K, const int P, const int Hc, const int n_pool, const int t_major,
+                                                   const FoldK k) {
   __shared__ float s_wp[SLODE_MAX_F * SLODE_MAX_C * JM];
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // [stage_rows ? the block's lin.weight rows : 0]
-  const int tid = threadIdx.x, J = k.J, C = k.C, K = k.K;
-  const float fP = (float)k.P;
-  // arrival counters of the chain launch, 128 B apart: slots 0..7 one per filter pair; the in-launch fold's: 8 conv pairs done, 9 riders
-  // done, 16 + m the blocks of hidden unit m
-  if (blockIdx.x == 0 && tid < 16 + SLODE_MAX_HC && k.counter) k.counter[32 * tid] = 0u;
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [STAGED ? the block's lin.weight rows : 0]
+  const int tid = threadIdx.x, J = K + P - 1, FQ = F * n_pool, CT = C * T;
+  const float fP = (float)P;
   STAMP(0);
-  const int n_w = k.Hc * k.CT;
-  const int nb_w = (n_w + WPB - 1) / WPB, nb_rs = (k.Hc + WNT / 64 - 1) / (WNT / 64);
+  const int per = C * fold_windows(T, TW), n_w = Hc * per;   // work items: (m, c, window of TW time points), one quad each
+  const int nb_w = (n_w + WIB - 1) / WIB, nb_rs = (Hc + WNT / 64 - 1) / (WNT / 64);
   float* s_lw = smem;
+  if ((int)blockIdx.x == nb_w - 1) STAMP_ANY(5);   // (the last W_eff block: how far behind block 0 it starts and ends)
   // Everything this block reads from global memory is fetched in ONE batch: the conv taps, and (W_eff blocks) the lin.weight rows
-  // of the hidden units its WPB outputs belong to (2 for C*T >= WPB) -- coalesced, instead of F*JM = 140 strided loads per thread.
-  const int e_first = (int)blockIdx.x * WPB, m0 = min(e_first, n_w - 1) / k.CT, m1 = min(e_first + WPB - 1, n_w - 1) / k.CT;
-  {
+  // of the hidden units its WIB items belong to (2 for C*T >= WPB) -- coalesced, instead of F*JM = 140 strided loads per thread.
+  const int e_first = (int)blockIdx.x * WIB, m0 = min(e_first, n_w - 1) / per, m1 = min(e_first + WIB - 1, n_w - 1) / per;
+  // The LDS copy of the rows is zero-padded around every filter's n_pool values (fold_math.h): a tap outside [0, n_pool) reads its zero.
+  constexpr int PAD = fold_pad(JM, TW);
+  const int PS = n_pool + PAD;
+  if ((int)blockIdx.x < nb_w) {   // (the row-sum and likelihood-scale blocks use none of it: they start their own loads at once)
     // Everything the block needs from global memory is requested in one batch and only then stored: the lin.weight rows, and -- per
     // thread -- the (up to P) conv taps under its own w' entry, so that w' needs no staged copy of the taps and no barrier of its own:
     //   w'[f][c][j] = (1/P) * sum_{k + p = j} w[f][c][k]   (rows padded to JM, zero beyond J)
-    const bool rows = stage_rows && (int)blockIdx.x < nb_w;
-    const int n_st = rows ? (m1 - m0 + 1) * k.FQ : 0;
-    const float* src = pl_lin_w + (long long)m0 * k.FQ;
-    const int n_wp = k.F * C * JM;
+    constexpr bool rows = STAGED;
+    const int n_st = rows ? (m1 - m0 + 1) * FQ : 0;
+    const float* src = pl_lin_w + (long long)m0 * FQ;
+    const int n_wp = F * C * JM;
     const int e = min(tid, n_wp - 1), j = e % JM, fc = e / JM;
     float tp[SLODE_MAX_P];
 #pragma unroll
     for (int p = 0; p < SLODE_MAX_P; ++p) {
       const int kk = j - p;
-      const bool on = p < k.P && j < J && kk >= 0 && kk < K;
+      const bool on = p < P && j < J && kk >= 0 && kk < K;
       tp[p] = on ? pl_conv_w[fc * K + min(max(kk, 0), K - 1)] : 0.f;
     }
     float v[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) v[q] = rows ? src[min(tid + q * WNT, n_st - 1)] : 0.f;
+    // element tid + q * WNT of the rows is value fq of filter row fr: one division, then steps of WNT
+    const int dr = WNT / n_pool, dq = WNT - dr * n_pool;
+    int fr = tid / n_pool, fq = tid - fr * n_pool, at[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      at[q] = fold_padded_at(fr, fq, n_pool, PAD);
+      fr += dr; fq += dq;
+      if (fq >= n_pool) { fq -= n_pool; ++fr; }
+    }
+    // (behind the requests) the zeros of the copy: one store per thread at the metric shape
+    const int n_z = rows ? ((m1 - m0 + 1) * F + 1) * PAD : 0;
+    if (tid < n_z) s_lw[(tid / PAD) * PS + tid % PAD] = 0.f;
+    for (int z = tid + WNT; z < n_z; z += WNT) s_lw[(z / PAD) * PS + z % PAD] = 0.f;
+    // arrival counters of the chain launch, 128 B apart: slots 0..7 one per filter pair; the in-launch fold's: 8 conv pairs done, 9 riders
+    // done, 16 + m the blocks of hidden unit m
+    if (blockIdx.x == 0 && tid < 16 + SLODE_MAX_HC && k.counter) k.counter[32 * tid] = 0u;
     if (tid < n_wp) {
       float sw = 0.f;
 #pragma unroll
@@ -152,11 +183,11 @@ __global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-      if (tid + q * WNT < n_st) s_lw[tid + q * WNT] = v[q];
+      if (tid + q * WNT < n_st) s_lw[at[q]] = v[q];
     for (int e2 = tid + WNT; e2 < n_wp; e2 += WNT) {   // (more than 512 entries: long-tap shapes)
       const int j2 = e2 % JM, fc2 = e2 / JM;
       float sw = 0.f;
-      for (int p = 0; p < k.P; ++p) {
+      for (int p = 0; p < P; ++p) {
         const int kk = j2 - p;
         if (j2 < J && kk >= 0 && kk < K) sw += pl_conv_w[fc2 * K + kk];
       }
@@ -169,24 +200,31 @@ __global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_
       for (int q = 0; q < 8; ++q) v[q] = src[min(i0 + q * WNT, n_st - 1)];
 #pragma unroll
       for (int q = 0; q < 8; ++q)
-        if (i0 + q * WNT < n_st) s_lw[i0 + q * WNT] = v[q];
+        if (i0 + q * WNT < n_st) s_lw[fold_padded_at((i0 + q * WNT) / n_pool, (i0 + q * WNT) % n_pool, n_pool, PAD)] = v[q];
     }
+    __syncthreads();
   }
-  __syncthreads();
   STAMP(1);
   if ((int)blockIdx.x < nb_w) {
-    // WPB = 128 outputs per block, WFG = 4 threads per output (each a group of the filters): ~250 blocks fill the 256 CUs.  The four
-    // threads of an output are one quad: their partial sums meet in two DPP adds (fixed order), no LDS, no barrier.
+    // WIB items per block, WFG = 4 threads per item (each a group of the filters): ~250 blocks fill the 256 CUs.  The four threads of
+    // an item are one quad: their partial sums meet in two DPP adds per output (fixed order), no LDS, no barrier.
     static_assert(WFG == 4, "the filter groups of an output are the lanes of a quad");
-    const int el = tid >> 2, fh = tid & 3;
-    const int e = min((int)blockIdx.x * WPB + el, n_w - 1);
-    const int m = e / k.CT, kap = e - m * k.CT;
-    int c, t;
-    if (k.t_major) { t = kap / C; c = kap - t * C; } else { c = kap / k.T; t = kap - c * k.T; }
-    const float* wlm = stage_rows ? s_lw + (m - m0) * k.FQ : k.lin_w + (long long)m * k.FQ;
-    const float r = weff_out<JM>(k, wlm, s_wp, c, t, fh);
-    if (fh == 0 && (int)blockIdx.x * WPB + el < n_w) k.weff[e] = r;
+    if (tid < WIB * WFG) {
+      const int el = tid >> 2, fh = tid & 3;
+      int m, c, t0;
+      fold_item(min((int)blockIdx.x * WIB + el, n_w - 1), T, C, t_major, TW, m, c, t0);
+      float r[TW];
+      if constexpr (STAGED) weff_window<JM, true>(F, C, n_pool, PS, s_lw + fold_padded_at((m - m0) * F, 0, n_pool, PAD), s_wp, c, t0, fh, r);
+      else weff_window<JM, false>(F, C, n_pool, n_pool, pl_lin_w + (long long)m * FQ, s_wp, c, t0, fh, r);
+      if (fh == 0 && (int)blockIdx.x * WIB + el < n_w) {
+        float* row = k.weff + (long long)m * CT;
+#pragma unroll
+        for (int w = 0; w < TW; ++w)
+          if (t0 + w < T) row[fold_kappa(T, C, t_major, c, t0 + w)] = r[w];
+      }
+    }
     STAMP(2);
+    if ((int)blockIdx.x == nb_w - 1) STAMP_ANY(6);
   } else if ((int)blockIdx.x >= nb_w + nb_rs) {
     // likelihood scales of this step (decoders.py:52-53: softplus(constant_std)) and what the likelihood and its gradient need of them:
     // parameter-only, so once per step here instead of once per trajectory in the ODE/ELBO kernel (same functions: same bits)
@@ -201,7 +239,9 @@ __global__ void __launch_bounds__(WNT) weff_kernel(const float* __restrict__ pl_
   } else {
     // one wave per hidden unit m: rowsum[m][f] for every f, then b_eff[m]
     const int m = ((int)blockIdx.x - nb_w) * (WNT / 64) + (tid >> 6), lane = tid & 63;
+    if ((int)blockIdx.x == nb_w) STAMP_ANY(3);
     if (m < k.Hc) rowsum_beff_wave(k, k.lin_w + (long long)m * k.FQ, m, lane, k.conv_b, k.lin_b[m]);
+    if ((int)blockIdx.x == nb_w) STAMP_ANY(4);
   }
 }
 
@@ -863,19 +903,26 @@ int slode_chain_resident_blocks(const slode_shape& s, int num_cu) {
 
 hipError_t slode_launch_fold_fwd(const FoldLaunch& a, hipStream_t stream) {
   FoldK k = make_foldk(a);
-  const int nb_w = (k.Hc * k.CT + WPB - 1) / WPB, nb_r = (k.Hc + WNT / 64 - 1) / (WNT / 64) + (k.sigtab ? (k.CT + WNT - 1) / WNT : 0);
-  // dynamic LDS: (when they fit) the lin.weight rows a block's WPB consecutive outputs can touch
-  const size_t max_rows = (size_t)(WPB - 1) / k.CT + 2;   // WPB outputs starting anywhere inside a row of CT
-  const int stage_rows = (max_rows * (size_t)k.FQ) * sizeof(float) <= 96 * 1024 ? 1 : 0;
-  const size_t wlds = sizeof(float) * (stage_rows ? max_rows * (size_t)k.FQ : 4);
+  const int per = k.C * fold_windows(k.T, TW);   // work items of a row of W_eff
+  const int nb_w = (k.Hc * per + WIB - 1) / WIB, nb_r = (k.Hc + WNT / 64 - 1) / (WNT / 64) + (k.sigtab ? (k.CT + WNT - 1) / WNT : 0);
+  // dynamic LDS: (when they fit) the lin.weight rows a block's WIB consecutive items can touch
+  const size_t max_rows = (size_t)(WIB - 1) / per + 2;   // WIB items starting anywhere inside a row of per
+  const int pad = k.J <= 14 ? fold_pad(14, TW) : fold_pad(SLODE_MAX_K + SLODE_MAX_P, TW);   // of the instantiation taken below
+  const size_t n_lds = max_rows * (size_t)k.F * (size_t)(k.n_pool + pad) + pad;          // (fold_padded_size, without its int)
+  const int stage_rows = n_lds * sizeof(float) <= 96 * 1024 ? 1 : 0;
+  const size_t wlds = sizeof(float) * (stage_rows ? n_lds : 4);
   if (a.fold_skip) {
     // (the previous step's chain launch folded the current weights: encoder forward only)
-  } else if (k.J <= 14) {
-    if (wlds > 48 * 1024) (void)hipFuncSetAttribute((const void*)weff_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds);
-    SLODE_LAUNCH("weff", (weff_kernel<14>), dim3(nb_w + nb_r), dim3(WNT), wlds, stream, k.conv_w, k.lin_w, k, stage_rows);
   } else {
-    if (wlds > 48 * 1024) (void)hipFuncSetAttribute((const void*)weff_kernel<SLODE_MAX_K + SLODE_MAX_P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds);
-    SLODE_LAUNCH("weff", (weff_kernel<SLODE_MAX_K + SLODE_MAX_P>), dim3(nb_w + nb_r), dim3(WNT), wlds, stream, k.conv_w, k.lin_w, k, stage_rows);
+#define SLODE_WEFF(JJ, SS)                                                                                                              \
+  do {                                                                                                                                \
+    if (wlds > 48 * 1024) (void)hipFuncSetAttribute((const void*)weff_kernel<JJ, SS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); \
+    SLODE_LAUNCH("weff", (weff_kernel<JJ, SS>), dim3(nb_w + nb_r), dim3(WNT), wlds, stream, k.conv_w, k.lin_w, k.T, k.C, k.F, k.K, k.P, k.Hc, \
+                 k.n_pool, k.t_major, k);                                                                                              \
+  } while (0)
+    if (k.J <= 14) { if (stage_rows) SLODE_WEFF(14, true); else SLODE_WEFF(14, false); }
+    else { if (stage_rows) SLODE_WEFF(SLODE_MAX_K + SLODE_MAX_P, true); else SLODE_WEFF(SLODE_MAX_K + SLODE_MAX_P, false); }
+#undef SLODE_WEFF
   }
   if (a.skip_enc) return hipGetLastError();
   const bool one = (k.CT & 1) == 0 && k.CT <= 128 * IU && (k.Hc + RB - 1) / RB <= FNT / 64;

@@ -8,6 +8,7 @@ N=$1; shift
 for i in $(seq $N); do
   for L in "$@"; do
     SLODE_LIB_PATH=$PWD/$L timeout -k 10 200 python bench.py --ab > gpurun_out/ab/ab.json 2>/dev/null
+    st=$?; if [ $st -ne 0 ]; then echo "$L: bench.py --ab exit $st: stopping (nothing more is started after a failed run)"; exit 1; fi
     python - $L <<'PY'
 import json,sys
 d=json.loads(open("gpurun_out/ab/ab.json").read().strip().splitlines()[-1])
