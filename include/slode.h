@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 290 /* 0.2.9: slode_pointwise_loo, slode_loo_plan (0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels; 0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 290 /* 0.2.9: slode_pointwise_loo, slode_loo_plan; slode_intervene_summary, slode_intervene_summary_plan (additions to 0.2.9: no entry point or struct of 0.2.9 changes, so the number stands) (0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels; 0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -46,6 +46,7 @@ extern "C" {
 #define SLODE_CALIBRATION_PHIM2 0.022750131948179195f /* Phi(-2): of mean - 2 s */
 #define SLODE_ATTRIBUTION_MAX_ARMS 16 /* most arms (block masks) of one slode_latent_attribution call */
 #define SLODE_SUMMARY_SLOTS 8 /* functionals of one slode_curve_summary row: peak, t_peak, trough, t_trough, auc, time_beyond, t_hit, crossed */
+#define SLODE_INTERVENE_SUMMARY_MAX_ARMS 64 /* most hypotheses (counterfactual arms) of one slode_intervene_summary call */
 #define SLODE_QUANTILE_MAX_LEVELS 8 /* most levels of one slode_recon_quantiles call */
 #define SLODE_JOINT_BAND_MAX_LEVELS 8 /* most levels of one slode_joint_band call */
 #define SLODE_MECHANISM_SLOTS 5 /* slots of slode_mechanism_moments: state, production, degradation, set_point, net_rate */
@@ -671,6 +672,59 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
                         float* mean /* [Q,B,C,8] */, float* sd /* [Q,B,C,8] or NULL */, float* p_beyond /* [Q,B,C,T] or NULL */,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- counterfactual summaries as ONE call: peak, AUC and threshold crossing of every subject's curves under V hypothesised inputs, with the
+ * paired effect on each functional (no reference counterpart: "by how much does input u' lower THIS subject's peak, and does the curve still
+ * cross the level?" is the product of slode_intervene_moments and slode_curve_summary -- the peak of the mean counterfactual curve is not the
+ * mean of the peaks, and the sd of a paired effect on a functional cannot be formed from two separate calls) ----
+ * Draws: for trajectory b and draw k, on ONE noise row (row k * B + b of one drawing call, as slode_intervene_moments), z_f = loc_q + scale_q eps.
+ * Arms: for v < V, z_cf,v = z_f outside the prior groups of group_mask and ploc_g(u'_{b,v}) + exp(pls_g(u'_{b,v})) eps inside them, with the bits
+ * slode_intervene_moments forms for the same labels.  Hypotheses: u'_{b,v} is row b's own label row with the columns of every non-NULL entry of
+ * hyp_labels (one entry per label tensor of the batch, a dense [V, width] table shared by all trajectories) replaced by row v of that table:
+ * the convention of slode_label_evidence.
+ * All V + 1 latents go through the same fixed-grid solve and heads; per head curve q, channel c and arm the eight functionals of a draw are
+ * exactly those of slode_curve_summary (same trapezoid node weights, same 16-lane walk and combine order -- xor 1, xor 2, half mirror, mirror
+ * --, the smallest i wins ties, same thr / sense).  Call them f_f[s] and f_v[s], s = 0 .. 7.  Three sets of shifted moments over the draws
+ * (mean and POPULATION sd, accumulated as in slode_recon_moments) are written:
+ *   f_mean, f_sd      [Q, B, C, 8]     the factual arm: bit for bit what slode_curve_summary(is_post = 1) writes on the same noise
+ *   cf_mean, cf_sd    [V, Q, B, C, 8]  arm v; slot 6 (t_hit) over that arm's crossing draws, NaN where none crosses
+ *   eff_mean, eff_sd  [V, Q, B, C, 8]  the paired difference e = fl(f_v[s] - f_f[s]): slots 0 - 5 and 7 over all draws, slot 7 the difference
+ *                                      of the two indicators in {-1, 0, 1}; slot 6 over the draws that cross in BOTH arms (shifted by the first
+ *                                      of them, divided by their count), NaN for mean and sd where there is none
+ *   Hence eff_mean[7] = P_cf - P_f (the change of P(cross)), and eff_sd[7]^2 + eff_mean[7]^2 = mean of e^2 = the share of draws whose crossing
+ *   changes.  Every output but cf_mean may be NULL; with f_* and eff_* all NULL the factual arm is not run.
+ *   thr: a HOST array [C] (copied into the kernel arguments at the call) or NULL: slots 5 - 7 of all three sets are then NaN.
+ *   group_mask = 0 (hyp_labels is then not read): every arm runs on z_f through the same instructions, cf == f bitwise and every effect is 0.
+ *   num_samples = 1: every sd that is not NaN is exactly 0.
+ *   Column v is bitwise independent of V and of the other rows of the tables: arm v of a V-arm call equals the V = 1 call with that row, so
+ *   more hypotheses than one call holds may be split over calls on the same noise.
+ *   Noise: batch->eps == NULL: ONE drawing call n (row k * B + b, plus first_trajectory), the counter left at n + 1; else a dense
+ *   [num_samples, B, L] tensor.  Three launches ("weff", "enc_fwd2", "intervene_summary" in slode_profile_read).  The result is a function of
+ *   (parameters, inputs, labels, hypotheses, noise, thr, sense) alone: independent of the grid, of where the noise comes from and of which
+ *   optional outputs are asked for, bitwise reproducible (every output has one owner thread, which takes the draws in the order
+ *   k = 0 .. num_samples - 1; no atomics).
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched or drawn: every refusal of slode_recon_moments for the
+ * posterior but its LDS rung -- a NULL handle (before anything else); num_samples < 1; adaptive solver (dopri5, bosh3, fehlberg2,
+ * adaptive_heun); particles > 1; the measured arms SLODE_FOLD_NEXT / SLODE_ODE_PACK / SLODE_ODE_ALG; batch->obs NULL, observation strides the
+ * folded encoder path does not take or SLODE_NO_FOLD -- and, after the observation rungs: cf_mean NULL; V outside
+ * [1, SLODE_INTERVENE_SUMMARY_MAX_ARMS]; sense not +1 / -1; a non-finite thr[c]; group_mask bits at or beyond n_groups; a non-zero mask with
+ * hyp_labels NULL or every entry NULL; a non-zero mask none of whose groups reads a column of a hypothesised tensor; LDS tables (step table
+ * 2 (T - 1) S, staged weights, posterior 2 L, counterfactual 2 L V, grid and node weights 2 T, value table Q C T, factual functionals Q C 8,
+ * moment triples 3 Q C 8 (1 + 2 V), the slot-6 counts Q C 2 V; every piece a multiple of 16 B) beyond the budget of 160 KiB, naming V and the
+ * largest V that fits. */
+
+/* The dynamic LDS bytes of slode_intervene_summary's kernel for a shape and V arms: pure host arithmetic -- no handle, no HIP call, works on a
+ * machine without a GPU.  SLODE_EINVAL (the reason is the global text slode_last_error(NULL)) for a bad shape, V outside
+ * [1, SLODE_INTERVENE_SUMMARY_MAX_ARMS] or tables beyond the budget (*lds_bytes is still written then; the text names the largest V that fits). */
+int slode_intervene_summary_plan(const slode_shape* s, int V, size_t* lds_bytes);
+int slode_intervene_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch,
+                            const float* const* hyp_labels /* n_labels pointers, each [V, width] or NULL (NULL altogether with group_mask == 0) */, int V,
+                            unsigned int group_mask, int num_samples, const float* thr /* HOST [C] or NULL */, int sense,
+                            float* f_mean /* [Q,B,C,8] or NULL */, float* f_sd /* [Q,B,C,8] or NULL */, float* cf_mean /* [V,Q,B,C,8] */,
+                            float* cf_sd /* [V,Q,B,C,8] or NULL */, float* eff_mean /* [V,Q,B,C,8] or NULL */, float* eff_sd /* [V,Q,B,C,8] or NULL */,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- sample quantiles of the head curves as ONE call: the credible band, the envelope, the median over the draws (no reference counterpart: the
  * reference saves the [B, C, T, num_samples] curves of multiple_samples and its users take np.percentile(samples, [2.5, 97.5], axis=-1) of them;
  * mean +- 2 sd of slode_recon_moments is no substitute for the skewed prior-side curves) ----
@@ -1011,11 +1065,11 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
                              size_t workspace_bytes, int* counts, void* stream);
 
 /* Measurement aid for bench.py's roofline block (no reference counterpart).  on = 1: every kernel that slode_elbo_step /
- * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_pointwise_loo / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration / slode_joint_band launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
+ * slode_elbo_adam_step / slode_aux_step / slode_adam_step / slode_eval_stats / slode_recon_moments / slode_traj_bounds / slode_label_evidence / slode_posterior_refine / slode_pointwise_density / slode_pointwise_loo / slode_intervene_moments / slode_latent_attribution / slode_curve_summary / slode_intervene_summary / slode_recon_quantiles / slode_mechanism_moments / slode_forecast_moments / slode_cohort_moments / slode_calibration / slode_joint_band launch from now on carries its own start / stop event pair (hipExtLaunchKernelGGL):
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "pointwise_loo", "latent_attribution", "curve_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "pointwise_loo", "latent_attribution", "curve_summary", "intervene_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

@@ -21,6 +21,7 @@ LOO_LDS_MAX = 160 * 1024   # SLODE_LOO_LDS_MAX: the LDS budget of its kernel
 EVIDENCE_SLOTS = 4     # SLODE_EVIDENCE_SLOTS: floats of one slode_label_evidence row [-ELBO, importance-weighted bound, effective sample size, log posterior]
 SUMMARY_SLOTS = 8        # SLODE_SUMMARY_SLOTS: functionals of one slode_curve_summary row
 SUMMARY_NAMES = ("peak", "t_peak", "trough", "t_trough", "auc", "time_beyond", "t_hit", "crossed")
+INTERVENE_SUMMARY_MAX_ARMS = 64   # SLODE_INTERVENE_SUMMARY_MAX_ARMS: most hypotheses of one slode_intervene_summary call
 QUANTILE_MAX_LEVELS = 8   # SLODE_QUANTILE_MAX_LEVELS: most levels of one slode_recon_quantiles call
 RECON_QUANTILES_LDS_MAX = 160 * 1024   # SLODE_RECON_QUANTILES_LDS_MAX: the LDS budget of its kernel
 MECHANISM_SLOTS = 5      # SLODE_MECHANISM_SLOTS: slots of slode_mechanism_moments, one bit each in its mask
@@ -85,7 +86,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_initialize_state", "slode_prior_nets", "slode_label_heads", "slode_dopri5_step_counts", "slode_decode_heads_bwd",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
-           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_loo_plan", "slode_pointwise_loo", "slode_intervene_moments", "slode_attribution_plan", "slode_latent_attribution", "slode_curve_summary_plan", "slode_curve_summary", "slode_quantile_plan", "slode_recon_quantiles", "slode_mechanism_plan", "slode_mechanism_moments", "slode_joint_band_plan", "slode_joint_band_levels", "slode_joint_band", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
+           "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_loo_plan", "slode_pointwise_loo", "slode_intervene_moments", "slode_attribution_plan", "slode_latent_attribution", "slode_curve_summary_plan", "slode_curve_summary", "slode_intervene_summary_plan", "slode_intervene_summary", "slode_quantile_plan", "slode_recon_quantiles", "slode_mechanism_plan", "slode_mechanism_moments", "slode_joint_band_plan", "slode_joint_band_levels", "slode_joint_band", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
            "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
@@ -167,6 +168,9 @@ def load():
     lib.slode_curve_summary_plan.argtypes = [P(Shape), C.c_int, P(C.c_size_t)]
     lib.slode_curve_summary.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, P(C.c_float), C.c_int, VP, VP, VP, VP,
                                         C.c_size_t, VP]
+    lib.slode_intervene_summary_plan.argtypes = [P(Shape), C.c_int, P(C.c_size_t)]
+    lib.slode_intervene_summary.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), P(VP), C.c_int, C.c_uint, C.c_int, P(C.c_float), C.c_int,
+                                            VP, VP, VP, VP, VP, VP, VP, C.c_size_t, VP]
     lib.slode_quantile_plan.argtypes = [P(Shape), C.c_int, C.c_int, P(C.c_double), C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_size_t)]
     lib.slode_recon_quantiles.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, C.c_int, P(C.c_double), C.c_int, VP, VP,
                                           C.c_size_t, VP]

@@ -1436,6 +1436,81 @@ int slode_curve_summary(slode_handle h, const slode_shape* s, const slode_layout
                      slode_launch_curve_summary);
 }
 
+// ---- counterfactual summaries: the paired draws of slode_intervene_moments under V hypothesised inputs, the functionals of
+// slode_curve_summary on every arm (include/slode.h) ----
+// the largest V in [0, SLODE_INTERVENE_SUMMARY_MAX_ARMS] whose tables fit the budget (0: not even one arm does)
+static int intervene_summary_fit(const slode_shape* s, int force_generic) {
+  int v = SLODE_INTERVENE_SUMMARY_MAX_ARMS;
+  while (v > 0 && slode_intervene_summary_lds_bytes(*s, v, force_generic) > SLODE_INTERVENE_SUMMARY_LDS_MAX) --v;
+  return v;
+}
+
+// The LDS bytes of slode_intervene_summary for a shape and V arms (host arithmetic only; the compiled state dims, no SLODE_ODE_GENERIC):
+// SLODE_EINVAL when the call would refuse them at its V or LDS rung.
+int slode_intervene_summary_plan(const slode_shape* s, int V, size_t* lds_bytes) {
+  if (int rc = plan_open("slode_intervene_summary_plan", s, !lds_bytes, "lds_bytes")) return rc;
+  if (V < 1 || V > SLODE_INTERVENE_SUMMARY_MAX_ARMS)
+    return fail(nullptr, SLODE_EINVAL, "slode_intervene_summary_plan: V = %d out of range [1, %d]", V, SLODE_INTERVENE_SUMMARY_MAX_ARMS);
+  *lds_bytes = slode_intervene_summary_lds_bytes(*s, V, 0);
+  if (*lds_bytes > SLODE_INTERVENE_SUMMARY_LDS_MAX)
+    return fail(nullptr, SLODE_EINVAL, "slode_intervene_summary_plan: the LDS tables of T = %d, S = %d, C = %d, V = %d (%zu B) exceed the budget of %d B; "
+                                       "at most V = %d fits", s->T, s->S, s->C, V, *lds_bytes, SLODE_INTERVENE_SUMMARY_LDS_MAX, intervene_summary_fit(s, 0));
+  return SLODE_OK;
+}
+
+// Mean / sd over num_samples paired posterior draws of the eight curve functionals of the factual arm, of V counterfactual arms and of
+// their paired differences (include/slode.h): refusals first -- slode_recon_moments' for the posterior without its LDS rung, then the call's
+// own, then its LDS rung; nothing launched, no draw consumed -- then slode_recon_moments' launches with the summary kernel in place of its own.
+int slode_intervene_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                            const float* stage_t, const slode_batch* batch, const float* const* hyp_labels, int V, unsigned int group_mask,
+                            int num_samples, const float* thr, int sense, float* f_mean, float* f_sd, float* cf_mean, float* cf_sd, float* eff_mean,
+                            float* eff_sd, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* N = "slode_intervene_summary";
+  DrawsCall d(N, "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, 1,
+              "reduce counterfactual samples instead", nullptr);
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
+  if (!cf_mean) return fail(h, SLODE_EINVAL, "%s: cf_mean is NULL", N);
+  if (V < 1 || V > SLODE_INTERVENE_SUMMARY_MAX_ARMS) return fail(h, SLODE_EINVAL, "%s: V = %d out of range [1, %d]", N, V, SLODE_INTERVENE_SUMMARY_MAX_ARMS);
+  if (sense != 1 && sense != -1) return fail(h, SLODE_EINVAL, "%s: sense = %d is neither +1 (beyond: above thr) nor -1 (below)", N, sense);
+  if (thr)
+    for (int c = 0; c < s->C; ++c)
+      if (!std::isfinite(thr[c])) return fail(h, SLODE_EINVAL, "%s: thr[%d] = %g is not finite", N, c, (double)thr[c]);
+  if (s->n_groups < 32 && (group_mask >> s->n_groups) != 0)
+    return fail(h, SLODE_EINVAL, "%s: group_mask = 0x%x has bits at or beyond n_groups = %d", N, group_mask, s->n_groups);
+  InterveneSummaryLaunch a{};
+  if (group_mask != 0) {
+    const int n = batch->n_labels < 0 ? 0 : (batch->n_labels > SLODE_MAX_LABELS ? SLODE_MAX_LABELS : batch->n_labels);
+    bool any = false, read = false;
+    int lo = 0;
+    for (int i = 0; hyp_labels && i < n; ++i) {
+      const int hi = lo + batch->label_width[i];
+      if (hyp_labels[i]) {
+        any = true;
+        for (int g = 0; g < s->n_groups; ++g)
+          read = read || (((group_mask >> g) & 1) && lo < s->groups[g].u_off + s->groups[g].u_dim && hi > s->groups[g].u_off);
+      }
+      lo = hi;
+    }
+    if (!any)
+      return fail(h, SLODE_EINVAL, "%s: group_mask = 0x%x needs the hypothesis tables (%s)", N, group_mask,
+                  !hyp_labels ? "hyp_labels is NULL" : (n == 0 ? "they take the widths of batch->labels: n_labels is 0" : "every entry of hyp_labels is NULL"));
+    if (!read) return fail(h, SLODE_EINVAL, "%s: no group of group_mask = 0x%x reads a column of a hypothesised label tensor", N, group_mask);
+  }
+  char arms[24], advice[96];
+  snprintf(arms, sizeof(arms), ", V = %d", V);
+  snprintf(advice, sizeof(advice), "at most V = %d fits: fewer hypotheses per call (slode_intervene_summary_plan)", intervene_summary_fit(s, h->ode_generic));
+  d.lds_tables = "step table, loc | scale of the V arms, grid and node weights, value table, factual functionals, moment triples and counts of 1 + 2 V sets, staged weights";
+  d.lds_advice = advice; d.lds_extra = arms;
+  if ((rc = eval_lds(h, s, d, slode_intervene_summary_lds_bytes(*s, V, h->ode_generic), SLODE_INTERVENE_SUMMARY_LDS_MAX)) != SLODE_OK) return rc;
+  a.f_mean = f_mean; a.f_sd = f_sd; a.cf_mean = cf_mean; a.cf_sd = cf_sd; a.eff_mean = eff_mean; a.eff_sd = eff_sd;
+  a.V = V; a.group_mask = group_mask; a.has_thr = thr ? 1 : 0; a.sense = sense;
+  for (int c = 0; c < SLODE_MAX_C; ++c) a.thr[c] = (thr && c < s->C) ? thr[c] : 0.f;
+  for (int i = 0; i < SLODE_MAX_LABELS; ++i) a.hyp[i] = (group_mask != 0 && hyp_labels && i < batch->n_labels) ? hyp_labels[i] : nullptr;
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, 1, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_intervene_summary);
+}
+
 // ---- sample quantiles: the draws of slode_recon_moments, order statistics of every value over the draws (include/slode.h) ----
 // The rank, depth and tile rules as data: what the plan reports and the launch takes.  why: the refusal.
 struct QuantilePlan { int tile, sweeps, depth_lo, depth_hi; size_t lds; int slot_lo[SLODE_QUANTILE_MAX_LEVELS], slot_hi[SLODE_QUANTILE_MAX_LEVELS]; float g[SLODE_QUANTILE_MAX_LEVELS]; };

@@ -748,6 +748,24 @@ struct CurveSummaryLaunch {
 hipError_t slode_launch_curve_summary(const CurveSummaryLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the tables do not fit the LDS
 size_t slode_curve_summary_lds_bytes(const slode_shape& s, int want_p_beyond, int force_generic);
 
+// Counterfactual summaries (intervene_summary_kernel.hip; slode_intervene_summary): over the paired posterior draws of d (is_post = 1; u unread,
+// lab: the batch's own labels) per trajectory, mean / sd of the eight curve functionals of the factual arm f [Q, B, C, SLODE_SUMMARY_SLOTS], of
+// each of V counterfactual arms cf [V, Q, B, C, SLODE_SUMMARY_SLOTS] and of the paired difference eff (same shape); every output but cf_mean may
+// be NULL.  hyp[i]: the [V, width] hypothesis table of label tensor i (NULL: every arm keeps the trajectory's own), read in the columns of the
+// groups in group_mask alone.  thr / sense travel by value; has_thr == 0: the threshold slots 5-7 are NaN.
+struct InterveneSummaryLaunch {
+  DrawsLaunch d;
+  float *f_mean, *f_sd, *cf_mean, *cf_sd, *eff_mean, *eff_sd;
+  const float* hyp[SLODE_MAX_LABELS];
+  int V;
+  unsigned int group_mask;
+  float thr[SLODE_MAX_C];
+  int has_thr, sense;
+};
+#define SLODE_INTERVENE_SUMMARY_LDS_MAX (160 * 1024)   // the LDS of one CU: the kernel's tables (step table, loc | scale of the posterior and of the V arms, grid and node weights, value table, factual functionals, moment triples and slot-6 counts of 1 + 2 V sets, staged weights) must fit
+hipError_t slode_launch_intervene_summary(const InterveneSummaryLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the tables do not fit the LDS
+size_t slode_intervene_summary_lds_bytes(const slode_shape& s, int V, int force_generic);
+
 // Sample quantiles (recon_quantiles_kernel.hip; slode_recon_quantiles): over the draws of d per trajectory, out [n_levels, Q, B, C, T] =
 // fma(g, v[hi] - v[lo], v[lo]) of the sorted draw values, served from two sorted LDS buffers per value column: the depth_lo smallest
 // (slots 0 .. depth_lo - 1 = ranks 0 ..) and the depth_hi largest (slots depth_lo + j = rank K - 1 - j); slot_lo / slot_hi: the buffer slots

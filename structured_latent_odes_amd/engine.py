@@ -945,6 +945,59 @@ class Engine:
                          self._p(mean), self._p(sd), self._p(p_beyond))
         return mean, sd, p_beyond
 
+    # ---- counterfactual summaries: the curve functionals of every subject under V hypothesised inputs, with the paired effects ------------
+    def intervene_summary_plan(self, B: int, V: int) -> int:
+        """``slode_intervene_summary_plan``: the dynamic LDS bytes of ``intervene_summary`` for this shape and ``V`` arms (host arithmetic
+        only; raises SlodeError, naming the largest V that fits, where the call would refuse them at its V or LDS rung)."""
+        return self._plan_bytes(self.lib.slode_intervene_summary_plan, B, V)
+
+    def intervene_summary(self, params, batch: L.Batch, B: int, hyp_labels, V: int, group_mask: int, num_samples: int, thr, sense: int,
+                          f_mean=None, f_sd=None, cf_mean=None, cf_sd=None, eff_mean=None, eff_sd=None, particles: int = 1):
+        """slode_intervene_summary: the ``L.SUMMARY_SLOTS`` curve functionals ``L.SUMMARY_NAMES`` of ``curve_summary`` on ``num_samples``
+        PAIRED posterior draws per trajectory, for the subject's own curve and for its curve under each of ``V`` hypothesised inputs.  All
+        V + 1 arms of a draw share one noise row: the factual latent is the posterior draw of ``curve_summary(is_post=True)``; arm v
+        replaces the dims of every prior group g with bit g of ``group_mask`` set by that group's conditional prior on the trajectory's
+        own labels with the columns of every hypothesised tensor replaced by row v of its table, as ``intervene_moments`` forms it.
+        ``hyp_labels``: one entry per label tensor of ``make_batch``: a float32 [V, width] table shared by all trajectories, or None (not
+        hypothesised); None altogether with ``group_mask`` = 0.  Returns ``(f_mean, f_sd, cf_mean, cf_sd, eff_mean, eff_sd)``: the
+        factual moments float32 [Q, B, C, 8] (bitwise ``curve_summary``'s on the same noise), those of every arm and of the paired
+        difference arm - factual float32 [V, Q, B, C, 8] (an output passed as False is not computed: None in its place; with both factual
+        and both effect outputs False the factual arm is not run).  Slot 6 of an arm takes its crossing draws, of an effect the draws
+        that cross in both arms (NaN where there is none); slot 7 of an effect is the change of P(cross).  ``thr``: None (slots 5 - 7 are
+        NaN) or C floats read on the host now; ``sense``: +1 / -1.  The batch's eps is [num_samples, B, L] or None (ONE drawing call).
+        Column v does not depend on V or on the other rows.  Raises SlodeError naming the reason for what the kernel does not take
+        (everything ``recon_moments(is_post=True)`` refuses; V outside [1, L.INTERVENE_SUMMARY_MAX_ARMS]; ``sense``; a non-finite
+        threshold; mask bits beyond the prior groups; a non-zero mask without a hypothesised column one of its groups reads; LDS budget,
+        naming the largest V that fits): nothing is launched and no draw is consumed then."""
+        V = int(V)
+        Q, _, Cn, _ = self._head_shape(B)
+        shp_f, shp_v = (Q, B, Cn, L.SUMMARY_SLOTS), (max(V, 1), Q, B, Cn, L.SUMMARY_SLOTS)     # (V < 1 is refused by name: the pointers must not be NULL for it)
+        if cf_mean is False:
+            raise ValueError("cf_mean is always computed")
+        outs = [None if t is False else self._out(t, name, shp)
+                for t, name, shp in ((f_mean, "f_mean", shp_f), (f_sd, "f_sd", shp_f), (cf_mean, "cf_mean", shp_v), (cf_sd, "cf_sd", shp_v),
+                                     (eff_mean, "eff_mean", shp_v), (eff_sd, "eff_sd", shp_v))]
+        ptrs = None
+        if hyp_labels is not None:
+            if len(hyp_labels) != int(batch.n_labels):
+                raise ValueError("hyp_labels needs one entry per label tensor of the batch (%d), got %d" % (int(batch.n_labels), len(hyp_labels)))
+            ptrs = (C.c_void_p * L.MAX_LABELS)()
+            for i, t in enumerate(hyp_labels):
+                if t is None:
+                    continue
+                if self._f32(t, "hyp label %d" % i).numel() != V * int(batch.label_width[i]):
+                    raise ValueError("hyp label %d must be [%d, %d], got %s" % (i, V, int(batch.label_width[i]), tuple(t.shape)))
+                ptrs[i] = t.data_ptr()
+        arr = None
+        if thr is not None:
+            vals = [float(v) for v in (thr.detach().cpu().reshape(-1).tolist() if isinstance(thr, torch.Tensor) else thr)]
+            if len(vals) != Cn:
+                raise ValueError("thr must hold %d values (one per channel), got %d" % (Cn, len(vals)))
+            arr = (C.c_float * Cn)(*vals)
+        self._batch_call(self.lib.slode_intervene_summary, params, batch, B, particles, ptrs, V, int(group_mask), int(num_samples), arr, int(sense),
+                         *(self._p(t) for t in outs))
+        return tuple(outs)
+
     # ---- sample quantiles: order statistics of every curve value over the draws ------------------------------------------------------------
     @staticmethod
     def _levels(levels):

@@ -1199,6 +1199,132 @@ class MechanisticBase(nn.Module):
             cells.append(cell)
         return "curve_summary_%s: n=%d  %s" % (tag, m.shape[0], "  ".join(cells))
 
+    # ---- counterfactual summaries: peak, AUC and crossing of THIS subject's curves under V hypothesised inputs, with the paired effects ----
+    INTERVENTION_SUMMARY_ARMS_PER_CALL = None     # most hypotheses of one engine call; None: what the engine's plan says fits the LDS (at most 64)
+    SUMMARY_ARMS = ("factual", "cf", "effect")
+
+    def _summary_hypotheses(self, hypotheses):
+        """``(V, tables, group_mask)`` of ``hypotheses`` = {label name: [V, width]} (``_hypothesis_tables``): every named label must be a
+        conditional-prior label of the family (``_intervened``'s error); bit g of the mask is set when a label of prior group g is named."""
+        V, tabs = self._hypothesis_tables(hypotheses)
+        known = [l for _, ls, _ in self.PRIORS for l in ls]
+        mask = 0
+        for name, t in tabs.items():
+            if name not in known:
+                raise ValueError("intervene: %r is not a conditional-prior label of the %s family (labels: %s)" % (name, self.FAMILY, ", ".join(known)))
+            if t.shape[1] != self.label_dims[name]:
+                raise ValueError("hypotheses[%r] must be [V, %d], got %s" % (name, self.label_dims[name], tuple(t.shape)))
+            mask |= 1 << next(g for g, (_, ls, _) in enumerate(self.PRIORS) if name in ls)
+        return V, tabs, mask
+
+    def intervention_summary(self, observations, num_samples: int, hypotheses, thresholds=None, sense="above", eps=None, **labels):
+        """"By how much does input u' change THIS subject's peak, its total, and does the curve still cross the level?": the functionals of
+        ``curve_summary`` on the paired draws of ``intervention_moments``, for V hypothesised inputs shared by all trajectories at once.
+        ``hypotheses`` = {label name: [V, width]} as ``label_evidence`` takes them (``label_grid`` builds the Cartesian product), every
+        name a conditional-prior label of the family; every prior group with a named label is redrawn from p(z_g | u'_g) on the subject's
+        own noise, a label that is not named keeps each trajectory's own value.  Returns ``{"hypotheses": tables, curve: {"factual":
+        {name: (mean, sd) [B, C]}, "cf": {name: (mean, sd) [V, B, C]}, "effect": {name: (mean, sd) [V, B, C]}}}`` per head curve
+        (``mu_50``, ``mu_75``, ``mu_25``; ``mean`` for the Gaussian family) over the eight names of ``SUMMARY_NAMES``: mean and population sd
+        over ``num_samples`` draws of the functional on the subject's own curve, on its curve under hypothesis v, and of the PAIRED
+        difference (both arms of a draw share their noise).  ``"t_hit"`` of an arm runs over its crossing draws, of an effect over the draws
+        that cross in both arms (NaN where none does); the effect on ``"crossed"`` is the change of P(cross), and its sd^2 + mean^2 is the
+        share of draws whose crossing changes.  ``thresholds`` / ``sense``: as ``curve_summary`` (None: the three threshold entries are
+        NaN).  ONE engine call (``slode_intervene_summary``) where the V arms fit the LDS, else the fewest calls that do, all on the same
+        noise -- column v does not depend on the others, so the split changes no bit; no ``[B, C, T, num_samples]`` tensor exists and
+        the encoder and the factual arm run once per call, not once per hypothesis.  ``eps`` ``[num_samples, B, L]`` makes it reproducible;
+        None draws one call of the engine's generator.  Where the engine refuses (adaptive solver, strided observations, measured arms)
+        the same dict is composed from ``counterfactual_samples`` per hypothesis in chunks over B, the functionals and the paired rules
+        in torch on the same definitions."""
+        from .. import _lib as L
+        b = self._bind()
+        B, ns, sn = observations.shape[0], self._count(num_samples), self._summary_sense(sense)
+        V, tabs, mask = self._summary_hypotheses(hypotheses)
+        thr = None if thresholds is None else [float(x) for x in torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).tolist()]
+        if thr is not None and len(thr) != observations.shape[1]:
+            raise ValueError("thresholds must hold %d values (one per channel), got %d" % (observations.shape[1], len(thr)))
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        dev = observations.device
+
+        def pack(f, cf, eff):      # each (mean, sd): f [Q, B, C, 8], cf / eff [V, Q, B, C, 8]
+            res = {"hypotheses": tabs}
+            for q, n in enumerate(names):
+                res[n] = {"factual": {k: (f[0][q][..., j], f[1][q][..., j]) for j, k in enumerate(self.SUMMARY_NAMES)},
+                          "cf": {k: (cf[0][:, q][..., j], cf[1][:, q][..., j]) for j, k in enumerate(self.SUMMARY_NAMES)},
+                          "effect": {k: (eff[0][:, q][..., j], eff[1][:, q][..., j]) for j, k in enumerate(self.SUMMARY_NAMES)}}
+            return res
+
+        def fused():
+            eng = b.engine
+            cap = min(L.INTERVENE_SUMMARY_MAX_ARMS, self.INTERVENTION_SUMMARY_ARMS_PER_CALL or L.INTERVENE_SUMMARY_MAX_ARMS)
+            slices = self._fewest_calls(V, cap, lambda n: eng.intervene_summary_plan(B, n))
+            bt = self._draws_batch(observations, labels, eps, ns)
+
+            def call(lo, hi):
+                hyp = [tabs[l][lo:hi].contiguous().to(dev) if l in tabs else None for l in self.LABELS]
+                first = None if lo == 0 else False            # the factual moments are the same in every call: asked for once
+                return eng.intervene_summary(b.flat, bt, B, hyp, hi - lo, mask, ns, thr, sn, f_mean=first, f_sd=first)
+            got = self._on_the_same_noise(eng, eps, slices, call)
+            cat = lambda i: got[0][i] if len(got) == 1 else torch.cat([g[i] for g in got], 0)      # noqa: E731
+            return pack((got[0][0], got[0][1]), (cat(2), cat(3)), (cat(4), cat(5)))
+
+        def composed():
+            cols = {n: [] for n in names}      # per chunk: (f mean, f sd [rows, C, 8], cf mean, cf sd, eff mean, eff sd [V, rows, C, 8])
+            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                part = {n: [None, None, [], [], [], []] for n in names}
+                for v in range(V):
+                    swap = {l: t[v:v + 1].to(dev).expand(hi - lo, -1).contiguous() for l, t in tabs.items()}
+                    res = self.counterfactual_samples(num_samples=ns, intervene=swap, eps=e, **d)
+                    for n in names:
+                        ff, _ = self._summary_functionals(res[n][0], thr, sn)
+                        fv, _ = self._summary_functionals(res[n][1], thr, sn)
+                        if v == 0:
+                            part[n][0], part[n][1] = self._summary_moments(ff)
+                        for i, t in zip((2, 3, 4, 5), self._summary_moments(fv) + self._summary_moments(fv - ff)):      # (NaN - x = NaN: slot 6 of
+                            part[n][i].append(t)                                                                       # an effect keeps the draws that cross in both arms)
+                    del res
+                for n in names:
+                    cols[n].append(part[n][:2] + [torch.stack(p, 0) for p in part[n][2:]])
+            st = lambda i, dim: torch.stack([torch.cat([c[i] for c in cols[n]], dim) for n in names], 0 if dim == 0 else 1)      # noqa: E731
+            return pack((st(0, 0), st(1, 0)), (st(2, 1), st(3, 1)), (st(4, 1), st(5, 1)))
+        return self._fused_or_composed(fused, composed)
+
+    def save_intervention_summary(self, results_dir: str, batches, num_samples: int, hypotheses, thresholds=None, sense="above"):
+        """Runs ``intervention_summary`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
+        ``summary_<curve>_factual_mean.npy`` / ``..._sd.npy``, float32 ``[n, C, 8]``, ``summary_<curve>_cf_{mean,sd}.npy`` and
+        ``summary_<curve>_effect_{mean,sd}.npy``, float32 ``[n, V, C, 8]`` (the trajectories in loader order, the slots in ``SUMMARY_NAMES``
+        order), and ``summary_hypotheses_<label>.npy`` (``[V, width]``) per hypothesised label.  One read-back, at the end.  Returns the
+        paths."""
+        V, tabs, _ = self._summary_hypotheses(hypotheses)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+
+        def rows(r):
+            for n in names:
+                for arm in self.SUMMARY_ARMS:
+                    for k in (0, 1):
+                        t = torch.stack([r[n][arm][slot][k] for slot in self.SUMMARY_NAMES], -1)
+                        yield "summary_%s_%s_%s.npy" % (n, arm, ("mean", "sd")[k]), t if arm == "factual" else t.transpose(0, 1)
+        written = self._save_over_batches(
+            results_dir, batches, lambda **d: self.intervention_summary(num_samples=num_samples, hypotheses=tabs, thresholds=thresholds, sense=sense, **d), rows)
+        return written + self._save_arrays(results_dir, [("summary_hypotheses_%s.npy" % l, tabs[l]) for l in self.LABELS if l in tabs])
+
+    def intervention_summary_lines(self, effect_mean, tables, with_threshold: bool):
+        """One printed line per hypothesis of a ``save_intervention_summary`` pass from the central curve's ``effect_mean`` array
+        ``[n, V, C, 8]`` and the hypothesis tables ``{label: [V, width]}``: per channel, the mean over trajectories of the paired effect on
+        the peak and on the AUC and, with thresholds, of ``P_cf - P_f``."""
+        import numpy as np
+        m = np.asarray(effect_mean, dtype=np.float64)
+        lines = []
+        for v in range(m.shape[1]):
+            tag = " ".join("%s=%s" % (l, np.asarray(t)[v].reshape(-1).tolist()) for l, t in tables.items())
+            cells = []
+            for c in range(m.shape[2]):
+                cell = "c%d d_peak=%.4g d_auc=%.4g" % (c, m[:, v, c, 0].mean(), m[:, v, c, 4].mean())
+                if with_threshold:
+                    cell += " d_p_cross=%.3f" % m[:, v, c, 7].mean()
+                cells.append(cell)
+            lines.append("intervention_summary: %s  n=%d  %s" % (tag, m.shape[0], "  ".join(cells)))
+        return lines
+
     # ---- sample quantiles: the credible band, the envelope, the median of every curve value over the draws ------------------------------
     QUANTILE_MAX_LEVELS = 8     # SLODE_QUANTILE_MAX_LEVELS
 

@@ -114,7 +114,8 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           results_dir: Optional[str] = None, test_bounds: int = 0, forecast_steps: int = 0, cohort_curves: bool = False, calibration: bool = False,
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
           curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
-          quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,), loo: int = 0):
+          quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,), loo: int = 0,
+          intervention_summary: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -169,7 +170,12 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     draws, posterior and prior (``save_simultaneous_band``: ``<curve>_<post|prior>_band_{mean,sd,crit,pointwise_joint,obs_dev}.npy``,
     ``band_levels.npy``) and one printed line per side (``joint_band_post: ...``: per level of the central curve, the mean critical value
     beside the pointwise z, the mean share of draws wholly inside the pointwise band and the share of subject-channels whose observation
-    lies wholly inside the simultaneous band); 0 (the default): no such stage runs."""
+    lies wholly inside the simultaneous band); 0 (the default): no such stage runs.
+    intervention_summary = K > 0: after training, the best model's counterfactual summaries over the validation loader from K paired
+    posterior draws on ``default_hypotheses`` (``save_intervention_summary``: ``summary_<curve>_{factual,cf,effect}_{mean,sd}.npy``,
+    ``summary_hypotheses_<label>.npy``), with ``summary_thresholds`` / ``summary_sense`` as for ``curve_summary``, and one printed line per
+    hypothesis (``intervention_summary: ...``: per channel of the central curve, the mean paired effect on the peak and on the AUC and, with
+    thresholds, the change of P(cross)); 0 (the default): no such stage runs."""
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -271,6 +277,17 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
         line = best_model.label_evidence_line(*(np.load(f) for f in written[:3]))
         print(line)
         logging.debug("%s (%s)", line, written)
+    if intervention_summary:
+        first = batch_to_device(next(iter(val_b)), device, family)
+        hyp = best_model.default_hypotheses(**{l: first[l] for l in best_model.LABELS})
+        written = best_model.save_intervention_summary(out_dir, (batch_to_device(b, device, family) for b in val_b), int(intervention_summary), hyp,
+                                                       thresholds=summary_thresholds, sense=summary_sense)
+        central = best_model.MOMENT_HEADS[bool(best_model.GAUSS)][0]
+        for line in best_model.intervention_summary_lines(np.load([f for f in written if f.endswith("summary_%s_effect_mean.npy" % central)][0]),
+                                                          hyp, summary_thresholds is not None):
+            print(line)
+            logging.debug("%s", line)
+        logging.debug("intervention summary: %s", written)
     if refine_steps:
         written = best_model.save_refined_posterior(out_dir, (batch_to_device(b, device, family) for b in val_b), int(refine_draws), int(refine_steps))
         table = np.load([f for f in written if f.endswith("refined_elbo.npy")][0])
@@ -404,6 +421,11 @@ def build_parser():
                     help="one level per channel for --curve-summary (default: none; the threshold entries are then NaN)")
     ap.add_argument("--summary-sense", choices=("above", "below"), default="above",
                     help="which side of --summary-thresholds counts as beyond (default: above)")
+    ap.add_argument("--intervention-summary", type=int, default=0, metavar="K",
+                    help="after training: the best model's counterfactual summaries over the validation loader from K paired posterior draws on "
+                         "the family's default hypotheses (save_intervention_summary: summary_<curve>_{factual,cf,effect}_*.npy) -- per hypothesis "
+                         "and channel of the central curve, the mean paired effect on the peak and the AUC and, with --summary-thresholds / "
+                         "--summary-sense, the change of P(cross), one line per hypothesis")
     ap.add_argument("--sample-quantiles", type=int, default=0, metavar="K",
                     help="after training: the best model's sample quantiles of every head curve over the validation loader from K draws, posterior "
                          "and prior (save_recon_quantiles: <curve>_<post|prior>_sample_quantiles.npy, sample_quantile_levels.npy) -- the mean band "
@@ -456,6 +478,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["attribution"] = a.attribution
     if a.curve_summary:
         kw["curve_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.curve_summary, a.summary_thresholds, a.summary_sense
+    if a.intervention_summary:
+        kw["intervention_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.intervention_summary, a.summary_thresholds, a.summary_sense
     if a.sample_quantiles:
         kw["sample_quantiles"], kw["quantile_levels"] = a.sample_quantiles, a.quantile_levels
     if a.mechanism:
