@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SLODE_VERSION 290 /* 0.2.9: slode_pointwise_loo, slode_loo_plan; slode_intervene_summary, slode_intervene_summary_plan (additions to 0.2.9: no entry point or struct of 0.2.9 changes, so the number stands) (0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels; 0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
+#define SLODE_VERSION 290 /* 0.2.9: slode_pointwise_loo, slode_loo_plan; slode_intervene_summary, slode_intervene_summary_plan; slode_forecast_summary, slode_forecast_summary_plan (additions to 0.2.9: no entry point or struct of 0.2.9 changes, so the number stands) (0.2.8: slode_joint_band, slode_joint_band_plan, slode_joint_band_levels; 0.2.7: slode_mechanism_moments, slode_mechanism_plan; 0.2.6: slode_recon_quantiles, slode_quantile_plan; 0.2.5: slode_curve_summary, slode_curve_summary_plan; 0.2.4: slode_latent_attribution, slode_attribution_plan; 0.2.3: slode_pointwise_density, slode_pointwise_plan; 0.2.2: slode_posterior_refine; 0.2.1: slode_label_evidence; 0.2.0: slode_calibration, slode_calibration_plan; 0.1.9: slode_cohort_moments, slode_cohort_plan; 0.1.8: slode_forecast_moments, slode_forecast_plan, slode_stage_times_n; 0.1.7: slode_intervene_moments; 0.1.6: slode_traj_bounds; 0.1.5: slode_recon_moments; 0.1.4: slode_eval_stats; 0.1.3: slode_shape::particles; 0.1.2: SLODE_BOSH3, SLODE_FEHLBERG2, SLODE_ADAPTIVE_HEUN; 0.1.1: slode_svi_step, slode_rng_*, slode_grad_*) */
 
 #define SLODE_MAX_GROUPS 4
 #define SLODE_MAX_HEADS 3
@@ -911,6 +911,48 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
                            float* sd /* [Q,B,C,T_out] or NULL */, float* x_mean /* [B,S,T_out] or NULL */, float* x_sd /* [B,S,T_out] or NULL */,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- forecast summaries: "will the curve cross the level AFTER the observed window, when, how high will it still get and how much is still
+ * to come?"  The moments of slode_forecast_moments do not answer it -- the peak of the mean forecast is not the mean of the peaks, P(cross) is
+ * no function of mean +- sd -- and forecast_samples reduced by the caller materialises [B, C, T_out, K] and stops at T_out = 1024. */
+
+/* The window slode_forecast_summary will use for (shape, T_out, window) and the dynamic LDS bytes of its kernel: pure host arithmetic, as
+ * slode_forecast_plan.  The LDS holds the staged weights, loc | scale, ONE carry [S], one window's tables -- step table 2 W S, grid and node
+ * weights 2 (W + 1), values Q C (W + 1) -- and the moment triples 3 Q C 8 (every piece a multiple of 16 B; budget 160 KiB).  There is no
+ * num_samples term: the kernel walks a draw through all its windows before the next draw starts.  The ladder is slode_forecast_plan's:
+ *   window > 0: clamped to T_out - 1 and used as given; SLODE_EINVAL naming the window if its tables do not fit.
+ *   window == 0: the whole grid if it fits; else the largest multiple of 256 steps that fits; failing that the largest multiple of 64;
+ *   failing that the largest that fits. */
+int slode_forecast_summary_plan(const slode_shape* s, int T_out, int window, int* window_out, size_t* lds_bytes);
+
+/* Per trajectory b, head curve q and channel c: the mean and the POPULATION sd over num_samples latent draws of the SLODE_SUMMARY_SLOTS = 8
+ * functionals of slode_curve_summary (same slot order and meaning), taken on the sub-grid times_out[first_point .. T_out) of the draw's curve
+ * v_k(t) as slode_forecast_moments solves it (the shape's fixed-grid method, x0 at times_out[0], stage_t_out from slode_stage_times_n):
+ *   peak, trough        the extreme over the points g >= first_point; t_peak, t_trough: the grid time of the FIRST point attaining it
+ *   auc                 the trapezoid rule on the sub-grid: sum of w[g] v[g], w[g] = 0.5f * (t[min(g + 1, T_out - 1)] - t[max(g - 1, first_point)])
+ *                       (a one-point sub-grid gives 0)
+ *   time_beyond         sum of w[g] over the points beyond thr[c] (sense +1: v > thr, -1: v < thr)
+ *   t_hit               the time of the first point g >= first_point beyond the threshold -- a draw already beyond at first_point hits there --
+ *                       mean / sd over the crossing draws only, NaN where none crosses
+ *   crossed             the share of draws that cross: P(cross)
+ *   mean, sd [Q, B, C, 8]; sd may be NULL; slots 5-7 are NaN with thr == NULL (thr: HOST [C] finite values, read before the call returns).
+ *   There is no p_beyond[T_out] output: it would need a T_out-sized table per trajectory, and slode_forecast_moments on indicator curves is
+ *   not this call's business.
+ *   The draws, the noise and the counter advance (ONE drawing call) are those of slode_recon_moments / slode_forecast_moments for the same is_post;
+ *   launches "weff", "enc_fwd2", "forecast_summary" (posterior) or "forecast_summary" alone (prior).
+ *   window: as slode_forecast_moments (0: slode_forecast_summary_plan's choice).  The kernel walks draws outer, windows inner and merges the
+ *   windows' functionals in time order (an extreme moves on strict improvement and carries its time; auc / time_beyond add in window order;
+ *   the first hit stays).  Bitwise reproducible for a given window and independent of the launch grid; two windows agree to fp32 rounding.
+ *   With one window, first_point = 0 and times_out = times the result is bit for bit slode_curve_summary's.  Neither num_samples nor T_out
+ *   sizes anything in the LDS.
+ * Enqueue only: no allocation, no synchronisation, no read-back; capturable.  Workspace: slode_workspace_bytes of the shape (unchanged).
+ * Refused with SLODE_EINVAL, by name in slode_last_error, before anything is launched, drawn or written, in this order: everything
+ * slode_forecast_moments refuses for the same is_post up to its grid (times_out / stage_t_out NULL; T_out outside [2, SLODE_FORECAST_MAX_T]);
+ * first_point outside [0, T_out - 1]; sense not +-1 (then a thr that is not finite); mean NULL; window < 0; the plan's refusal. */
+int slode_forecast_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                           const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const float* times_out,
+                           const float* stage_t_out, int T_out, int first_point, int window, const float* thr /* HOST [C] or NULL */, int sense,
+                           float* mean /* [Q,B,C,8] */, float* sd /* [Q,B,C,8] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- cohort curves: per-condition moments and the evaluation notebooks' L1 as ONE call (cvs_eval_final, sbio_eval_*, challenge_eval_*: the
  * subjects of one condition selected, every head curve averaged over them (and over the sample axis), np.std over the subjects for the band,
  * the observations averaged the same way, l1_error = sum_t |mean_y - mean_mu_50|) ------------------------------------------------------------
@@ -1069,7 +1111,7 @@ int slode_dopri5_step_counts(slode_handle h, const slode_shape* s, const slode_l
  * the begin -> end device timestamps of that dispatch -- the duration rocprofv3 --kernel-trace reports for it -- without any extra
  * packet on `stream`; on = 0: off.  slode_profile_read waits for the kernels of the LAST such call on this handle and returns their
  * number n (<= max_kernels; a negative slode_status on error), their names (static strings: "weff", "enc_fwd2", "ode_elbo", "enc_bwd_lin",
- * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "pointwise_loo", "latent_attribution", "curve_summary", "intervene_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
+ * "enc_chain", "dopri5_fwd", "dopri5_bwd", "aux", "enc_bwd2", "slab_stage1", "reduce", "adam", "eval_stats", "eval_reduce", "recon_moments", "traj_bounds", "label_evidence", "posterior_refine", "pointwise_density", "pointwise_loo", "latent_attribution", "curve_summary", "intervene_summary", "recon_quantiles", "mechanism_moments", "intervene_moments", "forecast_moments", "forecast_summary", "cohort_plan", "cohort_moments", "cohort_merge", "calibration", "calibration_merge", "joint_band", ...) in launch order and their durations in
  * microseconds. */
 #define SLODE_PROFILE_MAX_KERNELS 16
 int slode_profile_enable(slode_handle h, int on);

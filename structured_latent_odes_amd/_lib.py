@@ -87,7 +87,7 @@ EXPORTS = ["slode_version", "slode_create", "slode_destroy", "slode_last_error",
            "slode_svi_step", "slode_rng_seed", "slode_rng_set_counter", "slode_rng_get", "slode_rng_normal", "slode_sample_normal",
            "slode_grad_payload_floats", "slode_grad_partial", "slode_grad_apply", "slode_fold_invalidate", "slode_eval_stats", "slode_recon_moments",
            "slode_traj_bounds", "slode_label_evidence", "slode_posterior_refine", "slode_pointwise_plan", "slode_pointwise_density", "slode_loo_plan", "slode_pointwise_loo", "slode_intervene_moments", "slode_attribution_plan", "slode_latent_attribution", "slode_curve_summary_plan", "slode_curve_summary", "slode_intervene_summary_plan", "slode_intervene_summary", "slode_quantile_plan", "slode_recon_quantiles", "slode_mechanism_plan", "slode_mechanism_moments", "slode_joint_band_plan", "slode_joint_band_levels", "slode_joint_band", "slode_num_stage_times_n", "slode_stage_times_n", "slode_forecast_plan",
-           "slode_forecast_moments", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
+           "slode_forecast_moments", "slode_forecast_summary_plan", "slode_forecast_summary", "slode_cohort_plan", "slode_cohort_moments", "slode_calibration_plan", "slode_calibration"]
 
 _lib = None
 
@@ -185,6 +185,9 @@ def load():
     lib.slode_forecast_plan.argtypes = [P(Shape), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_size_t)]
     lib.slode_forecast_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, C.c_int, C.c_int,
                                            VP, VP, VP, VP, VP, C.c_size_t, VP]
+    lib.slode_forecast_summary_plan.argtypes = [P(Shape), C.c_int, C.c_int, P(C.c_int), P(C.c_size_t)]
+    lib.slode_forecast_summary.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int,
+                                           P(C.c_float), C.c_int, VP, VP, VP, C.c_size_t, VP]
     lib.slode_cohort_plan.argtypes = [P(Shape), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_size_t), P(C.c_size_t)]
     lib.slode_cohort_moments.argtypes = [VP, P(Shape), P(Layout), VP, VP, VP, P(Batch), C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int,
                                          C.c_float, VP, VP, VP, VP, VP, VP, C.c_size_t, VP, C.c_size_t, VP]

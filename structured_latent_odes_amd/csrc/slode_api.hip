@@ -1832,6 +1832,86 @@ int slode_forecast_moments(slode_handle h, const slode_shape* s, const slode_lay
                      slode_launch_forecast_moments, times_out, stage_t_out);   // (the kernel solves on the output grid)
 }
 
+// ---- forecast summaries: slode_forecast_moments' windowed solve, slode_curve_summary's functionals from first_point on (include/slode.h) ----
+// The window rule of forecast_plan on this kernel's carve, which has no num_samples term.  why: the refusal.
+static int forecast_summary_plan(const slode_shape& s, int T_out, int window, int force_generic, int* window_out, size_t* lds_out, char* why, size_t why_n) {
+  const size_t budget = SLODE_FORECAST_SUMMARY_LDS_MAX;
+  const int NS = T_out - 1;
+  auto bytes = [&](int W) { return slode_forecast_summary_lds_bytes(s, W, force_generic); };
+  int W;
+  if (window > 0) {
+    W = window < NS ? window : NS;
+    if (bytes(W) > budget) {
+      snprintf(why, why_n, "window = %d does not fit: its LDS tables of S = %d, C = %d (%zu B: staged weights, carry, step table, grid and node "
+               "weights, value table, moment triples) exceed the budget of %zu B; pass window = 0 to let the library choose", W, s.S, s.C, bytes(W), budget);
+      return SLODE_EINVAL;
+    }
+  } else {
+    if (bytes(1) > budget) {
+      snprintf(why, why_n, "the staged weights of S = %d, C = %d leave no room for one grid step beside them (%zu B of a budget of %zu B)", s.S, s.C,
+               bytes(1), budget);
+      return SLODE_EINVAL;
+    }
+    int lo = 1, hi = NS;   // bytes(lo) fits
+    while (lo < hi) {
+      const int mid = lo + (hi - lo + 1) / 2;
+      if (bytes(mid) <= budget) lo = mid; else hi = mid - 1;
+    }
+    W = lo;
+    if (W < NS) {   // not the whole grid: full rounds of the 256 threads in M4 where the room allows, else full waves
+      if (W >= 256) W -= W % 256;
+      else if (W >= 64) W -= W % 64;
+    }
+  }
+  *window_out = W;
+  *lds_out = bytes(W);
+  return SLODE_OK;
+}
+
+int slode_forecast_summary_plan(const slode_shape* s, int T_out, int window, int* window_out, size_t* lds_bytes) {
+  if (int rc = plan_open("slode_forecast_summary_plan", s, !window_out || !lds_bytes, "window_out / lds_bytes")) return rc;
+  if (T_out < 2 || T_out > SLODE_FORECAST_MAX_T)
+    return fail(nullptr, SLODE_EINVAL, "slode_forecast_summary_plan: T_out = %d out of range [2, %d]", T_out, SLODE_FORECAST_MAX_T);
+  if (window < 0) return fail(nullptr, SLODE_EINVAL, "slode_forecast_summary_plan: window = %d < 0", window);
+  char why[384];
+  if (forecast_summary_plan(*s, T_out, window, 0, window_out, lds_bytes, why, sizeof(why)) != SLODE_OK)
+    return fail(nullptr, SLODE_EINVAL, "slode_forecast_summary_plan: %s", why);
+  return SLODE_OK;
+}
+
+// Mean / sd over num_samples latent draws of the eight curve functionals on times_out[first_point .. T_out) (include/slode.h): the refusals of
+// slode_forecast_moments for the same is_post up to its grid rungs, then the call's own, the plan's refusal as its LDS rung; then
+// slode_forecast_moments' launches with the summary kernel in place of its own.
+int slode_forecast_summary(slode_handle h, const slode_shape* s, const slode_layout* lay, const float* params, const float* times,
+                           const float* stage_t, const slode_batch* batch, int is_post, int num_samples, const float* times_out,
+                           const float* stage_t_out, int T_out, int first_point, int window, const float* thr, int sense, float* mean, float* sd,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* N = "slode_forecast_summary";
+  const DrawsCall d(N, "batch / times / stage_t / workspace", !batch || !times || !stage_t || !workspace, num_samples, is_post,
+                    "reduce forecast_samples instead", nullptr);
+  int rc = eval_open(h, s, lay, params, batch, d);
+  if (rc != SLODE_OK) return rc;
+  if (!times_out || !stage_t_out) return fail(h, SLODE_EINVAL, "%s: times_out / stage_t_out is NULL", N);
+  if (T_out < 2 || T_out > SLODE_FORECAST_MAX_T) return fail(h, SLODE_EINVAL, "%s: T_out = %d out of range [2, %d]", N, T_out, SLODE_FORECAST_MAX_T);
+  if (first_point < 0 || first_point > T_out - 1)
+    return fail(h, SLODE_EINVAL, "%s: first_point = %d out of range [0, T_out - 1 = %d]", N, first_point, T_out - 1);
+  if (sense != 1 && sense != -1) return fail(h, SLODE_EINVAL, "%s: sense = %d is neither +1 (beyond: above thr) nor -1 (below)", N, sense);
+  if (thr)
+    for (int c = 0; c < s->C; ++c)
+      if (!std::isfinite(thr[c])) return fail(h, SLODE_EINVAL, "%s: thr[%d] = %g is not finite", N, c, (double)thr[c]);
+  if (!mean) return fail(h, SLODE_EINVAL, "%s: mean is NULL", N);
+  if (window < 0) return fail(h, SLODE_EINVAL, "%s: window = %d < 0", N, window);
+  ForecastSummaryLaunch a{};
+  size_t lds = 0;
+  char why[384];
+  if (forecast_summary_plan(*s, T_out, window, h->ode_generic, &a.window, &lds, why, sizeof(why)) != SLODE_OK)
+    return fail(h, SLODE_EINVAL, "%s: %s", N, why);
+  a.T_out = T_out; a.first_point = first_point; a.mean = mean; a.sd = sd; a.has_thr = thr ? 1 : 0; a.sense = sense;
+  for (int c = 0; c < SLODE_MAX_C; ++c) a.thr[c] = (thr && c < s->C) ? thr[c] : 0.f;
+  return draws_close(h, s, lay, d, a, params, times, stage_t, batch, is_post, num_samples, s->B, workspace, workspace_bytes, stream,
+                     slode_launch_forecast_summary, times_out, stage_t_out);   // (the kernel solves on the output grid)
+}
+
 // ---- cohort curves: the draws of slode_recon_moments reduced by cohort (include/slode.h) ----
 // the call's own argument rungs, shared by the plan and the call (who: the speaker)
 static const char* cohort_sizes(const slode_shape* s, int M, int G, int chunk, char* why, size_t why_n) {

@@ -823,6 +823,20 @@ struct ForecastMomentsLaunch {
 hipError_t slode_launch_forecast_moments(const ForecastMomentsLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: the window's tables do not fit the LDS
 size_t slode_forecast_lds_bytes(const slode_shape& s, int num_samples, int want_states, int window, int force_generic);
 
+// Forecast summaries (forecast_summary_kernel.hip; slode_forecast_summary): the draws of d, solved on the output grid d.times [T_out] (d.stage_t
+// from slode_stage_times_n) in windows of `window` steps (1 <= window <= T_out - 1, from the plan), draws outer and windows inner: mean / sd
+// [Q, B, C, SLODE_SUMMARY_SLOTS] of the eight curve functionals over the sub-grid [first_point, T_out) (0 <= first_point <= T_out - 1); sd may
+// be NULL.  thr / sense travel by value; has_thr == 0: the threshold slots 5-7 are NaN.
+struct ForecastSummaryLaunch {
+  DrawsLaunch d;
+  float *mean, *sd;
+  float thr[SLODE_MAX_C];
+  int has_thr, sense, T_out, window, first_point;
+};
+#define SLODE_FORECAST_SUMMARY_LDS_MAX (160 * 1024)   // the LDS of one CU: staged weights, loc | scale, one carry, one window's tables (step table, grid, node weights, values) and the moment triples must fit
+hipError_t slode_launch_forecast_summary(const ForecastSummaryLaunch& a, hipStream_t stream);   // hipErrorInvalidValue: sizes out of range / the window's tables do not fit the LDS
+size_t slode_forecast_summary_lds_bytes(const slode_shape& s, int window, int force_generic);
+
 // What the two calls that fold the draws of d by cohort share (cohort_moments, calibration): members [M] / offsets [G + 1] on the device;
 // chunk = R in [1, SLODE_COHORT_MAX_CHUNK] (from the plan); obs: dense rows of C*T floats (sb apart), t_major: [T][C] inside a row, else
 // [C][T]; scratch: slode_cohort_scratch(..).bytes for the call's partial size, 16-byte aligned.

@@ -5,7 +5,8 @@
 // This is curve_summary_kernel.hip's M6b restated operation for operation -- the same trapezoid weights, the same four-point trips, the same
 // combine order, the same tie rule -- so that a kernel which calls it writes that kernel's bits (tests/test_gpu_intervene_summary.py holds the
 // two against each other with torch.equal).  curve_summary_kernel.hip keeps its own copy: its code object is left as it is.
-// Included by intervene_summary_kernel.hip alone.
+// Included by intervene_summary_kernel.hip and forecast_summary_kernel.hip; the latter walks a curve window by window and merges the windows'
+// rows with the routines at the end of this file.
 #pragma once
 #include "slode_common.h"
 
@@ -69,6 +70,41 @@ __device__ __forceinline__ float summary_slot_value(const SummaryRow& r, const f
     case 5: return r.tb;
     case 6: return s_t[min(r.ihit, T - 1)];
     default: return r.ihit < T ? 1.f : 0.f;
+  }
+}
+
+// ---- a curve walked in several windows (forecast_summary_kernel.hip) ----
+// What a row carries across the windows of one curve: the extremes so far with the TIME of the first point that attained them, the running
+// trapezoid sums, the time of the first point beyond the threshold.  Every lane of the row holds the same values.
+struct SummaryCarry { float vmax, tmax, vmin, tmin, auc, tb, thit; bool hit; };
+
+__device__ __forceinline__ SummaryCarry summary_carry_init() {
+  return SummaryCarry{-INFINITY, 0.f, INFINITY, 0.f, 0.f, 0.f, 0.f, false};
+}
+
+// The SummaryRow r of a window's n >= 1 walked points into the carry; t_w: the times of those points (r's indices count from its first one).
+// Windows arrive in increasing time order: an extreme moves on STRICT improvement only, so the earliest point wins a tie across windows as
+// it does inside one; auc and time_beyond add in window order; the first hit stays once it is set.  A lane of a window shorter than the row
+// holds the sentinels (-inf / +inf, n) before the combine and loses every step to a lane with a point, so r's indices are < n here.
+__device__ __forceinline__ void summary_merge(SummaryCarry& c, const SummaryRow& r, const float* t_w, int n) {
+  if (r.vmax > c.vmax) { c.vmax = r.vmax; c.tmax = t_w[min(r.imax, n - 1)]; }
+  if (r.vmin < c.vmin) { c.vmin = r.vmin; c.tmin = t_w[min(r.imin, n - 1)]; }
+  c.auc += r.auc;
+  c.tb += r.tb;
+  if (!c.hit && r.ihit < n) { c.hit = true; c.thit = t_w[r.ihit]; }
+}
+
+// functional `slot` (0 .. 7) of the carry after the last window; slot 6 of a curve that does not cross must not be used
+__device__ __forceinline__ float summary_carry_value(const SummaryCarry& c, int slot) {
+  switch (slot) {
+    case 0: return c.vmax;
+    case 1: return c.tmax;
+    case 2: return c.vmin;
+    case 3: return c.tmin;
+    case 4: return c.auc;
+    case 5: return c.tb;
+    case 6: return c.thit;
+    default: return c.hit ? 1.f : 0.f;
   }
 }
 

@@ -586,6 +586,40 @@ class Engine:
                          T_out, int(window), self._p(mean), self._p(sd), self._p(x_mean), self._p(x_sd))
         return mean, sd, x_mean, x_sd
 
+    def forecast_summary_plan(self, T_out: int, window: int = 0):
+        """``slode_forecast_summary_plan``: (steps per window, dynamic LDS bytes) of ``forecast_summary`` for an output grid of ``T_out``
+        points; host arithmetic only.  Neither the batch size nor the draw count enters."""
+        w, nbytes = C.c_int(0), C.c_size_t(0)
+        _check(self.lib, None, self.lib.slode_forecast_summary_plan(C.byref(self.shape(1)), int(T_out), int(window), C.byref(w), C.byref(nbytes)))
+        return int(w.value), int(nbytes.value)
+
+    def forecast_summary(self, params, batch: L.Batch, B: int, is_post: bool, num_samples: int, times_out, first_point: int = 0, thr=None,
+                         sense: int = 1, mean=None, sd=None, window: int = 0):
+        """slode_forecast_summary: the ``L.SUMMARY_SLOTS`` functionals ``L.SUMMARY_NAMES`` of ``curve_summary``, taken on
+        ``times_out[first_point:]`` of every draw's curve as ``forecast_moments`` solves it (the draws of ``recon_moments`` on the same side
+        and noise; ``times_out`` of any length in [2, L.FORECAST_MAX_T], beginning at the bound grid's first time).  Returns ``(mean, sd)``:
+        ``mean`` float32 [Q, B, C, 8] (None: allocated) and ``sd`` likewise (None = not computed, True = allocated, or the tensor to write).
+        ``thr``: None (slots 5 - 7 are NaN) or C floats read on the host now; ``sense``: +1 (beyond: above ``thr``) or -1 (below).  ``t_hit``
+        takes the crossing draws only -- a draw already beyond at ``first_point`` hits there -- and is NaN where none crosses.  ``window``:
+        grid steps solved per pass, 0 = the library's choice (``forecast_summary_plan``).  Enqueued on the current stream; nothing sized by
+        num_samples or by T_out exists anywhere.  The batch's eps is [num_samples, B, L] or None (ONE drawing call).  Raises SlodeError naming
+        the reason for what the kernel does not take (everything ``forecast_moments`` refuses up to its grid; ``first_point`` outside
+        [0, T_out - 1]; ``sense``; a non-finite threshold; a window that does not fit): nothing is launched or drawn then."""
+        tt, st = self.forecast_grid(times_out)
+        T_out = tt.numel()
+        Q, _, Cn, _ = self._head_shape(B)
+        mean = self._out(mean, "mean", (Q, B, Cn, L.SUMMARY_SLOTS))
+        sd = None if sd is None else self._out(None if sd is True else sd, "sd", (Q, B, Cn, L.SUMMARY_SLOTS))
+        arr = None
+        if thr is not None:
+            vals = [float(v) for v in (thr.detach().cpu().reshape(-1).tolist() if isinstance(thr, torch.Tensor) else thr)]
+            if len(vals) != Cn:
+                raise ValueError("thr must hold %d values (one per channel), got %d" % (Cn, len(vals)))
+            arr = (C.c_float * Cn)(*vals)
+        self._batch_call(self.lib.slode_forecast_summary, params, batch, B, 1, 1 if is_post else 0, int(num_samples), self._p(tt), self._p(st),
+                         T_out, int(first_point), int(window), arr, int(sense), self._p(mean), self._p(sd))
+        return mean, sd
+
     # ---- cohort curves: the draws of recon_moments reduced by cohort -------------------------------------------------------------
     COHORT_OUTPUTS = ("sd", "sd_subjects", "obs_mean", "l1")
 

@@ -1083,20 +1083,22 @@ class MechanisticBase(nn.Module):
             return -1
         raise ValueError("sense must be 'above' or 'below', got %r" % (sense,))
 
-    def _summary_weights(self, device):
+    def _summary_weights(self, device, grid=None):
         """``(times, w)`` float32 [T] on ``device``: the grid and the trapezoid node weights w_0 = 0.5 (t_1 - t_0), w_i = 0.5 (t_{i+1} -
-        t_{i-1}), w_{T-1} = 0.5 (t_{T-1} - t_{T-2}), formed in fp32 as the kernel forms them."""
-        t = torch.as_tensor(self.times, dtype=torch.float32).reshape(-1).to(device)
+        t_{i-1}), w_{T-1} = 0.5 (t_{T-1} - t_{T-2}), formed in fp32 as the kernel forms them.  ``grid``: the grid to take them on (None:
+        the model's own)."""
+        t = torch.as_tensor(self.times if grid is None else grid, dtype=torch.float32).reshape(-1).to(device)
         i = torch.arange(t.numel(), device=device)
         return t, 0.5 * (t[(i + 1).clamp(max=t.numel() - 1)] - t[(i - 1).clamp(min=0)])
 
-    def _summary_functionals(self, v, thr, sense):
+    def _summary_functionals(self, v, thr, sense, grid=None):
         """The eight functionals of the curves ``v`` ``[rows, C, T, ns]`` in torch, on the definitions of ``slode_curve_summary``:
         ``(f [rows, C, ns, 8] float32, beyond [rows, C, T, ns] bool or None)``.  First indices are a masked ``min`` over the index (torch's
-        argmax tie rule is not relied on); ``t_hit`` of a draw that does not cross is NaN; ``thr`` None: slots 5 - 7 are NaN."""
+        argmax tie rule is not relied on); ``t_hit`` of a draw that does not cross is NaN; ``thr`` None: slots 5 - 7 are NaN.  ``grid``:
+        the T times the curves live on (None: the model's own grid)."""
         v = v.to(torch.float32)
         T = v.shape[2]
-        t, w = self._summary_weights(v.device)
+        t, w = self._summary_weights(v.device, grid)
         idx = torch.arange(T, device=v.device).reshape(1, 1, T, 1)
 
         def first(mask):
@@ -1185,9 +1187,10 @@ class MechanisticBase(nn.Module):
                        for n in names for k in (0, 1)),
             side=("summary_slots.npy", lambda path, _: np.save(path, np.array(self.SUMMARY_NAMES))))
 
-    def summary_line(self, mean, tag, with_threshold: bool):
+    def summary_line(self, mean, tag, with_threshold: bool, name: str = "curve_summary"):
         """One printed line of a ``save_curve_summary`` pass from the central curve's ``mean`` array ``[n, C, 8]``: per channel, the mean over
-        trajectories of the mean peak, time to peak and AUC and, with thresholds, of ``P(cross)`` and ``t_hit`` (NaN entries left out)."""
+        trajectories of the mean peak, time to peak and AUC and, with thresholds, of ``P(cross)`` and ``t_hit`` (NaN entries left out).
+        ``name``: the line's prefix (``save_forecast_summary``'s pass: ``"forecast_summary"``)."""
         import numpy as np
         m = np.asarray(mean, dtype=np.float64)
         cells = []
@@ -1197,7 +1200,84 @@ class MechanisticBase(nn.Module):
                 hit = m[:, c, 6]
                 cell += " p_cross=%.3f t_hit=%.4g" % (m[:, c, 7].mean(), float(np.nanmean(hit)) if np.isfinite(hit).any() else float("nan"))
             cells.append(cell)
-        return "curve_summary_%s: n=%d  %s" % (tag, m.shape[0], "  ".join(cells))
+        return "%s_%s: n=%d  %s" % (name, tag, m.shape[0], "  ".join(cells))
+
+    # ---- forecast summaries: the same functionals from a time on, on any output grid -------------------------------------------------------
+    @staticmethod
+    def _first_point(times_out, since) -> int:
+        """The first index of ``times_out`` whose time has reached ``since``, in the grid's own direction (an increasing grid: t >= since; a
+        decreasing one: t <= since); None: 0.  Found on the host.  ValueError where no point of the grid has reached it."""
+        if since is None:
+            return 0
+        t = torch.as_tensor(times_out).detach().to("cpu", torch.float32).reshape(-1)
+        s = torch.tensor(float(since), dtype=torch.float32)
+        reached = (t >= s) if bool(t[-1] >= t[0]) else (t <= s)
+        idx = torch.nonzero(reached)
+        if idx.numel() == 0:
+            raise ValueError("since = %r lies beyond the output grid [%r, %r]" % (float(since), float(t[0]), float(t[-1])))
+        return int(idx[0])
+
+    def forecast_summary(self, observations, is_post, num_samples: int, times_out, since=None, thresholds=None, sense="above", eps=None,
+                         window: int = 0, **labels):
+        """Will the curve cross the level after the observed window, when, how high will it still get and how much is still to come: the
+        functionals of ``curve_summary`` over ``num_samples`` latent draws, taken on the part of ``times_out`` from the time ``since`` on
+        (None: the whole grid).  ``times_out`` is any grid ``forecast_moments`` takes (``horizon_times(n)``, finer, longer than 1024 points).
+        Returns per head curve name a dict of ``(mean, sd)`` pairs, ``[B, C]`` each, under the eight names of ``curve_summary`` -- the area
+        and ``time_beyond`` by the trapezoid rule on the sub-grid, ``t_hit`` over the draws that cross at or after ``since`` (a draw already
+        beyond the level there hits there; NaN where none crosses) -- plus ``"first_point"``, the index of the first grid point used: the
+        first whose time has reached ``since``, in the grid's own direction.  That index is found on the host: a device-resident
+        ``times_out`` synchronises there, as ``cohort_index`` does; a ``since`` beyond the grid is a ValueError.  The moments of
+        ``forecast_moments`` do not yield these: the peak of the mean forecast is not the mean of the peaks.  ``thresholds`` / ``sense`` /
+        ``eps``: as ``curve_summary``.  ONE engine call (``slode_forecast_summary``), which walks the grid in windows of ``window`` steps (0:
+        the library's choice) and keeps nothing sized by ``num_samples`` or by the grid.  Where the engine refuses (adaptive solver, strided
+        observations, measured arms) the same dict is composed from ``forecast_samples`` in chunks over B (T_out <= 1024), the functionals
+        in torch on ``times_out[first_point:]``."""
+        b = self._bind()
+        B, ns, sn = observations.shape[0], self._count(num_samples), self._summary_sense(sense)
+        thr = None if thresholds is None else [float(x) for x in torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1).tolist()]
+        if thr is not None and len(thr) != observations.shape[1]:
+            raise ValueError("thresholds must hold %d values (one per channel), got %d" % (observations.shape[1], len(thr)))
+        t = self._forecast_times(times_out)
+        i0 = self._first_point(t, since)
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+
+        def pack(mean, sd):
+            return {n: dict({k: (mean[q][..., j], sd[q][..., j]) for j, k in enumerate(self.SUMMARY_NAMES)}, first_point=i0)
+                    for q, n in enumerate(names)}
+
+        def fused():
+            return pack(*b.engine.forecast_summary(b.flat, self._draws_batch(observations, labels, eps, ns), B, is_post, ns, t, first_point=i0,
+                                                   thr=thr, sense=sn, mean=None, sd=True, window=window))
+
+        def composed():
+            sub = torch.as_tensor(t, dtype=torch.float32).reshape(-1)[i0:]
+            cols = {n: ([], []) for n in names}
+            for lo, hi, e, d in self._chunks(observations, labels, ns, eps):
+                res = self.forecast_samples(is_post=is_post, num_samples=ns, times_out=t, eps=e, **d)
+                for n in names:
+                    f, _ = self._summary_functionals(res[n][:, :, i0:], thr, sn, grid=sub)
+                    m, s = self._summary_moments(f)
+                    cols[n][0].append(m); cols[n][1].append(s)
+                del res
+            return pack([torch.cat(cols[n][0], 0) for n in names], [torch.cat(cols[n][1], 0) for n in names])
+        return self._fused_or_composed(fused, composed)
+
+    def save_forecast_summary(self, results_dir: str, batches, is_post, num_samples: int, times_out, since=None, thresholds=None, sense="above"):
+        """Runs ``forecast_summary`` over ``batches`` (an iterable of device batch dicts: ``observations`` + the label tensors) and writes
+        ``summary_<curve>_<post|prior>_forecast_mean.npy`` / ``..._forecast_sd.npy``, float32 ``[n, C, 8]`` (the trajectories in loader
+        order, the slots in ``SUMMARY_NAMES`` order), and ``forecast_times.npy`` (``[T_out]``).  One read-back, at the end.  Returns the
+        paths."""
+        import numpy as np
+        names = self.MOMENT_HEADS[bool(self.GAUSS)]
+        tag = "post" if is_post else "prior"
+        tt = (times_out if torch.is_tensor(times_out) else torch.as_tensor(times_out, dtype=torch.float32)).detach().to(torch.float32).reshape(-1)
+        return self._save_over_batches(
+            results_dir, batches,
+            lambda **d: self.forecast_summary(is_post=is_post, num_samples=num_samples, times_out=times_out, since=since, thresholds=thresholds,
+                                              sense=sense, **d),
+            lambda r: (("summary_%s_%s_forecast_%s.npy" % (n, tag, ("mean", "sd")[k]), torch.stack([r[n][slot][k] for slot in self.SUMMARY_NAMES], -1))
+                       for n in names for k in (0, 1)),
+            side=("forecast_times.npy", lambda path, _: np.save(path, tt.cpu().numpy())))
 
     # ---- counterfactual summaries: peak, AUC and crossing of THIS subject's curves under V hypothesised inputs, with the paired effects ----
     INTERVENTION_SUMMARY_ARMS_PER_CALL = None     # most hypotheses of one engine call; None: what the engine's plan says fits the LDS (at most 64)

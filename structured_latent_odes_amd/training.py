@@ -115,7 +115,7 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
           label_evidence: int = 0, refine_steps: int = 0, refine_draws: int = 8, waic: int = 0, attribution: int = 0,
           curve_summary: int = 0, summary_thresholds=None, summary_sense: str = "above", sample_quantiles: int = 0,
           quantile_levels=(0.025, 0.975), mechanism: int = 0, joint_band: int = 0, band_levels=(0.95,), loo: int = 0,
-          intervention_summary: int = 0):
+          intervention_summary: int = 0, forecast_summary: int = 0):
     """fused_stats: the four statistics passes of every epoch run through ``input_pred_stats_fused`` (one engine call per batch, one
     read-back per pass) instead of ``input_pred_stats``.  The final test passes score two models at once (the losses stay bound to
     var_model while recon / label prediction run on best_model, as in the reference) and keep the unfused form.
@@ -175,7 +175,14 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
     posterior draws on ``default_hypotheses`` (``save_intervention_summary``: ``summary_<curve>_{factual,cf,effect}_{mean,sd}.npy``,
     ``summary_hypotheses_<label>.npy``), with ``summary_thresholds`` / ``summary_sense`` as for ``curve_summary``, and one printed line per
     hypothesis (``intervention_summary: ...``: per channel of the central curve, the mean paired effect on the peak and on the AUC and, with
-    thresholds, the change of P(cross)); 0 (the default): no such stage runs."""
+    thresholds, the change of P(cross)); 0 (the default): no such stage runs.
+    forecast_summary = K > 0 (needs ``forecast_steps`` = N > 0): after training, the best model's forecast summaries over the validation
+    loader from K posterior draws on ``horizon_times(N)``, taken from the model's last training time on (``save_forecast_summary``:
+    ``summary_<curve>_post_forecast_{mean,sd}.npy`` [n, C, 8], ``forecast_times.npy``), with ``summary_thresholds`` / ``summary_sense`` as
+    for ``curve_summary``, and one printed line per head curve (``forecast_summary_<curve>: ...``: per channel, the mean future peak and,
+    with thresholds, P(cross) and the mean t_hit over the subjects with a crossing draw); 0 (the default): no such stage runs."""
+    if forecast_summary and not forecast_steps:
+        raise ValueError("forecast_summary needs forecast_steps > 0 (the horizon to summarise)")
     set_seed(config.seed)
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if times is not None:
@@ -339,6 +346,17 @@ def train(config, family: str, model_cls, model_cls_gauss, batches_per_epoch: in
                     parts.setdefault("%s_post_forecast_%s.npy" % (name, kind), []).append(val)
         written = best_model._save_arrays(out_dir, [(f, torch.cat(v, 0)) for f, v in parts.items()] + [("forecast_times.npy", t_out)])
         logging.debug("forecast moments: %s", written)
+    if forecast_summary:
+        t_out = best_model.horizon_times(int(forecast_steps))
+        since = float(torch.as_tensor(best_model.times, dtype=torch.float32).reshape(-1)[-1])
+        written = best_model.save_forecast_summary(out_dir, (batch_to_device(b, device, family) for b in val_b), True, int(forecast_summary), t_out,
+                                                   since=since, thresholds=summary_thresholds, sense=summary_sense)
+        for n in best_model.MOMENT_HEADS[bool(best_model.GAUSS)]:
+            line = best_model.summary_line(np.load([f for f in written if f.endswith("summary_%s_post_forecast_mean.npy" % n)][0]), n,
+                                           summary_thresholds is not None, name="forecast_summary")
+            print(line)
+            logging.debug("%s", line)
+        logging.debug("forecast summary: %s", written)
     return var_model, best_model, best_epoch
 
 
@@ -446,6 +464,11 @@ def build_parser():
     ap.add_argument("--forecast-steps", type=int, default=0, metavar="N",
                     help="after training: the best model's posterior curves over the validation loader on the training grid extended by N steps, mean "
                          "and sd of config.num_samples draws (forecast_moments: <curve>_post_forecast_{mean,sd}.npy, forecast_times.npy)")
+    ap.add_argument("--forecast-summary", type=int, default=0, metavar="K",
+                    help="after training (needs --forecast-steps N > 0): the best model's forecast summaries over the validation loader from K "
+                         "posterior draws on the extended grid, taken from the last training time on (save_forecast_summary: "
+                         "summary_<curve>_post_forecast_{mean,sd}.npy) -- per channel of every head curve, the mean future peak and, with "
+                         "--summary-thresholds / --summary-sense, P(cross) and the mean first crossing time, one line per curve")
     ap.add_argument("--cohort-curves", action="store_true",
                     help="after training: per-condition mean / sd curves, mean observations and the evaluation notebooks' l1_error on the first "
                          "test batch, posterior and prior (save_cohort_moments)")
@@ -456,7 +479,10 @@ def build_parser():
 
 
 def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.forecast_summary and a.forecast_steps <= 0:
+        ap.error("--forecast-summary needs --forecast-steps N > 0 (the horizon to summarise)")
     config = load_config()
     config.num_epochs = a.epochs
     os.makedirs("results_%s" % config.model, exist_ok=True)
@@ -488,6 +514,8 @@ def main(family: str, load_config, model_cls, model_cls_gauss, argv=None):
         kw["joint_band"], kw["band_levels"] = a.joint_band, a.band_levels
     if a.forecast_steps:
         kw["forecast_steps"] = a.forecast_steps
+    if a.forecast_summary:
+        kw["forecast_summary"], kw["summary_thresholds"], kw["summary_sense"] = a.forecast_summary, a.summary_thresholds, a.summary_sense
     if a.cohort_curves:
         kw["cohort_curves"] = True
     if a.calibration:
